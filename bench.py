@@ -6,8 +6,15 @@ A "step" is one full frame: render_init + render over every pixel (src/main.cu:9
 inputs (the flattened scene) already resident in HBM.  A ray is one world->hit call from
 color() (main.cu:57), counted on the device.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (with the roofline object, which reads a committed
+PMC record and takes no run of its own).  --full adds what needs runs of its own: the CPU baseline (the oracle timed on
+the host cores; --no-cpu-baseline leaves it out).  --dump-outputs DIR writes what the last timed step computed, as .npy:
+frame.npy (float32 [ny][nx][3], row 0 = bottom, on rank 0 the whole frame) and rays.npy (float64 [1], rays of that frame).
+A frame above 48 MB is written as a fixed, seeded sample of its pixels instead (frame_sample.npy [n][3] and
+frame_sample_index.npy, the flat pixel indices row * nx + column).
 
 N > 1: one process per GPU; the frame is cut into 4-row tiles dealt round-robin to the
 ranks (no cross-GPU rays, the per-pixel seed is global so pixels are identical to the
@@ -183,10 +190,35 @@ def parse():
     ap.add_argument("--ns", type=int, default=500)
     ap.add_argument("--kernel", type=int, default=None, help="0 = pixel, 1 = persistent, 2 = parked, 3 = staged (default)")
     ap.add_argument("--opt", action="append", default=[], help="rt_set_option key=value (A/B knobs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own (the CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-ns", type=int, default=48, help="spp of the bounded CPU-baseline sample (48 spp of the headline frame = ~1e8 rays, tens of core-seconds)")
     ap.add_argument("--save-ppm", default=None, help="write the last frame as ASCII PPM (rank 0)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's frame and ray count as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 48 << 20   # stay well under 64 MB for all files together
+DUMP_SAMPLE_SEED = 1984
+
+
+def dump_outputs(out_dir: str, frame: np.ndarray, rays: float) -> None:
+    """What a caller of the render path receives for the last timed step: the frame and its ray count.  A frame larger
+    than DUMP_MAX_BYTES is written as a fixed, seeded sample of its pixels (same pixels for the same nx, ny)."""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+    else:
+        ny, nx = frame.shape[:2]
+        n = DUMP_MAX_BYTES // (3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(ny * nx, size=n, replace=False))
+        np.save(os.path.join(out_dir, "frame_sample.npy"), frame.reshape(-1, 3)[idx])
+        np.save(os.path.join(out_dir, "frame_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "rays.npy"), np.array([rays], dtype=np.float64))
 
 
 def host_cores() -> int:
@@ -355,11 +387,15 @@ def main():
         }
         if per_rank is not None:
             line["multi_gpu"] = multi_gpu_report(per_rank, ms_per_step, args, world)
-        if world == 1 and not args.no_cpu_baseline:
+        out = None
+        if args.dump_outputs or args.save_ppm:
+            out = (full if world > 1 else local[: args.ny]).cpu().numpy()   # the last timed step's frame
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, total_rays)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.scene, args.nx, args.ny, args.cpu_ns)
         print(json.dumps(line), flush=True)
         if args.save_ppm:
-            out = (full if world > 1 else local[: args.ny]).cpu().numpy()
             art.write_ppm(args.save_ppm, out, hs.ppm_double_scale)
     ds.close()
     if world > 1:
