@@ -15,6 +15,7 @@ name); import it through the ``accelerated_ray_tracer_amd`` symlink.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -64,9 +65,36 @@ class RtStats(C.Structure):
                 ("lds_bytes", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RtRayBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("origins", C.c_void_p), ("directions", C.c_void_p), ("times", C.c_void_p), ("tmax", C.c_void_p),
+                ("tmin", C.c_float), ("mode", C.c_int32),
+                ("t_out", C.c_void_p), ("prim_out", C.c_void_p), ("inst_out", C.c_void_p), ("point_out", C.c_void_p),
+                ("normal_out", C.c_void_p), ("uv_out", C.c_void_p), ("mat_out", C.c_void_p), ("hit_out", C.c_void_p)]
+
+
+RT_TRACE_CLOSEST, RT_TRACE_ANY = 0, 1
+RT_PRIM_SPHERE, RT_PRIM_QUAD, RT_PRIM_BOX, RT_PRIM_INSTANCE, RT_PRIM_MEDIUM = range(5)
+
+
+def prim_kind(ref):
+    """Kind of an RT_PRIM_REF (scalar or integer array); -1 refs (misses) give 15."""
+    return (np.asarray(ref).astype(np.int64) & 0xFFFFFFFF) >> 28
+
+
+def prim_index(ref):
+    return np.asarray(ref).astype(np.int64) & 0x0FFFFFFF
+
+
+# DeviceScene.trace(): closest hit -- the record fields are None unless record=True
+TraceResult = collections.namedtuple("TraceResult", "t prim inst point normal uv mat")
+
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("skip", "<i4"), ("bmax", "<f4", 3), ("prim", "<i4")])
 SPHERE_DTYPE = np.dtype([("c0", "<f4", 3), ("radius", "<f4"), ("vel", "<f4", 3), ("mat", "<i4")])
 MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("tex", "<i4"), ("fuzz", "<f4"), ("ior", "<f4"), ("albedo", "<f4", 3), ("pad", "<f4")])
+QUAD_DTYPE = np.dtype([("Q", "<f4", 3), ("D", "<f4"), ("u", "<f4", 3), ("mat", "<i4"), ("v", "<f4", 3), ("pad0", "<f4"),
+                       ("w", "<f4", 3), ("pad1", "<f4"), ("n", "<f4", 3), ("pad2", "<f4")])
+INSTANCE_DTYPE = np.dtype([("sin_t", "<f4"), ("cos_t", "<f4"), ("offset", "<f4", 3), ("child", "<i4"), ("flags", "<i4"), ("pad", "<i4")])
+MEDIUM_DTYPE = np.dtype([("boundary", "<i4"), ("neg_inv_density", "<f4"), ("mat", "<i4"), ("pad", "<i4")])
 
 # every symbol include/rt_abi.h declares
 RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", "rt_last_error_detail", "rt_scene_create",
@@ -74,7 +102,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_set_option", "rt_reset_options", "rt_scene_walk_info", "rt_init_devices", "rt_multi_create", "rt_multi_render",
                   "rt_multi_destroy", "rt_multi_device_count", "rt_multi_row_owner", "rt_multi_probe_rccl", "rt_multi_debug_uninterleave",
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
-                  "rt_plan_walk_array", "rt_regroup_leaves"]
+                  "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays"]
 
 _rt = None
 _host = None
@@ -146,6 +174,7 @@ def rt_lib():
                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rt_regroup_leaves.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.rt_regroup_leaves.restype = C.c_int
+        L.rt_trace_rays.argtypes = [C.c_void_p, C.POINTER(RtRayBatch), C.c_void_p, C.c_int]
         L.rt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _rt = L
     return _rt
@@ -216,6 +245,21 @@ class HostScene:
         buf = (C.c_char * (n * MATERIAL_DTYPE.itemsize)).from_address(self.desc.materials)
         return np.frombuffer(buf, MATERIAL_DTYPE, n).copy()
 
+    def _array(self, ptr, n, dtype) -> np.ndarray:
+        if n == 0:
+            return np.zeros(0, dtype)
+        buf = (C.c_char * (n * dtype.itemsize)).from_address(ptr)
+        return np.frombuffer(buf, dtype, n).copy()
+
+    def quads(self) -> np.ndarray:
+        return self._array(self.desc.quads, self.desc.n_quads, QUAD_DTYPE)
+
+    def instances(self) -> np.ndarray:
+        return self._array(self.desc.instances, self.desc.n_instances, INSTANCE_DTYPE)
+
+    def media(self) -> np.ndarray:
+        return self._array(self.desc.media, self.desc.n_media, MEDIUM_DTYPE)
+
     def leaf_order(self) -> np.ndarray:
         L = host_lib()
         n = self.desc.n_nodes
@@ -274,6 +318,7 @@ class DeviceScene:
         if _initialised_device is None:
             init(0)
         self.host = host_scene
+        self.device = _initialised_device
         self._p = C.c_void_p()
         _check(rt_lib().rt_scene_create(C.byref(host_scene.desc), C.byref(self._p)), "rt_scene_create")
 
@@ -292,6 +337,95 @@ class DeviceScene:
             return out, stats
         _check(L.rt_render(self._p, C.byref(frame), C.c_void_p(int(out)), 1, stream, 1 if blocking else 0, C.byref(stats)), "rt_render")
         return None, stats
+
+    def trace(self, origins, directions, times=None, tmin: float = 0.001, tmax=None, any_hit: bool = False, record: bool = False,
+              stream=None):
+        """Batched ray queries (rt_trace_rays): the closest hit -- or, with any_hit, whether anything is hit -- of every ray
+        in its window (tmin, tmax), applied by each object as the reference's hit function applies it (include/rt_abi.h).
+
+        origins, directions: (N, 3) float32; times, tmax: (N,) float32 or None (0 / FLT_MAX for every ray).  Either all
+        torch tensors on this scene's device -- used in place (made contiguous if they are not), outputs are tensors on the
+        device, the work is enqueued on `stream` (a torch.cuda.Stream; default: the current stream) and the call does not
+        wait; a `stream` other than the current one first waits for the current stream's work, and the caller orders any
+        later use of the outputs after `stream` -- or all numpy arrays -- copied to the device through torch, outputs are numpy arrays and the call waits.
+        Returns a TraceResult (t: FLT_MAX on a miss, prim: RT_PRIM_REF or -1, inst: instance index or -1; point, normal,
+        uv, mat only with record=True, zeros and mat = -1 on a miss), or with any_hit a bool array (record must then be False).  Malformed input raises
+        ValueError before anything is launched."""
+        import torch
+        on_host = isinstance(origins, np.ndarray)
+        dev = torch.device("cuda", self.device)
+
+        def prep(x, name, cols):
+            if x is None:
+                return None
+            if on_host:
+                if not isinstance(x, np.ndarray):
+                    raise ValueError(f"{name}: a numpy array is expected (origins is one)")
+                if x.dtype != np.float32:
+                    raise ValueError(f"{name}: float32 expected, got {x.dtype}")
+            else:
+                if not isinstance(x, torch.Tensor):
+                    raise ValueError(f"{name}: a torch tensor is expected (origins is one)")
+                if x.dtype != torch.float32:
+                    raise ValueError(f"{name}: float32 expected, got {x.dtype}")
+                if x.device != dev:
+                    raise ValueError(f"{name}: tensor on {x.device}, the scene is on {dev}")
+            want = (n, 3) if cols == 3 else (n,)
+            if tuple(x.shape) != want:
+                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {want}")
+            return x
+
+        if any_hit and record:
+            raise ValueError("any_hit returns hit flags only: record=True needs a closest-hit query")
+        if not on_host and not isinstance(origins, torch.Tensor):
+            raise ValueError("origins: a numpy array or a torch tensor is expected")
+        if origins.ndim != 2 or origins.shape[1] != 3:
+            raise ValueError(f"origins: shape {tuple(origins.shape)}, expected (N, 3)")
+        n = int(origins.shape[0])
+        if directions is None:
+            raise ValueError("directions are required")
+        if not np.isfinite(tmin):
+            raise ValueError("tmin must be finite")
+        ins = [prep(origins, "origins", 3), prep(directions, "directions", 3), prep(times, "times", 1), prep(tmax, "tmax", 1)]
+        ins = [None if x is None else (torch.from_numpy(np.ascontiguousarray(x)).to(dev) if on_host else x.contiguous()) for x in ins]
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+
+        def empty(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if any_hit:
+            outs = {"hit_out": empty((n,), torch.uint8)}
+        else:
+            outs = {"t_out": empty((n,), torch.float32), "prim_out": empty((n,), torch.int32), "inst_out": empty((n,), torch.int32)}
+            if record:
+                outs.update(point_out=empty((n, 3), torch.float32), normal_out=empty((n, 3), torch.float32),
+                            uv_out=empty((n, 2), torch.float32), mat_out=empty((n,), torch.int32))
+        if n > 0:
+            b = RtRayBatch()
+            b.n = n
+            b.origins, b.directions, b.times, b.tmax = (None if x is None else x.data_ptr() for x in ins)
+            b.tmin = float(tmin)
+            b.mode = RT_TRACE_ANY if any_hit else RT_TRACE_CLOSEST
+            for k, v in outs.items():
+                setattr(b, k, v.data_ptr())
+            current = torch.cuda.current_stream(dev)
+            if stream != current:
+                # The inputs' contiguous copies and the outputs were made on the current stream: `stream` waits for that
+                # work (and for whatever last used the outputs' blocks there) before the trace writes, and the caching
+                # allocator must not hand any of them out again before `stream` is done with them.
+                stream.wait_stream(current)
+                for x in ins + list(outs.values()):
+                    if x is not None:
+                        x.record_stream(stream)
+            _check(rt_lib().rt_trace_rays(self._p, C.byref(b), C.c_void_p(stream.cuda_stream), 0), "rt_trace_rays")
+        if on_host:
+            stream.synchronize()
+            outs = {k: v.cpu().numpy() for k, v in outs.items()}
+        if any_hit:
+            h = outs["hit_out"]
+            return h.view(np.bool_) if on_host else h.view(torch.bool)
+        return TraceResult(outs["t_out"], outs["prim_out"], outs["inst_out"], outs.get("point_out"), outs.get("normal_out"),
+                           outs.get("uv_out"), outs.get("mat_out"))
 
     def progressive(self, frame: RtFrameDesc) -> "ProgressiveFrame":
         """Progressive accumulation of `frame` (rt_render_window): windows of samples, a displayable frame after each."""

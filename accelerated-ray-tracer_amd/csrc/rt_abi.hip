@@ -85,6 +85,8 @@ struct rt_options {
     int scan_nodes = 24;         // scenes whose walk array has at most this many nodes are scanned in lockstep (lds_mode 4); 0 = never
     int multi_force_rccl = 0;    // rt_multi_render: go through the RCCL gather even with one device (tests the path on a one-GPU box)
     int lpt = 1;                 // cost prepass + longest-first tile order (staged kernel, ns >= 2 * split_samples)
+    int trace_lds = -1;          // rt_trace_rays: -1 = auto, 0 = scene through L1/L2, 1 = nodes in LDS, 2 = nodes and spheres in LDS
+    int trace_tree = 1;          // rt_trace_rays: 1 = the walk array, 0 = the reference's full tree
 };
 rt_options g_opt;
 
@@ -645,6 +647,8 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "lds_mode") { if (value < -1 || value > 4) return invalid("lds_mode: -1..4"); g_opt.lds_mode = value; }
     else if (k == "steps_per_trip") { if (value < 1 || value > 64) return invalid("steps_per_trip: 1..64"); g_opt.steps_per_trip = value; }
     else if (k == "shade_threshold") { if (value < 0 || value > 64) return invalid("shade_threshold: 0 (by the launch's load) or 1..64"); g_opt.shade_threshold = value; }
+    else if (k == "trace_lds") { if (value < -1 || value > 2) return invalid("trace_lds: -1 (auto) .. 2"); g_opt.trace_lds = value; }
+    else if (k == "trace_tree") { if (value < 0 || value > 1) return invalid("trace_tree: 0 (reference tree) or 1 (walk array)"); g_opt.trace_tree = value; }
     else if (k == "wg_per_cu") { if (value < 0 || value > 8) return invalid("wg_per_cu: 0 (per kernel family) .. 8"); g_opt.wg_per_cu = value; }
     else return invalid("unknown option");
     return RT_OK;
@@ -1138,6 +1142,113 @@ rt_status rt_frame_finish(rt_scene* s, rt_stats* stats) {
     }
     s->frame_pending = false;
     if (stats) *stats = s->pending_stats;
+    return RT_OK;
+}
+
+namespace {
+// a pointer rt_trace_rays hands to a kernel: null, or `bytes` of device (or managed) memory of `device`, 4-byte aligned
+static rt_status check_trace_ptr(const void* p, size_t bytes, int device, const char* what) {
+    if (!p) return RT_OK;
+    std::string why;
+    if (reinterpret_cast<uintptr_t>(p) & 3u) { why = std::string("rt_trace_rays: ") + what + " is not 4-byte aligned"; return invalid(why.c_str()); }
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        why = std::string("rt_trace_rays: ") + what + " is not device memory (unregistered pointer)";
+        return invalid(why.c_str());
+    }
+    if (a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged) {
+        why = std::string("rt_trace_rays: ") + what + " is not device memory";
+        return invalid(why.c_str());
+    }
+    if (a.type == hipMemoryTypeDevice && a.device != device) {
+        why = std::string("rt_trace_rays: ") + what + " is memory of another device";
+        return invalid(why.c_str());
+    }
+    void* base = nullptr;
+    size_t size = 0;
+    if (a.type == hipMemoryTypeDevice && hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) == hipSuccess) {
+        if (static_cast<const char*>(p) + bytes > static_cast<const char*>(base) + size) {
+            why = std::string("rt_trace_rays: ") + what + " is shorter than the batch";
+            return invalid(why.c_str());
+        }
+    } else {
+        (void)hipGetLastError();
+    }
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_trace_rays(rt_scene* s, const rt_ray_batch* b, void* stream_v, int blocking) {
+    // argument checks: no HIP call and no look at the scene before they pass
+    if (!b) return invalid("rt_trace_rays: null batch");
+    if (b->n < 0) return invalid("rt_trace_rays: negative ray count");
+    if (!std::isfinite(b->tmin)) return invalid("rt_trace_rays: tmin is not finite");
+    if (b->mode != RT_TRACE_CLOSEST && b->mode != RT_TRACE_ANY) return invalid("rt_trace_rays: unknown mode");
+    if (!b->origins || !b->directions) return invalid("rt_trace_rays: null origins or directions");
+    const bool record = b->point_out || b->normal_out || b->uv_out || b->mat_out;
+    if (b->mode == RT_TRACE_ANY) {
+        if (b->t_out || b->prim_out || b->inst_out || record) return invalid("rt_trace_rays: ANY mode takes hit_out only");
+        if (!b->hit_out) return invalid("rt_trace_rays: ANY mode needs hit_out");
+    } else {
+        if (b->hit_out) return invalid("rt_trace_rays: CLOSEST mode does not take hit_out");
+        if (!b->t_out || !b->prim_out) return invalid("rt_trace_rays: CLOSEST mode needs t_out and prim_out");
+    }
+    if (!s) return invalid("rt_trace_rays: null scene");
+    if (b->n == 0) return RT_OK;
+    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    const size_t n = (size_t)b->n, f = sizeof(float), i = sizeof(int32_t);
+    const struct { const void* p; size_t bytes; const char* what; } ptrs[] = {
+        {b->origins, 3 * n * f, "origins"}, {b->directions, 3 * n * f, "directions"}, {b->times, n * f, "times"}, {b->tmax, n * f, "tmax"},
+        {b->t_out, n * f, "t_out"}, {b->prim_out, n * i, "prim_out"}, {b->inst_out, n * i, "inst_out"}, {b->point_out, 3 * n * f, "point_out"},
+        {b->normal_out, 3 * n * f, "normal_out"}, {b->uv_out, 2 * n * f, "uv_out"}, {b->mat_out, n * i, "mat_out"}, {b->hit_out, n, "hit_out"}};
+    for (const auto& q : ptrs) {
+        const rt_status st = check_trace_ptr(q.p, q.bytes, s->device, q.what);
+        if (st != RT_OK) return st;
+    }
+
+    rt_trace_params tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.n = b->n; tp.origins = b->origins; tp.directions = b->directions; tp.times = b->times; tp.tmax = b->tmax; tp.tmin = b->tmin;
+    tp.record = record ? 1 : 0;
+    tp.t_out = b->t_out; tp.prim_out = b->prim_out; tp.inst_out = b->inst_out;
+    tp.point_out = b->point_out; tp.normal_out = b->normal_out; tp.uv_out = b->uv_out; tp.mat_out = b->mat_out;
+    tp.hit_out = b->hit_out;
+
+    // the node array: the walk array (the render's) or the reference's full tree; both carry the same leaves
+    rt_scene_dev sd = s->dev;
+    if (g_opt.trace_tree == 0) { sd.nodes = sd.nodes_ref; sd.n_nodes = sd.n_nodes_ref; }
+    const size_t node_bytes = (size_t)sd.n_nodes * sizeof(rt_node);
+    // LDS residency: the modes whose image fits a CU (nodes + spheres, nodes only, none); a forced mode that does not fit
+    // falls back to the largest that does.  Auto takes the largest mode that keeps at least 3/4 of the workgroups per CU
+    // that mode 0 gets: the walk is latency-bound, and an image that costs residency costs more than it saves -- one
+    // workgroup per CU for the Book-2 final scene's nodes ran at 0.6 instead of 1.4 Grays/s; the headline scene's nodes (7 of
+    // 8 workgroups) were 1-8 % faster than mode 0 (profiles/trace_bench_mi355x.jsonl)
+    const size_t budget = g_devices[s->device].lds_per_cu - 2048;
+    const int fit = node_bytes + s->sphere_bytes <= budget ? 2 : (node_bytes <= budget ? 1 : 0);
+    auto lds_of = [&](int m) -> size_t { return m == 2 ? node_bytes + s->sphere_bytes : (m == 1 ? node_bytes : 0); };
+    const bool any = b->mode == RT_TRACE_ANY;
+    int lds_mode = g_opt.trace_lds < 0 ? fit : std::min(g_opt.trace_lds, fit);
+    int per_cu = 0;
+    HIPCHK(rt_trace_occupancy(s->spheres_only, lds_mode, any, record, lds_of(lds_mode), &per_cu));
+    if (g_opt.trace_lds < 0 && lds_mode > 0) {
+        int per_cu0 = 0;
+        HIPCHK(rt_trace_occupancy(s->spheres_only, 0, any, record, 0, &per_cu0));
+        while (lds_mode > 0 && 4 * per_cu < 3 * per_cu0) {
+            --lds_mode;
+            HIPCHK(rt_trace_occupancy(s->spheres_only, lds_mode, any, record, lds_of(lds_mode), &per_cu));
+        }
+    }
+    const size_t lds = lds_of(lds_mode);
+    // persistent grid: as many workgroups as are resident at once (registers and LDS), never more than the batch needs
+    if (per_cu < 1) per_cu = 1;
+    const long long want = (long long)g_devices[s->device].num_cu * per_cu;
+    const long long need = (b->n + RT_TRACE_THREADS - 1) / RT_TRACE_THREADS;
+    const dim3 grid((unsigned)std::min(want, need));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    HIPCHK(rt_launch_trace(s->spheres_only, lds_mode, sd, tp, grid, lds, stream));
+    if (blocking) HIPCHK(hipStreamSynchronize(stream));
     return RT_OK;
 }
 

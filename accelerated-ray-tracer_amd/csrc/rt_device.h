@@ -216,3 +216,29 @@ hipError_t rt_launch_staged_general_tex(int lds_mode, const rt_scene_dev& sd, co
 // the tier kernel of a ranked launch (rt_tier_*.hip); *vgprs_out (optional) = the instantiation's register count
 hipError_t rt_launch_tier_spheres(int tex_level, const rt_scene_dev& sd, const rt_frame_params& fp, dim3 grid, size_t lds, hipStream_t st);
 hipError_t rt_launch_tier_general(int tex_level, bool need_uv, const rt_scene_dev& sd, const rt_frame_params& fp, dim3 grid, size_t lds, hipStream_t st);
+
+// rt_trace_rays (rt_kernel_trace.hip): one batch of caller rays, the pointers already checked on the host (rt_abi.hip)
+struct rt_trace_params {
+    int64_t n;
+    const float* origins;
+    const float* directions;
+    const float* times;       // null = 0
+    const float* tmax;        // null = FLT_MAX
+    float tmin;
+    int32_t record;           // some record output (point / normal / uv / mat) is requested
+    float* t_out;
+    int32_t* prim_out;
+    int32_t* inst_out;
+    float* point_out;
+    float* normal_out;
+    float* uv_out;
+    int32_t* mat_out;
+    uint8_t* hit_out;         // non-null: any-hit mode
+};
+// sd.nodes / sd.n_nodes: the node array to walk (the walk array or the reference's tree); lds_mode 0..2 as stage_scene;
+// grid = persistent workgroups of RT_TRACE_THREADS.  rt_trace_occupancy: workgroups per CU of the instantiation a launch
+// with these arguments would use, `lds` bytes of dynamic LDS each.
+#define RT_TRACE_THREADS 256
+hipError_t rt_launch_trace(bool spheres_only, int lds_mode, const rt_scene_dev& sd, const rt_trace_params& tp, dim3 grid, size_t lds,
+                           hipStream_t st);
+hipError_t rt_trace_occupancy(bool spheres_only, int lds_mode, bool any, bool record, size_t lds, int* blocks_per_cu);

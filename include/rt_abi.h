@@ -229,6 +229,53 @@ rt_status rt_render(rt_scene* scene, const rt_frame_desc* f, float* fb, int fb_o
                     void* stream, int blocking, rt_stats* stats);
 rt_status rt_frame_finish(rt_scene* scene, rt_stats* stats);
 
+/* ---- batched ray queries against a scene resident on the device ----
+ * The render kernels' BVH walk and leaf tests (the reference's bvh_node::hit, bvh.cuh:95-106, and its objects' hit
+ * functions), asked for caller-supplied rays.  For a ray with the default window (tmin = 0.001f, tmax null) the closest t
+ * is bit-identical to what the reference's world->hit returns for it (main.cu:57), media included: constant_medium draws
+ * its uniform from a hash of the ray, so its result is a function of the ray alone.
+ *
+ * Pointers: every pointer in the batch is device (or managed) memory of the scene's device, 4-byte aligned.  Each
+ * non-null one is checked with hipPointerGetAttributes before anything is launched; a host pointer, an unregistered
+ * pointer or one on another device is RT_ERR_INVALID.
+ * Arguments: a null scene or batch, n < 0, a non-finite tmin, an unknown mode or a wrong set of outputs for the mode is
+ * RT_ERR_INVALID; these checks run before any HIP call and before the scene is looked at, and rt_last_error_detail()
+ * names the one that failed.
+ * Window: each object applies (tmin, tmax) as the reference's hit function does: a sphere accepts tmin < t < tmax, a quad
+ * (and a box face) tmin <= t <= tmax, a medium clamps its interval to [tmin, tmax] (so may return t == tmax).  tmax is
+ * per ray (null = FLT_MAX); a ray whose tmax is NaN is a miss.
+ * Stream: the work is enqueued on `stream` (a hipStream_t, 0 = default stream), like rt_render; with `blocking` != 0 the
+ * call returns when every output is written.
+ * Shared state: none.  The call reads only the scene's immutable device arrays and the process options; it touches none
+ * of the per-frame resources of rt_render (counters, events, the pending frame, the tier stream).  A trace may therefore
+ * run while a non-blocking rt_render of the same scene is still pending on another stream.  Options (rt_set_option):
+ * "trace_lds" -1 = auto (the largest LDS mode whose image still leaves at least 3/4 of the workgroups per CU that the
+ * scene-through-L1/L2 mode gets), 0 = scene through L1/L2, 1 = nodes in LDS, 2 = nodes and spheres in LDS (a forced mode
+ * that does not fit falls back to the largest that does); "trace_tree" 1 = the walk array, 0 = the reference's full tree.
+ * Neither changes a result. */
+enum { RT_TRACE_CLOSEST = 0, RT_TRACE_ANY = 1 };
+typedef struct rt_ray_batch {
+    int64_t n;                 /* rays; 0 is a no-op */
+    const float* origins;      /* n*3, required */
+    const float* directions;   /* n*3, required; not normalised (the reference never normalises) */
+    const float* times;        /* n, null = 0 for every ray (moving spheres; the camera's rays carry time0..time1) */
+    const float* tmax;         /* n, null = FLT_MAX for every ray; upper end of the window (see Window above) */
+    float tmin;                /* lower end of the window; the reference's is 0.001f (main.cu:57); must be finite */
+    int32_t mode;              /* RT_TRACE_CLOSEST or RT_TRACE_ANY */
+    /* CLOSEST: t_out and prim_out required, the rest optional (null = not written). */
+    float* t_out;              /* closest t, FLT_MAX on a miss */
+    int32_t* prim_out;         /* resolved leaf as RT_PRIM_REF: sphere, quad (a box face: its quad) or medium; -1 on a miss */
+    int32_t* inst_out;         /* instance index the hit went through, -1 if none or on a miss */
+    float* point_out;          /* n*3 hit_record p */
+    float* normal_out;         /* n*3 hit_record normal as the reference orients it (quad and rotate_y face the ray; medium (1,0,0)) */
+    float* uv_out;             /* n*2 hit_record u, v (sphere: get_sphere_uv of the object-space normal, sphere.cuh:42-49; medium 0, 0) */
+    int32_t* mat_out;          /* n material index */
+    /* ANY: hit_out only, required; every CLOSEST output must be null. */
+    uint8_t* hit_out;          /* 1 if some leaf is accepted in the window, else 0 */
+    /* A miss writes t = FLT_MAX, prim = inst = mat = -1 and zeros to point, normal and uv. */
+} rt_ray_batch;
+rt_status rt_trace_rays(rt_scene* scene, const rt_ray_batch* batch, void* stream, int blocking);
+
 /* ---- progressive accumulation (the reference writes every pixel's curandState back at the end of render(),
  * main.cu:126, which is what would allow it and what nothing in the reference uses) ----
  * rt_render_window renders samples [sample_begin, sample_end) of every pixel the frame description assigns to the call,

@@ -54,7 +54,7 @@ with ThreadPoolExecutor(max_workers=min(8, len(units))) as ex:
 pretty = demangle([r["name"] for r in rows])
 for r, p in zip(rows, pretty):
     p = re.sub(r"^void ", "", p)
-    p = re.sub(r"\((anonymous namespace)::", "", p)
+    p = p.replace("(anonymous namespace)::", "")
     p = re.sub(r"\(rt_scene_dev, rt_frame_params\)|\(rt_rank_params\)|\(.*\)$", "", p)
     r["short"] = p.replace("(anonymous namespace)::", "")
 kernels = [r for r in rows if "kernel" in r["short"]]
