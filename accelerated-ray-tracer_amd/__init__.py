@@ -350,7 +350,8 @@ class DeviceScene:
         later use of the outputs after `stream` -- or all numpy arrays -- copied to the device through torch, outputs are numpy arrays and the call waits.
         Returns a TraceResult (t: FLT_MAX on a miss, prim: RT_PRIM_REF or -1, inst: instance index or -1; point, normal,
         uv, mat only with record=True, zeros and mat = -1 on a miss), or with any_hit a bool array (record must then be False).  Malformed input raises
-        ValueError before anything is launched."""
+        ValueError before anything is launched.  A ray whose tmax is NaN, or with a NaN or infinite component in its origin,
+        direction or time, is a miss."""
         import torch
         on_host = isinstance(origins, np.ndarray)
         dev = torch.device("cuda", self.device)

@@ -73,8 +73,12 @@ __global__ void __launch_bounds__(RT_TRACE_THREADS) rt_trace_kernel(rt_scene_dev
         loose = inv_is_finite(inv) && loose_ok(inv, r.o, sd.bound);
         lr = loose_setup(inv, r.o, sd.bound);
         // a NaN tmax is a miss: sphere_test would reject every root under it, but quad_test's `t > tmax` and medium_test's
-        // clamp do not see a NaN, so the walk is not entered at all
-        node = best.t == best.t ? 0 : nn;
+        // clamp do not see a NaN, so the walk is not entered at all.  So is a ray with a non-finite origin, direction or
+        // time: quad_test and medium_test would accept a NaN t, and the box forms disagree on NaN (fminf / fmaxf drop it,
+        // the ternaries keep it), so the walk taken would decide the answer.
+        const bool finite = isfinite(r.o.x) && isfinite(r.o.y) && isfinite(r.o.z) && isfinite(r.d.x) && isfinite(r.d.y) &&
+                            isfinite(r.d.z) && isfinite(r.tm);
+        node = (finite && best.t == best.t) ? 0 : nn;
     };
     begin();
     while (__ballot(idx < n) != 0ull) {

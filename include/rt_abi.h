@@ -243,7 +243,8 @@ rt_status rt_frame_finish(rt_scene* scene, rt_stats* stats);
  * names the one that failed.
  * Window: each object applies (tmin, tmax) as the reference's hit function does: a sphere accepts tmin < t < tmax, a quad
  * (and a box face) tmin <= t <= tmax, a medium clamps its interval to [tmin, tmax] (so may return t == tmax).  tmax is
- * per ray (null = FLT_MAX); a ray whose tmax is NaN is a miss.
+ * per ray (null = FLT_MAX); a ray whose tmax is NaN is a miss.  So is a ray with a NaN or infinite component in its origin,
+ * direction or time: it is decided before the walk (the reference's quad and medium tests would accept a NaN t).
  * Stream: the work is enqueued on `stream` (a hipStream_t, 0 = default stream), like rt_render; with `blocking` != 0 the
  * call returns when every output is written.
  * Shared state: none.  The call reads only the scene's immutable device arrays and the process options; it touches none

@@ -107,6 +107,25 @@ class OracleScene:
             L.orc_node_stats_enable(self.h, 0)
         return p.astype(np.float64), cnt["rays"], cnt["box_tests"]
 
+    def trace(self, o, d, tm=None, tmin: float = 0.001, tmax=None, threads: int = 0):
+        """orc_trace_rays: obj_hit of the world for caller rays.  o, d: (N, 3) float32; tm, tmax: (N,) float32 or None (0 /
+        FLT_MAX).  Returns (t, p, n, uv, mat): t FLT_MAX and zero records on a miss; mat is the index of the hit's material
+        in the oracle's material list (not the product's numbering), -1 on a miss."""
+        L = lib()
+        L.orc_trace_rays.argtypes = [C.c_int, C.c_longlong] + [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 6 + [C.c_int]
+        o, d = (np.ascontiguousarray(x, np.float32).reshape(-1, 3) for x in (o, d))
+        n = len(o)
+        assert d.shape == (n, 3)
+        tm = None if tm is None else np.ascontiguousarray(tm, np.float32).reshape(n)
+        tmax = None if tmax is None else np.ascontiguousarray(tmax, np.float32).reshape(n)
+        t, p, nn = np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        uv, mat = np.zeros((n, 2), np.float32), np.zeros(n, np.int32)
+        threads = threads or min(os.cpu_count() or 1, 16)
+        ptr = lambda x: None if x is None else x.ctypes.data   # noqa: E731
+        L.orc_trace_rays(self.h, n, ptr(o), ptr(d), ptr(tm), float(tmin), ptr(tmax), ptr(t), ptr(p), ptr(nn), ptr(uv), ptr(mat),
+                         threads)
+        return t, p, nn, uv, mat
+
     def census(self) -> dict:
         c = np.zeros(12, np.int32)
         lib().orc_scene_census(self.h, c.ctypes.data)

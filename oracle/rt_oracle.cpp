@@ -1235,6 +1235,43 @@ int orc_ray_sample(int h, int nx, int ny, int ns, int row0, int row1, unsigned l
     return m;
 }
 
+// Caller rays against the scene: obj_hit(world, ray, tmin, tmax[k]) for each of n rays (origins, directions: 3n floats; times:
+// n floats or null = 0; tmax: n floats or null = FLT_MAX), the restated reference's own hit with nothing added -- a ray the
+// product rules a miss before any hit function (a non-finite one) is the caller's business.  Per ray: t (FLT_MAX on a
+// miss), p and n (3 floats each), (float)u, (float)v (2 floats), and the material as its index in the scene's material
+// list (-1 on a miss).  Records of a miss are zeros.  Rays are split over `nthreads` threads (< 1 means 1).
+void orc_trace_rays(int h, long long n, const float* origins, const float* directions, const float* times, float tmin,
+                    const float* tmax, float* t_out, float* p_out, float* n_out, float* uv_out, int* mat_out, int nthreads) {
+    const Scene& S = *g_scenes[h];
+    if (nthreads < 1) nthreads = 1;
+    auto work = [&](int tid) {
+        for (long long k = tid; k < n; k += nthreads) {
+            Ray r;
+            r.o = v3(origins[3 * k], origins[3 * k + 1], origins[3 * k + 2]);
+            r.d = v3(directions[3 * k], directions[3 * k + 1], directions[3 * k + 2]);
+            r.tm = times ? (double)times[k] : 0.0;
+            Hit rec;
+            const bool hit = obj_hit(S.world, r, tmin, tmax ? tmax[k] : FLT_MAX, rec);
+            int mat = -1;
+            if (hit)
+                for (size_t m = 0; m < S.mats.size(); ++m)
+                    if (S.mats[m].get() == rec.mat) { mat = (int)m; break; }
+            const V3 p = hit ? rec.p : v3(0, 0, 0), nn = hit ? rec.n : v3(0, 0, 0);
+            t_out[k] = hit ? rec.t : FLT_MAX;
+            p_out[3 * k] = p.x; p_out[3 * k + 1] = p.y; p_out[3 * k + 2] = p.z;
+            n_out[3 * k] = nn.x; n_out[3 * k + 1] = nn.y; n_out[3 * k + 2] = nn.z;
+            uv_out[2 * k] = hit ? (float)rec.u : 0.0f; uv_out[2 * k + 1] = hit ? (float)rec.v : 0.0f;
+            mat_out[k] = mat;
+        }
+    };
+    if (nthreads == 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nthreads; ++t) th.emplace_back(work, t);
+        for (auto& t : th) t.join();
+    }
+}
+
 void orc_scene_census(int h, int* out) {
     const Scene& S = *g_scenes[h];
     for (int k = 0; k < 12; ++k) out[k] = 0;
