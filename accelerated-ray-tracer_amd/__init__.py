@@ -198,7 +198,8 @@ def load_ppm(path: str):
     return buf, w.value, h.value
 
 
-SCENE_TEXTURES = {"earth": "earthmap.ppm", "final": "earthmap.ppm", "simple_light": "poolball.ppm", "original": "8ball.ppm"}
+SCENE_TEXTURES = {"earth": "earthmap.ppm", "final": "earthmap.ppm", "simple_light": "poolball.ppm", "original": "8ball.ppm",
+                  "instanced": "earthmap.ppm"}
 
 
 def default_texture(scene: str = "final"):

@@ -316,6 +316,158 @@ void original_scene(built_scene& sc) {
     sc.background = vec3(0.043f, 0.030f, 0.094f);      // main.cu:1276
 }
 
+// ---- test scenes (not in the reference).  Each exists to reach a path no reference scene reaches; oracle/rt_oracle.cpp
+// builds the same scenes through its own classes.
+
+// "instanced": spheres, moving spheres, quads and boxes under translate only, rotate_y only and both, at 0, 90, -90, 180
+// degrees, a tiny and a generic angle; a dielectric sphere under rotate_y (the normal flip when a ray leaves it); an
+// image-textured sphere and quad under instances (uv from the object-space hit); one child shared by two instances; and
+// coincident duplicates with different materials -- a sphere, translate(sphere, 0) and rotate_y(sphere, 0), two coplanar
+// quads -- which give exact ties in t between different leaves.  A ground quad, a column of small spheres left of the
+// duplicates and a row right of the rest make 128 leaves (two tier slots) laid out so that the BVH's first split falls between the duplicates:
+// one of them is leaf 0 and another leaf 64, the same lane of the tier kernel's two slots.
+void instanced_scene(built_scene& sc) {
+    std::vector<hittable*> objs;
+    material* earth_tex = new lambertian(new image_texture(image_view(sc)));
+    objs.push_back(new quad(vec3(-7.4f, 0, -3), vec3(20.6f, 0, 0), vec3(0, 0, 6.5f), new lambertian(vec3(0.5f, 0.5f, 0.5f))));
+    // spheres: translate only; rotate_y only (90); both (-90)
+    objs.push_back(new translate(new sphere(vec3(0, 0, 0), 0.45f, new lambertian(vec3(0.8f, 0.2f, 0.2f))), vec3(-3.5f, 0.45f, 0)));
+    objs.push_back(new rotate_y(new sphere(vec3(0, 0.45f, 2.5f), 0.45f, new lambertian(vec3(0.2f, 0.8f, 0.2f))), 90.0f));
+    objs.push_back(new translate(new rotate_y(new sphere(vec3(1, 0, 0), 0.45f, new metal(vec3(0.8f, 0.8f, 0.7f), 0.1f)), -90.0f), vec3(-1.5f, 0.45f, -1)));
+    // moving spheres (shutter 0..1): translate only; rotate_y only (generic angle); both (180)
+    objs.push_back(new translate(new sphere(vec3(0, 0, 0), vec3(0, 0.4f, 0), 0.4f, new lambertian(vec3(0.2f, 0.3f, 0.9f))), vec3(-2.5f, 0.4f, 1.5f)));
+    objs.push_back(new rotate_y(new sphere(vec3(1.5f, 0.4f, 0), vec3(1.5f, 0.4f, 0.5f), 0.4f, new lambertian(vec3(0.9f, 0.8f, 0.1f))), 37.0f));
+    objs.push_back(new translate(new rotate_y(new sphere(vec3(0.5f, 0, 0), vec3(0.5f, 0.3f, 0.2f), 0.4f, new metal(vec3(0.6f, 0.7f, 0.8f), 0.0f)), 180.0f),
+                                 vec3(3.5f, 0.4f, 1.5f)));
+    // a dielectric sphere under rotate_y only
+    objs.push_back(new rotate_y(new sphere(vec3(0.8f, 0.6f, -0.8f), 0.6f, new dielectric(1.5f)), 45.0f));
+    // (u, v) read under an instance: an image-textured sphere and quad, both under translate(rotate_y(.))
+    objs.push_back(new translate(new rotate_y(new sphere(vec3(0, 0, 0), 0.6f, earth_tex), 120.0f), vec3(1.2f, 0.6f, 1.2f)));
+    objs.push_back(new translate(new rotate_y(new quad(vec3(0, 0, 0), vec3(1, 0, 0), vec3(0, 1, 0), earth_tex), 37.0f), vec3(1.5f, 0, -2.5f)));
+    // quads: translate only; rotate_y only (tiny angle)
+    objs.push_back(new translate(new quad(vec3(0, 0, 0), vec3(1, 0, 0), vec3(0, 1, 0), new lambertian(vec3(0.9f, 0.4f, 0.1f))), vec3(-4, 0, -2)));
+    objs.push_back(new rotate_y(new quad(vec3(-1, 0, -3.5f), vec3(1.2f, 0, 0), vec3(0, 1.2f, 0), new lambertian(vec3(0.3f, 0.6f, 0.6f))), 0.001f));
+    // boxes: translate only; rotate_y only (-90); both (generic)
+    objs.push_back(new translate(make_box(vec3(0, 0, 0), vec3(0.6f, 0.6f, 0.6f), new lambertian(vec3(0.7f, 0.7f, 0.2f))), vec3(-3.8f, 0, 2.2f)));
+    objs.push_back(new rotate_y(make_box(vec3(2.8f, 0, -1.5f), vec3(3.5f, 0.8f, -0.8f), new metal(vec3(0.9f, 0.6f, 0.6f), 0.3f)), -90.0f));
+    objs.push_back(new translate(new rotate_y(make_box(vec3(0, 0, 0), vec3(0.7f, 1.0f, 0.7f), new lambertian(vec3(0.6f, 0.2f, 0.7f))), 15.0f), vec3(3.2f, 0, -2)));
+    // one child, two instances
+    hittable* shared = new sphere(vec3(0, 0, 0), 0.3f, new metal(vec3(0.9f, 0.9f, 0.9f), 0.2f));
+    objs.push_back(new translate(shared, vec3(-0.5f, 0.3f, 2.2f)));
+    objs.push_back(new translate(new rotate_y(shared, 60.0f), vec3(0.6f, 0.3f, 2.4f)));
+    // coplanar overlapping quads
+    objs.push_back(new quad(vec3(-0.6f, 0, -3), vec3(1.2f, 0, 0), vec3(0, 1.0f, 0), new lambertian(vec3(0.9f, 0.9f, 0.9f))));
+    objs.push_back(new quad(vec3(-0.2f, 0.3f, -3), vec3(1.2f, 0, 0), vec3(0, 1.0f, 0), new lambertian(vec3(0.1f, 0.8f, 0.8f))));
+    // coincident spheres, each with its own material
+    const vec3 dup(-7.0f, 0.5f, -1.0f);
+    objs.push_back(new sphere(dup, 0.5f, new lambertian(vec3(1.0f, 0.5f, 0.0f))));
+    objs.push_back(new translate(new sphere(dup, 0.5f, new metal(vec3(0.5f, 0.5f, 1.0f), 0.0f)), vec3(0, 0, 0)));
+    objs.push_back(new rotate_y(new sphere(dup, 0.5f, new lambertian(vec3(0.5f, 0.0f, 0.5f))), 0.0f));
+    // the column (63 spheres) and the row (43)
+    material* small = new lambertian(vec3(0.4f, 0.4f, 0.4f));
+    for (int k = 0; k < 63; ++k) objs.push_back(new sphere(vec3(-8.0f, 2.0f + 0.1f * (float)k, -1.0f), 0.045f, small));
+    for (int k = 0; k < 43; ++k) objs.push_back(new sphere(vec3(4.5f + 0.2f * (float)k, 0.1f, -3.0f), 0.09f, small));
+    const vec3 eye(-1.5f, 2.5f, 8), target(-1.5f, 0.5f, -1);
+    finish(sc, objs, new camera(eye, target, vec3(0, 1, 0), 64.0f, aspect_of(sc.nx, sc.ny), 0.0f, 9.0f, 0.0, 1.0));
+    sc.use_gradient_bg = 1;
+}
+
+// "fog": four constant_media, so no tier data (at most two): boundaries a box (the camera inside it), a quad, a translated
+// sphere and a rotated box; the sphere's medium lies inside the box's and overlaps the rotated box's, and a dielectric
+// sphere sits inside the rotated box's.
+void fog_scene(built_scene& sc) {
+    std::vector<hittable*> objs;
+    objs.push_back(new sphere(vec3(0, -1000, 0), 1000.f, new lambertian(vec3(0.5f, 0.5f, 0.5f))));
+    objs.push_back(new sphere(vec3(-2, 0.7f, 0), 0.7f, new lambertian(vec3(0.7f, 0.3f, 0.2f))));
+    objs.push_back(new sphere(vec3(0, 5, -2), 1.0f, new diffuse_light(vec3(6, 6, 6))));
+    objs.push_back(new sphere(vec3(1.436f, 0.8f, -0.713f), 0.35f, new dielectric(1.5f)));
+    objs.push_back(new constant_medium(make_box(vec3(-8, -1, -8), vec3(8, 5, 12), new dielectric(1.5f)), 0.03f, vec3(0.9f, 0.9f, 0.9f)));
+    objs.push_back(new constant_medium(new translate(new sphere(vec3(0, 0, 0), 1.2f, new dielectric(1.5f)), vec3(0.3f, 1.2f, 0)), 0.6f, vec3(0.2f, 0.4f, 0.9f)));
+    objs.push_back(new constant_medium(new rotate_y(make_box(vec3(1, 0, -0.5f), vec3(2.2f, 1.8f, 0.7f), new dielectric(1.5f)), 30.0f), 0.9f, vec3(0.9f, 0.5f, 0.2f)));
+    objs.push_back(new constant_medium(new quad(vec3(-3, 0, -3), vec3(6, 0, 0), vec3(0, 4, 0), new dielectric(1.5f)), 0.5f, vec3(1, 1, 1)));
+    const vec3 eye(0, 1.5f, 9), target(0, 1, 0);
+    finish(sc, objs, new camera(eye, target, vec3(0, 1, 0), 40.0f, aspect_of(sc.nx, sc.ny), 0.0f, 9.0f, 0.0, 1.0));
+    sc.use_gradient_bg = 1;
+}
+
+// "crowd_4096" / "crowd_4097": spheres only (static and moving, all four sphere materials), a ground sphere and a 64-wide
+// grid: exactly 4096 leaves, the most the tier kernel's 64 slots of 64 hold, and one more, which has no tier data.
+// "crowd_2400": the same recipe with 2 400 leaves, for LDS mode 1: a walk array of 2 400 .. 4 799 nodes fits the CU's LDS
+// (at most 5 056 nodes of 32 bytes), the walk array and 2 400 spheres of 32 bytes do not unless the planner drops all but
+// 256 interior nodes.  (The 4 096-leaf crowds keep ~6 600 nodes: LDS mode 0.)
+void crowd_spheres(built_scene& sc, int leaves) {
+    world_rng rnd;
+    std::vector<hittable*> objs;
+    objs.push_back(new sphere(vec3(0, -1000, 0), 1000.f, new lambertian(vec3(0.5f, 0.5f, 0.5f))));
+    for (int i = 0; i + 1 < leaves; ++i) {
+        const int a = i % 64, b = i / 64;
+        const float pick = rnd();
+        const float px = (float)(a - 32) + 0.7f * rnd();
+        const float pz = (float)(b - 32) + 0.7f * rnd();
+        const vec3 at(px, 0.3f, pz);
+        material* m;
+        if (pick < 0.55f) {
+            const float r = rnd();
+            const float g = rnd();
+            const float bl = rnd();
+            m = new lambertian(vec3(r, g, bl));
+        } else if (pick < 0.75f) {
+            m = new metal(vec3(0.7f, 0.6f, 0.5f), 0.5f * rnd());
+        } else if (pick < 0.9f) {
+            m = new dielectric(1.5f);
+        } else {
+            m = new diffuse_light(vec3(4, 4, 4));
+        }
+        if (rnd() < 0.5f) {
+            const float vy = 0.4f * rnd();
+            objs.push_back(new sphere(at, at + vec3(0, vy, 0), 0.3f, m));
+        } else {
+            objs.push_back(new sphere(at, 0.3f, m));
+        }
+    }
+    const vec3 eye(0, 14, 44), target(0, 0, 0);
+    finish(sc, objs, new camera(eye, target, vec3(0, 1, 0), 50.0f, aspect_of(sc.nx, sc.ny), 0.0f, 40.0f, 0.0, 1.0));
+    sc.use_gradient_bg = 1;
+}
+void crowd_4096(built_scene& sc) { crowd_spheres(sc, 4096); }
+void crowd_4097(built_scene& sc) { crowd_spheres(sc, 4097); }
+void crowd_2400(built_scene& sc) { crowd_spheres(sc, 2400); }
+
+// "crowd_big": 8 401 leaves of every solid kind (spheres, quads, boxes, rotated and translated boxes): more than the 8 192
+// leaves the regroup planner's third method takes, and a walk array too large for LDS at 32 bytes a leaf (LDS mode 0).
+void crowd_big(built_scene& sc) {
+    world_rng rnd;
+    std::vector<hittable*> objs;
+    material* ground = new lambertian(vec3(0.5f, 0.5f, 0.5f));
+    material* red = new lambertian(vec3(0.7f, 0.2f, 0.2f));
+    material* white = new lambertian(vec3(0.8f, 0.8f, 0.8f));
+    material* shiny = new metal(vec3(0.7f, 0.7f, 0.8f), 0.1f);
+    material* glass = new dielectric(1.5f);
+    objs.push_back(new sphere(vec3(0, -1000, 0), 1000.f, ground));
+    for (int i = 0; i < 8400; ++i) {
+        const int a = i % 100, b = i / 100;
+        const float px = (float)(a - 50) + 0.5f * rnd();
+        const float pz = (float)(b - 42) + 0.5f * rnd();
+        const float pick = rnd();
+        switch (i % 7) {
+        case 4:
+            objs.push_back(new quad(vec3(px, 0, pz), vec3(0.5f, 0, 0), vec3(0, 0.6f, 0), red));
+            break;
+        case 5:
+            objs.push_back(make_box(vec3(px, 0, pz), vec3(px + 0.4f, 0.5f, pz + 0.4f), white));
+            break;
+        case 6:
+            objs.push_back(new translate(new rotate_y(make_box(vec3(0, 0, 0), vec3(0.4f, 0.6f, 0.4f), red), 360.0f * pick), vec3(px, 0, pz)));
+            break;
+        default:
+            objs.push_back(new sphere(vec3(px, 0.25f, pz), 0.25f, pick < 0.6f ? white : (pick < 0.8f ? shiny : glass)));
+        }
+    }
+    const vec3 eye(0, 15, 60), target(0, 0, -5);
+    finish(sc, objs, new camera(eye, target, vec3(0, 1, 0), 50.0f, aspect_of(sc.nx, sc.ny), 0.0f, 65.0f, 0.0, 1.0));
+    sc.use_gradient_bg = 1;
+}
+
 struct entry {
     const char* name;
     void (*build)(built_scene&);
@@ -336,6 +488,12 @@ const entry k_scenes[] = {
     {"final", final_scene, 800, 800, 10000},
     {"simple_light", simple_light, 1200, 600, 10000},
     {"original", original_scene, 800, 800, 10000},
+    {"instanced", instanced_scene, 64, 64, 8},
+    {"fog", fog_scene, 64, 64, 8},
+    {"crowd_4096", crowd_4096, 64, 64, 8},
+    {"crowd_4097", crowd_4097, 64, 64, 8},
+    {"crowd_2400", crowd_2400, 64, 64, 8},
+    {"crowd_big", crowd_big, 64, 64, 8},
 };
 const int k_num_scenes = (int)(sizeof(k_scenes) / sizeof(k_scenes[0]));
 

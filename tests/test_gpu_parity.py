@@ -61,7 +61,9 @@ def test_golden_fixtures(gpu, kernel):
 @pytest.mark.parametrize("name,nx,ny,ns", [("two_spheres", 200, 100, 4), ("bouncing", 160, 96, 16), ("book1", 160, 96, 8),
                                            ("cornell", 96, 96, 16), ("cornell_smoke", 96, 96, 16), ("final", 80, 80, 8),
                                            ("degenerate", 32, 16, 8), ("checker", 96, 48, 8), ("earth", 96, 48, 8), ("perlin", 64, 32, 4),
-                                           ("quads", 96, 48, 8), ("simple_light", 96, 48, 16), ("original", 64, 64, 8)])
+                                           ("quads", 96, 48, 8), ("simple_light", 96, 48, 16), ("original", 64, 64, 8),
+                                           ("instanced", 64, 64, 8), ("fog", 64, 64, 8), ("crowd_4096", 64, 64, 4), ("crowd_4097", 64, 64, 4),
+                                           ("crowd_2400", 64, 64, 4), ("crowd_big", 64, 64, 4)])
 def test_scene_matches_oracle(gpu, orc, name, nx, ny, ns):
     img, iw, ih = gpu.default_texture(name)
     hs = gpu.HostScene(name, nx, ny, img, iw, ih)
@@ -100,7 +102,9 @@ def test_calibration_pass_counts_are_the_oracles(gpu, orc, name, ny):
     assert abs(after - info["tests_after"]) < 1e-9 * max(1.0, after)
 
 
-@pytest.mark.parametrize("name,nx,ny,ns", [("bouncing", 160, 96, 8), ("cornell", 64, 64, 8), ("cornell_smoke", 64, 64, 8), ("final", 64, 64, 4), ("degenerate", 32, 16, 8)])
+@pytest.mark.parametrize("name,nx,ny,ns", [("bouncing", 160, 96, 8), ("cornell", 64, 64, 8), ("cornell_smoke", 64, 64, 8), ("final", 64, 64, 4), ("degenerate", 32, 16, 8),
+                                           ("instanced", 64, 64, 4), ("fog", 64, 64, 4), ("crowd_4096", 64, 64, 2), ("crowd_4097", 64, 64, 2),
+                                           ("crowd_2400", 64, 64, 2), ("crowd_big", 64, 64, 2)])
 def test_walk_array_is_invisible(gpu, orc, name, nx, ny, ns):
     """rt_scene_create drops the interior nodes of the reference's tree whose box test does not pay (option bvh_collapse:
     0 = none, 1 = chosen by surface area, 2 = by measured pass counts, 3 = as 2 or a regrouping of the same leaves by
@@ -220,12 +224,22 @@ def test_scheduling_knobs_do_not_change_pixels(gpu):
         fb, st = render(gpu, hs, kernel, opts, ns=6)
         assert st.rays == st0.rays, (kernel, opts)
         assert np.array_equal(fb.view(np.uint32), base.view(np.uint32)), (kernel, opts)
-    hs2 = gpu.HostScene("cornell_smoke", 48, 48)
-    base2, _ = render(gpu, hs2, 0, ns=4)
+    # the general family with media (cornell_smoke, fog) and with instances of every kind and textures under them (instanced)
+    for name in ("cornell_smoke", "instanced", "fog"):
+        _knobs_on_general_scene(gpu, name)
+
+
+def _knobs_on_general_scene(gpu, name):
+    img, iw, ih = gpu.default_texture(name)
+    hs2 = gpu.HostScene(name, 48, 48, img, iw, ih)
+    base2, st2 = render(gpu, hs2, 0, ns=4)
     for kernel, opts in [(3, {}), (3, {"split_samples": 2, "presplit_samples": 1, "heavy_factor_x10": 10, "tier1_factor_x10": 10, "tier1_pixels": 4096}), (3, {"split_samples": 2, "tier_kernel": 0}), (3, {"lds_mode": 0, "diel_threshold": 1}), (3, {"lds_mode": 1, "box_threshold": 1, "medium_threshold": 1}), (3, {"steps_per_trip": 2, "shade_threshold": 60, "box_threshold": 64, "medium_threshold": 64}),
-                         (3, {"bvh_collapse": 0}), (3, {"bvh_collapse": 1, "leaf_threshold": 1}), (3, {"bvh_collapse": 2, "leaf_threshold": 40, "steps_per_trip": 5})]:
-        fb, _ = render(gpu, hs2, kernel, opts, ns=4)
-        assert np.array_equal(fb.view(np.uint32), base2.view(np.uint32)), (kernel, opts)
+                         (3, {"bvh_collapse": 0}), (3, {"bvh_collapse": 1, "leaf_threshold": 1}), (3, {"bvh_collapse": 2, "leaf_threshold": 40, "steps_per_trip": 5}),
+                         (3, {"lds_mode": 0, "steps_per_trip": 1, "shade_threshold": 1, "diel_threshold": 1, "newpath_threshold": 1, "leaf_threshold": 1, "box_threshold": 1, "medium_threshold": 1}),
+                         (3, {"lds_mode": 1, "steps_per_trip": 11, "shade_threshold": 64, "diel_threshold": 64, "newpath_threshold": 64, "leaf_threshold": 64, "box_threshold": 64, "medium_threshold": 64})]:
+        fb, st = render(gpu, hs2, kernel, opts, ns=4)
+        assert st.rays == st2.rays, (name, kernel, opts)
+        assert np.array_equal(fb.view(np.uint32), base2.view(np.uint32)), (name, kernel, opts)
 
 
 def test_headline_frame_properties(gpu, orc):
@@ -331,8 +345,18 @@ def test_drop_in_executable_writes_the_reference_ppm(gpu, orc, tmp_path):
     assert r.returncode != 0
 
 
+# Scene options the schedule tests add to every setting.  crowd_4096 has tier data (4 096 leaves, 64 slots), and the tier
+# kernel's 133 KB image fits only beside a main kernel that keeps nothing in LDS.  Its ~6 600-node walk array does not fit
+# LDS, so auto picks that mode already; lds_mode 0 is forced so that the tier kernel keeps running here even if a
+# planner change ever brought the walk array into LDS.  crowd_4097 (one leaf over) and fog (four media) have no tier data at all: there the same
+# settings must degrade to the main kernel alone.
+SCHEDULE_SCENE_OPTS = {"crowd_4096": {"lds_mode": 0}}
+NO_TIER_DATA = ("crowd_4097", "fog")
+
+
 @pytest.mark.parametrize("name,nx,ny,ns", [("bouncing", 160, 96, 16), ("cornell", 96, 96, 12), ("cornell_smoke", 96, 96, 12), ("final", 80, 80, 8),
-                                           ("degenerate", 96, 64, 8), ("simple_light", 96, 64, 8)])
+                                           ("degenerate", 96, 64, 8), ("simple_light", 96, 64, 8),
+                                           ("instanced", 64, 64, 8), ("crowd_4096", 64, 64, 8), ("crowd_4097", 64, 64, 8), ("fog", 64, 64, 8)])
 def test_split_frame_schedule_matches_oracle(gpu, orc, name, nx, ny, ns):
     """The cost-aware schedule (frame split at sample boundaries, pixels parked and resumed, heavy pixels on sparse waves
     and on the tier kernel's one-pixel waves: trace_wave over spheres, quads, boxes, instances and media) is scheduling
@@ -353,13 +377,15 @@ def test_split_frame_schedule_matches_oracle(gpu, orc, name, nx, ny, ns):
                  # without the cost prior (unranked first part), without the tier kernel
                  {"split_samples": 4, "presplit_samples": 2, "prior": 0, "heavy_factor_x10": 12, "tier1_factor_x10": 15, "tier1_pixels": 4096},
                  {"split_samples": 4, "tier_kernel": 0, "heavy_factor_x10": 12}):
+        opts = dict(opts, **SCHEDULE_SCENE_OPTS.get(name, {}))
         fb, st = render(gpu, hs, 3, opts, ns=ns)
         assert st.rays == cnt["rays"], (opts, st.rays, cnt["rays"])
         assert_frames_equal(fb, ref, f"{name} {opts}")
 
 
 @pytest.mark.parametrize("name,nx,ny,ns", [("bouncing", 160, 96, 16), ("cornell", 96, 96, 12), ("cornell_smoke", 96, 96, 12), ("final", 80, 80, 8),
-                                           ("simple_light", 96, 64, 8)])
+                                           ("simple_light", 96, 64, 8), ("instanced", 64, 64, 8), ("crowd_4096", 64, 64, 8), ("crowd_4097", 64, 64, 8),
+                                           ("fog", 64, 64, 8)])
 def test_tail_handoff_matches_oracle(gpu, orc, name, nx, ny, ns):
     """The tail hand-off (rt_device.h: once few pixels are in flight the main kernel parks them at their next sample boundary and a
     launch of the tier kernel after it finishes them, one per wave) is scheduling only.  Thresholds from "never" to "every pixel,
@@ -379,6 +405,7 @@ def test_tail_handoff_matches_oracle(gpu, orc, name, nx, ny, ns):
                       ("some", {"handoff_pixels": nx * ny // 4, "handoff_poll_us": 5, "split_samples": 3, "heavy_factor_x10": 12, "tier1_factor_x10": 20, "tier1_pixels": 64}),
                       ("no scan", {"handoff_scan": 0})):
         gpu.reset_options()
+        opts = dict(opts, **SCHEDULE_SCENE_OPTS.get(name, {}))
         for k, v in opts.items():
             gpu.set_option(k, v)
         if any(k.startswith(("tier1_", "heavy_")) for k in opts):
@@ -395,10 +422,15 @@ def test_tail_handoff_matches_oracle(gpu, orc, name, nx, ny, ns):
         assert st.rays == cnt["rays"], (tag, st.rays, cnt["rays"])
         assert_frames_equal(fb, ref, f"{name} hand-off {tag}")
     assert handed["off"] == 0 and handed["never"] == 0
-    assert handed["all"] > 0, handed      # the path under test did run
+    if name in NO_TIER_DATA:
+        assert sum(handed.values()) == 0, handed      # no tier kernel to hand off to: the main kernel finishes every pixel
+    else:
+        assert handed["all"] > 0, handed      # the path under test did run
     # a row band (what one rank of a multi-GPU run renders) with everything handed off
     gpu.reset_options()
     gpu.set_option("handoff_pixels", 1 << 24); gpu.set_option("handoff_poll_us", 1); gpu.set_option("split_samples", 4)
+    for k, v in SCHEDULE_SCENE_OPTS.get(name, {}).items():
+        gpu.set_option(k, v)
     ds = gpu.DeviceScene(hs)
     try:
         f = hs.frame(ns=ns, tile_rows=4, tile_first=1, tile_stride=3)
@@ -411,7 +443,7 @@ def test_tail_handoff_matches_oracle(gpu, orc, name, nx, ny, ns):
     assert_frames_equal(fb, ref[rows], f"{name} hand-off on a row band")
 
 
-@pytest.mark.parametrize("name,nx,ny", [("bouncing", 96, 64), ("cornell_smoke", 64, 64), ("final", 48, 48)])
+@pytest.mark.parametrize("name,nx,ny", [("bouncing", 96, 64), ("cornell_smoke", 64, 64), ("final", 48, 48), ("instanced", 64, 64), ("fog", 64, 64)])
 def test_progressive_windows_equal_one_shot(gpu, orc, name, nx, ny):
     """rt_render_window (progressive accumulation on the carried per-pixel RNG state, main.cu:126): windows
     [0, 5), [5, 12), [12, 24) leave after each window the frame a one-shot render of that many samples gives, bit for bit --
@@ -464,3 +496,61 @@ def test_tail_handoff_queue_cannot_overflow(gpu):
         assert st.rays == st0.rays, (opts, st.rays, st0.rays)
         assert np.array_equal(fb.view(np.uint32), base.view(np.uint32)), opts
         assert int(h[0]) > 0, opts
+
+
+# The path each test scene exists to reach, as rt_render reports it in kernel_variant = kernel * 1000 + lds_mode * 100 +
+# tex_level * 10 + spheres_only, at the shipped defaults.  instanced: the staged kernel's textured general family with nodes
+# and spheres in LDS; fog: 8 walk nodes, scanned in lockstep (lds_mode 4); crowd_2400: the walk array in LDS, the spheres not
+# (lds_mode 1); the 4 096-leaf crowds (~6 600 walk nodes) and crowd_big (8 401 leaves): nothing in LDS.
+TEST_SCENE_VARIANTS = {"instanced": 3220, "fog": 3400, "crowd_2400": 3101, "crowd_4096": 3001, "crowd_4097": 3001, "crowd_big": 3000}
+
+
+def test_test_scenes_reach_their_paths(gpu):
+    """Each test scene still reaches the path it was built for: the kernel variant at default options; a forced LDS mode
+    that does not fit is refused (RT_ERR_INVALID) and leaves the scene usable; the tier kernel and the tail hand-off on or
+    off change no bit and no ray count, and the hand-off runs exactly where the scene has tier data that fits."""
+    L = gpu.rt_lib()
+    L.rt_debug_handoff.argtypes = [C.c_void_p, C.c_void_p]
+    ranked = {"split_samples": 2, "heavy_factor_x10": 10, "tier1_factor_x10": 10, "tier1_pixels": 65536, "tier_auto": 0,
+              "handoff_pixels": 1 << 24, "handoff_poll_us": 1}
+    for name, variant in TEST_SCENE_VARIANTS.items():
+        img, iw, ih = gpu.default_texture(name)
+        hs = gpu.HostScene(name, 64, 64, img, iw, ih)
+        base, st0 = render(gpu, hs, DEFAULT_KERNEL, ns=4)
+        assert st0.kernel_variant == variant, (name, st0.kernel_variant, variant)
+        for tier in (0, 1):
+            for handoff in (0, 1):
+                opts = dict(ranked, tier_kernel=tier, handoff=handoff, **SCHEDULE_SCENE_OPTS.get(name, {}))
+                gpu.reset_options()
+                for k, v in opts.items():
+                    gpu.set_option(k, v)
+                ds = gpu.DeviceScene(hs)
+                try:
+                    fb, st = ds.render(hs.frame(ns=4))
+                    h = np.zeros(2, np.uint64)
+                    assert L.rt_debug_handoff(ds._p, h.ctypes.data) == 0
+                finally:
+                    ds.close()
+                    gpu.reset_options()
+                assert st.rays == st0.rays, (name, opts)
+                assert np.array_equal(fb.view(np.uint32), base.view(np.uint32)), (name, opts)
+                # crowd_2400: tier data, but beside its walk array in LDS no room for the tier kernel's image
+                runs = handoff == 1 and name in ("instanced", "crowd_4096")
+                assert (int(h[0]) > 0) == runs, (name, opts, int(h[0]))
+    # crowd_big: neither the walk array nor the walk array and spheres fit the CU's LDS
+    hs = gpu.HostScene("crowd_big", 64, 64)
+    base, st0 = render(gpu, hs, DEFAULT_KERNEL, ns=2)
+    gpu.reset_options()
+    ds = gpu.DeviceScene(hs)
+    try:
+        for lds in (1, 2):
+            gpu.set_option("lds_mode", lds)
+            with pytest.raises(gpu.RtError, match="invalid argument.*does not fit"):
+                ds.render(hs.frame(ns=2))
+            gpu.reset_options()
+            fb, st = ds.render(hs.frame(ns=2))
+            assert st.kernel_variant == 3000 and st.rays == st0.rays
+            assert np.array_equal(fb.view(np.uint32), base.view(np.uint32))
+    finally:
+        ds.close()
+        gpu.reset_options()

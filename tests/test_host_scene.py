@@ -9,7 +9,10 @@ import pytest
 
 SCENES = [("two_spheres", 200, 100), ("bouncing", 240, 160), ("book1", 120, 80), ("cornell", 120, 120),
           ("cornell_smoke", 120, 120), ("final", 100, 100), ("checker", 120, 60), ("earth", 120, 60), ("perlin", 120, 60),
-          ("quads", 120, 60), ("simple_light", 120, 60), ("original", 80, 80), ("degenerate", 32, 16)]
+          ("quads", 120, 60), ("simple_light", 120, 60), ("original", 80, 80), ("degenerate", 32, 16),
+          # test scenes: instances of every kind, four media, the tier kernel's 4 096-leaf limit on both sides, 8 401 leaves
+          ("instanced", 64, 64), ("fog", 64, 64), ("crowd_4096", 64, 64), ("crowd_4097", 64, 64), ("crowd_2400", 64, 64),
+          ("crowd_big", 64, 64)]
 
 
 @pytest.mark.parametrize("name,nx,ny", SCENES)
@@ -53,15 +56,21 @@ def test_bouncing_scene_contents(art):
     assert hs.use_gradient_bg == 0 and hs.gamma == pytest.approx(2.2)
 
 
-def test_reference_scene_defaults(art):
+def test_reference_scene_defaults(art, orc):
     # what each reference host function passes to render<<<>>> (main.cu:656-661, 1074, 1130, 1179)
     expect = {"bouncing": (1200, 600, 10000, 0), "cornell": (600, 600, 10000, 0), "cornell_smoke": (600, 600, 1000, 0),
               "final": (800, 800, 10000, 0), "checker": (1200, 600, 500, 1), "quads": (1200, 600, 500, 1),
               "two_spheres": (200, 100, 1, 1), "random_scene": (1200, 800, 500, 0), "simple_light": (1200, 600, 10000, 0),
-              "original": (800, 800, 10000, 0), "earth": (1200, 600, 500, 1), "perlin": (1200, 600, 500, 1)}
+              "original": (800, 800, 10000, 0), "earth": (1200, 600, 500, 1), "perlin": (1200, 600, 500, 1),
+              # test scenes (not the reference's): small frames, gradient sky
+              "degenerate": (32, 16, 8, 1), "instanced": (64, 64, 8, 1), "fog": (64, 64, 8, 1), "crowd_4096": (64, 64, 8, 1),
+              "crowd_4097": (64, 64, 8, 1), "crowd_2400": (64, 64, 8, 1), "crowd_big": (64, 64, 8, 1)}
     for name, (nx, ny, ns, grad) in expect.items():
         hs = art.HostScene(name)
         assert (hs.nx, hs.ny, hs.ns, hs.use_gradient_bg) == (nx, ny, ns, grad), name
+        if name in ("degenerate", "instanced", "fog", "crowd_4096", "crowd_4097", "crowd_2400", "crowd_big"):
+            o = orc.OracleScene(name, nx, ny)
+            assert (o.def_nx, o.def_ny, o.def_ns, o.gradient) == (nx, ny, ns, grad), name
 
 
 def test_unknown_scene_is_an_error(art):
@@ -150,7 +159,9 @@ def test_ppm_texture_loader(art, tmp_path):
     assert (w, h) == (4, 3) and np.array_equal(data, rgb)
 
 
-@pytest.mark.parametrize("name,nx,ny,ns", [("bouncing", 96, 64, 2), ("cornell", 48, 48, 4), ("final", 40, 40, 2)])
+@pytest.mark.parametrize("name,nx,ny,ns", [("bouncing", 96, 64, 2), ("cornell", 48, 48, 4), ("final", 40, 40, 2), ("instanced", 64, 64, 4),
+                                           ("fog", 64, 64, 4), ("crowd_4096", 64, 64, 2), ("crowd_4097", 64, 64, 2), ("crowd_2400", 64, 64, 2),
+                                           ("crowd_big", 64, 64, 2)])
 def test_walk_array_planner(art, orc, name, nx, ny, ns):
     """rt_scene_create's planner (host only): which interior nodes of the reference's tree to drop.  With
     the oracle's own per-node pass counts as input, (1) its "before" figure is the oracle's box-test counter exactly -- the
@@ -198,7 +209,9 @@ def test_walk_array_planner(art, orc, name, nx, ny, ns):
 
 
 @pytest.mark.parametrize("method", [0, 1])
-@pytest.mark.parametrize("name,nx,ny", [("bouncing", 240, 160), ("cornell", 120, 120), ("final", 100, 100), ("two_spheres", 200, 100)])
+@pytest.mark.parametrize("name,nx,ny", [("bouncing", 240, 160), ("cornell", 120, 120), ("final", 100, 100), ("two_spheres", 200, 100),
+                                        ("instanced", 64, 64), ("fog", 64, 64), ("crowd_4096", 64, 64), ("crowd_4097", 64, 64),
+                                        ("crowd_2400", 64, 64), ("crowd_big", 64, 64)])
 def test_regrouped_hierarchy_keeps_what_exactness_needs(art, name, nx, ny, method):
     """rt_regroup_leaves (host only): a different hierarchy over the reference's leaves.  The walk gives the
     reference's results as long as (1) the leaves -- boxes, objects, order -- are the reference's and (2) every interior box

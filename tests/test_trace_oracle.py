@@ -7,9 +7,14 @@ import pytest
 import trace_families as tf
 
 SCENES = ["two_spheres", "degenerate", "bouncing", "book1", "cornell", "cornell_smoke", "final", "checker", "earth", "perlin",
-          "quads", "simple_light", "original"]
+          "quads", "simple_light", "original", "instanced", "fog", "crowd_4096", "crowd_4097", "crowd_2400",
+          "crowd_big"]
+MEDIA_SCENES = ("cornell_smoke", "final", "original", "fog")
+# crowd_big is left out of the float64 check: its boxes stand on the ground sphere and touch each other, so the check's
+# bounds leave over 1 % of the volume family undecided there (it has no off-surface or missed hit; the GPU module checks it)
 NX, NY, NS = 48, 32, 4
 F64_ROWS = 3000          # rays per batch that go through the float64 brute force (it is O(rays x primitives))
+F64_ROWS_CROWD = 300     # the same for the sphere crowds (2 400 .. 4 097 spheres)
 # Share of a family's rays that the float64 check may leave undecided.  Only the volume family is capped: the others are
 # built on features, window ends and range limits, where the bounds of f64_check leave many rays undecided; those families
 # are decided bit for bit against the oracle on the GPU (tests/test_trace_edges.py), and here they must still have every
@@ -67,7 +72,7 @@ def test_families_are_well_formed(scene, name):
     assert (bad | zero).all() and zero.sum() > 0 and bad.sum() > 0
 
 
-@pytest.mark.parametrize("name", [s for s in SCENES if s not in ("cornell_smoke", "final", "original")])
+@pytest.mark.parametrize("name", [s for s in SCENES if s not in MEDIA_SCENES + ("crowd_big",)])
 def test_oracle_agrees_with_float64(art, scene, name):
     """On every finite family of a solid scene (no media) the oracle's closest hit lies on its primitive and no primitive has
     a clear hit in the window before it (trace_families.f64_check states the bounds).  Undecided rays of the volume family
@@ -78,7 +83,8 @@ def test_oracle_agrees_with_float64(art, scene, name):
     for f in tf.FINITE_FAMILIES:
         und = tot = 0
         for k, b in enumerate(fam[f]):
-            b = tf.Batch(*(x[:F64_ROWS] if isinstance(x, np.ndarray) else x for x in b))
+            rows = F64_ROWS_CROWD if name.startswith("crowd") else F64_ROWS
+            b = tf.Batch(*(x[:rows] if isinstance(x, np.ndarray) else x for x in b))
             t, _, _, _, _ = os_.trace(b.o, b.d, b.tm, b.tmin, b.tmax)
             prim, inst = _oracle_prim(hs, b, t)
             r = tf.f64_check(hs, b, t, prim, inst)

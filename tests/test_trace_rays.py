@@ -9,7 +9,8 @@ pytestmark = pytest.mark.gpu
 
 FLT_MAX = np.float32(np.finfo(np.float32).max)
 SCENES = ["two_spheres", "degenerate", "bouncing", "book1", "cornell", "cornell_smoke", "final", "checker", "earth", "perlin",
-          "quads", "simple_light", "original"]
+          "quads", "simple_light", "original", "instanced", "fog", "crowd_4096", "crowd_4097", "crowd_2400",
+          "crowd_big"]
 NX, NY, NS = 48, 32, 4
 OPTIONS = [(lds, tree) for lds in (0, 1, 2, -1) for tree in (0, 1)]
 
