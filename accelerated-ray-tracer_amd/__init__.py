@@ -72,6 +72,10 @@ class RtRayBatch(C.Structure):
                 ("normal_out", C.c_void_p), ("uv_out", C.c_void_p), ("mat_out", C.c_void_p), ("hit_out", C.c_void_p)]
 
 
+class RtAdaptiveDesc(C.Structure):
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
+
+
 RT_TRACE_CLOSEST, RT_TRACE_ANY = 0, 1
 RT_PRIM_SPHERE, RT_PRIM_QUAD, RT_PRIM_BOX, RT_PRIM_INSTANCE, RT_PRIM_MEDIUM = range(5)
 
@@ -102,7 +106,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_set_option", "rt_reset_options", "rt_scene_walk_info", "rt_init_devices", "rt_multi_create", "rt_multi_render",
                   "rt_multi_destroy", "rt_multi_device_count", "rt_multi_row_owner", "rt_multi_probe_rccl", "rt_multi_debug_uninterleave",
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
-                  "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays"]
+                  "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive"]
 
 _rt = None
 _host = None
@@ -175,6 +179,9 @@ def rt_lib():
         L.rt_regroup_leaves.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.rt_regroup_leaves.restype = C.c_int
         L.rt_trace_rays.argtypes = [C.c_void_p, C.POINTER(RtRayBatch), C.c_void_p, C.c_int]
+        L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAdaptiveDesc), C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.POINTER(RtStats)]
+        L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.rt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _rt = L
     return _rt
@@ -428,6 +435,77 @@ class DeviceScene:
             return h.view(np.bool_) if on_host else h.view(torch.bool)
         return TraceResult(outs["t_out"], outs["prim_out"], outs["inst_out"], outs.get("point_out"), outs.get("normal_out"),
                            outs.get("uv_out"), outs.get("mat_out"))
+
+    def render_adaptive(self, frame: RtFrameDesc, min_spp: int, max_spp: int, threshold: float, floor: float = 0.01, out=None,
+                        spp_out=None, stream=0):
+        """Adaptive sampling (rt_render_adaptive): each pixel stops at the first checkpoint min_spp * 2^k where its average
+        moved by at most threshold * (brightness + floor) since the previous checkpoint, else at max_spp (include/rt_abi.h).
+
+        out / spp_out: None (numpy arrays are made), float32 / int32 numpy arrays of rows x nx (x 3), or device memory of
+        this scene's device -- torch tensors or integer pointers, both or neither.  stream: a hipStream_t as an integer or a
+        torch.cuda.Stream.  The call returns when the frame is complete.  Returns (fb, spp, stats); fb / spp are what was
+        passed in (None where an integer pointer was).  Malformed arguments raise ValueError before anything is launched."""
+        vals = {"min_spp": min_spp, "max_spp": max_spp}
+        for k, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{k} must be an integer")
+        min_spp, max_spp = int(min_spp), int(max_spp)
+        if min_spp < 2 or min_spp % 2:
+            raise ValueError("min_spp must be even and >= 2")
+        if max_spp < min_spp or max_spp % min_spp or (max_spp // min_spp) & (max_spp // min_spp - 1) or max_spp // min_spp > 1 << 16:
+            raise ValueError("max_spp must be min_spp * 2**K with 0 <= K <= 16")
+        threshold, floor = float(threshold), float(floor)
+        f32_max = float(np.finfo(np.float32).max)   # (the descriptor holds float32: a larger double would become infinite)
+        if not np.isfinite(threshold) or abs(threshold) > f32_max:
+            raise ValueError("threshold must be finite")
+        if not np.isfinite(floor) or floor > f32_max or floor < 0:
+            raise ValueError("floor must be finite and >= 0")
+        L = rt_lib()
+        rows = L.rt_frame_local_rows(C.byref(frame))
+        if frame.nx <= 0 or frame.ny <= 0 or rows < 0:
+            raise ValueError("bad frame size or row partition")
+        if out is None:
+            out = np.empty((rows, frame.nx, 3), np.float32)
+            if spp_out is None:
+                spp_out = np.empty((rows, frame.nx), np.int32)
+        on_host = isinstance(out, np.ndarray)
+        if spp_out is not None and isinstance(spp_out, np.ndarray) != on_host:
+            raise ValueError("out and spp_out must both be host (numpy) or both device memory")
+
+        def ptr(x, dtype, size, name):
+            if x is None:
+                return None
+            if isinstance(x, np.ndarray):
+                if x.dtype != dtype or x.size != size or not x.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"{name}: a C-contiguous {np.dtype(dtype).name} array of {size} elements is expected")
+                return x.ctypes.data
+            if hasattr(x, "data_ptr"):
+                import torch
+                want = torch.float32 if dtype == np.float32 else torch.int32
+                if x.dtype != want or x.numel() != size or not x.is_contiguous() or x.device != torch.device("cuda", self.device):
+                    raise ValueError(f"{name}: a contiguous {want} tensor of {size} elements on cuda:{self.device} is expected")
+                return x.data_ptr()
+            return int(x)
+        p_fb = ptr(out, np.float32, rows * frame.nx * 3, "out")
+        p_spp = ptr(spp_out, np.int32, rows * frame.nx, "spp_out")
+        if hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        a = RtAdaptiveDesc(min_spp, max_spp, threshold, floor)
+        stats = RtStats()
+        st = L.rt_render_adaptive(self._p, C.byref(frame), C.byref(a), C.c_void_p(p_fb), 0 if on_host else 1, C.c_void_p(p_spp) if p_spp else None,
+                                  C.c_void_p(int(stream)) if stream else None, C.byref(stats))
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_render_adaptive")
+        ret = lambda x: x if (x is None or isinstance(x, np.ndarray) or hasattr(x, "data_ptr")) else None   # noqa: E731
+        return ret(out), ret(spp_out), stats
+
+    def adaptive_passes(self) -> list:
+        """The passes of the last adaptive frame (diagnostics): dicts of route ("main" / "tier"), active pixels, samples, device ms."""
+        buf = np.zeros((32, 5), np.int64)
+        n = rt_lib().rt_debug_adaptive_passes(self._p, buf.ctypes.data, 32)
+        return [{"route": "tier" if r[0] else "main", "active": int(r[1]), "samples": [int(r[2]), int(r[3])], "ms": r[4] / 1000.0}
+                for r in buf[:max(n, 0)]]
 
     def progressive(self, frame: RtFrameDesc) -> "ProgressiveFrame":
         """Progressive accumulation of `frame` (rt_render_window): windows of samples, a displayable frame after each."""

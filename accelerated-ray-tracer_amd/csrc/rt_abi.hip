@@ -87,6 +87,8 @@ struct rt_options {
     int lpt = 1;                 // cost prepass + longest-first tile order (staged kernel, ns >= 2 * split_samples)
     int trace_lds = -1;          // rt_trace_rays: -1 = auto, 0 = scene through L1/L2, 1 = nodes in LDS, 2 = nodes and spheres in LDS
     int trace_tree = 1;          // rt_trace_rays: 1 = the walk array, 0 = the reference's full tree
+    int adaptive_tier = -1;      // rt_render_adaptive: -1 = a pass goes to the tier kernel when its active pixels fit the tier waves at once
+                                 // (DESIGN.md 4.8), 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit
 };
 rt_options g_opt;
 
@@ -156,6 +158,21 @@ struct rt_scene {
     bool frame_pending = false;
     hipStream_t pending_stream = nullptr;
     rt_stats pending_stats;
+    // rt_render_adaptive (cached like d_state): parked pixels, the average at the previous checkpoint, two pixel lists, the tail
+    // queue, and a small block: [0] the decision kernel's append head, then an rt_rank_info and the host copy of a work-counter block
+    rt_pixel_state* d_adapt_state = nullptr;
+    float* d_adapt_half = nullptr;
+    uint32_t* d_adapt_list[2] = {nullptr, nullptr};
+    unsigned long long* d_adapt_queue = nullptr;
+    int32_t* d_adapt_spp = nullptr;              // host spp_out: the device map copied back
+    uint32_t* d_adapt_count = nullptr;
+    rt_rank_info* d_adapt_rank = nullptr;
+    size_t adapt_capacity = 0;
+    std::vector<hipEvent_t> adapt_events;        // two per pass (rt_debug_adaptive_passes)
+    std::vector<long long> adapt_log;            // per pass of the last adaptive frame: route, active pixels, sample_begin, sample_end
+    std::vector<float> adapt_ms;
+    rt_rank_info adapt_rank_host;                // host sides of the small copies between passes (alive until the next sync)
+    unsigned int adapt_wc_host[RT_WORK_COUNTER_BYTES / 4];
 };
 
 // Progressive accumulation (rt_render_window): the parked pixels of one frame description between windows.
@@ -649,6 +666,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "shade_threshold") { if (value < 0 || value > 64) return invalid("shade_threshold: 0 (by the launch's load) or 1..64"); g_opt.shade_threshold = value; }
     else if (k == "trace_lds") { if (value < -1 || value > 2) return invalid("trace_lds: -1 (auto) .. 2"); g_opt.trace_lds = value; }
     else if (k == "trace_tree") { if (value < 0 || value > 1) return invalid("trace_tree: 0 (reference tree) or 1 (walk array)"); g_opt.trace_tree = value; }
+    else if (k == "adaptive_tier") { if (value < -1 || value > 1) return invalid("adaptive_tier: -1 (auto), 0 (main kernel) or 1 (tier kernel)"); g_opt.adaptive_tier = value; }
     else if (k == "wg_per_cu") { if (value < 0 || value > 8) return invalid("wg_per_cu: 0 (per kernel family) .. 8"); g_opt.wg_per_cu = value; }
     else return invalid("unknown option");
     return RT_OK;
@@ -669,6 +687,10 @@ rt_status rt_scene_destroy(rt_scene* s) {
     if (s->d_rank) (void)hipFree(s->d_rank);
     if (s->d_handoff) (void)hipFree(s->d_handoff);
     if (s->d_cal_cost) (void)hipFree(s->d_cal_cost);
+    for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue,
+                    (void*)s->d_adapt_spp, (void*)s->d_adapt_count, (void*)s->d_adapt_rank})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : s->adapt_events) (void)hipEventDestroy(e);
     if (s->tier_stream) (void)hipStreamDestroy(s->tier_stream);
     for (int k = 0; k < 4; ++k) { if (s->ev_fork[k]) (void)hipEventDestroy(s->ev_fork[k]); if (s->ev_join[k]) (void)hipEventDestroy(s->ev_join[k]); }
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
@@ -1294,6 +1316,82 @@ rt_status rt_debug_wave_last(rt_scene* s, unsigned long long* out, int n_waves) 
     return RT_OK;
 }
 
+namespace {
+// The main kernel's launch shape for a launch over `n_pixels` pixels (`fp.work_items` work items): LDS residency mode, workgroup
+// shape, grid and stage quorums (written to fp).  Shared by rt_render / rt_render_window and rt_render_adaptive's passes.
+struct main_launch {
+    int lds_mode;
+    size_t lds_bytes;
+    dim3 grid, block;
+    int per_cu_resident;   // workgroups of this launch that can be resident on one CU (persistent kernels)
+    bool lean_family;
+};
+rt_status plan_main_launch(const rt_scene* s, int kernel, size_t n_pixels, rt_frame_params& fp, main_launch& ml) {
+    const int g_num_cu = g_devices[s->device].num_cu;
+    const size_t g_lds_per_cu = g_devices[s->device].lds_per_cu;
+    // LDS residency: nodes + spheres in every workgroup of a CU if they fit that many times (2 workgroups for the lean
+    // spheres-only kernels, 3 otherwise: see the workgroup shapes below), else once (one big workgroup per CU), else nodes only
+    int lds_mode = g_opt.lds_mode;
+    const bool lean_family = s->spheres_only && s->tex_level < 2;
+    const size_t budget1 = g_lds_per_cu - 2048;   // one workgroup per CU
+    if (lds_mode < 0) {
+        // nodes + spheres where they fit a CU at all (several workgroups each with its own image, or one big workgroup
+        // sharing one: see the workgroup shapes below), else nodes only, else everything through L1 / L2
+        // (lds_mode 3 -- materials and textures in LDS too -- is selectable but measured no faster: profiles/r01_sweep34)
+        if (s->node_bytes + s->sphere_bytes <= budget1) lds_mode = 2;
+        else if (s->node_bytes <= budget1) lds_mode = 1;
+        else lds_mode = 0;
+    }
+    if (g_opt.lds_mode < 0 && kernel == RT_KERNEL_STAGED && g_opt.scan_nodes > 0 && s->dev.n_nodes <= g_opt.scan_nodes) lds_mode = 4;   // lockstep scan of a tiny scene
+    if (lds_mode >= 3 && kernel != RT_KERNEL_STAGED) lds_mode = 2;
+    if (kernel == RT_KERNEL_PIXEL) lds_mode = 0;   // the cross-check kernel reads the scene through L1/L2
+    size_t lds_bytes = 0;
+    if (lds_mode >= 1 && lds_mode <= 3) lds_bytes += s->node_bytes;
+    if (lds_mode >= 2 && lds_mode <= 3) lds_bytes += s->sphere_bytes;
+    if (lds_mode == 3) lds_bytes += s->shade_bytes;
+    if (lds_bytes > budget1) return invalid("requested lds_mode does not fit the CU's LDS");
+    dim3 grid, block;
+    int per_cu_resident = 1;   // workgroups of this launch that can be resident on one CU (persistent kernels)
+    if (kernel == RT_KERNEL_PIXEL) {
+        block = dim3(256);
+        grid = dim3((fp.work_items + 255u) / 256u);
+    } else {
+        // workgroup shape per kernel family (register budgets: launch bounds, rt_device.h): the lean spheres-only
+        // kernels 2 x 512 threads per CU (4 waves per SIMD), the others 3 x 256 (3 waves per SIMD; workgroups of four
+        // waves, one per SIMD -- 2 x 384 threads is the same occupancy and measured 1.4x slower on the Cornell box)
+        const bool lean = lean_family;
+        const int fam_max_threads = lean ? RT_LEAN_MAX_THREADS : RT_HEAVY_MAX_THREADS;
+        const int lds_fit = lds_bytes ? (int)(g_lds_per_cu / (lds_bytes + 512)) : 8;
+        int per_cu = g_opt.wg_per_cu > 0 ? g_opt.wg_per_cu : (lean ? 2 : 3);
+        int threads = g_opt.threads > 0 ? g_opt.threads : (lean ? 512 : 256);
+        if (g_opt.wg_per_cu <= 0 && g_opt.threads <= 0 && lds_fit < per_cu) {
+            // the scene's LDS image does not fit that many times: one workgroup with all the CU's waves shares one image
+            per_cu = 1; threads = fam_max_threads;
+        }
+        if (lds_fit < per_cu) per_cu = lds_fit < 1 ? 1 : lds_fit;
+        if (threads > fam_max_threads) threads = fam_max_threads;
+        if (threads < 64) threads = 64;
+        block = dim3((unsigned)threads);
+        unsigned want = (unsigned)(g_num_cu * per_cu);
+        const unsigned need = (fp.work_items + (unsigned)threads - 1) / (unsigned)threads;
+        grid = dim3(want < need ? want : need);
+        per_cu_resident = per_cu;
+    }
+    {   // stage quorums.  In a launch that leaves the machine mostly empty (a small share of a frame) a lane waiting for 32 others
+        // to finish their walks is waiting on the frame's critical path: the quorums are halved there.
+        const double pixels_per_lane = (double)n_pixels / ((double)g_num_cu * (double)per_cu_resident * (double)block.x);
+        // (lean family: every share of the BASELINE frames -- a whole frame is 3.3 - 3.7; the Cornell box's 1/8 share is slower with them: 172 -> 179 ms)
+        const bool latency_regime = kernel == RT_KERNEL_STAGED && lean_family && pixels_per_lane < 2.75;
+        fp.shade_threshold = g_opt.shade_threshold > 0 ? g_opt.shade_threshold : (latency_regime ? 16 : 32);
+        fp.newpath_threshold = g_opt.newpath_threshold > 0 ? g_opt.newpath_threshold : (s->spheres_only ? (latency_regime ? 12 : 24) : 8);
+    }
+    ml.lds_mode = lds_mode; ml.lds_bytes = lds_bytes; ml.grid = grid; ml.block = block; ml.per_cu_resident = per_cu_resident;
+    ml.lean_family = lean_family;
+    return RT_OK;
+}
+
+}  // namespace
+
 static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int fb_on_device, void* stream_v, int blocking, rt_stats* stats,
                              rt_progressive* win, int32_t win_begin, int32_t win_end);
 
@@ -1390,63 +1488,14 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     fp.diel_threshold = g_opt.diel_threshold;
     fp.box_threshold = g_opt.box_threshold; fp.medium_threshold = g_opt.medium_threshold;
 
-    // LDS residency: nodes + spheres in every workgroup of a CU if they fit that many times (2 workgroups for the lean
-    // spheres-only kernels, 3 otherwise: see the workgroup shapes below), else once (one big workgroup per CU), else nodes only
     const int kernel = win ? RT_KERNEL_STAGED : g_opt.kernel;   // (kernel 0 renders whole pixels only)
-    int lds_mode = g_opt.lds_mode;
-    const bool lean_family = s->spheres_only && s->tex_level < 2;
-    const size_t budget1 = g_lds_per_cu - 2048;   // one workgroup per CU
-    if (lds_mode < 0) {
-        // nodes + spheres where they fit a CU at all (several workgroups each with its own image, or one big workgroup
-        // sharing one: see the workgroup shapes below), else nodes only, else everything through L1 / L2
-        // (lds_mode 3 -- materials and textures in LDS too -- is selectable but measured no faster: profiles/r01_sweep34)
-        if (s->node_bytes + s->sphere_bytes <= budget1) lds_mode = 2;
-        else if (s->node_bytes <= budget1) lds_mode = 1;
-        else lds_mode = 0;
-    }
-    if (g_opt.lds_mode < 0 && kernel == RT_KERNEL_STAGED && g_opt.scan_nodes > 0 && s->dev.n_nodes <= g_opt.scan_nodes) lds_mode = 4;   // lockstep scan of a tiny scene
-    if (lds_mode >= 3 && kernel != RT_KERNEL_STAGED) lds_mode = 2;
-    if (kernel == RT_KERNEL_PIXEL) lds_mode = 0;   // the cross-check kernel reads the scene through L1/L2
-    size_t lds_bytes = 0;
-    if (lds_mode >= 1 && lds_mode <= 3) lds_bytes += s->node_bytes;
-    if (lds_mode >= 2 && lds_mode <= 3) lds_bytes += s->sphere_bytes;
-    if (lds_mode == 3) lds_bytes += s->shade_bytes;
-    if (lds_bytes > budget1) return invalid("requested lds_mode does not fit the CU's LDS");
-    dim3 grid, block;
-    int per_cu_resident = 1;   // workgroups of this launch that can be resident on one CU (persistent kernels)
-    if (kernel == RT_KERNEL_PIXEL) {
-        block = dim3(256);
-        grid = dim3((fp.work_items + 255u) / 256u);
-    } else {
-        // workgroup shape per kernel family (register budgets: launch bounds, rt_device.h): the lean spheres-only
-        // kernels 2 x 512 threads per CU (4 waves per SIMD), the others 3 x 256 (3 waves per SIMD; workgroups of four
-        // waves, one per SIMD -- 2 x 384 threads is the same occupancy and measured 1.4x slower on the Cornell box)
-        const bool lean = lean_family;
-        const int fam_max_threads = lean ? RT_LEAN_MAX_THREADS : RT_HEAVY_MAX_THREADS;
-        const int lds_fit = lds_bytes ? (int)(g_lds_per_cu / (lds_bytes + 512)) : 8;
-        int per_cu = g_opt.wg_per_cu > 0 ? g_opt.wg_per_cu : (lean ? 2 : 3);
-        int threads = g_opt.threads > 0 ? g_opt.threads : (lean ? 512 : 256);
-        if (g_opt.wg_per_cu <= 0 && g_opt.threads <= 0 && lds_fit < per_cu) {
-            // the scene's LDS image does not fit that many times: one workgroup with all the CU's waves shares one image
-            per_cu = 1; threads = fam_max_threads;
-        }
-        if (lds_fit < per_cu) per_cu = lds_fit < 1 ? 1 : lds_fit;
-        if (threads > fam_max_threads) threads = fam_max_threads;
-        if (threads < 64) threads = 64;
-        block = dim3((unsigned)threads);
-        unsigned want = (unsigned)(g_num_cu * per_cu);
-        const unsigned need = (fp.work_items + (unsigned)threads - 1) / (unsigned)threads;
-        grid = dim3(want < need ? want : need);
-        per_cu_resident = per_cu;
-    }
-    {   // stage quorums.  In a launch that leaves the machine mostly empty (a small share of a frame) a lane waiting for 32 others
-        // to finish their walks is waiting on the frame's critical path: the quorums are halved there.
-        const double pixels_per_lane = (double)local_rows * (double)f->nx / ((double)g_num_cu * (double)per_cu_resident * (double)block.x);
-        // (lean family: every share of the BASELINE frames -- a whole frame is 3.3 - 3.7; the Cornell box's 1/8 share is slower with them: 172 -> 179 ms)
-        const bool latency_regime = kernel == RT_KERNEL_STAGED && lean_family && pixels_per_lane < 2.75;
-        fp.shade_threshold = g_opt.shade_threshold > 0 ? g_opt.shade_threshold : (latency_regime ? 16 : 32);
-        fp.newpath_threshold = g_opt.newpath_threshold > 0 ? g_opt.newpath_threshold : (s->spheres_only ? (latency_regime ? 12 : 24) : 8);
-    }
+    main_launch ml;
+    { const rt_status pl = plan_main_launch(s, kernel, (size_t)local_rows * (size_t)f->nx, fp, ml); if (pl != RT_OK) return pl; }
+    const int lds_mode = ml.lds_mode;
+    const size_t lds_bytes = ml.lds_bytes;
+    const bool lean_family = ml.lean_family;
+    dim3 grid = ml.grid, block = ml.block;
+    const int per_cu_resident = ml.per_cu_resident;
     // ---- the tier kernel of ranked launches (rt_kernel_tier.h): its LDS image and where its workgroups find room.
     // Lean family: the main kernel's 4 x 104 registers per SIMD leave 96 free, so ONE tier workgroup (four waves, one per
     // SIMD, 76 VGPRs) is resident on a CU beside a full main grid if the LDS left over holds its image.  Other families:
@@ -1723,6 +1772,251 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     if (blocking) return rt_frame_finish(s, stats);
     if (stats) *stats = out;
     return RT_OK;
+}
+
+// ---- rt_render_adaptive (include/rt_abi.h).  Passes [0, min/2) and [min/2, min) over every pixel, then [c_k, c_k+1)
+// over the pixels still active.  The render passes only park pixels (d_adapt_state); the decision kernel (rt_kernel_adaptive.hip)
+// writes fb and the sample-count map and compacts the active pixels into the next pass's list (main kernel) and queue (tier kernel).
+rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adaptive_desc* a, float* fb, int fb_on_device, int32_t* spp_out,
+                             void* stream_v, rt_stats* stats) {
+    // argument checks: no HIP call before they pass
+    if (!s) return invalid("rt_render_adaptive: null scene");
+    if (!f) return invalid("rt_render_adaptive: null frame description");
+    if (!a) return invalid("rt_render_adaptive: null adaptive description");
+    if (!fb) return invalid("rt_render_adaptive: null fb");
+    if (a->min_spp < 2 || (a->min_spp & 1)) return invalid("rt_render_adaptive: min_spp must be even and >= 2");
+    int levels = -1;   // K
+    for (int k = 0; k <= 16; ++k)
+        if ((long long)a->min_spp << k == (long long)a->max_spp) { levels = k; break; }
+    if (levels < 0) return invalid("rt_render_adaptive: max_spp must be min_spp * 2^K with 0 <= K <= 16");
+    if (!std::isfinite(a->threshold)) return invalid("rt_render_adaptive: threshold is not finite");
+    if (!std::isfinite(a->floor) || a->floor < 0.0f) return invalid("rt_render_adaptive: floor must be finite and >= 0");
+    if (f->nx <= 0 || f->ny <= 0 || (long long)f->nx * f->ny >= (1ll << 31)) return invalid("rt_render_adaptive: bad frame size");
+    const int local_rows = rt_frame_local_rows(f);
+    if (local_rows < 0) return invalid("rt_render_adaptive: bad row partition");
+
+    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    if (s->frame_pending) { const rt_status st = rt_frame_finish(s, nullptr); if (st != RT_OK) return st; }
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const int num_cu = g_devices[s->device].num_cu;
+    const size_t lds_per_cu = g_devices[s->device].lds_per_cu;
+    const int min_spp = a->min_spp, max_spp = a->max_spp;
+    const size_t n_pixels = (size_t)local_rows * (size_t)f->nx;
+    s->adapt_log.clear(); s->adapt_ms.clear();
+
+    rt_stats out;
+    memset(&out, 0, sizeof(out));
+    out.local_rows = local_rows;
+    if (n_pixels == 0) { s->pending_stats = out; if (stats) *stats = out; return RT_OK; }
+
+    // ---- buffers: cached in the scene, grown when a frame needs more
+    const size_t floats = n_pixels * 3;
+    if (s->adapt_capacity < n_pixels) {
+        for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue,
+                        (void*)s->d_adapt_spp})
+            if (p) (void)hipFree(p);
+        s->d_adapt_state = nullptr; s->d_adapt_half = nullptr; s->d_adapt_list[0] = s->d_adapt_list[1] = nullptr; s->d_adapt_queue = nullptr;
+        s->d_adapt_spp = nullptr; s->adapt_capacity = 0;
+        HIPCHK(hipMalloc((void**)&s->d_adapt_state, n_pixels * sizeof(rt_pixel_state)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_half, floats * sizeof(float)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_list[0], n_pixels * sizeof(uint32_t)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_list[1], n_pixels * sizeof(uint32_t)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_queue, n_pixels * sizeof(unsigned long long)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_spp, n_pixels * sizeof(int32_t)));
+        s->adapt_capacity = n_pixels;
+    }
+    if (!s->d_adapt_count) HIPCHK(hipMalloc((void**)&s->d_adapt_count, 64));
+    if (!s->d_adapt_rank) HIPCHK(hipMalloc((void**)&s->d_adapt_rank, sizeof(rt_rank_info)));
+    while (s->adapt_events.size() < 2u * 18u) {
+        hipEvent_t e = nullptr;
+        HIPCHK(hipEventCreate(&e));
+        s->adapt_events.push_back(e);
+    }
+    float* d_fb = fb;
+    if (!fb_on_device) {
+        if (s->d_fb_floats < floats) {
+            if (s->d_fb) (void)hipFree(s->d_fb);
+            s->d_fb = nullptr; s->d_fb_floats = 0;
+            HIPCHK(hipMalloc((void**)&s->d_fb, floats * sizeof(float)));
+            s->d_fb_floats = floats;
+        }
+        d_fb = s->d_fb;
+    }
+    int32_t* d_spp = fb_on_device ? spp_out : (spp_out ? s->d_adapt_spp : nullptr);
+
+    // ---- the main kernel's frame parameters (as rt_render_window's, without store_parked: a pass only parks)
+    rt_frame_params fp;
+    memset(&fp, 0, sizeof(fp));
+    fp.fb = d_fb;
+    fp.ray_counter = s->d_ray_counter;
+    fp.work_counter = s->d_work_counter;
+    fp.seed_base = f->seed_base;
+    fp.nx = f->nx; fp.ny = f->ny; fp.ns = max_spp; fp.gamma = f->gamma;
+    fp.background[0] = f->background[0]; fp.background[1] = f->background[1]; fp.background[2] = f->background[2];
+    fp.use_gradient_bg = f->use_gradient_bg;
+    fp.tile_rows = f->tile_rows; fp.tile_first = f->tile_first; fp.tile_stride = f->tile_stride;
+    fp.local_rows = local_rows;
+    fp.tiles_x = (f->nx + 7) / 8;
+    const int tiles_y = (local_rows + 7) / 8;
+    if ((long long)fp.tiles_x * tiles_y * 64 >= (1ll << 31)) return invalid("rt_render_adaptive: frame too large");
+    const uint32_t all_items = (uint32_t)fp.tiles_x * (uint32_t)tiles_y * 64u;
+    fp.sparse_priority = g_opt.sparse_priority; fp.sparse_eager = g_opt.sparse_eager; fp.semi_priority = g_opt.semi_priority; fp.tier_priority = g_opt.tier_priority;
+    fp.steps_per_trip = g_opt.steps_per_trip;
+    fp.leaf_threshold = g_opt.leaf_threshold;
+    fp.diel_threshold = g_opt.diel_threshold;
+    fp.box_threshold = g_opt.box_threshold; fp.medium_threshold = g_opt.medium_threshold;
+    fp.state_out = s->d_adapt_state;
+
+    // ---- the tier route: the tier kernel's tail mode alone on the machine, one pixel per wave, where the scene has tier data
+    // (at most 4096 leaves and 2 media) and its image fits a CU
+    const bool lean_family = s->spheres_only && s->tex_level < 2;
+    bool tier_ok = s->dev.leaf_lo != nullptr;
+    size_t tier_lds = 0;
+    int tier_scene = 0;
+    unsigned tier_grid = 0;
+    if (tier_ok) {
+        const int ns_ = s->dev.n_slots, nsph = s->dev.n_spheres, nm = s->dev.n_materials, nt = s->dev.n_textures;
+        const size_t budget = lds_per_cu - 2048;
+        if (rt_tier_lds_bytes(ns_, nsph, nm, nt, false) > budget) tier_ok = false;
+        else {
+            tier_scene = rt_tier_lds_bytes(ns_, nsph, nm, nt, true) <= budget ? 1 : 0;
+            tier_lds = rt_tier_lds_bytes(ns_, nsph, nm, nt, tier_scene != 0);
+            const unsigned by_lds = (unsigned)(lds_per_cu / (tier_lds + 512));
+            const unsigned by_regs = lean_family ? 4u : 3u;
+            tier_grid = (unsigned)num_cu * (by_lds < by_regs ? by_lds : by_regs);
+            if (tier_grid < 1u) tier_grid = 1u;
+        }
+    }
+    const size_t tier_waves = (size_t)tier_grid * (RT_TIER_THREADS / 64);
+    // auto crossover: a pass goes to the tier kernel when it has at most this many active pixels per resident tier wave.  Measured
+    // on row shares with every pixel active (tools/adaptive_sweep.py --config crossover, profiles/adaptive_mi355x.jsonl, DESIGN.md
+    // 4.8): the Cornell box's routes tie at 22 800 pixels (7.4 per wave of 3 072); on the headline scene the tier route is 1.6x
+    // faster at 60 000 pixels and still 10 % faster at 107 500 (26 per wave of 4 096), and 1.5x slower at 240 000
+    const size_t tier_per_wave = lean_family ? 32 : 6;
+    auto use_tier = [&](uint32_t active) -> bool {
+        if (!tier_ok || g_opt.adaptive_tier == 0) return false;
+        if (g_opt.adaptive_tier == 1) return true;
+        return (size_t)active <= tier_per_wave * tier_waves;
+    };
+
+    int pass_index = 0;
+    // one render pass: samples [b, e) of `active` pixels -- every local pixel (list null), or the list / queue the last decision wrote
+    auto render_pass = [&](int32_t b, int32_t e, const uint32_t* list, uint32_t active) -> rt_status {
+        rt_frame_params q = fp;
+        q.sample_begin = b; q.sample_end = e;
+        q.state_in = b > 0 ? s->d_adapt_state : nullptr;
+        const bool tier = list && use_tier(active);
+        hipEvent_t* ev = s->adapt_events.data() + 2 * pass_index;
+        HIPCHK(hipEventRecord(ev[0], stream));
+        if (tier) {
+            // the tail queue (n << 32 | pixel) with the adaptive state as both hand-off state and park target: samples [n, e)
+            memset(s->adapt_wc_host, 0, sizeof(s->adapt_wc_host));
+            s->adapt_wc_host[RT_WC_PUSHED] = active;   // (the queue head RT_WC_TAIL_HEAD starts at 0)
+            HIPCHK(hipMemcpyAsync(s->d_work_counter, s->adapt_wc_host, RT_WORK_COUNTER_BYTES, hipMemcpyHostToDevice, stream));
+            q.tail_mode = 1; q.handoff_queue = s->d_adapt_queue; q.handoff_cap = (uint32_t)n_pixels; q.handoff_state = s->d_adapt_state;
+            q.tier_lds_scene = tier_scene;
+            q.work_items = 0;
+            const unsigned want = (active + (unsigned)(RT_TIER_THREADS / 64) - 1u) / (unsigned)(RT_TIER_THREADS / 64);
+            const dim3 grid(want < tier_grid ? want : tier_grid);
+            HIPCHK(s->spheres_only ? rt_launch_tier_spheres(s->tex_level, s->dev, q, grid, tier_lds, stream)
+                                   : rt_launch_tier_general(s->tex_level, s->need_uv, s->dev, q, grid, tier_lds, stream));
+        } else {
+            main_launch ml;
+            q.work_items = list ? active : all_items;
+            { const rt_status pl = plan_main_launch(s, RT_KERNEL_STAGED, list ? (size_t)active : n_pixels, q, ml); if (pl != RT_OK) return pl; }
+            dim3 grid = ml.grid;
+            if (list) {
+                // the pixel list is tier 3 of a heavy list (rt_kernel_staged.h stage E): ordinary lanes take its entries first, and
+                // with no tiles behind it (work_items 0) a lane that finds it empty is done.  The whole resident grid is launched: the
+                // pixels spread over every CU, and waves with few live lanes advance their rays faster
+                memset(&s->adapt_rank_host, 0, sizeof(s->adapt_rank_host));
+                s->adapt_rank_host.heavy_items = active; s->adapt_rank_host.heavy_threshold = 0xFFFFFFFFu;
+                s->adapt_rank_host.sparse_stride = 1; s->adapt_rank_host.semi_stride = 1;
+                HIPCHK(hipMemcpyAsync(s->d_adapt_rank, &s->adapt_rank_host, sizeof(rt_rank_info), hipMemcpyHostToDevice, stream));
+                q.heavy_pixels = list; q.rank = s->d_adapt_rank; q.work_items = 0;
+                grid = dim3((unsigned)(num_cu * ml.per_cu_resident));
+            }
+            HIPCHK(hipMemsetAsync(s->d_work_counter, 0, RT_WORK_COUNTER_BYTES, stream));
+            HIPCHK(launch_render(RT_KERNEL_STAGED, ml.lds_mode, s, q, grid, ml.block, ml.lds_bytes, stream));
+            if (pass_index == 0) {
+                out.kernel_variant = RT_KERNEL_STAGED * 1000 + ml.lds_mode * 100 + s->tex_level * 10 + (s->spheres_only ? 1 : 0);
+                out.workgroups = (int)grid.x; out.threads_per_group = (int)ml.block.x; out.lds_bytes = (int)ml.lds_bytes;
+            }
+        }
+        HIPCHK(hipEventRecord(ev[1], stream));
+        s->adapt_log.push_back(tier ? 1 : 0); s->adapt_log.push_back((long long)active); s->adapt_log.push_back(b); s->adapt_log.push_back(e);
+        out.samples += (uint64_t)active * (uint64_t)(e - b);
+        ++pass_index;
+        return RT_OK;
+    };
+    // the decision kernel over the pixels of the pass that just ended (list null: every local pixel)
+    auto decide = [&](int mode, int32_t n, const uint32_t* list, uint32_t count, uint32_t* list_out) -> rt_status {
+        rt_adaptive_params p;
+        memset(&p, 0, sizeof(p));
+        p.state = s->d_adapt_state; p.half = s->d_adapt_half; p.list_in = list; p.n_in = count;
+        p.list_out = list_out; p.queue_out = s->d_adapt_queue; p.count_out = s->d_adapt_count;
+        p.fb = d_fb; p.spp = d_spp; p.n = n; p.mode = mode; p.nx = f->nx;
+        p.threshold = a->threshold; p.floor = a->floor; p.gamma = f->gamma;
+        HIPCHK(rt_launch_adaptive(p, stream));
+        return RT_OK;
+    };
+#define RT_TRY(expr) do { const rt_status st_ = (expr); if (st_ != RT_OK) return st_; } while (0)
+    HIPCHK(hipMemsetAsync(s->d_ray_counter, 0, 256, stream));
+    HIPCHK(hipEventRecord(s->ev_start, stream));
+    const uint32_t all = (uint32_t)n_pixels;
+    RT_TRY(render_pass(0, min_spp / 2, nullptr, all));
+    if (levels > 0) RT_TRY(decide(RT_ADAPTIVE_SNAPSHOT, min_spp / 2, nullptr, all, nullptr));
+    RT_TRY(render_pass(min_spp / 2, min_spp, nullptr, all));
+    const uint32_t* list = nullptr;    // the pixels of the pass that just ended (null = every local pixel)
+    uint32_t active = all;
+    int32_t n = min_spp;
+    int which = 0;
+    while (n < max_spp && active > 0) {
+        uint32_t* next = s->d_adapt_list[which];
+        HIPCHK(hipMemsetAsync(s->d_adapt_count, 0, sizeof(uint32_t), stream));
+        RT_TRY(decide(RT_ADAPTIVE_DECIDE, n, list, active, next));
+        HIPCHK(hipMemcpyAsync(&active, s->d_adapt_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        list = next; which ^= 1;
+        if (active == 0) break;
+        RT_TRY(render_pass(n, 2 * n, list, active));
+        n *= 2;
+    }
+    if (n == max_spp && active > 0) RT_TRY(decide(RT_ADAPTIVE_FINAL, n, list, active, nullptr));
+#undef RT_TRY
+    HIPCHK(hipEventRecord(s->ev_stop, stream));
+    if (!fb_on_device) {
+        HIPCHK(hipMemcpyAsync(fb, d_fb, floats * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (spp_out) HIPCHK(hipMemcpyAsync(spp_out, d_spp, n_pixels * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
+    unsigned long long rays = 0;
+    HIPCHK(hipMemcpy(&rays, s->d_ray_counter, sizeof(rays), hipMemcpyDeviceToHost));
+    for (int k = 0; k < pass_index; ++k) {
+        float pm = 0.f;
+        HIPCHK(hipEventElapsedTime(&pm, s->adapt_events[2 * k], s->adapt_events[2 * k + 1]));
+        s->adapt_ms.push_back(pm);
+    }
+    out.ms_render = (double)ms;
+    out.rays = rays;
+    out.reserved = pass_index;
+    s->pending_stats = out;
+    if (stats) *stats = out;
+    return RT_OK;
+}
+
+// The passes of the last adaptive frame (diagnostics, tools/adaptive_sweep.py): per pass 5 values -- route (0 main kernel,
+// 1 tier kernel), active pixels, sample_begin, sample_end, device ms (x1000) of the render launch.  Returns the number of passes.
+int32_t rt_debug_adaptive_passes(const rt_scene* s, long long* out, int32_t cap) {
+    if (!s) return -1;
+    const int32_t np = (int32_t)s->adapt_ms.size();
+    for (int32_t k = 0; k < np && k < cap; ++k) {
+        for (int c = 0; c < 4; ++c) out[5 * k + c] = s->adapt_log[4 * k + c];
+        out[5 * k + 4] = (long long)llround((double)s->adapt_ms[k] * 1000.0);
+    }
+    return np;
 }
 
 }  // extern "C"

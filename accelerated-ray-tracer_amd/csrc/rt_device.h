@@ -242,3 +242,27 @@ struct rt_trace_params {
 hipError_t rt_launch_trace(bool spheres_only, int lds_mode, const rt_scene_dev& sd, const rt_trace_params& tp, dim3 grid, size_t lds,
                            hipStream_t st);
 hipError_t rt_trace_occupancy(bool spheres_only, int lds_mode, bool any, bool record, size_t lds, int* blocks_per_cu);
+
+// rt_render_adaptive (rt_kernel_adaptive.hip): after each pass, one lane per pixel of that pass decides whether the pixel has
+// converged at checkpoint n (include/rt_abi.h), writes the converged ones to fb / spp and appends the others -- wave-aggregated
+// -- to list_out (local pixel ids, the main kernel's pixel list) and queue_out ((n << 32) | pixel, the tier kernel's tail queue).
+enum { RT_ADAPTIVE_SNAPSHOT = 0,   // record h = the average at n for every pixel of the pass, decide nothing
+       RT_ADAPTIVE_DECIDE = 1,     // the criterion at checkpoint n
+       RT_ADAPTIVE_FINAL = 2 };    // n = max_spp: every pixel of the pass is written
+#define RT_ADAPTIVE_THREADS 256
+struct rt_adaptive_params {
+    const rt_pixel_state* state;          // pixels parked at n samples
+    float* half;                          // per pixel: the linear average at the previous checkpoint (3 floats)
+    const uint32_t* list_in;              // the pass's pixels; null = local pixels [0, n_in)
+    uint32_t n_in;
+    uint32_t* list_out;                   // DECIDE: the next pass's pixels ...
+    unsigned long long* queue_out;        // ... and the same as tail-queue entries
+    uint32_t* count_out;                  // ... appended at this head
+    float* fb;                            // compact local rows, nx * 3 floats each
+    int32_t* spp;                         // final sample count per local pixel; null = not written
+    int32_t n;                            // the checkpoint: samples in state
+    int32_t mode;
+    int32_t nx;
+    float threshold, floor, gamma;
+};
+hipError_t rt_launch_adaptive(const rt_adaptive_params& p, hipStream_t st);

@@ -7,8 +7,11 @@
 // `--scene bouncing` is case 1, `--scene final` case 9.
 //
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
-//             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--list]
+//             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--list]
 //
+// --adaptive T renders with adaptive sampling (rt_render_adaptive): each pixel stops at the first checkpoint M * 2^k where its
+// average moved by at most T * (brightness + 0.01) since the previous one, and at --ns (= max_spp) otherwise.  M defaults to
+// the smallest checkpoint of --ns that is even and >= 16.  Not with --progressive or --gpus > 1.
 // --gpus N (N > 1) spreads the frame over the first N GPUs of the node: interleaved 4-row tiles, one scene replica
 // per device, one RCCL gather to device 0 (rt_multi_*, include/rt_abi.h).  The PPM is byte-identical for every N by construction (global per-pixel seeds,
 // no cross-device rays); verified on one GPU for N = 1 and for every rank's share, not yet on N > 1 hardware.
@@ -31,7 +34,9 @@ static void check(rt_status st, const char* what) {
 int main(int argc, char** argv) {
     std::string scene_name = "bouncing", texture_path;
     int nx = 0, ny = 0, ns = 0, device = 0, gpus = 1, progressive = 0;
-    bool p6 = false;
+    bool p6 = false, adaptive = false;
+    float threshold = 0.f;
+    int min_spp = 0;
     unsigned long long seed = 1984ull;
     for (int a = 1; a < argc; ++a) {
         std::string k = argv[a];
@@ -46,9 +51,14 @@ int main(int argc, char** argv) {
         else if (k == "--gpus") gpus = atoi(val());
         else if (k == "--p6") p6 = true;                        // binary PPM (clamped); the default is the reference's ASCII P3
         else if (k == "--progressive") progressive = atoi(val());   // render in windows of K samples (rt_render_window): same pixels, a frame after each
+        else if (k == "--adaptive") { adaptive = true; threshold = strtof(val(), nullptr); }
+        else if (k == "--min-spp") min_spp = atoi(val());
         else if (k == "--list") { int n = 0; const char* const* v = rtw::scene_names(&n); for (int i = 0; i < n; ++i) printf("%s\n", v[i]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); return 2; }
     }
+
+    if (adaptive && (progressive > 0 || gpus > 1)) { fprintf(stderr, "--adaptive cannot be combined with --progressive or --gpus > 1\n"); return 2; }
+    if (min_spp > 0 && !adaptive) { fprintf(stderr, "--min-spp needs --adaptive\n"); return 2; }
 
     std::vector<unsigned char> tex;
     int tw = 0, th = 0;
@@ -86,7 +96,19 @@ int main(int argc, char** argv) {
     } else {
         check(rt_init(device), "rt_init");
         check(rt_scene_create(&desc, &dev_scene), "rt_scene_create");
-        if (progressive > 0) {
+        if (adaptive) {
+            rt_adaptive_desc ad;
+            ad.max_spp = scene->ns;
+            if (min_spp <= 0) {   // the smallest checkpoint of max_spp that is even and >= 16 (max_spp itself below that)
+                min_spp = scene->ns;
+                while (min_spp % 4 == 0 && min_spp / 2 >= 16) min_spp /= 2;
+            }
+            ad.min_spp = min_spp; ad.threshold = threshold; ad.floor = 0.01f;
+            check(rt_render_adaptive(dev_scene, &f, &ad, fb.data(), /*fb_on_device=*/0, /*spp_out=*/nullptr, /*stream=*/nullptr, &stats),
+                  "rt_render_adaptive");
+            fprintf(stderr, "adaptive: spp %d..%d, mean %.2f, %d passes\n", ad.min_spp, ad.max_spp,
+                    (double)stats.samples / ((double)scene->nx * scene->ny), stats.reserved);
+        } else if (progressive > 0) {
             // progressive accumulation: the per-pixel XORWOW state and colour sum are carried from window to window (the
             // reference writes its curandState back for exactly this, main.cu:126); the last window's frame is the one-shot frame
             void* state = nullptr;

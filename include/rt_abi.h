@@ -291,6 +291,36 @@ rt_status rt_progressive_state_destroy(rt_scene* scene, void* state);
 rt_status rt_render_window(rt_scene* scene, const rt_frame_desc* f, float* fb, int fb_on_device, void* state,
                            int32_t sample_begin, int32_t sample_end, void* stream, int blocking, rt_stats* stats);
 
+/* ---- adaptive sampling: each pixel stops once its estimate converges ----
+ * rt_render_adaptive renders the pixels the frame description assigns to the call (row partition as rt_render; f->ns is
+ * ignored) with a per-pixel sample count n_i chosen at the checkpoints c_k = min_spp * 2^k, k = 0..K, where
+ * max_spp = min_spp * 2^K.  Parameters: min_spp even and >= 2; 0 <= K <= 16; threshold finite; floor finite and >= 0.
+ * At each checkpoint n < max_spp a pixel still active compares its linear average at n samples, a, with its linear average
+ * at n/2 samples, h -- each the float the frame would hold at ns = n (resp. n/2) with gamma 1: the colour sum times
+ * (float)(1.0 / (double)(float)n), per channel.  In double, left to right, from those floats:
+ *     d = |a.x - h.x| + |a.y - h.y| + |a.z - h.z|,   s = a.x + a.y + a.z,
+ *     converged  iff  threshold >= 0  and  d <= (double)threshold * (s + (double)floor)
+ * (a NaN in d never converges).  A pixel stops at its first converged checkpoint, otherwise at max_spp.
+ * Per pixel, with its final count n_i: fb holds what rt_render with ns = n_i and the frame's gamma writes for that pixel
+ * (each pixel is one chain seeded by seed_base + its index, so it is the same pixel); spp_out (optional, null = not written;
+ * the same kind of memory as fb, compact local rows of nx int32) holds n_i.  stats: rays = the sum of every pixel's rays at
+ * its n_i, samples = the sum of the n_i, ms_render = device time from the first pass to the last, reserved = render passes
+ * that had work.  So K = 0 gives rt_render at ns = min_spp, and threshold < 0 gives rt_render at ns = max_spp.
+ * Passes: [0, min/2) and [min/2, min) over every pixel, then [c_k, c_k+1) over the pixels still active; the call enqueues
+ * them on `stream`, reads back one active-pixel count between passes and returns when the frame is complete (a host fb /
+ * spp_out is copied back at the end).  A null scene, f, a or fb, a bad min_spp / max_spp, a non-finite threshold, a
+ * non-finite or negative floor, or a bad frame size or partition is RT_ERR_INVALID before any HIP call, and
+ * rt_last_error_detail() names the failed check.  The call is a frame of the scene: not re-entrant per scene; a pending
+ * non-blocking rt_render of the scene is finished first.  Option "adaptive_tier": -1 (auto) = a pass runs on the tier
+ * kernel when few pixels are active, 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit;
+ * none changes a pixel. */
+typedef struct rt_adaptive_desc {
+    int32_t min_spp, max_spp;
+    float threshold, floor;
+} rt_adaptive_desc; /* 16 B */
+rt_status rt_render_adaptive(rt_scene* scene, const rt_frame_desc* f, const rt_adaptive_desc* a, float* fb, int fb_on_device,
+                             int32_t* spp_out, void* stream, rt_stats* stats);
+
 /* ---- several GPUs of one node from one host thread ----
  * The reference is single-GPU (one render<<<>>> launch, main.cu:707); these entry points are what its host function
  * would call to spread that launch over the N GPUs of a node: rt_init_devices(N) replaces rt_init, rt_multi_create /
