@@ -49,7 +49,9 @@ enum { RT_PRIM_SPHERE = 0, RT_PRIM_QUAD = 1, RT_PRIM_BOX = 2, RT_PRIM_INSTANCE =
  * a node whose box is hit continues at index+1 (its left child) unless it is a
  * leaf; a node whose box is missed, and a finished leaf, continue at `skip`.
  * prim < 0: internal node.  Every object sits in its own leaf node whose box
- * is the object's box (the reference's n==1 node, bvh.cuh:38-43). */
+ * is the object's box (the reference's n==1 node, bvh.cuh:38-43).
+ * n_nodes == 0 is a legal description: an empty world, every ray misses and the
+ * frame is the background (one ray per sample). */
 typedef struct rt_node {
     float bmin[3];
     int32_t skip;

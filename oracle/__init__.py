@@ -33,10 +33,16 @@ def build() -> None:
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            build()
+        try:
+            build()          # make: a no-op when the library is newer than rt_oracle.cpp and include/rt_abi.h
+        except (RuntimeError, OSError):
+            if not os.path.exists(LIB_PATH):
+                raise        # (a read-only tree with a library already built is still usable)
         L = C.CDLL(LIB_PATH)
+        if not hasattr(L, "orc_scene_from_desc"):
+            raise RuntimeError(f"{LIB_PATH} is out of date and could not be rebuilt (make -C oracle)")
         L.orc_scene_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.orc_scene_from_desc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
         L.orc_scene_defaults.restype = C.c_float
         L.orc_scene_defaults.argtypes = [C.c_int, C.c_void_p]
         L.orc_render.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int,
@@ -69,6 +75,32 @@ class OracleScene:
         if self.h < 0:
             raise ValueError(f"oracle has no scene '{name}'")
         self.name, self.nx, self.ny = name, nx, ny
+        self._read_defaults()
+
+    @classmethod
+    def from_desc(cls, desc, nx: int, ny: int, gamma: float = 2.2, background=(0.0, 0.0, 0.0), gradient: int = 0, name: str = "desc"):
+        """orc_scene_from_desc: the oracle's object graph filled from an rt_scene_desc (a ctypes structure laid out as
+        include/rt_abi.h, e.g. HostScene.desc), copied.  nx, ny: the frame render() draws; gamma, background, gradient: what
+        the frame description carries.  trace() reports a material as its index in the description; nodes() numbers the
+        leaves by position.  ValueError when the description is refused (a bad index or kind, a non-binary interior node)."""
+        import ctypes
+        self = cls.__new__(cls)
+        self._img = None
+        bg = np.ascontiguousarray(background, np.float32)
+        self.h = lib().orc_scene_from_desc(ctypes.addressof(desc), bg.ctypes.data, int(gradient), float(gamma))
+        if self.h < 0:
+            raise ValueError("the oracle refuses this scene description")
+        self.name, self.nx, self.ny = name, nx, ny
+        self._read_defaults()
+        return self
+
+    @classmethod
+    def from_host(cls, hs, nx=None, ny=None):
+        """from_desc for anything with HostScene's surface: its description, frame size and frame defaults."""
+        return cls.from_desc(hs.desc, hs.nx if nx is None else nx, hs.ny if ny is None else ny, hs.gamma, hs.background,
+                             hs.use_gradient_bg, getattr(hs, "name", "desc"))
+
+    def _read_defaults(self):
         d = np.zeros(7, np.float32)
         self.gamma = float(lib().orc_scene_defaults(self.h, d.ctypes.data))
         self.def_nx, self.def_ny, self.def_ns, self.gradient = int(d[0]), int(d[1]), int(d[2]), int(d[3])

@@ -64,6 +64,8 @@
 #include <thread>
 #include <vector>
 
+#include "rt_abi.h"   // the public struct layout only (orc_scene_from_desc); nothing else of the product is included
+
 namespace {
 
 // ---------------------------------------------------------------- vec3
@@ -1148,6 +1150,130 @@ void scene_crowd_big(Scene& S, int nx, int ny) {
     S.gradient = 1; S.def_nx = 64; S.def_ny = 64; S.def_ns = 8;
 }
 
+// ---------------------------------------------------------------- scene from a description
+// orc_scene_from_desc: the object graph filled from the flat arrays of an rt_scene_desc (include/rt_abi.h), every value as
+// given -- nothing is derived again, so whatever built the description (the product's host library, a test's generator) is
+// checked as it stands.  One Obj per array entry (shared children stay shared), materials and textures one to one (so a
+// material's index here is its index in the description).  Only bvh nodes carry a box: bvh_hit is the one reader of bbox.
+struct DescBuilder {
+    Scene& S; const rt_scene_desc& d;
+    std::vector<Obj*> sph, quad, box, inst, med;
+    std::vector<Mat*> mat;
+    bool ok = true;
+    int leaves = 0;
+    DescBuilder(Scene& s, const rt_scene_desc& dd) : S(s), d(dd) {}
+
+    static V3 f3(const float* p) { return v3(p[0], p[1], p[2]); }
+    Obj* blank(ObjKind k) { auto o = new Obj; o->kind = k; o->bbox = box_empty(); o->c0 = o->vel = o->Q = o->eu = o->ev = o->w = o->normal = o->offset = v3(0, 0, 0); return S.add(o); }
+    const Mat* material(int i) { if (i < 0 || i >= d.n_materials) { ok = false; return nullptr; } return mat[(size_t)i]; }
+    // sphere, quad, box; with_instances: an instance too
+    const Obj* solid(int32_t ref, bool with_instances) {
+        if (ref < 0) { ok = false; return nullptr; }
+        const int k = RT_PRIM_KIND(ref), i = RT_PRIM_INDEX(ref);
+        if (k == RT_PRIM_SPHERE && i < d.n_spheres) return sph[(size_t)i];
+        if (k == RT_PRIM_QUAD && i < d.n_quads) return quad[(size_t)i];
+        if (k == RT_PRIM_BOX && i < d.n_boxes) return box[(size_t)i];
+        if (with_instances && k == RT_PRIM_INSTANCE && i < d.n_instances) return inst[(size_t)i];
+        ok = false; return nullptr;
+    }
+    void textures() {
+        for (int i = 0; i < d.n_textures; ++i) S.texs.emplace_back(new Tex);
+        for (int i = 0; i < d.n_textures; ++i) {
+            const rt_texture& t = d.textures[i];
+            Tex* x = S.texs[(size_t)i].get();
+            auto ref = [&](int k) -> const Tex* { if (k < 0 || k >= d.n_textures) { ok = false; return nullptr; } return S.texs[(size_t)k].get(); };
+            x->color = f3(t.color);
+            switch (t.kind) {
+            case RT_TEX_SOLID: x->kind = TEX_SOLID; break;
+            case RT_TEX_CHECKER: x->kind = TEX_CHECKER; x->inv_scale = t.scale; x->even = ref(t.a); x->odd = ref(t.b); break;
+            case RT_TEX_IMAGE:
+                x->kind = TEX_IMAGE;
+                if (t.a >= 0) {
+                    if (t.b <= 0 || t.c <= 0 || (size_t)t.a + (size_t)t.b * (size_t)t.c * 3 > S.image.size()) { ok = false; break; }
+                    x->img = S.image.data() + t.a; x->w = t.b; x->h = t.c;
+                }
+                break;
+            case RT_TEX_NOISE: x->kind = TEX_NOISE; x->scale = t.scale; break;
+            case RT_TEX_NOODLE: x->kind = TEX_NOODLE; x->k = t.scale; x->A = t.p[6]; x->f = t.p[7]; x->octaves = t.a; x->dir = f3(t.p + 3);
+                x->cN = f3(t.color); x->cG = f3(t.p); break;
+            case RT_TEX_FELT: x->kind = TEX_FELT; x->m_scale = t.scale; x->m_amt = t.p[0]; x->f_scale = t.p[1]; x->f_amt = t.p[2]; break;
+            case RT_TEX_UV_OFFSET: x->kind = TEX_UVOFF; x->base = ref(t.a); x->du = t.scale; x->dv = t.p[0]; break;
+            default: ok = false;
+            }
+        }
+    }
+    void materials() {
+        for (int i = 0; i < d.n_materials; ++i) {
+            const rt_material& m = d.materials[i];
+            auto x = new Mat; S.mats.emplace_back(x); mat.push_back(x);
+            if (m.kind < RT_MAT_LAMBERTIAN || m.kind > RT_MAT_ISOTROPIC || m.tex >= d.n_textures) { ok = false; continue; }
+            x->kind = (MatKind)m.kind; x->albedo = f3(m.albedo); x->fuzz = m.fuzz; x->ior = m.ior;
+            if (m.tex >= 0) x->tex = S.texs[(size_t)m.tex].get();
+            else if (m.kind == RT_MAT_LAMBERTIAN || m.kind == RT_MAT_ISOTROPIC) x->tex = S.tex_solid(x->albedo);   // (appended after the description's)
+        }
+    }
+    void objects() {
+        for (int i = 0; i < d.n_spheres; ++i) {
+            const rt_sphere& s = d.spheres[i];
+            Obj* o = blank(OBJ_SPHERE); o->c0 = f3(s.c0); o->vel = f3(s.vel); o->radius = s.radius; o->mat = material(s.mat);
+            sph.push_back(o);
+        }
+        for (int i = 0; i < d.n_quads; ++i) {
+            const rt_quad& q = d.quads[i];
+            Obj* o = blank(OBJ_QUAD); o->Q = f3(q.Q); o->eu = f3(q.u); o->ev = f3(q.v); o->w = f3(q.w); o->normal = f3(q.n); o->D = q.D;
+            o->mat = material(q.mat);
+            quad.push_back(o);
+        }
+        for (int i = 0; i < d.n_boxes; ++i) {
+            const int f = d.boxes[i].first_quad;
+            Obj* o = blank(OBJ_BOX6);
+            if (f < 0 || f + 6 > d.n_quads) ok = false;
+            else for (int k = 0; k < 6; ++k) o->face[k] = quad[(size_t)(f + k)];
+            box.push_back(o);
+        }
+        for (int i = 0; i < d.n_instances; ++i) {   // translate(rotate_y(child)), either half as `flags` says
+            const rt_instance& in = d.instances[i];
+            const Obj* c = solid(in.child, false);
+            if (in.flags & RT_INST_ROTATE_Y) { Obj* r = blank(OBJ_ROTY); r->child = c; r->sin_t = in.sin_t; r->cos_t = in.cos_t; c = r; }
+            if (in.flags & RT_INST_TRANSLATE) { Obj* t = blank(OBJ_TRANSLATE); t->child = c; t->offset = f3(in.offset); c = t; }
+            if (!(in.flags & (RT_INST_ROTATE_Y | RT_INST_TRANSLATE)) || (in.flags & ~3)) ok = false;
+            inst.push_back(const_cast<Obj*>(c));
+        }
+        for (int i = 0; i < d.n_media; ++i) {
+            const rt_medium& m = d.media[i];
+            Obj* o = blank(OBJ_MEDIUM); o->child = solid(m.boundary, true); o->neg_inv_density = m.neg_inv_density; o->mat = material(m.mat);
+            med.push_back(o);
+        }
+    }
+    // node i of the pre-order array and the index after its subtree; an interior node has exactly two children
+    const Obj* tree(int i, int depth) {
+        const int n = d.n_nodes;
+        if (i < 0 || i >= n || depth > 4096) { ok = false; return nullptr; }
+        const rt_node& nd = d.nodes[i];
+        if (nd.skip <= i || nd.skip > n) { ok = false; return nullptr; }
+        Obj* node = blank(OBJ_BVH);
+        node->bbox.lo = f3(nd.bmin); node->bbox.hi = f3(nd.bmax);
+        if (nd.prim >= 0) {
+            if (nd.skip != i + 1) { ok = false; return nullptr; }
+            const int k = RT_PRIM_KIND(nd.prim), idx = RT_PRIM_INDEX(nd.prim);
+            const Obj* o = (k == RT_PRIM_MEDIUM) ? (idx < d.n_media ? med[(size_t)idx] : nullptr) : solid(nd.prim, true);
+            if (!o) { ok = false; return nullptr; }
+            // the leaf's own record: an object shared by two leaves keeps one list position each
+            Obj* leaf = new Obj(*o); S.add(leaf); leaf->list_index = leaves++; S.list.push_back(leaf);
+            node->left = node->right = leaf;
+            return node;
+        }
+        const int c1 = i + 1;
+        if (c1 >= nd.skip) { ok = false; return nullptr; }
+        const int c2 = d.nodes[c1].skip;
+        if (c2 <= c1 || c2 >= nd.skip || d.nodes[c2].skip != nd.skip) { ok = false; return nullptr; }
+        node->left = tree(c1, depth + 1);
+        if (!ok) return nullptr;
+        node->right = tree(c2, depth + 1);
+        return ok ? node : nullptr;
+    }
+};
+
 // ---------------------------------------------------------------- render
 inline float apply_gamma(float c, float gamma) {                                    // main.cu:37-42
     if (gamma == 1.0f) return c;
@@ -1250,6 +1376,37 @@ int orc_scene_create(const char* name, int nx, int ny, const unsigned char* img,
     else if (n == "crowd_big") scene_crowd_big(*S, nx, ny);
     else return -1;
     for (auto& t : S->texs) if (t->kind == TEX_IMAGE && !S->image.empty()) { t->img = S->image.data(); t->w = iw; t->h = ih; }
+    g_scenes.push_back(std::move(S));
+    return (int)g_scenes.size() - 1;
+}
+
+// Build a scene from a description (include/rt_abi.h), copied: nothing of `d` is referenced afterwards.  What the frame adds
+// (the reference passes it to render<<<>>>): background, gradient, gamma -- the defaults OracleScene.render uses.  Returns a
+// handle >= 0, or -1: an index out of range, an unknown kind, or an interior node without exactly two children (bvh_hit is
+// binary, and which of two equal hits wins depends on that).  n_nodes == 0 is an empty world: every ray misses.
+int orc_scene_from_desc(const rt_scene_desc* d, const float* bg, int gradient, float gamma) {
+    if (!d || d->n_nodes < 0 || d->n_spheres < 0 || d->n_quads < 0 || d->n_boxes < 0 || d->n_instances < 0 || d->n_media < 0 ||
+        d->n_materials < 0 || d->n_textures < 0)
+        return -1;
+    auto S = std::make_unique<Scene>();
+    if (d->images && d->image_bytes) S->image.assign(d->images, d->images + d->image_bytes);
+    DescBuilder b(*S, *d);
+    b.textures();
+    if (b.ok) b.materials();
+    if (b.ok) b.objects();
+    if (!b.ok) return -1;
+    if (d->n_nodes == 0) S->world = S->build_bvh(0, 0);
+    else {
+        S->world = b.tree(0, 0);
+        if (!b.ok || !S->world || d->nodes[0].skip != d->n_nodes) return -1;
+    }
+    const rt_camera& c = d->camera;
+    S->cam.origin = DescBuilder::f3(c.origin); S->cam.llc = DescBuilder::f3(c.lower_left_corner);
+    S->cam.horizontal = DescBuilder::f3(c.horizontal); S->cam.vertical = DescBuilder::f3(c.vertical);
+    S->cam.u = DescBuilder::f3(c.u); S->cam.v = DescBuilder::f3(c.v); S->cam.w = v3(0, 0, 0);   // (w is not read after init())
+    S->cam.lens_radius = c.lens_radius; S->cam.time0 = c.time0; S->cam.time1 = c.time1;
+    if (bg) S->background = v3(bg[0], bg[1], bg[2]);
+    S->gradient = gradient; S->gamma = gamma;
     g_scenes.push_back(std::move(S));
     return (int)g_scenes.size() - 1;
 }
