@@ -72,6 +72,12 @@ class RtRayBatch(C.Structure):
                 ("normal_out", C.c_void_p), ("uv_out", C.c_void_p), ("mat_out", C.c_void_p), ("hit_out", C.c_void_p)]
 
 
+class RtRadianceBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("origins", C.c_void_p), ("directions", C.c_void_p), ("times", C.c_void_p), ("seeds", C.c_void_p),
+                ("seed_base", C.c_uint64), ("ns", C.c_int32), ("background", C.c_float * 3), ("use_gradient_bg", C.c_int32),
+                ("reserved", C.c_int32), ("rgb_out", C.c_void_p), ("rays_out", C.c_void_p)]
+
+
 class RtAdaptiveDesc(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
 
@@ -91,6 +97,8 @@ def prim_index(ref):
 
 # DeviceScene.trace(): closest hit -- the record fields are None unless record=True
 TraceResult = collections.namedtuple("TraceResult", "t prim inst point normal uv mat")
+# DeviceScene.radiance(): rays is None unless count_rays=True
+RadianceResult = collections.namedtuple("RadianceResult", "rgb rays")
 
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("skip", "<i4"), ("bmax", "<f4", 3), ("prim", "<i4")])
 SPHERE_DTYPE = np.dtype([("c0", "<f4", 3), ("radius", "<f4"), ("vel", "<f4", 3), ("mat", "<i4")])
@@ -106,7 +114,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_set_option", "rt_reset_options", "rt_scene_walk_info", "rt_init_devices", "rt_multi_create", "rt_multi_render",
                   "rt_multi_destroy", "rt_multi_device_count", "rt_multi_row_owner", "rt_multi_probe_rccl", "rt_multi_debug_uninterleave",
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
-                  "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive"]
+                  "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive",
+                  "rt_radiance_rays"]
 
 _rt = None
 _host = None
@@ -179,6 +188,7 @@ def rt_lib():
         L.rt_regroup_leaves.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.rt_regroup_leaves.restype = C.c_int
         L.rt_trace_rays.argtypes = [C.c_void_p, C.POINTER(RtRayBatch), C.c_void_p, C.c_int]
+        L.rt_radiance_rays.argtypes = [C.c_void_p, C.POINTER(RtRadianceBatch), C.c_void_p, C.c_int]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAdaptiveDesc), C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.POINTER(RtStats)]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -435,6 +445,94 @@ class DeviceScene:
             return h.view(np.bool_) if on_host else h.view(torch.bool)
         return TraceResult(outs["t_out"], outs["prim_out"], outs["inst_out"], outs.get("point_out"), outs.get("normal_out"),
                            outs.get("uv_out"), outs.get("mat_out"))
+
+    def radiance(self, origins, directions, times=None, ns: int = 1, seeds=None, seed_base: int = 1984, background=None, gradient=None,
+                 count_rays: bool = False, stream=None):
+        """Radiance queries (rt_radiance_rays): the path-traced colour along every ray, `ns` samples each -- per ray what
+        rt_render writes, at gamma 1, for the one pixel of a camera that sends every sample along that ray (include/rt_abi.h).
+
+        origins, directions: (N, 3) float32; times: (N,) float32 or None (0 for every ray); seeds: (N,) int64 or uint64 (the
+        bits are the seed) or None (seed_base + i).  background: three floats, gradient: bool; None = the host scene's.
+        Tensors or numpy arrays, streams and waiting as in trace().  Returns a RadianceResult (rgb: (N, 3) float32; rays: (N,)
+        int32 holding each query's ray count, only with count_rays=True).  Malformed input raises ValueError before anything
+        is launched.  A ray with a NaN or infinite component in its origin, direction or time, or with a zero direction,
+        gets zeros and 0 rays."""
+        import torch
+        on_host = isinstance(origins, np.ndarray)
+        dev = torch.device("cuda", self.device)
+        if not on_host and not isinstance(origins, torch.Tensor):
+            raise ValueError("origins: a numpy array or a torch tensor is expected")
+        if origins.ndim != 2 or origins.shape[1] != 3:
+            raise ValueError(f"origins: shape {tuple(origins.shape)}, expected (N, 3)")
+        n = int(origins.shape[0])
+        if directions is None:
+            raise ValueError("directions are required")
+
+        def prep(x, name, cols, np_types, torch_types):
+            if x is None:
+                return None
+            if on_host:
+                if not isinstance(x, np.ndarray):
+                    raise ValueError(f"{name}: a numpy array is expected (origins is one)")
+                if x.dtype not in np_types:
+                    raise ValueError(f"{name}: {' or '.join(np.dtype(t).name for t in np_types)} expected, got {x.dtype}")
+            else:
+                if not isinstance(x, torch.Tensor):
+                    raise ValueError(f"{name}: a torch tensor is expected (origins is one)")
+                if x.dtype not in torch_types:
+                    raise ValueError(f"{name}: {' or '.join(str(t) for t in torch_types)} expected, got {x.dtype}")
+                if x.device != dev:
+                    raise ValueError(f"{name}: tensor on {x.device}, the scene is on {dev}")
+            want = (n, 3) if cols == 3 else (n,)
+            if tuple(x.shape) != want:
+                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {want}")
+            return x
+
+        f32, t32 = (np.dtype(np.float32),), (torch.float32,)
+        i64, t64 = (np.dtype(np.int64), np.dtype(np.uint64)), (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
+        if isinstance(ns, bool) or not isinstance(ns, (int, np.integer)) or not 1 <= int(ns) <= 1 << 20:
+            raise ValueError("ns must be an integer in 1 .. 1 << 20")
+        if isinstance(seed_base, bool) or not isinstance(seed_base, (int, np.integer)) or not 0 <= int(seed_base) < 1 << 64:
+            raise ValueError("seed_base must be an integer in 0 .. 2**64 - 1")
+        bg = self.host.background if background is None else [float(x) for x in np.asarray(background, np.float64).reshape(-1)]
+        if len(bg) != 3:
+            raise ValueError("background: three floats are expected")
+        gradient = self.host.use_gradient_bg if gradient is None else gradient
+        ins = [prep(origins, "origins", 3, f32, t32), prep(directions, "directions", 3, f32, t32), prep(times, "times", 1, f32, t32),
+               prep(seeds, "seeds", 1, i64, t64)]
+        if on_host:   # (torch has no uint64 arithmetic to speak of: the seeds travel as their int64 bits)
+            ins = [None if x is None else torch.from_numpy(np.ascontiguousarray(x).view(np.int64) if x.dtype == np.uint64 else np.ascontiguousarray(x)).to(dev)
+                   for x in ins]
+        else:
+            ins = [None if x is None else x.contiguous() for x in ins]
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        outs = {"rgb_out": torch.empty((n, 3), dtype=torch.float32, device=dev)}
+        if count_rays:
+            outs["rays_out"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        if n > 0:
+            b = RtRadianceBatch()
+            b.n = n
+            b.origins, b.directions, b.times, b.seeds = (None if x is None else x.data_ptr() for x in ins)
+            b.seed_base, b.ns = int(seed_base), int(ns)
+            b.background[:] = bg
+            b.use_gradient_bg = 1 if gradient else 0
+            for k, v in outs.items():
+                setattr(b, k, v.data_ptr())
+            current = torch.cuda.current_stream(dev)
+            if stream != current:   # as in trace(): `stream` waits for the copies and buffers made on the current stream
+                stream.wait_stream(current)
+                for x in ins + list(outs.values()):
+                    if x is not None:
+                        x.record_stream(stream)
+            st = rt_lib().rt_radiance_rays(self._p, C.byref(b), C.c_void_p(stream.cuda_stream), 0)
+            if st == 1:
+                raise ValueError(rt_lib().rt_last_error_detail().decode())
+            _check(st, "rt_radiance_rays")
+        if on_host:
+            stream.synchronize()
+            outs = {k: v.cpu().numpy() for k, v in outs.items()}
+        return RadianceResult(outs["rgb_out"], outs.get("rays_out"))
 
     def render_adaptive(self, frame: RtFrameDesc, min_spp: int, max_spp: int, threshold: float, floor: float = 0.01, out=None,
                         spp_out=None, stream=0):

@@ -87,6 +87,7 @@ struct rt_options {
     int lpt = 1;                 // cost prepass + longest-first tile order (staged kernel, ns >= 2 * split_samples)
     int trace_lds = -1;          // rt_trace_rays: -1 = auto, 0 = scene through L1/L2, 1 = nodes in LDS, 2 = nodes and spheres in LDS
     int trace_tree = 1;          // rt_trace_rays: 1 = the walk array, 0 = the reference's full tree
+    int radiance_lds = -1;       // rt_radiance_rays: as trace_lds
     int adaptive_tier = -1;      // rt_render_adaptive: -1 = a pass goes to the tier kernel when its active pixels fit the tier waves at once
                                  // (DESIGN.md 4.8), 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit
 };
@@ -665,6 +666,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "steps_per_trip") { if (value < 1 || value > 64) return invalid("steps_per_trip: 1..64"); g_opt.steps_per_trip = value; }
     else if (k == "shade_threshold") { if (value < 0 || value > 64) return invalid("shade_threshold: 0 (by the launch's load) or 1..64"); g_opt.shade_threshold = value; }
     else if (k == "trace_lds") { if (value < -1 || value > 2) return invalid("trace_lds: -1 (auto) .. 2"); g_opt.trace_lds = value; }
+    else if (k == "radiance_lds") { if (value < -1 || value > 2) return invalid("radiance_lds: -1 (auto) .. 2"); g_opt.radiance_lds = value; }
     else if (k == "trace_tree") { if (value < 0 || value > 1) return invalid("trace_tree: 0 (reference tree) or 1 (walk array)"); g_opt.trace_tree = value; }
     else if (k == "adaptive_tier") { if (value < -1 || value > 1) return invalid("adaptive_tier: -1 (auto), 0 (main kernel) or 1 (tier kernel)"); g_opt.adaptive_tier = value; }
     else if (k == "wg_per_cu") { if (value < 0 || value > 8) return invalid("wg_per_cu: 0 (per kernel family) .. 8"); g_opt.wg_per_cu = value; }
@@ -1168,31 +1170,32 @@ rt_status rt_frame_finish(rt_scene* s, rt_stats* stats) {
 }
 
 namespace {
-// a pointer rt_trace_rays hands to a kernel: null, or `bytes` of device (or managed) memory of `device`, 4-byte aligned
-static rt_status check_trace_ptr(const void* p, size_t bytes, int device, const char* what) {
+// a pointer rt_trace_rays / rt_radiance_rays (`who`) hands to a kernel: null, or `bytes` of device (or managed) memory of
+// `device`, aligned to `align` bytes
+static rt_status check_trace_ptr(const void* p, size_t bytes, int device, const char* what, const char* who = "rt_trace_rays", unsigned align = 4) {
     if (!p) return RT_OK;
     std::string why;
-    if (reinterpret_cast<uintptr_t>(p) & 3u) { why = std::string("rt_trace_rays: ") + what + " is not 4-byte aligned"; return invalid(why.c_str()); }
+    if (reinterpret_cast<uintptr_t>(p) & (align - 1u)) { why = std::string(who) + ": " + what + " is not " + std::to_string(align) + "-byte aligned"; return invalid(why.c_str()); }
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof(a));
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
-        why = std::string("rt_trace_rays: ") + what + " is not device memory (unregistered pointer)";
+        why = std::string(who) + ": " + what + " is not device memory (unregistered pointer)";
         return invalid(why.c_str());
     }
     if (a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged) {
-        why = std::string("rt_trace_rays: ") + what + " is not device memory";
+        why = std::string(who) + ": " + what + " is not device memory";
         return invalid(why.c_str());
     }
     if (a.type == hipMemoryTypeDevice && a.device != device) {
-        why = std::string("rt_trace_rays: ") + what + " is memory of another device";
+        why = std::string(who) + ": " + what + " is memory of another device";
         return invalid(why.c_str());
     }
     void* base = nullptr;
     size_t size = 0;
     if (a.type == hipMemoryTypeDevice && hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) == hipSuccess) {
         if (static_cast<const char*>(p) + bytes > static_cast<const char*>(base) + size) {
-            why = std::string("rt_trace_rays: ") + what + " is shorter than the batch";
+            why = std::string(who) + ": " + what + " is shorter than the batch";
             return invalid(why.c_str());
         }
     } else {
@@ -1242,6 +1245,7 @@ rt_status rt_trace_rays(rt_scene* s, const rt_ray_batch* b, void* stream_v, int 
     rt_scene_dev sd = s->dev;
     if (g_opt.trace_tree == 0) { sd.nodes = sd.nodes_ref; sd.n_nodes = sd.n_nodes_ref; }
     const size_t node_bytes = (size_t)sd.n_nodes * sizeof(rt_node);
+    // (rt_radiance_rays below carries a twin of this block)
     // LDS residency: the modes whose image fits a CU (nodes + spheres, nodes only, none); a forced mode that does not fit
     // falls back to the largest that does.  Auto takes the largest mode that keeps at least 3/4 of the workgroups per CU
     // that mode 0 gets: the walk is latency-bound, and an image that costs residency costs more than it saves -- one
@@ -1270,6 +1274,62 @@ rt_status rt_trace_rays(rt_scene* s, const rt_ray_batch* b, void* stream_v, int 
     const dim3 grid((unsigned)std::min(want, need));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     HIPCHK(rt_launch_trace(s->spheres_only, lds_mode, sd, tp, grid, lds, stream));
+    if (blocking) HIPCHK(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+rt_status rt_radiance_rays(rt_scene* s, const rt_radiance_batch* b, void* stream_v, int blocking) {
+    // argument checks: no HIP call and no look at the scene before they pass
+    if (!b) return invalid("rt_radiance_rays: null batch");
+    if (b->n < 0) return invalid("rt_radiance_rays: negative ray count");
+    if (b->ns < 1 || b->ns > (1 << 20)) return invalid("rt_radiance_rays: ns outside 1 .. 1 << 20");
+    if (!b->origins || !b->directions) return invalid("rt_radiance_rays: null origins or directions");
+    if (!b->rgb_out) return invalid("rt_radiance_rays: null rgb_out");
+    if (!s) return invalid("rt_radiance_rays: null scene");
+    if (b->n == 0) return RT_OK;
+    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    const size_t n = (size_t)b->n, f = sizeof(float);
+    const struct { const void* p; size_t bytes; const char* what; unsigned align; } ptrs[] = {
+        {b->origins, 3 * n * f, "origins", 4}, {b->directions, 3 * n * f, "directions", 4}, {b->times, n * f, "times", 4},
+        {b->seeds, n * sizeof(uint64_t), "seeds", 8}, {b->rgb_out, 3 * n * f, "rgb_out", 4}, {b->rays_out, n * sizeof(uint32_t), "rays_out", 4}};
+    for (const auto& q : ptrs) {
+        const rt_status st = check_trace_ptr(q.p, q.bytes, s->device, q.what, "rt_radiance_rays", q.align);
+        if (st != RT_OK) return st;
+    }
+
+    rt_radiance_params rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.n = b->n; rp.origins = b->origins; rp.directions = b->directions; rp.times = b->times; rp.seeds = b->seeds;
+    rp.seed_base = b->seed_base; rp.ns = b->ns; rp.use_gradient_bg = b->use_gradient_bg;
+    for (int k = 0; k < 3; ++k) rp.background[k] = b->background[k];
+    rp.rgb_out = b->rgb_out; rp.rays_out = b->rays_out;
+
+    // Twin of the block in rt_trace_rays above (other occupancy query, other option): a change to one belongs in the other.
+    // LDS residency and the persistent grid: rt_trace_rays' rule (the walk array; auto = the largest image that keeps at least
+    // 3/4 of the workgroups per CU that the scene-through-L1/L2 mode gets)
+    const rt_scene_dev& sd = s->dev;
+    const size_t node_bytes = (size_t)sd.n_nodes * sizeof(rt_node);
+    const size_t budget = g_devices[s->device].lds_per_cu - 2048;
+    const int fit = node_bytes + s->sphere_bytes <= budget ? 2 : (node_bytes <= budget ? 1 : 0);
+    auto lds_of = [&](int m) -> size_t { return m == 2 ? node_bytes + s->sphere_bytes : (m == 1 ? node_bytes : 0); };
+    int lds_mode = g_opt.radiance_lds < 0 ? fit : std::min(g_opt.radiance_lds, fit);
+    int per_cu = 0;
+    HIPCHK(rt_radiance_occupancy(s->spheres_only, s->tex_level, lds_mode, lds_of(lds_mode), &per_cu));
+    if (g_opt.radiance_lds < 0 && lds_mode > 0) {
+        int per_cu0 = 0;
+        HIPCHK(rt_radiance_occupancy(s->spheres_only, s->tex_level, 0, 0, &per_cu0));
+        while (lds_mode > 0 && 4 * per_cu < 3 * per_cu0) {
+            --lds_mode;
+            HIPCHK(rt_radiance_occupancy(s->spheres_only, s->tex_level, lds_mode, lds_of(lds_mode), &per_cu));
+        }
+    }
+    const size_t lds = lds_of(lds_mode);
+    if (per_cu < 1) per_cu = 1;
+    const long long want = (long long)g_devices[s->device].num_cu * per_cu;
+    const long long need = (b->n + RT_RADIANCE_THREADS - 1) / RT_RADIANCE_THREADS;
+    const dim3 grid((unsigned)std::min(want, need));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    HIPCHK(rt_launch_radiance(s->spheres_only, s->tex_level, lds_mode, sd, rp, grid, lds, stream));
     if (blocking) HIPCHK(hipStreamSynchronize(stream));
     return RT_OK;
 }

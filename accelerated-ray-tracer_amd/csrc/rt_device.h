@@ -243,6 +243,27 @@ hipError_t rt_launch_trace(bool spheres_only, int lds_mode, const rt_scene_dev& 
                            hipStream_t st);
 hipError_t rt_trace_occupancy(bool spheres_only, int lds_mode, bool any, bool record, size_t lds, int* blocks_per_cu);
 
+// rt_radiance_rays (rt_kernel_radiance.hip): one batch of caller rays to shade, the pointers already checked on the host
+struct rt_radiance_params {
+    int64_t n;
+    const float* origins;
+    const float* directions;
+    const float* times;       // null = 0
+    const uint64_t* seeds;    // null = seed_base + i
+    uint64_t seed_base;
+    int32_t ns;
+    int32_t use_gradient_bg;
+    float background[3];
+    float* rgb_out;
+    uint32_t* rays_out;       // null = not written
+};
+// sd.nodes / sd.n_nodes: the walk array; tex_level as rt_launch_pixel; lds_mode 0..2 as stage_scene; grid = persistent
+// workgroups of RT_RADIANCE_THREADS.  rt_radiance_occupancy: workgroups per CU of the instantiation such a launch would use.
+#define RT_RADIANCE_THREADS 256
+hipError_t rt_launch_radiance(bool spheres_only, int tex_level, int lds_mode, const rt_scene_dev& sd, const rt_radiance_params& rp,
+                              dim3 grid, size_t lds, hipStream_t st);
+hipError_t rt_radiance_occupancy(bool spheres_only, int tex_level, int lds_mode, size_t lds, int* blocks_per_cu);
+
 // rt_render_adaptive (rt_kernel_adaptive.hip): after each pass, one lane per pixel of that pass decides whether the pixel has
 // converged at checkpoint n (include/rt_abi.h), writes the converged ones to fb / spp and appends the others -- wave-aggregated
 // -- to list_out (local pixel ids, the main kernel's pixel list) and queue_out ((n << 32) | pixel, the tier kernel's tail queue).

@@ -279,6 +279,47 @@ typedef struct rt_ray_batch {
 } rt_ray_batch;
 rt_status rt_trace_rays(rt_scene* scene, const rt_ray_batch* batch, void* stream, int blocking);
 
+/* ---- radiance queries: path-traced colour along caller-supplied rays ----
+ * The renderer's color() loop (main.cu:52-94: bounces, materials, textures, media, the 50-bounce cut) for rays the caller
+ * chose instead of the one thin-lens camera of rt_scene_desc: panoramic or orthographic views, light probes, lightmap texels.
+ *
+ * Contract per ray i, with seed_i = seeds[i] (seeds null: seed_base + i): rgb_out[i] is bit for bit what rt_render writes for
+ * the single pixel of a 1 x 1 frame with `ns` samples, gamma 1, the batch's background and seed_base = seed_i, of a scene
+ * whose camera is the degenerate one that sends every sample along this ray -- horizontal = vertical = 0, lens_radius = 0,
+ * origin = o, time0 = time1 = tm and lower_left_corner chosen so that fl(lower_left_corner - o) = d -- and rays_out[i] is
+ * that frame's ray count (world->hit calls).  Spelled out: one XORWOW chain is seeded with seed_i; each of the ns samples
+ * first draws and discards what a render sample draws before its path (two jitter uniforms, the lens-disk rejection loop at
+ * two uniforms per turn, one shutter uniform), then runs color() on (o, d, tm); the sum is scaled as the frame's pixel is, by
+ * (float)(1.0 / (double)(float)ns).  The camera draws are kept although they select nothing: they make a query equal to a
+ * pixel of rt_render, and that identity is what makes every query checkable against the renderer and its CPU oracle.
+ * A ray with a NaN or infinite component in its origin, direction or time, or with an all-zero direction, gets rgb = 0 and
+ * rays = 0; it is decided before the walk and consumes no draws.
+ *
+ * Pointers, arguments, stream and shared state: the contract of rt_trace_rays.  Every pointer is device (or managed) memory
+ * of the scene's device, 4-byte aligned (seeds: 8-byte), checked with hipPointerGetAttributes before anything is launched.
+ * A null scene or batch, n < 0, ns outside [1, 1 << 20] or a missing required pointer (origins, directions, rgb_out) is
+ * RT_ERR_INVALID; these checks run before any HIP call and before the scene is looked at, and rt_last_error_detail() names
+ * the one that failed.  The work is enqueued on `stream`; with `blocking` != 0 the call returns when every output is
+ * written.  The call touches none of rt_render's per-frame resources, so it may run beside a pending non-blocking
+ * rt_render of the same scene.  Option "radiance_lds": -1 = auto ("trace_lds"'s rule), 0 = scene through L1/L2, 1 = nodes
+ * in LDS, 2 = nodes and spheres in LDS (a forced mode that does not fit falls back to the largest that does); it changes
+ * no result. */
+typedef struct rt_radiance_batch {
+    int64_t n;                 /* rays; 0 is a no-op */
+    const float* origins;      /* n*3, required */
+    const float* directions;   /* n*3, required; not normalised */
+    const float* times;        /* n, null = 0 for every ray */
+    const uint64_t* seeds;     /* n, null = seed_base + i */
+    uint64_t seed_base;
+    int32_t ns;                /* samples per ray, 1 <= ns <= 1 << 20 */
+    float background[3];       /* the miss term, as rt_frame_desc */
+    int32_t use_gradient_bg;
+    int32_t reserved;
+    float* rgb_out;            /* n*3, required */
+    uint32_t* rays_out;        /* n, optional (null = not written): the world->hit calls of each query */
+} rt_radiance_batch; /* 88 B */
+rt_status rt_radiance_rays(rt_scene* scene, const rt_radiance_batch* batch, void* stream, int blocking);
+
 /* ---- progressive accumulation (the reference writes every pixel's curandState back at the end of render(),
  * main.cu:126, which is what would allow it and what nothing in the reference uses) ----
  * rt_render_window renders samples [sample_begin, sample_end) of every pixel the frame description assigns to the call,
