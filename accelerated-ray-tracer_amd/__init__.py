@@ -78,6 +78,11 @@ class RtRadianceBatch(C.Structure):
                 ("reserved", C.c_int32), ("rgb_out", C.c_void_p), ("rays_out", C.c_void_p)]
 
 
+class RtAovDesc(C.Structure):
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p),
+                ("prim", C.c_void_p), ("inst", C.c_void_p), ("mat", C.c_void_p)]
+
+
 class RtAdaptiveDesc(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
 
@@ -97,6 +102,9 @@ def prim_index(ref):
 
 # DeviceScene.trace(): closest hit -- the record fields are None unless record=True
 TraceResult = collections.namedtuple("TraceResult", "t prim inst point normal uv mat")
+# DeviceScene.render_aov(): the outputs of rt_render_aov -> (channels, numpy dtype)
+AOV_OUTPUTS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "alpha": (1, np.float32),
+               "prim": (1, np.int32), "inst": (1, np.int32), "mat": (1, np.int32)}
 # DeviceScene.radiance(): rays is None unless count_rays=True
 RadianceResult = collections.namedtuple("RadianceResult", "rgb rays")
 
@@ -115,7 +123,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_multi_destroy", "rt_multi_device_count", "rt_multi_row_owner", "rt_multi_probe_rccl", "rt_multi_debug_uninterleave",
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
                   "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive",
-                  "rt_radiance_rays"]
+                  "rt_radiance_rays", "rt_render_aov"]
 
 _rt = None
 _host = None
@@ -189,6 +197,7 @@ def rt_lib():
         L.rt_regroup_leaves.restype = C.c_int
         L.rt_trace_rays.argtypes = [C.c_void_p, C.POINTER(RtRayBatch), C.c_void_p, C.c_int]
         L.rt_radiance_rays.argtypes = [C.c_void_p, C.POINTER(RtRadianceBatch), C.c_void_p, C.c_int]
+        L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAovDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAdaptiveDesc), C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.POINTER(RtStats)]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -533,6 +542,55 @@ class DeviceScene:
             stream.synchronize()
             outs = {k: v.cpu().numpy() for k, v in outs.items()}
         return RadianceResult(outs["rgb_out"], outs.get("rays_out"))
+
+    def render_aov(self, frame: RtFrameDesc, albedo: bool = True, normal: bool = True, depth: bool = True, alpha: bool = True,
+                   ids: bool = False, out=None, stream=0, blocking: bool = True) -> dict:
+        """Feature buffers of `frame` (rt_render_aov): per pixel the albedo, normal, depth (the ray parameter t) and coverage
+        of the primary rays' first hits, averaged over the frame's ns samples, and with ids=True the first sample's prim,
+        inst and mat (-1 on a miss) -- what a denoiser or a compositor wants beside a noisy frame (include/rt_abi.h).
+
+        out=None: a dict of numpy arrays for the selected outputs, rows x nx (x 3), float32 (ids: int32); the call waits.
+        out = a dict whose keys are output names (AOV_OUTPUTS): those outputs are written in place and the flags are not
+        looked at -- all numpy arrays (the call waits), or all contiguous torch tensors on this scene's device, zero-copy,
+        enqueued on `stream` (a hipStream_t as an integer or a torch.cuda.Stream) and waited for only with blocking=True.
+        Returns the dict.  Malformed arguments raise ValueError before anything is launched."""
+        L = rt_lib()
+        rows = L.rt_frame_local_rows(C.byref(frame))
+        if frame.nx <= 0 or frame.ny <= 0 or frame.ns <= 0 or rows < 0:
+            raise ValueError("bad frame size, sample count or row partition")
+        if out is None:
+            names = [k for k, on in (("albedo", albedo), ("normal", normal), ("depth", depth), ("alpha", alpha)) if on]
+            names += ["prim", "inst", "mat"] if ids else []
+            out = {k: np.empty((rows, frame.nx, 3) if AOV_OUTPUTS[k][0] == 3 else (rows, frame.nx), AOV_OUTPUTS[k][1]) for k in names}
+        if not isinstance(out, dict) or not out:
+            raise ValueError("no output is requested")
+        on_host = all(isinstance(v, np.ndarray) for v in out.values())
+        a = RtAovDesc()
+        for k, v in out.items():
+            if k not in AOV_OUTPUTS:
+                raise ValueError(f"unknown output '{k}': one of {', '.join(AOV_OUTPUTS)} is expected")
+            ch, dtype = AOV_OUTPUTS[k]
+            size = rows * frame.nx * ch
+            if on_host:
+                if v.dtype != dtype or v.size != size or not v.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"{k}: a C-contiguous {np.dtype(dtype).name} array of {size} elements is expected")
+                setattr(a, k, v.ctypes.data)
+            else:
+                import torch
+                want = torch.float32 if dtype == np.float32 else torch.int32
+                if not isinstance(v, torch.Tensor):
+                    raise ValueError("out: all numpy arrays or all torch tensors are expected")
+                if v.dtype != want or v.numel() != size or not v.is_contiguous() or v.device != torch.device("cuda", self.device):
+                    raise ValueError(f"{k}: a contiguous {want} tensor of {size} elements on cuda:{self.device} is expected")
+                setattr(a, k, v.data_ptr())
+        if hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        st = L.rt_render_aov(self._p, C.byref(frame), C.byref(a), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None,
+                             1 if blocking else 0)
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_render_aov")
+        return out
 
     def render_adaptive(self, frame: RtFrameDesc, min_spp: int, max_spp: int, threshold: float, floor: float = 0.01, out=None,
                         spp_out=None, stream=0):

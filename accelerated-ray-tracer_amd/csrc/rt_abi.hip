@@ -11,6 +11,7 @@
 #include <cfloat>
 #include <utility>
 #include <cmath>
+#include <functional>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -88,6 +89,7 @@ struct rt_options {
     int trace_lds = -1;          // rt_trace_rays: -1 = auto, 0 = scene through L1/L2, 1 = nodes in LDS, 2 = nodes and spheres in LDS
     int trace_tree = 1;          // rt_trace_rays: 1 = the walk array, 0 = the reference's full tree
     int radiance_lds = -1;       // rt_radiance_rays: as trace_lds
+    int aov_lds = -1;            // rt_render_aov: as trace_lds
     int adaptive_tier = -1;      // rt_render_adaptive: -1 = a pass goes to the tier kernel when its active pixels fit the tier waves at once
                                  // (DESIGN.md 4.8), 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit
 };
@@ -667,6 +669,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "shade_threshold") { if (value < 0 || value > 64) return invalid("shade_threshold: 0 (by the launch's load) or 1..64"); g_opt.shade_threshold = value; }
     else if (k == "trace_lds") { if (value < -1 || value > 2) return invalid("trace_lds: -1 (auto) .. 2"); g_opt.trace_lds = value; }
     else if (k == "radiance_lds") { if (value < -1 || value > 2) return invalid("radiance_lds: -1 (auto) .. 2"); g_opt.radiance_lds = value; }
+    else if (k == "aov_lds") { if (value < -1 || value > 2) return invalid("aov_lds: -1 (auto) .. 2"); g_opt.aov_lds = value; }
     else if (k == "trace_tree") { if (value < 0 || value > 1) return invalid("trace_tree: 0 (reference tree) or 1 (walk array)"); g_opt.trace_tree = value; }
     else if (k == "adaptive_tier") { if (value < -1 || value > 1) return invalid("adaptive_tier: -1 (auto), 0 (main kernel) or 1 (tier kernel)"); g_opt.adaptive_tier = value; }
     else if (k == "wg_per_cu") { if (value < 0 || value > 8) return invalid("wg_per_cu: 0 (per kernel family) .. 8"); g_opt.wg_per_cu = value; }
@@ -1203,6 +1206,39 @@ static rt_status check_trace_ptr(const void* p, size_t bytes, int device, const 
     }
     return RT_OK;
 }
+
+// LDS residency and the persistent grid of the one-item-per-lane kernels (rt_trace_rays, rt_radiance_rays, rt_render_aov) for a
+// node array of `node_bytes`: the modes whose image fits a CU (2 = nodes + spheres, 1 = nodes only, 0 = none); a forced mode
+// (`option` >= 0) that does not fit falls back to the largest that does.  Auto (`option` < 0) takes the largest mode that keeps
+// at least 3/4 of the workgroups per CU that mode 0 gets: the walk is latency-bound, and an image that costs residency costs
+// more than it saves -- one workgroup per CU for the Book-2 final scene's nodes ran at 0.6 instead of 1.4 Grays/s; the headline
+// scene's nodes (7 of 8 workgroups) were 1-8 % faster than mode 0 (profiles/trace_bench_mi355x.jsonl).
+// occupancy(mode, lds bytes, &workgroups per CU) asks the kernel that would be launched.  The grid holds as many workgroups
+// as are resident at once (registers and LDS), never more than `need`.
+struct resident_plan { int lds_mode; size_t lds; dim3 grid; };
+rt_status plan_resident(const rt_scene* s, size_t node_bytes, int option, long long need,
+                        const std::function<hipError_t(int, size_t, int*)>& occupancy, resident_plan& plan) {
+    const size_t budget = g_devices[s->device].lds_per_cu - 2048;
+    const int fit = node_bytes + s->sphere_bytes <= budget ? 2 : (node_bytes <= budget ? 1 : 0);
+    auto lds_of = [&](int m) -> size_t { return m == 2 ? node_bytes + s->sphere_bytes : (m == 1 ? node_bytes : 0); };
+    int lds_mode = option < 0 ? fit : std::min(option, fit);
+    int per_cu = 0;
+    HIPCHK(occupancy(lds_mode, lds_of(lds_mode), &per_cu));
+    if (option < 0 && lds_mode > 0) {
+        int per_cu0 = 0;
+        HIPCHK(occupancy(0, (size_t)0, &per_cu0));
+        while (lds_mode > 0 && 4 * per_cu < 3 * per_cu0) {
+            --lds_mode;
+            HIPCHK(occupancy(lds_mode, lds_of(lds_mode), &per_cu));
+        }
+    }
+    if (per_cu < 1) per_cu = 1;
+    const long long want = (long long)g_devices[s->device].num_cu * per_cu;
+    plan.lds_mode = lds_mode;
+    plan.lds = lds_of(lds_mode);
+    plan.grid = dim3((unsigned)std::min(want, need));
+    return RT_OK;
+}
 }  // namespace
 
 rt_status rt_trace_rays(rt_scene* s, const rt_ray_batch* b, void* stream_v, int blocking) {
@@ -1244,36 +1280,15 @@ rt_status rt_trace_rays(rt_scene* s, const rt_ray_batch* b, void* stream_v, int 
     // the node array: the walk array (the render's) or the reference's full tree; both carry the same leaves
     rt_scene_dev sd = s->dev;
     if (g_opt.trace_tree == 0) { sd.nodes = sd.nodes_ref; sd.n_nodes = sd.n_nodes_ref; }
-    const size_t node_bytes = (size_t)sd.n_nodes * sizeof(rt_node);
-    // (rt_radiance_rays below carries a twin of this block)
-    // LDS residency: the modes whose image fits a CU (nodes + spheres, nodes only, none); a forced mode that does not fit
-    // falls back to the largest that does.  Auto takes the largest mode that keeps at least 3/4 of the workgroups per CU
-    // that mode 0 gets: the walk is latency-bound, and an image that costs residency costs more than it saves -- one
-    // workgroup per CU for the Book-2 final scene's nodes ran at 0.6 instead of 1.4 Grays/s; the headline scene's nodes (7 of
-    // 8 workgroups) were 1-8 % faster than mode 0 (profiles/trace_bench_mi355x.jsonl)
-    const size_t budget = g_devices[s->device].lds_per_cu - 2048;
-    const int fit = node_bytes + s->sphere_bytes <= budget ? 2 : (node_bytes <= budget ? 1 : 0);
-    auto lds_of = [&](int m) -> size_t { return m == 2 ? node_bytes + s->sphere_bytes : (m == 1 ? node_bytes : 0); };
     const bool any = b->mode == RT_TRACE_ANY;
-    int lds_mode = g_opt.trace_lds < 0 ? fit : std::min(g_opt.trace_lds, fit);
-    int per_cu = 0;
-    HIPCHK(rt_trace_occupancy(s->spheres_only, lds_mode, any, record, lds_of(lds_mode), &per_cu));
-    if (g_opt.trace_lds < 0 && lds_mode > 0) {
-        int per_cu0 = 0;
-        HIPCHK(rt_trace_occupancy(s->spheres_only, 0, any, record, 0, &per_cu0));
-        while (lds_mode > 0 && 4 * per_cu < 3 * per_cu0) {
-            --lds_mode;
-            HIPCHK(rt_trace_occupancy(s->spheres_only, lds_mode, any, record, lds_of(lds_mode), &per_cu));
-        }
+    resident_plan plan;
+    {
+        const rt_status st = plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), g_opt.trace_lds, (b->n + RT_TRACE_THREADS - 1) / RT_TRACE_THREADS,
+                                           [&](int m, size_t lds, int* per_cu) { return rt_trace_occupancy(s->spheres_only, m, any, record, lds, per_cu); }, plan);
+        if (st != RT_OK) return st;
     }
-    const size_t lds = lds_of(lds_mode);
-    // persistent grid: as many workgroups as are resident at once (registers and LDS), never more than the batch needs
-    if (per_cu < 1) per_cu = 1;
-    const long long want = (long long)g_devices[s->device].num_cu * per_cu;
-    const long long need = (b->n + RT_TRACE_THREADS - 1) / RT_TRACE_THREADS;
-    const dim3 grid((unsigned)std::min(want, need));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    HIPCHK(rt_launch_trace(s->spheres_only, lds_mode, sd, tp, grid, lds, stream));
+    HIPCHK(rt_launch_trace(s->spheres_only, plan.lds_mode, sd, tp, plan.grid, plan.lds, stream));
     if (blocking) HIPCHK(hipStreamSynchronize(stream));
     return RT_OK;
 }
@@ -1304,34 +1319,87 @@ rt_status rt_radiance_rays(rt_scene* s, const rt_radiance_batch* b, void* stream
     for (int k = 0; k < 3; ++k) rp.background[k] = b->background[k];
     rp.rgb_out = b->rgb_out; rp.rays_out = b->rays_out;
 
-    // Twin of the block in rt_trace_rays above (other occupancy query, other option): a change to one belongs in the other.
-    // LDS residency and the persistent grid: rt_trace_rays' rule (the walk array; auto = the largest image that keeps at least
-    // 3/4 of the workgroups per CU that the scene-through-L1/L2 mode gets)
-    const rt_scene_dev& sd = s->dev;
-    const size_t node_bytes = (size_t)sd.n_nodes * sizeof(rt_node);
-    const size_t budget = g_devices[s->device].lds_per_cu - 2048;
-    const int fit = node_bytes + s->sphere_bytes <= budget ? 2 : (node_bytes <= budget ? 1 : 0);
-    auto lds_of = [&](int m) -> size_t { return m == 2 ? node_bytes + s->sphere_bytes : (m == 1 ? node_bytes : 0); };
-    int lds_mode = g_opt.radiance_lds < 0 ? fit : std::min(g_opt.radiance_lds, fit);
-    int per_cu = 0;
-    HIPCHK(rt_radiance_occupancy(s->spheres_only, s->tex_level, lds_mode, lds_of(lds_mode), &per_cu));
-    if (g_opt.radiance_lds < 0 && lds_mode > 0) {
-        int per_cu0 = 0;
-        HIPCHK(rt_radiance_occupancy(s->spheres_only, s->tex_level, 0, 0, &per_cu0));
-        while (lds_mode > 0 && 4 * per_cu < 3 * per_cu0) {
-            --lds_mode;
-            HIPCHK(rt_radiance_occupancy(s->spheres_only, s->tex_level, lds_mode, lds_of(lds_mode), &per_cu));
-        }
+    const rt_scene_dev& sd = s->dev;   // the walk array
+    resident_plan plan;
+    {
+        const rt_status st = plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), g_opt.radiance_lds, (b->n + RT_RADIANCE_THREADS - 1) / RT_RADIANCE_THREADS,
+                                           [&](int m, size_t lds, int* per_cu) { return rt_radiance_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu); }, plan);
+        if (st != RT_OK) return st;
     }
-    const size_t lds = lds_of(lds_mode);
-    if (per_cu < 1) per_cu = 1;
-    const long long want = (long long)g_devices[s->device].num_cu * per_cu;
-    const long long need = (b->n + RT_RADIANCE_THREADS - 1) / RT_RADIANCE_THREADS;
-    const dim3 grid((unsigned)std::min(want, need));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    HIPCHK(rt_launch_radiance(s->spheres_only, s->tex_level, lds_mode, sd, rp, grid, lds, stream));
+    HIPCHK(rt_launch_radiance(s->spheres_only, s->tex_level, plan.lds_mode, sd, rp, plan.grid, plan.lds, stream));
     if (blocking) HIPCHK(hipStreamSynchronize(stream));
     return RT_OK;
+}
+
+rt_status rt_render_aov(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* a, int buffers_on_device, void* stream_v, int blocking) {
+    // argument checks: no HIP call and no look at the scene before they pass
+    if (!f) return invalid("rt_render_aov: null frame description");
+    if (!a) return invalid("rt_render_aov: null output description");
+    if (!a->albedo && !a->normal && !a->depth && !a->alpha && !a->prim && !a->inst && !a->mat) return invalid("rt_render_aov: every output is null");
+    if (f->nx <= 0 || f->ny <= 0 || f->ns <= 0) return invalid("rt_render_aov: nx, ny and ns must be positive");
+    if ((long long)f->nx * f->ny >= (1ll << 31)) return invalid("rt_render_aov: frame too large");
+    const int local_rows = rt_frame_local_rows(f);
+    if (local_rows < 0) return invalid("rt_render_aov: bad row partition");
+    const int tiles_x = (f->nx + 7) / 8, tiles_y = (local_rows + 7) / 8;
+    if ((long long)tiles_x * tiles_y * 64 >= (1ll << 31)) return invalid("rt_render_aov: frame too large");
+    if (!s) return invalid("rt_render_aov: null scene");
+    if (local_rows == 0) return RT_OK;
+    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+
+    rt_aov_params ap;
+    memset(&ap, 0, sizeof(ap));
+    const size_t pixels = (size_t)local_rows * f->nx;
+    struct out_buffer { void* user; size_t bytes; const char* what; void** dev; };
+    const out_buffer outs[] = {
+        {a->albedo, 3 * pixels * sizeof(float), "albedo", (void**)&ap.albedo}, {a->normal, 3 * pixels * sizeof(float), "normal", (void**)&ap.normal},
+        {a->depth, pixels * sizeof(float), "depth", (void**)&ap.depth}, {a->alpha, pixels * sizeof(float), "alpha", (void**)&ap.alpha},
+        {a->prim, pixels * sizeof(int32_t), "prim", (void**)&ap.prim}, {a->inst, pixels * sizeof(int32_t), "inst", (void**)&ap.inst},
+        {a->mat, pixels * sizeof(int32_t), "mat", (void**)&ap.mat}};
+    // host buffers are staged in one allocation of this call's own (no per-frame resource of rt_render is used)
+    char* staging = nullptr;
+    if (buffers_on_device) {
+        for (const auto& o : outs) {
+            const rt_status st = check_trace_ptr(o.user, o.bytes, s->device, o.what, "rt_render_aov");
+            if (st != RT_OK) return st;
+            *o.dev = o.user;
+        }
+    } else {
+        size_t total = 0;
+        for (const auto& o : outs) if (o.user) total += (o.bytes + 255) & ~(size_t)255;
+        HIPCHK(hipMalloc((void**)&staging, total));
+        size_t at = 0;
+        for (const auto& o : outs) if (o.user) { *o.dev = staging + at; at += (o.bytes + 255) & ~(size_t)255; }
+    }
+    ap.seed_base = f->seed_base;
+    ap.nx = f->nx; ap.ny = f->ny; ap.ns = f->ns;
+    ap.use_gradient_bg = f->use_gradient_bg;
+    for (int k = 0; k < 3; ++k) ap.background[k] = f->background[k];
+    ap.tile_rows = f->tile_rows; ap.tile_first = f->tile_first; ap.tile_stride = f->tile_stride;
+    ap.local_rows = local_rows;
+    ap.tiles_x = tiles_x;
+    ap.work_items = (uint32_t)tiles_x * (uint32_t)tiles_y * 64u;
+
+    const rt_scene_dev& sd = s->dev;   // the walk array
+    // (the staging block is released on every way out from here on)
+    auto run = [&]() -> rt_status {
+        resident_plan plan;
+        const rt_status st = plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), g_opt.aov_lds, ((long long)ap.work_items + RT_AOV_THREADS - 1) / RT_AOV_THREADS,
+                                           [&](int m, size_t lds, int* per_cu) { return rt_aov_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu); }, plan);
+        if (st != RT_OK) return st;
+        HIPCHK(rt_launch_aov(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, plan.grid, plan.lds, stream));
+        if (!buffers_on_device)
+            for (const auto& o : outs) if (o.user) HIPCHK(hipMemcpyAsync(o.user, *o.dev, o.bytes, hipMemcpyDeviceToHost, stream));
+        if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
+        return RT_OK;
+    };
+    const rt_status st = run();
+    if (staging) {
+        if (st != RT_OK) (void)hipStreamSynchronize(stream);   // nothing of this call may still write into the block
+        (void)hipFree(staging);
+    }
+    return st;
 }
 
 // Tail hand-off of the last frame (diagnostics, every build): [0] pixels the main kernel handed to the tail launches, summed over

@@ -264,6 +264,32 @@ hipError_t rt_launch_radiance(bool spheres_only, int tex_level, int lds_mode, co
                               dim3 grid, size_t lds, hipStream_t st);
 hipError_t rt_radiance_occupancy(bool spheres_only, int tex_level, int lds_mode, size_t lds, int* blocks_per_cu);
 
+// rt_render_aov (rt_kernel_aov.hip): the feature pass of one frame, the pointers already checked on the host.  Every output is
+// optional (null = not written) and holds compact local rows like rt_frame_params.fb.
+struct rt_aov_params {
+    float* albedo;            // local_rows * nx * 3
+    float* normal;            // local_rows * nx * 3
+    float* depth;             // local_rows * nx
+    float* alpha;             // local_rows * nx
+    int32_t* prim;            // local_rows * nx each: the first sample's ids
+    int32_t* inst;
+    int32_t* mat;
+    uint64_t seed_base;
+    int32_t nx, ny, ns;
+    int32_t use_gradient_bg;
+    float background[3];
+    int32_t tile_rows, tile_first, tile_stride;
+    int32_t local_rows;       // rows this call renders
+    int32_t tiles_x;          // 8x8 pixel tiles per local row band
+    uint32_t work_items;      // tiles_x * tiles_y * 64, as rt_frame_params
+};
+// sd.nodes / sd.n_nodes: the walk array; tex_level as rt_launch_pixel; lds_mode 0..2 as stage_scene; grid = persistent
+// workgroups of RT_AOV_THREADS.  rt_aov_occupancy: workgroups per CU of the instantiation such a launch would use.
+#define RT_AOV_THREADS 256
+hipError_t rt_launch_aov(bool spheres_only, int tex_level, int lds_mode, const rt_scene_dev& sd, const rt_aov_params& ap, dim3 grid,
+                         size_t lds, hipStream_t st);
+hipError_t rt_aov_occupancy(bool spheres_only, int tex_level, int lds_mode, size_t lds, int* blocks_per_cu);
+
 // rt_render_adaptive (rt_kernel_adaptive.hip): after each pass, one lane per pixel of that pass decides whether the pixel has
 // converged at checkpoint n (include/rt_abi.h), writes the converged ones to fb / spp and appends the others -- wave-aggregated
 // -- to list_out (local pixel ids, the main kernel's pixel list) and queue_out ((n << 32) | pixel, the tier kernel's tail queue).

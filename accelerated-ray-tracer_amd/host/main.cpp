@@ -7,8 +7,12 @@
 // `--scene bouncing` is case 1, `--scene final` case 9.
 //
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
-//             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--list]
+//             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--list]
 //
+// --aov PREFIX also writes the frame's feature buffers (rt_render_aov, same camera, seed and sample count) next to the image,
+// in the image's PPM flavour: PREFIX.albedo.ppm, PREFIX.normal.ppm (0.5 n + 0.5) and PREFIX.depth.ppm (grey, the ray parameter
+// t over the frame's largest).  Not with --gpus > 1.
+
 // --adaptive T renders with adaptive sampling (rt_render_adaptive): each pixel stops at the first checkpoint M * 2^k where its
 // average moved by at most T * (brightness + 0.01) since the previous one, and at --ns (= max_spp) otherwise.  M defaults to
 // the smallest checkpoint of --ns that is even and >= 16.  Not with --progressive or --gpus > 1.
@@ -32,7 +36,7 @@ static void check(rt_status st, const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string scene_name = "bouncing", texture_path;
+    std::string scene_name = "bouncing", texture_path, aov_prefix;
     int nx = 0, ny = 0, ns = 0, device = 0, gpus = 1, progressive = 0;
     bool p6 = false, adaptive = false;
     float threshold = 0.f;
@@ -53,11 +57,13 @@ int main(int argc, char** argv) {
         else if (k == "--progressive") progressive = atoi(val());   // render in windows of K samples (rt_render_window): same pixels, a frame after each
         else if (k == "--adaptive") { adaptive = true; threshold = strtof(val(), nullptr); }
         else if (k == "--min-spp") min_spp = atoi(val());
+        else if (k == "--aov") aov_prefix = val();
         else if (k == "--list") { int n = 0; const char* const* v = rtw::scene_names(&n); for (int i = 0; i < n; ++i) printf("%s\n", v[i]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); return 2; }
     }
 
     if (adaptive && (progressive > 0 || gpus > 1)) { fprintf(stderr, "--adaptive cannot be combined with --progressive or --gpus > 1\n"); return 2; }
+    if (!aov_prefix.empty() && gpus > 1) { fprintf(stderr, "--aov cannot be combined with --gpus > 1\n"); return 2; }
     if (min_spp > 0 && !adaptive) { fprintf(stderr, "--min-spp needs --adaptive\n"); return 2; }
 
     std::vector<unsigned char> tex;
@@ -133,6 +139,28 @@ int main(int argc, char** argv) {
 
     if (p6) rtw::write_ppm_p6(stdout, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
     else rtw::write_ppm_p3(stdout, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
+
+    if (!aov_prefix.empty()) {
+        const size_t px = (size_t)scene->nx * scene->ny;
+        std::vector<float> albedo(px * 3), normal(px * 3), depth(px), grey(px * 3);
+        rt_aov_desc aov;
+        memset(&aov, 0, sizeof(aov));
+        aov.albedo = albedo.data(); aov.normal = normal.data(); aov.depth = depth.data();
+        check(rt_render_aov(dev_scene, &f, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
+        for (float& c : normal) c = 0.5f * c + 0.5f;
+        float t_far = 0.f;
+        for (float t : depth) if (t > t_far) t_far = t;
+        for (size_t p = 0; p < px; ++p) grey[3 * p] = grey[3 * p + 1] = grey[3 * p + 2] = t_far > 0.f ? depth[p] / t_far : 0.f;
+        const struct { const char* name; const float* data; } files[] = {{"albedo", albedo.data()}, {"normal", normal.data()}, {"depth", grey.data()}};
+        for (const auto& o : files) {
+            const std::string path = aov_prefix + "." + o.name + ".ppm";
+            FILE* out = fopen(path.c_str(), "wb");
+            if (!out) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+            if (p6) rtw::write_ppm_p6(out, o.data, scene->nx, scene->ny, false);
+            else rtw::write_ppm_p3(out, o.data, scene->nx, scene->ny, false);
+            fclose(out);
+        }
+    }
 
     if (multi) check(rt_multi_destroy(multi), "rt_multi_destroy");
     if (dev_scene) check(rt_scene_destroy(dev_scene), "rt_scene_destroy");

@@ -320,6 +320,58 @@ typedef struct rt_radiance_batch {
 } rt_radiance_batch; /* 88 B */
 rt_status rt_radiance_rays(rt_scene* scene, const rt_radiance_batch* batch, void* stream, int blocking);
 
+/* ---- feature buffers: per-pixel albedo, normal, depth, coverage and ids of a frame's first hits ----
+ * What a denoiser, a compositor, a picker or an edge-aware upscaler needs beside a noisy frame (rt_render at few samples,
+ * rt_render_adaptive) of the same camera.
+ *
+ * The feature pass of a frame runs, per pixel, one XORWOW chain seeded seed_base + pixel_index, with rt_render's pixel
+ * indexing (pixel_index = global_row * nx + column) and row partition.  Each of the ns samples draws what a render sample
+ * draws before its path -- two jitter uniforms, camera_get_ray's lens-disk loop at two uniforms per turn, its shutter
+ * uniform -- and nothing else; its primary ray is walked with the render's window (0.001, FLT_MAX) (world->hit, main.cu:57)
+ * and the hit record is resolved as rt_trace_rays resolves it.  Sample s of a pixel is therefore the primary ray rt_render
+ * would send if no path ever consumed a draw; sample 0 is exactly rt_render's first primary ray of that pixel.
+ *
+ * Per sample:
+ *   albedo  lambertian or isotropic hit: the material's texture value at (u, v, p), or its `albedo` when tex < 0; metal:
+ *           `albedo`; dielectric: (1, 1, 1); diffuse light: what it emits there; miss: the frame's miss term as rt_render
+ *           computes it (background, or the gradient of the ray).  The first hit only: no specular bounce is followed.
+ *   normal  the hit record's normal, oriented as normal_out of rt_trace_rays (against the ray for quads and rotated
+ *           instances, outward for spheres); a constant medium gives (1, 0, 0); a miss gives 0.
+ *   depth   the hit record's t: the ray PARAMETER, not a distance -- directions are not normalised, so the distance is
+ *           t * |d|.  A miss gives 0.
+ *   alpha   1 on a hit, 0 on a miss.
+ * Per pixel, each float output is the sum over the samples in sample order, per channel, plain sum = sum + x in binary32
+ * with no contraction, multiplied by (float)(1.0 / (double)(float)ns) -- store_pixel's factor.  No gamma is applied:
+ * f->gamma is ignored.  prim / inst / mat are sample 0's prim_out / inst_out / mat_out as rt_trace_rays defines them, -1 on
+ * a miss.
+ *
+ * The identity that makes every output checkable: in the "emissive twin" of a scene -- every material turned into
+ * RT_MAT_DIFFUSE_LIGHT; lambertian, isotropic and light keep tex and albedo, metal takes tex = -1, dielectric tex = -1 and
+ * albedo = (1, 1, 1) -- every path ends at its first hit and consumes no draw, so `albedo` equals, bit for bit, the frame
+ * rt_render gives for the twin at gamma 1 with the same ns, seed_base, background and partition.
+ *
+ * f supplies nx, ny, ns, background, use_gradient_bg, seed_base and the tile partition.  Every pointer of rt_aov_desc is
+ * optional, at least one is non-null; the buffers hold compact local rows like fb (rt_frame_local_rows(f) rows).  What no
+ * requested output needs is not computed (no texture without albedo).  buffers_on_device != 0: device (or managed) memory
+ * of the scene's device, 4-byte aligned, checked with hipPointerGetAttributes before anything is launched; the work is
+ * enqueued on `stream` and with `blocking` != 0 the call returns when every output is written (rt_trace_rays' rules).
+ * buffers_on_device == 0: host memory; the library stages the outputs in device memory of the call's own, copies them back
+ * and returns when they are complete, whatever `blocking` says.  A null scene, f or a, every output null, non-positive nx, ny
+ * or ns, a frame of 2^31 pixels or more or a bad row partition (rt_render's checks) is RT_ERR_INVALID; these checks run
+ * before any HIP call and before the scene is looked at, and rt_last_error_detail() names the one that failed.  The call
+ * uses none of rt_render's per-frame resources and no shared state, so it may run beside a pending non-blocking rt_render
+ * of the same scene on another stream.  Option "aov_lds": the meaning and auto rule of "trace_lds"; it changes no result. */
+typedef struct rt_aov_desc {
+    float* albedo;             /* rows*nx*3 */
+    float* normal;             /* rows*nx*3 */
+    float* depth;              /* rows*nx */
+    float* alpha;              /* rows*nx */
+    int32_t* prim;             /* rows*nx each */
+    int32_t* inst;
+    int32_t* mat;
+} rt_aov_desc; /* 56 B */
+rt_status rt_render_aov(rt_scene* scene, const rt_frame_desc* f, const rt_aov_desc* a, int buffers_on_device, void* stream, int blocking);
+
 /* ---- progressive accumulation (the reference writes every pixel's curandState back at the end of render(),
  * main.cu:126, which is what would allow it and what nothing in the reference uses) ----
  * rt_render_window renders samples [sample_begin, sample_end) of every pixel the frame description assigns to the call,
