@@ -83,6 +83,13 @@ class RtAovDesc(C.Structure):
                 ("prim", C.c_void_p), ("inst", C.c_void_p), ("mat", C.c_void_p)]
 
 
+class RtDenoiseDesc(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("color", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p),
+                ("depth", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("iterations", C.c_int32), ("normal_sharpness", C.c_int32), ("demodulate", C.c_int32), ("reserved", C.c_int32),
+                ("sigma_color", C.c_float), ("color_floor", C.c_float), ("sigma_depth", C.c_float), ("pad", C.c_float)]
+
+
 class RtAdaptiveDesc(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
 
@@ -105,6 +112,8 @@ TraceResult = collections.namedtuple("TraceResult", "t prim inst point normal uv
 # DeviceScene.render_aov(): the outputs of rt_render_aov -> (channels, numpy dtype)
 AOV_OUTPUTS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "alpha": (1, np.float32),
                "prim": (1, np.int32), "inst": (1, np.int32), "mat": (1, np.int32)}
+# denoise(): the keyword defaults (they live here, not in the ABI); settled on the oracle's 4-spp frames
+DENOISE_DEFAULTS = {"iterations": 5, "normal_sharpness": 4, "sigma_depth": 0.2, "sigma_color": 2.0, "color_floor": 0.01}
 # DeviceScene.radiance(): rays is None unless count_rays=True
 RadianceResult = collections.namedtuple("RadianceResult", "rgb rays")
 
@@ -123,7 +132,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_multi_destroy", "rt_multi_device_count", "rt_multi_row_owner", "rt_multi_probe_rccl", "rt_multi_debug_uninterleave",
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
                   "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive",
-                  "rt_radiance_rays", "rt_render_aov"]
+                  "rt_radiance_rays", "rt_render_aov", "rt_denoise_workspace_bytes", "rt_denoise"]
 
 _rt = None
 _host = None
@@ -198,6 +207,9 @@ def rt_lib():
         L.rt_trace_rays.argtypes = [C.c_void_p, C.POINTER(RtRayBatch), C.c_void_p, C.c_int]
         L.rt_radiance_rays.argtypes = [C.c_void_p, C.POINTER(RtRadianceBatch), C.c_void_p, C.c_int]
         L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAovDesc), C.c_int, C.c_void_p, C.c_int]
+        L.rt_denoise_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.rt_denoise_workspace_bytes.restype = C.c_size_t
+        L.rt_denoise.argtypes = [C.POINTER(RtDenoiseDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAdaptiveDesc), C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.POINTER(RtStats)]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -336,6 +348,91 @@ def set_option(key: str, value: int) -> None:
 def reset_options() -> None:
     """Every scheduling knob back to the shipped default."""
     _check(rt_lib().rt_reset_options(), "rt_reset_options")
+
+
+def denoise_workspace_bytes(nx: int, ny: int) -> int:
+    """Bytes of device memory rt_denoise wants as its workspace for an nx x ny frame (0 for a bad size)."""
+    return int(rt_lib().rt_denoise_workspace_bytes(int(nx), int(ny)))
+
+
+def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_DEFAULTS["iterations"],
+            sigma_color=DENOISE_DEFAULTS["sigma_color"], color_floor=DENOISE_DEFAULTS["color_floor"],
+            normal_sharpness=DENOISE_DEFAULTS["normal_sharpness"], sigma_depth=DENOISE_DEFAULTS["sigma_depth"], demodulate=None,
+            out=None, workspace=None, stream=0, blocking=True):
+    """The edge-avoiding a-trous filter of rt_denoise (include/rt_abi.h): a noisy linear frame `color` (ny, nx, 3), guided by
+    the feature buffers of render_aov -- albedo, normal (ny, nx, 3) and depth (ny, nx), each optional.  It runs on the device
+    of init().
+
+    Either all numpy float32 arrays (C-contiguous; the call waits; `workspace` must be None) or all contiguous float32
+    torch tensors on that device: zero-copy, enqueued on `stream` (a hipStream_t as an integer or a torch.cuda.Stream) and
+    waited for only with blocking=True.  out: None (an array or tensor like color is made) or one of the same kind and
+    shape; it may be `color` itself (in place).  workspace: None (the library allocates its own and the call waits) or a
+    contiguous torch tensor of at least denoise_workspace_bytes(nx, ny) bytes on the device.  demodulate=None means "when
+    albedo is given".  Returns out.  Malformed arguments raise ValueError before anything is launched."""
+    on_host = isinstance(color, np.ndarray)
+    if not on_host and not hasattr(color, "data_ptr"):
+        raise ValueError("color: a numpy array or a torch tensor is expected")
+    if color.ndim != 3 or color.shape[2] != 3 or color.shape[0] < 1 or color.shape[1] < 1:
+        raise ValueError(f"color: shape {tuple(color.shape)}, expected (ny, nx, 3)")
+    ny, nx = int(color.shape[0]), int(color.shape[1])
+    if nx * ny >= 1 << 31:
+        raise ValueError("frame too large")
+    for k, v, lo, hi in (("iterations", iterations, 1, 8), ("normal_sharpness", normal_sharpness, 0, 10)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{k} must be an integer in {lo}..{hi}")
+    sigma_color, color_floor, sigma_depth = float(sigma_color), float(color_floor), float(sigma_depth)
+    for k, v in (("sigma_color", sigma_color), ("sigma_depth", sigma_depth)):
+        if not (v == 0 or (np.isfinite(v) and np.float32(1e-6) <= np.float32(v) <= np.float32(1e6))):
+            raise ValueError(f"{k} must be 0 or in [1e-6, 1e6]")
+    if sigma_color > 0 and not (np.isfinite(color_floor) and 0 < np.float32(color_floor) < np.inf):
+        raise ValueError("color_floor must be finite and positive")
+    if demodulate is None:
+        demodulate = albedo is not None
+    if demodulate and albedo is None:
+        raise ValueError("demodulate needs albedo")
+    if on_host:
+        if workspace is not None:
+            raise ValueError("workspace: device memory goes with device tensors; pass None with numpy arrays")
+        dev = None
+    else:
+        import torch
+        dev = torch.device("cuda", 0 if _initialised_device is None else _initialised_device)
+    if out is None:
+        out = np.empty_like(color, order="C") if on_host else __import__("torch").empty_like(color)
+
+    def ptr(x, name, shape):
+        if x is None:
+            return None
+        if on_host:
+            if not isinstance(x, np.ndarray):
+                raise ValueError(f"{name}: a numpy array is expected (color is one)")
+            if x.dtype != np.float32 or tuple(x.shape) != shape or not x.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{name}: a C-contiguous float32 array of shape {shape} is expected")
+            return x.ctypes.data
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: a torch tensor is expected (color is one)")
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"{name}: a contiguous float32 tensor of shape {shape} on {dev} is expected")
+        return x.data_ptr()
+
+    d = RtDenoiseDesc()
+    d.nx, d.ny = nx, ny
+    d.color, d.albedo, d.normal = ptr(color, "color", (ny, nx, 3)), ptr(albedo, "albedo", (ny, nx, 3)), ptr(normal, "normal", (ny, nx, 3))
+    d.depth, d.out = ptr(depth, "depth", (ny, nx)), ptr(out, "out", (ny, nx, 3))
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or not workspace.is_contiguous() or workspace.device != dev:
+            raise ValueError(f"workspace: a contiguous torch tensor on {dev} is expected")
+        d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    d.iterations, d.normal_sharpness, d.demodulate = int(iterations), int(normal_sharpness), 1 if demodulate else 0
+    d.sigma_color, d.color_floor, d.sigma_depth = sigma_color, color_floor, sigma_depth
+    if hasattr(stream, "cuda_stream"):
+        stream = stream.cuda_stream
+    L = rt_lib()
+    st = L.rt_denoise(C.byref(d), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None, 1 if blocking else 0)
+    if st == 1:
+        raise ValueError(L.rt_last_error_detail().decode())
+    _check(st, "rt_denoise")
+    return out
 
 
 class DeviceScene:
@@ -591,6 +688,23 @@ class DeviceScene:
             raise ValueError(L.rt_last_error_detail().decode())
         _check(st, "rt_render_aov")
         return out
+
+    def render_denoised(self, frame: RtFrameDesc, **denoise_args) -> dict:
+        """A denoised frame: render() of `frame` at gamma 1, render_aov() of it (albedo, normal, depth at min(frame.ns, 16)
+        samples) and denoise() of the two (its keyword arguments pass through).  Returns {"color": the denoised linear
+        frame, "noisy": the render, "albedo", "normal", "depth"} as numpy arrays.  The frame must be the whole image: a
+        partitioned one is ValueError."""
+        if frame.nx <= 0 or frame.ny <= 0 or frame.ns <= 0:
+            raise ValueError("bad frame size or sample count")
+        if frame.tile_first != 0 or frame.tile_stride != 1 or frame.tile_rows < frame.ny:
+            raise ValueError("render_denoised needs the whole frame (tile_rows >= ny, tile_first = 0, tile_stride = 1)")
+        f = RtFrameDesc.from_buffer_copy(frame)
+        f.gamma = 1.0
+        noisy, _ = self.render(f)
+        f.ns = min(frame.ns, 16)
+        aov = self.render_aov(f, alpha=False)
+        color = denoise(noisy, aov["albedo"], aov["normal"], aov["depth"], **denoise_args)
+        return {"color": color, "noisy": noisy, "albedo": aov["albedo"], "normal": aov["normal"], "depth": aov["depth"]}
 
     def render_adaptive(self, frame: RtFrameDesc, min_spp: int, max_spp: int, threshold: float, floor: float = 0.01, out=None,
                         spp_out=None, stream=0):

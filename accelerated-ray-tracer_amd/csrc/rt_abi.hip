@@ -90,6 +90,8 @@ struct rt_options {
     int trace_tree = 1;          // rt_trace_rays: 1 = the walk array, 0 = the reference's full tree
     int radiance_lds = -1;       // rt_radiance_rays: as trace_lds
     int aov_lds = -1;            // rt_render_aov: as trace_lds
+    int denoise_lds = -1;        // rt_denoise: -1 = iterations with taps up to 4 pixels apart stage tile + halo in LDS, 0 = never,
+                                 // 1 = wherever the tile fits (taps up to 8 apart)
     int adaptive_tier = -1;      // rt_render_adaptive: -1 = a pass goes to the tier kernel when its active pixels fit the tier waves at once
                                  // (DESIGN.md 4.8), 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit
 };
@@ -670,6 +672,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "trace_lds") { if (value < -1 || value > 2) return invalid("trace_lds: -1 (auto) .. 2"); g_opt.trace_lds = value; }
     else if (k == "radiance_lds") { if (value < -1 || value > 2) return invalid("radiance_lds: -1 (auto) .. 2"); g_opt.radiance_lds = value; }
     else if (k == "aov_lds") { if (value < -1 || value > 2) return invalid("aov_lds: -1 (auto) .. 2"); g_opt.aov_lds = value; }
+    else if (k == "denoise_lds") { if (value < -1 || value > 1) return invalid("denoise_lds: -1 (auto), 0 (direct) or 1 (staged)"); g_opt.denoise_lds = value; }
     else if (k == "trace_tree") { if (value < 0 || value > 1) return invalid("trace_tree: 0 (reference tree) or 1 (walk array)"); g_opt.trace_tree = value; }
     else if (k == "adaptive_tier") { if (value < -1 || value > 1) return invalid("adaptive_tier: -1 (auto), 0 (main kernel) or 1 (tier kernel)"); g_opt.adaptive_tier = value; }
     else if (k == "wg_per_cu") { if (value < 0 || value > 8) return invalid("wg_per_cu: 0 (per kernel family) .. 8"); g_opt.wg_per_cu = value; }
@@ -1398,6 +1401,109 @@ rt_status rt_render_aov(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* 
     if (staging) {
         if (st != RT_OK) (void)hipStreamSynchronize(stream);   // nothing of this call may still write into the block
         (void)hipFree(staging);
+    }
+    return st;
+}
+
+size_t rt_denoise_workspace_bytes(int32_t nx, int32_t ny) {
+    if (nx < 1 || ny < 1 || (long long)nx * ny >= (1ll << 31)) return 0;
+    const size_t image = ((size_t)nx * ny * sizeof(float4) + 255) & ~(size_t)255;
+    return 3 * image;   // x_k, x_{k+1} and the guide records
+}
+
+rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stream_v, int blocking) {
+    // argument checks: no HIP call before they pass
+    if (!d) return invalid("rt_denoise: null description");
+    if (d->nx < 1 || d->ny < 1) return invalid("rt_denoise: nx and ny must be positive");
+    if ((long long)d->nx * d->ny >= (1ll << 31)) return invalid("rt_denoise: frame too large");
+    if (d->iterations < 1 || d->iterations > 8) return invalid("rt_denoise: iterations must be in 1..8");
+    if (d->normal_sharpness < 0 || d->normal_sharpness > 10) return invalid("rt_denoise: normal_sharpness must be in 0..10");
+    auto sigma_ok = [](float v) { return v == 0.f || (std::isfinite(v) && v >= 1e-6f && v <= 1e6f); };
+    if (!sigma_ok(d->sigma_depth)) return invalid("rt_denoise: sigma_depth must be 0 or in [1e-6, 1e6]");
+    if (!sigma_ok(d->sigma_color)) return invalid("rt_denoise: sigma_color must be 0 or in [1e-6, 1e6]");
+    if (d->sigma_color > 0.f && !(std::isfinite(d->color_floor) && d->color_floor > 0.f)) return invalid("rt_denoise: color_floor must be finite and positive");
+    if (!d->color) return invalid("rt_denoise: null color");
+    if (!d->out) return invalid("rt_denoise: null out");
+    if (d->demodulate && !d->albedo) return invalid("rt_denoise: demodulate needs albedo");
+    const size_t pixels = (size_t)d->nx * d->ny;
+    const size_t ws_bytes = rt_denoise_workspace_bytes(d->nx, d->ny);
+    const bool own_workspace = !buffers_on_device || !d->workspace;
+    if (d->workspace && d->workspace_bytes < ws_bytes) return invalid("rt_denoise: workspace smaller than rt_denoise_workspace_bytes");
+    struct buffer { const void* user; size_t bytes; const char* what; unsigned align; };
+    const buffer bufs[] = {{d->color, 3 * pixels * sizeof(float), "color", 4}, {d->albedo, 3 * pixels * sizeof(float), "albedo", 4},
+                           {d->normal, 3 * pixels * sizeof(float), "normal", 4}, {d->depth, pixels * sizeof(float), "depth", 4},
+                           {d->out, 3 * pixels * sizeof(float), "out", 4}, {own_workspace ? nullptr : d->workspace, ws_bytes, "workspace", 16}};
+    {   // out may be exactly color; nothing else may share a byte with out or with the workspace
+        auto overlap = [](const buffer& a, const buffer& b) {
+            const uintptr_t pa = (uintptr_t)a.user, pb = (uintptr_t)b.user;
+            return a.user && b.user && pa < pb + b.bytes && pb < pa + a.bytes;
+        };
+        for (int k = 0; k < 6; ++k) {
+            if (k != 4 && overlap(bufs[k], bufs[4]) && !(k == 0 && d->out == d->color)) return invalid("rt_denoise: out overlaps another buffer (it may only be exactly color)");
+            if (k != 5 && overlap(bufs[k], bufs[5])) return invalid("rt_denoise: the workspace overlaps another buffer");
+        }
+    }
+    { const rt_status ud = use_device(g_device); if (ud != RT_OK) return ud; }
+    if (buffers_on_device)
+        for (const auto& b : bufs) {
+            const rt_status st = check_trace_ptr(b.user, b.bytes, g_device, b.what, "rt_denoise", b.align);
+            if (st != RT_OK) return st;
+        }
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+
+    const bool normal_on = d->normal && d->normal_sharpness > 0, depth_on = d->depth && d->sigma_depth > 0.f, color_on = d->sigma_color > 0.f;
+    const bool guide = normal_on || depth_on;
+    // one allocation of this call's own: the workspace when the caller gives none and, for host buffers, their device images
+    const void* dev[5] = {d->color, d->albedo, d->normal, d->depth, d->out};
+    char* block = nullptr;
+    char* ws = static_cast<char*>(d->workspace);
+    auto round = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    if (own_workspace) {
+        size_t total = ws_bytes;
+        if (!buffers_on_device) for (int k = 0; k < 5; ++k) if (bufs[k].user && !(k == 4 && d->out == d->color)) total += round(bufs[k].bytes);
+        HIPCHK(hipMalloc((void**)&block, total));
+        ws = block;
+        if (!buffers_on_device) {
+            size_t at = ws_bytes;
+            for (int k = 0; k < 5; ++k) if (bufs[k].user && !(k == 4 && d->out == d->color)) { dev[k] = block + at; at += round(bufs[k].bytes); }
+            if (d->out == d->color) dev[4] = dev[0];
+        }
+    }
+    auto run = [&]() -> rt_status {
+        if (!buffers_on_device)
+            for (int k = 0; k < 4; ++k) if (bufs[k].user) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].user, bufs[k].bytes, hipMemcpyHostToDevice, stream));
+        const size_t image = ws_bytes / 3;
+        float4* x[2] = {reinterpret_cast<float4*>(ws), reinterpret_cast<float4*>(ws + image)};
+        rt_denoise_params dp;
+        memset(&dp, 0, sizeof(dp));
+        dp.color = static_cast<const float*>(dev[0]); dp.albedo = d->demodulate ? static_cast<const float*>(dev[1]) : nullptr;
+        dp.normal = normal_on ? static_cast<const float*>(dev[2]) : nullptr; dp.depth = depth_on ? static_cast<const float*>(dev[3]) : nullptr;
+        dp.out = static_cast<float*>(const_cast<void*>(dev[4]));
+        dp.guide = reinterpret_cast<float4*>(ws + 2 * image);
+        dp.nx = d->nx; dp.ny = d->ny;
+        dp.tiles_x = (d->nx + RT_DENOISE_TILE - 1) / RT_DENOISE_TILE;
+        dp.normal_sharpness = d->normal_sharpness; dp.demodulate = d->demodulate ? 1 : 0;
+        dp.color_floor = d->color_floor; dp.sigma_depth = d->sigma_depth;
+        dp.x_out = x[0];
+        HIPCHK(rt_launch_denoise_pack(dp, guide, stream));
+        // staged or direct, per iteration: staging fetches (16 + 4 s)^2 / 256 records per pixel and array instead
+        // of 25 -- 1.6, 2.3, 4 for s = 1, 2, 4 -- and at s = 8 (9 per pixel, 84 KiB: one workgroup per CU) no longer pays
+        const int max_staged = g_opt.denoise_lds < 0 ? 4 : (g_opt.denoise_lds == 0 ? 0 : RT_DENOISE_MAX_STAGED_STEP);
+        for (int k = 0; k < d->iterations; ++k) {
+            dp.step = 1 << k;
+            dp.sigma_color_k = d->sigma_color * (1.0f / (float)(1 << k));
+            dp.x_in = x[k & 1]; dp.x_out = x[(k + 1) & 1];
+            dp.last = k == d->iterations - 1;
+            HIPCHK(rt_launch_denoise(normal_on, depth_on, color_on, dp.step <= max_staged, dp, stream));
+        }
+        if (!buffers_on_device) HIPCHK(hipMemcpyAsync(d->out, dev[4], bufs[4].bytes, hipMemcpyDeviceToHost, stream));
+        if (blocking || own_workspace) HIPCHK(hipStreamSynchronize(stream));
+        return RT_OK;
+    };
+    const rt_status st = run();
+    if (block) {
+        if (st != RT_OK) (void)hipStreamSynchronize(stream);   // nothing of this call may still use the block
+        (void)hipFree(block);
     }
     return st;
 }

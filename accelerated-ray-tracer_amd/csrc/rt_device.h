@@ -290,6 +290,41 @@ hipError_t rt_launch_aov(bool spheres_only, int tex_level, int lds_mode, const r
                          size_t lds, hipStream_t st);
 hipError_t rt_aov_occupancy(bool spheres_only, int tex_level, int lds_mode, size_t lds, int* blocks_per_cu);
 
+// rt_denoise (rt_kernel_denoise.hip): the pack pass and one iteration of the filter, the pointers already checked on the host.
+// A pixel is two 16-byte records in the workspace: colour (x.rgb, (x.r + x.g) + x.b) and guide (N.xyz, Z; zeros where absent).
+struct rt_denoise_params {
+    const float* color;       // pack: the planar inputs (albedo, normal, depth may be null)
+    const float* albedo;      // ... and, when `demodulate`, read again by the last iteration
+    const float* normal;
+    const float* depth;
+    float* out;               // last iteration: ny * nx * 3
+    const float4* x_in;       // iteration: x_k
+    float4* x_out;            // pack: x_0; iteration (not the last): x_{k+1}
+    float4* guide;            // pack writes, iterations read; unused when no guide factor is on
+    int32_t nx, ny;
+    int32_t tiles_x;          // 16x16-pixel workgroup tiles per row band
+    int32_t step;             // s = 2^k
+    int32_t normal_sharpness; // m
+    int32_t demodulate;
+    int32_t last;
+    float sigma_color_k;      // sigma_color * 2^-k
+    float color_floor;
+    float sigma_depth;
+};
+#define RT_DENOISE_THREADS 256
+#define RT_DENOISE_TILE 16
+#define RT_DENOISE_MAX_STAGED_STEP 8
+// the LDS image of a staged iteration: (16 + 4 s)^2 records per array, rows padded to 8 mod 16 records (128 mod 256 bytes),
+// which spreads the four rows a 16-lane read group touches over the 64 banks
+__host__ __device__ inline int rt_denoise_lds_width(int step) { return RT_DENOISE_TILE + 4 * step; }
+__host__ __device__ inline int rt_denoise_lds_stride(int step) { return ((rt_denoise_lds_width(step) + 7) & ~15) + 8; }
+inline size_t rt_denoise_lds_bytes(int step, bool guide) {
+    return (size_t)rt_denoise_lds_stride(step) * rt_denoise_lds_width(step) * sizeof(float4) * (guide ? 2 : 1);
+}
+hipError_t rt_launch_denoise_pack(const rt_denoise_params& dp, bool guide, hipStream_t st);
+// staged: the tile and its 2 s halo through LDS (step <= RT_DENOISE_MAX_STAGED_STEP), else every tap through L1/L2
+hipError_t rt_launch_denoise(bool normal_on, bool depth_on, bool color_on, bool staged, const rt_denoise_params& dp, hipStream_t st);
+
 // rt_render_adaptive (rt_kernel_adaptive.hip): after each pass, one lane per pixel of that pass decides whether the pixel has
 // converged at checkpoint n (include/rt_abi.h), writes the converged ones to fb / spp and appends the others -- wave-aggregated
 // -- to list_out (local pixel ids, the main kernel's pixel list) and queue_out ((n << 32) | pixel, the tier kernel's tail queue).

@@ -1,0 +1,179 @@
+// rt_kernel_denoise.hip -- rt_denoise: the edge-avoiding a-trous filter of include/rt_abi.h ("denoiser"), gfx950.
+//
+// Two kernels.  The pack pass turns the planar inputs into two 16-byte records per pixel (colour: x_0.rgb and its sum;
+// guide: N.xyz, Z), so that a tap is two dwordx4 loads.  The iteration kernel runs once per iteration k on workgroups of 256
+// threads = four waves on 8x8 pixels each = a 16x16 tile, one pixel per lane in registers; it reads x_k and writes
+// x_{k+1} (or, in the last iteration, the planar output, remodulated).  Specialised on which of the three factors are on
+// and on how the taps are fetched:
+//   staged  the tile and its halo of 2 s pixels go to LDS once, and the 25 taps of every pixel are LDS reads;
+//   direct  every tap is read through L1/L2.
+// Which one an iteration gets is the host's choice (rt_abi.hip, option "denoise_lds"); the arithmetic is the
+// same statements in the same order in both, so the choice changes no bit.
+//
+// Bounds: a tap outside the image is skipped by an index test before any address is formed; the staging loop loads only
+// the records inside the image, and a tap that passes the index test is inside the image and inside the staged window by
+// construction (|offset| <= 2 s), so no slot is read that was not written.  No address depends on pixel data.
+#include "rt_device.h"
+
+namespace {
+
+constexpr int TILE = RT_DENOISE_TILE;
+constexpr float ALBEDO_FLOOR = 0.0009765625f;   // 2^-10
+
+__global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_denoise_pack_kernel(rt_denoise_params dp, int guide) {
+    const size_t n = (size_t)dp.nx * dp.ny;
+    const size_t p = (size_t)blockIdx.x * RT_DENOISE_THREADS + threadIdx.x;
+    if (p >= n) return;
+    float r = dp.color[3 * p], g = dp.color[3 * p + 1], b = dp.color[3 * p + 2];
+    if (dp.demodulate) {
+        r = r / fmaxf(dp.albedo[3 * p], ALBEDO_FLOOR);
+        g = g / fmaxf(dp.albedo[3 * p + 1], ALBEDO_FLOOR);
+        b = b / fmaxf(dp.albedo[3 * p + 2], ALBEDO_FLOOR);
+    }
+    dp.x_out[p] = make_float4(r, g, b, (r + g) + b);
+    if (guide) {
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (dp.normal) { q.x = dp.normal[3 * p]; q.y = dp.normal[3 * p + 1]; q.z = dp.normal[3 * p + 2]; }
+        if (dp.depth) q.w = dp.depth[p];
+        dp.guide[p] = q;
+    }
+}
+
+template <bool NRM, bool DEP, bool COL, bool STAGED>
+__global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_denoise_kernel(rt_denoise_params dp) {
+    extern __shared__ float4 lds[];
+    constexpr bool GUIDE = NRM || DEP;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nx = dp.nx, ny = dp.ny, s = dp.step;
+    const int by = (int)(blockIdx.x / (unsigned)dp.tiles_x), bx = (int)(blockIdx.x - (unsigned)by * (unsigned)dp.tiles_x);
+    const int x0 = bx * TILE, y0 = by * TILE;
+    // a wave on one 8x8 tile, as in the other kernels
+    // (coordinates are unsigned: one below 0 or past 2^31 - 1 wraps and compares as out of the image)
+    const unsigned i = (unsigned)x0 + (wave & 1) * 8 + (lane & 7), j = (unsigned)y0 + (wave >> 1) * 8 + (lane >> 3);
+
+    const int lw = TILE + 4 * s, stride = rt_denoise_lds_stride(s);
+    const unsigned ox = (unsigned)x0 - 2u * s, oy = (unsigned)y0 - 2u * s;     // image coordinates of LDS slot (0, 0)
+    const float4* lc = lds;
+    const float4* lg = lds + stride * lw;
+    if (STAGED) {
+        for (int t = tid; t < lw * lw; t += RT_DENOISE_THREADS) {
+            const int ly = t / lw, lx = t - ly * lw;
+            const unsigned gx = ox + lx, gy = oy + ly;
+            if (gx < (unsigned)nx && gy < (unsigned)ny) {
+                const size_t q = (size_t)gy * nx + gx;
+                lds[ly * stride + lx] = dp.x_in[q];
+                if (GUIDE) lds[stride * lw + ly * stride + lx] = dp.guide[q];
+            }
+        }
+        __syncthreads();
+    }
+    if (i >= (unsigned)nx || j >= (unsigned)ny) return;
+
+    const size_t p = (size_t)j * nx + i;
+    float4 xp, gp = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (STAGED) {
+        const int c = (int)(j - oy) * stride + (int)(i - ox);
+        xp = lc[c];
+        if (GUIDE) gp = lg[c];
+    } else {
+        xp = dp.x_in[p];
+        if (GUIDE) gp = dp.guide[p];
+    }
+
+    const float H[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    float W = 0.f, Sr = 0.f, Sg = 0.f, Sb = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const unsigned qy = j + (unsigned)(s * dy);
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const unsigned qx = i + (unsigned)(s * dx);
+            if (qx >= (unsigned)nx || qy >= (unsigned)ny) continue;
+            float4 xq, gq = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (STAGED) {
+                const int c = (int)(qy - oy) * stride + (int)(qx - ox);
+                xq = lc[c];
+                if (GUIDE) gq = lg[c];
+            } else {
+                const size_t q = (size_t)qy * nx + qx;
+                xq = dp.x_in[q];
+                if (GUIDE) gq = dp.guide[q];
+            }
+            float w = H[dy + 2] * H[dx + 2];
+            if (dx != 0 || dy != 0) {
+                if (NRM) {
+                    float d = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
+                    d = fmaxf(d, 0.f);
+                    for (int m = 0; m < dp.normal_sharpness; ++m) d = d * d;
+                    w = w * d;
+                }
+                if (DEP) {
+                    const float den = dp.sigma_depth * fmaxf(gp.w, gq.w) + 1e-20f;
+                    const float r = fabsf(gp.w - gq.w) / den;
+                    const float t = fmaxf(1.f - r, 0.f);
+                    w = w * (t * t);
+                }
+                if (COL) {
+                    const float d1 = (fabsf(xp.x - xq.x) + fabsf(xp.y - xq.y)) + fabsf(xp.z - xq.z);
+                    const float den = dp.sigma_color_k * ((xp.w + xq.w) + dp.color_floor);
+                    const float r = d1 / den;
+                    const float t = fmaxf(1.f - r, 0.f);
+                    w = w * (t * t);
+                }
+            }
+            W = W + w;
+            Sr = Sr + w * xq.x;
+            Sg = Sg + w * xq.y;
+            Sb = Sb + w * xq.z;
+        }
+    }
+    float r = Sr / W, g = Sg / W, b = Sb / W;
+    if (!dp.last) {
+        dp.x_out[p] = make_float4(r, g, b, (r + g) + b);
+        return;
+    }
+    if (dp.demodulate) {
+        r = r * fmaxf(dp.albedo[3 * p], ALBEDO_FLOOR);
+        g = g * fmaxf(dp.albedo[3 * p + 1], ALBEDO_FLOOR);
+        b = b * fmaxf(dp.albedo[3 * p + 2], ALBEDO_FLOOR);
+    }
+    dp.out[3 * p] = r;
+    dp.out[3 * p + 1] = g;
+    dp.out[3 * p + 2] = b;
+}
+
+template <bool NRM, bool DEP, bool COL, bool STAGED>
+hipError_t launch(const rt_denoise_params& dp, hipStream_t st) {
+    const size_t lds = STAGED ? rt_denoise_lds_bytes(dp.step, NRM || DEP) : 0;
+    if (lds > 65536) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_denoise_kernel<NRM, DEP, COL, STAGED>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const unsigned tiles_y = ((unsigned)dp.ny + TILE - 1) / TILE;
+    hipLaunchKernelGGL((rt_denoise_kernel<NRM, DEP, COL, STAGED>), dim3((unsigned)dp.tiles_x * tiles_y), dim3(RT_DENOISE_THREADS), lds, st, dp);
+    return hipGetLastError();
+}
+
+template <bool NRM, bool DEP, bool COL>
+hipError_t launch_staged(bool staged, const rt_denoise_params& dp, hipStream_t st) {
+    return staged ? launch<NRM, DEP, COL, true>(dp, st) : launch<NRM, DEP, COL, false>(dp, st);
+}
+template <bool NRM, bool DEP>
+hipError_t launch_color(bool color_on, bool staged, const rt_denoise_params& dp, hipStream_t st) {
+    return color_on ? launch_staged<NRM, DEP, true>(staged, dp, st) : launch_staged<NRM, DEP, false>(staged, dp, st);
+}
+
+}  // namespace
+
+hipError_t rt_launch_denoise_pack(const rt_denoise_params& dp, bool guide, hipStream_t st) {
+    const size_t n = (size_t)dp.nx * dp.ny;
+    hipLaunchKernelGGL(rt_denoise_pack_kernel, dim3((unsigned)((n + RT_DENOISE_THREADS - 1) / RT_DENOISE_THREADS)), dim3(RT_DENOISE_THREADS), 0, st, dp,
+                       guide ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_denoise(bool normal_on, bool depth_on, bool color_on, bool staged, const rt_denoise_params& dp, hipStream_t st) {
+    if (normal_on) return depth_on ? launch_color<true, true>(color_on, staged, dp, st) : launch_color<true, false>(color_on, staged, dp, st);
+    return depth_on ? launch_color<false, true>(color_on, staged, dp, st) : launch_color<false, false>(color_on, staged, dp, st);
+}

@@ -7,8 +7,13 @@
 // `--scene bouncing` is case 1, `--scene final` case 9.
 //
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
-//             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--list]
+//             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K]] [--list]
 //
+// --denoise [K] filters the frame with rt_denoise (K iterations, 5 when K is left out; the binding's other defaults): the frame
+// is rendered at gamma 1, the feature pass (albedo, normal, depth at min(ns, 16) samples) guides the filter, and the frame's
+// gamma is applied on the host afterwards -- as powf(c, 1 / gamma) per channel, so the image is not rt_render's bit for bit
+// even where the filter changes nothing.  With --aov PREFIX the unfiltered frame is written to PREFIX_noisy.ppm as well.  Works
+// with --adaptive; not with --progressive or --gpus > 1.
 // --aov PREFIX also writes the frame's feature buffers (rt_render_aov, same camera, seed and sample count) next to the image,
 // in the image's PPM flavour: PREFIX.albedo.ppm, PREFIX.normal.ppm (0.5 n + 0.5) and PREFIX.depth.ppm (grey, the ray parameter
 // t over the frame's largest).  Not with --gpus > 1.
@@ -19,6 +24,7 @@
 // --gpus N (N > 1) spreads the frame over the first N GPUs of the node: interleaved 4-row tiles, one scene replica
 // per device, one RCCL gather to device 0 (rt_multi_*, include/rt_abi.h).  The PPM is byte-identical for every N by construction (global per-pixel seeds,
 // no cross-device rays); verified on one GPU for N = 1 and for every rank's share, not yet on N > 1 hardware.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,7 +46,7 @@ int main(int argc, char** argv) {
     int nx = 0, ny = 0, ns = 0, device = 0, gpus = 1, progressive = 0;
     bool p6 = false, adaptive = false;
     float threshold = 0.f;
-    int min_spp = 0;
+    int min_spp = 0, denoise = 0;
     unsigned long long seed = 1984ull;
     for (int a = 1; a < argc; ++a) {
         std::string k = argv[a];
@@ -58,12 +64,18 @@ int main(int argc, char** argv) {
         else if (k == "--adaptive") { adaptive = true; threshold = strtof(val(), nullptr); }
         else if (k == "--min-spp") min_spp = atoi(val());
         else if (k == "--aov") aov_prefix = val();
+        else if (k == "--denoise") {   // K is optional: the next argument when it is a number
+            denoise = 5;
+            if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') denoise = atoi(argv[++a]);
+            if (denoise < 1 || denoise > 8) { fprintf(stderr, "--denoise K: K must be in 1..8\n"); return 2; }
+        }
         else if (k == "--list") { int n = 0; const char* const* v = rtw::scene_names(&n); for (int i = 0; i < n; ++i) printf("%s\n", v[i]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); return 2; }
     }
 
     if (adaptive && (progressive > 0 || gpus > 1)) { fprintf(stderr, "--adaptive cannot be combined with --progressive or --gpus > 1\n"); return 2; }
     if (!aov_prefix.empty() && gpus > 1) { fprintf(stderr, "--aov cannot be combined with --gpus > 1\n"); return 2; }
+    if (denoise && (progressive > 0 || gpus > 1)) { fprintf(stderr, "--denoise cannot be combined with --progressive or --gpus > 1\n"); return 2; }
     if (min_spp > 0 && !adaptive) { fprintf(stderr, "--min-spp needs --adaptive\n"); return 2; }
 
     std::vector<unsigned char> tex;
@@ -90,6 +102,7 @@ int main(int argc, char** argv) {
     f.use_gradient_bg = scene->use_gradient_bg;
     f.seed_base = seed;
     f.tile_rows = scene->ny; f.tile_first = 0; f.tile_stride = 1;
+    if (denoise) f.gamma = 1.0f;   // the filter works on the linear frame; the gamma is applied after it, below
 
     std::vector<float> fb((size_t)scene->nx * scene->ny * 3);
     rt_stats stats;
@@ -136,6 +149,39 @@ int main(int argc, char** argv) {
     fprintf(stderr, "{\"scene\": \"%s\", \"nx\": %d, \"ny\": %d, \"ns\": %d, \"gpus\": %d, \"rays\": %llu, \"ms_render\": %.3f, \"mrays_per_s\": %.1f}\n",
             scene_name.c_str(), scene->nx, scene->ny, scene->ns, gpus, (unsigned long long)stats.rays, stats.ms_render,
             stats.ms_render > 0 ? (double)stats.rays / (stats.ms_render * 1e3) : 0.0);
+
+    if (denoise) {
+        const size_t px = (size_t)scene->nx * scene->ny;
+        auto apply_gamma = [&](std::vector<float>& img) {
+            if (scene->gamma != 1.0f) for (float& c : img) c = powf(c, 1.0f / scene->gamma);
+        };
+        std::vector<float> albedo(px * 3), normal(px * 3), depth(px);
+        rt_frame_desc ff = f;
+        if (ff.ns > 16) ff.ns = 16;
+        rt_aov_desc aov;
+        memset(&aov, 0, sizeof(aov));
+        aov.albedo = albedo.data(); aov.normal = normal.data(); aov.depth = depth.data();
+        check(rt_render_aov(dev_scene, &ff, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
+        if (!aov_prefix.empty()) {
+            std::vector<float> noisy = fb;
+            apply_gamma(noisy);
+            const std::string path = aov_prefix + "_noisy.ppm";
+            FILE* out = fopen(path.c_str(), "wb");
+            if (!out) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+            if (p6) rtw::write_ppm_p6(out, noisy.data(), scene->nx, scene->ny, scene->ppm_double_scale);
+            else rtw::write_ppm_p3(out, noisy.data(), scene->nx, scene->ny, scene->ppm_double_scale);
+            fclose(out);
+        }
+        rt_denoise_desc dn;
+        memset(&dn, 0, sizeof(dn));
+        dn.nx = scene->nx; dn.ny = scene->ny;
+        dn.color = fb.data(); dn.albedo = albedo.data(); dn.normal = normal.data(); dn.depth = depth.data();
+        dn.out = fb.data();
+        dn.iterations = denoise; dn.normal_sharpness = 4; dn.demodulate = 1;
+        dn.sigma_color = 2.0f; dn.color_floor = 0.01f; dn.sigma_depth = 0.2f;
+        check(rt_denoise(&dn, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_denoise");
+        apply_gamma(fb);
+    }
 
     if (p6) rtw::write_ppm_p6(stdout, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
     else rtw::write_ppm_p3(stdout, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);

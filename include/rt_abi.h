@@ -372,6 +372,68 @@ typedef struct rt_aov_desc {
 } rt_aov_desc; /* 56 B */
 rt_status rt_render_aov(rt_scene* scene, const rt_frame_desc* f, const rt_aov_desc* a, int buffers_on_device, void* stream, int blocking);
 
+/* ---- denoiser: an edge-avoiding a-trous wavelet filter guided by the feature buffers ----
+ * rt_denoise filters a noisy linear frame (rt_render or rt_render_adaptive at gamma 1) with a 5x5 B3-spline kernel whose
+ * taps are spread 2^k pixels apart in iteration k and weighted down across edges of the normal, the depth and the colour.
+ * It takes no scene and runs on the device the last rt_init selected.
+ *
+ * The numerical contract.  All arithmetic is binary32, every written operation is rounded once, nothing is contracted
+ * into an FMA, sums run left to right as written; only + - * /, max, abs and comparisons occur.  Images are whole frames of
+ * ny x nx pixels, row-major, row 0 at the bottom, as rt_render writes an unpartitioned frame: color (x3) is required;
+ * albedo (x3), normal (x3) and depth (x1) are optional and are what rt_render_aov writes.
+ *   Prepare.  demodulate != 0: per channel a = max(albedo, 2^-10), x_0 = color / a (a null albedo is then RT_ERR_INVALID);
+ *     otherwise x_0 = color.
+ *   Iteration k = 0 .. iterations-1, s = 2^k, pixel p = (i, j).  W = 0, S = (0, 0, 0).  For dy = -2..2 (outer), dx = -2..2
+ *     (inner), q = (i + s dx, j + s dy); a q outside the image is skipped.  w = H[dy] H[dx], H = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *     (every product is exact).  The centre tap (dx = dy = 0) takes no further factor, so W >= 9/64 whatever the guides
+ *     hold.  Every other tap multiplies w by these factors, in this order (w = w * factor); a factor that is off is not applied:
+ *       normal  (normal non-null and normal_sharpness = m in 1..10; 0 = off):
+ *               d = (Np.x Nq.x + Np.y Nq.y) + Np.z Nq.z;  d = max(d, 0);  then d = d d, m times (the exponent is 2^m);
+ *               the factor is d.
+ *       depth   (depth non-null and sigma_depth > 0):
+ *               den = sigma_depth max(Zp, Zq) + 1e-20f;  r = |Zp - Zq| / den;  t = max(1 - r, 0);  the factor is t t.
+ *       colour  (sigma_color > 0), on x_k:  sp = (xp.r + xp.g) + xp.b, sq likewise;  d1 = (|dr| + |dg|) + |db|, the channel
+ *               differences xp - xq;  den = (sigma_color 2^-k) ((sp + sq) + color_floor);  r = d1 / den;
+ *               t = max(1 - r, 0);  the factor is t t.
+ *     Then W = W + w and, per channel, S.ch = S.ch + w xq.ch.  After the 25 taps x_{k+1}(p).ch = S.ch / W.
+ *   Finish.  out = x_K a per channel when demodulating, else x_K.  No gamma is applied.
+ * tests/denoise_expect.py restates this in NumPy float32; the device result equals it bit for bit.
+ * Inputs are expected to be finite.  What a NaN or an infinity does to the pixels within reach of it (2 (2^K - 1) pixels
+ * each way) is unspecified, but no value of any input makes the call fault: no address depends on pixel data.
+ *
+ * Parameters (anything else is RT_ERR_INVALID): iterations 1..8; nx, ny >= 1 and nx ny < 2^31; normal_sharpness 0..10;
+ * sigma_depth and sigma_color each 0 or finite in [1e-6, 1e6]; color_floor finite and > 0 when sigma_color > 0; color and
+ * out non-null.  out may be exactly color (in place); any other overlap among the buffers and the workspace is
+ * RT_ERR_INVALID where the host can see it and undefined otherwise.
+ *
+ * Buffers: rt_render_aov's rules.  buffers_on_device != 0: every non-null buffer (and the workspace) is device or managed
+ * memory of that device, 4-byte aligned (the workspace 16-byte), checked with hipPointerGetAttributes before anything is
+ * launched; the work is enqueued on `stream` and with `blocking` != 0 the call returns when out is written.
+ * buffers_on_device == 0: host memory; the library stages the buffers in device memory of the call's own, copies out back
+ * and returns when it is complete, whatever `blocking` says; a workspace is then checked for its size and not used.
+ * Workspace: rt_denoise_workspace_bytes(nx, ny) bytes of device memory (0 for a bad size) -- two colour images and one
+ * guide image of 16-byte records.  A non-null workspace smaller than that is RT_ERR_INVALID.  With a null workspace the
+ * library allocates its own and waits before freeing it, whatever `blocking` says; with a caller's workspace and
+ * blocking == 0 the call only enqueues.  The argument checks run before any HIP call and rt_last_error_detail() names the
+ * one that failed.  The call uses no scene and no shared state, so it may run beside a pending non-blocking rt_render on
+ * another stream.  Option "denoise_lds": -1 (auto) = iterations whose taps are at most 4 pixels apart stage their tile and
+ * its halo in LDS, the others read their taps through L1/L2; 0 = never stage; 1 = stage wherever the tile fits (taps up to 8
+ * apart).  It changes no result. */
+typedef struct rt_denoise_desc {
+    int32_t nx, ny;
+    const float* color;        /* ny*nx*3, linear */
+    const float* albedo;       /* ny*nx*3 or null */
+    const float* normal;       /* ny*nx*3 or null */
+    const float* depth;        /* ny*nx or null */
+    float* out;                /* ny*nx*3; may be exactly `color` */
+    void* workspace;           /* device memory, or null */
+    size_t workspace_bytes;
+    int32_t iterations, normal_sharpness, demodulate, reserved;
+    float sigma_color, color_floor, sigma_depth, pad;
+} rt_denoise_desc; /* 96 B */
+size_t rt_denoise_workspace_bytes(int32_t nx, int32_t ny);
+rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stream, int blocking);
+
 /* ---- progressive accumulation (the reference writes every pixel's curandState back at the end of render(),
  * main.cu:126, which is what would allow it and what nothing in the reference uses) ----
  * rt_render_window renders samples [sample_begin, sample_end) of every pixel the frame description assigns to the call,
