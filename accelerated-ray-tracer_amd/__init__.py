@@ -94,6 +94,14 @@ class RtAdaptiveDesc(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
 
 
+class RtVarianceDesc(C.Structure):
+    _fields_ = [("batches", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RtDenoiseVarianceDesc(C.Structure):
+    _fields_ = [("variance", C.c_void_p), ("variance_out", C.c_void_p), ("sigma_variance", C.c_float), ("variance_floor", C.c_float)]
+
+
 RT_TRACE_CLOSEST, RT_TRACE_ANY = 0, 1
 RT_PRIM_SPHERE, RT_PRIM_QUAD, RT_PRIM_BOX, RT_PRIM_INSTANCE, RT_PRIM_MEDIUM = range(5)
 
@@ -114,6 +122,8 @@ AOV_OUTPUTS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1
                "prim": (1, np.int32), "inst": (1, np.int32), "mat": (1, np.int32)}
 # denoise(): the keyword defaults (they live here, not in the ABI); settled on the oracle's 4-spp frames
 DENOISE_DEFAULTS = {"iterations": 5, "normal_sharpness": 4, "sigma_depth": 0.2, "sigma_color": 2.0, "color_floor": 0.01}
+# denoise(variance=...): the keyword defaults of the variance factor, settled by a sweep on the same frames
+DENOISE_VARIANCE_DEFAULTS = {"sigma_variance": 3.0, "variance_floor": 1e-4}
 # DeviceScene.radiance(): rays is None unless count_rays=True
 RadianceResult = collections.namedtuple("RadianceResult", "rgb rays")
 
@@ -132,7 +142,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_multi_destroy", "rt_multi_device_count", "rt_multi_row_owner", "rt_multi_probe_rccl", "rt_multi_debug_uninterleave",
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
                   "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive",
-                  "rt_radiance_rays", "rt_render_aov", "rt_denoise_workspace_bytes", "rt_denoise"]
+                  "rt_radiance_rays", "rt_render_aov", "rt_denoise_workspace_bytes", "rt_denoise", "rt_render_variance",
+                  "rt_denoise_variance"]
 
 _rt = None
 _host = None
@@ -212,6 +223,9 @@ def rt_lib():
         L.rt_denoise.argtypes = [C.POINTER(RtDenoiseDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAdaptiveDesc), C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.POINTER(RtStats)]
+        L.rt_render_variance.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtVarianceDesc), C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.POINTER(RtStats)]
+        L.rt_denoise_variance.argtypes = [C.POINTER(RtDenoiseDesc), C.POINTER(RtDenoiseVarianceDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.rt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _rt = L
@@ -356,9 +370,10 @@ def denoise_workspace_bytes(nx: int, ny: int) -> int:
 
 
 def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_DEFAULTS["iterations"],
-            sigma_color=DENOISE_DEFAULTS["sigma_color"], color_floor=DENOISE_DEFAULTS["color_floor"],
+            sigma_color=None, color_floor=DENOISE_DEFAULTS["color_floor"],
             normal_sharpness=DENOISE_DEFAULTS["normal_sharpness"], sigma_depth=DENOISE_DEFAULTS["sigma_depth"], demodulate=None,
-            out=None, workspace=None, stream=0, blocking=True):
+            out=None, workspace=None, stream=0, blocking=True, variance=None, variance_out=None,
+            sigma_variance=DENOISE_VARIANCE_DEFAULTS["sigma_variance"], variance_floor=DENOISE_VARIANCE_DEFAULTS["variance_floor"]):
     """The edge-avoiding a-trous filter of rt_denoise (include/rt_abi.h): a noisy linear frame `color` (ny, nx, 3), guided by
     the feature buffers of render_aov -- albedo, normal (ny, nx, 3) and depth (ny, nx), each optional.  It runs on the device
     of init().
@@ -368,7 +383,27 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_D
     waited for only with blocking=True.  out: None (an array or tensor like color is made) or one of the same kind and
     shape; it may be `color` itself (in place).  workspace: None (the library allocates its own and the call waits) or a
     contiguous torch tensor of at least denoise_workspace_bytes(nx, ny) bytes on the device.  demodulate=None means "when
-    albedo is given".  Returns out.  Malformed arguments raise ValueError before anything is launched."""
+    albedo is given".  Returns out.  Malformed arguments raise ValueError before anything is launched.
+
+    variance: None, or the per-pixel variance (ny, nx) that render_variance returns -- the filter then runs variance-guided
+    (rt_denoise_variance): a tap is weighed by the squared colour difference over sigma_variance^2 times the two pixels'
+    variances plus variance_floor, in place of the colour factor, so sigma_color is passed as 0 and an explicit non-zero
+    one is a ValueError.  variance_out: None or an array / tensor (ny, nx) that receives the filtered variance.  sigma_color=None
+    means DENOISE_DEFAULTS["sigma_color"] without a variance."""
+    if variance is None:
+        if variance_out is not None:
+            raise ValueError("variance_out needs variance")
+        if sigma_color is None:
+            sigma_color = DENOISE_DEFAULTS["sigma_color"]
+    else:
+        if sigma_color is not None and float(sigma_color) != 0:
+            raise ValueError("sigma_color must be left out or 0 with a variance: the variance factor replaces the colour factor")
+        sigma_color = 0.0
+        sigma_variance, variance_floor = float(sigma_variance), float(variance_floor)
+        if not (np.isfinite(sigma_variance) and np.float32(1e-6) <= np.float32(sigma_variance) <= np.float32(1e6)):
+            raise ValueError("sigma_variance must be in [1e-6, 1e6]")
+        if not (np.isfinite(variance_floor) and 0 < np.float32(variance_floor) < np.inf):
+            raise ValueError("variance_floor must be finite and positive")
     on_host = isinstance(color, np.ndarray)
     if not on_host and not hasattr(color, "data_ptr"):
         raise ValueError("color: a numpy array or a torch tensor is expected")
@@ -428,10 +463,17 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_D
     if hasattr(stream, "cuda_stream"):
         stream = stream.cuda_stream
     L = rt_lib()
-    st = L.rt_denoise(C.byref(d), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None, 1 if blocking else 0)
+    if variance is None:
+        st = L.rt_denoise(C.byref(d), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None, 1 if blocking else 0)
+    else:
+        vd = RtDenoiseVarianceDesc()
+        vd.variance, vd.variance_out = ptr(variance, "variance", (ny, nx)), ptr(variance_out, "variance_out", (ny, nx))
+        vd.sigma_variance, vd.variance_floor = sigma_variance, variance_floor
+        st = L.rt_denoise_variance(C.byref(d), C.byref(vd), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None,
+                                   1 if blocking else 0)
     if st == 1:
         raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_denoise")
+    _check(st, "rt_denoise" if variance is None else "rt_denoise_variance")
     return out
 
 
@@ -689,22 +731,100 @@ class DeviceScene:
         _check(st, "rt_render_aov")
         return out
 
-    def render_denoised(self, frame: RtFrameDesc, **denoise_args) -> dict:
+    def render_denoised(self, frame: RtFrameDesc, variance: bool = False, batches=None, **denoise_args) -> dict:
         """A denoised frame: render() of `frame` at gamma 1, render_aov() of it (albedo, normal, depth at min(frame.ns, 16)
         samples) and denoise() of the two (its keyword arguments pass through).  Returns {"color": the denoised linear
         frame, "noisy": the render, "albedo", "normal", "depth"} as numpy arrays.  The frame must be the whole image: a
-        partitioned one is ValueError."""
+        partitioned one is ValueError.
+
+        variance=True: the frame comes from render_variance() -- `batches` batches, by default the largest divisor of
+        frame.ns in 2..16 (a frame.ns without one, such as 1 or 17, is ValueError: pass batches) -- and the filter runs variance-guided
+        (denoise(variance=...)); the result also holds "variance", the render's per-pixel variance."""
         if frame.nx <= 0 or frame.ny <= 0 or frame.ns <= 0:
             raise ValueError("bad frame size or sample count")
         if frame.tile_first != 0 or frame.tile_stride != 1 or frame.tile_rows < frame.ny:
             raise ValueError("render_denoised needs the whole frame (tile_rows >= ny, tile_first = 0, tile_stride = 1)")
+        if not variance and batches is not None:
+            raise ValueError("batches needs variance=True")
         f = RtFrameDesc.from_buffer_copy(frame)
         f.gamma = 1.0
-        noisy, _ = self.render(f)
+        var = None
+        if variance:
+            if batches is None:
+                batches = min(frame.ns, 16)
+                while frame.ns % batches:
+                    batches -= 1
+                if batches < 2:
+                    raise ValueError(f"frame.ns = {frame.ns} has no divisor in 2..16: pass batches (2..64, a divisor of frame.ns)")
+            noisy, var, _ = self.render_variance(f, batches)
+        else:
+            noisy, _ = self.render(f)
         f.ns = min(frame.ns, 16)
         aov = self.render_aov(f, alpha=False)
+        if variance:
+            denoise_args = dict(denoise_args, variance=var)
         color = denoise(noisy, aov["albedo"], aov["normal"], aov["depth"], **denoise_args)
-        return {"color": color, "noisy": noisy, "albedo": aov["albedo"], "normal": aov["normal"], "depth": aov["depth"]}
+        r = {"color": color, "noisy": noisy, "albedo": aov["albedo"], "normal": aov["normal"], "depth": aov["depth"]}
+        if variance:
+            r["variance"] = var
+        return r
+
+    def render_variance(self, frame: RtFrameDesc, batches: int, out=None, variance_out=None, stream=0):
+        """A frame and the variance of each of its pixels (rt_render_variance): fb is render()'s frame at frame.ns samples, and
+        variance (rows x nx) estimates, from the spread of `batches` batch averages, the variance of the pixel's mean of
+        r + g + b (include/rt_abi.h).  2 <= batches <= 64 and frame.ns a multiple of it.
+
+        out / variance_out: None (numpy arrays are made), float32 numpy arrays of rows x nx (x 3), or device memory of this
+        scene's device -- torch tensors or integer pointers; both host or both device.  stream: a hipStream_t as an integer
+        or a torch.cuda.Stream.  The call returns when the frame is complete.  Returns (fb, variance, stats); fb / variance are
+        what was passed in (None where an integer pointer was).  Malformed arguments raise ValueError before anything is
+        launched."""
+        if isinstance(batches, bool) or not isinstance(batches, (int, np.integer)):
+            raise ValueError("batches must be an integer")
+        batches = int(batches)
+        if not 2 <= batches <= 64:
+            raise ValueError("batches must be in 2..64")
+        if frame.ns <= 0 or frame.ns % batches:
+            raise ValueError("frame.ns must be a positive multiple of batches")
+        L = rt_lib()
+        rows = L.rt_frame_local_rows(C.byref(frame))
+        if frame.nx <= 0 or frame.ny <= 0 or rows < 0:
+            raise ValueError("bad frame size or row partition")
+        if out is None and variance_out is None:
+            out = np.empty((rows, frame.nx, 3), np.float32)
+            variance_out = np.empty((rows, frame.nx), np.float32)
+        if out is None or variance_out is None:
+            raise ValueError("out and variance_out go together: pass both or neither")
+        on_host = isinstance(out, np.ndarray)
+        if isinstance(variance_out, np.ndarray) != on_host:
+            raise ValueError("out and variance_out must both be host (numpy) or both device memory")
+
+        def ptr(x, size, name):
+            if isinstance(x, np.ndarray):
+                if x.dtype != np.float32 or x.size != size or not x.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"{name}: a C-contiguous float32 array of {size} elements is expected")
+                return x.ctypes.data
+            if hasattr(x, "data_ptr"):
+                import torch
+                if x.dtype != torch.float32 or x.numel() != size or not x.is_contiguous() or x.device != torch.device("cuda", self.device):
+                    raise ValueError(f"{name}: a contiguous float32 tensor of {size} elements on cuda:{self.device} is expected")
+                return x.data_ptr()
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+                raise ValueError(f"{name}: a numpy array, a torch tensor or an integer device pointer is expected")
+            return int(x)
+        p_fb = ptr(out, rows * frame.nx * 3, "out")
+        p_var = ptr(variance_out, rows * frame.nx, "variance_out")
+        if hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        v = RtVarianceDesc(batches, 0)
+        stats = RtStats()
+        st = L.rt_render_variance(self._p, C.byref(frame), C.byref(v), C.c_void_p(p_fb), 0 if on_host else 1, C.c_void_p(p_var),
+                                  C.c_void_p(int(stream)) if stream else None, C.byref(stats))
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_render_variance")
+        ret = lambda x: x if (isinstance(x, np.ndarray) or hasattr(x, "data_ptr")) else None   # noqa: E731
+        return ret(out), ret(variance_out), stats
 
     def render_adaptive(self, frame: RtFrameDesc, min_spp: int, max_spp: int, threshold: float, floor: float = 0.01, out=None,
                         spp_out=None, stream=0):

@@ -172,12 +172,16 @@ struct rt_scene {
     int32_t* d_adapt_spp = nullptr;              // host spp_out: the device map copied back
     uint32_t* d_adapt_count = nullptr;
     rt_rank_info* d_adapt_rank = nullptr;
-    size_t adapt_capacity = 0;
+    size_t adapt_capacity = 0, adapt_lists_capacity = 0;   // d_adapt_state and d_adapt_spp; half, lists and queue
     std::vector<hipEvent_t> adapt_events;        // two per pass (rt_debug_adaptive_passes)
     std::vector<long long> adapt_log;            // per pass of the last adaptive frame: route, active pixels, sample_begin, sample_end
     std::vector<float> adapt_ms;
     rt_rank_info adapt_rank_host;                // host sides of the small copies between passes (alive until the next sync)
     unsigned int adapt_wc_host[RT_WORK_COUNTER_BYTES / 4];
+    // rt_render_variance: per local pixel T_{b-1}, A, Q (the parked pixels live in d_adapt_state, a host variance_out's device
+    // image in d_adapt_spp: 4 bytes per pixel either way)
+    double* d_var_acc = nullptr;
+    size_t var_capacity = 0;
 };
 
 // Progressive accumulation (rt_render_window): the parked pixels of one frame description between windows.
@@ -696,7 +700,7 @@ rt_status rt_scene_destroy(rt_scene* s) {
     if (s->d_handoff) (void)hipFree(s->d_handoff);
     if (s->d_cal_cost) (void)hipFree(s->d_cal_cost);
     for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue,
-                    (void*)s->d_adapt_spp, (void*)s->d_adapt_count, (void*)s->d_adapt_rank})
+                    (void*)s->d_adapt_spp, (void*)s->d_adapt_count, (void*)s->d_adapt_rank, (void*)s->d_var_acc})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : s->adapt_events) (void)hipEventDestroy(e);
     if (s->tier_stream) (void)hipStreamDestroy(s->tier_stream);
@@ -1411,42 +1415,58 @@ size_t rt_denoise_workspace_bytes(int32_t nx, int32_t ny) {
     return 3 * image;   // x_k, x_{k+1} and the guide records
 }
 
-rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stream_v, int blocking) {
+// rt_denoise (vd null) and rt_denoise_variance (vd non-null, checked by the caller for null): one body, `who` names the entry
+// point in the texts of failed checks
+static rt_status denoise_impl(const rt_denoise_desc* d, const rt_denoise_variance_desc* vd, const char* who_c, int buffers_on_device, void* stream_v, int blocking) {
     // argument checks: no HIP call before they pass
-    if (!d) return invalid("rt_denoise: null description");
-    if (d->nx < 1 || d->ny < 1) return invalid("rt_denoise: nx and ny must be positive");
-    if ((long long)d->nx * d->ny >= (1ll << 31)) return invalid("rt_denoise: frame too large");
-    if (d->iterations < 1 || d->iterations > 8) return invalid("rt_denoise: iterations must be in 1..8");
-    if (d->normal_sharpness < 0 || d->normal_sharpness > 10) return invalid("rt_denoise: normal_sharpness must be in 0..10");
-    auto sigma_ok = [](float v) { return v == 0.f || (std::isfinite(v) && v >= 1e-6f && v <= 1e6f); };
-    if (!sigma_ok(d->sigma_depth)) return invalid("rt_denoise: sigma_depth must be 0 or in [1e-6, 1e6]");
-    if (!sigma_ok(d->sigma_color)) return invalid("rt_denoise: sigma_color must be 0 or in [1e-6, 1e6]");
-    if (d->sigma_color > 0.f && !(std::isfinite(d->color_floor) && d->color_floor > 0.f)) return invalid("rt_denoise: color_floor must be finite and positive");
-    if (!d->color) return invalid("rt_denoise: null color");
-    if (!d->out) return invalid("rt_denoise: null out");
-    if (d->demodulate && !d->albedo) return invalid("rt_denoise: demodulate needs albedo");
+    const std::string who(who_c);
+    auto bad = [&](const char* why) { return invalid((who + ": " + why).c_str()); };
+    if (!d) return bad("null description");
+    if (d->nx < 1 || d->ny < 1) return bad("nx and ny must be positive");
+    if ((long long)d->nx * d->ny >= (1ll << 31)) return bad("frame too large");
+    if (d->iterations < 1 || d->iterations > 8) return bad("iterations must be in 1..8");
+    if (d->normal_sharpness < 0 || d->normal_sharpness > 10) return bad("normal_sharpness must be in 0..10");
+    auto in_range = [](float v) { return std::isfinite(v) && v >= 1e-6f && v <= 1e6f; };
+    auto sigma_ok = [&](float v) { return v == 0.f || in_range(v); };
+    if (!sigma_ok(d->sigma_depth)) return bad("sigma_depth must be 0 or in [1e-6, 1e6]");
+    if (vd) {
+        if (d->sigma_color != 0.f) return bad("sigma_color must be 0 (the variance factor replaces the colour factor)");
+        if (!in_range(vd->sigma_variance)) return bad("sigma_variance must be in [1e-6, 1e6]");
+        if (!(std::isfinite(vd->variance_floor) && vd->variance_floor > 0.f)) return bad("variance_floor must be finite and positive");
+        if (!vd->variance) return bad("null variance");
+    } else {
+        if (!sigma_ok(d->sigma_color)) return bad("sigma_color must be 0 or in [1e-6, 1e6]");
+        if (d->sigma_color > 0.f && !(std::isfinite(d->color_floor) && d->color_floor > 0.f)) return bad("color_floor must be finite and positive");
+    }
+    if (!d->color) return bad("null color");
+    if (!d->out) return bad("null out");
+    if (d->demodulate && !d->albedo) return bad("demodulate needs albedo");
     const size_t pixels = (size_t)d->nx * d->ny;
     const size_t ws_bytes = rt_denoise_workspace_bytes(d->nx, d->ny);
     const bool own_workspace = !buffers_on_device || !d->workspace;
-    if (d->workspace && d->workspace_bytes < ws_bytes) return invalid("rt_denoise: workspace smaller than rt_denoise_workspace_bytes");
-    struct buffer { const void* user; size_t bytes; const char* what; unsigned align; };
-    const buffer bufs[] = {{d->color, 3 * pixels * sizeof(float), "color", 4}, {d->albedo, 3 * pixels * sizeof(float), "albedo", 4},
-                           {d->normal, 3 * pixels * sizeof(float), "normal", 4}, {d->depth, pixels * sizeof(float), "depth", 4},
-                           {d->out, 3 * pixels * sizeof(float), "out", 4}, {own_workspace ? nullptr : d->workspace, ws_bytes, "workspace", 16}};
-    {   // out may be exactly color; nothing else may share a byte with out or with the workspace
+    if (d->workspace && d->workspace_bytes < ws_bytes) return bad("workspace smaller than rt_denoise_workspace_bytes");
+    struct buffer { const void* user; size_t bytes; const char* what; unsigned align; bool input; };
+    enum { COLOR = 0, ALBEDO, NORMAL, DEPTH, OUT, WORKSPACE, VARIANCE, VARIANCE_OUT, N_BUFS };
+    const buffer bufs[N_BUFS] = {{d->color, 3 * pixels * sizeof(float), "color", 4, true}, {d->albedo, 3 * pixels * sizeof(float), "albedo", 4, true},
+                                 {d->normal, 3 * pixels * sizeof(float), "normal", 4, true}, {d->depth, pixels * sizeof(float), "depth", 4, true},
+                                 {d->out, 3 * pixels * sizeof(float), "out", 4, false}, {own_workspace ? nullptr : d->workspace, ws_bytes, "workspace", 16, false},
+                                 {vd ? vd->variance : nullptr, pixels * sizeof(float), "variance", 4, true},
+                                 {vd ? vd->variance_out : nullptr, pixels * sizeof(float), "variance_out", 4, false}};
+    {   // out may be exactly color; nothing else may share a byte with out, with variance_out or with the workspace
         auto overlap = [](const buffer& a, const buffer& b) {
             const uintptr_t pa = (uintptr_t)a.user, pb = (uintptr_t)b.user;
             return a.user && b.user && pa < pb + b.bytes && pb < pa + a.bytes;
         };
-        for (int k = 0; k < 6; ++k) {
-            if (k != 4 && overlap(bufs[k], bufs[4]) && !(k == 0 && d->out == d->color)) return invalid("rt_denoise: out overlaps another buffer (it may only be exactly color)");
-            if (k != 5 && overlap(bufs[k], bufs[5])) return invalid("rt_denoise: the workspace overlaps another buffer");
+        for (int k = 0; k < N_BUFS; ++k) {
+            if (k != OUT && overlap(bufs[k], bufs[OUT]) && !(k == COLOR && d->out == d->color)) return bad("out overlaps another buffer (it may only be exactly color)");
+            if (k != WORKSPACE && overlap(bufs[k], bufs[WORKSPACE])) return bad("the workspace overlaps another buffer");
+            if (k != VARIANCE_OUT && overlap(bufs[k], bufs[VARIANCE_OUT])) return bad("variance_out overlaps another buffer");
         }
     }
     { const rt_status ud = use_device(g_device); if (ud != RT_OK) return ud; }
     if (buffers_on_device)
         for (const auto& b : bufs) {
-            const rt_status st = check_trace_ptr(b.user, b.bytes, g_device, b.what, "rt_denoise", b.align);
+            const rt_status st = check_trace_ptr(b.user, b.bytes, g_device, b.what, who_c, b.align);
             if (st != RT_OK) return st;
         }
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
@@ -1454,38 +1474,48 @@ rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stre
     const bool normal_on = d->normal && d->normal_sharpness > 0, depth_on = d->depth && d->sigma_depth > 0.f, color_on = d->sigma_color > 0.f;
     const bool guide = normal_on || depth_on;
     // one allocation of this call's own: the workspace when the caller gives none and, for host buffers, their device images
-    const void* dev[5] = {d->color, d->albedo, d->normal, d->depth, d->out};
+    const void* dev[N_BUFS];
+    for (int k = 0; k < N_BUFS; ++k) dev[k] = bufs[k].user;
     char* block = nullptr;
     char* ws = static_cast<char*>(d->workspace);
     auto round = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    auto staged_image = [&](int k) { return k != WORKSPACE && bufs[k].user && !(k == OUT && d->out == d->color); };
     if (own_workspace) {
         size_t total = ws_bytes;
-        if (!buffers_on_device) for (int k = 0; k < 5; ++k) if (bufs[k].user && !(k == 4 && d->out == d->color)) total += round(bufs[k].bytes);
+        if (!buffers_on_device) for (int k = 0; k < N_BUFS; ++k) if (staged_image(k)) total += round(bufs[k].bytes);
         HIPCHK(hipMalloc((void**)&block, total));
         ws = block;
         if (!buffers_on_device) {
             size_t at = ws_bytes;
-            for (int k = 0; k < 5; ++k) if (bufs[k].user && !(k == 4 && d->out == d->color)) { dev[k] = block + at; at += round(bufs[k].bytes); }
-            if (d->out == d->color) dev[4] = dev[0];
+            for (int k = 0; k < N_BUFS; ++k) if (staged_image(k)) { dev[k] = block + at; at += round(bufs[k].bytes); }
+            if (d->out == d->color) dev[OUT] = dev[COLOR];
         }
     }
     auto run = [&]() -> rt_status {
         if (!buffers_on_device)
-            for (int k = 0; k < 4; ++k) if (bufs[k].user) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].user, bufs[k].bytes, hipMemcpyHostToDevice, stream));
+            for (int k = 0; k < N_BUFS; ++k) if (bufs[k].input && bufs[k].user) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].user, bufs[k].bytes, hipMemcpyHostToDevice, stream));
         const size_t image = ws_bytes / 3;
         float4* x[2] = {reinterpret_cast<float4*>(ws), reinterpret_cast<float4*>(ws + image)};
         rt_denoise_params dp;
         memset(&dp, 0, sizeof(dp));
-        dp.color = static_cast<const float*>(dev[0]); dp.albedo = d->demodulate ? static_cast<const float*>(dev[1]) : nullptr;
-        dp.normal = normal_on ? static_cast<const float*>(dev[2]) : nullptr; dp.depth = depth_on ? static_cast<const float*>(dev[3]) : nullptr;
-        dp.out = static_cast<float*>(const_cast<void*>(dev[4]));
+        dp.color = static_cast<const float*>(dev[COLOR]); dp.albedo = d->demodulate ? static_cast<const float*>(dev[ALBEDO]) : nullptr;
+        dp.normal = normal_on ? static_cast<const float*>(dev[NORMAL]) : nullptr; dp.depth = depth_on ? static_cast<const float*>(dev[DEPTH]) : nullptr;
+        dp.out = static_cast<float*>(const_cast<void*>(dev[OUT]));
         dp.guide = reinterpret_cast<float4*>(ws + 2 * image);
         dp.nx = d->nx; dp.ny = d->ny;
         dp.tiles_x = (d->nx + RT_DENOISE_TILE - 1) / RT_DENOISE_TILE;
         dp.normal_sharpness = d->normal_sharpness; dp.demodulate = d->demodulate ? 1 : 0;
         dp.color_floor = d->color_floor; dp.sigma_depth = d->sigma_depth;
         dp.x_out = x[0];
-        HIPCHK(rt_launch_denoise_pack(dp, guide, stream));
+        rt_denoise_variance_params dv;
+        memset(&dv, 0, sizeof(dv));
+        if (vd) {
+            dv.variance = static_cast<const float*>(dev[VARIANCE]); dv.variance_out = static_cast<float*>(const_cast<void*>(dev[VARIANCE_OUT]));
+            dv.sigma_variance = vd->sigma_variance; dv.variance_floor = vd->variance_floor;
+            HIPCHK(rt_launch_denoise_pack_variance(dp, dv, guide, stream));
+        } else {
+            HIPCHK(rt_launch_denoise_pack(dp, guide, stream));
+        }
         // staged or direct, per iteration: staging fetches (16 + 4 s)^2 / 256 records per pixel and array instead
         // of 25 -- 1.6, 2.3, 4 for s = 1, 2, 4 -- and at s = 8 (9 per pixel, 84 KiB: one workgroup per CU) no longer pays
         const int max_staged = g_opt.denoise_lds < 0 ? 4 : (g_opt.denoise_lds == 0 ? 0 : RT_DENOISE_MAX_STAGED_STEP);
@@ -1494,9 +1524,11 @@ rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stre
             dp.sigma_color_k = d->sigma_color * (1.0f / (float)(1 << k));
             dp.x_in = x[k & 1]; dp.x_out = x[(k + 1) & 1];
             dp.last = k == d->iterations - 1;
-            HIPCHK(rt_launch_denoise(normal_on, depth_on, color_on, dp.step <= max_staged, dp, stream));
+            if (vd) HIPCHK(rt_launch_denoise_variance(normal_on, depth_on, dp.step <= max_staged, dp, dv, stream));
+            else HIPCHK(rt_launch_denoise(normal_on, depth_on, color_on, dp.step <= max_staged, dp, stream));
         }
-        if (!buffers_on_device) HIPCHK(hipMemcpyAsync(d->out, dev[4], bufs[4].bytes, hipMemcpyDeviceToHost, stream));
+        if (!buffers_on_device)
+            for (int k : {(int)OUT, (int)VARIANCE_OUT}) if (bufs[k].user) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].user), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
         if (blocking || own_workspace) HIPCHK(hipStreamSynchronize(stream));
         return RT_OK;
     };
@@ -1506,6 +1538,15 @@ rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stre
         (void)hipFree(block);
     }
     return st;
+}
+
+rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stream_v, int blocking) {
+    return denoise_impl(d, nullptr, "rt_denoise", buffers_on_device, stream_v, blocking);
+}
+
+rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_variance_desc* vd, int buffers_on_device, void* stream_v, int blocking) {
+    if (!vd) return invalid("rt_denoise_variance: null variance description");
+    return denoise_impl(d, vd, "rt_denoise_variance", buffers_on_device, stream_v, blocking);
 }
 
 // Tail hand-off of the last frame (diagnostics, every build): [0] pixels the main kernel handed to the tail launches, summed over
@@ -2008,6 +2049,30 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     return RT_OK;
 }
 
+// the per-pixel buffers of rt_render_adaptive, cached in the scene and grown when a frame needs more, in two groups: the parked
+// pixels and the 4-byte-per-pixel map, which rt_render_variance shares, and (`lists`) what only the adaptive decisions need
+static rt_status ensure_adaptive_buffers(rt_scene* s, size_t n_pixels, bool lists) {
+    if (s->adapt_capacity < n_pixels) {
+        for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_spp})
+            if (p) (void)hipFree(p);
+        s->d_adapt_state = nullptr; s->d_adapt_spp = nullptr; s->adapt_capacity = 0;
+        HIPCHK(hipMalloc((void**)&s->d_adapt_state, n_pixels * sizeof(rt_pixel_state)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_spp, n_pixels * sizeof(int32_t)));
+        s->adapt_capacity = n_pixels;
+    }
+    if (lists && s->adapt_lists_capacity < n_pixels) {
+        for (void* p : {(void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue})
+            if (p) (void)hipFree(p);
+        s->d_adapt_half = nullptr; s->d_adapt_list[0] = s->d_adapt_list[1] = nullptr; s->d_adapt_queue = nullptr; s->adapt_lists_capacity = 0;
+        HIPCHK(hipMalloc((void**)&s->d_adapt_half, n_pixels * 3 * sizeof(float)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_list[0], n_pixels * sizeof(uint32_t)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_list[1], n_pixels * sizeof(uint32_t)));
+        HIPCHK(hipMalloc((void**)&s->d_adapt_queue, n_pixels * sizeof(unsigned long long)));
+        s->adapt_lists_capacity = n_pixels;
+    }
+    return RT_OK;
+}
+
 // ---- rt_render_adaptive (include/rt_abi.h).  Passes [0, min/2) and [min/2, min) over every pixel, then [c_k, c_k+1)
 // over the pixels still active.  The render passes only park pixels (d_adapt_state); the decision kernel (rt_kernel_adaptive.hip)
 // writes fb and the sample-count map and compacts the active pixels into the next pass's list (main kernel) and queue (tier kernel).
@@ -2045,20 +2110,7 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
 
     // ---- buffers: cached in the scene, grown when a frame needs more
     const size_t floats = n_pixels * 3;
-    if (s->adapt_capacity < n_pixels) {
-        for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue,
-                        (void*)s->d_adapt_spp})
-            if (p) (void)hipFree(p);
-        s->d_adapt_state = nullptr; s->d_adapt_half = nullptr; s->d_adapt_list[0] = s->d_adapt_list[1] = nullptr; s->d_adapt_queue = nullptr;
-        s->d_adapt_spp = nullptr; s->adapt_capacity = 0;
-        HIPCHK(hipMalloc((void**)&s->d_adapt_state, n_pixels * sizeof(rt_pixel_state)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_half, floats * sizeof(float)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_list[0], n_pixels * sizeof(uint32_t)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_list[1], n_pixels * sizeof(uint32_t)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_queue, n_pixels * sizeof(unsigned long long)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_spp, n_pixels * sizeof(int32_t)));
-        s->adapt_capacity = n_pixels;
-    }
+    { const rt_status eb = ensure_adaptive_buffers(s, n_pixels, true); if (eb != RT_OK) return eb; }
     if (!s->d_adapt_count) HIPCHK(hipMalloc((void**)&s->d_adapt_count, 64));
     if (!s->d_adapt_rank) HIPCHK(hipMalloc((void**)&s->d_adapt_rank, sizeof(rt_rank_info)));
     while (s->adapt_events.size() < 2u * 18u) {
@@ -2236,6 +2288,119 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
     out.ms_render = (double)ms;
     out.rays = rays;
     out.reserved = pass_index;
+    s->pending_stats = out;
+    if (stats) *stats = out;
+    return RT_OK;
+}
+
+// ---- rt_render_variance (include/rt_abi.h).  B passes [c_{b-1}, c_b) over every pixel on the main kernel, as
+// rt_render_adaptive's first two passes run (they only park pixels, d_adapt_state in and out); after each the batch-means kernel
+// (rt_kernel_variance.hip) updates 24 bytes per pixel, and after the last it writes fb and the variance.  One enqueue, one wait.
+rt_status rt_render_variance(rt_scene* s, const rt_frame_desc* f, const rt_variance_desc* v, float* fb, int fb_on_device, float* variance_out,
+                             void* stream_v, rt_stats* stats) {
+    // argument checks: no HIP call before they pass
+    if (!s) return invalid("rt_render_variance: null scene");
+    if (!f) return invalid("rt_render_variance: null frame description");
+    if (!v) return invalid("rt_render_variance: null variance description");
+    if (!fb) return invalid("rt_render_variance: null fb");
+    if (!variance_out) return invalid("rt_render_variance: null variance_out");
+    if (v->batches < 2 || v->batches > 64) return invalid("rt_render_variance: batches must be in 2..64");
+    if (f->ns <= 0 || f->ns % v->batches != 0) return invalid("rt_render_variance: ns must be a positive multiple of batches");
+    if (f->nx <= 0 || f->ny <= 0 || (long long)f->nx * f->ny >= (1ll << 31)) return invalid("rt_render_variance: bad frame size");
+    const int local_rows = rt_frame_local_rows(f);
+    if (local_rows < 0) return invalid("rt_render_variance: bad row partition");
+    const int tiles_x = (f->nx + 7) / 8, tiles_y = (local_rows + 7) / 8;
+    if ((long long)tiles_x * tiles_y * 64 >= (1ll << 31)) return invalid("rt_render_variance: bad frame size (too many 8x8 tiles)");
+
+    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    if (s->frame_pending) { const rt_status st = rt_frame_finish(s, nullptr); if (st != RT_OK) return st; }
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const int B = v->batches, per = f->ns / B;
+    s->adapt_log.clear(); s->adapt_ms.clear();   // (rt_debug_adaptive_passes reports the last adaptive frame: this is none)
+    const size_t n_pixels = (size_t)local_rows * (size_t)f->nx;
+
+    rt_stats out;
+    memset(&out, 0, sizeof(out));
+    out.local_rows = local_rows;
+    out.samples = (uint64_t)n_pixels * (uint64_t)f->ns;
+    if (n_pixels == 0) { s->pending_stats = out; if (stats) *stats = out; return RT_OK; }
+
+    // ---- buffers: the adaptive frame's parked pixels and 4-byte-per-pixel map, the accumulators, a host fb's device image
+    const size_t floats = n_pixels * 3;
+    { const rt_status eb = ensure_adaptive_buffers(s, n_pixels, false); if (eb != RT_OK) return eb; }
+    if (s->var_capacity < n_pixels) {
+        if (s->d_var_acc) (void)hipFree(s->d_var_acc);
+        s->d_var_acc = nullptr; s->var_capacity = 0;
+        HIPCHK(hipMalloc((void**)&s->d_var_acc, n_pixels * 3 * sizeof(double)));
+        s->var_capacity = n_pixels;
+    }
+    float* d_fb = fb;
+    float* d_var = variance_out;
+    if (!fb_on_device) {
+        if (s->d_fb_floats < floats) {
+            if (s->d_fb) (void)hipFree(s->d_fb);
+            s->d_fb = nullptr; s->d_fb_floats = 0;
+            HIPCHK(hipMalloc((void**)&s->d_fb, floats * sizeof(float)));
+            s->d_fb_floats = floats;
+        }
+        d_fb = s->d_fb;
+        d_var = reinterpret_cast<float*>(s->d_adapt_spp);
+    }
+
+    // ---- the main kernel's frame parameters (rt_render_adaptive's: a pass only parks)
+    rt_frame_params fp;
+    memset(&fp, 0, sizeof(fp));
+    fp.fb = d_fb;
+    fp.ray_counter = s->d_ray_counter;
+    fp.work_counter = s->d_work_counter;
+    fp.seed_base = f->seed_base;
+    fp.nx = f->nx; fp.ny = f->ny; fp.ns = f->ns; fp.gamma = f->gamma;
+    fp.background[0] = f->background[0]; fp.background[1] = f->background[1]; fp.background[2] = f->background[2];
+    fp.use_gradient_bg = f->use_gradient_bg;
+    fp.tile_rows = f->tile_rows; fp.tile_first = f->tile_first; fp.tile_stride = f->tile_stride;
+    fp.local_rows = local_rows;
+    fp.tiles_x = tiles_x;
+    fp.work_items = (uint32_t)fp.tiles_x * (uint32_t)tiles_y * 64u;
+    fp.sparse_priority = g_opt.sparse_priority; fp.sparse_eager = g_opt.sparse_eager; fp.semi_priority = g_opt.semi_priority; fp.tier_priority = g_opt.tier_priority;
+    fp.steps_per_trip = g_opt.steps_per_trip;
+    fp.leaf_threshold = g_opt.leaf_threshold;
+    fp.diel_threshold = g_opt.diel_threshold;
+    fp.box_threshold = g_opt.box_threshold; fp.medium_threshold = g_opt.medium_threshold;
+    fp.state_out = s->d_adapt_state;
+    main_launch ml;
+    { const rt_status pl = plan_main_launch(s, RT_KERNEL_STAGED, n_pixels, fp, ml); if (pl != RT_OK) return pl; }
+    out.kernel_variant = RT_KERNEL_STAGED * 1000 + ml.lds_mode * 100 + s->tex_level * 10 + (s->spheres_only ? 1 : 0);
+    out.workgroups = (int)ml.grid.x; out.threads_per_group = (int)ml.block.x; out.lds_bytes = (int)ml.lds_bytes;
+
+    rt_variance_params vp;
+    memset(&vp, 0, sizeof(vp));
+    vp.state = s->d_adapt_state; vp.acc = s->d_var_acc; vp.fb = d_fb; vp.variance = d_var;
+    vp.n_pixels = (uint32_t)n_pixels; vp.per = per; vp.batches = B; vp.nx = f->nx; vp.gamma = f->gamma;
+
+    HIPCHK(hipMemsetAsync(s->d_ray_counter, 0, 256, stream));
+    HIPCHK(hipEventRecord(s->ev_start, stream));
+    for (int b = 1; b <= B; ++b) {
+        rt_frame_params q = fp;
+        q.sample_begin = (b - 1) * per; q.sample_end = b * per;
+        q.state_in = b > 1 ? s->d_adapt_state : nullptr;
+        HIPCHK(hipMemsetAsync(s->d_work_counter, 0, RT_WORK_COUNTER_BYTES, stream));
+        HIPCHK(launch_render(RT_KERNEL_STAGED, ml.lds_mode, s, q, ml.grid, ml.block, ml.lds_bytes, stream));
+        vp.c = b * per; vp.first = b == 1; vp.last = b == B;
+        HIPCHK(rt_launch_variance(vp, stream));
+    }
+    HIPCHK(hipEventRecord(s->ev_stop, stream));
+    if (!fb_on_device) {
+        HIPCHK(hipMemcpyAsync(fb, d_fb, floats * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(variance_out, d_var, n_pixels * sizeof(float), hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
+    unsigned long long rays = 0;
+    HIPCHK(hipMemcpy(&rays, s->d_ray_counter, sizeof(rays), hipMemcpyDeviceToHost));
+    out.ms_render = (double)ms;
+    out.rays = rays;
+    out.reserved = B;
     s->pending_stats = out;
     if (stats) *stats = out;
     return RT_OK;

@@ -348,3 +348,36 @@ struct rt_adaptive_params {
     float threshold, floor, gamma;
 };
 hipError_t rt_launch_adaptive(const rt_adaptive_params& p, hipStream_t st);
+
+// rt_denoise_variance (rt_kernel_denoise.hip): the variance-guided mode of the filter.  The fourth float of the colour record
+// carries the pixel's variance v_k instead of the colour sum (only the colour factor, which is off in this mode, reads that
+// sum), so a tap still costs two 16-byte reads and the workspace is rt_denoise's.  A second kernel argument beside
+// rt_denoise_params, which the existing instantiations keep as it is.
+struct rt_denoise_variance_params {
+    const float* variance;    // pack: ny * nx, what rt_render_variance writes
+    float* variance_out;      // last iteration: ny * nx, the filtered variance; null = not written
+    float sigma_variance;
+    float variance_floor;
+};
+hipError_t rt_launch_denoise_pack_variance(const rt_denoise_params& dp, const rt_denoise_variance_params& dv, bool guide, hipStream_t st);
+hipError_t rt_launch_denoise_variance(bool normal_on, bool depth_on, bool staged, const rt_denoise_params& dp, const rt_denoise_variance_params& dv,
+                                      hipStream_t st);
+
+// rt_render_variance (rt_kernel_variance.hip): after pass b of B, one lane per local pixel reads the pixel's parked colour sum at
+// c_b samples, forms the frame's float m_b as store_pixel does and updates the pixel's batch-means accumulators (include/rt_abi.h);
+// the last pass also writes the frame and the variance.
+#define RT_VARIANCE_THREADS 256
+struct rt_variance_params {
+    const rt_pixel_state* state;          // pixels parked at c samples
+    double* acc;                          // per local pixel: T_{b-1}, A, Q
+    float* fb;                            // last pass: compact local rows, nx * 3 floats each
+    float* variance;                      // last pass: compact local rows of nx floats
+    uint32_t n_pixels;
+    int32_t c;                            // c_b: samples in state
+    int32_t per;                          // n / B
+    int32_t batches;                      // B
+    int32_t first, last;                  // b == 1, b == B
+    int32_t nx;
+    float gamma;
+};
+hipError_t rt_launch_variance(const rt_variance_params& p, hipStream_t st);

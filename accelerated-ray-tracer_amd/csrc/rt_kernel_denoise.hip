@@ -10,6 +10,12 @@
 // Which one an iteration gets is the host's choice (rt_abi.hip, option "denoise_lds"); the arithmetic is the
 // same statements in the same order in both, so the choice changes no bit.
 //
+// rt_denoise_variance (second half of this file) is the same filter with a variance factor in the colour factor's place: the
+// record's fourth float is then the pixel's variance v_k, which its pack pass pre-blurs 3x3 from the planar input and every
+// iteration filters with the squared weights.  Its kernels are templates of their own, placed after rt_denoise's, and take
+// their extra arguments in a second block, so that rt_denoise's instantiations compile to the code they had before the mode
+// existed (profiles/variance_isa_unchanged.txt).
+//
 // Bounds: a tap outside the image is skipped by an index test before any address is formed; the staging loop loads only
 // the records inside the image, and a tap that passes the index test is inside the image and inside the staged window by
 // construction (|offset| <= 2 s), so no slot is read that was not written.  No address depends on pixel data.
@@ -39,6 +45,8 @@ __global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_denoise_pack_kernel(rt_
     }
 }
 
+// (rt_denoise_variance_kernel below repeats this kernel's tiling, staging, bounds tests and tap loop: a change to any of them
+// belongs in both)
 template <bool NRM, bool DEP, bool COL, bool STAGED>
 __global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_denoise_kernel(rt_denoise_params dp) {
     extern __shared__ float4 lds[];
@@ -176,4 +184,202 @@ hipError_t rt_launch_denoise_pack(const rt_denoise_params& dp, bool guide, hipSt
 hipError_t rt_launch_denoise(bool normal_on, bool depth_on, bool color_on, bool staged, const rt_denoise_params& dp, hipStream_t st) {
     if (normal_on) return depth_on ? launch_color<true, true>(color_on, staged, dp, st) : launch_color<true, false>(color_on, staged, dp, st);
     return depth_on ? launch_color<false, true>(color_on, staged, dp, st) : launch_color<false, false>(color_on, staged, dp, st);
+}
+
+// ---- the variance-guided mode (rt_denoise_variance) ----
+namespace {
+
+// t of the contract: carries the variance of r + g + b over to the demodulated image and back
+__device__ __forceinline__ float variance_scale(const float* albedo, size_t q) {
+    const float ar = fmaxf(albedo[3 * q], ALBEDO_FLOOR), ag = fmaxf(albedo[3 * q + 1], ALBEDO_FLOOR), ab = fmaxf(albedo[3 * q + 2], ALBEDO_FLOOR);
+    return 3.0f / ((ar + ag) + ab);
+}
+
+// the pack pass: x_0 and the guide record as rt_denoise_pack_kernel writes them, and in the colour record's fourth float
+// v_0 = the 3x3 binomial pre-blur of u, straight from the planar inputs
+template <bool GUIDE>
+__global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_denoise_pack_variance_kernel(rt_denoise_params dp, rt_denoise_variance_params dv) {
+    const size_t n = (size_t)dp.nx * dp.ny;
+    const size_t p = (size_t)blockIdx.x * RT_DENOISE_THREADS + threadIdx.x;
+    if (p >= n) return;
+    float r = dp.color[3 * p], g = dp.color[3 * p + 1], b = dp.color[3 * p + 2];
+    if (dp.demodulate) {
+        r = r / fmaxf(dp.albedo[3 * p], ALBEDO_FLOOR);
+        g = g / fmaxf(dp.albedo[3 * p + 1], ALBEDO_FLOOR);
+        b = b / fmaxf(dp.albedo[3 * p + 2], ALBEDO_FLOOR);
+    }
+    // (coordinates are unsigned: -1 wraps and compares as out of the image)
+    const unsigned j = (unsigned)(p / (size_t)dp.nx), i = (unsigned)(p - (size_t)j * dp.nx);
+    const float G[3] = {0.25f, 0.5f, 0.25f};
+    float num = 0.f, den = 0.f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const unsigned qy = j + (unsigned)dy;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const unsigned qx = i + (unsigned)dx;
+            if (qx >= (unsigned)dp.nx || qy >= (unsigned)dp.ny) continue;
+            const size_t q = (size_t)qy * dp.nx + qx;
+            float u = dv.variance[q];
+            if (dp.demodulate) {
+                const float t = variance_scale(dp.albedo, q);
+                u = (u * t) * t;
+            }
+            const float w = G[dy + 1] * G[dx + 1];
+            num = num + w * u;
+            den = den + w;
+        }
+    }
+    dp.x_out[p] = make_float4(r, g, b, num / den);
+    if (GUIDE) {
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (dp.normal) { q.x = dp.normal[3 * p]; q.y = dp.normal[3 * p + 1]; q.z = dp.normal[3 * p + 2]; }
+        if (dp.depth) q.w = dp.depth[p];
+        dp.guide[p] = q;
+    }
+}
+
+// one iteration: rt_denoise_kernel's tiling, staging, bounds rules and statements (its twin: keep the two in step), with the
+// variance factor as the last factor of a tap and the variance filtered beside the colour
+template <bool NRM, bool DEP, bool STAGED>
+__global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_denoise_variance_kernel(rt_denoise_params dp, rt_denoise_variance_params dv) {
+    extern __shared__ float4 lds[];
+    constexpr bool GUIDE = NRM || DEP;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nx = dp.nx, ny = dp.ny, s = dp.step;
+    const int by = (int)(blockIdx.x / (unsigned)dp.tiles_x), bx = (int)(blockIdx.x - (unsigned)by * (unsigned)dp.tiles_x);
+    const int x0 = bx * TILE, y0 = by * TILE;
+    const unsigned i = (unsigned)x0 + (wave & 1) * 8 + (lane & 7), j = (unsigned)y0 + (wave >> 1) * 8 + (lane >> 3);
+
+    const int lw = TILE + 4 * s, stride = rt_denoise_lds_stride(s);
+    const unsigned ox = (unsigned)x0 - 2u * s, oy = (unsigned)y0 - 2u * s;     // image coordinates of LDS slot (0, 0)
+    const float4* lc = lds;
+    const float4* lg = lds + stride * lw;
+    if (STAGED) {
+        for (int t = tid; t < lw * lw; t += RT_DENOISE_THREADS) {
+            const int ly = t / lw, lx = t - ly * lw;
+            const unsigned gx = ox + lx, gy = oy + ly;
+            if (gx < (unsigned)nx && gy < (unsigned)ny) {
+                const size_t q = (size_t)gy * nx + gx;
+                lds[ly * stride + lx] = dp.x_in[q];
+                if (GUIDE) lds[stride * lw + ly * stride + lx] = dp.guide[q];
+            }
+        }
+        __syncthreads();
+    }
+    if (i >= (unsigned)nx || j >= (unsigned)ny) return;
+
+    const size_t p = (size_t)j * nx + i;
+    float4 xp, gp = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (STAGED) {
+        const int c = (int)(j - oy) * stride + (int)(i - ox);
+        xp = lc[c];
+        if (GUIDE) gp = lg[c];
+    } else {
+        xp = dp.x_in[p];
+        if (GUIDE) gp = dp.guide[p];
+    }
+
+    const float H[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    const float sigma2 = dv.sigma_variance * dv.sigma_variance;
+    float W = 0.f, Sr = 0.f, Sg = 0.f, Sb = 0.f, Sv = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const unsigned qy = j + (unsigned)(s * dy);
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const unsigned qx = i + (unsigned)(s * dx);
+            if (qx >= (unsigned)nx || qy >= (unsigned)ny) continue;
+            float4 xq, gq = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (STAGED) {
+                const int c = (int)(qy - oy) * stride + (int)(qx - ox);
+                xq = lc[c];
+                if (GUIDE) gq = lg[c];
+            } else {
+                const size_t q = (size_t)qy * nx + qx;
+                xq = dp.x_in[q];
+                if (GUIDE) gq = dp.guide[q];
+            }
+            float w = H[dy + 2] * H[dx + 2];
+            if (dx != 0 || dy != 0) {
+                if (NRM) {
+                    float d = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
+                    d = fmaxf(d, 0.f);
+                    for (int m = 0; m < dp.normal_sharpness; ++m) d = d * d;
+                    w = w * d;
+                }
+                if (DEP) {
+                    const float den = dp.sigma_depth * fmaxf(gp.w, gq.w) + 1e-20f;
+                    const float r = fabsf(gp.w - gq.w) / den;
+                    const float t = fmaxf(1.f - r, 0.f);
+                    w = w * (t * t);
+                }
+                {   // the variance factor: the colour difference against what the two pixels' noise explains
+                    const float d1 = (fabsf(xp.x - xq.x) + fabsf(xp.y - xq.y)) + fabsf(xp.z - xq.z);
+                    const float den = sigma2 * (xp.w + xq.w) + dv.variance_floor;
+                    const float r = (d1 * d1) / den;
+                    const float t = fmaxf(1.f - r, 0.f);
+                    w = w * (t * t);
+                }
+            }
+            W = W + w;
+            Sr = Sr + w * xq.x;
+            Sg = Sg + w * xq.y;
+            Sb = Sb + w * xq.z;
+            Sv = Sv + (w * w) * xq.w;
+        }
+    }
+    float r = Sr / W, g = Sg / W, b = Sb / W, v = Sv / (W * W);
+    if (!dp.last) {
+        dp.x_out[p] = make_float4(r, g, b, v);
+        return;
+    }
+    if (dp.demodulate) {
+        r = r * fmaxf(dp.albedo[3 * p], ALBEDO_FLOOR);
+        g = g * fmaxf(dp.albedo[3 * p + 1], ALBEDO_FLOOR);
+        b = b * fmaxf(dp.albedo[3 * p + 2], ALBEDO_FLOOR);
+    }
+    dp.out[3 * p] = r;
+    dp.out[3 * p + 1] = g;
+    dp.out[3 * p + 2] = b;
+    if (dv.variance_out) {
+        if (dp.demodulate) {
+            const float t = variance_scale(dp.albedo, p);
+            v = (v / t) / t;
+        }
+        dv.variance_out[p] = v;
+    }
+}
+
+template <bool NRM, bool DEP, bool STAGED>
+hipError_t launch_variance(const rt_denoise_params& dp, const rt_denoise_variance_params& dv, hipStream_t st) {
+    const size_t lds = STAGED ? rt_denoise_lds_bytes(dp.step, NRM || DEP) : 0;
+    if (lds > 65536) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_denoise_variance_kernel<NRM, DEP, STAGED>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const unsigned tiles_y = ((unsigned)dp.ny + TILE - 1) / TILE;
+    hipLaunchKernelGGL((rt_denoise_variance_kernel<NRM, DEP, STAGED>), dim3((unsigned)dp.tiles_x * tiles_y), dim3(RT_DENOISE_THREADS), lds, st, dp, dv);
+    return hipGetLastError();
+}
+template <bool NRM, bool DEP>
+hipError_t launch_variance_staged(bool staged, const rt_denoise_params& dp, const rt_denoise_variance_params& dv, hipStream_t st) {
+    return staged ? launch_variance<NRM, DEP, true>(dp, dv, st) : launch_variance<NRM, DEP, false>(dp, dv, st);
+}
+
+}  // namespace
+
+hipError_t rt_launch_denoise_pack_variance(const rt_denoise_params& dp, const rt_denoise_variance_params& dv, bool guide, hipStream_t st) {
+    const size_t n = (size_t)dp.nx * dp.ny;
+    const dim3 grid((unsigned)((n + RT_DENOISE_THREADS - 1) / RT_DENOISE_THREADS));
+    if (guide) hipLaunchKernelGGL(rt_denoise_pack_variance_kernel<true>, grid, dim3(RT_DENOISE_THREADS), 0, st, dp, dv);
+    else hipLaunchKernelGGL(rt_denoise_pack_variance_kernel<false>, grid, dim3(RT_DENOISE_THREADS), 0, st, dp, dv);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_denoise_variance(bool normal_on, bool depth_on, bool staged, const rt_denoise_params& dp, const rt_denoise_variance_params& dv,
+                                      hipStream_t st) {
+    if (normal_on) return depth_on ? launch_variance_staged<true, true>(staged, dp, dv, st) : launch_variance_staged<true, false>(staged, dp, dv, st);
+    return depth_on ? launch_variance_staged<false, true>(staged, dp, dv, st) : launch_variance_staged<false, false>(staged, dp, dv, st);
 }

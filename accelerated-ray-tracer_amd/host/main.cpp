@@ -7,13 +7,16 @@
 // `--scene bouncing` is case 1, `--scene final` case 9.
 //
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
-//             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K]] [--list]
+//             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K] [--denoise-variance [B]]] [--list]
 //
 // --denoise [K] filters the frame with rt_denoise (K iterations, 5 when K is left out; the binding's other defaults): the frame
 // is rendered at gamma 1, the feature pass (albedo, normal, depth at min(ns, 16) samples) guides the filter, and the frame's
 // gamma is applied on the host afterwards -- as powf(c, 1 / gamma) per channel, so the image is not rt_render's bit for bit
 // even where the filter changes nothing.  With --aov PREFIX the unfiltered frame is written to PREFIX_noisy.ppm as well.  Works
 // with --adaptive; not with --progressive or --gpus > 1.
+// --denoise-variance [B] (needs --denoise) makes the filter variance-guided (rt_denoise_variance, the binding's defaults): the
+// frame comes from rt_render_variance with B batches -- when B is left out, the largest divisor of --ns in 2..16 (an --ns without one is refused) -- and
+// its per-pixel variance takes the colour factor's place.  --ns must be a multiple of B (2..64).  Not with --adaptive.
 // --aov PREFIX also writes the frame's feature buffers (rt_render_aov, same camera, seed and sample count) next to the image,
 // in the image's PPM flavour: PREFIX.albedo.ppm, PREFIX.normal.ppm (0.5 n + 0.5) and PREFIX.depth.ppm (grey, the ray parameter
 // t over the frame's largest).  Not with --gpus > 1.
@@ -46,7 +49,7 @@ int main(int argc, char** argv) {
     int nx = 0, ny = 0, ns = 0, device = 0, gpus = 1, progressive = 0;
     bool p6 = false, adaptive = false;
     float threshold = 0.f;
-    int min_spp = 0, denoise = 0;
+    int min_spp = 0, denoise = 0, batches = -1;   // batches: -1 = no --denoise-variance, 0 = B left out
     unsigned long long seed = 1984ull;
     for (int a = 1; a < argc; ++a) {
         std::string k = argv[a];
@@ -69,6 +72,13 @@ int main(int argc, char** argv) {
             if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') denoise = atoi(argv[++a]);
             if (denoise < 1 || denoise > 8) { fprintf(stderr, "--denoise K: K must be in 1..8\n"); return 2; }
         }
+        else if (k == "--denoise-variance") {   // B is optional, as K above
+            batches = 0;
+            if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') {
+                batches = atoi(argv[++a]);
+                if (batches < 2 || batches > 64) { fprintf(stderr, "--denoise-variance B: B must be in 2..64\n"); return 2; }
+            }
+        }
         else if (k == "--list") { int n = 0; const char* const* v = rtw::scene_names(&n); for (int i = 0; i < n; ++i) printf("%s\n", v[i]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); return 2; }
     }
@@ -76,6 +86,8 @@ int main(int argc, char** argv) {
     if (adaptive && (progressive > 0 || gpus > 1)) { fprintf(stderr, "--adaptive cannot be combined with --progressive or --gpus > 1\n"); return 2; }
     if (!aov_prefix.empty() && gpus > 1) { fprintf(stderr, "--aov cannot be combined with --gpus > 1\n"); return 2; }
     if (denoise && (progressive > 0 || gpus > 1)) { fprintf(stderr, "--denoise cannot be combined with --progressive or --gpus > 1\n"); return 2; }
+    if (batches >= 0 && !denoise) { fprintf(stderr, "--denoise-variance needs --denoise\n"); return 2; }
+    if (batches >= 0 && adaptive) { fprintf(stderr, "--denoise-variance cannot be combined with --adaptive\n"); return 2; }
     if (min_spp > 0 && !adaptive) { fprintf(stderr, "--min-spp needs --adaptive\n"); return 2; }
 
     std::vector<unsigned char> tex;
@@ -88,6 +100,15 @@ int main(int argc, char** argv) {
     auto scene = rtw::build_scene(scene_name, nx, ny, tex.empty() ? nullptr : tex.data(), tw, th, err);
     if (!scene) { fprintf(stderr, "%s\n", err.c_str()); return 2; }
     if (ns > 0) scene->ns = ns;
+    if (batches == 0) {   // the largest divisor of ns that is at most 16
+        batches = scene->ns < 16 ? scene->ns : 16;
+        while (batches > 1 && scene->ns % batches) --batches;
+    }
+    if (batches == 1) { fprintf(stderr, "--denoise-variance: --ns %d has no divisor in 2..16; give B (2..64, a divisor of --ns)\n", scene->ns); return 2; }
+    if (batches >= 0 && scene->ns % batches) {
+        fprintf(stderr, "--denoise-variance: --ns %d is not a multiple of B = %d\n", scene->ns, batches);
+        return 2;
+    }
 
     rtw::flat_scene flat;
     rt_status st = rtw::flatten(scene->world, *scene->cam, flat, err, scene->created.data(), (int)scene->created.size());
@@ -104,7 +125,7 @@ int main(int argc, char** argv) {
     f.tile_rows = scene->ny; f.tile_first = 0; f.tile_stride = 1;
     if (denoise) f.gamma = 1.0f;   // the filter works on the linear frame; the gamma is applied after it, below
 
-    std::vector<float> fb((size_t)scene->nx * scene->ny * 3);
+    std::vector<float> fb((size_t)scene->nx * scene->ny * 3), variance;
     rt_stats stats;
     rt_scene* dev_scene = nullptr;
     rt_multi* multi = nullptr;
@@ -141,6 +162,11 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "samples [%d, %d): %.3f ms\n", begin, end, part.ms_render);
             }
             check(rt_progressive_state_destroy(dev_scene, state), "rt_progressive_state_destroy");
+        } else if (batches >= 2) {
+            rt_variance_desc vd;
+            vd.batches = batches; vd.reserved = 0;
+            variance.resize((size_t)scene->nx * scene->ny);
+            check(rt_render_variance(dev_scene, &f, &vd, fb.data(), /*fb_on_device=*/0, variance.data(), /*stream=*/nullptr, &stats), "rt_render_variance");
         } else {
             check(rt_render(dev_scene, &f, fb.data(), /*fb_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1, &stats), "rt_render");
         }
@@ -179,7 +205,16 @@ int main(int argc, char** argv) {
         dn.out = fb.data();
         dn.iterations = denoise; dn.normal_sharpness = 4; dn.demodulate = 1;
         dn.sigma_color = 2.0f; dn.color_floor = 0.01f; dn.sigma_depth = 0.2f;
-        check(rt_denoise(&dn, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_denoise");
+        if (batches >= 2) {
+            rt_denoise_variance_desc dv;
+            memset(&dv, 0, sizeof(dv));
+            dv.variance = variance.data();
+            dv.sigma_variance = 3.0f; dv.variance_floor = 1e-4f;
+            dn.sigma_color = 0.0f;
+            check(rt_denoise_variance(&dn, &dv, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_denoise_variance");
+        } else {
+            check(rt_denoise(&dn, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_denoise");
+        }
         apply_gamma(fb);
     }
 

@@ -478,6 +478,65 @@ typedef struct rt_adaptive_desc {
 rt_status rt_render_adaptive(rt_scene* scene, const rt_frame_desc* f, const rt_adaptive_desc* a, float* fb, int fb_on_device,
                              int32_t* spp_out, void* stream, rt_stats* stats);
 
+/* ---- per-pixel variance: a frame plus an estimate of how noisy each of its pixels is ----
+ * rt_render_variance renders the pixels the frame description assigns to the call (row partition as rt_render) at n = f->ns
+ * samples and, beside the frame, writes per pixel the estimated variance of the pixel's mean of r + g + b, by batch means:
+ * the n samples of a pixel are cut into B = v->batches consecutive batches of n / B samples, and the spread of the B batch
+ * averages estimates the variance of their mean.  Parameters: 2 <= B <= 64 and n % B == 0 (so n >= B).
+ * The contract, checkable from frames alone.  Let c_b = b * (n / B) for b = 0..B, and m_b the float triple the frame would
+ * hold at ns = c_b with gamma 1 -- the colour sum of the first c_b samples times (float)(1.0 / (double)(float)c_b), per
+ * channel, as store_pixel forms it (each pixel is one chain seeded by seed_base + its index, so the first c_b samples of a
+ * frame at ns = n are the frame at ns = c_b); m_0 is not used.  Per pixel, in double, left to right, nothing contracted:
+ *     s_b = ((double)m_b.x + (double)m_b.y) + (double)m_b.z,   T_b = (double)c_b * s_b,   T_0 = 0,
+ *     y_b = (T_b - T_{b-1}) / (double)(n / B)                       for b = 1..B   (the average of batch b alone),
+ *     A = A + y_b,   Q = Q + y_b * y_b,   both from 0,              for b = 1..B,
+ *     mu = A / B,   v = Q / B - mu * mu,   v = (v > 0) ? v : 0      (so a NaN gives 0),
+ *     variance_out = (float)(v / (double)(B - 1)).
+ * fb is bit for bit what rt_render writes at ns = n with the frame's gamma; variance_out (required; the same kind of memory as
+ * fb, compact local rows of nx floats) is linear whatever the gamma.  stats: rays and samples are rt_render's, ms_render = device
+ * time from the first pass to the last, reserved = render passes (B).
+ * Passes: [c_{b-1}, c_b) over every pixel, b = 1..B, each followed by one small kernel that updates 24 bytes per pixel; the
+ * whole frame is enqueued on `stream` with no host round trip between passes, then the call waits for it (a host fb /
+ * variance_out is copied back at the end).  The passes have no cost-aware schedule: a variance frame costs more than
+ * rt_render's (measured 1.5 - 3.1 x).  A null scene, f, v, fb or variance_out, a B outside 2..64, an ns that is not a positive
+ * multiple of B, or a bad frame size or partition is RT_ERR_INVALID before any HIP call, and rt_last_error_detail() names the
+ * failed check.  The call is a frame of the scene: not re-entrant per scene; a pending non-blocking rt_render of the scene is
+ * finished first. */
+typedef struct rt_variance_desc { int32_t batches, reserved; } rt_variance_desc; /* 8 B */
+rt_status rt_render_variance(rt_scene* scene, const rt_frame_desc* f, const rt_variance_desc* v, float* fb, int fb_on_device,
+                             float* variance_out, void* stream, rt_stats* stats);
+
+/* ---- denoiser, variance-guided: rt_denoise with a variance factor in the colour factor's place ----
+ * rt_denoise's colour factor compares two noisy estimates with each other and so turns away exactly the noisy neighbours
+ * that should be averaged.  rt_denoise_variance asks instead whether two pixels differ by more than their noise explains: it
+ * takes the per-pixel variance rt_render_variance writes, filters it along with the colour, and weighs a tap by the squared
+ * colour difference over the two pixels' variances.
+ * Everything of rt_denoise's contract holds -- the arithmetic rule, the buffers, the workspace of rt_denoise_workspace_bytes
+ * (it does not grow), option "denoise_lds", out == color -- with these differences:
+ *   Parameters.  d->sigma_color must be 0 (the variance factor REPLACES the colour factor); vd->sigma_variance finite and in
+ *     [1e-6, 1e6]; vd->variance_floor finite and > 0; vd->variance non-null: ny x nx floats, the variance of the mean of
+ *     r + g + b per pixel.  vd->variance_out (ny x nx, optional) may overlap no other buffer.
+ *   Prepare.  u = variance, or when demodulating, with a' = max(albedo, 2^-10) per channel at the same pixel:
+ *     t = 3.0f / ((a'.r + a'.g) + a'.b),  u(q) = (variance(q) t) t.  v_0(p) is a 3x3 pre-blur of u: num = den = 0; for
+ *     dy = -1..1 (outer), dx = -1..1 (inner), a tap outside the image is skipped, g = G[dy] G[dx] with G = {1/4, 1/2, 1/4},
+ *     num = num + g u(q), den = den + g;  v_0 = num / den.
+ *   Iteration k.  Every tap but the centre takes, after the normal and depth factors, one more factor on x_k and v_k:
+ *     d1 = (|dr| + |dg|) + |db|;  den = (sigma_variance sigma_variance) (vp + vq) + variance_floor;  r = (d1 d1) / den;
+ *     t = max(1 - r, 0);  the factor is t t.  Beside W and S every tap, the centre included, adds with its final w
+ *     Sv = Sv + (w w) vq, Sv from 0;  after the 25 taps v_{k+1}(p) = Sv / (W W).
+ *   Finish.  variance_out = (v_K / t) / t when demodulating (t of the pixel, as above), else v_K.
+ * Only + - * /, max, abs and comparisons occur; there is no square root.  The variance is expected to be finite and >= 0
+ * (zeros are fine: the floor keeps den positive); what a negative or non-finite one does to the pixels within reach of it is
+ * unspecified, but nothing faults: no address depends on data.  tests/variance_expect.py restates this in NumPy float32; the
+ * device result equals it bit for bit.  A null d or vd and every violation above is RT_ERR_INVALID before any HIP call, and
+ * rt_last_error_detail() names the failed check. */
+typedef struct rt_denoise_variance_desc {
+    const float* variance;     /* ny*nx, what rt_render_variance writes; required */
+    float* variance_out;       /* ny*nx or null: the filtered variance */
+    float sigma_variance, variance_floor;
+} rt_denoise_variance_desc; /* 24 B */
+rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_variance_desc* vd, int buffers_on_device, void* stream, int blocking);
+
 /* ---- several GPUs of one node from one host thread ----
  * The reference is single-GPU (one render<<<>>> launch, main.cu:707); these entry points are what its host function
  * would call to spread that launch over the N GPUs of a node: rt_init_devices(N) replaces rt_init, rt_multi_create /
