@@ -83,6 +83,10 @@ class RtAovDesc(C.Structure):
                 ("prim", C.c_void_p), ("inst", C.c_void_p), ("mat", C.c_void_p)]
 
 
+class RtAovThroughDesc(C.Structure):
+    _fields_ = [("max_bounces", C.c_int32), ("fuzz_limit", C.c_float), ("through", C.c_void_p), ("bounces", C.c_void_p)]
+
+
 class RtDenoiseDesc(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("color", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p),
                 ("depth", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
@@ -120,6 +124,10 @@ TraceResult = collections.namedtuple("TraceResult", "t prim inst point normal uv
 # DeviceScene.render_aov(): the outputs of rt_render_aov -> (channels, numpy dtype)
 AOV_OUTPUTS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "alpha": (1, np.float32),
                "prim": (1, np.int32), "inst": (1, np.int32), "mat": (1, np.int32)}
+# DeviceScene.render_aov_through(): rt_render_aov's outputs and the two of rt_aov_through_desc
+AOV_THROUGH_OUTPUTS = dict(AOV_OUTPUTS, through=(1, np.float32), bounces=(1, np.int32))
+# ... and its keyword defaults; fuzz_limit settled on the oracle's 4-spp frames
+AOV_THROUGH_DEFAULTS = {"max_bounces": 8, "fuzz_limit": 0.0}
 # denoise(): the keyword defaults (they live here, not in the ABI); settled on the oracle's 4-spp frames
 DENOISE_DEFAULTS = {"iterations": 5, "normal_sharpness": 4, "sigma_depth": 0.2, "sigma_color": 2.0, "color_floor": 0.01}
 # denoise(variance=...): the keyword defaults of the variance factor, settled by a sweep on the same frames
@@ -142,7 +150,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_multi_destroy", "rt_multi_device_count", "rt_multi_row_owner", "rt_multi_probe_rccl", "rt_multi_debug_uninterleave",
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
                   "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive",
-                  "rt_radiance_rays", "rt_render_aov", "rt_denoise_workspace_bytes", "rt_denoise", "rt_render_variance",
+                  "rt_radiance_rays", "rt_render_aov", "rt_render_aov_through", "rt_denoise_workspace_bytes", "rt_denoise", "rt_render_variance",
                   "rt_denoise_variance"]
 
 _rt = None
@@ -218,6 +226,8 @@ def rt_lib():
         L.rt_trace_rays.argtypes = [C.c_void_p, C.POINTER(RtRayBatch), C.c_void_p, C.c_int]
         L.rt_radiance_rays.argtypes = [C.c_void_p, C.POINTER(RtRadianceBatch), C.c_void_p, C.c_int]
         L.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAovDesc), C.c_int, C.c_void_p, C.c_int]
+        L.rt_render_aov_through.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtAovDesc), C.POINTER(RtAovThroughDesc), C.c_int,
+                                            C.c_void_p, C.c_int]
         L.rt_denoise_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
         L.rt_denoise_workspace_bytes.restype = C.c_size_t
         L.rt_denoise.argtypes = [C.POINTER(RtDenoiseDesc), C.c_int, C.c_void_p, C.c_int]
@@ -477,6 +487,16 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_D
     return out
 
 
+def _chain_args(max_bounces, fuzz_limit):
+    """(max_bounces, fuzz_limit) of render_aov_through as rt_aov_through_desc takes them, or ValueError."""
+    if isinstance(max_bounces, bool) or not isinstance(max_bounces, (int, np.integer)) or not 0 <= int(max_bounces) <= 16:
+        raise ValueError("max_bounces must be an integer in 0..16")
+    fuzz_limit = float(fuzz_limit)
+    if not (np.isfinite(fuzz_limit) and 0 <= fuzz_limit <= float(np.finfo(np.float32).max)):
+        raise ValueError("fuzz_limit must be finite and >= 0")
+    return int(max_bounces), fuzz_limit
+
+
 class DeviceScene:
     """rt_scene*: the flattened scene resident in HBM."""
 
@@ -693,27 +713,32 @@ class DeviceScene:
         looked at -- all numpy arrays (the call waits), or all contiguous torch tensors on this scene's device, zero-copy,
         enqueued on `stream` (a hipStream_t as an integer or a torch.cuda.Stream) and waited for only with blocking=True.
         Returns the dict.  Malformed arguments raise ValueError before anything is launched."""
+        names = [k for k, on in (("albedo", albedo), ("normal", normal), ("depth", depth), ("alpha", alpha)) if on]
+        names += ["prim", "inst", "mat"] if ids else []
+        return self._aov_call(frame, names, out, None, stream, blocking)
+
+    def _aov_call(self, frame, names, out, chain, stream, blocking) -> dict:
+        """render_aov (chain None) and render_aov_through (chain = (max_bounces, fuzz_limit)): the outputs `names`, or `out`."""
         L = rt_lib()
+        table = AOV_OUTPUTS if chain is None else AOV_THROUGH_OUTPUTS
         rows = L.rt_frame_local_rows(C.byref(frame))
         if frame.nx <= 0 or frame.ny <= 0 or frame.ns <= 0 or rows < 0:
             raise ValueError("bad frame size, sample count or row partition")
         if out is None:
-            names = [k for k, on in (("albedo", albedo), ("normal", normal), ("depth", depth), ("alpha", alpha)) if on]
-            names += ["prim", "inst", "mat"] if ids else []
-            out = {k: np.empty((rows, frame.nx, 3) if AOV_OUTPUTS[k][0] == 3 else (rows, frame.nx), AOV_OUTPUTS[k][1]) for k in names}
+            out = {k: np.empty((rows, frame.nx, 3) if table[k][0] == 3 else (rows, frame.nx), table[k][1]) for k in names}
         if not isinstance(out, dict) or not out:
             raise ValueError("no output is requested")
         on_host = all(isinstance(v, np.ndarray) for v in out.values())
-        a = RtAovDesc()
+        a, t = RtAovDesc(), RtAovThroughDesc()
         for k, v in out.items():
-            if k not in AOV_OUTPUTS:
-                raise ValueError(f"unknown output '{k}': one of {', '.join(AOV_OUTPUTS)} is expected")
-            ch, dtype = AOV_OUTPUTS[k]
+            if k not in table:
+                raise ValueError(f"unknown output '{k}': one of {', '.join(table)} is expected")
+            ch, dtype = table[k]
             size = rows * frame.nx * ch
             if on_host:
                 if v.dtype != dtype or v.size != size or not v.flags["C_CONTIGUOUS"]:
                     raise ValueError(f"{k}: a C-contiguous {np.dtype(dtype).name} array of {size} elements is expected")
-                setattr(a, k, v.ctypes.data)
+                setattr(a if k in AOV_OUTPUTS else t, k, v.ctypes.data)
             else:
                 import torch
                 want = torch.float32 if dtype == np.float32 else torch.int32
@@ -721,17 +746,42 @@ class DeviceScene:
                     raise ValueError("out: all numpy arrays or all torch tensors are expected")
                 if v.dtype != want or v.numel() != size or not v.is_contiguous() or v.device != torch.device("cuda", self.device):
                     raise ValueError(f"{k}: a contiguous {want} tensor of {size} elements on cuda:{self.device} is expected")
-                setattr(a, k, v.data_ptr())
+                setattr(a if k in AOV_OUTPUTS else t, k, v.data_ptr())
         if hasattr(stream, "cuda_stream"):
             stream = stream.cuda_stream
-        st = L.rt_render_aov(self._p, C.byref(frame), C.byref(a), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None,
-                             1 if blocking else 0)
+        args = (0 if on_host else 1, C.c_void_p(int(stream)) if stream else None, 1 if blocking else 0)
+        if chain is None:
+            st = L.rt_render_aov(self._p, C.byref(frame), C.byref(a), *args)
+        else:
+            t.max_bounces, t.fuzz_limit = chain
+            st = L.rt_render_aov_through(self._p, C.byref(frame), C.byref(a), C.byref(t), *args)
         if st == 1:
             raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_render_aov")
+        _check(st, "rt_render_aov" if chain is None else "rt_render_aov_through")
         return out
 
-    def render_denoised(self, frame: RtFrameDesc, variance: bool = False, batches=None, **denoise_args) -> dict:
+    def render_aov_through(self, frame: RtFrameDesc, max_bounces: int = AOV_THROUGH_DEFAULTS["max_bounces"],
+                           fuzz_limit: float = AOV_THROUGH_DEFAULTS["fuzz_limit"], albedo: bool = True, normal: bool = True,
+                           depth: bool = True, alpha: bool = True, ids: bool = False, through: bool = False, bounces: bool = False,
+                           out=None, stream=0, blocking: bool = True) -> dict:
+        """Feature buffers of `frame` at the first non-specular surface (rt_render_aov_through): every sample of render_aov is
+        followed through glass (refracted, or mirrored under total internal reflection) and off metals whose fuzz is at most
+        fuzz_limit, for at most max_bounces (0..16) bounces; albedo is the surface's where the chain ends times the tint of the
+        mirrors on the way, normal is that surface's, depth the whole way in the primary ray's parameter (include/rt_abi.h).
+        through=True adds the share of the pixel's samples that followed at least one bounce, bounces=True the first
+        sample's bounce count (int32).  max_bounces=0 is render_aov.
+
+        out, stream, blocking and the returned dict: as render_aov, with the keys of AOV_THROUGH_OUTPUTS.  Malformed arguments
+        raise ValueError before anything is launched."""
+        chain = _chain_args(max_bounces, fuzz_limit)
+        names = [k for k, on in (("albedo", albedo), ("normal", normal), ("depth", depth), ("alpha", alpha)) if on]
+        names += ["prim", "inst", "mat"] if ids else []
+        names += [k for k, on in (("through", through), ("bounces", bounces)) if on]
+        return self._aov_call(frame, names, out, chain, stream, blocking)
+
+    def render_denoised(self, frame: RtFrameDesc, variance: bool = False, batches=None, through: bool = False,
+                        max_bounces: int = AOV_THROUGH_DEFAULTS["max_bounces"], fuzz_limit: float = AOV_THROUGH_DEFAULTS["fuzz_limit"],
+                        **denoise_args) -> dict:
         """A denoised frame: render() of `frame` at gamma 1, render_aov() of it (albedo, normal, depth at min(frame.ns, 16)
         samples) and denoise() of the two (its keyword arguments pass through).  Returns {"color": the denoised linear
         frame, "noisy": the render, "albedo", "normal", "depth"} as numpy arrays.  The frame must be the whole image: a
@@ -739,13 +789,18 @@ class DeviceScene:
 
         variance=True: the frame comes from render_variance() -- `batches` batches, by default the largest divisor of
         frame.ns in 2..16 (a frame.ns without one, such as 1 or 17, is ValueError: pass batches) -- and the filter runs variance-guided
-        (denoise(variance=...)); the result also holds "variance", the render's per-pixel variance."""
+        (denoise(variance=...)); the result also holds "variance", the render's per-pixel variance.
+
+        through=True: the guides come from render_aov_through(max_bounces, fuzz_limit) -- the surfaces seen through glass and
+        in mirrors -- instead of render_aov."""
         if frame.nx <= 0 or frame.ny <= 0 or frame.ns <= 0:
             raise ValueError("bad frame size or sample count")
         if frame.tile_first != 0 or frame.tile_stride != 1 or frame.tile_rows < frame.ny:
             raise ValueError("render_denoised needs the whole frame (tile_rows >= ny, tile_first = 0, tile_stride = 1)")
         if not variance and batches is not None:
             raise ValueError("batches needs variance=True")
+        if through:
+            max_bounces, fuzz_limit = _chain_args(max_bounces, fuzz_limit)
         f = RtFrameDesc.from_buffer_copy(frame)
         f.gamma = 1.0
         var = None
@@ -760,7 +815,7 @@ class DeviceScene:
         else:
             noisy, _ = self.render(f)
         f.ns = min(frame.ns, 16)
-        aov = self.render_aov(f, alpha=False)
+        aov = self.render_aov_through(f, max_bounces, fuzz_limit, alpha=False) if through else self.render_aov(f, alpha=False)
         if variance:
             denoise_args = dict(denoise_args, variance=var)
         color = denoise(noisy, aov["albedo"], aov["normal"], aov["depth"], **denoise_args)

@@ -90,6 +90,7 @@ struct rt_options {
     int trace_tree = 1;          // rt_trace_rays: 1 = the walk array, 0 = the reference's full tree
     int radiance_lds = -1;       // rt_radiance_rays: as trace_lds
     int aov_lds = -1;            // rt_render_aov: as trace_lds
+    int aov_through_lds = -1;    // rt_render_aov_through: as trace_lds
     int denoise_lds = -1;        // rt_denoise: -1 = iterations with taps up to 4 pixels apart stage tile + halo in LDS, 0 = never,
                                  // 1 = wherever the tile fits (taps up to 8 apart)
     int adaptive_tier = -1;      // rt_render_adaptive: -1 = a pass goes to the tier kernel when its active pixels fit the tier waves at once
@@ -676,6 +677,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "trace_lds") { if (value < -1 || value > 2) return invalid("trace_lds: -1 (auto) .. 2"); g_opt.trace_lds = value; }
     else if (k == "radiance_lds") { if (value < -1 || value > 2) return invalid("radiance_lds: -1 (auto) .. 2"); g_opt.radiance_lds = value; }
     else if (k == "aov_lds") { if (value < -1 || value > 2) return invalid("aov_lds: -1 (auto) .. 2"); g_opt.aov_lds = value; }
+    else if (k == "aov_through_lds") { if (value < -1 || value > 2) return invalid("aov_through_lds: -1 (auto) .. 2"); g_opt.aov_through_lds = value; }
     else if (k == "denoise_lds") { if (value < -1 || value > 1) return invalid("denoise_lds: -1 (auto), 0 (direct) or 1 (staged)"); g_opt.denoise_lds = value; }
     else if (k == "trace_tree") { if (value < 0 || value > 1) return invalid("trace_tree: 0 (reference tree) or 1 (walk array)"); g_opt.trace_tree = value; }
     else if (k == "adaptive_tier") { if (value < -1 || value > 1) return invalid("adaptive_tier: -1 (auto), 0 (main kernel) or 1 (tier kernel)"); g_opt.adaptive_tier = value; }
@@ -1339,36 +1341,50 @@ rt_status rt_radiance_rays(rt_scene* s, const rt_radiance_batch* b, void* stream
     return RT_OK;
 }
 
-rt_status rt_render_aov(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* a, int buffers_on_device, void* stream_v, int blocking) {
+// rt_render_aov (t null) and rt_render_aov_through (t non-null, checked by the caller for null): one body, `who` names the entry
+// point in the texts of failed checks
+static rt_status aov_impl(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* a, const rt_aov_through_desc* t, const char* who_c,
+                          int buffers_on_device, void* stream_v, int blocking) {
     // argument checks: no HIP call and no look at the scene before they pass
-    if (!f) return invalid("rt_render_aov: null frame description");
-    if (!a) return invalid("rt_render_aov: null output description");
-    if (!a->albedo && !a->normal && !a->depth && !a->alpha && !a->prim && !a->inst && !a->mat) return invalid("rt_render_aov: every output is null");
-    if (f->nx <= 0 || f->ny <= 0 || f->ns <= 0) return invalid("rt_render_aov: nx, ny and ns must be positive");
-    if ((long long)f->nx * f->ny >= (1ll << 31)) return invalid("rt_render_aov: frame too large");
+    const std::string who(who_c);
+    auto bad = [&](const char* why) { return invalid((who + ": " + why).c_str()); };
+    if (!f) return bad("null frame description");
+    if (!a) return bad("null output description");
+    if (t) {
+        if (t->max_bounces < 0 || t->max_bounces > 16) return bad("max_bounces must be in 0..16");
+        if (!(std::isfinite(t->fuzz_limit) && t->fuzz_limit >= 0.f)) return bad("fuzz_limit must be finite and >= 0");
+    }
+    if (!a->albedo && !a->normal && !a->depth && !a->alpha && !a->prim && !a->inst && !a->mat && !(t && (t->through || t->bounces)))
+        return bad("every output is null");
+    if (f->nx <= 0 || f->ny <= 0 || f->ns <= 0) return bad("nx, ny and ns must be positive");
+    if ((long long)f->nx * f->ny >= (1ll << 31)) return bad("frame too large");
     const int local_rows = rt_frame_local_rows(f);
-    if (local_rows < 0) return invalid("rt_render_aov: bad row partition");
+    if (local_rows < 0) return bad("bad row partition");
     const int tiles_x = (f->nx + 7) / 8, tiles_y = (local_rows + 7) / 8;
-    if ((long long)tiles_x * tiles_y * 64 >= (1ll << 31)) return invalid("rt_render_aov: frame too large");
-    if (!s) return invalid("rt_render_aov: null scene");
+    if ((long long)tiles_x * tiles_y * 64 >= (1ll << 31)) return bad("frame too large");
+    if (!s) return bad("null scene");
     if (local_rows == 0) return RT_OK;
     { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
 
     rt_aov_params ap;
     memset(&ap, 0, sizeof(ap));
+    rt_aov_through_params tp;
+    memset(&tp, 0, sizeof(tp));
     const size_t pixels = (size_t)local_rows * f->nx;
     struct out_buffer { void* user; size_t bytes; const char* what; void** dev; };
     const out_buffer outs[] = {
         {a->albedo, 3 * pixels * sizeof(float), "albedo", (void**)&ap.albedo}, {a->normal, 3 * pixels * sizeof(float), "normal", (void**)&ap.normal},
         {a->depth, pixels * sizeof(float), "depth", (void**)&ap.depth}, {a->alpha, pixels * sizeof(float), "alpha", (void**)&ap.alpha},
         {a->prim, pixels * sizeof(int32_t), "prim", (void**)&ap.prim}, {a->inst, pixels * sizeof(int32_t), "inst", (void**)&ap.inst},
-        {a->mat, pixels * sizeof(int32_t), "mat", (void**)&ap.mat}};
+        {a->mat, pixels * sizeof(int32_t), "mat", (void**)&ap.mat},
+        {t ? t->through : nullptr, pixels * sizeof(float), "through", (void**)&tp.through},
+        {t ? t->bounces : nullptr, pixels * sizeof(int32_t), "bounces", (void**)&tp.bounces}};
     // host buffers are staged in one allocation of this call's own (no per-frame resource of rt_render is used)
     char* staging = nullptr;
     if (buffers_on_device) {
         for (const auto& o : outs) {
-            const rt_status st = check_trace_ptr(o.user, o.bytes, s->device, o.what, "rt_render_aov");
+            const rt_status st = check_trace_ptr(o.user, o.bytes, s->device, o.what, who_c);
             if (st != RT_OK) return st;
             *o.dev = o.user;
         }
@@ -1387,15 +1403,21 @@ rt_status rt_render_aov(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* 
     ap.local_rows = local_rows;
     ap.tiles_x = tiles_x;
     ap.work_items = (uint32_t)tiles_x * (uint32_t)tiles_y * 64u;
+    if (t) { tp.max_bounces = t->max_bounces; tp.fuzz_limit = t->fuzz_limit; }
 
     const rt_scene_dev& sd = s->dev;   // the walk array
     // (the staging block is released on every way out from here on)
     auto run = [&]() -> rt_status {
         resident_plan plan;
-        const rt_status st = plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), g_opt.aov_lds, ((long long)ap.work_items + RT_AOV_THREADS - 1) / RT_AOV_THREADS,
-                                           [&](int m, size_t lds, int* per_cu) { return rt_aov_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu); }, plan);
+        const rt_status st = plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), t ? g_opt.aov_through_lds : g_opt.aov_lds,
+                                           ((long long)ap.work_items + RT_AOV_THREADS - 1) / RT_AOV_THREADS,
+                                           [&](int m, size_t lds, int* per_cu) {
+                                               return t ? rt_aov_through_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu)
+                                                        : rt_aov_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu);
+                                           }, plan);
         if (st != RT_OK) return st;
-        HIPCHK(rt_launch_aov(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, plan.grid, plan.lds, stream));
+        if (t) HIPCHK(rt_launch_aov_through(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, tp, plan.grid, plan.lds, stream));
+        else HIPCHK(rt_launch_aov(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, plan.grid, plan.lds, stream));
         if (!buffers_on_device)
             for (const auto& o : outs) if (o.user) HIPCHK(hipMemcpyAsync(o.user, *o.dev, o.bytes, hipMemcpyDeviceToHost, stream));
         if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
@@ -1407,6 +1429,16 @@ rt_status rt_render_aov(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* 
         (void)hipFree(staging);
     }
     return st;
+}
+
+rt_status rt_render_aov(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* a, int buffers_on_device, void* stream_v, int blocking) {
+    return aov_impl(s, f, a, nullptr, "rt_render_aov", buffers_on_device, stream_v, blocking);
+}
+
+rt_status rt_render_aov_through(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* a, const rt_aov_through_desc* t, int buffers_on_device,
+                                void* stream_v, int blocking) {
+    if (!t) return invalid("rt_render_aov_through: null chain description");
+    return aov_impl(s, f, a, t, "rt_render_aov_through", buffers_on_device, stream_v, blocking);
 }
 
 size_t rt_denoise_workspace_bytes(int32_t nx, int32_t ny) {

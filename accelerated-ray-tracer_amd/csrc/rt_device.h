@@ -381,3 +381,16 @@ struct rt_variance_params {
     float gamma;
 };
 hipError_t rt_launch_variance(const rt_variance_params& p, hipStream_t st);
+
+// rt_render_aov_through (rt_kernel_aov_through.hip): the feature pass that follows the specular chain of every sample
+// (include/rt_abi.h).  A second kernel argument beside rt_aov_params, which rt_kernel_aov.hip keeps as it is.
+struct rt_aov_through_params {
+    float* through;           // local_rows * nx; null = not written
+    int32_t* bounces;         // local_rows * nx; null = not written
+    int32_t max_bounces;
+    float fuzz_limit;
+};
+// as rt_launch_aov / rt_aov_occupancy; grid = persistent workgroups of RT_AOV_THREADS
+hipError_t rt_launch_aov_through(bool spheres_only, int tex_level, int lds_mode, const rt_scene_dev& sd, const rt_aov_params& ap,
+                                 const rt_aov_through_params& tp, dim3 grid, size_t lds, hipStream_t st);
+hipError_t rt_aov_through_occupancy(bool spheres_only, int tex_level, int lds_mode, size_t lds, int* blocks_per_cu);

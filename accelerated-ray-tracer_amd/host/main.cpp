@@ -8,6 +8,7 @@
 //
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
 //             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K] [--denoise-variance [B]]] [--list]
+//             [--aov-through PREFIX] [--through-bounces N] [--through-fuzz F] [--denoise-through]
 //
 // --denoise [K] filters the frame with rt_denoise (K iterations, 5 when K is left out; the binding's other defaults): the frame
 // is rendered at gamma 1, the feature pass (albedo, normal, depth at min(ns, 16) samples) guides the filter, and the frame's
@@ -20,6 +21,10 @@
 // --aov PREFIX also writes the frame's feature buffers (rt_render_aov, same camera, seed and sample count) next to the image,
 // in the image's PPM flavour: PREFIX.albedo.ppm, PREFIX.normal.ppm (0.5 n + 0.5) and PREFIX.depth.ppm (grey, the ray parameter
 // t over the frame's largest).  Not with --gpus > 1.
+// --aov-through PREFIX writes the same three files from rt_render_aov_through: the features of the first non-specular surface
+// behind glass and in mirrors, and PREFIX.through.ppm (grey: the share of the pixel's samples that followed a bounce).
+// --through-bounces N (0..16, default 8) and --through-fuzz F (>= 0, default 0: perfect mirrors only) are the chain's limits.
+// --denoise-through (needs --denoise) takes the filter's guides from that pass instead of rt_render_aov.  Not with --gpus > 1.
 
 // --adaptive T renders with adaptive sampling (rt_render_adaptive): each pixel stops at the first checkpoint M * 2^k where its
 // average moved by at most T * (brightness + 0.01) since the previous one, and at --ns (= max_spp) otherwise.  M defaults to
@@ -45,7 +50,11 @@ static void check(rt_status st, const char* what) {
 }
 
 int main(int argc, char** argv) {
-    std::string scene_name = "bouncing", texture_path, aov_prefix;
+    std::string scene_name = "bouncing", texture_path, aov_prefix, through_prefix;
+    rt_aov_through_desc chain;   // the binding's defaults (AOV_THROUGH_DEFAULTS)
+    memset(&chain, 0, sizeof(chain));
+    chain.max_bounces = 8; chain.fuzz_limit = 0.0f;
+    bool denoise_through = false, chain_given = false;
     int nx = 0, ny = 0, ns = 0, device = 0, gpus = 1, progressive = 0;
     bool p6 = false, adaptive = false;
     float threshold = 0.f;
@@ -67,6 +76,16 @@ int main(int argc, char** argv) {
         else if (k == "--adaptive") { adaptive = true; threshold = strtof(val(), nullptr); }
         else if (k == "--min-spp") min_spp = atoi(val());
         else if (k == "--aov") aov_prefix = val();
+        else if (k == "--aov-through") through_prefix = val();
+        else if (k == "--through-bounces") {
+            chain.max_bounces = atoi(val()); chain_given = true;
+            if (chain.max_bounces < 0 || chain.max_bounces > 16) { fprintf(stderr, "--through-bounces N: N must be in 0..16\n"); return 2; }
+        }
+        else if (k == "--through-fuzz") {
+            chain.fuzz_limit = strtof(val(), nullptr); chain_given = true;
+            if (!(std::isfinite(chain.fuzz_limit) && chain.fuzz_limit >= 0.f)) { fprintf(stderr, "--through-fuzz F: F must be finite and >= 0\n"); return 2; }
+        }
+        else if (k == "--denoise-through") denoise_through = true;
         else if (k == "--denoise") {   // K is optional: the next argument when it is a number
             denoise = 5;
             if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') denoise = atoi(argv[++a]);
@@ -85,6 +104,9 @@ int main(int argc, char** argv) {
 
     if (adaptive && (progressive > 0 || gpus > 1)) { fprintf(stderr, "--adaptive cannot be combined with --progressive or --gpus > 1\n"); return 2; }
     if (!aov_prefix.empty() && gpus > 1) { fprintf(stderr, "--aov cannot be combined with --gpus > 1\n"); return 2; }
+    if (!through_prefix.empty() && gpus > 1) { fprintf(stderr, "--aov-through cannot be combined with --gpus > 1\n"); return 2; }
+    if (denoise_through && !denoise) { fprintf(stderr, "--denoise-through needs --denoise\n"); return 2; }
+    if (chain_given && through_prefix.empty() && !denoise_through) { fprintf(stderr, "--through-bounces and --through-fuzz need --aov-through or --denoise-through\n"); return 2; }
     if (denoise && (progressive > 0 || gpus > 1)) { fprintf(stderr, "--denoise cannot be combined with --progressive or --gpus > 1\n"); return 2; }
     if (batches >= 0 && !denoise) { fprintf(stderr, "--denoise-variance needs --denoise\n"); return 2; }
     if (batches >= 0 && adaptive) { fprintf(stderr, "--denoise-variance cannot be combined with --adaptive\n"); return 2; }
@@ -187,7 +209,8 @@ int main(int argc, char** argv) {
         rt_aov_desc aov;
         memset(&aov, 0, sizeof(aov));
         aov.albedo = albedo.data(); aov.normal = normal.data(); aov.depth = depth.data();
-        check(rt_render_aov(dev_scene, &ff, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
+        if (denoise_through) check(rt_render_aov_through(dev_scene, &ff, &aov, &chain, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov_through");
+        else check(rt_render_aov(dev_scene, &ff, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
         if (!aov_prefix.empty()) {
             std::vector<float> noisy = fb;
             apply_gamma(noisy);
@@ -221,27 +244,40 @@ int main(int argc, char** argv) {
     if (p6) rtw::write_ppm_p6(stdout, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
     else rtw::write_ppm_p3(stdout, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
 
-    if (!aov_prefix.empty()) {
+    // the feature buffers of the frame as images: rt_render_aov's, or with `through` rt_render_aov_through's and its share buffer
+    auto write_features = [&](const std::string& prefix, bool through) -> bool {
         const size_t px = (size_t)scene->nx * scene->ny;
-        std::vector<float> albedo(px * 3), normal(px * 3), depth(px), grey(px * 3);
+        std::vector<float> albedo(px * 3), normal(px * 3), depth(px), grey(px * 3), share(through ? px : 0), share3(through ? px * 3 : 0);
         rt_aov_desc aov;
         memset(&aov, 0, sizeof(aov));
         aov.albedo = albedo.data(); aov.normal = normal.data(); aov.depth = depth.data();
-        check(rt_render_aov(dev_scene, &f, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
+        if (through) {
+            rt_aov_through_desc t = chain;
+            t.through = share.data();
+            check(rt_render_aov_through(dev_scene, &f, &aov, &t, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov_through");
+            for (size_t p = 0; p < px; ++p) share3[3 * p] = share3[3 * p + 1] = share3[3 * p + 2] = share[p];
+        } else {
+            check(rt_render_aov(dev_scene, &f, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
+        }
         for (float& c : normal) c = 0.5f * c + 0.5f;
         float t_far = 0.f;
         for (float t : depth) if (t > t_far) t_far = t;
         for (size_t p = 0; p < px; ++p) grey[3 * p] = grey[3 * p + 1] = grey[3 * p + 2] = t_far > 0.f ? depth[p] / t_far : 0.f;
-        const struct { const char* name; const float* data; } files[] = {{"albedo", albedo.data()}, {"normal", normal.data()}, {"depth", grey.data()}};
+        const struct { const char* name; const float* data; } files[] = {{"albedo", albedo.data()}, {"normal", normal.data()}, {"depth", grey.data()},
+                                                                         {"through", share3.data()}};
         for (const auto& o : files) {
-            const std::string path = aov_prefix + "." + o.name + ".ppm";
+            if (!through && o.data == share3.data()) continue;
+            const std::string path = prefix + "." + o.name + ".ppm";
             FILE* out = fopen(path.c_str(), "wb");
-            if (!out) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+            if (!out) { fprintf(stderr, "cannot write %s\n", path.c_str()); return false; }
             if (p6) rtw::write_ppm_p6(out, o.data, scene->nx, scene->ny, false);
             else rtw::write_ppm_p3(out, o.data, scene->nx, scene->ny, false);
             fclose(out);
         }
-    }
+        return true;
+    };
+    if (!aov_prefix.empty() && !write_features(aov_prefix, false)) return 1;
+    if (!through_prefix.empty() && !write_features(through_prefix, true)) return 1;
 
     if (multi) check(rt_multi_destroy(multi), "rt_multi_destroy");
     if (dev_scene) check(rt_scene_destroy(dev_scene), "rt_scene_destroy");

@@ -372,6 +372,57 @@ typedef struct rt_aov_desc {
 } rt_aov_desc; /* 56 B */
 rt_status rt_render_aov(rt_scene* scene, const rt_frame_desc* f, const rt_aov_desc* a, int buffers_on_device, void* stream, int blocking);
 
+/* ---- feature buffers through mirrors and glass: the first non-specular surface of every sample ----
+ * rt_render_aov stops at the first hit, so a glass ball has albedo (1, 1, 1) and a mirror its tint, and both have their own
+ * normal: nothing of what is seen through or in them.  rt_render_aov_through follows a deterministic specular chain from
+ * each primary ray -- the mirror direction of a metal, the refracted direction of a dielectric (the mirror direction under
+ * total internal reflection) -- and reports the surface where the chain ends: what a denoiser asks its caller for.
+ *
+ * Everything of rt_render_aov's contract holds: the pixel's XORWOW chain and its draws, pixel indexing, row partition, the
+ * buffers and their rules, the checks before any HIP call, the stream rules, no shared state.  The specular chain consumes no
+ * draw, so sample s of a pixel starts from exactly the primary ray rt_render_aov uses.  Per sample, with ray 0 the primary
+ * ray (o0, d0, tm) and k = 0:
+ *   Walk.  Ray k is walked with the window (0.001, FLT_MAX) and its hit resolved as rt_trace_rays resolves it.
+ *   Terminal events.  The chain ends at: a miss; a hit on a lambertian, isotropic or light material (a constant medium's
+ *     material included); a metal with fuzz > fuzz_limit; any hit once k == max_bounces; a followed metal whose mirror
+ *     direction r has dot(n, r) <= 0.
+ *   Follow.  Otherwise the hit is followed: ray k + 1 is (p, d', tm), p the hit record's point, n its normal as normal_out
+ *     orients it, and k = k + 1.
+ *   d'.  All binary32, every written operation rounded once, nothing contracted into an FMA, sums left to right as written;
+ *     only + - * / sqrt and comparisons occur.  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.  u = d / sqrt(dot(d, d)), three
+ *     divisions.
+ *       metal       c = dot(u, n);  r = u - (2 c) n per component.  dot(n, r) <= 0: the hit is terminal and the tint stays.
+ *                   Else d' = r and the chain's tint, (1, 1, 1) at the start, is multiplied per channel by the
+ *                   material's albedo.
+ *       dielectric  dn = dot(d, n);  dn > 0: m = -n, e = ior;  else m = n, e = 1 / ior.  dt = dot(u, m);
+ *                   disc = 1 - (e e) (1 - dt dt).  disc > 0: d' = e (u - dt m) - sqrt(disc) m per component (refraction);
+ *                   else d' = u - (2 dot(u, n)) n (total internal reflection).  The tint is unchanged.
+ *   Terms of the sample, from the terminal event:
+ *     albedo   tint times, per channel, rt_render_aov's albedo of the terminal hit -- or, on a miss, its miss term of the
+ *              last ray.
+ *     normal   the terminal hit's normal; 0 on a miss.
+ *     alpha    1 on a terminal hit, 0 on a miss.
+ *     depth    on a terminal hit, in the PRIMARY ray's parameter: t0 when nothing was followed (k = 0), else
+ *              t0 + ((t1 + t2) + ... + tk) / sqrt(dot(d0, d0)), t_j the hit's t along ray j; 0 on a miss.
+ *     through  1 if k >= 1, else 0.
+ *   Per pixel each float output (albedo, normal, depth, alpha, through) is the sum of the terms in sample order, scaled by
+ *   (float)(1.0 / (double)(float)ns), as rt_render_aov does.  prim / inst / mat are sample 0's terminal hit (-1 on a terminal
+ *   miss) and bounces is sample 0's k, whatever ended its chain.
+ * With max_bounces = 0 every output of rt_aov_desc is bit for bit rt_render_aov's (through = 0, bounces = 0).
+ *
+ * A null t, max_bounces outside 0..16, a non-finite or negative fuzz_limit, or every output of a and t null is
+ * RT_ERR_INVALID beside rt_render_aov's checks; all run before any HIP call and before the scene is looked at, and
+ * rt_last_error_detail() names the one that failed.  Option "aov_through_lds": the meaning and auto rule of "trace_lds"; it
+ * changes no result. */
+typedef struct rt_aov_through_desc {
+    int32_t max_bounces;       /* 0..16; 0 = rt_render_aov */
+    float fuzz_limit;          /* finite, >= 0: a metal is followed iff its fuzz <= fuzz_limit */
+    float* through;            /* rows*nx or null: share of the pixel's samples that followed at least one bounce */
+    int32_t* bounces;          /* rows*nx or null: sample 0's number of followed bounces */
+} rt_aov_through_desc; /* 24 B */
+rt_status rt_render_aov_through(rt_scene* scene, const rt_frame_desc* f, const rt_aov_desc* a, const rt_aov_through_desc* t,
+                                int buffers_on_device, void* stream, int blocking);
+
 /* ---- denoiser: an edge-avoiding a-trous wavelet filter guided by the feature buffers ----
  * rt_denoise filters a noisy linear frame (rt_render or rt_render_adaptive at gamma 1) with a 5x5 B3-spline kernel whose
  * taps are spread 2^k pixels apart in iteration k and weighted down across edges of the normal, the depth and the colour.
