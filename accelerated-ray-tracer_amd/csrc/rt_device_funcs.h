@@ -602,7 +602,9 @@ DEV float apply_gamma(float c, float gamma) {   // main.cu:37-42
     return cr_pow(fmaxf(c, 0.0f), inv);
 }
 
-DEV f3 miss_color(const rt_frame_params& fp, const Ray& r) {   // main.cu:59-65
+// the miss term of color() (main.cu:59-65); P: any argument block with background and use_gradient_bg
+template <typename P>
+DEV f3 miss_color(const P& fp, const Ray& r) {
     f3 bg = mk3(fp.background[0], fp.background[1], fp.background[2]);
     if (fp.use_gradient_bg) {
         const f3 ud = unit_vector(r.d);

@@ -12,37 +12,10 @@
 // The feature pass draws, per sample, what a render sample draws before its path (rt_kernel_pixel.hip: two jitter uniforms,
 // camera_get_ray's lens-disk loop and its shutter uniform) and nothing else: sample s of a pixel is the primary ray rt_render
 // would send if no path consumed a draw, sample 0 is rt_render's first primary ray of that pixel.
-#include "rt_device_funcs.h"
+#include "rt_kernel_query.h"
+#include "rt_launch.h"
 
 namespace {
-
-// One node visit of the walk for a ray with the window (0.001, best.t): twin of rt_kernel_radiance.hip's walk_step (and of
-// trace_step<SPHERES_ONLY, false> in rt_kernel_trace.hip with tmin fixed): a change to one belongs in the others (kept apart
-// so that those units compile to the assembly they had).  `loose`: interior boxes take the widened one-fma form and a leaf's
-// own box is tested again exactly before its object; otherwise (a zero direction component) the reference's
-// own slab form everywhere.  Returns the next node.
-template <bool SPHERES_ONLY>
-DEV int walk_step(const SceneView& sc, const float4* nodes4, int node, const Ray& r, const f3 inv, const LooseRay& lr, bool loose,
-                  HitInfo& best) {
-    const float tmin = 0.001f;   // main.cu:57
-    const float4 a = nodes4[2 * node], b = nodes4[2 * node + 1];
-    const bool pass = loose ? slab_test_loose(a, b, inv, lr, tmin, best.t) : slab_test(a, b, r.o, inv, tmin, best.t);
-    const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);   // rt_device.h, RT_NODE_SKIP
-    const int next = ~((pass && link < 0) ? link : nskip);
-    if (pass && link >= 0 && (!loose || slab_test_finite(a, b, r.o, inv, tmin, best.t))) leaf_test<SPHERES_ONLY>(sc, link, r, tmin, best);
-    return next;
-}
-
-// the miss term of color() (main.cu:59-65): miss_color() for this pass's argument block
-DEV f3 miss_term(const rt_aov_params& ap, const Ray& r) {
-    f3 bg = mk3(ap.background[0], ap.background[1], ap.background[2]);
-    if (ap.use_gradient_bg) {
-        const f3 ud = unit_vector(r.d);
-        const float t = 0.5f * (ud.y + 1.0f);
-        bg = mk3(fmaf(t, 0.5f, 1.0f - t), fmaf(t, 0.7f, 1.0f - t), (1.0f - t) + t);
-    }
-    return bg;
-}
 
 // the albedo of a hit (include/rt_abi.h): what a lambertian or isotropic surface attenuates by and what a light emits -- the
 // texture's value at (u, v, p) or the inline colour, as shade() reads them --, a metal's colour, 1 for glass
@@ -53,8 +26,6 @@ DEV f3 hit_albedo(const SceneView& sc, const HitRec& rec) {
     if (TEX > 0 && m.kind != RT_MAT_METAL && m.tex >= 0) return texture_value<TEX>(sc, m.tex, rec.u, rec.v, rec.p);
     return ld3(m.albedo);
 }
-
-DEV void st3(float* p, f3 v, float k) { p[0] = v.x * k; p[1] = v.y * k; p[2] = v.z * k; }
 
 template <bool SPHERES_ONLY, int TEX, int LDS_MODE>
 __global__ void __launch_bounds__(RT_AOV_THREADS) rt_aov_kernel(rt_scene_dev sd, rt_aov_params ap) {
@@ -86,13 +57,10 @@ __global__ void __launch_bounds__(RT_AOV_THREADS) rt_aov_kernel(rt_scene_dev sd,
         const float u = ((float)i + rt_xorwow_uniform(g)) / (float)ap.nx;
         const float v = ((float)j + rt_xorwow_uniform(g)) / (float)ap.ny;
         cur = camera_get_ray(sd.camera, u, v, g);
-        best.t = FLT_MAX; best.prim = -1; best.inst = -1;   // world->hit for `cur` (main.cu:57)
-        inv = mk3(1.0f / cur.d.x, 1.0f / cur.d.y, 1.0f / cur.d.z);
-        loose = inv_is_finite(inv) && loose_ok(inv, cur.o, sd.bound);
-        lr = loose_setup(inv, cur.o, sd.bound);
-        node = 0;
+        walk_start(cur, sd.bound, FLT_MAX, best, inv, loose, lr, node);   // world->hit for `cur` (main.cu:57)
     };
-    // the lane's next work item that is a pixel of the frame (tiles overhang its right and top edges)
+    // the lane's next work item that is a pixel of the frame (tiles overhang its right and top edges); rt_kernel_aov_through.hip
+    // has the same lambda
     auto begin = [&]() {
         node = nn;
         int lrow = 0;
@@ -115,7 +83,7 @@ __global__ void __launch_bounds__(RT_AOV_THREADS) rt_aov_kernel(rt_scene_dev sd,
 
     begin();
     while (__ballot(w < items) != 0ull) {
-        if (node < nn) node = walk_step<SPHERES_ONLY>(sc, nodes4, node, cur, inv, lr, loose, best);
+        if (node < nn) node = walk_step<SPHERES_ONLY, false>(sc, nodes4, node, cur, inv, lr, loose, 0.001f, best);   // main.cu:57
         if (w < items && node >= nn) {   // this sample's walk is over: its terms, summed in sample order
             const bool hit = best.prim >= 0;
             int32_t mat = -1;
@@ -131,7 +99,7 @@ __global__ void __launch_bounds__(RT_AOV_THREADS) rt_aov_kernel(rt_scene_dev sd,
                 depth = depth + best.t;
                 alpha = alpha + 1.0f;
             } else if (want_albedo) {
-                alb = alb + miss_term(ap, cur);
+                alb = alb + miss_color(ap, cur);
             }
             if (sample == 0) {           // the ids are the first sample's (rt_trace_rays' prim_out / inst_out / mat_out)
                 if (ap.prim) ap.prim[px] = best.prim;
@@ -153,57 +121,31 @@ __global__ void __launch_bounds__(RT_AOV_THREADS) rt_aov_kernel(rt_scene_dev sd,
     }
 }
 
-template <bool SO, int TEX, int LM>
-hipError_t set_lds(size_t lds) {
-    if (lds <= 65536) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_aov_kernel<SO, TEX, LM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
+using Kernel = void (*)(rt_scene_dev, rt_aov_params);
 
-template <bool SO, int TEX, int LM>
-struct Launch {
-    static hipError_t run(const rt_scene_dev* sd, const rt_aov_params* ap, dim3 grid, size_t lds, hipStream_t st) {
-        const hipError_t e = set_lds<SO, TEX, LM>(lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rt_aov_kernel<SO, TEX, LM>), grid, dim3(RT_AOV_THREADS), lds, st, *sd, *ap);
-        return hipGetLastError();
-    }
-};
-template <bool SO, int TEX, int LM>
-struct Occupancy {
-    static hipError_t run(size_t lds, int* blocks) {
-        const hipError_t e = set_lds<SO, TEX, LM>(lds);
-        if (e != hipSuccess) return e;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, reinterpret_cast<const void*>(&rt_aov_kernel<SO, TEX, LM>),
-                                                            RT_AOV_THREADS, lds);
-    }
-};
-
-// every instantiation behind one switch: F<SO, TEX, LM>::run(args...)
-template <template <bool, int, int> class F, bool SO, int TEX, typename... A>
-hipError_t dispatch_lds(int lds_mode, A... args) {
-    if (lds_mode == 2) return F<SO, TEX, 2>::run(args...);
-    if (lds_mode == 1) return F<SO, TEX, 1>::run(args...);
-    return F<SO, TEX, 0>::run(args...);
+template <bool SO, int TEX>
+Kernel pick_lds(int lds_mode) {
+    if (lds_mode == 2) return rt_aov_kernel<SO, TEX, 2>;
+    if (lds_mode == 1) return rt_aov_kernel<SO, TEX, 1>;
+    return rt_aov_kernel<SO, TEX, 0>;
 }
-template <template <bool, int, int> class F, typename... A>
-hipError_t dispatch(bool spheres_only, int tex_level, int lds_mode, A... args) {
-    if (spheres_only) {
-        if (tex_level == 0) return dispatch_lds<F, true, 0>(lds_mode, args...);
-        if (tex_level == 1) return dispatch_lds<F, true, 1>(lds_mode, args...);
-        return dispatch_lds<F, true, 2>(lds_mode, args...);
-    }
-    if (tex_level == 0) return dispatch_lds<F, false, 0>(lds_mode, args...);
-    if (tex_level == 1) return dispatch_lds<F, false, 1>(lds_mode, args...);
-    return dispatch_lds<F, false, 2>(lds_mode, args...);
+template <bool SO>
+Kernel pick_tex(int tex_level, int lds_mode) {
+    if (tex_level == 0) return pick_lds<SO, 0>(lds_mode);
+    if (tex_level == 1) return pick_lds<SO, 1>(lds_mode);
+    return pick_lds<SO, 2>(lds_mode);
+}
+Kernel pick(bool spheres_only, int tex_level, int lds_mode) {
+    return spheres_only ? pick_tex<true>(tex_level, lds_mode) : pick_tex<false>(tex_level, lds_mode);
 }
 
 }  // namespace
 
 hipError_t rt_launch_aov(bool spheres_only, int tex_level, int lds_mode, const rt_scene_dev& sd, const rt_aov_params& ap, dim3 grid,
                          size_t lds, hipStream_t st) {
-    return dispatch<Launch>(spheres_only, tex_level, lds_mode, &sd, &ap, grid, lds, st);
+    return rt_launch_kernel(pick(spheres_only, tex_level, lds_mode), dim3(RT_AOV_THREADS), grid, lds, st, sd, ap);
 }
 
 hipError_t rt_aov_occupancy(bool spheres_only, int tex_level, int lds_mode, size_t lds, int* blocks_per_cu) {
-    return dispatch<Occupancy>(spheres_only, tex_level, lds_mode, lds, blocks_per_cu);
+    return rt_kernel_occupancy(pick(spheres_only, tex_level, lds_mode), RT_AOV_THREADS, lds, blocks_per_cu);
 }

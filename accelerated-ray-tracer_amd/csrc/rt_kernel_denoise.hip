@@ -20,6 +20,7 @@
 // the records inside the image, and a tap that passes the index test is inside the image and inside the staged window by
 // construction (|offset| <= 2 s), so no slot is read that was not written.  No address depends on pixel data.
 #include "rt_device.h"
+#include "rt_launch.h"
 
 namespace {
 
@@ -153,14 +154,8 @@ __global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_denoise_kernel(rt_denoi
 template <bool NRM, bool DEP, bool COL, bool STAGED>
 hipError_t launch(const rt_denoise_params& dp, hipStream_t st) {
     const size_t lds = STAGED ? rt_denoise_lds_bytes(dp.step, NRM || DEP) : 0;
-    if (lds > 65536) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_denoise_kernel<NRM, DEP, COL, STAGED>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
     const unsigned tiles_y = ((unsigned)dp.ny + TILE - 1) / TILE;
-    hipLaunchKernelGGL((rt_denoise_kernel<NRM, DEP, COL, STAGED>), dim3((unsigned)dp.tiles_x * tiles_y), dim3(RT_DENOISE_THREADS), lds, st, dp);
-    return hipGetLastError();
+    return rt_launch_kernel(rt_denoise_kernel<NRM, DEP, COL, STAGED>, dim3(RT_DENOISE_THREADS), dim3((unsigned)dp.tiles_x * tiles_y), lds, st, dp);
 }
 
 template <bool NRM, bool DEP, bool COL>
@@ -354,14 +349,8 @@ __global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_denoise_variance_kernel
 template <bool NRM, bool DEP, bool STAGED>
 hipError_t launch_variance(const rt_denoise_params& dp, const rt_denoise_variance_params& dv, hipStream_t st) {
     const size_t lds = STAGED ? rt_denoise_lds_bytes(dp.step, NRM || DEP) : 0;
-    if (lds > 65536) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_denoise_variance_kernel<NRM, DEP, STAGED>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
     const unsigned tiles_y = ((unsigned)dp.ny + TILE - 1) / TILE;
-    hipLaunchKernelGGL((rt_denoise_variance_kernel<NRM, DEP, STAGED>), dim3((unsigned)dp.tiles_x * tiles_y), dim3(RT_DENOISE_THREADS), lds, st, dp, dv);
-    return hipGetLastError();
+    return rt_launch_kernel(rt_denoise_variance_kernel<NRM, DEP, STAGED>, dim3(RT_DENOISE_THREADS), dim3((unsigned)dp.tiles_x * tiles_y), lds, st, dp, dv);
 }
 template <bool NRM, bool DEP>
 hipError_t launch_variance_staged(bool staged, const rt_denoise_params& dp, const rt_denoise_variance_params& dv, hipStream_t st) {

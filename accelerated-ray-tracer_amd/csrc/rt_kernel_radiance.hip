@@ -12,38 +12,10 @@
 // A query is the single pixel of a 1 x 1 frame of a degenerate camera (include/rt_abi.h), so each sample first draws what
 // a render sample draws before its path (rt_kernel_pixel.hip: two jitter uniforms, camera_get_ray's lens-disk loop and its
 // shutter uniform) and discards it.
-#include "rt_device_funcs.h"
+#include "rt_kernel_query.h"
+#include "rt_launch.h"
 
 namespace {
-
-// One node visit of the walk for a ray with the window (0.001, best.t): bvh_node::hit (bvh.cuh:95-106) with the render
-// kernels' guards on the faster box tests, as rt_kernel_trace.hip's trace_step.  `loose` (every 1/d component finite and
-// loose_ok): interior boxes take the widened one-fma form and a leaf's own box is tested again exactly before its object;
-// otherwise (a zero direction component) the reference's own slab form everywhere.  Returns the next node.
-// Twin of trace_step<SPHERES_ONLY, false> there with tmin fixed: a change to one belongs in the other (kept apart so that
-// rt_kernel_trace.hip compiles to the assembly it had).
-template <bool SPHERES_ONLY>
-DEV int walk_step(const SceneView& sc, const float4* nodes4, int node, const Ray& r, const f3 inv, const LooseRay& lr, bool loose,
-                  HitInfo& best) {
-    const float tmin = 0.001f;   // main.cu:57
-    const float4 a = nodes4[2 * node], b = nodes4[2 * node + 1];
-    const bool pass = loose ? slab_test_loose(a, b, inv, lr, tmin, best.t) : slab_test(a, b, r.o, inv, tmin, best.t);
-    const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);   // rt_device.h, RT_NODE_SKIP
-    const int next = ~((pass && link < 0) ? link : nskip);
-    if (pass && link >= 0 && (!loose || slab_test_finite(a, b, r.o, inv, tmin, best.t))) leaf_test<SPHERES_ONLY>(sc, link, r, tmin, best);
-    return next;
-}
-
-// the miss term of color() (main.cu:59-65): miss_color() for a batch's background
-DEV f3 miss_term(const rt_radiance_params& rp, const Ray& r) {
-    f3 bg = mk3(rp.background[0], rp.background[1], rp.background[2]);
-    if (rp.use_gradient_bg) {
-        const f3 ud = unit_vector(r.d);
-        const float t = 0.5f * (ud.y + 1.0f);
-        bg = mk3(fmaf(t, 0.5f, 1.0f - t), fmaf(t, 0.7f, 1.0f - t), (1.0f - t) + t);
-    }
-    return bg;
-}
 
 template <bool SPHERES_ONLY, int TEX, int LDS_MODE>
 __global__ void __launch_bounds__(RT_RADIANCE_THREADS) rt_radiance_kernel(rt_scene_dev sd, rt_radiance_params rp) {
@@ -64,7 +36,9 @@ __global__ void __launch_bounds__(RT_RADIANCE_THREADS) rt_radiance_kernel(rt_sce
     uint32_t rays = 0;
     f3 throughput, radiance, col;
 
-    auto start_walk = [&]() {    // world->hit for `cur` (main.cu:57)
+    // world->hit for `cur` (main.cu:57); walk_start (rt_kernel_query.h) written out: calling it changes this kernel's
+    // instruction stream
+    auto start_walk = [&]() {
         ++rays;
         best.t = FLT_MAX; best.prim = -1; best.inst = -1;
         inv = mk3(1.0f / cur.d.x, 1.0f / cur.d.y, 1.0f / cur.d.z);
@@ -90,17 +64,14 @@ __global__ void __launch_bounds__(RT_RADIANCE_THREADS) rt_radiance_kernel(rt_sce
         start_walk();
     };
     // the lane's next query with a ray that can be walked; the others (a NaN or infinite component, the zero direction) get
-    // zeros and no rays here, before any draw: quad_test and medium_test would accept a NaN t, and the box forms disagree on
-    // NaN, so the walk taken would decide the answer (rt_kernel_trace.hip)
+    // zeros and no rays here, before any draw (ray_is_finite)
     auto begin = [&]() {
         node = nn;
         for (; idx < n; idx += stride) {
             q.o = ld3(rp.origins + 3 * idx);
             q.d = ld3(rp.directions + 3 * idx);
             q.tm = rp.times ? rp.times[idx] : 0.0f;
-            const bool finite = isfinite(q.o.x) && isfinite(q.o.y) && isfinite(q.o.z) && isfinite(q.d.x) && isfinite(q.d.y) &&
-                                isfinite(q.d.z) && isfinite(q.tm);
-            if (finite && (q.d.x != 0.0f || q.d.y != 0.0f || q.d.z != 0.0f)) break;
+            if (ray_is_finite(q) && (q.d.x != 0.0f || q.d.y != 0.0f || q.d.z != 0.0f)) break;
             rp.rgb_out[3 * idx] = 0.0f; rp.rgb_out[3 * idx + 1] = 0.0f; rp.rgb_out[3 * idx + 2] = 0.0f;
             if (rp.rays_out) rp.rays_out[idx] = 0u;
         }
@@ -113,11 +84,11 @@ __global__ void __launch_bounds__(RT_RADIANCE_THREADS) rt_radiance_kernel(rt_sce
 
     begin();
     while (__ballot(idx < n) != 0ull) {
-        if (node < nn) node = walk_step<SPHERES_ONLY>(sc, nodes4, node, cur, inv, lr, loose, best);
+        if (node < nn) node = walk_step<SPHERES_ONLY, false>(sc, nodes4, node, cur, inv, lr, loose, 0.001f, best);   // main.cu:57
         if (idx < n && node >= nn) {   // this ray's walk is over: the rest of color()'s loop body (main.cu:57-92)
             bool path_over;
             if (best.prim < 0) {
-                radiance = fma3(throughput, miss_term(rp, cur), radiance);
+                radiance = fma3(throughput, miss_color(rp, cur), radiance);
                 path_over = true;
             } else {
                 const HitRec rec = resolve_hit<SPHERES_ONLY, TEX == 2>(sc, cur, best);
@@ -150,57 +121,31 @@ __global__ void __launch_bounds__(RT_RADIANCE_THREADS) rt_radiance_kernel(rt_sce
     }
 }
 
-template <bool SO, int TEX, int LM>
-hipError_t set_lds(size_t lds) {
-    if (lds <= 65536) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_radiance_kernel<SO, TEX, LM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
+using Kernel = void (*)(rt_scene_dev, rt_radiance_params);
 
-template <bool SO, int TEX, int LM>
-struct Launch {
-    static hipError_t run(const rt_scene_dev* sd, const rt_radiance_params* rp, dim3 grid, size_t lds, hipStream_t st) {
-        const hipError_t e = set_lds<SO, TEX, LM>(lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((rt_radiance_kernel<SO, TEX, LM>), grid, dim3(RT_RADIANCE_THREADS), lds, st, *sd, *rp);
-        return hipGetLastError();
-    }
-};
-template <bool SO, int TEX, int LM>
-struct Occupancy {
-    static hipError_t run(size_t lds, int* blocks) {
-        const hipError_t e = set_lds<SO, TEX, LM>(lds);
-        if (e != hipSuccess) return e;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, reinterpret_cast<const void*>(&rt_radiance_kernel<SO, TEX, LM>),
-                                                            RT_RADIANCE_THREADS, lds);
-    }
-};
-
-// every instantiation behind one switch: F<SO, TEX, LM>::run(args...)
-template <template <bool, int, int> class F, bool SO, int TEX, typename... A>
-hipError_t dispatch_lds(int lds_mode, A... args) {
-    if (lds_mode == 2) return F<SO, TEX, 2>::run(args...);
-    if (lds_mode == 1) return F<SO, TEX, 1>::run(args...);
-    return F<SO, TEX, 0>::run(args...);
+template <bool SO, int TEX>
+Kernel pick_lds(int lds_mode) {
+    if (lds_mode == 2) return rt_radiance_kernel<SO, TEX, 2>;
+    if (lds_mode == 1) return rt_radiance_kernel<SO, TEX, 1>;
+    return rt_radiance_kernel<SO, TEX, 0>;
 }
-template <template <bool, int, int> class F, typename... A>
-hipError_t dispatch(bool spheres_only, int tex_level, int lds_mode, A... args) {
-    if (spheres_only) {
-        if (tex_level == 0) return dispatch_lds<F, true, 0>(lds_mode, args...);
-        if (tex_level == 1) return dispatch_lds<F, true, 1>(lds_mode, args...);
-        return dispatch_lds<F, true, 2>(lds_mode, args...);
-    }
-    if (tex_level == 0) return dispatch_lds<F, false, 0>(lds_mode, args...);
-    if (tex_level == 1) return dispatch_lds<F, false, 1>(lds_mode, args...);
-    return dispatch_lds<F, false, 2>(lds_mode, args...);
+template <bool SO>
+Kernel pick_tex(int tex_level, int lds_mode) {
+    if (tex_level == 0) return pick_lds<SO, 0>(lds_mode);
+    if (tex_level == 1) return pick_lds<SO, 1>(lds_mode);
+    return pick_lds<SO, 2>(lds_mode);
+}
+Kernel pick(bool spheres_only, int tex_level, int lds_mode) {
+    return spheres_only ? pick_tex<true>(tex_level, lds_mode) : pick_tex<false>(tex_level, lds_mode);
 }
 
 }  // namespace
 
 hipError_t rt_launch_radiance(bool spheres_only, int tex_level, int lds_mode, const rt_scene_dev& sd, const rt_radiance_params& rp,
                               dim3 grid, size_t lds, hipStream_t st) {
-    return dispatch<Launch>(spheres_only, tex_level, lds_mode, &sd, &rp, grid, lds, st);
+    return rt_launch_kernel(pick(spheres_only, tex_level, lds_mode), dim3(RT_RADIANCE_THREADS), grid, lds, st, sd, rp);
 }
 
 hipError_t rt_radiance_occupancy(bool spheres_only, int tex_level, int lds_mode, size_t lds, int* blocks_per_cu) {
-    return dispatch<Occupancy>(spheres_only, tex_level, lds_mode, lds, blocks_per_cu);
+    return rt_kernel_occupancy(pick(spheres_only, tex_level, lds_mode), RT_RADIANCE_THREADS, lds, blocks_per_cu);
 }

@@ -4,6 +4,7 @@
 #define RT_STEP_UNROLL 2
 #endif
 #include "rt_device_funcs.h"
+#include "rt_launch.h"
 
 // =============================================================================
 // Kernel D ("staged"): kernel C with the shading block cut into stages.
@@ -540,20 +541,9 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
 template <bool SO, int TX, bool UV>
 static hipError_t rt_launch_staged_family(int lds_mode, const rt_scene_dev& sd, const rt_frame_params& fp, dim3 grid, dim3 block,
                                           size_t lds, hipStream_t st) {
-#define RT_STAGED_LAUNCH(LM)                                                                                              \
-    do {                                                                                                                  \
-        if (lds > 65536) {                                                                                                \
-            const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_render_staged_kernel<SO, TX, UV, LM>), \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-            if (e_ != hipSuccess) return e_;                                                                              \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((rt_render_staged_kernel<SO, TX, UV, LM>), grid, block, lds, st, sd, fp);                      \
-        return hipGetLastError();                                                                                         \
-    } while (0)
-    if (lds_mode == 4) RT_STAGED_LAUNCH(4);
-    if (lds_mode == 3) RT_STAGED_LAUNCH(3);
-    if (lds_mode == 2) RT_STAGED_LAUNCH(2);
-    if (lds_mode == 1) RT_STAGED_LAUNCH(1);
-    RT_STAGED_LAUNCH(0);
-#undef RT_STAGED_LAUNCH
+    if (lds_mode == 4) return rt_launch_kernel(rt_render_staged_kernel<SO, TX, UV, 4>, block, grid, lds, st, sd, fp);
+    if (lds_mode == 3) return rt_launch_kernel(rt_render_staged_kernel<SO, TX, UV, 3>, block, grid, lds, st, sd, fp);
+    if (lds_mode == 2) return rt_launch_kernel(rt_render_staged_kernel<SO, TX, UV, 2>, block, grid, lds, st, sd, fp);
+    if (lds_mode == 1) return rt_launch_kernel(rt_render_staged_kernel<SO, TX, UV, 1>, block, grid, lds, st, sd, fp);
+    return rt_launch_kernel(rt_render_staged_kernel<SO, TX, UV, 0>, block, grid, lds, st, sd, fp);
 }

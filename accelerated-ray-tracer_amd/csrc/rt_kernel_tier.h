@@ -18,6 +18,7 @@
 // and the tier workgroups take their slots (tools/ubench/concurrent_kernels.hip measures both cases).
 #pragma once
 #include "rt_device_funcs.h"
+#include "rt_launch.h"
 
 // the scene's leaves as the tier kernel reads them (rt_scene_dev: leaf_lo / leaf_hi / slot_ranges), in LDS
 struct TierView {
@@ -393,12 +394,7 @@ __global__ void __launch_bounds__(RT_TIER_THREADS, (SPHERES_ONLY && TEX < 2) ? 4
 
 template <bool SO, int TX, bool UV, bool LS>
 static hipError_t rt_launch_tier_variant(const rt_scene_dev& sd, const rt_frame_params& fp, dim3 grid, size_t lds, hipStream_t st) {
-    if (lds > 65536) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_tier_kernel<SO, TX, UV, LS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((rt_tier_kernel<SO, TX, UV, LS>), grid, dim3(RT_TIER_THREADS), lds, st, sd, fp);
-    return hipGetLastError();
+    return rt_launch_kernel(rt_tier_kernel<SO, TX, UV, LS>, dim3(RT_TIER_THREADS), grid, lds, st, sd, fp);
 }
 template <bool SO, int TX, bool UV>
 static hipError_t rt_launch_tier_one(const rt_scene_dev& sd, const rt_frame_params& fp, dim3 grid, size_t lds, hipStream_t st) {

@@ -6,30 +6,10 @@
 // the rest of its wave (incoherent rays end at very different times); only when a hit record is requested does a wave
 // finish its rays together, so that the record code -- a transform, a division, acos / atan2 in double -- runs once per
 // 64 rays rather than once per finishing lane.  No atomics, no inter-workgroup communication.
-#include "rt_device_funcs.h"
+#include "rt_kernel_query.h"
+#include "rt_launch.h"
 
 namespace {
-
-// One node visit of the walk for a ray with the window (tmin, best.t): bvh_node::hit (bvh.cuh:95-106) as trace() walks it,
-// with the render kernels' guards on the faster box tests.  `loose` (every 1/d component finite and loose_ok): interior
-// boxes take the widened one-fma form, a superset of aabb::hit's passes, and a leaf's own box is tested again exactly
-// (slab_test_finite) before its object -- the walk then reaches exactly the objects the reference reaches (rt_device_funcs.h,
-// "the walk loop's box test").  Otherwise (a zero direction component): the reference's own
-// slab form everywhere.  Returns the next node; for ANY it returns n_nodes at the first accepted leaf.
-template <bool SPHERES_ONLY, bool ANY>
-DEV int trace_step(const SceneView& sc, const float4* nodes4, int node, const Ray& r, const f3 inv, const LooseRay& lr, bool loose,
-                   float tmin, HitInfo& best) {
-    const float4 a = nodes4[2 * node], b = nodes4[2 * node + 1];
-    const bool pass = loose ? slab_test_loose(a, b, inv, lr, tmin, best.t) : slab_test(a, b, r.o, inv, tmin, best.t);
-    // device encoding of the links (rt_device.h, RT_NODE_SKIP): a.w = ~skip; b.w = ~(node + 1) inside, the object id at a leaf
-    const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);
-    int next = ~((pass && link < 0) ? link : nskip);
-    if (pass && link >= 0 && (!loose || slab_test_finite(a, b, r.o, inv, tmin, best.t))) {
-        leaf_test<SPHERES_ONLY>(sc, link, r, tmin, best);
-        if (ANY && best.prim >= 0) next = sc.n_nodes;
-    }
-    return next;
-}
 
 // the hit record of a closest hit: resolve_hit() as the render computes it, and the sphere's (u, v) always (the render
 // computes them only where a material reads them) -- get_sphere_uv of the object-space outward normal, sphere.cuh:42-49
@@ -67,22 +47,19 @@ __global__ void __launch_bounds__(RT_TRACE_THREADS) rt_trace_kernel(rt_scene_dev
         r.o = ld3(tp.origins + 3 * idx);
         r.d = ld3(tp.directions + 3 * idx);
         r.tm = tp.times ? tp.times[idx] : 0.0f;
+        // walk_start (rt_kernel_query.h) written out: calling it changes this kernel's instruction stream
         best.t = tp.tmax ? tp.tmax[idx] : FLT_MAX;
         best.prim = -1; best.inst = -1;
         inv = mk3(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
         loose = inv_is_finite(inv) && loose_ok(inv, r.o, sd.bound);
         lr = loose_setup(inv, r.o, sd.bound);
         // a NaN tmax is a miss: sphere_test would reject every root under it, but quad_test's `t > tmax` and medium_test's
-        // clamp do not see a NaN, so the walk is not entered at all.  So is a ray with a non-finite origin, direction or
-        // time: quad_test and medium_test would accept a NaN t, and the box forms disagree on NaN (fminf / fmaxf drop it,
-        // the ternaries keep it), so the walk taken would decide the answer.
-        const bool finite = isfinite(r.o.x) && isfinite(r.o.y) && isfinite(r.o.z) && isfinite(r.d.x) && isfinite(r.d.y) &&
-                            isfinite(r.d.z) && isfinite(r.tm);
-        node = (finite && best.t == best.t) ? 0 : nn;
+        // clamp do not see a NaN, so the walk is not entered at all.  So is a ray that is not finite (ray_is_finite).
+        node = (ray_is_finite(r) && best.t == best.t) ? 0 : nn;
     };
     begin();
     while (__ballot(idx < n) != 0ull) {
-        if (node < nn) node = trace_step<SPHERES_ONLY, ANY>(sc, nodes4, node, r, inv, lr, loose, tmin, best);
+        if (node < nn) node = walk_step<SPHERES_ONLY, ANY>(sc, nodes4, node, r, inv, lr, loose, tmin, best);
         const bool finish = RECORD ? __ballot(idx < n && node < nn) == 0ull : (idx < n && node >= nn);
         if (finish) {
             if (idx < n) {
@@ -115,57 +92,33 @@ __global__ void __launch_bounds__(RT_TRACE_THREADS) rt_trace_kernel(rt_scene_dev
     }
 }
 
-template <bool SO, int LM, bool ANY, bool REC>
-hipError_t launch_one(const rt_scene_dev& sd, const rt_trace_params& tp, dim3 grid, size_t lds, hipStream_t st) {
-    if (lds > 65536) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_trace_kernel<SO, LM, ANY, REC>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((rt_trace_kernel<SO, LM, ANY, REC>), grid, dim3(RT_TRACE_THREADS), lds, st, sd, tp);
-    return hipGetLastError();
-}
+using Kernel = void (*)(rt_scene_dev, rt_trace_params);
 
-template <bool SO, int LM, bool ANY, bool REC>
-hipError_t occupancy_one(size_t lds, int* blocks) {
-    if (lds > 65536) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rt_trace_kernel<SO, LM, ANY, REC>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, reinterpret_cast<const void*>(&rt_trace_kernel<SO, LM, ANY, REC>),
-                                                        RT_TRACE_THREADS, lds);
+// the instantiation of a launch: any-hit before record
+template <bool SO, int LM>
+Kernel pick_mode(bool any, bool record) {
+    if (any) return rt_trace_kernel<SO, LM, true, false>;
+    if (record) return rt_trace_kernel<SO, LM, false, true>;
+    return rt_trace_kernel<SO, LM, false, false>;
 }
-
-// every instantiation behind one switch: F<SO, LM, ANY, REC>::run(args...)
-template <template <bool, int, bool, bool> class F, bool SO, typename... A>
-hipError_t dispatch_lds(int lds_mode, bool any, bool record, A... args) {
-#define RT_TRACE_CASE(LM)                                                        \
-    do {                                                                         \
-        if (any) return F<SO, LM, true, false>::run(args...);                   \
-        if (record) return F<SO, LM, false, true>::run(args...);                \
-        return F<SO, LM, false, false>::run(args...);                           \
-    } while (0)
-    if (lds_mode == 2) RT_TRACE_CASE(2);
-    if (lds_mode == 1) RT_TRACE_CASE(1);
-    RT_TRACE_CASE(0);
-#undef RT_TRACE_CASE
+template <bool SO>
+Kernel pick_lds(int lds_mode, bool any, bool record) {
+    if (lds_mode == 2) return pick_mode<SO, 2>(any, record);
+    if (lds_mode == 1) return pick_mode<SO, 1>(any, record);
+    return pick_mode<SO, 0>(any, record);
 }
-template <bool SO, int LM, bool ANY, bool REC>
-struct Launch { static hipError_t run(const rt_scene_dev* sd, const rt_trace_params* tp, dim3 grid, size_t lds, hipStream_t st) { return launch_one<SO, LM, ANY, REC>(*sd, *tp, grid, lds, st); } };
-template <bool SO, int LM, bool ANY, bool REC>
-struct Occupancy { static hipError_t run(size_t lds, int* blocks) { return occupancy_one<SO, LM, ANY, REC>(lds, blocks); } };
+Kernel pick(bool spheres_only, int lds_mode, bool any, bool record) {
+    return spheres_only ? pick_lds<true>(lds_mode, any, record) : pick_lds<false>(lds_mode, any, record);
+}
 
 }  // namespace
 
 hipError_t rt_launch_trace(bool spheres_only, int lds_mode, const rt_scene_dev& sd, const rt_trace_params& tp, dim3 grid, size_t lds,
                            hipStream_t st) {
-    const bool any = tp.hit_out != nullptr, record = tp.record != 0;
-    if (spheres_only) return dispatch_lds<Launch, true>(lds_mode, any, record, &sd, &tp, grid, lds, st);
-    return dispatch_lds<Launch, false>(lds_mode, any, record, &sd, &tp, grid, lds, st);
+    const Kernel kernel = pick(spheres_only, lds_mode, tp.hit_out != nullptr, tp.record != 0);
+    return rt_launch_kernel(kernel, dim3(RT_TRACE_THREADS), grid, lds, st, sd, tp);
 }
 
 hipError_t rt_trace_occupancy(bool spheres_only, int lds_mode, bool any, bool record, size_t lds, int* blocks_per_cu) {
-    if (spheres_only) return dispatch_lds<Occupancy, true>(lds_mode, any, record, lds, blocks_per_cu);
-    return dispatch_lds<Occupancy, false>(lds_mode, any, record, lds, blocks_per_cu);
+    return rt_kernel_occupancy(pick(spheres_only, lds_mode, any, record), RT_TRACE_THREADS, lds, blocks_per_cu);
 }
