@@ -151,7 +151,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
                   "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive",
                   "rt_radiance_rays", "rt_render_aov", "rt_render_aov_through", "rt_denoise_workspace_bytes", "rt_denoise", "rt_render_variance",
-                  "rt_denoise_variance"]
+                  "rt_denoise_variance", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info"]
 
 _rt = None
 _host = None
@@ -237,6 +237,11 @@ def rt_lib():
                                          C.c_void_p, C.POINTER(RtStats)]
         L.rt_denoise_variance.argtypes = [C.POINTER(RtDenoiseDesc), C.POINTER(RtDenoiseVarianceDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.rt_debug_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rt_debug_prior.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_uint64)]
+        L.rt_debug_cal_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.rt_debug_rank_info.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _rt = L
     return _rt

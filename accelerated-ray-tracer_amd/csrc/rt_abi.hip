@@ -1142,6 +1142,11 @@ rt_status rt_scene_walk_info(const rt_scene* s, int32_t* nodes_reference, int32_
     return RT_OK;
 }
 
+namespace {
+// 8x8 pixel tiles across `pixels` pixels or rows (the tile grid of a call is tiles_across(nx) x tiles_across(local_rows))
+inline int tiles_across(int pixels) { return (pixels + 7) / 8; }
+}  // namespace
+
 int32_t rt_frame_local_rows(const rt_frame_desc* f) {
     if (!f || f->ny <= 0 || f->tile_rows <= 0 || f->tile_stride <= 0 || f->tile_first < 0) return -1;
     const int n_tiles = (f->ny + f->tile_rows - 1) / f->tile_rows;
@@ -1623,6 +1628,142 @@ rt_status rt_debug_wave_last(rt_scene* s, unsigned long long* out, int n_waves) 
     return RT_OK;
 }
 
+// ---- test seams of the ranking and the cost prior (rt_rank.hip; tests/test_rank.py): the launches rt_render makes, once, on
+// caller-supplied host data.  Null stream, synchronous; every check runs before any HIP call.
+namespace {
+enum { RANK_PARAM_WORDS = 20, RANK_INFO_WORDS = 13 };
+static_assert(sizeof(rt_rank_info) == RANK_INFO_WORDS * 4, "rt_debug_rank / rt_debug_rank_info copy rt_rank_info as 13 words");
+// device allocations of one seam call, freed when it returns
+struct seam_buffers {
+    std::vector<void*> all;
+    ~seam_buffers() { for (void* p : all) (void)hipFree(p); }
+    hipError_t get(void** p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) all.push_back(*p); return e; }
+};
+}  // namespace
+
+rt_status rt_debug_rank(const uint32_t* cost, const uint32_t* tile_cost, uint64_t rays, const uint32_t* params, uint32_t* tile_order,
+                        uint32_t* cost_out, uint32_t* heavy_pixels, uint32_t* info13) {
+    if (!cost || !tile_cost || !params || !tile_order || !cost_out || !heavy_pixels || !info13) return invalid("rt_debug_rank: null argument");
+    rt_rank_params rp;
+    memset(&rp, 0, sizeof(rp));
+    const int32_t* ip = reinterpret_cast<const int32_t*>(params);
+    rp.n_pixels = params[0]; rp.n_tiles = params[1]; rp.heavy_cap = params[2];
+    rp.max_grid = params[3]; rp.waves_per_wg = params[4]; rp.normal_need = params[5];
+    rp.sparse_stride = ip[6]; rp.semi_stride = ip[7]; rp.sparse_percent = ip[8]; rp.sparse_work_percent = ip[9];
+    rp.tier_possible = ip[10]; rp.tier1_pixels = ip[11]; rp.tier1_depth = ip[12]; rp.tier_wgs_cap = ip[13];
+    rp.tier_waves_per_main_wg = ip[14]; rp.nx = ip[15]; rp.smooth_percent = ip[16];
+    memcpy(&rp.heavy_factor, params + 17, 4); memcpy(&rp.sparse_factor, params + 18, 4); memcpy(&rp.tier1_factor, params + 19, 4);
+    if (rp.n_pixels < 1u || rp.n_pixels >= (1u << 31)) return invalid("rt_debug_rank: n_pixels must be 1 .. 2^31 - 1");
+    if (rp.n_tiles < 1u || rp.n_tiles > rp.n_pixels) return invalid("rt_debug_rank: n_tiles must be 1 .. n_pixels");
+    if (rp.heavy_cap < 1u || rp.heavy_cap > (1u << 24)) return invalid("rt_debug_rank: heavy_cap must be 1 .. 2^24");
+    if (rp.max_grid > (1u << 20) || rp.normal_need > (1u << 20)) return invalid("rt_debug_rank: max_grid and normal_need must be at most 2^20");
+    if (rp.waves_per_wg < 1u || rp.waves_per_wg > 16u) return invalid("rt_debug_rank: waves_per_wg must be 1 .. 16");
+    if (rp.sparse_stride < 0 || rp.sparse_stride > 64 || rp.semi_stride < 0 || rp.semi_stride > 64) return invalid("rt_debug_rank: sparse_stride and semi_stride must be 0 .. 64");
+    if (rp.sparse_percent < 0 || rp.sparse_percent > 100 || rp.sparse_work_percent < 0 || rp.sparse_work_percent > 100 || rp.smooth_percent < 0 || rp.smooth_percent > 100)
+        return invalid("rt_debug_rank: sparse_percent, sparse_work_percent and smooth_percent must be 0 .. 100");
+    if (rp.tier1_pixels < 0 || rp.tier1_depth < 0 || rp.tier1_depth > 65536 || rp.tier_wgs_cap < 0 || rp.tier_waves_per_main_wg < 0)
+        return invalid("rt_debug_rank: tier1_pixels, tier1_depth (at most 65536), tier_wgs_cap and tier_waves_per_main_wg must not be negative");
+    if (rp.nx < 1 || (uint32_t)rp.nx > rp.n_pixels) return invalid("rt_debug_rank: nx must be 1 .. n_pixels");
+    float top = 0.f;
+    for (const float fac : {rp.heavy_factor, rp.sparse_factor, rp.tier1_factor}) {
+        if (!(fac >= 0.f) || !(fac <= 1000.f)) return invalid("rt_debug_rank: the three factors must be 0 .. 1000");
+        top = fac > top ? fac : top;
+    }
+    if (!((double)rays / (double)rp.n_pixels * (double)top + 1.0 < 4294967296.0)) return invalid("rt_debug_rank: rays / n_pixels x the largest factor must stay below 2^32");
+    { const rt_status ud = use_device(g_device); if (ud != RT_OK) return ud; }
+    seam_buffers mem;
+    unsigned int *d_tile_cost = nullptr, *d_tile_order = nullptr;
+    unsigned long long* d_rays = nullptr;
+    HIPCHK(mem.get((void**)&rp.state, (size_t)rp.n_pixels * sizeof(rt_pixel_state)));
+    HIPCHK(mem.get((void**)&d_tile_cost, (size_t)rp.n_tiles * sizeof(unsigned int)));
+    HIPCHK(mem.get((void**)&d_tile_order, (size_t)rp.n_tiles * sizeof(unsigned int)));
+    HIPCHK(mem.get((void**)&d_rays, sizeof(unsigned long long)));
+    HIPCHK(mem.get((void**)&rp.heavy_list, (size_t)rp.heavy_cap * sizeof(unsigned long long)));
+    HIPCHK(mem.get((void**)&rp.heavy_pixels, (size_t)rp.heavy_cap * sizeof(unsigned int)));
+    HIPCHK(mem.get((void**)&rp.info, sizeof(rt_rank_info)));
+    rp.tile_cost = d_tile_cost; rp.tile_order = d_tile_order; rp.ray_counter = d_rays;
+    std::vector<rt_pixel_state> h_state(rp.n_pixels);                  // (value-initialised: every field but the cost is zero)
+    for (uint32_t i = 0; i < rp.n_pixels; ++i) h_state[i].cost = cost[i];
+    const unsigned long long h_rays = rays;
+    HIPCHK(hipMemcpy(rp.state, h_state.data(), (size_t)rp.n_pixels * sizeof(rt_pixel_state), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tile_cost, tile_cost, (size_t)rp.n_tiles * sizeof(unsigned int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rays, &h_rays, sizeof(h_rays), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_tile_order, 0xFF, (size_t)rp.n_tiles * sizeof(unsigned int)));
+    HIPCHK(hipMemset(rp.heavy_list, 0xFF, (size_t)rp.heavy_cap * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(rp.heavy_pixels, 0xFF, (size_t)rp.heavy_cap * sizeof(unsigned int)));   // entries the ranking does not write stay 0xFFFFFFFF
+    HIPCHK(hipMemset(rp.info, 0xFF, sizeof(rt_rank_info)));
+    HIPCHK(rt_launch_rank(rp, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(h_state.data(), rp.state, (size_t)rp.n_pixels * sizeof(rt_pixel_state), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < rp.n_pixels; ++i) cost_out[i] = h_state[i].cost;
+    HIPCHK(hipMemcpy(tile_order, d_tile_order, (size_t)rp.n_tiles * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(heavy_pixels, rp.heavy_pixels, (size_t)rp.heavy_cap * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(info13, rp.info, sizeof(rt_rank_info), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status rt_debug_prior(const uint32_t* cal_cost, int32_t cal_nx, int32_t cal_ny, int32_t nx, int32_t ny, int32_t tile_rows, int32_t tile_first,
+                         int32_t tile_stride, uint32_t* cost_out, uint32_t* tile_cost_out, uint64_t* total_out) {
+    if (!cal_cost || !cost_out || !tile_cost_out || !total_out) return invalid("rt_debug_prior: null argument");
+    if (cal_nx < 1 || cal_ny < 1 || (long long)cal_nx * cal_ny >= (1ll << 31)) return invalid("rt_debug_prior: bad calibration grid size");
+    if (nx < 1 || ny < 1 || (long long)nx * ny >= (1ll << 31)) return invalid("rt_debug_prior: bad frame size");
+    rt_frame_desc f;
+    memset(&f, 0, sizeof(f));
+    f.nx = nx; f.ny = ny; f.tile_rows = tile_rows; f.tile_first = tile_first; f.tile_stride = tile_stride;
+    const int local_rows = rt_frame_local_rows(&f);
+    if (local_rows < 0) return invalid("rt_debug_prior: bad row partition");
+    if (local_rows == 0) return invalid("rt_debug_prior: the partition has no rows");
+    { const rt_status ud = use_device(g_device); if (ud != RT_OK) return ud; }
+    rt_prior_params pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.cal_nx = cal_nx; pp.cal_ny = cal_ny; pp.nx = nx; pp.ny = ny; pp.local_rows = local_rows; pp.tiles_x = tiles_across(nx);
+    pp.tile_rows = tile_rows; pp.tile_first = tile_first; pp.tile_stride = tile_stride;
+    const size_t n_pixels = (size_t)local_rows * (size_t)nx, n_tiles = (size_t)pp.tiles_x * (size_t)tiles_across(local_rows), n_cal = (size_t)cal_nx * (size_t)cal_ny;
+    seam_buffers mem;
+    unsigned int* d_cal = nullptr;
+    HIPCHK(mem.get((void**)&pp.state, n_pixels * sizeof(rt_pixel_state)));
+    HIPCHK(mem.get((void**)&pp.tile_cost, n_tiles * sizeof(unsigned int)));
+    HIPCHK(mem.get((void**)&pp.total, sizeof(unsigned long long)));
+    HIPCHK(mem.get((void**)&d_cal, n_cal * sizeof(unsigned int)));
+    pp.cal_cost = d_cal;
+    HIPCHK(hipMemcpy(d_cal, cal_cost, n_cal * sizeof(unsigned int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(pp.state, 0xFF, n_pixels * sizeof(rt_pixel_state)));          // a pixel the kernel skips shows as 0xFFFFFFFF
+    HIPCHK(hipMemset(pp.tile_cost, 0, n_tiles * sizeof(unsigned int)));            // (the kernel adds to both, as in rt_render)
+    HIPCHK(hipMemset(pp.total, 0, sizeof(unsigned long long)));
+    HIPCHK(rt_launch_prior(pp, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<rt_pixel_state> h_state(n_pixels);
+    HIPCHK(hipMemcpy(h_state.data(), pp.state, n_pixels * sizeof(rt_pixel_state), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_pixels; ++i) cost_out[i] = h_state[i].cost;
+    HIPCHK(hipMemcpy(tile_cost_out, pp.tile_cost, n_tiles * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpy(&total, pp.total, sizeof(total), hipMemcpyDeviceToHost));
+    *total_out = total;
+    return RT_OK;
+}
+
+rt_status rt_debug_cal_cost(rt_scene* s, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny) {
+    if (!s) return invalid("rt_debug_cal_cost: null scene");
+    if (!out || !nx || !ny) return invalid("rt_debug_cal_cost: null argument");
+    if (cap < 64) return invalid("rt_debug_cal_cost: cap must be at least 64 (the smallest calibration grid is 8 x 8)");
+    if (!s->d_cal_cost || s->cal_nx <= 0 || s->cal_ny <= 0) return invalid("rt_debug_cal_cost: the scene kept no calibration costs");
+    *nx = s->cal_nx; *ny = s->cal_ny;
+    if ((long long)cap < (long long)s->cal_nx * s->cal_ny) return invalid("rt_debug_cal_cost: cap is smaller than the calibration grid (nx and ny are set)");
+    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    HIPCHK(hipMemcpy(out, s->d_cal_cost, (size_t)s->cal_nx * s->cal_ny * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status rt_debug_rank_info(rt_scene* s, uint32_t* out13) {
+    if (!s) return invalid("rt_debug_rank_info: null scene");
+    if (!out13) return invalid("rt_debug_rank_info: null argument");
+    if (!s->ranked_frame || !s->d_rank) return invalid("rt_debug_rank_info: the scene's last frame was not ranked");
+    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    if (s->frame_pending) HIPCHK(hipStreamSynchronize(s->pending_stream));
+    HIPCHK(hipMemcpy(out13, s->d_rank, sizeof(rt_rank_info), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 namespace {
 // The main kernel's launch shape for a launch over `n_pixels` pixels (`fp.work_items` work items): LDS residency mode, workgroup
 // shape, grid and stage quorums (written to fp).  Shared by rt_render / rt_render_window and rt_render_adaptive's passes.
@@ -1785,8 +1926,8 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     fp.use_gradient_bg = f->use_gradient_bg;
     fp.tile_rows = f->tile_rows; fp.tile_first = f->tile_first; fp.tile_stride = f->tile_stride;
     fp.local_rows = local_rows;
-    fp.tiles_x = (f->nx + 7) / 8;
-    const int tiles_y = (local_rows + 7) / 8;
+    fp.tiles_x = tiles_across(f->nx);
+    const int tiles_y = tiles_across(local_rows);
     if ((long long)fp.tiles_x * tiles_y * 64 >= (1ll << 31)) return invalid("frame too large");
     fp.work_items = (uint32_t)fp.tiles_x * (uint32_t)tiles_y * 64u;
     fp.sparse_priority = g_opt.sparse_priority; fp.sparse_eager = g_opt.sparse_eager; fp.semi_priority = g_opt.semi_priority; fp.tier_priority = g_opt.tier_priority;

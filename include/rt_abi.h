@@ -617,6 +617,32 @@ rt_status rt_multi_row_owner(int32_t global_row, int32_t tile_rows, int32_t n_gp
  * reassembly step on caller-supplied device buffers, staging[world][max_rows][nx*3] -> frame[ny][nx*3], synchronous. */
 rt_status rt_multi_probe_rccl(const char* library_name);
 rt_status rt_multi_debug_uninterleave(const float* staging, float* frame, int32_t nx, int32_t ny, int32_t tile_rows, int32_t world, int32_t max_rows);
+/* diagnostics of the cost-aware schedule (tests/test_rank.py, tests/rank_expect.py): the device-side ranking and the cost prior
+ * run once on caller-supplied HOST buffers -- device memory allocated, the launches rt_render makes enqueued on the null stream,
+ * synchronised, copied back, freed -- and what a scene holds of them.  Every argument check runs before any HIP call and is
+ * RT_ERR_INVALID with a detail string; the first two need rt_init and no scene.
+ * rt_debug_rank: one ranking (tile order, heavy list, tiers).  cost[n_pixels] = the parked costs (bit 31 may be set: a stale list
+ * flag), tile_cost[n_tiles], rays = the "rays so far" the thresholds are taken from; params = 20 words:
+ *   [0] n_pixels  [1] n_tiles  [2] heavy_cap  [3] max_grid  [4] waves_per_wg  [5] normal_need                       (uint32)
+ *   [6] sparse_stride  [7] semi_stride  [8] sparse_percent  [9] sparse_work_percent  [10] tier_possible  [11] tier1_pixels
+ *   [12] tier1_depth  [13] tier_wgs_cap  [14] tier_waves_per_main_wg  [15] nx (pixels per local row)  [16] smooth_percent (int32)
+ *   [17] heavy_factor  [18] sparse_factor  [19] tier1_factor                                                       (float)
+ * Out: tile_order[n_tiles], cost_out[n_pixels] (the costs with this ranking's list flags), heavy_pixels[heavy_cap] (entries the
+ * ranking did not write are 0xFFFFFFFF) and info13 = heavy_items, heavy_threshold, tier1_items, tier2_items, tier1_wgs,
+ * main_skip_wgs, sparse_wgs, sparse_stride, semi_wgs, semi_stride, threshold1, threshold2, collected.
+ * rt_debug_prior: the cost prior of the rows (tile_rows, tile_first, tile_stride) of an nx x ny frame from the calibration
+ * costs cal_cost[cal_ny][cal_nx] (row 0 = bottom).  Out: cost_out[local_rows * nx] with local_rows = rt_frame_local_rows,
+ * tile_cost_out[((local_rows + 7) / 8) * ((nx + 7) / 8)] and their sum.
+ * rt_debug_cal_cost: the calibration costs the scene kept at rt_scene_create, out[*ny][*nx]; cap = the words out holds, at
+ * least 64 (the smallest grid is 8 x 8).  A scene that kept none, or a cap below the grid (nx, ny are set), is RT_ERR_INVALID.
+ * rt_debug_rank_info: the 13 words, as above, that the last ranking of the scene's last frame left; RT_ERR_INVALID when that
+ * frame was not ranked. */
+rt_status rt_debug_rank(const uint32_t* cost, const uint32_t* tile_cost, uint64_t rays, const uint32_t* params, uint32_t* tile_order,
+                        uint32_t* cost_out, uint32_t* heavy_pixels, uint32_t* info13);
+rt_status rt_debug_prior(const uint32_t* cal_cost, int32_t cal_nx, int32_t cal_ny, int32_t nx, int32_t ny, int32_t tile_rows, int32_t tile_first,
+                         int32_t tile_stride, uint32_t* cost_out, uint32_t* tile_cost_out, uint64_t* total_out);
+rt_status rt_debug_cal_cost(rt_scene* scene, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny);
+rt_status rt_debug_rank_info(rt_scene* scene, uint32_t* out13);
 
 /* Tuning knobs (for A/B measurements; defaults are what ships).  Unknown keys
  * return RT_ERR_INVALID.  The knobs are process-wide; rt_reset_options()
