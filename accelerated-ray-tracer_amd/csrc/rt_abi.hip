@@ -52,7 +52,7 @@ struct rt_options {
     int newpath_threshold = 0;   // lanes waiting for a new path before stage E runs; 0 = by kernel family: 24 spheres-only, 8 general (measured: Book-2 final 382 -> 364 ms with 8, Book-1 32.2 -> 35.1)
     int sparse_stride = 8;      // lanes per pixel in sparse waves (64 / live lanes); 0 disables sparse waves
     int split_samples = 16;      // samples per pixel rendered before pixels are ranked by measured cost (round 3: 16 and no presplit -- two parts; was 32 after a first look at 8)
-    int tier_auto = 1;           // size the tiers from the share of the frame this call renders (see rank_pixels); 0 = the knobs as set
+    int tier_auto = 1;           // size the tiers from the share of the frame this call renders (effective_tier_sizes); 0 = the knobs as set
     int tier_kernel = 1;         // tier 1 of the list goes to the tier kernel (rt_kernel_tier.h) on a side stream; 0 = no tier 1
     int prior = 1;               // the first part of a split frame is already ranked: on the cost prior of the calibration frame
     int resplit_samples = 0;     // a second ranking: samples [split, resplit) run with tiers ranked on `split` samples, the rest ranked on `resplit` (0 = off)
@@ -112,8 +112,13 @@ rt_options g_opt;
             return RT_ERR_HIP;                                                        \
         }                                                                             \
     } while (0)
+// a step that returns an rt_status: a failure is the caller's result
+#define RT_TRY(expr) do { const rt_status st_ = (expr); if (st_ != RT_OK) return st_; } while (0)
 
 rt_status invalid(const char* why) { g_detail = why; return RT_ERR_INVALID; }
+
+// 8x8 pixel tiles across `pixels` pixels or rows (the tile grid of a call is tiles_across(nx) x tiles_across(local_rows))
+inline int tiles_across(int pixels) { return (pixels + 7) / 8; }
 
 template <class T>
 rt_status upload(const T* src, size_t count, const T** dst) {
@@ -128,6 +133,41 @@ rt_status upload(const T* src, size_t count, const T** dst) {
     *dst = static_cast<const T*>(p);
     return RT_OK;
 }
+
+// Frees what the pointers hold and allocates them anew: the step every cached buffer, or group of buffers under one capacity,
+// takes when a frame needs more than it has.
+struct sized_buffer { void** p; size_t bytes; };
+rt_status reallocate(std::initializer_list<sized_buffer> buffers) {
+    for (const sized_buffer& b : buffers) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
+    for (const sized_buffer& b : buffers) HIPCHK(hipMalloc(b.p, b.bytes));
+    return RT_OK;
+}
+// a cached device buffer of `capacity` elements, grown to hold `need`
+template <class T> rt_status grow(T*& p, size_t& capacity, size_t need) {
+    if (capacity >= need) return RT_OK;
+    capacity = 0;
+    RT_TRY(reallocate({{(void**)&p, need * sizeof(T)}}));
+    capacity = need;
+    return RT_OK;
+}
+
+// Device memory of one call, freed when the call returns: allocations of their own (get), which a caller may cut into
+// 256-byte-rounded pieces (rounded, take).  A call that enqueues work on the memory guards it with its stream: every way out
+// but the one through settled() -- the call has waited for its work -- synchronises that stream before the memory is freed.
+struct call_memory {
+    std::vector<void*> all;
+    hipStream_t stream = nullptr;
+    bool guarded = false;
+    ~call_memory() {
+        if (guarded && !all.empty()) (void)hipStreamSynchronize(stream);   // nothing of a failed call may still use the memory
+        for (void* p : all) (void)hipFree(p);
+    }
+    void guard(hipStream_t st) { stream = st; guarded = true; }
+    void settled() { guarded = false; }
+    hipError_t get(void** p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) all.push_back(*p); return e; }
+    static size_t rounded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+    static char* take(char*& at, size_t bytes) { char* piece = at; at += rounded(bytes); return piece; }
+};
 
 }  // namespace
 
@@ -182,7 +222,7 @@ struct rt_scene {
     // rt_render_variance: per local pixel T_{b-1}, A, Q (the parked pixels live in d_adapt_state, a host variance_out's device
     // image in d_adapt_spp: 4 bytes per pixel either way)
     double* d_var_acc = nullptr;
-    size_t var_capacity = 0;
+    size_t var_capacity = 0;                     // in doubles: three per pixel
 };
 
 // Progressive accumulation (rt_render_window): the parked pixels of one frame description between windows.
@@ -741,8 +781,8 @@ rt_status measure_pass_counts(rt_scene* s, const rt_node* d_tree, int n_tree, st
     fp.node_pass_lds = (size_t)n * sizeof(unsigned int) <= 48u * 1024u ? 1 : 0;
     fp.seed_base = 1984; fp.nx = nx; fp.ny = ny; fp.ns = 4; fp.gamma = 1.0f;
     fp.tile_rows = ny; fp.tile_first = 0; fp.tile_stride = 1; fp.local_rows = ny;
-    fp.tiles_x = (nx + 7) / 8;
-    fp.work_items = (uint32_t)fp.tiles_x * (uint32_t)((ny + 7) / 8) * 64u;
+    fp.tiles_x = tiles_across(nx);
+    fp.work_items = (uint32_t)fp.tiles_x * (uint32_t)tiles_across(ny) * 64u;
     fp.sample_begin = 0; fp.sample_end = fp.ns;
     rt_status st = RT_OK;
     std::vector<unsigned int> h((size_t)n);
@@ -845,14 +885,11 @@ rt_status build_tier_data(rt_scene* s, const rt_scene_desc* d) {
         for (int c = 0; c < 3; ++c) { ranges[(size_t)k * 8 + c] = rl[c]; ranges[(size_t)k * 8 + 3 + c] = rh[c]; }
     }
     const float* d_lo = nullptr; const float* d_hi = nullptr; const float* d_ranges = nullptr;
-    rt_status st = upload(lo.data(), lo.size(), &d_lo);
-    if (st != RT_OK) return st;
+    RT_TRY(upload(lo.data(), lo.size(), &d_lo));
     s->allocs.push_back(const_cast<float*>(d_lo));
-    st = upload(hi.data(), hi.size(), &d_hi);
-    if (st != RT_OK) return st;
+    RT_TRY(upload(hi.data(), hi.size(), &d_hi));
     s->allocs.push_back(const_cast<float*>(d_hi));
-    st = upload(ranges.data(), ranges.size(), &d_ranges);
-    if (st != RT_OK) return st;
+    RT_TRY(upload(ranges.data(), ranges.size(), &d_ranges));
     s->allocs.push_back(const_cast<float*>(d_ranges));
     s->dev.leaf_lo = reinterpret_cast<const float4*>(d_lo); s->dev.leaf_hi = reinterpret_cast<const float4*>(d_hi); s->dev.slot_ranges = d_ranges;
     s->dev.n_leaves = m; s->dev.n_slots = slots; s->dev.n_media_leaves = media;
@@ -881,10 +918,7 @@ rt_status build_walk(rt_scene* s, const rt_scene_desc* d) {
     std::vector<double> pass;
     std::vector<float> ray_sample;
     double root_visits = 0.0;
-    if (g_opt.bvh_collapse >= 2) {
-        const rt_status st = measure_pass_counts(s, s->dev.nodes_ref, n, pass, root_visits, nullptr, 0, /*keep_cost=*/true);
-        if (st != RT_OK) return st;
-    }
+    if (g_opt.bvh_collapse >= 2) RT_TRY(measure_pass_counts(s, s->dev.nodes_ref, n, pass, root_visits, nullptr, 0, /*keep_cost=*/true));
     const bool measured = root_visits > 0.0;
     if (!measured) {   // by surface area: a ray that passes a box passes a box inside it about in proportion to the areas
         pass.assign((size_t)n, 0.0);
@@ -916,12 +950,11 @@ rt_status build_walk(rt_scene* s, const rt_scene_desc* d) {
             std::vector<rt_node> enc;
             device_nodes(tree.data(), tree.size(), enc);
             const rt_node* d_tree = nullptr;
-            rt_status st = upload(enc.data(), enc.size(), &d_tree);
-            if (st != RT_OK) return st;
+            RT_TRY(upload(enc.data(), enc.size(), &d_tree));
             std::vector<double> pass2;
             double rays2 = 0.0;
             // the first of these passes also keeps ~4000 of its rays for method 2 (same frame, same rays in every pass)
-            st = measure_pass_counts(s, d_tree, m, pass2, rays2, method == 0 ? &ray_sample : nullptr, (uint32_t)(root_visits / 4096.0) + 1u);
+            const rt_status st = measure_pass_counts(s, d_tree, m, pass2, rays2, method == 0 ? &ray_sample : nullptr, (uint32_t)(root_visits / 4096.0) + 1u);
             (void)hipFree(const_cast<rt_node*>(d_tree));
             if (st != RT_OK) return st;
             collapse_plan plan2;
@@ -941,8 +974,7 @@ rt_status build_walk(rt_scene* s, const rt_scene_desc* d) {
     const rt_node* d_walk = nullptr;
     std::vector<rt_node> enc;
     device_nodes(walk.data(), walk.size(), enc);
-    const rt_status st = upload(enc.data(), enc.size(), &d_walk);
-    if (st != RT_OK) return st;
+    RT_TRY(upload(enc.data(), enc.size(), &d_walk));
     s->allocs.push_back(const_cast<void*>(static_cast<const void*>(d_walk)));
     s->dev.nodes = d_walk; s->dev.n_nodes = (int32_t)walk.size();
     s->walk_tests_before = plan.tests_before; s->walk_tests_after = plan.tests_after;
@@ -971,11 +1003,11 @@ int rt_internal_option(const char* key) { return std::string(key) == "multi_forc
 rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_scene** out) {
     if (!out) return invalid("null output pointer");
     *out = nullptr;
-    { const rt_status ud = use_device(device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(device));
     bool so = false, uv = false;
     int tx = 0;
-    rt_status st = validate(d, so, tx, uv);
-    if (st != RT_OK) return st;
+    RT_TRY(validate(d, so, tx, uv));
+    rt_status st = RT_OK;
 
 #define UPSRC_spheres spheres
 #define UPSRC_quads quads
@@ -1143,8 +1175,41 @@ rt_status rt_scene_walk_info(const rt_scene* s, int32_t* nodes_reference, int32_
 }
 
 namespace {
-// 8x8 pixel tiles across `pixels` pixels or rows (the tile grid of a call is tiles_across(nx) x tiles_across(local_rows))
-inline int tiles_across(int pixels) { return (pixels + 7) / 8; }
+// What a call renders of the frame `f` describes: its rows of the partition, its grid of 8x8 tiles, and the pixels and work items
+// (64 per tile) in them.
+struct frame_geometry {
+    int local_rows, tiles_x, tiles_y;
+    size_t n_pixels;
+    uint32_t work_items;
+};
+// The words of the four failed checks.  They differ between the entry points, and tests and the Python layer match on them.
+struct frame_texts { const char *size, *large, *partition, *tiles; };
+const frame_texts RENDER_FRAME_TEXTS = {"nx, ny and ns must be positive", "frame too large", "bad row partition", "frame too large"};
+const frame_texts STATE_FRAME_TEXTS = {"bad frame size", "bad frame size", "bad row partition", "bad frame size"};
+
+// The frame checks of every entry point that takes a frame: a positive size (and sample count, where the entry point reads
+// f->ns), fewer than 2^31 pixels, a valid row partition, fewer than 2^31 work items.  `who` (may be null) prefixes the text of
+// a failed check.  No HIP call.
+rt_status check_frame(const char* who, const rt_frame_desc* f, bool check_ns, const frame_texts& text, frame_geometry& g) {
+    auto bad = [&](const char* why) { return who ? invalid((std::string(who) + ": " + why).c_str()) : invalid(why); };
+    if (f->nx <= 0 || f->ny <= 0 || (check_ns && f->ns <= 0)) return bad(text.size);
+    if ((long long)f->nx * f->ny >= (1ll << 31)) return bad(text.large);
+    g.local_rows = rt_frame_local_rows(f);
+    if (g.local_rows < 0) return bad(text.partition);
+    g.tiles_x = tiles_across(f->nx); g.tiles_y = tiles_across(g.local_rows);
+    if ((long long)g.tiles_x * g.tiles_y * 64 >= (1ll << 31)) return bad(text.tiles);
+    g.n_pixels = (size_t)g.local_rows * (size_t)f->nx;
+    g.work_items = (uint32_t)g.tiles_x * (uint32_t)g.tiles_y * 64u;
+    return RT_OK;
+}
+
+// where the kernels write the frame: the caller's device buffer, or the scene's image of a host buffer (`floats` floats)
+rt_status device_fb(rt_scene* s, float* fb, int fb_on_device, size_t floats, float** d_fb) {
+    if (!fb_on_device) RT_TRY(grow(s->d_fb, s->d_fb_floats, floats));
+    *d_fb = fb_on_device ? fb : s->d_fb;
+    return RT_OK;
+}
+
 }  // namespace
 
 int32_t rt_frame_local_rows(const rt_frame_desc* f) {
@@ -1168,7 +1233,7 @@ int32_t rt_local_to_global_row(const rt_frame_desc* f, int32_t local_row) {
 rt_status rt_frame_finish(rt_scene* s, rt_stats* stats) {
     if (!s) return invalid("null scene");
     if (!s->frame_pending) { if (stats) *stats = s->pending_stats; return RT_OK; }
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     HIPCHK(hipEventSynchronize(s->ev_stop));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
@@ -1189,7 +1254,7 @@ rt_status rt_frame_finish(rt_scene* s, rt_stats* stats) {
 namespace {
 // a pointer rt_trace_rays / rt_radiance_rays (`who`) hands to a kernel: null, or `bytes` of device (or managed) memory of
 // `device`, aligned to `align` bytes
-static rt_status check_trace_ptr(const void* p, size_t bytes, int device, const char* what, const char* who = "rt_trace_rays", unsigned align = 4) {
+rt_status check_trace_ptr(const void* p, size_t bytes, int device, const char* what, const char* who, unsigned align) {
     if (!p) return RT_OK;
     std::string why;
     if (reinterpret_cast<uintptr_t>(p) & (align - 1u)) { why = std::string(who) + ": " + what + " is not " + std::to_string(align) + "-byte aligned"; return invalid(why.c_str()); }
@@ -1218,6 +1283,12 @@ static rt_status check_trace_ptr(const void* p, size_t bytes, int device, const 
     } else {
         (void)hipGetLastError();
     }
+    return RT_OK;
+}
+// a table of such pointers, checked in its order
+struct traced_ptr { const void* p; size_t bytes; const char* what; unsigned align; };
+extern "C++" template <class Table> rt_status check_trace_ptrs(const Table& table, int device, const char* who) {
+    for (const traced_ptr& q : table) RT_TRY(check_trace_ptr(q.p, q.bytes, device, q.what, who, q.align));
     return RT_OK;
 }
 
@@ -1272,16 +1343,13 @@ rt_status rt_trace_rays(rt_scene* s, const rt_ray_batch* b, void* stream_v, int 
     }
     if (!s) return invalid("rt_trace_rays: null scene");
     if (b->n == 0) return RT_OK;
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     const size_t n = (size_t)b->n, f = sizeof(float), i = sizeof(int32_t);
-    const struct { const void* p; size_t bytes; const char* what; } ptrs[] = {
-        {b->origins, 3 * n * f, "origins"}, {b->directions, 3 * n * f, "directions"}, {b->times, n * f, "times"}, {b->tmax, n * f, "tmax"},
-        {b->t_out, n * f, "t_out"}, {b->prim_out, n * i, "prim_out"}, {b->inst_out, n * i, "inst_out"}, {b->point_out, 3 * n * f, "point_out"},
-        {b->normal_out, 3 * n * f, "normal_out"}, {b->uv_out, 2 * n * f, "uv_out"}, {b->mat_out, n * i, "mat_out"}, {b->hit_out, n, "hit_out"}};
-    for (const auto& q : ptrs) {
-        const rt_status st = check_trace_ptr(q.p, q.bytes, s->device, q.what);
-        if (st != RT_OK) return st;
-    }
+    const traced_ptr ptrs[] = {
+        {b->origins, 3 * n * f, "origins", 4}, {b->directions, 3 * n * f, "directions", 4}, {b->times, n * f, "times", 4}, {b->tmax, n * f, "tmax", 4},
+        {b->t_out, n * f, "t_out", 4}, {b->prim_out, n * i, "prim_out", 4}, {b->inst_out, n * i, "inst_out", 4}, {b->point_out, 3 * n * f, "point_out", 4},
+        {b->normal_out, 3 * n * f, "normal_out", 4}, {b->uv_out, 2 * n * f, "uv_out", 4}, {b->mat_out, n * i, "mat_out", 4}, {b->hit_out, n, "hit_out", 4}};
+    RT_TRY(check_trace_ptrs(ptrs, s->device, "rt_trace_rays"));
 
     rt_trace_params tp;
     memset(&tp, 0, sizeof(tp));
@@ -1296,11 +1364,8 @@ rt_status rt_trace_rays(rt_scene* s, const rt_ray_batch* b, void* stream_v, int 
     if (g_opt.trace_tree == 0) { sd.nodes = sd.nodes_ref; sd.n_nodes = sd.n_nodes_ref; }
     const bool any = b->mode == RT_TRACE_ANY;
     resident_plan plan;
-    {
-        const rt_status st = plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), g_opt.trace_lds, (b->n + RT_TRACE_THREADS - 1) / RT_TRACE_THREADS,
-                                           [&](int m, size_t lds, int* per_cu) { return rt_trace_occupancy(s->spheres_only, m, any, record, lds, per_cu); }, plan);
-        if (st != RT_OK) return st;
-    }
+    RT_TRY(plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), g_opt.trace_lds, (b->n + RT_TRACE_THREADS - 1) / RT_TRACE_THREADS,
+                         [&](int m, size_t lds, int* per_cu) { return rt_trace_occupancy(s->spheres_only, m, any, record, lds, per_cu); }, plan));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     HIPCHK(rt_launch_trace(s->spheres_only, plan.lds_mode, sd, tp, plan.grid, plan.lds, stream));
     if (blocking) HIPCHK(hipStreamSynchronize(stream));
@@ -1316,15 +1381,12 @@ rt_status rt_radiance_rays(rt_scene* s, const rt_radiance_batch* b, void* stream
     if (!b->rgb_out) return invalid("rt_radiance_rays: null rgb_out");
     if (!s) return invalid("rt_radiance_rays: null scene");
     if (b->n == 0) return RT_OK;
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     const size_t n = (size_t)b->n, f = sizeof(float);
-    const struct { const void* p; size_t bytes; const char* what; unsigned align; } ptrs[] = {
+    const traced_ptr ptrs[] = {
         {b->origins, 3 * n * f, "origins", 4}, {b->directions, 3 * n * f, "directions", 4}, {b->times, n * f, "times", 4},
         {b->seeds, n * sizeof(uint64_t), "seeds", 8}, {b->rgb_out, 3 * n * f, "rgb_out", 4}, {b->rays_out, n * sizeof(uint32_t), "rays_out", 4}};
-    for (const auto& q : ptrs) {
-        const rt_status st = check_trace_ptr(q.p, q.bytes, s->device, q.what, "rt_radiance_rays", q.align);
-        if (st != RT_OK) return st;
-    }
+    RT_TRY(check_trace_ptrs(ptrs, s->device, "rt_radiance_rays"));
 
     rt_radiance_params rp;
     memset(&rp, 0, sizeof(rp));
@@ -1335,11 +1397,8 @@ rt_status rt_radiance_rays(rt_scene* s, const rt_radiance_batch* b, void* stream
 
     const rt_scene_dev& sd = s->dev;   // the walk array
     resident_plan plan;
-    {
-        const rt_status st = plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), g_opt.radiance_lds, (b->n + RT_RADIANCE_THREADS - 1) / RT_RADIANCE_THREADS,
-                                           [&](int m, size_t lds, int* per_cu) { return rt_radiance_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu); }, plan);
-        if (st != RT_OK) return st;
-    }
+    RT_TRY(plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), g_opt.radiance_lds, (b->n + RT_RADIANCE_THREADS - 1) / RT_RADIANCE_THREADS,
+                         [&](int m, size_t lds, int* per_cu) { return rt_radiance_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu); }, plan));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     HIPCHK(rt_launch_radiance(s->spheres_only, s->tex_level, plan.lds_mode, sd, rp, plan.grid, plan.lds, stream));
     if (blocking) HIPCHK(hipStreamSynchronize(stream));
@@ -1361,79 +1420,64 @@ static rt_status aov_impl(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc
     }
     if (!a->albedo && !a->normal && !a->depth && !a->alpha && !a->prim && !a->inst && !a->mat && !(t && (t->through || t->bounces)))
         return bad("every output is null");
-    if (f->nx <= 0 || f->ny <= 0 || f->ns <= 0) return bad("nx, ny and ns must be positive");
-    if ((long long)f->nx * f->ny >= (1ll << 31)) return bad("frame too large");
-    const int local_rows = rt_frame_local_rows(f);
-    if (local_rows < 0) return bad("bad row partition");
-    const int tiles_x = (f->nx + 7) / 8, tiles_y = (local_rows + 7) / 8;
-    if ((long long)tiles_x * tiles_y * 64 >= (1ll << 31)) return bad("frame too large");
+    frame_geometry g;
+    RT_TRY(check_frame(who_c, f, true, RENDER_FRAME_TEXTS, g));
     if (!s) return bad("null scene");
-    if (local_rows == 0) return RT_OK;
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    if (g.local_rows == 0) return RT_OK;
+    RT_TRY(use_device(s->device));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
 
     rt_aov_params ap;
     memset(&ap, 0, sizeof(ap));
     rt_aov_through_params tp;
     memset(&tp, 0, sizeof(tp));
-    const size_t pixels = (size_t)local_rows * f->nx;
-    struct out_buffer { void* user; size_t bytes; const char* what; void** dev; };
+    const size_t pixels = g.n_pixels;
+    struct out_buffer : traced_ptr { void** dev; };
     const out_buffer outs[] = {
-        {a->albedo, 3 * pixels * sizeof(float), "albedo", (void**)&ap.albedo}, {a->normal, 3 * pixels * sizeof(float), "normal", (void**)&ap.normal},
-        {a->depth, pixels * sizeof(float), "depth", (void**)&ap.depth}, {a->alpha, pixels * sizeof(float), "alpha", (void**)&ap.alpha},
-        {a->prim, pixels * sizeof(int32_t), "prim", (void**)&ap.prim}, {a->inst, pixels * sizeof(int32_t), "inst", (void**)&ap.inst},
-        {a->mat, pixels * sizeof(int32_t), "mat", (void**)&ap.mat},
-        {t ? t->through : nullptr, pixels * sizeof(float), "through", (void**)&tp.through},
-        {t ? t->bounces : nullptr, pixels * sizeof(int32_t), "bounces", (void**)&tp.bounces}};
+        {{a->albedo, 3 * pixels * sizeof(float), "albedo", 4}, (void**)&ap.albedo}, {{a->normal, 3 * pixels * sizeof(float), "normal", 4}, (void**)&ap.normal},
+        {{a->depth, pixels * sizeof(float), "depth", 4}, (void**)&ap.depth}, {{a->alpha, pixels * sizeof(float), "alpha", 4}, (void**)&ap.alpha},
+        {{a->prim, pixels * sizeof(int32_t), "prim", 4}, (void**)&ap.prim}, {{a->inst, pixels * sizeof(int32_t), "inst", 4}, (void**)&ap.inst},
+        {{a->mat, pixels * sizeof(int32_t), "mat", 4}, (void**)&ap.mat},
+        {{t ? t->through : nullptr, pixels * sizeof(float), "through", 4}, (void**)&tp.through},
+        {{t ? t->bounces : nullptr, pixels * sizeof(int32_t), "bounces", 4}, (void**)&tp.bounces}};
     // host buffers are staged in one allocation of this call's own (no per-frame resource of rt_render is used)
-    char* staging = nullptr;
+    call_memory mem;
+    mem.guard(stream);
     if (buffers_on_device) {
-        for (const auto& o : outs) {
-            const rt_status st = check_trace_ptr(o.user, o.bytes, s->device, o.what, who_c);
-            if (st != RT_OK) return st;
-            *o.dev = o.user;
-        }
+        RT_TRY(check_trace_ptrs(outs, s->device, who_c));
+        for (const auto& o : outs) *o.dev = const_cast<void*>(o.p);
     } else {
         size_t total = 0;
-        for (const auto& o : outs) if (o.user) total += (o.bytes + 255) & ~(size_t)255;
-        HIPCHK(hipMalloc((void**)&staging, total));
-        size_t at = 0;
-        for (const auto& o : outs) if (o.user) { *o.dev = staging + at; at += (o.bytes + 255) & ~(size_t)255; }
+        for (const auto& o : outs) if (o.p) total += call_memory::rounded(o.bytes);
+        char* staging = nullptr;
+        HIPCHK(mem.get((void**)&staging, total));
+        for (const auto& o : outs) if (o.p) *o.dev = call_memory::take(staging, o.bytes);
     }
     ap.seed_base = f->seed_base;
     ap.nx = f->nx; ap.ny = f->ny; ap.ns = f->ns;
     ap.use_gradient_bg = f->use_gradient_bg;
     for (int k = 0; k < 3; ++k) ap.background[k] = f->background[k];
     ap.tile_rows = f->tile_rows; ap.tile_first = f->tile_first; ap.tile_stride = f->tile_stride;
-    ap.local_rows = local_rows;
-    ap.tiles_x = tiles_x;
-    ap.work_items = (uint32_t)tiles_x * (uint32_t)tiles_y * 64u;
+    ap.local_rows = g.local_rows;
+    ap.tiles_x = g.tiles_x;
+    ap.work_items = g.work_items;
     if (t) { tp.max_bounces = t->max_bounces; tp.fuzz_limit = t->fuzz_limit; }
 
     const rt_scene_dev& sd = s->dev;   // the walk array
-    // (the staging block is released on every way out from here on)
-    auto run = [&]() -> rt_status {
-        resident_plan plan;
-        const rt_status st = plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), t ? g_opt.aov_through_lds : g_opt.aov_lds,
-                                           ((long long)ap.work_items + RT_AOV_THREADS - 1) / RT_AOV_THREADS,
-                                           [&](int m, size_t lds, int* per_cu) {
-                                               return t ? rt_aov_through_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu)
-                                                        : rt_aov_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu);
-                                           }, plan);
-        if (st != RT_OK) return st;
-        if (t) HIPCHK(rt_launch_aov_through(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, tp, plan.grid, plan.lds, stream));
-        else HIPCHK(rt_launch_aov(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, plan.grid, plan.lds, stream));
-        if (!buffers_on_device)
-            for (const auto& o : outs) if (o.user) HIPCHK(hipMemcpyAsync(o.user, *o.dev, o.bytes, hipMemcpyDeviceToHost, stream));
-        if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
-        return RT_OK;
-    };
-    const rt_status st = run();
-    if (staging) {
-        if (st != RT_OK) (void)hipStreamSynchronize(stream);   // nothing of this call may still write into the block
-        (void)hipFree(staging);
-    }
-    return st;
+    resident_plan plan;
+    RT_TRY(plan_resident(s, (size_t)sd.n_nodes * sizeof(rt_node), t ? g_opt.aov_through_lds : g_opt.aov_lds,
+                         ((long long)ap.work_items + RT_AOV_THREADS - 1) / RT_AOV_THREADS,
+                         [&](int m, size_t lds, int* per_cu) {
+                             return t ? rt_aov_through_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu)
+                                      : rt_aov_occupancy(s->spheres_only, s->tex_level, m, lds, per_cu);
+                         }, plan));
+    if (t) HIPCHK(rt_launch_aov_through(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, tp, plan.grid, plan.lds, stream));
+    else HIPCHK(rt_launch_aov(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, plan.grid, plan.lds, stream));
+    if (!buffers_on_device)
+        for (const auto& o : outs) if (o.p) HIPCHK(hipMemcpyAsync(const_cast<void*>(o.p), *o.dev, o.bytes, hipMemcpyDeviceToHost, stream));
+    if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
+    mem.settled();
+    return RT_OK;
 }
 
 rt_status rt_render_aov(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* a, int buffers_on_device, void* stream_v, int blocking) {
@@ -1482,17 +1526,17 @@ static rt_status denoise_impl(const rt_denoise_desc* d, const rt_denoise_varianc
     const size_t ws_bytes = rt_denoise_workspace_bytes(d->nx, d->ny);
     const bool own_workspace = !buffers_on_device || !d->workspace;
     if (d->workspace && d->workspace_bytes < ws_bytes) return bad("workspace smaller than rt_denoise_workspace_bytes");
-    struct buffer { const void* user; size_t bytes; const char* what; unsigned align; bool input; };
+    struct buffer : traced_ptr { bool input; };
     enum { COLOR = 0, ALBEDO, NORMAL, DEPTH, OUT, WORKSPACE, VARIANCE, VARIANCE_OUT, N_BUFS };
-    const buffer bufs[N_BUFS] = {{d->color, 3 * pixels * sizeof(float), "color", 4, true}, {d->albedo, 3 * pixels * sizeof(float), "albedo", 4, true},
-                                 {d->normal, 3 * pixels * sizeof(float), "normal", 4, true}, {d->depth, pixels * sizeof(float), "depth", 4, true},
-                                 {d->out, 3 * pixels * sizeof(float), "out", 4, false}, {own_workspace ? nullptr : d->workspace, ws_bytes, "workspace", 16, false},
-                                 {vd ? vd->variance : nullptr, pixels * sizeof(float), "variance", 4, true},
-                                 {vd ? vd->variance_out : nullptr, pixels * sizeof(float), "variance_out", 4, false}};
+    const buffer bufs[N_BUFS] = {{{d->color, 3 * pixels * sizeof(float), "color", 4}, true}, {{d->albedo, 3 * pixels * sizeof(float), "albedo", 4}, true},
+                                 {{d->normal, 3 * pixels * sizeof(float), "normal", 4}, true}, {{d->depth, pixels * sizeof(float), "depth", 4}, true},
+                                 {{d->out, 3 * pixels * sizeof(float), "out", 4}, false}, {{own_workspace ? nullptr : d->workspace, ws_bytes, "workspace", 16}, false},
+                                 {{vd ? vd->variance : nullptr, pixels * sizeof(float), "variance", 4}, true},
+                                 {{vd ? vd->variance_out : nullptr, pixels * sizeof(float), "variance_out", 4}, false}};
     {   // out may be exactly color; nothing else may share a byte with out, with variance_out or with the workspace
         auto overlap = [](const buffer& a, const buffer& b) {
-            const uintptr_t pa = (uintptr_t)a.user, pb = (uintptr_t)b.user;
-            return a.user && b.user && pa < pb + b.bytes && pb < pa + a.bytes;
+            const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
+            return a.p && b.p && pa < pb + b.bytes && pb < pa + a.bytes;
         };
         for (int k = 0; k < N_BUFS; ++k) {
             if (k != OUT && overlap(bufs[k], bufs[OUT]) && !(k == COLOR && d->out == d->color)) return bad("out overlaps another buffer (it may only be exactly color)");
@@ -1500,81 +1544,69 @@ static rt_status denoise_impl(const rt_denoise_desc* d, const rt_denoise_varianc
             if (k != VARIANCE_OUT && overlap(bufs[k], bufs[VARIANCE_OUT])) return bad("variance_out overlaps another buffer");
         }
     }
-    { const rt_status ud = use_device(g_device); if (ud != RT_OK) return ud; }
-    if (buffers_on_device)
-        for (const auto& b : bufs) {
-            const rt_status st = check_trace_ptr(b.user, b.bytes, g_device, b.what, who_c, b.align);
-            if (st != RT_OK) return st;
-        }
+    RT_TRY(use_device(g_device));
+    if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, g_device, who_c));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
 
     const bool normal_on = d->normal && d->normal_sharpness > 0, depth_on = d->depth && d->sigma_depth > 0.f, color_on = d->sigma_color > 0.f;
     const bool guide = normal_on || depth_on;
     // one allocation of this call's own: the workspace when the caller gives none and, for host buffers, their device images
     const void* dev[N_BUFS];
-    for (int k = 0; k < N_BUFS; ++k) dev[k] = bufs[k].user;
-    char* block = nullptr;
+    for (int k = 0; k < N_BUFS; ++k) dev[k] = bufs[k].p;
+    call_memory mem;
+    mem.guard(stream);
     char* ws = static_cast<char*>(d->workspace);
-    auto round = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    auto staged_image = [&](int k) { return k != WORKSPACE && bufs[k].user && !(k == OUT && d->out == d->color); };
+    auto staged_image = [&](int k) { return k != WORKSPACE && bufs[k].p && !(k == OUT && d->out == d->color); };
     if (own_workspace) {
         size_t total = ws_bytes;
-        if (!buffers_on_device) for (int k = 0; k < N_BUFS; ++k) if (staged_image(k)) total += round(bufs[k].bytes);
-        HIPCHK(hipMalloc((void**)&block, total));
-        ws = block;
+        if (!buffers_on_device) for (int k = 0; k < N_BUFS; ++k) if (staged_image(k)) total += call_memory::rounded(bufs[k].bytes);
+        HIPCHK(mem.get((void**)&ws, total));
         if (!buffers_on_device) {
-            size_t at = ws_bytes;
-            for (int k = 0; k < N_BUFS; ++k) if (staged_image(k)) { dev[k] = block + at; at += round(bufs[k].bytes); }
+            char* at = ws + ws_bytes;
+            for (int k = 0; k < N_BUFS; ++k) if (staged_image(k)) dev[k] = call_memory::take(at, bufs[k].bytes);
             if (d->out == d->color) dev[OUT] = dev[COLOR];
         }
     }
-    auto run = [&]() -> rt_status {
-        if (!buffers_on_device)
-            for (int k = 0; k < N_BUFS; ++k) if (bufs[k].input && bufs[k].user) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].user, bufs[k].bytes, hipMemcpyHostToDevice, stream));
-        const size_t image = ws_bytes / 3;
-        float4* x[2] = {reinterpret_cast<float4*>(ws), reinterpret_cast<float4*>(ws + image)};
-        rt_denoise_params dp;
-        memset(&dp, 0, sizeof(dp));
-        dp.color = static_cast<const float*>(dev[COLOR]); dp.albedo = d->demodulate ? static_cast<const float*>(dev[ALBEDO]) : nullptr;
-        dp.normal = normal_on ? static_cast<const float*>(dev[NORMAL]) : nullptr; dp.depth = depth_on ? static_cast<const float*>(dev[DEPTH]) : nullptr;
-        dp.out = static_cast<float*>(const_cast<void*>(dev[OUT]));
-        dp.guide = reinterpret_cast<float4*>(ws + 2 * image);
-        dp.nx = d->nx; dp.ny = d->ny;
-        dp.tiles_x = (d->nx + RT_DENOISE_TILE - 1) / RT_DENOISE_TILE;
-        dp.normal_sharpness = d->normal_sharpness; dp.demodulate = d->demodulate ? 1 : 0;
-        dp.color_floor = d->color_floor; dp.sigma_depth = d->sigma_depth;
-        dp.x_out = x[0];
-        rt_denoise_variance_params dv;
-        memset(&dv, 0, sizeof(dv));
-        if (vd) {
-            dv.variance = static_cast<const float*>(dev[VARIANCE]); dv.variance_out = static_cast<float*>(const_cast<void*>(dev[VARIANCE_OUT]));
-            dv.sigma_variance = vd->sigma_variance; dv.variance_floor = vd->variance_floor;
-            HIPCHK(rt_launch_denoise_pack_variance(dp, dv, guide, stream));
-        } else {
-            HIPCHK(rt_launch_denoise_pack(dp, guide, stream));
-        }
-        // staged or direct, per iteration: staging fetches (16 + 4 s)^2 / 256 records per pixel and array instead
-        // of 25 -- 1.6, 2.3, 4 for s = 1, 2, 4 -- and at s = 8 (9 per pixel, 84 KiB: one workgroup per CU) no longer pays
-        const int max_staged = g_opt.denoise_lds < 0 ? 4 : (g_opt.denoise_lds == 0 ? 0 : RT_DENOISE_MAX_STAGED_STEP);
-        for (int k = 0; k < d->iterations; ++k) {
-            dp.step = 1 << k;
-            dp.sigma_color_k = d->sigma_color * (1.0f / (float)(1 << k));
-            dp.x_in = x[k & 1]; dp.x_out = x[(k + 1) & 1];
-            dp.last = k == d->iterations - 1;
-            if (vd) HIPCHK(rt_launch_denoise_variance(normal_on, depth_on, dp.step <= max_staged, dp, dv, stream));
-            else HIPCHK(rt_launch_denoise(normal_on, depth_on, color_on, dp.step <= max_staged, dp, stream));
-        }
-        if (!buffers_on_device)
-            for (int k : {(int)OUT, (int)VARIANCE_OUT}) if (bufs[k].user) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].user), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
-        if (blocking || own_workspace) HIPCHK(hipStreamSynchronize(stream));
-        return RT_OK;
-    };
-    const rt_status st = run();
-    if (block) {
-        if (st != RT_OK) (void)hipStreamSynchronize(stream);   // nothing of this call may still use the block
-        (void)hipFree(block);
+    if (!buffers_on_device)
+        for (int k = 0; k < N_BUFS; ++k) if (bufs[k].input && bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, stream));
+    const size_t image = ws_bytes / 3;
+    float4* x[2] = {reinterpret_cast<float4*>(ws), reinterpret_cast<float4*>(ws + image)};
+    rt_denoise_params dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.color = static_cast<const float*>(dev[COLOR]); dp.albedo = d->demodulate ? static_cast<const float*>(dev[ALBEDO]) : nullptr;
+    dp.normal = normal_on ? static_cast<const float*>(dev[NORMAL]) : nullptr; dp.depth = depth_on ? static_cast<const float*>(dev[DEPTH]) : nullptr;
+    dp.out = static_cast<float*>(const_cast<void*>(dev[OUT]));
+    dp.guide = reinterpret_cast<float4*>(ws + 2 * image);
+    dp.nx = d->nx; dp.ny = d->ny;
+    dp.tiles_x = (d->nx + RT_DENOISE_TILE - 1) / RT_DENOISE_TILE;
+    dp.normal_sharpness = d->normal_sharpness; dp.demodulate = d->demodulate ? 1 : 0;
+    dp.color_floor = d->color_floor; dp.sigma_depth = d->sigma_depth;
+    dp.x_out = x[0];
+    rt_denoise_variance_params dv;
+    memset(&dv, 0, sizeof(dv));
+    if (vd) {
+        dv.variance = static_cast<const float*>(dev[VARIANCE]); dv.variance_out = static_cast<float*>(const_cast<void*>(dev[VARIANCE_OUT]));
+        dv.sigma_variance = vd->sigma_variance; dv.variance_floor = vd->variance_floor;
+        HIPCHK(rt_launch_denoise_pack_variance(dp, dv, guide, stream));
+    } else {
+        HIPCHK(rt_launch_denoise_pack(dp, guide, stream));
     }
-    return st;
+    // staged or direct, per iteration: staging fetches (16 + 4 s)^2 / 256 records per pixel and array instead
+    // of 25 -- 1.6, 2.3, 4 for s = 1, 2, 4 -- and at s = 8 (9 per pixel, 84 KiB: one workgroup per CU) no longer pays
+    const int max_staged = g_opt.denoise_lds < 0 ? 4 : (g_opt.denoise_lds == 0 ? 0 : RT_DENOISE_MAX_STAGED_STEP);
+    for (int k = 0; k < d->iterations; ++k) {
+        dp.step = 1 << k;
+        dp.sigma_color_k = d->sigma_color * (1.0f / (float)(1 << k));
+        dp.x_in = x[k & 1]; dp.x_out = x[(k + 1) & 1];
+        dp.last = k == d->iterations - 1;
+        if (vd) HIPCHK(rt_launch_denoise_variance(normal_on, depth_on, dp.step <= max_staged, dp, dv, stream));
+        else HIPCHK(rt_launch_denoise(normal_on, depth_on, color_on, dp.step <= max_staged, dp, stream));
+    }
+    if (!buffers_on_device)
+        for (int k : {(int)OUT, (int)VARIANCE_OUT}) if (bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
+    if (blocking || own_workspace) HIPCHK(hipStreamSynchronize(stream));
+    mem.settled();
+    return RT_OK;
 }
 
 rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stream_v, int blocking) {
@@ -1590,7 +1622,7 @@ rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_varianc
 // the frame's parts, [1] the samples those pixels still had to go.
 rt_status rt_debug_handoff(rt_scene* s, unsigned long long* out2) {
     if (!s || !out2) return invalid("null argument");
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     HIPCHK(hipMemcpy(out2, s->d_ray_counter + 28, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -1598,7 +1630,7 @@ rt_status rt_debug_handoff(rt_scene* s, unsigned long long* out2) {
 // Diagnostic builds (-DRT_DIAG) leave per-stage execution counts behind the ray counter; 16 values.
 rt_status rt_debug_counters(rt_scene* s, unsigned long long* out16) {
     if (!s || !out16) return invalid("null argument");
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     HIPCHK(hipMemcpy(out16, s->d_ray_counter + 1, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -1607,7 +1639,7 @@ rt_status rt_debug_counters(rt_scene* s, unsigned long long* out16) {
 // tier workgroup: [8] resolve + shade in the tier loops, [9] the whole tier loop; shader-clock cycles).
 rt_status rt_debug_stage_cycles(rt_scene* s, unsigned long long* out10) {
     if (!s || !out10) return invalid("null argument");
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     HIPCHK(hipMemcpy(out10, s->d_ray_counter + 17, 10 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -1615,7 +1647,7 @@ rt_status rt_debug_stage_cycles(rt_scene* s, unsigned long long* out10) {
 // wave's start (ordinary waves, then waves that started in sparse / tier mode).
 rt_status rt_debug_wave_ends(rt_scene* s, unsigned long long* out, int n) {
     if (!s || !out || n < 0 || n > 2 * RT_DIAG_BINS) return invalid("bad argument");
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     HIPCHK(hipMemcpy(out, s->d_ray_counter + RT_DIAG_HIST_SLOT, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -1623,7 +1655,7 @@ rt_status rt_debug_wave_ends(rt_scene* s, unsigned long long* out, int n) {
 // pixel), (source queue << 60 | started sparse << 59 | local pixel id)
 rt_status rt_debug_wave_last(rt_scene* s, unsigned long long* out, int n_waves) {
     if (!s || !out || n_waves < 0 || n_waves > RT_DIAG_MAX_WAVES) return invalid("bad argument");
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     HIPCHK(hipMemcpy(out, s->d_ray_counter + RT_DIAG_WAVE_SLOT, (size_t)2 * n_waves * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -1633,12 +1665,6 @@ rt_status rt_debug_wave_last(rt_scene* s, unsigned long long* out, int n_waves) 
 namespace {
 enum { RANK_PARAM_WORDS = 20, RANK_INFO_WORDS = 13 };
 static_assert(sizeof(rt_rank_info) == RANK_INFO_WORDS * 4, "rt_debug_rank / rt_debug_rank_info copy rt_rank_info as 13 words");
-// device allocations of one seam call, freed when it returns
-struct seam_buffers {
-    std::vector<void*> all;
-    ~seam_buffers() { for (void* p : all) (void)hipFree(p); }
-    hipError_t get(void** p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) all.push_back(*p); return e; }
-};
 }  // namespace
 
 rt_status rt_debug_rank(const uint32_t* cost, const uint32_t* tile_cost, uint64_t rays, const uint32_t* params, uint32_t* tile_order,
@@ -1670,8 +1696,8 @@ rt_status rt_debug_rank(const uint32_t* cost, const uint32_t* tile_cost, uint64_
         top = fac > top ? fac : top;
     }
     if (!((double)rays / (double)rp.n_pixels * (double)top + 1.0 < 4294967296.0)) return invalid("rt_debug_rank: rays / n_pixels x the largest factor must stay below 2^32");
-    { const rt_status ud = use_device(g_device); if (ud != RT_OK) return ud; }
-    seam_buffers mem;
+    RT_TRY(use_device(g_device));
+    call_memory mem;
     unsigned int *d_tile_cost = nullptr, *d_tile_order = nullptr;
     unsigned long long* d_rays = nullptr;
     HIPCHK(mem.get((void**)&rp.state, (size_t)rp.n_pixels * sizeof(rt_pixel_state)));
@@ -1706,20 +1732,19 @@ rt_status rt_debug_prior(const uint32_t* cal_cost, int32_t cal_nx, int32_t cal_n
                          int32_t tile_stride, uint32_t* cost_out, uint32_t* tile_cost_out, uint64_t* total_out) {
     if (!cal_cost || !cost_out || !tile_cost_out || !total_out) return invalid("rt_debug_prior: null argument");
     if (cal_nx < 1 || cal_ny < 1 || (long long)cal_nx * cal_ny >= (1ll << 31)) return invalid("rt_debug_prior: bad calibration grid size");
-    if (nx < 1 || ny < 1 || (long long)nx * ny >= (1ll << 31)) return invalid("rt_debug_prior: bad frame size");
     rt_frame_desc f;
     memset(&f, 0, sizeof(f));
     f.nx = nx; f.ny = ny; f.tile_rows = tile_rows; f.tile_first = tile_first; f.tile_stride = tile_stride;
-    const int local_rows = rt_frame_local_rows(&f);
-    if (local_rows < 0) return invalid("rt_debug_prior: bad row partition");
-    if (local_rows == 0) return invalid("rt_debug_prior: the partition has no rows");
-    { const rt_status ud = use_device(g_device); if (ud != RT_OK) return ud; }
+    frame_geometry g;
+    RT_TRY(check_frame("rt_debug_prior", &f, false, STATE_FRAME_TEXTS, g));
+    if (g.local_rows == 0) return invalid("rt_debug_prior: the partition has no rows");
+    RT_TRY(use_device(g_device));
     rt_prior_params pp;
     memset(&pp, 0, sizeof(pp));
-    pp.cal_nx = cal_nx; pp.cal_ny = cal_ny; pp.nx = nx; pp.ny = ny; pp.local_rows = local_rows; pp.tiles_x = tiles_across(nx);
+    pp.cal_nx = cal_nx; pp.cal_ny = cal_ny; pp.nx = nx; pp.ny = ny; pp.local_rows = g.local_rows; pp.tiles_x = g.tiles_x;
     pp.tile_rows = tile_rows; pp.tile_first = tile_first; pp.tile_stride = tile_stride;
-    const size_t n_pixels = (size_t)local_rows * (size_t)nx, n_tiles = (size_t)pp.tiles_x * (size_t)tiles_across(local_rows), n_cal = (size_t)cal_nx * (size_t)cal_ny;
-    seam_buffers mem;
+    const size_t n_pixels = g.n_pixels, n_tiles = (size_t)g.tiles_x * (size_t)g.tiles_y, n_cal = (size_t)cal_nx * (size_t)cal_ny;
+    call_memory mem;
     unsigned int* d_cal = nullptr;
     HIPCHK(mem.get((void**)&pp.state, n_pixels * sizeof(rt_pixel_state)));
     HIPCHK(mem.get((void**)&pp.tile_cost, n_tiles * sizeof(unsigned int)));
@@ -1749,7 +1774,7 @@ rt_status rt_debug_cal_cost(rt_scene* s, uint32_t* out, int32_t cap, int32_t* nx
     if (!s->d_cal_cost || s->cal_nx <= 0 || s->cal_ny <= 0) return invalid("rt_debug_cal_cost: the scene kept no calibration costs");
     *nx = s->cal_nx; *ny = s->cal_ny;
     if ((long long)cap < (long long)s->cal_nx * s->cal_ny) return invalid("rt_debug_cal_cost: cap is smaller than the calibration grid (nx and ny are set)");
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     HIPCHK(hipMemcpy(out, s->d_cal_cost, (size_t)s->cal_nx * s->cal_ny * sizeof(unsigned int), hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -1758,7 +1783,7 @@ rt_status rt_debug_rank_info(rt_scene* s, uint32_t* out13) {
     if (!s) return invalid("rt_debug_rank_info: null scene");
     if (!out13) return invalid("rt_debug_rank_info: null argument");
     if (!s->ranked_frame || !s->d_rank) return invalid("rt_debug_rank_info: the scene's last frame was not ranked");
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     if (s->frame_pending) HIPCHK(hipStreamSynchronize(s->pending_stream));
     HIPCHK(hipMemcpy(out13, s->d_rank, sizeof(rt_rank_info), hipMemcpyDeviceToHost));
     return RT_OK;
@@ -1768,7 +1793,7 @@ namespace {
 // The main kernel's launch shape for a launch over `n_pixels` pixels (`fp.work_items` work items): LDS residency mode, workgroup
 // shape, grid and stage quorums (written to fp).  Shared by rt_render / rt_render_window and rt_render_adaptive's passes.
 struct main_launch {
-    int lds_mode;
+    int kernel, lds_mode;
     size_t lds_bytes;
     dim3 grid, block;
     int per_cu_resident;   // workgroups of this launch that can be resident on one CU (persistent kernels)
@@ -1833,8 +1858,132 @@ rt_status plan_main_launch(const rt_scene* s, int kernel, size_t n_pixels, rt_fr
         fp.shade_threshold = g_opt.shade_threshold > 0 ? g_opt.shade_threshold : (latency_regime ? 16 : 32);
         fp.newpath_threshold = g_opt.newpath_threshold > 0 ? g_opt.newpath_threshold : (s->spheres_only ? (latency_regime ? 12 : 24) : 8);
     }
-    ml.lds_mode = lds_mode; ml.lds_bytes = lds_bytes; ml.grid = grid; ml.block = block; ml.per_cu_resident = per_cu_resident;
+    ml.kernel = kernel; ml.lds_mode = lds_mode; ml.lds_bytes = lds_bytes; ml.grid = grid; ml.block = block; ml.per_cu_resident = per_cu_resident;
     ml.lean_family = lean_family;
+    return RT_OK;
+}
+
+// kernel_variant and the launch shape as rt_stats reports them
+void stats_of_launch(const rt_scene* s, const main_launch& ml, rt_stats& out) {
+    out.kernel_variant = ml.kernel * 1000 + ml.lds_mode * 100 + s->tex_level * 10 + (s->spheres_only ? 1 : 0);
+    out.workgroups = (int)ml.grid.x; out.threads_per_group = (int)ml.block.x; out.lds_bytes = (int)ml.lds_bytes;
+}
+
+// The frame parameters every entry of the main kernel sets alike, for a frame of `ns` samples per pixel: the scene's counters, the
+// frame description, the call's geometry and the scheduling knobs.  The caller adds fb, state_in / state_out, the sample window
+// and store_parked; plan_main_launch adds the stage quorums.
+void fill_frame_params(const rt_scene* s, const rt_frame_desc* f, const frame_geometry& g, int ns, rt_frame_params& fp) {
+    memset(&fp, 0, sizeof(fp));
+    fp.ray_counter = s->d_ray_counter;
+    fp.work_counter = s->d_work_counter;
+    fp.seed_base = f->seed_base;
+    fp.nx = f->nx; fp.ny = f->ny; fp.ns = ns; fp.gamma = f->gamma;
+    fp.background[0] = f->background[0]; fp.background[1] = f->background[1]; fp.background[2] = f->background[2];
+    fp.use_gradient_bg = f->use_gradient_bg;
+    fp.tile_rows = f->tile_rows; fp.tile_first = f->tile_first; fp.tile_stride = f->tile_stride;
+    fp.local_rows = g.local_rows;
+    fp.tiles_x = g.tiles_x;
+    fp.work_items = g.work_items;
+    fp.sparse_priority = g_opt.sparse_priority; fp.sparse_eager = g_opt.sparse_eager; fp.semi_priority = g_opt.semi_priority; fp.tier_priority = g_opt.tier_priority;
+    fp.steps_per_trip = g_opt.steps_per_trip;
+    fp.leaf_threshold = g_opt.leaf_threshold;
+    fp.diel_threshold = g_opt.diel_threshold;
+    fp.box_threshold = g_opt.box_threshold; fp.medium_threshold = g_opt.medium_threshold;
+}
+
+// Room for the tier kernel (rt_kernel_tier.h) in `budget` bytes of LDS per workgroup: whether its image fits -- the scene has
+// tier data, and the leaf arrays, which the image always holds, fit --, whether spheres, materials and textures fit too
+// (rt_frame_params::tier_lds_scene), the image's size, and the grid of a tail launch.
+// The tail launch has the machine to itself: as many tier workgroups per CU as registers (launch bounds: 4 resp. 3 waves per SIMD,
+// a workgroup is one wave per SIMD) and LDS hold
+struct tier_room {
+    bool fits;
+    int lds_scene;
+    size_t lds;
+    unsigned tail_grid;
+};
+tier_room plan_tier_room(const rt_scene* s, size_t budget) {
+    tier_room r = {false, 0, 0, 0};
+    const int ns_ = s->dev.n_slots, nsph = s->dev.n_spheres, nm = s->dev.n_materials, nt = s->dev.n_textures;
+    if (s->dev.leaf_lo == nullptr || rt_tier_lds_bytes(ns_, nsph, nm, nt, false) > budget) return r;
+    r.fits = true;
+    r.lds_scene = rt_tier_lds_bytes(ns_, nsph, nm, nt, true) <= budget ? 1 : 0;
+    r.lds = rt_tier_lds_bytes(ns_, nsph, nm, nt, r.lds_scene != 0);
+    const bool lean_family = s->spheres_only && s->tex_level < 2;
+    const unsigned by_lds = (unsigned)(g_devices[s->device].lds_per_cu / (r.lds + 512));
+    const unsigned by_regs = lean_family ? 4u : 3u;
+    r.tail_grid = (unsigned)g_devices[s->device].num_cu * (by_lds < by_regs ? by_lds : by_regs);
+    if (r.tail_grid < 1u) r.tail_grid = 1u;
+    return r;
+}
+// the tier kernel of the scene's family
+hipError_t launch_tier(const rt_scene* s, const rt_frame_params& fp, dim3 grid, size_t lds, hipStream_t stream) {
+    return s->spheres_only ? rt_launch_tier_spheres(s->tex_level, s->dev, fp, grid, lds, stream)
+                           : rt_launch_tier_general(s->tex_level, s->need_uv, s->dev, fp, grid, lds, stream);
+}
+
+struct tier_sizes { int tier1_pixels, tier1_factor, tier1_depth, heavy_factor, sparse_factor, sparse_percent, work_percent; };
+tier_sizes effective_tier_sizes(double per_lane, bool lean_family, const rt_options& o) {
+    // Effective tier sizes by the share of the frame this call renders (1/N in an N-GPU run): the fewer pixels a
+    // rank has per lane, the more of them can afford a wave of their own.  Measured on rank-local renders of the
+    // headline frame (tools/partition_time.py).
+    int e_tier1_pixels = o.tier1_pixels, e_tier1_factor = o.tier1_factor_x10, e_tier1_depth = o.tier1_depth,
+        e_heavy_factor = o.heavy_factor_x10, e_sparse_factor = o.sparse_factor_x10, e_sparse_percent = o.sparse_wg_percent,
+        e_work_percent = o.sparse_work_percent;
+    if (o.tier_auto) {
+        // keyed by pixels per resident lane (the 1200x800 frame: 3.7 whole, 1.8 / 0.9 / 0.5 for a half, a quarter,
+        // an eighth; a quarter of 1920x1080 is 2.0): what matters is how empty the machine is, not the fraction
+        if (per_lane > 2.75) {
+            // whole frames.  Lean family: the defaults.  The others: a tier wave is a main workgroup's slot taken away and
+            // their dear pixels are many and alike (Book-2 final: the fog ball), so only the very dearest get one
+            // (Book-2 final 800x800 @ 200: 352 ms with the lean sizes, 342 ms with these, profiles/r03_general_defaults.log)
+            if (!lean_family) { e_tier1_factor = 70; e_tier1_pixels = 256; e_tier1_depth = 1; }
+        }
+        // shares, lean family: re-fitted in round 3 with the tier kernel beside the main kernel (tools/share_sweep.py on rank 0
+        // of the 1200x800 and 1920x1080 frames, profiles/r03_share_sweep_pass*.log; slowest-rank tables in DESIGN.md section 6)
+        // -- and again with the tail hand-off, which takes over what the largest tiers were there for (rank 0 of 8: 48.1 ms with
+        // round 3's first fit 16384 / 1.5x, 40.6 ms with the quarter's sizes; rank 0 of 2: 66.2 -> 62.6 ms, profiles/r03_handoff_shares.log)
+        else if (lean_family) {
+            if (per_lane > 1.375) { e_tier1_pixels = 1536; e_tier1_factor = 40; e_tier1_depth = 3; e_heavy_factor = 20; e_sparse_factor = 40; e_sparse_percent = 80; e_work_percent = 5; }
+            else { e_tier1_pixels = 8192; e_tier1_factor = 20; e_tier1_depth = 4; e_heavy_factor = 15; e_sparse_factor = 20; e_sparse_percent = 80; e_work_percent = 40; }
+        }
+        // shares, other families: round 2's sizes (Book-2 final's 1/8 share: 216 ms with these, 236 with the lean family's,
+        // 252 without a tier kernel, profiles/r03_share_sweep_final_eighth.log)
+        else if (per_lane > 1.375) { e_tier1_pixels = 4096; e_tier1_factor = 30; e_tier1_depth = 4; e_heavy_factor = 20; e_sparse_factor = 30; e_sparse_percent = 80; }
+        else if (per_lane > 0.6875) { e_tier1_pixels = 4096; e_tier1_factor = 30; e_tier1_depth = 4; e_heavy_factor = 20; e_sparse_factor = 30; e_sparse_percent = 80; e_work_percent = 20; }
+        else { e_tier1_pixels = 8192; e_tier1_factor = 20; e_tier1_depth = 4; e_heavy_factor = 15; e_sparse_factor = 15; e_sparse_percent = 80; e_work_percent = 40; }
+    }
+    if (e_sparse_factor < e_heavy_factor) e_sparse_factor = e_heavy_factor;
+    return {e_tier1_pixels, e_tier1_factor, e_tier1_depth, e_heavy_factor, e_sparse_factor, e_sparse_percent, e_work_percent};
+}
+
+// The buffers of a ranked frame (rt_scene), cached and grown together: tile costs and order, the parked pixels, the heavy list
+// unsorted and sorted, the tier sizes.
+enum { RT_HEAVY_CAP = 262144 };
+rt_status grow_ranked_buffers(rt_scene* s, size_t n_tiles, size_t n_pixels) {
+    if (s->tile_capacity >= n_tiles && s->pixel_capacity >= n_pixels && s->d_rank) return RT_OK;
+    s->tile_capacity = s->pixel_capacity = 0;
+    RT_TRY(reallocate({{(void**)&s->d_tile_cost, n_tiles * sizeof(unsigned int)}, {(void**)&s->d_tile_order, n_tiles * sizeof(unsigned int)},
+                       {(void**)&s->d_state, n_pixels * sizeof(rt_pixel_state)}, {(void**)&s->d_heavy_list, (size_t)RT_HEAVY_CAP * sizeof(unsigned long long)},
+                       {(void**)&s->d_heavy_pixels, (size_t)RT_HEAVY_CAP * sizeof(unsigned int)}, {(void**)&s->d_rank, sizeof(rt_rank_info)}}));
+    s->tile_capacity = n_tiles; s->pixel_capacity = n_pixels;
+    return RT_OK;
+}
+
+// The end of a synchronous frame (rt_render_adaptive, rt_render_variance), after its last enqueue: the wait, the time between
+// ev_start and ev_stop, the ray counter, and the statistics, which stay in the scene as rt_render's do.  `passes` is what
+// rt_stats::reserved reports for these entries.
+rt_status finish_sync_frame(rt_scene* s, hipStream_t stream, int passes, rt_stats& out, rt_stats* stats) {
+    HIPCHK(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
+    unsigned long long rays = 0;
+    HIPCHK(hipMemcpy(&rays, s->d_ray_counter, sizeof(rays), hipMemcpyDeviceToHost));
+    out.ms_render = (double)ms;
+    out.rays = rays;
+    out.reserved = passes;
+    s->pending_stats = out;
+    if (stats) *stats = out;
     return RT_OK;
 }
 
@@ -1850,12 +1999,11 @@ rt_status rt_render(rt_scene* s, const rt_frame_desc* f, float* fb, int fb_on_de
 rt_status rt_progressive_state_create(rt_scene* s, const rt_frame_desc* f, void** state) {
     if (!s || !f || !state) return invalid("null argument");
     *state = nullptr;
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
-    if (f->nx <= 0 || f->ny <= 0 || (long long)f->nx * f->ny >= (1ll << 31)) return invalid("bad frame size");
-    const int local_rows = rt_frame_local_rows(f);
-    if (local_rows < 0) return invalid("bad row partition");
+    RT_TRY(use_device(s->device));
+    frame_geometry g;
+    RT_TRY(check_frame(nullptr, f, false, STATE_FRAME_TEXTS, g));
     rt_progressive* p = new rt_progressive;
-    p->scene = s; p->frame = *f; p->pixels = (size_t)local_rows * (size_t)f->nx; p->next_sample = 0;
+    p->scene = s; p->frame = *f; p->pixels = g.n_pixels; p->next_sample = 0;
     const hipError_t e = hipMalloc((void**)&p->d_state, (p->pixels ? p->pixels : 1) * sizeof(rt_pixel_state));
     if (e != hipSuccess) { delete p; g_last_hip_error = (int)e; g_detail = "allocating the progressive state failed"; return RT_ERR_HIP; }
     *state = p;
@@ -1888,79 +2036,54 @@ rt_status rt_render_window(rt_scene* s, const rt_frame_desc* f, float* fb, int f
 static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int fb_on_device, void* stream_v, int blocking, rt_stats* stats,
                              rt_progressive* win, int32_t win_begin, int32_t win_end) {
     if (!s || !f || !fb) return invalid("null argument");
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
+    RT_TRY(use_device(s->device));
     const int g_num_cu = g_devices[s->device].num_cu;
     const size_t g_lds_per_cu = g_devices[s->device].lds_per_cu;
-    const int frame_ns = win ? win_end : f->ns;       // a progressive window averages over the samples rendered so far
-    if (f->nx <= 0 || f->ny <= 0 || frame_ns <= 0) return invalid("nx, ny and ns must be positive");
-    if ((long long)f->nx * f->ny >= (1ll << 31)) return invalid("frame too large");
-    const int local_rows = rt_frame_local_rows(f);
-    if (local_rows < 0) return invalid("bad row partition");
-    if (s->frame_pending) { rt_status st = rt_frame_finish(s, nullptr); if (st != RT_OK) return st; }
+    // ---- check.  A progressive window averages over the samples rendered so far: win_end, which rt_render_window has checked,
+    // stands for f->ns
+    frame_geometry g;
+    RT_TRY(check_frame(nullptr, f, !win, RENDER_FRAME_TEXTS, g));
+    const int frame_ns = win ? win_end : f->ns;
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
 
     rt_stats out;
     memset(&out, 0, sizeof(out));
-    out.local_rows = local_rows;
-    out.samples = (uint64_t)local_rows * f->nx * (uint64_t)(win ? win_end - win_begin : f->ns);
-    if (local_rows == 0) { s->pending_stats = out; if (stats) *stats = out; return RT_OK; }
+    out.local_rows = g.local_rows;
+    out.samples = (uint64_t)g.local_rows * f->nx * (uint64_t)(win ? win_end - win_begin : f->ns);
+    if (g.local_rows == 0) { s->pending_stats = out; if (stats) *stats = out; return RT_OK; }
 
+    // ---- fill
     rt_frame_params fp;
-    memset(&fp, 0, sizeof(fp));
-    const size_t floats = (size_t)local_rows * f->nx * 3;
-    if (fb_on_device) fp.fb = fb;
-    else {
-        if (s->d_fb_floats < floats) {
-            if (s->d_fb) (void)hipFree(s->d_fb);
-            s->d_fb = nullptr; s->d_fb_floats = 0;
-            HIPCHK(hipMalloc((void**)&s->d_fb, floats * sizeof(float)));
-            s->d_fb_floats = floats;
-        }
-        fp.fb = s->d_fb;
-    }
-    fp.ray_counter = s->d_ray_counter;
-    fp.work_counter = s->d_work_counter;
-    fp.seed_base = f->seed_base;
-    fp.nx = f->nx; fp.ny = f->ny; fp.ns = frame_ns; fp.gamma = f->gamma;
-    fp.background[0] = f->background[0]; fp.background[1] = f->background[1]; fp.background[2] = f->background[2];
-    fp.use_gradient_bg = f->use_gradient_bg;
-    fp.tile_rows = f->tile_rows; fp.tile_first = f->tile_first; fp.tile_stride = f->tile_stride;
-    fp.local_rows = local_rows;
-    fp.tiles_x = tiles_across(f->nx);
-    const int tiles_y = tiles_across(local_rows);
-    if ((long long)fp.tiles_x * tiles_y * 64 >= (1ll << 31)) return invalid("frame too large");
-    fp.work_items = (uint32_t)fp.tiles_x * (uint32_t)tiles_y * 64u;
-    fp.sparse_priority = g_opt.sparse_priority; fp.sparse_eager = g_opt.sparse_eager; fp.semi_priority = g_opt.semi_priority; fp.tier_priority = g_opt.tier_priority;
-    fp.steps_per_trip = g_opt.steps_per_trip;
-    fp.leaf_threshold = g_opt.leaf_threshold;
-    fp.diel_threshold = g_opt.diel_threshold;
-    fp.box_threshold = g_opt.box_threshold; fp.medium_threshold = g_opt.medium_threshold;
+    fill_frame_params(s, f, g, frame_ns, fp);
+    const size_t floats = g.n_pixels * 3;
+    RT_TRY(device_fb(s, fb, fb_on_device, floats, &fp.fb));
+    fp.sample_begin = 0; fp.sample_end = frame_ns;
 
+    // ---- plan
     const int kernel = win ? RT_KERNEL_STAGED : g_opt.kernel;   // (kernel 0 renders whole pixels only)
     main_launch ml;
-    { const rt_status pl = plan_main_launch(s, kernel, (size_t)local_rows * (size_t)f->nx, fp, ml); if (pl != RT_OK) return pl; }
+    RT_TRY(plan_main_launch(s, kernel, g.n_pixels, fp, ml));
+    stats_of_launch(s, ml, out);
     const int lds_mode = ml.lds_mode;
-    const size_t lds_bytes = ml.lds_bytes;
     const bool lean_family = ml.lean_family;
-    dim3 grid = ml.grid, block = ml.block;
+    dim3 grid = ml.grid;
+    const dim3 block = ml.block;
     const int per_cu_resident = ml.per_cu_resident;
-    // ---- the tier kernel of ranked launches (rt_kernel_tier.h): its LDS image and where its workgroups find room.
+
+    // ---- tier room.  The tier kernel of ranked launches (rt_kernel_tier.h): its LDS image and where its workgroups find room.
     // Lean family: the main kernel's 4 x 104 registers per SIMD leave 96 free, so ONE tier workgroup (four waves, one per
     // SIMD, 76 VGPRs) is resident on a CU beside a full main grid if the LDS left over holds its image.  Other families:
     // no register room beside a full main grid; the ranking makes main workgroups leave (main_skip_wgs) and a tier workgroup
     // has what one of them had.  The image always holds the leaf arrays; spheres, materials and textures too where all of them fit.
     bool tier_possible = false;
-    size_t tier_lds = 0;
     unsigned tier_grid = 0;
     int tier_waves_per_main_wg = 0;
-    fp.tier_lds_scene = 0;
-    // (not for scenes scanned in lockstep, lds_mode 4: a handful of leaves, every pixel about as dear as the next -- the Cornell
-    // box's 1/8 share measured 182 ms without it and 199 ms with it, profiles/r03_general_defaults.log)
-    bool tier_fits = false;      // the tier kernel's image fits: enough for the tail launches (tail hand-off) even where tier 1 is not used
+    tier_room room = {false, 0, 0, 0};   // fits: enough for the tail launches (tail hand-off) even where tier 1 is not used
     if (kernel == RT_KERNEL_STAGED && (g_opt.tier_kernel || g_opt.handoff) && s->dev.leaf_lo != nullptr) {
         size_t budget;
         if (lean_family) {
-            const size_t used = (size_t)per_cu_resident * (lds_bytes + 512);
+            const size_t used = (size_t)per_cu_resident * (ml.lds_bytes + 512);
             budget = g_lds_per_cu > used + 1024 ? g_lds_per_cu - used - 1024 : 0;
         } else {
             // the slot of one main workgroup, shared by the tier workgroups it holds: as many as it has groups of four waves
@@ -1968,29 +2091,20 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
             budget = (g_lds_per_cu / (size_t)per_cu_resident - 1024) / tier_wgs_per_slot;
             tier_waves_per_main_wg = (int)(tier_wgs_per_slot * (RT_TIER_THREADS / 64));
         }
-        const int ns_ = s->dev.n_slots, nsph = s->dev.n_spheres, nm = s->dev.n_materials, nt = s->dev.n_textures;
-        if (rt_tier_lds_bytes(ns_, nsph, nm, nt, false) <= budget) {
-            tier_fits = true;
+        room = plan_tier_room(s, budget);
+        if (room.fits) {
+            // (not for scenes scanned in lockstep, lds_mode 4: a handful of leaves, every pixel about as dear as the next -- the Cornell
+            // box's 1/8 share measured 182 ms without it and 199 ms with it, profiles/r03_general_defaults.log)
             tier_possible = g_opt.tier_kernel && lds_mode != 4 && g_opt.tier1_pixels > 0;
-            if (rt_tier_lds_bytes(ns_, nsph, nm, nt, true) <= budget) fp.tier_lds_scene = 1;
-            tier_lds = rt_tier_lds_bytes(ns_, nsph, nm, nt, fp.tier_lds_scene != 0);
             // the tier kernel's grid is fixed before the ranking has sized the tier: what can be resident beside the main
             // grid (one workgroup per CU) and as much again queued behind it; workgroups beyond the tier's size leave at once
             tier_grid = lean_family ? (unsigned)(2 * g_num_cu) : (unsigned)(g_num_cu * per_cu_resident) * (unsigned)(tier_waves_per_main_wg / (RT_TIER_THREADS / 64)) / 2u;
             if (tier_grid < 1u) tier_grid = 1u;
         }
     }
-    // the tail launch has the machine to itself: as many tier workgroups per CU as registers (launch bounds: 4 resp. 3 waves per SIMD,
-    // a workgroup is one wave per SIMD) and LDS hold
-    unsigned tail_grid = 0;
-    if (tier_fits && g_opt.handoff && (lds_mode != 4 || g_opt.handoff_scan)) {
-        const unsigned by_lds = (unsigned)(g_lds_per_cu / (tier_lds + 512));
-        const unsigned by_regs = lean_family ? 4u : 3u;
-        tail_grid = (unsigned)g_num_cu * (by_lds < by_regs ? by_lds : by_regs);
-        if (tail_grid < 1u) tail_grid = 1u;
-    }
-    out.kernel_variant = kernel * 1000 + lds_mode * 100 + s->tex_level * 10 + (s->spheres_only ? 1 : 0);
-    out.workgroups = (int)grid.x; out.threads_per_group = (int)block.x; out.lds_bytes = (int)lds_bytes;
+    fp.tier_lds_scene = room.lds_scene;
+    const size_t tier_lds = room.lds;
+    const unsigned tail_grid = room.fits && g_opt.handoff && (lds_mode != 4 || g_opt.handoff_scan) ? room.tail_grid : 0u;
 
     HIPCHK(hipEventRecord(s->ev_start, stream));
     // ---- cost-aware schedule (staged kernel): the frame is split at sample boundaries.
@@ -2012,11 +2126,8 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     // The ranking runs on the device (rt_rank.hip) and leaves the tier sizes in device memory, so the whole frame is
     // enqueued without a host round trip.  Scheduling only: every sample of every pixel is rendered exactly once, in
     // its pixel's stream order; frames are bit-identical with and without it (tests sweep the knobs).
-    fp.tile_order = nullptr; fp.tile_cost = nullptr; fp.state_out = nullptr; fp.state_in = nullptr; fp.heavy_pixels = nullptr; fp.rank = nullptr;
-    fp.sample_begin = 0; fp.sample_end = frame_ns; fp.fresh = 0; fp.store_parked = 0;
-    const size_t n_tiles = (size_t)fp.tiles_x * (size_t)tiles_y;
-    const size_t n_pixels = (size_t)local_rows * (size_t)f->nx;
-    enum { RT_HEAVY_CAP = 262144 };
+    const size_t n_tiles = (size_t)g.tiles_x * (size_t)g.tiles_y;
+    const size_t n_pixels = g.n_pixels;
     s->ranked_frame = false;
     HIPCHK(hipMemsetAsync(s->d_ray_counter, 0, 256, stream));
     int part_index = 0;
@@ -2029,18 +2140,16 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
         if (tiers) {
             HIPCHK(hipEventRecord(s->ev_fork[pi], stream));
             HIPCHK(hipStreamWaitEvent(s->tier_stream, s->ev_fork[pi], 0));
-            HIPCHK(s->spheres_only ? rt_launch_tier_spheres(s->tex_level, s->dev, q, dim3(tier_grid), tier_lds, s->tier_stream)
-                                   : rt_launch_tier_general(s->tex_level, s->need_uv, s->dev, q, dim3(tier_grid), tier_lds, s->tier_stream));
+            HIPCHK(launch_tier(s, q, dim3(tier_grid), tier_lds, s->tier_stream));
             HIPCHK(hipEventRecord(s->ev_join[pi], s->tier_stream));
         }
-        HIPCHK(launch_render(kernel, lds_mode, s, q, grid_q, block, lds_bytes, stream));
+        HIPCHK(launch_render(kernel, lds_mode, s, q, grid_q, block, ml.lds_bytes, stream));
         if (q.handoff_queue) {
             // the tail: the pixels the main kernel handed off, one per wave, on whatever the tier kernel -- which may still be
             // running on its own stream: other pixels, other queue head -- leaves free of the machine
             rt_frame_params t = q;
             t.tail_mode = 1;
-            HIPCHK(s->spheres_only ? rt_launch_tier_spheres(s->tex_level, s->dev, t, dim3(tail_grid), tier_lds, stream)
-                                   : rt_launch_tier_general(s->tex_level, s->need_uv, s->dev, t, dim3(tail_grid), tier_lds, stream));
+            HIPCHK(launch_tier(s, t, dim3(tail_grid), tier_lds, stream));
         }
         if (tiers) HIPCHK(hipStreamWaitEvent(stream, s->ev_join[pi], 0));
         return RT_OK;
@@ -2051,28 +2160,11 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
         fp.state_in = win_begin > 0 ? win->d_state : nullptr; fp.state_out = win->d_state;
         fp.sample_begin = win_begin; fp.sample_end = win_end; fp.store_parked = 1;
     } else if (g_opt.lpt && kernel == RT_KERNEL_STAGED && f->ns >= 2 * g_opt.split_samples && n_tiles >= 64 && n_pixels < (1ull << 31)) {
-        if (s->tile_capacity < n_tiles || s->pixel_capacity < n_pixels || !s->d_rank) {
-            for (void* p : {(void*)s->d_tile_cost, (void*)s->d_tile_order, (void*)s->d_state, (void*)s->d_heavy_list, (void*)s->d_heavy_pixels, (void*)s->d_rank})
-                if (p) (void)hipFree(p);
-            s->d_tile_cost = s->d_tile_order = s->d_heavy_pixels = nullptr; s->d_state = nullptr; s->d_heavy_list = nullptr; s->d_rank = nullptr;
-            s->tile_capacity = s->pixel_capacity = 0;
-            HIPCHK(hipMalloc((void**)&s->d_tile_cost, n_tiles * sizeof(unsigned int)));
-            HIPCHK(hipMalloc((void**)&s->d_tile_order, n_tiles * sizeof(unsigned int)));
-            HIPCHK(hipMalloc((void**)&s->d_state, n_pixels * sizeof(rt_pixel_state)));
-            HIPCHK(hipMalloc((void**)&s->d_heavy_list, (size_t)RT_HEAVY_CAP * sizeof(unsigned long long)));
-            HIPCHK(hipMalloc((void**)&s->d_heavy_pixels, (size_t)RT_HEAVY_CAP * sizeof(unsigned int)));
-            HIPCHK(hipMalloc((void**)&s->d_rank, sizeof(rt_rank_info)));
-            s->tile_capacity = n_tiles; s->pixel_capacity = n_pixels;
-        }
+        // ---- buffers
+        RT_TRY(grow_ranked_buffers(s, n_tiles, n_pixels));
         if (tail_grid > 0) {
             // tail hand-off (rt_device.h): a lane hands off at most one pixel per launch, so the queue holds one entry per resident lane
-            const size_t lanes = (size_t)g_num_cu * (size_t)per_cu_resident * (size_t)block.x;
-            if (s->handoff_capacity < lanes) {
-                if (s->d_handoff) (void)hipFree(s->d_handoff);
-                s->d_handoff = nullptr; s->handoff_capacity = 0;
-                HIPCHK(hipMalloc((void**)&s->d_handoff, lanes * sizeof(unsigned long long)));
-                s->handoff_capacity = lanes;
-            }
+            RT_TRY(grow(s->d_handoff, s->handoff_capacity, (size_t)g_num_cu * (size_t)per_cu_resident * (size_t)block.x));
             fp.handoff_queue = s->d_handoff; fp.handoff_cap = (uint32_t)s->handoff_capacity; fp.handoff_state = s->d_state;
             fp.handoff_poll_ticks = g_opt.handoff_poll_us * 100;
             // auto: six pixels per wave of the tail launch (the headline frame: 18432 of 960000; 8192 .. 32768 measure the same,
@@ -2082,42 +2174,14 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
             const size_t cap_px = n_pixels / 8;
             fp.handoff_pixels = g_opt.handoff_pixels >= 0 ? g_opt.handoff_pixels : (int32_t)(6 * tail_waves < cap_px ? 6 * tail_waves : cap_px);
         }
+        // ---- schedule
         // One ranking: three small kernels order the tiles, list the heavy pixels and size the tiers for the launch
         // described by `q` (which resumes every pixel from d_state).  The grids are fixed here, before the sizes are known:
         // the workgroups the ordinary queue needs plus the most the sparse tier may take; a workgroup that finds both its
         // queues empty leaves at once.  `total` = the device counter holding the sum of the costs ranked on.
         const unsigned max_grid = (unsigned)(g_num_cu * per_cu_resident);
+        const tier_sizes e = effective_tier_sizes((double)n_pixels / ((double)max_grid * (double)block.x), lean_family, g_opt);
         auto rank_pixels = [&](rt_frame_params& q, dim3& grid_q, const unsigned long long* total) -> rt_status {
-            // Effective tier sizes by the share of the frame this call renders (1/N in an N-GPU run): the fewer pixels a
-            // rank has per lane, the more of them can afford a wave of their own.  Measured on rank-local renders of the
-            // headline frame (tools/partition_time.py).
-            int e_tier1_pixels = g_opt.tier1_pixels, e_tier1_factor = g_opt.tier1_factor_x10, e_tier1_depth = g_opt.tier1_depth,
-                e_heavy_factor = g_opt.heavy_factor_x10, e_sparse_factor = g_opt.sparse_factor_x10, e_sparse_percent = g_opt.sparse_wg_percent,
-                e_work_percent = g_opt.sparse_work_percent;
-            if (g_opt.tier_auto) {
-                // keyed by pixels per resident lane (the 1200x800 frame: 3.7 whole, 1.8 / 0.9 / 0.5 for a half, a quarter,
-                // an eighth; a quarter of 1920x1080 is 2.0): what matters is how empty the machine is, not the fraction
-                const double per_lane = (double)n_pixels / ((double)max_grid * (double)block.x);
-                if (per_lane > 2.75) {
-                    // whole frames.  Lean family: the defaults.  The others: a tier wave is a main workgroup's slot taken away and
-                    // their dear pixels are many and alike (Book-2 final: the fog ball), so only the very dearest get one
-                    // (Book-2 final 800x800 @ 200: 352 ms with the lean sizes, 342 ms with these, profiles/r03_general_defaults.log)
-                    if (!lean_family) { e_tier1_factor = 70; e_tier1_pixels = 256; e_tier1_depth = 1; }
-                }
-                // shares, lean family: re-fitted in round 3 with the tier kernel beside the main kernel (tools/share_sweep.py on rank 0
-                // of the 1200x800 and 1920x1080 frames, profiles/r03_share_sweep_pass*.log; slowest-rank tables in DESIGN.md section 6)
-                // -- and again with the tail hand-off, which takes over what the largest tiers were there for (rank 0 of 8: 48.1 ms with
-                // round 3's first fit 16384 / 1.5x, 40.6 ms with the quarter's sizes; rank 0 of 2: 66.2 -> 62.6 ms, profiles/r03_handoff_shares.log)
-                else if (lean_family) {
-                    if (per_lane > 1.375) { e_tier1_pixels = 1536; e_tier1_factor = 40; e_tier1_depth = 3; e_heavy_factor = 20; e_sparse_factor = 40; e_sparse_percent = 80; e_work_percent = 5; }
-                    else { e_tier1_pixels = 8192; e_tier1_factor = 20; e_tier1_depth = 4; e_heavy_factor = 15; e_sparse_factor = 20; e_sparse_percent = 80; e_work_percent = 40; }
-                }
-                // shares, other families: round 2's sizes (Book-2 final's 1/8 share: 216 ms with these, 236 with the lean family's,
-                // 252 without a tier kernel, profiles/r03_share_sweep_final_eighth.log)
-                else if (per_lane > 1.375) { e_tier1_pixels = 4096; e_tier1_factor = 30; e_tier1_depth = 4; e_heavy_factor = 20; e_sparse_factor = 30; e_sparse_percent = 80; }
-                else if (per_lane > 0.6875) { e_tier1_pixels = 4096; e_tier1_factor = 30; e_tier1_depth = 4; e_heavy_factor = 20; e_sparse_factor = 30; e_sparse_percent = 80; e_work_percent = 20; }
-                else { e_tier1_pixels = 8192; e_tier1_factor = 20; e_tier1_depth = 4; e_heavy_factor = 15; e_sparse_factor = 15; e_sparse_percent = 80; e_work_percent = 40; }
-            }
             rt_rank_params rp;
             memset(&rp, 0, sizeof(rp));
             rp.state = s->d_state; rp.tile_cost = s->d_tile_cost; rp.tile_order = s->d_tile_order; rp.ray_counter = total;
@@ -2127,22 +2191,31 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
             rp.normal_need = (uint32_t)((q.work_items + block.x - 1) / block.x);
             rp.sparse_stride = (g_opt.sparse_stride > 0 && block.x >= 64) ? g_opt.sparse_stride : 0;
             rp.semi_stride = g_opt.semi_stride >= 0 ? g_opt.semi_stride : (lean_family ? 1 : 0);
-            rp.sparse_percent = e_sparse_percent;
-            rp.sparse_work_percent = e_work_percent;
+            rp.sparse_percent = e.sparse_percent;
+            rp.sparse_work_percent = e.work_percent;
             rp.tier_possible = tier_possible ? 1 : 0;
-            rp.tier1_pixels = e_tier1_pixels; rp.tier1_depth = e_tier1_depth;
+            rp.tier1_pixels = e.tier1_pixels; rp.tier1_depth = e.tier1_depth;
             rp.tier_wgs_cap = (int32_t)tier_grid; rp.tier_waves_per_main_wg = tier_waves_per_main_wg;
             rp.nx = f->nx; rp.smooth_percent = g_opt.cost_smooth_percent;
-            if (e_sparse_factor < e_heavy_factor) e_sparse_factor = e_heavy_factor;
-            rp.heavy_factor = (float)e_heavy_factor / 10.0f; rp.sparse_factor = (float)e_sparse_factor / 10.0f; rp.tier1_factor = (float)e_tier1_factor / 10.0f;
+            rp.heavy_factor = (float)e.heavy_factor / 10.0f; rp.sparse_factor = (float)e.sparse_factor / 10.0f; rp.tier1_factor = (float)e.tier1_factor / 10.0f;
             HIPCHK(rt_launch_rank(rp, stream));
             q.tile_order = s->d_tile_order; q.heavy_pixels = s->d_heavy_pixels; q.rank = s->d_rank;
-            unsigned total_wgs = rp.normal_need + (rp.sparse_stride > 0 ? max_grid * (unsigned)e_sparse_percent / 100u : 0u);
+            unsigned total_wgs = rp.normal_need + (rp.sparse_stride > 0 ? max_grid * (unsigned)e.sparse_percent / 100u : 0u);
             if (tier_waves_per_main_wg > 0 && tier_possible) total_wgs = max_grid;      // (workgroups that make room for the tier kernel are part of the grid)
             if (total_wgs > max_grid) total_wgs = max_grid;
             if (total_wgs < 1u) total_wgs = 1u;
             grid_q = dim3(total_wgs);
             return RT_OK;
+        };
+        // a ranked part between two others: samples [begin, end) of every pixel, resumed from and parked into d_state, with
+        // tiers ranked on the rays measured so far
+        auto ranked_part = [&](int begin, int end) -> rt_status {
+            rt_frame_params q = fp;
+            dim3 grid_q = grid;
+            q.sample_begin = begin; q.sample_end = end;
+            q.state_in = s->d_state; q.state_out = s->d_state; q.tile_cost = s->d_tile_cost;
+            RT_TRY(rank_pixels(q, grid_q, s->d_ray_counter));
+            return launch_part(q, grid_q, true);
         };
         // ---- part 1: samples [0, S_a); S_a = presplit_samples, or S0.  Nothing has been measured yet; with the cost prior
         // (rt_prior_kernel: the calibration frame's rays per pixel, scaled to this frame) the part is ranked all the same,
@@ -2158,56 +2231,38 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
             memset(&pp, 0, sizeof(pp));
             pp.state = s->d_state; pp.tile_cost = s->d_tile_cost; pp.total = s->d_ray_counter + 3;
             pp.cal_cost = s->d_cal_cost; pp.cal_nx = s->cal_nx; pp.cal_ny = s->cal_ny;
-            pp.nx = f->nx; pp.ny = f->ny; pp.local_rows = local_rows; pp.tiles_x = fp.tiles_x;
+            pp.nx = f->nx; pp.ny = f->ny; pp.local_rows = g.local_rows; pp.tiles_x = g.tiles_x;
             pp.tile_rows = f->tile_rows; pp.tile_first = f->tile_first; pp.tile_stride = f->tile_stride;
             HIPCHK(rt_launch_prior(pp, stream));
             p1.state_in = s->d_state; p1.fresh = 1;
-            const rt_status st1 = rank_pixels(p1, grid1, s->d_ray_counter + 3);
-            if (st1 != RT_OK) return st1;
+            RT_TRY(rank_pixels(p1, grid1, s->d_ray_counter + 3));
             HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));   // from here on: measured rays
             ranked1 = true;
         }
-        { const rt_status st1 = launch_part(p1, grid1, ranked1); if (st1 != RT_OK) return st1; }
+        RT_TRY(launch_part(p1, grid1, ranked1));
         // ---- part 1b: samples [S_a, S0), with tiers ranked on the first S_a samples.
-        if (first_end < g_opt.split_samples) {
-            rt_frame_params p2 = fp;
-            dim3 grid2 = grid;
-            p2.sample_begin = first_end; p2.sample_end = g_opt.split_samples;
-            p2.state_in = s->d_state; p2.state_out = s->d_state; p2.tile_cost = s->d_tile_cost;
-            rt_status st2 = rank_pixels(p2, grid2, s->d_ray_counter);
-            if (st2 != RT_OK) return st2;
-            st2 = launch_part(p2, grid2, true);
-            if (st2 != RT_OK) return st2;
-        }
+        if (first_end < g_opt.split_samples) RT_TRY(ranked_part(first_end, g_opt.split_samples));
         // ---- part 1c (optional): samples [S0, S1), ranked on the first S0 samples; the last part is then ranked again on
         // S1 samples.  A pixel's cost over 32 samples is a noisy estimate of its cost over 500 (paths through glass are
         // heavy-tailed): pixels that look cheap and are not start late and end the frame (tools/diag_wave_ends.py).
         int last_begin = g_opt.split_samples;
         if (g_opt.resplit_samples > g_opt.split_samples && f->ns >= 2 * g_opt.resplit_samples) {
-            rt_frame_params p3 = fp;
-            dim3 grid3 = grid;
-            p3.sample_begin = g_opt.split_samples; p3.sample_end = g_opt.resplit_samples;
-            p3.state_in = s->d_state; p3.state_out = s->d_state; p3.tile_cost = s->d_tile_cost;
-            rt_status st2 = rank_pixels(p3, grid3, s->d_ray_counter);
-            if (st2 != RT_OK) return st2;
-            st2 = launch_part(p3, grid3, true);
-            if (st2 != RT_OK) return st2;
+            RT_TRY(ranked_part(g_opt.split_samples, g_opt.resplit_samples));
             last_begin = g_opt.resplit_samples;
         }
         // ---- last part: samples [S1 or S0, ns), ranked on everything rendered so far
         fp.state_in = s->d_state; fp.sample_begin = last_begin;
-        const rt_status st3 = rank_pixels(fp, grid, s->d_ray_counter);
-        if (st3 != RT_OK) return st3;
+        RT_TRY(rank_pixels(fp, grid, s->d_ray_counter));
         out.workgroups = (int)grid.x;
         s->ranked_frame = true;
     }
-    out.reserved = 0;
 #ifdef RT_DIAG
     // wave-end histograms of the frame's last launch only (rt_debug_wave_ends)
     HIPCHK(hipMemsetAsync(s->d_ray_counter + RT_DIAG_T0_SLOT, 0xFF, 8, stream));
     HIPCHK(hipMemsetAsync(s->d_ray_counter + RT_DIAG_HIST_SLOT, 0, (size_t)(2 * RT_DIAG_BINS + 7 + 2 * RT_DIAG_MAX_WAVES) * 8, stream));
 #endif
-    { const rt_status stl = launch_part(fp, grid, s->ranked_frame); if (stl != RT_OK) return stl; }
+    RT_TRY(launch_part(fp, grid, s->ranked_frame));
+    // ---- finish
     HIPCHK(hipEventRecord(s->ev_stop, stream));
     s->frame_pending = true;
     s->pending_stream = stream;
@@ -2226,21 +2281,14 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
 // pixels and the 4-byte-per-pixel map, which rt_render_variance shares, and (`lists`) what only the adaptive decisions need
 static rt_status ensure_adaptive_buffers(rt_scene* s, size_t n_pixels, bool lists) {
     if (s->adapt_capacity < n_pixels) {
-        for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_spp})
-            if (p) (void)hipFree(p);
-        s->d_adapt_state = nullptr; s->d_adapt_spp = nullptr; s->adapt_capacity = 0;
-        HIPCHK(hipMalloc((void**)&s->d_adapt_state, n_pixels * sizeof(rt_pixel_state)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_spp, n_pixels * sizeof(int32_t)));
+        s->adapt_capacity = 0;
+        RT_TRY(reallocate({{(void**)&s->d_adapt_state, n_pixels * sizeof(rt_pixel_state)}, {(void**)&s->d_adapt_spp, n_pixels * sizeof(int32_t)}}));
         s->adapt_capacity = n_pixels;
     }
     if (lists && s->adapt_lists_capacity < n_pixels) {
-        for (void* p : {(void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue})
-            if (p) (void)hipFree(p);
-        s->d_adapt_half = nullptr; s->d_adapt_list[0] = s->d_adapt_list[1] = nullptr; s->d_adapt_queue = nullptr; s->adapt_lists_capacity = 0;
-        HIPCHK(hipMalloc((void**)&s->d_adapt_half, n_pixels * 3 * sizeof(float)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_list[0], n_pixels * sizeof(uint32_t)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_list[1], n_pixels * sizeof(uint32_t)));
-        HIPCHK(hipMalloc((void**)&s->d_adapt_queue, n_pixels * sizeof(unsigned long long)));
+        s->adapt_lists_capacity = 0;
+        RT_TRY(reallocate({{(void**)&s->d_adapt_half, n_pixels * 3 * sizeof(float)}, {(void**)&s->d_adapt_list[0], n_pixels * sizeof(uint32_t)},
+                           {(void**)&s->d_adapt_list[1], n_pixels * sizeof(uint32_t)}, {(void**)&s->d_adapt_queue, n_pixels * sizeof(unsigned long long)}}));
         s->adapt_lists_capacity = n_pixels;
     }
     return RT_OK;
@@ -2263,27 +2311,26 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
     if (levels < 0) return invalid("rt_render_adaptive: max_spp must be min_spp * 2^K with 0 <= K <= 16");
     if (!std::isfinite(a->threshold)) return invalid("rt_render_adaptive: threshold is not finite");
     if (!std::isfinite(a->floor) || a->floor < 0.0f) return invalid("rt_render_adaptive: floor must be finite and >= 0");
-    if (f->nx <= 0 || f->ny <= 0 || (long long)f->nx * f->ny >= (1ll << 31)) return invalid("rt_render_adaptive: bad frame size");
-    const int local_rows = rt_frame_local_rows(f);
-    if (local_rows < 0) return invalid("rt_render_adaptive: bad row partition");
+    frame_geometry g;
+    RT_TRY(check_frame("rt_render_adaptive", f, false, {"bad frame size", "bad frame size", "bad row partition", "frame too large"}, g));
 
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
-    if (s->frame_pending) { const rt_status st = rt_frame_finish(s, nullptr); if (st != RT_OK) return st; }
+    RT_TRY(use_device(s->device));
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const int num_cu = g_devices[s->device].num_cu;
     const size_t lds_per_cu = g_devices[s->device].lds_per_cu;
     const int min_spp = a->min_spp, max_spp = a->max_spp;
-    const size_t n_pixels = (size_t)local_rows * (size_t)f->nx;
+    const size_t n_pixels = g.n_pixels;
     s->adapt_log.clear(); s->adapt_ms.clear();
 
     rt_stats out;
     memset(&out, 0, sizeof(out));
-    out.local_rows = local_rows;
+    out.local_rows = g.local_rows;
     if (n_pixels == 0) { s->pending_stats = out; if (stats) *stats = out; return RT_OK; }
 
     // ---- buffers: cached in the scene, grown when a frame needs more
     const size_t floats = n_pixels * 3;
-    { const rt_status eb = ensure_adaptive_buffers(s, n_pixels, true); if (eb != RT_OK) return eb; }
+    RT_TRY(ensure_adaptive_buffers(s, n_pixels, true));
     if (!s->d_adapt_count) HIPCHK(hipMalloc((void**)&s->d_adapt_count, 64));
     if (!s->d_adapt_rank) HIPCHK(hipMalloc((void**)&s->d_adapt_rank, sizeof(rt_rank_info)));
     while (s->adapt_events.size() < 2u * 18u) {
@@ -2291,69 +2338,29 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
         HIPCHK(hipEventCreate(&e));
         s->adapt_events.push_back(e);
     }
-    float* d_fb = fb;
-    if (!fb_on_device) {
-        if (s->d_fb_floats < floats) {
-            if (s->d_fb) (void)hipFree(s->d_fb);
-            s->d_fb = nullptr; s->d_fb_floats = 0;
-            HIPCHK(hipMalloc((void**)&s->d_fb, floats * sizeof(float)));
-            s->d_fb_floats = floats;
-        }
-        d_fb = s->d_fb;
-    }
+    float* d_fb = nullptr;
+    RT_TRY(device_fb(s, fb, fb_on_device, floats, &d_fb));
     int32_t* d_spp = fb_on_device ? spp_out : (spp_out ? s->d_adapt_spp : nullptr);
 
     // ---- the main kernel's frame parameters (as rt_render_window's, without store_parked: a pass only parks)
     rt_frame_params fp;
-    memset(&fp, 0, sizeof(fp));
+    fill_frame_params(s, f, g, max_spp, fp);
     fp.fb = d_fb;
-    fp.ray_counter = s->d_ray_counter;
-    fp.work_counter = s->d_work_counter;
-    fp.seed_base = f->seed_base;
-    fp.nx = f->nx; fp.ny = f->ny; fp.ns = max_spp; fp.gamma = f->gamma;
-    fp.background[0] = f->background[0]; fp.background[1] = f->background[1]; fp.background[2] = f->background[2];
-    fp.use_gradient_bg = f->use_gradient_bg;
-    fp.tile_rows = f->tile_rows; fp.tile_first = f->tile_first; fp.tile_stride = f->tile_stride;
-    fp.local_rows = local_rows;
-    fp.tiles_x = (f->nx + 7) / 8;
-    const int tiles_y = (local_rows + 7) / 8;
-    if ((long long)fp.tiles_x * tiles_y * 64 >= (1ll << 31)) return invalid("rt_render_adaptive: frame too large");
-    const uint32_t all_items = (uint32_t)fp.tiles_x * (uint32_t)tiles_y * 64u;
-    fp.sparse_priority = g_opt.sparse_priority; fp.sparse_eager = g_opt.sparse_eager; fp.semi_priority = g_opt.semi_priority; fp.tier_priority = g_opt.tier_priority;
-    fp.steps_per_trip = g_opt.steps_per_trip;
-    fp.leaf_threshold = g_opt.leaf_threshold;
-    fp.diel_threshold = g_opt.diel_threshold;
-    fp.box_threshold = g_opt.box_threshold; fp.medium_threshold = g_opt.medium_threshold;
     fp.state_out = s->d_adapt_state;
+    const uint32_t all_items = g.work_items;
 
     // ---- the tier route: the tier kernel's tail mode alone on the machine, one pixel per wave, where the scene has tier data
     // (at most 4096 leaves and 2 media) and its image fits a CU
     const bool lean_family = s->spheres_only && s->tex_level < 2;
-    bool tier_ok = s->dev.leaf_lo != nullptr;
-    size_t tier_lds = 0;
-    int tier_scene = 0;
-    unsigned tier_grid = 0;
-    if (tier_ok) {
-        const int ns_ = s->dev.n_slots, nsph = s->dev.n_spheres, nm = s->dev.n_materials, nt = s->dev.n_textures;
-        const size_t budget = lds_per_cu - 2048;
-        if (rt_tier_lds_bytes(ns_, nsph, nm, nt, false) > budget) tier_ok = false;
-        else {
-            tier_scene = rt_tier_lds_bytes(ns_, nsph, nm, nt, true) <= budget ? 1 : 0;
-            tier_lds = rt_tier_lds_bytes(ns_, nsph, nm, nt, tier_scene != 0);
-            const unsigned by_lds = (unsigned)(lds_per_cu / (tier_lds + 512));
-            const unsigned by_regs = lean_family ? 4u : 3u;
-            tier_grid = (unsigned)num_cu * (by_lds < by_regs ? by_lds : by_regs);
-            if (tier_grid < 1u) tier_grid = 1u;
-        }
-    }
-    const size_t tier_waves = (size_t)tier_grid * (RT_TIER_THREADS / 64);
+    const tier_room room = plan_tier_room(s, lds_per_cu - 2048);
+    const size_t tier_waves = (size_t)room.tail_grid * (RT_TIER_THREADS / 64);
     // auto crossover: a pass goes to the tier kernel when it has at most this many active pixels per resident tier wave.  Measured
     // on row shares with every pixel active (tools/adaptive_sweep.py --config crossover, profiles/adaptive_mi355x.jsonl, DESIGN.md
     // 4.8): the Cornell box's routes tie at 22 800 pixels (7.4 per wave of 3 072); on the headline scene the tier route is 1.6x
     // faster at 60 000 pixels and still 10 % faster at 107 500 (26 per wave of 4 096), and 1.5x slower at 240 000
     const size_t tier_per_wave = lean_family ? 32 : 6;
     auto use_tier = [&](uint32_t active) -> bool {
-        if (!tier_ok || g_opt.adaptive_tier == 0) return false;
+        if (!room.fits || g_opt.adaptive_tier == 0) return false;
         if (g_opt.adaptive_tier == 1) return true;
         return (size_t)active <= tier_per_wave * tier_waves;
     };
@@ -2373,16 +2380,15 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
             s->adapt_wc_host[RT_WC_PUSHED] = active;   // (the queue head RT_WC_TAIL_HEAD starts at 0)
             HIPCHK(hipMemcpyAsync(s->d_work_counter, s->adapt_wc_host, RT_WORK_COUNTER_BYTES, hipMemcpyHostToDevice, stream));
             q.tail_mode = 1; q.handoff_queue = s->d_adapt_queue; q.handoff_cap = (uint32_t)n_pixels; q.handoff_state = s->d_adapt_state;
-            q.tier_lds_scene = tier_scene;
+            q.tier_lds_scene = room.lds_scene;
             q.work_items = 0;
             const unsigned want = (active + (unsigned)(RT_TIER_THREADS / 64) - 1u) / (unsigned)(RT_TIER_THREADS / 64);
-            const dim3 grid(want < tier_grid ? want : tier_grid);
-            HIPCHK(s->spheres_only ? rt_launch_tier_spheres(s->tex_level, s->dev, q, grid, tier_lds, stream)
-                                   : rt_launch_tier_general(s->tex_level, s->need_uv, s->dev, q, grid, tier_lds, stream));
+            HIPCHK(launch_tier(s, q, dim3(want < room.tail_grid ? want : room.tail_grid), room.lds, stream));
         } else {
             main_launch ml;
             q.work_items = list ? active : all_items;
-            { const rt_status pl = plan_main_launch(s, RT_KERNEL_STAGED, list ? (size_t)active : n_pixels, q, ml); if (pl != RT_OK) return pl; }
+            RT_TRY(plan_main_launch(s, RT_KERNEL_STAGED, list ? (size_t)active : n_pixels, q, ml));
+            if (pass_index == 0) stats_of_launch(s, ml, out);
             dim3 grid = ml.grid;
             if (list) {
                 // the pixel list is tier 3 of a heavy list (rt_kernel_staged.h stage E): ordinary lanes take its entries first, and
@@ -2397,10 +2403,6 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
             }
             HIPCHK(hipMemsetAsync(s->d_work_counter, 0, RT_WORK_COUNTER_BYTES, stream));
             HIPCHK(launch_render(RT_KERNEL_STAGED, ml.lds_mode, s, q, grid, ml.block, ml.lds_bytes, stream));
-            if (pass_index == 0) {
-                out.kernel_variant = RT_KERNEL_STAGED * 1000 + ml.lds_mode * 100 + s->tex_level * 10 + (s->spheres_only ? 1 : 0);
-                out.workgroups = (int)grid.x; out.threads_per_group = (int)ml.block.x; out.lds_bytes = (int)ml.lds_bytes;
-            }
         }
         HIPCHK(hipEventRecord(ev[1], stream));
         s->adapt_log.push_back(tier ? 1 : 0); s->adapt_log.push_back((long long)active); s->adapt_log.push_back(b); s->adapt_log.push_back(e);
@@ -2419,7 +2421,6 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
         HIPCHK(rt_launch_adaptive(p, stream));
         return RT_OK;
     };
-#define RT_TRY(expr) do { const rt_status st_ = (expr); if (st_ != RT_OK) return st_; } while (0)
     HIPCHK(hipMemsetAsync(s->d_ray_counter, 0, 256, stream));
     HIPCHK(hipEventRecord(s->ev_start, stream));
     const uint32_t all = (uint32_t)n_pixels;
@@ -2442,27 +2443,17 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
         n *= 2;
     }
     if (n == max_spp && active > 0) RT_TRY(decide(RT_ADAPTIVE_FINAL, n, list, active, nullptr));
-#undef RT_TRY
     HIPCHK(hipEventRecord(s->ev_stop, stream));
     if (!fb_on_device) {
         HIPCHK(hipMemcpyAsync(fb, d_fb, floats * sizeof(float), hipMemcpyDeviceToHost, stream));
         if (spp_out) HIPCHK(hipMemcpyAsync(spp_out, d_spp, n_pixels * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     }
-    HIPCHK(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
-    unsigned long long rays = 0;
-    HIPCHK(hipMemcpy(&rays, s->d_ray_counter, sizeof(rays), hipMemcpyDeviceToHost));
+    RT_TRY(finish_sync_frame(s, stream, pass_index, out, stats));
     for (int k = 0; k < pass_index; ++k) {
         float pm = 0.f;
         HIPCHK(hipEventElapsedTime(&pm, s->adapt_events[2 * k], s->adapt_events[2 * k + 1]));
         s->adapt_ms.push_back(pm);
     }
-    out.ms_render = (double)ms;
-    out.rays = rays;
-    out.reserved = pass_index;
-    s->pending_stats = out;
-    if (stats) *stats = out;
     return RT_OK;
 }
 
@@ -2479,71 +2470,39 @@ rt_status rt_render_variance(rt_scene* s, const rt_frame_desc* f, const rt_varia
     if (!variance_out) return invalid("rt_render_variance: null variance_out");
     if (v->batches < 2 || v->batches > 64) return invalid("rt_render_variance: batches must be in 2..64");
     if (f->ns <= 0 || f->ns % v->batches != 0) return invalid("rt_render_variance: ns must be a positive multiple of batches");
-    if (f->nx <= 0 || f->ny <= 0 || (long long)f->nx * f->ny >= (1ll << 31)) return invalid("rt_render_variance: bad frame size");
-    const int local_rows = rt_frame_local_rows(f);
-    if (local_rows < 0) return invalid("rt_render_variance: bad row partition");
-    const int tiles_x = (f->nx + 7) / 8, tiles_y = (local_rows + 7) / 8;
-    if ((long long)tiles_x * tiles_y * 64 >= (1ll << 31)) return invalid("rt_render_variance: bad frame size (too many 8x8 tiles)");
+    frame_geometry g;
+    RT_TRY(check_frame("rt_render_variance", f, false, {"bad frame size", "bad frame size", "bad row partition", "bad frame size (too many 8x8 tiles)"}, g));
 
-    { const rt_status ud = use_device(s->device); if (ud != RT_OK) return ud; }
-    if (s->frame_pending) { const rt_status st = rt_frame_finish(s, nullptr); if (st != RT_OK) return st; }
+    RT_TRY(use_device(s->device));
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const int B = v->batches, per = f->ns / B;
     s->adapt_log.clear(); s->adapt_ms.clear();   // (rt_debug_adaptive_passes reports the last adaptive frame: this is none)
-    const size_t n_pixels = (size_t)local_rows * (size_t)f->nx;
+    const size_t n_pixels = g.n_pixels;
 
     rt_stats out;
     memset(&out, 0, sizeof(out));
-    out.local_rows = local_rows;
+    out.local_rows = g.local_rows;
     out.samples = (uint64_t)n_pixels * (uint64_t)f->ns;
     if (n_pixels == 0) { s->pending_stats = out; if (stats) *stats = out; return RT_OK; }
 
-    // ---- buffers: the adaptive frame's parked pixels and 4-byte-per-pixel map, the accumulators, a host fb's device image
+    // ---- buffers: the adaptive frame's parked pixels and 4-byte-per-pixel map, the accumulators (T_{b-1}, A, Q: three doubles
+    // per pixel), a host fb's device image
     const size_t floats = n_pixels * 3;
-    { const rt_status eb = ensure_adaptive_buffers(s, n_pixels, false); if (eb != RT_OK) return eb; }
-    if (s->var_capacity < n_pixels) {
-        if (s->d_var_acc) (void)hipFree(s->d_var_acc);
-        s->d_var_acc = nullptr; s->var_capacity = 0;
-        HIPCHK(hipMalloc((void**)&s->d_var_acc, n_pixels * 3 * sizeof(double)));
-        s->var_capacity = n_pixels;
-    }
-    float* d_fb = fb;
-    float* d_var = variance_out;
-    if (!fb_on_device) {
-        if (s->d_fb_floats < floats) {
-            if (s->d_fb) (void)hipFree(s->d_fb);
-            s->d_fb = nullptr; s->d_fb_floats = 0;
-            HIPCHK(hipMalloc((void**)&s->d_fb, floats * sizeof(float)));
-            s->d_fb_floats = floats;
-        }
-        d_fb = s->d_fb;
-        d_var = reinterpret_cast<float*>(s->d_adapt_spp);
-    }
+    RT_TRY(ensure_adaptive_buffers(s, n_pixels, false));
+    RT_TRY(grow(s->d_var_acc, s->var_capacity, n_pixels * 3));
+    float* d_fb = nullptr;
+    RT_TRY(device_fb(s, fb, fb_on_device, floats, &d_fb));
+    float* d_var = fb_on_device ? variance_out : reinterpret_cast<float*>(s->d_adapt_spp);
 
     // ---- the main kernel's frame parameters (rt_render_adaptive's: a pass only parks)
     rt_frame_params fp;
-    memset(&fp, 0, sizeof(fp));
+    fill_frame_params(s, f, g, f->ns, fp);
     fp.fb = d_fb;
-    fp.ray_counter = s->d_ray_counter;
-    fp.work_counter = s->d_work_counter;
-    fp.seed_base = f->seed_base;
-    fp.nx = f->nx; fp.ny = f->ny; fp.ns = f->ns; fp.gamma = f->gamma;
-    fp.background[0] = f->background[0]; fp.background[1] = f->background[1]; fp.background[2] = f->background[2];
-    fp.use_gradient_bg = f->use_gradient_bg;
-    fp.tile_rows = f->tile_rows; fp.tile_first = f->tile_first; fp.tile_stride = f->tile_stride;
-    fp.local_rows = local_rows;
-    fp.tiles_x = tiles_x;
-    fp.work_items = (uint32_t)fp.tiles_x * (uint32_t)tiles_y * 64u;
-    fp.sparse_priority = g_opt.sparse_priority; fp.sparse_eager = g_opt.sparse_eager; fp.semi_priority = g_opt.semi_priority; fp.tier_priority = g_opt.tier_priority;
-    fp.steps_per_trip = g_opt.steps_per_trip;
-    fp.leaf_threshold = g_opt.leaf_threshold;
-    fp.diel_threshold = g_opt.diel_threshold;
-    fp.box_threshold = g_opt.box_threshold; fp.medium_threshold = g_opt.medium_threshold;
     fp.state_out = s->d_adapt_state;
     main_launch ml;
-    { const rt_status pl = plan_main_launch(s, RT_KERNEL_STAGED, n_pixels, fp, ml); if (pl != RT_OK) return pl; }
-    out.kernel_variant = RT_KERNEL_STAGED * 1000 + ml.lds_mode * 100 + s->tex_level * 10 + (s->spheres_only ? 1 : 0);
-    out.workgroups = (int)ml.grid.x; out.threads_per_group = (int)ml.block.x; out.lds_bytes = (int)ml.lds_bytes;
+    RT_TRY(plan_main_launch(s, RT_KERNEL_STAGED, n_pixels, fp, ml));
+    stats_of_launch(s, ml, out);
 
     rt_variance_params vp;
     memset(&vp, 0, sizeof(vp));
@@ -2566,17 +2525,7 @@ rt_status rt_render_variance(rt_scene* s, const rt_frame_desc* f, const rt_varia
         HIPCHK(hipMemcpyAsync(fb, d_fb, floats * sizeof(float), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(variance_out, d_var, n_pixels * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
-    HIPCHK(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, s->ev_start, s->ev_stop));
-    unsigned long long rays = 0;
-    HIPCHK(hipMemcpy(&rays, s->d_ray_counter, sizeof(rays), hipMemcpyDeviceToHost));
-    out.ms_render = (double)ms;
-    out.rays = rays;
-    out.reserved = B;
-    s->pending_stats = out;
-    if (stats) *stats = out;
-    return RT_OK;
+    return finish_sync_frame(s, stream, B, out, stats);
 }
 
 // The passes of the last adaptive frame (diagnostics, tools/adaptive_sweep.py): per pass 5 values -- route (0 main kernel,

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Launch shapes of every render entry point, one JSON line per case: what a change of the host code that plans the launches
+(csrc/rt_abi.hip) must leave as it is.  A wrong grid or LDS size still renders the right frame, so the test suite does not see
+it.  Per case: the launch fields of rt_stats, the 13 words of rt_debug_rank_info where the frame was ranked, whether the tail
+hand-off took pixels, the passes of an adaptive frame, and the SHA-256 of the outputs.
+
+  RT_LIB_OVERRIDE=<library of the parent commit> python tools/launch_shapes.py > parent.jsonl
+  python tools/launch_shapes.py > new.jsonl && diff parent.jsonl new.jsonl
+
+profiles/abi_refactor_launch_shapes.jsonl is this tool's output on an MI355X."""
+import ctypes as C
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import accelerated_ray_tracer_amd as art   # noqa: E402
+
+art.init(0)
+L = art.rt_lib()
+L.rt_debug_handoff.argtypes = [C.c_void_p, C.c_void_p]
+
+
+def emit(case, **kw):
+    print(json.dumps(dict(case=case, **kw), sort_keys=True), flush=True)
+
+
+def stats_dict(st):
+    return {k: int(getattr(st, k)) for k in ("kernel_variant", "workgroups", "threads_per_group", "lds_bytes", "samples", "reserved")}
+
+
+def rank_and_handoff(ds):
+    w = np.zeros(13, np.uint32)
+    ranked = L.rt_debug_rank_info(ds._p, w.ctypes.data) == 0
+    h = np.zeros(2, np.uint64)
+    assert L.rt_debug_handoff(ds._p, h.ctypes.data) == 0
+    return dict(rank_info=[int(x) for x in w] if ranked else None, handoff=[bool(h[0]), bool(h[1])])
+
+
+def sha(*arrays):
+    m = hashlib.sha256()
+    for a in arrays:
+        m.update(np.ascontiguousarray(a).tobytes())
+    return m.hexdigest()
+
+
+def dev_buf(n, dtype=torch.float32):
+    return torch.zeros(n, dtype=dtype, device="cuda:0")
+
+
+for scene in ("random_scene", "cornell"):
+    frames = [("64x64@32", dict(nx=64, ny=64, ns=32)), ("64x64@8", dict(nx=64, ny=64, ns=8)),
+              ("64x64@32 share", dict(nx=64, ny=64, ns=32, tile_rows=8, tile_stride=2, tile_first=1)),
+              ("61x43@32", dict(nx=61, ny=43, ns=32)), ("131x67@32", dict(nx=131, ny=67, ns=32))]
+    for name, kw in frames:
+        hs = art.HostScene(scene, kw["nx"], kw["ny"])
+        ds = art.DeviceScene(hs)
+        f = hs.frame(**kw)
+        rows = L.rt_frame_local_rows(C.byref(f))
+        for where in ("host", "device"):
+            if where == "host":
+                fb, st = ds.render(f)
+                digest = sha(fb)
+            else:
+                t = dev_buf(rows * f.nx * 3)
+                _, st = ds.render(f, out=t.data_ptr())
+                digest = sha(t.cpu().numpy())
+            emit(f"{scene} rt_render {name} {where} fb", fb_sha256=digest, **stats_dict(st), **rank_and_handoff(ds))
+        ds.close()
+
+    hs = art.HostScene(scene, 64, 64)
+    ds = art.DeviceScene(hs)
+    f = hs.frame(nx=64, ny=64, ns=16)
+    pf = ds.progressive(f)
+    for b, e in ((0, 8), (8, 16)):
+        fb, st = pf.render(b, e)
+        emit(f"{scene} rt_render_window [{b},{e})", fb_sha256=sha(fb), **stats_dict(st), **rank_and_handoff(ds))
+    pf.close()
+
+    for tier in (0, 1):
+        art.set_option("adaptive_tier", tier)
+        for where in ("host", "device"):
+            fa = hs.frame(nx=64, ny=64, ns=32)
+            if where == "host":
+                fb, spp, st = ds.render_adaptive(fa, 4, 32, 0.05)
+                digest = sha(fb, spp)
+            else:
+                t, ts = dev_buf(64 * 64 * 3), dev_buf(64 * 64, torch.int32)
+                _, _, st = ds.render_adaptive(fa, 4, 32, 0.05, out=t, spp_out=ts)
+                digest = sha(t.cpu().numpy(), ts.cpu().numpy())
+            passes = [[p["route"], p["active"], p["samples"][0], p["samples"][1]] for p in ds.adaptive_passes()]
+            emit(f"{scene} rt_render_adaptive 4..32 adaptive_tier={tier} {where} fb", fb_sha256=digest, passes=passes, **stats_dict(st))
+    art.reset_options()
+
+    for where in ("host", "device"):
+        fv = hs.frame(nx=64, ny=64, ns=16)
+        if where == "host":
+            fb, var, st = ds.render_variance(fv, 4)
+            digest = sha(fb, var)
+        else:
+            t, tv = dev_buf(64 * 64 * 3), dev_buf(64 * 64)
+            _, _, st = ds.render_variance(fv, 4, out=t, variance_out=tv)
+            digest = sha(t.cpu().numpy(), tv.cpu().numpy())
+        emit(f"{scene} rt_render_variance 4x4 {where} fb", fb_sha256=digest, **stats_dict(st))
+
+    fq = hs.frame(nx=64, ny=64, ns=4)
+    aov = ds.render_aov(fq, ids=True)
+    emit(f"{scene} rt_render_aov host", sha256=sha(*[aov[k] for k in sorted(aov)]))
+    thr = ds.render_aov_through(fq, ids=True, through=True, bounces=True)
+    emit(f"{scene} rt_render_aov_through host", sha256=sha(*[thr[k] for k in sorted(thr)]))
+    noisy, _ = ds.render(fq)
+    noisy = np.ascontiguousarray(noisy.reshape(64, 64, 3))
+    den = art.denoise(noisy, albedo=np.ascontiguousarray(aov["albedo"].reshape(64, 64, 3)), normal=np.ascontiguousarray(aov["normal"].reshape(64, 64, 3)),
+                      depth=np.ascontiguousarray(aov["depth"].reshape(64, 64)))
+    emit(f"{scene} rt_denoise host", sha256=sha(den))
+    ds.close()
