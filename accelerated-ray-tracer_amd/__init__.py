@@ -106,6 +106,14 @@ class RtDenoiseVarianceDesc(C.Structure):
     _fields_ = [("variance", C.c_void_p), ("variance_out", C.c_void_p), ("sigma_variance", C.c_float), ("variance_floor", C.c_float)]
 
 
+class RtReprojectDesc(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("cur", RtCamera), ("prev", RtCamera),
+                ("color", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p), ("normal", C.c_void_p), ("prim", C.c_void_p),
+                ("history", C.c_void_p), ("history_len", C.c_void_p), ("prev_depth", C.c_void_p), ("prev_alpha", C.c_void_p),
+                ("prev_normal", C.c_void_p), ("prev_prim", C.c_void_p), ("out", C.c_void_p), ("out_len", C.c_void_p), ("motion", C.c_void_p),
+                ("alpha_min", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_float)]
+
+
 RT_TRACE_CLOSEST, RT_TRACE_ANY = 0, 1
 RT_PRIM_SPHERE, RT_PRIM_QUAD, RT_PRIM_BOX, RT_PRIM_INSTANCE, RT_PRIM_MEDIUM = range(5)
 
@@ -132,6 +140,11 @@ AOV_THROUGH_DEFAULTS = {"max_bounces": 8, "fuzz_limit": 0.0}
 DENOISE_DEFAULTS = {"iterations": 5, "normal_sharpness": 4, "sigma_depth": 0.2, "sigma_color": 2.0, "color_floor": 0.01}
 # denoise(variance=...): the keyword defaults of the variance factor, settled by a sweep on the same frames
 DENOISE_VARIANCE_DEFAULTS = {"sigma_variance": 3.0, "variance_floor": 1e-4}
+# reproject() / TemporalAccumulator: the keyword defaults of rt_reproject's four thresholds
+REPROJECT_DEFAULTS = {"alpha_min": 0.5, "depth_tol": 0.05, "normal_min": 0.5, "max_history": 32.0}
+# reproject(): out is the accumulated frame (the next call's history), length its per-pixel history length, motion the
+# per-pixel offset into the previous frame (None unless motion=True)
+ReprojectResult = collections.namedtuple("ReprojectResult", "out length motion")
 # DeviceScene.radiance(): rays is None unless count_rays=True
 RadianceResult = collections.namedtuple("RadianceResult", "rgb rays")
 
@@ -151,7 +164,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_progressive_state_create", "rt_progressive_state_destroy", "rt_render_window",
                   "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive",
                   "rt_radiance_rays", "rt_render_aov", "rt_render_aov_through", "rt_denoise_workspace_bytes", "rt_denoise", "rt_render_variance",
-                  "rt_denoise_variance", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info"]
+                  "rt_denoise_variance", "rt_scene_set_camera", "rt_scene_get_camera", "rt_multi_set_camera", "rt_reproject",
+                  "rt_reproject_matrix", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info"]
 
 _rt = None
 _host = None
@@ -186,6 +200,8 @@ def host_lib():
         L.rtw_scene_leaf_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.rtw_write_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.rtw_load_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rtw_camera_init.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_double, C.c_double, C.POINTER(RtCamera)]
         _host = L
     return _host
 
@@ -236,6 +252,11 @@ def rt_lib():
         L.rt_render_variance.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtVarianceDesc), C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.POINTER(RtStats)]
         L.rt_denoise_variance.argtypes = [C.POINTER(RtDenoiseDesc), C.POINTER(RtDenoiseVarianceDesc), C.c_int, C.c_void_p, C.c_int]
+        L.rt_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera), C.c_int]
+        L.rt_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera)]
+        L.rt_multi_set_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera), C.c_int]
+        L.rt_reproject.argtypes = [C.POINTER(RtReprojectDesc), C.c_int, C.c_void_p, C.c_int]
+        L.rt_reproject_matrix.argtypes = [C.POINTER(RtCamera), C.POINTER(C.c_float)]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.rt_debug_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_debug_prior.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -492,6 +513,132 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_D
     return out
 
 
+def make_camera(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist, t0=0.0, t1=0.0) -> RtCamera:
+    """The rt_camera a reference scene function would construct from these arguments (camera.cuh:59-78): the host scene
+    library's camera class, i.e. the reference's own float arithmetic -- what HostScene(name).desc.camera holds for the
+    arguments in host/rtw_scenes.cpp.  lookfrom, lookat, vup: three floats each; vfov in degrees; [t0, t1]: the shutter."""
+    v = [np.asarray(x, np.float64).reshape(-1) for x in (lookfrom, lookat, vup)]
+    if any(len(x) != 3 for x in v):
+        raise ValueError("lookfrom, lookat and vup: three floats each are expected")
+    scalars = [float(x) for x in (vfov, aspect, aperture, focus_dist, t0, t1)]
+    if not all(np.isfinite(x).all() for x in v) or not np.isfinite(scalars).all():
+        raise ValueError("the camera arguments must be finite")
+    if scalars[5] < scalars[4]:
+        raise ValueError("t1 must not be before t0")
+    a = [(C.c_float * 3)(*x) for x in v]
+    c = RtCamera()
+    if host_lib().rtw_camera_init(a[0], a[1], a[2], *scalars, C.byref(c)) != 0:
+        raise RtError("rtw_camera_init failed")
+    return c
+
+
+def reproject_matrix(prev: RtCamera) -> np.ndarray:
+    """rt_reproject_matrix: the 3 x 3 float32 matrix that takes a vector from `prev`'s origin to (a, a s, a t), its ray
+    parameter and frame coordinates in `prev` (include/rt_abi.h).  Host only.  A singular camera is ValueError."""
+    m = (C.c_float * 9)()
+    L = rt_lib()
+    st = L.rt_reproject_matrix(C.byref(prev), m)
+    if st == 1:
+        raise ValueError(L.rt_last_error_detail().decode())
+    _check(st, "rt_reproject_matrix")
+    return np.array(m, np.float32).reshape(3, 3)
+
+
+def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, prim=None, history=None, history_len=None,
+              prev_depth=None, prev_alpha=None, prev_normal=None, prev_prim=None, *, out=None, out_len=None, motion=False,
+              alpha_min=REPROJECT_DEFAULTS["alpha_min"], depth_tol=REPROJECT_DEFAULTS["depth_tol"],
+              normal_min=REPROJECT_DEFAULTS["normal_min"], max_history=REPROJECT_DEFAULTS["max_history"], stream=0, blocking=True):
+    """Temporal reprojection (rt_reproject, include/rt_abi.h): the current linear frame `color` (ny, nx, 3) blended into the
+    history of the previous frame, fetched where each pixel's surface point -- from `depth` and `alpha` (ny, nx) of
+    render_aov and the cameras `cur` and `prev` -- was in that frame.  history (ny, nx, 3) and history_len (ny, nx) are the
+    previous call's out and length, prev_depth / prev_alpha the previous frame's depth and alpha; history=None is the first
+    frame (out = color, length 1).  normal (ny, nx, 3) with prev_normal, and prim (ny, nx) int32 with prev_prim, switch on
+    the normal and the id test of a tap.  It runs on the device of init().
+
+    Either all numpy arrays (C-contiguous; the call waits) or all contiguous torch tensors on that device: zero-copy,
+    enqueued on `stream` (a hipStream_t as an integer or a torch.cuda.Stream) and waited for only with blocking=True.  out /
+    out_len: None (made like color) or arrays / tensors of the same kind; they may overlap no input.  motion: False, True (a
+    (ny, nx, 2) buffer is made) or such a buffer.  Returns a ReprojectResult (out, length, motion).  Malformed arguments raise
+    ValueError before anything is launched."""
+    on_host = isinstance(color, np.ndarray)
+    if not on_host and not hasattr(color, "data_ptr"):
+        raise ValueError("color: a numpy array or a torch tensor is expected")
+    if color.ndim != 3 or color.shape[2] != 3 or color.shape[0] < 1 or color.shape[1] < 1:
+        raise ValueError(f"color: shape {tuple(color.shape)}, expected (ny, nx, 3)")
+    ny, nx = int(color.shape[0]), int(color.shape[1])
+    if nx * ny >= 1 << 31:
+        raise ValueError("frame too large")
+    alpha_min, depth_tol, normal_min, max_history = (float(np.float32(x)) for x in (alpha_min, depth_tol, normal_min, max_history))
+    if not 0 < alpha_min <= 1:
+        raise ValueError("alpha_min must be in (0, 1]")
+    if not 0 <= depth_tol <= 1:
+        raise ValueError("depth_tol must be in [0, 1]")
+    if not -1 <= normal_min <= 1:
+        raise ValueError("normal_min must be in [-1, 1]")
+    if not 1 <= max_history <= 65536:
+        raise ValueError("max_history must be in [1, 65536]")
+    if not isinstance(cur, RtCamera) or not isinstance(prev, RtCamera):
+        raise ValueError("cur and prev: RtCamera structures are expected")
+    if depth is None or alpha is None:
+        raise ValueError("depth and alpha are required")
+    if history is None:
+        if any(x is not None for x in (history_len, prev_depth, prev_alpha)):
+            raise ValueError("history_len, prev_depth and prev_alpha need history")
+    elif any(x is None for x in (history_len, prev_depth, prev_alpha)):
+        raise ValueError("history needs history_len, prev_depth and prev_alpha")
+    if on_host:
+        dev = None
+        make = lambda shape: np.empty(shape, np.float32)   # noqa: E731
+    else:
+        import torch
+        dev = torch.device("cuda", 0 if _initialised_device is None else _initialised_device)
+        make = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+    if out is None:
+        out = make((ny, nx, 3))
+    if out_len is None:
+        out_len = make((ny, nx))
+    if motion is True:
+        motion = make((ny, nx, 2))
+    elif motion is False:
+        motion = None
+
+    def ptr(x, name, shape, integer=False):
+        if x is None:
+            return None
+        if on_host:
+            want = np.int32 if integer else np.float32
+            if not isinstance(x, np.ndarray):
+                raise ValueError(f"{name}: a numpy array is expected (color is one)")
+            if x.dtype != want or tuple(x.shape) != shape or not x.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{name}: a C-contiguous {np.dtype(want).name} array of shape {shape} is expected")
+            return x.ctypes.data
+        want = torch.int32 if integer else torch.float32
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name}: a torch tensor is expected (color is one)")
+        if x.dtype != want or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"{name}: a contiguous {want} tensor of shape {shape} on {dev} is expected")
+        return x.data_ptr()
+
+    d = RtReprojectDesc()
+    d.nx, d.ny, d.cur, d.prev = nx, ny, cur, prev
+    rgb, one = (ny, nx, 3), (ny, nx)
+    d.color, d.depth, d.alpha = ptr(color, "color", rgb), ptr(depth, "depth", one), ptr(alpha, "alpha", one)
+    d.normal, d.prim = ptr(normal, "normal", rgb), ptr(prim, "prim", one, True)
+    d.history, d.history_len = ptr(history, "history", rgb), ptr(history_len, "history_len", one)
+    d.prev_depth, d.prev_alpha = ptr(prev_depth, "prev_depth", one), ptr(prev_alpha, "prev_alpha", one)
+    d.prev_normal, d.prev_prim = ptr(prev_normal, "prev_normal", rgb), ptr(prev_prim, "prev_prim", one, True)
+    d.out, d.out_len, d.motion = ptr(out, "out", rgb), ptr(out_len, "out_len", one), ptr(motion, "motion", (ny, nx, 2))
+    d.alpha_min, d.depth_tol, d.normal_min, d.max_history = alpha_min, depth_tol, normal_min, max_history
+    if hasattr(stream, "cuda_stream"):
+        stream = stream.cuda_stream
+    L = rt_lib()
+    st = L.rt_reproject(C.byref(d), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None, 1 if blocking else 0)
+    if st == 1:
+        raise ValueError(L.rt_last_error_detail().decode())
+    _check(st, "rt_reproject")
+    return ReprojectResult(out, out_len, motion)
+
+
 def _chain_args(max_bounces, fuzz_limit):
     """(max_bounces, fuzz_limit) of render_aov_through as rt_aov_through_desc takes them, or ValueError."""
     if isinstance(max_bounces, bool) or not isinstance(max_bounces, (int, np.integer)) or not 0 <= int(max_bounces) <= 16:
@@ -512,6 +659,23 @@ class DeviceScene:
         self.device = _initialised_device
         self._p = C.c_void_p()
         _check(rt_lib().rt_scene_create(C.byref(host_scene.desc), C.byref(self._p)), "rt_scene_create")
+
+    def set_camera(self, camera: RtCamera, recalibrate: bool = False) -> None:
+        """Another view of the scene as it stands on the device (rt_scene_set_camera): every later frame entry writes what it
+        would write on a scene created with this camera.  recalibrate=True also renders the small calibration frame again
+        for the cost prior of ranked frames; without it the old prior stays, which costs time and never a pixel.  A
+        non-finite field or time1 < time0 is ValueError."""
+        L = rt_lib()
+        st = L.rt_scene_set_camera(self._p, C.byref(camera), 1 if recalibrate else 0)
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_scene_set_camera")
+
+    def camera(self) -> RtCamera:
+        """The camera the next frame uses (rt_scene_get_camera): the description's, or the last one set."""
+        c = RtCamera()
+        _check(rt_lib().rt_scene_get_camera(self._p, C.byref(c)), "rt_scene_get_camera")
+        return c
 
     def render(self, frame: RtFrameDesc, out=None, stream: int = 0, blocking: bool = True):
         """Render into `out`: a float32 numpy array (host) or an integer device pointer.  Returns (array|None, stats)."""
@@ -1012,6 +1176,53 @@ class ProgressiveFrame:
             pass
 
 
+class TemporalAccumulator:
+    """Frames of a moving camera accumulated over time: push(camera) sets the camera, renders `frame` at gamma 1, takes the
+    feature buffers of render_aov (normal, depth, alpha and the ids, at min(frame.ns, 16) samples), reprojects the history
+    kept from the last push into the new view (reproject(), normals and ids on) and keeps the result and the buffers for the
+    next push.  Returns the accumulated linear frame (ny, nx, 3) as a numpy array -- with denoise=True filtered by denoise()
+    with the albedo, normal and depth of the same pass; the history itself stays unfiltered.  **params: thresholds of
+    REPROJECT_DEFAULTS.  `frame` must be the whole image.  `length` holds the last push's per-pixel history length."""
+
+    def __init__(self, scene: "DeviceScene", frame: RtFrameDesc, denoise: bool = False, **params):
+        unknown = set(params) - set(REPROJECT_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown parameter(s) {sorted(unknown)}: one of {', '.join(REPROJECT_DEFAULTS)} is expected")
+        if frame.nx <= 0 or frame.ny <= 0 or frame.ns <= 0:
+            raise ValueError("bad frame size or sample count")
+        if frame.tile_first != 0 or frame.tile_stride != 1 or frame.tile_rows < frame.ny:
+            raise ValueError("TemporalAccumulator needs the whole frame (tile_rows >= ny, tile_first = 0, tile_stride = 1)")
+        self.scene, self.denoise, self.params = scene, bool(denoise), dict(REPROJECT_DEFAULTS, **params)
+        self.frame = RtFrameDesc.from_buffer_copy(frame)
+        self.frame.gamma = 1.0
+        self.aov_frame = RtFrameDesc.from_buffer_copy(self.frame)
+        self.aov_frame.ns = min(frame.ns, 16)
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget the history: the next push is a first frame."""
+        self._prev = None
+        self.length = None
+
+    def push(self, camera: RtCamera, recalibrate: bool = False) -> np.ndarray:
+        self.scene.set_camera(camera, recalibrate)
+        color, _ = self.scene.render(self.frame)
+        aov = self.scene.render_aov(self.aov_frame, albedo=self.denoise, ids=True)
+        cam = RtCamera.from_buffer_copy(camera)
+        p = self._prev
+        if p is None:
+            r = reproject(color, aov["depth"], aov["alpha"], cam, cam, **self.params)
+        else:
+            r = reproject(color, aov["depth"], aov["alpha"], cam, p["camera"], aov["normal"], aov["prim"], p["out"], p["length"],
+                          p["depth"], p["alpha"], p["normal"], p["prim"], **self.params)
+        self._prev = {"camera": cam, "out": r.out, "length": r.length, "depth": aov["depth"], "alpha": aov["alpha"],
+                      "normal": aov["normal"], "prim": aov["prim"]}
+        self.length = r.length
+        if self.denoise:
+            return denoise(r.out, aov["albedo"], aov["normal"], aov["depth"])
+        return r.out
+
+
 class MultiScene:
     """rt_multi*: one replica of the scene per GPU, driven from this thread (rt_multi_* of include/rt_abi.h)."""
 
@@ -1022,6 +1233,14 @@ class MultiScene:
         self.host = host_scene
         self._p = C.c_void_p()
         _check(rt_lib().rt_multi_create(C.byref(host_scene.desc), n_gpus, C.byref(self._p)), "rt_multi_create")
+
+    def set_camera(self, camera: RtCamera, recalibrate: bool = False) -> None:
+        """DeviceScene.set_camera on every replica (rt_multi_set_camera)."""
+        L = rt_lib()
+        st = L.rt_multi_set_camera(self._p, C.byref(camera), 1 if recalibrate else 0)
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_multi_set_camera")
 
     def render(self, frame: RtFrameDesc, tile_rows: int = 4):
         """The whole frame as float32[ny][nx][3] in host memory, and the summed statistics."""

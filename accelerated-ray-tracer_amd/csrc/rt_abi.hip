@@ -1252,6 +1252,44 @@ rt_status rt_frame_finish(rt_scene* s, rt_stats* stats) {
 }
 
 namespace {
+// the checks rt_scene_set_camera and rt_reproject make of a camera: every field finite (pad is not looked at), time0 <= time1
+const char* camera_fault(const rt_camera& c) {
+    const float* groups[6] = {c.origin, c.lower_left_corner, c.horizontal, c.vertical, c.u, c.v};
+    for (const float* g : groups)
+        for (int k = 0; k < 3; ++k) if (!std::isfinite(g[k])) return "a camera field is not finite";
+    if (!std::isfinite(c.lens_radius) || !std::isfinite(c.time0) || !std::isfinite(c.time1)) return "a camera field is not finite";
+    if (c.time1 < c.time0) return "the camera's time1 is before its time0";
+    return nullptr;
+}
+}  // namespace
+
+// ---- rt_scene_set_camera (include/rt_abi.h).  The camera lives in rt_scene_dev, which every launch copies into
+// its kernel's argument block: replacing it is the whole change.  The walk array, the tier data and the LDS plans do not depend
+// on it.  recalibrate: the cost half of the calibration alone -- the pass of build_walk on the reference's tree with keep_cost,
+// its pass counts dropped.
+rt_status rt_scene_set_camera(rt_scene* s, const rt_camera* camera, int recalibrate) {
+    if (!s) return invalid("rt_scene_set_camera: null scene");
+    if (!camera) return invalid("rt_scene_set_camera: null camera");
+    if (const char* why = camera_fault(*camera)) return invalid((std::string("rt_scene_set_camera: ") + why).c_str());
+    RT_TRY(use_device(s->device));
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
+    s->dev.camera = *camera;
+    if (recalibrate && s->d_cal_cost) {   // (a scene that kept no prior at creation gets none: a fresh scene would have none either)
+        std::vector<double> pass;
+        double rays = 0.0;
+        RT_TRY(measure_pass_counts(s, s->dev.nodes_ref, s->dev.n_nodes_ref, pass, rays, nullptr, 0, /*keep_cost=*/true));
+    }
+    return RT_OK;
+}
+
+rt_status rt_scene_get_camera(const rt_scene* s, rt_camera* out) {
+    if (!s) return invalid("rt_scene_get_camera: null scene");
+    if (!out) return invalid("rt_scene_get_camera: null output pointer");
+    *out = s->dev.camera;
+    return RT_OK;
+}
+
+namespace {
 // a pointer rt_trace_rays / rt_radiance_rays (`who`) hands to a kernel: null, or `bytes` of device (or managed) memory of
 // `device`, aligned to `align` bytes
 rt_status check_trace_ptr(const void* p, size_t bytes, int device, const char* what, const char* who, unsigned align) {
@@ -1616,6 +1654,125 @@ rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stre
 rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_variance_desc* vd, int buffers_on_device, void* stream_v, int blocking) {
     if (!vd) return invalid("rt_denoise_variance: null variance description");
     return denoise_impl(d, vd, "rt_denoise_variance", buffers_on_device, stream_v, blocking);
+}
+
+// ---- rt_reproject (include/rt_abi.h)
+// The inverse of the previous camera's (A, H, V) basis, in double from its float fields, one rounding per written operation
+// (the library is built with -ffp-contract=off, which this function's contract needs: no product may fuse into a sum).
+rt_status rt_reproject_matrix(const rt_camera* prev, float m[9]) {
+    if (!prev) return invalid("rt_reproject_matrix: null camera");
+    if (!m) return invalid("rt_reproject_matrix: null output pointer");
+    double A[3], H[3], V[3];
+    for (int c = 0; c < 3; ++c) {
+        A[c] = (double)prev->lower_left_corner[c] - (double)prev->origin[c];
+        H[c] = (double)prev->horizontal[c];
+        V[c] = (double)prev->vertical[c];
+    }
+    auto cross = [](const double* x, const double* y, double* out) {
+        out[0] = x[1] * y[2] - x[2] * y[1];
+        out[1] = x[2] * y[0] - x[0] * y[2];
+        out[2] = x[0] * y[1] - x[1] * y[0];
+    };
+    double r[3][3];
+    cross(H, V, r[0]);
+    cross(V, A, r[1]);
+    cross(A, H, r[2]);
+    const double D = (A[0] * r[0][0] + A[1] * r[0][1]) + A[2] * r[0][2];
+    if (D == 0.0) return invalid("rt_reproject_matrix: the camera's basis is singular (D == 0)");
+    float out[9];
+    for (int k = 0; k < 3; ++k)
+        for (int c = 0; c < 3; ++c) {
+            out[3 * k + c] = (float)(r[k][c] / D);
+            if (!std::isfinite(out[3 * k + c])) return invalid("rt_reproject_matrix: the matrix is not finite");
+        }
+    memcpy(m, out, sizeof(out));
+    return RT_OK;
+}
+
+rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* stream_v, int blocking) {
+    // argument checks: no HIP call before they pass
+    auto bad = [&](const char* why) { return invalid((std::string("rt_reproject: ") + why).c_str()); };
+    if (!d) return bad("null description");
+    if (d->nx < 1 || d->ny < 1) return bad("nx and ny must be positive");
+    if ((long long)d->nx * d->ny >= (1ll << 31)) return bad("frame too large");
+    if (!(d->alpha_min > 0.f && d->alpha_min <= 1.f)) return bad("alpha_min must be in (0, 1]");
+    if (!(d->depth_tol >= 0.f && d->depth_tol <= 1.f)) return bad("depth_tol must be in [0, 1]");
+    if (!(d->normal_min >= -1.f && d->normal_min <= 1.f)) return bad("normal_min must be in [-1, 1]");
+    if (!(d->max_history >= 1.f && d->max_history <= 65536.f)) return bad("max_history must be in [1, 65536]");
+    if (!d->color) return bad("null color");
+    if (!d->depth) return bad("null depth");
+    if (!d->alpha) return bad("null alpha");
+    if (!d->out) return bad("null out");
+    if (!d->out_len) return bad("null out_len");
+    if (d->history) {
+        if (!d->history_len || !d->prev_depth || !d->prev_alpha) return bad("history needs history_len, prev_depth and prev_alpha");
+    } else if (d->history_len || d->prev_depth || d->prev_alpha) {
+        return bad("history_len, prev_depth and prev_alpha need history");
+    }
+    rt_reproject_params rp;
+    memset(&rp, 0, sizeof(rp));
+    if (rt_reproject_matrix(&d->prev, rp.m) != RT_OK) return bad("prev: the camera's basis is singular or its inverse is not finite");
+    const size_t pixels = (size_t)d->nx * d->ny;
+    struct buffer : traced_ptr { bool input; };
+    enum { COLOR = 0, DEPTH, ALPHA, NORMAL, PRIM, HISTORY, HISTORY_LEN, PREV_DEPTH, PREV_ALPHA, PREV_NORMAL, PREV_PRIM, OUT, OUT_LEN, MOTION, N_BUFS };
+    const size_t f1 = pixels * sizeof(float), f3 = 3 * f1;
+    const buffer bufs[N_BUFS] = {{{d->color, f3, "color", 4}, true}, {{d->depth, f1, "depth", 4}, true}, {{d->alpha, f1, "alpha", 4}, true},
+                                 {{d->normal, f3, "normal", 4}, true}, {{d->prim, f1, "prim", 4}, true}, {{d->history, f3, "history", 4}, true},
+                                 {{d->history_len, f1, "history_len", 4}, true}, {{d->prev_depth, f1, "prev_depth", 4}, true},
+                                 {{d->prev_alpha, f1, "prev_alpha", 4}, true}, {{d->prev_normal, f3, "prev_normal", 4}, true},
+                                 {{d->prev_prim, f1, "prev_prim", 4}, true}, {{d->out, f3, "out", 4}, false}, {{d->out_len, f1, "out_len", 4}, false},
+                                 {{d->motion, 2 * f1, "motion", 4}, false}};
+    for (int o = OUT; o < N_BUFS; ++o)     // an output shares no byte with any other buffer
+        for (int k = 0; k < N_BUFS; ++k) {
+            const uintptr_t pa = (uintptr_t)bufs[o].p, pb = (uintptr_t)bufs[k].p;
+            if (k != o && bufs[o].p && bufs[k].p && pa < pb + bufs[k].bytes && pb < pa + bufs[o].bytes)
+                return bad((std::string(bufs[o].what) + " overlaps " + bufs[k].what).c_str());
+        }
+    RT_TRY(use_device(g_device));
+    if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, g_device, "rt_reproject"));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+
+    // (without a history no tap is read: the tests on taps are then off whatever guides were given)
+    const bool normals_on = d->history && d->normal && d->prev_normal, ids_on = d->history && d->prim && d->prev_prim, motion_on = d->motion != nullptr;
+    auto used = [&](int k) {   // what the kernel reads or writes
+        if (!bufs[k].p) return false;
+        if (k == NORMAL || k == PREV_NORMAL) return normals_on;
+        if (k == PRIM || k == PREV_PRIM) return ids_on;
+        return true;
+    };
+    const void* dev[N_BUFS];
+    for (int k = 0; k < N_BUFS; ++k) dev[k] = used(k) ? bufs[k].p : nullptr;
+    call_memory mem;
+    mem.guard(stream);
+    if (!buffers_on_device) {   // host buffers: their device images in one allocation of this call's own
+        size_t total = 0;
+        for (int k = 0; k < N_BUFS; ++k) if (used(k)) total += call_memory::rounded(bufs[k].bytes);
+        char* at = nullptr;
+        HIPCHK(mem.get((void**)&at, total));
+        for (int k = 0; k < N_BUFS; ++k) if (used(k)) dev[k] = call_memory::take(at, bufs[k].bytes);
+        for (int k = 0; k < N_BUFS; ++k)
+            if (used(k) && bufs[k].input) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, stream));
+    }
+    auto fptr = [&](int k) { return static_cast<const float*>(dev[k]); };
+    auto iptr = [&](int k) { return static_cast<const int32_t*>(dev[k]); };
+    rp.color = fptr(COLOR); rp.depth = fptr(DEPTH); rp.alpha = fptr(ALPHA); rp.normal = fptr(NORMAL); rp.prim = iptr(PRIM);
+    rp.history = fptr(HISTORY); rp.history_len = fptr(HISTORY_LEN); rp.prev_depth = fptr(PREV_DEPTH); rp.prev_alpha = fptr(PREV_ALPHA);
+    rp.prev_normal = fptr(PREV_NORMAL); rp.prev_prim = iptr(PREV_PRIM);
+    rp.out = const_cast<float*>(fptr(OUT)); rp.out_len = const_cast<float*>(fptr(OUT_LEN)); rp.motion = const_cast<float*>(fptr(MOTION));
+    rp.nx = d->nx; rp.ny = d->ny;
+    rp.tiles_x = (d->nx + RT_REPROJECT_TILE - 1) / RT_REPROJECT_TILE;
+    for (int c = 0; c < 3; ++c) {
+        rp.origin[c] = d->cur.origin[c]; rp.lower_left[c] = d->cur.lower_left_corner[c];
+        rp.horizontal[c] = d->cur.horizontal[c]; rp.vertical[c] = d->cur.vertical[c];
+        rp.prev_origin[c] = d->prev.origin[c];
+    }
+    rp.alpha_min = d->alpha_min; rp.depth_tol = d->depth_tol; rp.normal_min = d->normal_min; rp.max_history = d->max_history;
+    HIPCHK(rt_launch_reproject(normals_on, ids_on, motion_on, rp, stream));
+    if (!buffers_on_device)
+        for (int k = OUT; k < N_BUFS; ++k) if (bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
+    if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
+    mem.settled();
+    return RT_OK;
 }
 
 // Tail hand-off of the last frame (diagnostics, every build): [0] pixels the main kernel handed to the tail launches, summed over

@@ -394,3 +394,31 @@ struct rt_aov_through_params {
 hipError_t rt_launch_aov_through(bool spheres_only, int tex_level, int lds_mode, const rt_scene_dev& sd, const rt_aov_params& ap,
                                  const rt_aov_through_params& tp, dim3 grid, size_t lds, hipStream_t st);
 hipError_t rt_aov_through_occupancy(bool spheres_only, int tex_level, int lds_mode, size_t lds, int* blocks_per_cu);
+
+// rt_reproject (rt_kernel_reproject.hip): the current frame blended into the reprojected history of the previous one
+// (include/rt_abi.h), one lane per pixel, the pointers already checked on the host.  All buffers are planar, as the callers of
+// rt_render_aov hold them.  history == null: the first frame (the four prev_* / history_len pointers are then not read).
+#define RT_REPROJECT_THREADS 256
+#define RT_REPROJECT_TILE 16
+struct rt_reproject_params {
+    const float* color;        // ny * nx * 3
+    const float* depth;        // ny * nx
+    const float* alpha;
+    const float* normal;       // ny * nx * 3; read iff the normal test is on
+    const int32_t* prim;       // read iff the id test is on
+    const float* history;      // ny * nx * 3 or null
+    const float* history_len;
+    const float* prev_depth;
+    const float* prev_alpha;
+    const float* prev_normal;
+    const int32_t* prev_prim;
+    float* out;                // ny * nx * 3
+    float* out_len;            // ny * nx
+    float* motion;             // ny * nx * 2; written iff the motion output is on
+    int32_t nx, ny, tiles_x, pad;
+    float origin[3], lower_left[3], horizontal[3], vertical[3];   // of the current camera
+    float prev_origin[3];
+    float m[9];                // rt_reproject_matrix of the previous camera
+    float alpha_min, depth_tol, normal_min, max_history;
+};
+hipError_t rt_launch_reproject(bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp, hipStream_t st);

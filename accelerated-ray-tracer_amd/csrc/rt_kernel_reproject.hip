@@ -1,0 +1,160 @@
+// rt_kernel_reproject.hip -- rt_reproject: the current frame blended into the reprojected history of the previous frame, as
+// include/rt_abi.h ("temporal reprojection") spells it out, gfx950.
+//
+// One kernel, one lane per pixel, workgroups of 256 threads on 16x16 pixel tiles.  Inside a tile the lanes run row-major
+// (lane & 15 across, four rows per wave): every planar access of a wave -- the pixel's own colour, depth, alpha, normal and
+// id, and the three outputs -- is then four runs of 16 consecutive pixels (64 B of a scalar plane, 192 B of an rgb plane),
+// and since a reprojection is locally close to a translation the four taps of those lanes fall on neighbouring runs of at
+// most six rows of the previous frame, which the next wave of the tile (four rows further up) mostly shares through L1/L2.
+// There is no LDS staging: where a tile's taps land is data (the depth), so a window cannot be fetched before it is known, and
+// the footprint of a tile is already about one tile of each plane.  Per pixel it reads up to 36 B of the current frame and
+// four taps of up to 40 B, and writes up to 24 B; what it waits for is the latency of two dependent memory phases (the pixel's
+// own data, then the taps), which is why the taps' loads are all issued before the first of them is looked at.
+// Specialised on (normal test, id test, motion output) so that a guide that is off costs neither loads nor registers.
+//
+// The arithmetic is the contract's, statement by statement (-ffp-contract=off: no FMA is formed).
+//
+// Bounds.  The pixel's own index is tested against the frame before any address is formed.  A tap address is formed only from
+// x0, y0 after the float comparisons -1 <= x0 <= nx - 1, -1 <= y0 <= ny - 1 (false for a NaN) have passed and after the tap's
+// integer coordinates have compared as inside the image (unsigned: -1 wraps and compares as outside).  Every plane of the
+// previous frame holds ny * nx pixels, so every load of a tap that is inside the image is inside its buffer, whatever the
+// other buffers hold; a tap outside the image reads at the pixel's own index instead and is not counted.  The loads of all
+// four taps are issued together, ahead of the tests that decide whether a tap counts.
+#include "rt_device.h"
+#include "rt_launch.h"
+
+namespace {
+
+constexpr int TILE = RT_REPROJECT_TILE;
+
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+template <bool NRM, bool IDS, bool MOT>
+__global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_reproject_params rp) {
+    const int tid = threadIdx.x;
+    const int nx = rp.nx, ny = rp.ny;
+    const unsigned by = blockIdx.x / (unsigned)rp.tiles_x, bx = blockIdx.x - by * (unsigned)rp.tiles_x;
+    const unsigned i = bx * TILE + (tid & (TILE - 1)), j = by * TILE + (tid / TILE);
+    if (i >= (unsigned)nx || j >= (unsigned)ny) return;
+    const size_t p = (size_t)j * nx + i;
+
+    const float cr = rp.color[3 * p], cg = rp.color[3 * p + 1], cb = rp.color[3 * p + 2];
+    const float al = rp.alpha[p], dep = rp.depth[p];
+    float npx = 0.f, npy = 0.f, npz = 0.f;
+    if (NRM) { npx = rp.normal[3 * p]; npy = rp.normal[3 * p + 1]; npz = rp.normal[3 * p + 2]; }
+    int32_t idp = 0;
+    if (IDS) idp = rp.prim[p];
+
+    // 1. the pixel's centre ray and its world point (or, for sky, its direction: a point at infinity)
+    const float fi = (float)(int)i, fj = (float)(int)j, fnx = (float)nx, fny = (float)ny;
+    const float s = (fi + 0.5f) / fnx, t = (fj + 0.5f) / fny;
+    float q[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = ((rp.lower_left[c] + s * rp.horizontal[c]) + t * rp.vertical[c]) - rp.origin[c];
+    const bool surface = al >= rp.alpha_min;
+    if (surface) {
+        const float z = dep / al;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float P = rp.origin[c] + z * q[c];
+            q[c] = P - rp.prev_origin[c];
+        }
+    }
+
+    // 2. into the previous camera
+    const float a = dot3(rp.m[0], rp.m[1], rp.m[2], q[0], q[1], q[2]);
+    const float b = dot3(rp.m[3], rp.m[4], rp.m[5], q[0], q[1], q[2]);
+    const float c = dot3(rp.m[6], rp.m[7], rp.m[8], q[0], q[1], q[2]);
+    float mx = 0.f, my = 0.f;
+    float W = 0.f, Cr = 0.f, Cg = 0.f, Cb = 0.f, L = 0.f;
+    if (a > 0.f) {
+        const float x = (b / a) * fnx - 0.5f, y = (c / a) * fny - 0.5f;
+        mx = x - fi;
+        my = y - fj;
+        const float x0 = floorf(x), y0 = floorf(y);
+        if (rp.history && x0 >= -1.f && x0 <= (float)(nx - 1) && y0 >= -1.f && y0 <= (float)(ny - 1)) {
+            // ((float)(n - 1) rounds up to 2^31 for the largest widths: the conversion stays defined and the tap is outside)
+            const int ix = x0 >= 2147483648.f ? 2147483647 : (int)x0, iy = y0 >= 2147483648.f ? 2147483647 : (int)y0;
+            const float fx = x - x0, fy = y - y0;
+            const float gx = 1.f - fx, gy = 1.f - fy;
+            const float w4[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+            // 3. the four taps.  Their loads are issued together, ahead of every test on what they return: one memory round
+            // trip per pixel, where load-test-load tap by tap takes four (measured 1.7 x slower).  A tap outside the image
+            // reads at the pixel's own index p instead (an address that depends on no data) and is not counted.
+            bool inside[4];
+            size_t o[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned qx = (unsigned)ix + (unsigned)(k & 1), qy = (unsigned)iy + (unsigned)(k >> 1);
+                inside[k] = qx < (unsigned)nx && qy < (unsigned)ny;
+                o[k] = inside[k] ? (size_t)qy * nx + qx : p;
+            }
+            float hl[4], pa[4], pd[4], hr[4], hg[4], hb[4], nqx[4] = {}, nqy[4] = {}, nqz[4] = {};
+            int32_t idq[4] = {};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                hl[k] = rp.history_len[o[k]]; pa[k] = rp.prev_alpha[o[k]]; pd[k] = rp.prev_depth[o[k]];
+                hr[k] = rp.history[3 * o[k]]; hg[k] = rp.history[3 * o[k] + 1]; hb[k] = rp.history[3 * o[k] + 2];
+                if (NRM) { nqx[k] = rp.prev_normal[3 * o[k]]; nqy[k] = rp.prev_normal[3 * o[k] + 1]; nqz[k] = rp.prev_normal[3 * o[k] + 2]; }
+                if (IDS) idq[k] = rp.prev_prim[o[k]];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                bool counts = inside[k] && hl[k] > 0.f;
+                if (surface) {
+                    const float zq = pd[k] / pa[k];
+                    counts = counts && pa[k] >= rp.alpha_min && fabsf(zq - a) <= rp.depth_tol * fmaxf(zq, a);
+                    if (NRM) counts = counts && dot3(npx, npy, npz, nqx[k], nqy[k], nqz[k]) >= rp.normal_min;
+                } else {
+                    counts = counts && pa[k] < rp.alpha_min;
+                }
+                if (IDS) counts = counts && idp == idq[k];
+                if (counts) {
+                    const float w = w4[k];
+                    W = W + w;
+                    Cr = Cr + w * hr[k];
+                    Cg = Cg + w * hg[k];
+                    Cb = Cb + w * hb[k];
+                    L = L + w * hl[k];
+                }
+            }
+        }
+    }
+
+    // 4. blend
+    float outr = cr, outg = cg, outb = cb, len = 1.f;
+    if (W > 0.f) {
+        const float hr = Cr / W, hg = Cg / W, hb = Cb / W;
+        const float n = fminf(L / W, rp.max_history);
+        len = n + 1.f;
+        const float g = 1.f / len;
+        outr = hr + (cr - hr) * g;
+        outg = hg + (cg - hg) * g;
+        outb = hb + (cb - hb) * g;
+    }
+    rp.out[3 * p] = outr;
+    rp.out[3 * p + 1] = outg;
+    rp.out[3 * p + 2] = outb;
+    rp.out_len[p] = len;
+    if (MOT) {
+        rp.motion[2 * p] = mx;
+        rp.motion[2 * p + 1] = my;
+    }
+}
+
+template <bool NRM, bool IDS, bool MOT>
+hipError_t launch(const rt_reproject_params& rp, hipStream_t st) {
+    const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
+    return rt_launch_kernel(rt_reproject_kernel<NRM, IDS, MOT>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp);
+}
+template <bool NRM, bool IDS>
+hipError_t launch_motion(bool motion_on, const rt_reproject_params& rp, hipStream_t st) {
+    return motion_on ? launch<NRM, IDS, true>(rp, st) : launch<NRM, IDS, false>(rp, st);
+}
+
+}  // namespace
+
+hipError_t rt_launch_reproject(bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp, hipStream_t st) {
+    if (normals_on) return ids_on ? launch_motion<true, true>(motion_on, rp, st) : launch_motion<true, false>(motion_on, rp, st);
+    return ids_on ? launch_motion<false, true>(motion_on, rp, st) : launch_motion<false, false>(motion_on, rp, st);
+}

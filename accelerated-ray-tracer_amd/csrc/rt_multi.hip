@@ -170,6 +170,17 @@ rt_status rt_multi_create(const rt_scene_desc* desc, int n_gpus, rt_multi** out)
 
 int32_t rt_multi_device_count(const rt_multi* m) { return m ? m->n : 0; }
 
+// rt_scene_set_camera on every replica (its checks run in the first of these calls, before any HIP call); device 0 last, so
+// that it stays the current device
+rt_status rt_multi_set_camera(rt_multi* m, const rt_camera* camera, int recalibrate) {
+    if (!m) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_set_camera: null rt_multi"); return RT_ERR_INVALID; }
+    for (int d = m->n - 1; d >= 0; --d) {
+        const rt_status st = rt_scene_set_camera(m->scenes[d], camera, recalibrate);
+        if (st != RT_OK) return st;
+    }
+    return RT_OK;
+}
+
 rt_status rt_multi_row_owner(int32_t global_row, int32_t tile_rows, int32_t n_gpus, int32_t* device, int32_t* local_row) {
     if (global_row < 0 || tile_rows <= 0 || n_gpus <= 0 || !device || !local_row) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_row_owner: bad argument"); return RT_ERR_INVALID; }
     int r, l;

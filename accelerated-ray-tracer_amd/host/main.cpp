@@ -9,6 +9,15 @@
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
 //             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K] [--denoise-variance [B]]] [--list]
 //             [--aov-through PREFIX] [--through-bounces N] [--through-fuzz F] [--denoise-through]
+//             [--orbit FRAMES DEGREES --out PREFIX [--temporal]]
+//
+// --orbit FRAMES DEGREES renders a turntable: FRAMES frames of one device scene, the scene's lookfrom rotated about the vertical
+// axis through its lookat in equal steps of DEGREES / FRAMES (frame k at k steps; every other camera argument kept), each
+// through rt_scene_set_camera -- one rt_scene_create for the whole sequence.  The images go to PREFIX_000.ppm, PREFIX_001.ppm,
+// ... (--out PREFIX is required; nothing is written to stdout).  With --temporal every image is the temporal accumulation of
+// the frames so far (rt_reproject with the binding's defaults, normals and ids on, guided by rt_render_aov at min(ns, 16)
+// samples): the frames are rendered at gamma 1 and the gamma is applied on the host afterwards, as --denoise does.  Not with
+// --gpus > 1, --progressive, --adaptive, --denoise, --aov or --aov-through.
 //
 // --denoise [K] filters the frame with rt_denoise (K iterations, 5 when K is left out; the binding's other defaults): the frame
 // is rendered at gamma 1, the feature pass (albedo, normal, depth at min(ns, 16) samples) guides the filter, and the frame's
@@ -59,6 +68,10 @@ int main(int argc, char** argv) {
     bool p6 = false, adaptive = false;
     float threshold = 0.f;
     int min_spp = 0, denoise = 0, batches = -1;   // batches: -1 = no --denoise-variance, 0 = B left out
+    int orbit_frames = 0;
+    double orbit_degrees = 0.0;
+    bool temporal = false;
+    std::string out_prefix;
     unsigned long long seed = 1984ull;
     for (int a = 1; a < argc; ++a) {
         std::string k = argv[a];
@@ -98,6 +111,13 @@ int main(int argc, char** argv) {
                 if (batches < 2 || batches > 64) { fprintf(stderr, "--denoise-variance B: B must be in 2..64\n"); return 2; }
             }
         }
+        else if (k == "--orbit") {
+            orbit_frames = atoi(val());
+            orbit_degrees = strtod(val(), nullptr);
+            if (orbit_frames < 1 || orbit_frames > 1000 || !std::isfinite(orbit_degrees)) { fprintf(stderr, "--orbit FRAMES DEGREES: FRAMES must be in 1..1000 and DEGREES finite\n"); return 2; }
+        }
+        else if (k == "--out") out_prefix = val();
+        else if (k == "--temporal") temporal = true;
         else if (k == "--list") { int n = 0; const char* const* v = rtw::scene_names(&n); for (int i = 0; i < n; ++i) printf("%s\n", v[i]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); return 2; }
     }
@@ -111,6 +131,12 @@ int main(int argc, char** argv) {
     if (batches >= 0 && !denoise) { fprintf(stderr, "--denoise-variance needs --denoise\n"); return 2; }
     if (batches >= 0 && adaptive) { fprintf(stderr, "--denoise-variance cannot be combined with --adaptive\n"); return 2; }
     if (min_spp > 0 && !adaptive) { fprintf(stderr, "--min-spp needs --adaptive\n"); return 2; }
+    if (orbit_frames > 0 && out_prefix.empty()) { fprintf(stderr, "--orbit needs --out PREFIX\n"); return 2; }
+    if (orbit_frames == 0 && (temporal || !out_prefix.empty())) { fprintf(stderr, "--temporal and --out need --orbit\n"); return 2; }
+    if (orbit_frames > 0 && (gpus > 1 || progressive > 0 || adaptive || denoise || !aov_prefix.empty() || !through_prefix.empty())) {
+        fprintf(stderr, "--orbit cannot be combined with --gpus > 1, --progressive, --adaptive, --denoise, --aov or --aov-through\n");
+        return 2;
+    }
 
     std::vector<unsigned char> tex;
     int tw = 0, th = 0;
@@ -151,6 +177,68 @@ int main(int argc, char** argv) {
     rt_stats stats;
     rt_scene* dev_scene = nullptr;
     rt_multi* multi = nullptr;
+    if (orbit_frames > 0) {
+        // a turntable of one device scene: a camera per frame (rt_scene_set_camera), optionally accumulated over time (rt_reproject)
+        const size_t px = (size_t)scene->nx * scene->ny;
+        check(rt_init(device), "rt_init");
+        check(rt_scene_create(&desc, &dev_scene), "rt_scene_create");
+        const rtw::camera& c0 = *scene->cam;
+        if (temporal) f.gamma = 1.0f;
+        struct features { std::vector<float> normal, depth, alpha; std::vector<int32_t> prim; };
+        features feat[2];
+        for (features& x : feat) { x.normal.resize(px * 3); x.depth.resize(px); x.alpha.resize(px); x.prim.resize(px); }
+        std::vector<float> acc[2] = {std::vector<float>(px * 3), std::vector<float>(px * 3)}, len[2] = {std::vector<float>(px), std::vector<float>(px)};
+        rt_camera prev_cam;
+        memset(&prev_cam, 0, sizeof(prev_cam));
+        double ms = 0.0;
+        for (int k = 0; k < orbit_frames; ++k) {
+            const double th = (double)k * orbit_degrees / (double)orbit_frames * 3.14159265358979323846 / 180.0;
+            const double dx = (double)c0.lookfrom.x() - c0.lookat.x(), dz = (double)c0.lookfrom.z() - c0.lookat.z();
+            const rtw::vec3 eye((float)(c0.lookat.x() + cos(th) * dx + sin(th) * dz), c0.lookfrom.y(), (float)(c0.lookat.z() - sin(th) * dx + cos(th) * dz));
+            const rt_camera cam = rtw::camera_desc(rtw::camera(eye, c0.lookat, c0.vup, c0.vfov, c0.aspect, c0.aperture, c0.focus_dist, c0.time0, c0.time1));
+            check(rt_scene_set_camera(dev_scene, &cam, /*recalibrate=*/0), "rt_scene_set_camera");
+            check(rt_render(dev_scene, &f, fb.data(), /*fb_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1, &stats), "rt_render");
+            ms += stats.ms_render;
+            if (temporal) {
+                features& cur = feat[k & 1];
+                const features& old = feat[(k + 1) & 1];
+                rt_frame_desc ff = f;
+                if (ff.ns > 16) ff.ns = 16;
+                rt_aov_desc aov;
+                memset(&aov, 0, sizeof(aov));
+                aov.normal = cur.normal.data(); aov.depth = cur.depth.data(); aov.alpha = cur.alpha.data(); aov.prim = cur.prim.data();
+                check(rt_render_aov(dev_scene, &ff, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
+                rt_reproject_desc rd;
+                memset(&rd, 0, sizeof(rd));
+                rd.nx = scene->nx; rd.ny = scene->ny; rd.cur = cam; rd.prev = k ? prev_cam : cam;
+                rd.color = fb.data(); rd.depth = cur.depth.data(); rd.alpha = cur.alpha.data();
+                if (k) {
+                    rd.normal = cur.normal.data(); rd.prim = cur.prim.data();
+                    rd.history = acc[(k + 1) & 1].data(); rd.history_len = len[(k + 1) & 1].data();
+                    rd.prev_depth = old.depth.data(); rd.prev_alpha = old.alpha.data(); rd.prev_normal = old.normal.data(); rd.prev_prim = old.prim.data();
+                }
+                rd.out = acc[k & 1].data(); rd.out_len = len[k & 1].data();
+                rd.alpha_min = 0.5f; rd.depth_tol = 0.05f; rd.normal_min = 0.5f; rd.max_history = 32.0f;   // the binding's REPROJECT_DEFAULTS
+                check(rt_reproject(&rd, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_reproject");
+                prev_cam = cam;
+                fb = acc[k & 1];
+                if (scene->gamma != 1.0f) for (float& c : fb) c = powf(c, 1.0f / scene->gamma);
+            }
+            char name[32];
+            snprintf(name, sizeof(name), "_%03d.ppm", k);
+            const std::string path = out_prefix + name;
+            FILE* out = fopen(path.c_str(), "wb");
+            if (!out) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+            if (p6) rtw::write_ppm_p6(out, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
+            else rtw::write_ppm_p3(out, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
+            fclose(out);
+            fprintf(stderr, "frame %d: %.3f ms -> %s\n", k, stats.ms_render, path.c_str());
+        }
+        fprintf(stderr, "took %g seconds.\n", ms * 1e-3);
+        check(rt_scene_destroy(dev_scene), "rt_scene_destroy");
+        check(rt_shutdown(), "rt_shutdown");
+        return 0;
+    }
     if (gpus > 1) {
         check(rt_init_devices(gpus), "rt_init_devices");
         check(rt_multi_create(&desc, gpus, &multi), "rt_multi_create");

@@ -137,6 +137,8 @@ bvh_node::bvh_node(hittable** objects, int start, int end) {
 // ------------------------------------------------------------------ camera
 // src/camera.cuh:59-78
 void camera::init(vec3 lookfrom, vec3 lookat, vec3 vup, float vfov, float aspect, float aperture, float focus_dist) {
+    this->lookfrom = lookfrom; this->lookat = lookat; this->vup = vup;
+    this->vfov = vfov; this->aspect = aspect; this->aperture = aperture; this->focus_dist = focus_dist;
     lens_radius = aperture * 0.5f;
     const float theta = vfov * 3.141592654f / 180.0f;
     const float half_height = tanf(theta * 0.5f);
@@ -403,13 +405,18 @@ rt_status flatten(const hittable* world, const camera& cam, flat_scene& out, std
     if (!world) { err = "null world"; return RT_ERR_INVALID; }
     f.emit(world);
     if (!f.ok) return RT_ERR_UNSUPPORTED;
-    rt_camera& c = out.camera;
+    out.camera = camera_desc(cam);
+    return RT_OK;
+}
+
+rt_camera camera_desc(const camera& cam) {
+    rt_camera c;
     memset(&c, 0, sizeof(c));
     put3(c.origin, cam.origin); put3(c.lower_left_corner, cam.lower_left_corner);
     put3(c.horizontal, cam.horizontal); put3(c.vertical, cam.vertical);
     put3(c.u, cam.u); put3(c.v, cam.v);
     c.lens_radius = cam.lens_radius; c.time0 = cam.time0; c.time1 = cam.time1;
-    return RT_OK;
+    return c;
 }
 
 }  // namespace rtw

@@ -340,6 +340,9 @@ public:
     vec3 origin, lower_left_corner, horizontal, vertical, u, v, w;
     float lens_radius;
     double time0, time1;
+    // the constructor's arguments, kept so that a caller can build the same camera from another place (rayTracer --orbit)
+    vec3 lookfrom, lookat, vup;
+    float vfov, aspect, aperture, focus_dist;
 private:
     void init(vec3 lookfrom, vec3 lookat, vec3 vup, float vfov, float aspect, float aperture, float focus_dist);
 };
@@ -368,6 +371,8 @@ struct flat_scene {
 // implement.
 rt_status flatten(const hittable* world, const camera& cam, flat_scene& out, std::string& err,
                   hittable* const* creation_order = nullptr, int count = 0);
+// the camera as the description carries it (what flatten puts into flat_scene::camera)
+rt_camera camera_desc(const camera& cam);
 
 // util.cuh:3-11
 vec3 random_in_unit_cube(int seed);

@@ -69,6 +69,17 @@ int rtw_write_ppm(const char* path, const float* fb, int nx, int ny, int flags) 
     return 0;
 }
 
+// camera.cuh:59-78 through the host camera class -- the reference's own float arithmetic -- into the ABI's rt_camera: the camera
+// a reference scene function would construct from these arguments (lookfrom, lookat, vup: three floats each)
+int rtw_camera_init(const float* lookfrom, const float* lookat, const float* vup, float vfov, float aspect, float aperture, float focus_dist,
+                    double t0, double t1, rt_camera* out) {
+    if (!lookfrom || !lookat || !vup || !out) return -1;
+    const rtw::camera cam(rtw::vec3(lookfrom[0], lookfrom[1], lookfrom[2]), rtw::vec3(lookat[0], lookat[1], lookat[2]),
+                          rtw::vec3(vup[0], vup[1], vup[2]), vfov, aspect, aperture, focus_dist, t0, t1);
+    *out = rtw::camera_desc(cam);
+    return 0;
+}
+
 int rtw_load_ppm(const char* path, unsigned char* out, int cap, int* w, int* h) {
     std::vector<unsigned char> px;
     if (!rtw::load_ppm(path, px, *w, *h)) return -1;

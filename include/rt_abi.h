@@ -588,6 +588,98 @@ typedef struct rt_denoise_variance_desc {
 } rt_denoise_variance_desc; /* 24 B */
 rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_variance_desc* vd, int buffers_on_device, void* stream, int blocking);
 
+/* ---- a camera per frame: another view of a scene that stays on the device ----
+ * rt_scene_create copies the description's camera into the scene; rt_scene_set_camera replaces it, so that a turntable or a
+ * viewport renders frame after frame without a second rt_scene_create (upload, tier data, calibration passes, regrouping and
+ * collapse search).  Every kernel receives the camera by value at its launch, so the change costs the device nothing.
+ *
+ * Contract.  From the call on, every frame entry -- rt_render, rt_render_window, rt_render_adaptive, rt_render_variance,
+ * rt_render_aov, rt_render_aov_through -- writes, bit for bit, what the same call writes on a scene made by rt_scene_create
+ * from the same description with this camera in it, and reports the same rays and samples.  rt_trace_rays and
+ * rt_radiance_rays do not read the camera.  The walk array, the tier data and the LDS plans are kept: any hierarchy over the
+ * same leaves in the same order gives the reference's results for any ray; the one the scene walks was
+ * chosen on the old camera's calibration frame and is merely no longer the measured optimum.
+ * recalibrate == 0 keeps the cost prior of the old camera (the per-pixel ray counts of the calibration frame, which order
+ * and split a ranked rt_render): it is then stale, which changes the schedule and never a pixel.  recalibrate != 0 renders
+ * the calibration frame again -- 4 spp, its aspect taken from the new camera, its node pass counts thrown away -- and keeps
+ * its costs: rt_debug_cal_cost returns the new grid.  A scene that kept no prior at creation gets none.
+ * A pending non-blocking rt_render of the scene is finished first.  A progressive state made before the change keeps working
+ * and its later windows use the new camera: what such a mixed accumulation means is the caller's business.
+ * A null scene or camera, a non-finite field (pad is not looked at) or time1 < time0 is RT_ERR_INVALID before any HIP call,
+ * and rt_last_error_detail() names the failed check.  rt_scene_get_camera returns the camera the next frame will use.
+ * rt_multi_set_camera does the same for every replica of an rt_multi. */
+rt_status rt_scene_set_camera(rt_scene* scene, const rt_camera* camera, int recalibrate);
+rt_status rt_scene_get_camera(const rt_scene* scene, rt_camera* out);
+
+/* ---- temporal reprojection: the current frame blended into the reprojected history of the previous one ----
+ * With a camera that moves, the samples of one frame can be reused in the next: rt_reproject finds, for every pixel of the
+ * current frame, where its surface point was in the previous frame (through the depth rt_render_aov writes and the two
+ * cameras), fetches the accumulated history there -- four taps, each checked against the previous frame's feature buffers --
+ * and blends the current frame in with weight 1 / (history length + 1).  Its outputs are the next call's history.  It takes no
+ * scene and runs on the device the last rt_init selected.
+ *
+ * The numerical contract.  All arithmetic is binary32 unless stated, every written operation is rounded once, nothing is
+ * contracted into an FMA, sums run left to right as written; only + - * /, floor, min, max, abs and comparisons occur
+ * (min and max return the other operand when one is a NaN).  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.  Images are whole
+ * unpartitioned frames of ny x nx pixels, row-major, row 0 at the bottom.
+ *   Matrix (rt_reproject_matrix; host, in double from the float fields of `prev`, uncontracted).  A = LL - O (lower_left_corner
+ *     - origin), H = horizontal, V = vertical;  cross(x, y) = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0);  r0 = H x V,
+ *     r1 = V x A, r2 = A x H;  D = (A0 r0_0 + A1 r0_1) + A2 r0_2;  M[k][c] = (float)(r_k[c] / D), m[3 k + c].  So for
+ *     q = a (A + s H + t V):  dot(M0, q) = a, dot(M1, q) = a s, dot(M2, q) = a t.  D == 0 or a non-finite M is RT_ERR_INVALID.
+ *     rt_reproject calls it for d->prev.
+ *   Pixel p = (i, j).
+ *   1. s = ((float)i + 0.5f) / (float)nx, t = ((float)j + 0.5f) / (float)ny;  dir.c = ((LL.c + s H.c) + t V.c) - O.c of `cur`,
+ *      per component (the centre ray: no lens offset).  surface = alpha[p] >= alpha_min.  Surface: z = depth[p] / alpha[p],
+ *      P.c = O.c + z dir.c, q.c = P.c - O'.c, O' the origin of `prev`.  Otherwise the pixel is sky, a point at infinity: q = dir.
+ *   2. a = dot(M0, q), b = dot(M1, q), c = dot(M2, q).  Unless a > 0 the pixel has no history.  x = (b / a) (float)nx - 0.5f,
+ *      y = (c / a) (float)ny - 0.5f;  x0 = floor(x), y0 = floor(y), fx = x - x0, fy = y - y0.  Unless x0 >= -1, x0 <= (float)(nx - 1),
+ *      y0 >= -1 and y0 <= (float)(ny - 1) the pixel has no history: float comparisons made before any conversion, so a NaN
+ *      ends here.
+ *   3. The taps q_k = (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), in this order, with the weights
+ *      (1 - fx) (1 - fy), fx (1 - fy), (1 - fx) fy, fx fy.  A tap counts iff it is inside the image, history_len[q] > 0, it
+ *      passes the geometry test -- surface pixel: prev_alpha[q] >= alpha_min and, with zq = prev_depth[q] / prev_alpha[q],
+ *      |zq - a| <= depth_tol max(zq, a);  sky pixel: prev_alpha[q] < alpha_min -- and, with normals on and on a surface pixel,
+ *      dot(normal[p], prev_normal[q]) >= normal_min, and, with ids on, prim[p] == prev_prim[q].  Each counting tap does
+ *      W = W + w, C.ch = C.ch + w history[q].ch, L = L + w history_len[q], all from 0.
+ *   4. W > 0: h = C / W per channel, n = min(L / W, max_history), out_len = n + 1, g = 1 / out_len,
+ *      out.ch = h.ch + (color.ch - h.ch) g.  No history, or a null `history` (the first frame): out = color, out_len = 1.
+ *      motion = (x - (float)i, y - (float)j) whenever step 2 produced x and y (a > 0), else (0, 0); it does not need a history.
+ * tests/reproject_expect.py restates this in NumPy; the device result equals it bit for bit.
+ * Limits.  The centre ray ignores the lens and the shutter: under defocus, or with moving spheres, the reprojection is
+ * approximate (the geometry test then rejects more).  depth and alpha must be rt_render_aov's; rt_render_aov_through's depth
+ * runs along a bent path and is not geometric.  Normals are on iff normal and prev_normal are both non-null, ids iff prim and
+ * prev_prim are.
+ * Memory safety.  No address depends on a value that has not passed the comparisons of steps 2 and 3; no value of any input
+ * makes the call fault.
+ *
+ * Parameters (anything else is RT_ERR_INVALID): nx, ny >= 1 and nx ny < 2^31; alpha_min in (0, 1]; depth_tol finite in [0, 1];
+ * normal_min finite in [-1, 1]; max_history finite in [1, 65536]; color, depth, alpha, out and out_len non-null; history_len,
+ * prev_depth and prev_alpha non-null iff history is; no output may overlap an input or another output where the host can see
+ * it.  Buffers, stream and blocking: rt_denoise's rules -- buffers_on_device != 0: device or managed memory of that device,
+ * 4-byte aligned, checked with hipPointerGetAttributes before anything is launched, the work enqueued on `stream` and waited
+ * for only with `blocking` != 0; buffers_on_device == 0: host memory staged in device memory of the call's own, and the call
+ * returns when the outputs are complete.  The argument checks run before any HIP call and rt_last_error_detail() names the one
+ * that failed.  No scene and no shared state: the call may run beside a pending non-blocking rt_render on another stream. */
+typedef struct rt_reproject_desc {
+    int32_t nx, ny;
+    rt_camera cur, prev;            /* cameras of the current and the previous frame */
+    const float* color;             /* ny*nx*3 current linear frame, required */
+    const float* depth, *alpha;     /* current rt_render_aov depth and alpha, required */
+    const float* normal;            /* current, ny*nx*3 or null */
+    const int32_t* prim;            /* current, or null */
+    const float* history;           /* ny*nx*3 previous OUTPUT of this call; null = first frame */
+    const float* history_len;       /* ny*nx previous out_len; required iff history */
+    const float* prev_depth, *prev_alpha;   /* required iff history */
+    const float* prev_normal;       /* used iff normal and prev_normal both non-null */
+    const int32_t* prev_prim;       /* used iff prim and prev_prim both non-null */
+    float* out;                     /* ny*nx*3 required */
+    float* out_len;                 /* ny*nx required */
+    float* motion;                  /* ny*nx*2 or null: (x - i, y - j), 0 where nothing was projected */
+    float alpha_min, depth_tol, normal_min, max_history;
+} rt_reproject_desc;
+rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* stream, int blocking);
+rt_status rt_reproject_matrix(const rt_camera* prev, float m[9]);   /* host only, no device */
+
 /* ---- several GPUs of one node from one host thread ----
  * The reference is single-GPU (one render<<<>>> launch, main.cu:707); these entry points are what its host function
  * would call to spread that launch over the N GPUs of a node: rt_init_devices(N) replaces rt_init, rt_multi_create /
@@ -608,6 +700,7 @@ rt_status rt_init_devices(int n_gpus);
 rt_status rt_multi_create(const rt_scene_desc* desc, int n_gpus, rt_multi** out);
 rt_status rt_multi_render(rt_multi* m, const rt_frame_desc* f, float* fb, int fb_on_device, int tile_rows, rt_stats* stats);
 rt_status rt_multi_destroy(rt_multi* m);
+rt_status rt_multi_set_camera(rt_multi* m, const rt_camera* camera, int recalibrate);   /* rt_scene_set_camera on every replica */
 int32_t rt_multi_device_count(const rt_multi* m);
 /* the row partition rt_multi_render uses: which device renders global row j and at which row of its compact buffer
  * (the inverse of rt_local_to_global_row for tile_first = device, tile_stride = n_gpus) */

@@ -1,0 +1,179 @@
+#!/usr/bin/env python3
+"""rt_reproject and rt_scene_set_camera on an MI355X.
+
+(a) rt_reproject at 1200 x 800 with every guide on (normals, ids, motion) and with none: the headline scene under two cameras
+    3 degrees apart, its 4-spp frames and feature buffers on the device.  Median of 20 calls between device events (device
+    tensors, nothing allocated or copied inside the window).  Yardsticks from the same process: one unstaged iteration of
+    rt_denoise at the same size (option denoise_lds = 0; the total at K = 2 minus the total at K = 1, i.e. without the pack
+    pass) -- 25 taps where this kernel has 4 -- and a device-to-device copy of the bytes a pixel of rt_reproject must move at
+    the least with every guide on (36 B of the current frame + 24 B written: a copy of 30 B per pixel reads 30 and writes 30).
+(b) What a stale cost prior costs: rt_render of the headline scene at 1200 x 800, 500 spp, after a 20 degree set_camera with
+    recalibrate 0 and with 1, against a scene created for that camera.  The three alternate, medians of `--frames` frames of
+    stats.ms_render each; set_camera's own host time (with and without recalibration) and rt_scene_create's beside them.
+--kernel-loop N instead enqueues N calls of rt_reproject with every guide, N with none and N of rt_denoise (K = 3, unstaged)
+and exits: the run to put under `rocprofv3 --kernel-trace --stats`, whose per-kernel averages are the device times -- between
+events a single call of either is dominated by the host side of the call (argument and pointer checks, the launch).
+--kernel-stats FILE reads that run's kernel_stats.csv and prints / appends the rows of the two kernels as one JSON line.
+One JSON line per measurement goes to stdout and, with --out, is appended to that file (profiles/reproject_mi355x.jsonl).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import accelerated_ray_tracer_amd as art  # noqa: E402
+
+EYE, LOOKAT = (13.0, 2.0, 3.0), (0.0, 0.0, 0.0)      # host/rtw_scenes.cpp, bouncing_spheres
+
+
+def orbited(degrees, nx, ny):
+    th = np.radians(degrees)
+    eye = (np.cos(th) * EYE[0] + np.sin(th) * EYE[2], EYE[1], -np.sin(th) * EYE[0] + np.cos(th) * EYE[2])
+    return art.make_camera(eye, LOOKAT, (0, 1, 0), 30.0, nx / ny, 0.1, float(np.linalg.norm(EYE)), 0.0, 1.0)
+
+
+def median_ms(fn, calls=20, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(calls):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return statistics.median(times), min(times), max(times)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nx", type=int, default=1200)
+    ap.add_argument("--ny", type=int, default=800)
+    ap.add_argument("--ns", type=int, default=500)
+    ap.add_argument("--frames", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-loop", type=int, default=0)
+    ap.add_argument("--kernel-stats", default=None)
+    args = ap.parse_args()
+    nx, ny = args.nx, args.ny
+    if args.kernel_stats:
+        import csv
+        rows = {}
+        with open(args.kernel_stats) as fh:
+            for r in csv.DictReader(fh):
+                name = r["Name"]
+                if "rt_reproject_kernel" in name or "rt_denoise_kernel" in name or "rt_denoise_pack_kernel" in name:
+                    rows[name.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")] = {
+                        "calls": int(r["Calls"]), "average_us": round(float(r["AverageNs"]) / 1e3, 3), "min_us": round(float(r["MinNs"]) / 1e3, 3),
+                        "max_us": round(float(r["MaxNs"]) / 1e3, 3)}
+        line = {"what": "device time per kernel (rocprofv3 --kernel-trace --stats)", "nx": nx, "ny": ny, "kernels": rows}
+        print(json.dumps(line))
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(json.dumps(line) + "\n")
+        return
+    art.init(0)
+    dev = torch.device("cuda", 0)
+    hs = art.HostScene("random_scene", nx, ny)
+    lines = []
+
+    # ---- (a) the kernel
+    ds = art.DeviceScene(hs)
+    f4 = hs.frame(nx=nx, ny=ny, ns=4, gamma=1.0)
+    cams = [orbited(0.0, nx, ny), orbited(3.0, nx, ny)]
+    host = []
+    for cam in cams:
+        ds.set_camera(cam)
+        color, _ = ds.render(f4)
+        host.append(dict(ds.render_aov(f4, ids=True), color=color))
+    t = [{k: torch.from_numpy(v).to(dev) for k, v in h.items()} for h in host]
+    first = art.reproject(t[0]["color"], t[0]["depth"], t[0]["alpha"], cams[0], cams[0])
+    out, out_len = torch.empty_like(first.out), torch.empty_like(first.length)
+    motion = torch.empty((ny, nx, 2), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    base = dict(history=first.out, history_len=first.length, prev_depth=t[0]["depth"], prev_alpha=t[0]["alpha"], out=out, out_len=out_len,
+                stream=stream, blocking=False)
+    guides = dict(normal=t[1]["normal"], prim=t[1]["prim"], prev_normal=t[0]["normal"], prev_prim=t[0]["prim"], motion=motion)
+    if args.kernel_loop:
+        ws = torch.empty(art.denoise_workspace_bytes(nx, ny), dtype=torch.uint8, device=dev)
+        art.set_option("denoise_lds", 0)
+        for _ in range(args.kernel_loop):
+            art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], **dict(base, **guides))
+            art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], **base)
+            art.denoise(t[1]["color"], t[1]["albedo"], t[1]["normal"], t[1]["depth"], out=out, workspace=ws, stream=stream, blocking=False,
+                        **dict(art.DENOISE_DEFAULTS, iterations=3))
+        torch.cuda.synchronize()
+        art.reset_options()
+        ds.close()
+        return
+    for name, kw, per_pixel in (("all_guides", dict(base, **guides), 30), ("no_guides", base, 22)):
+        ms = median_ms(lambda: art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], **kw))
+        src = torch.empty(nx * ny * per_pixel, dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(src)
+        copy = median_ms(lambda: dst.copy_(src))
+        found = float((out_len > 1).float().mean().item())
+        lines.append({"what": "rt_reproject", "config": name, "nx": nx, "ny": ny, "median_ms": round(ms[0], 4), "min_ms": round(ms[1], 4),
+                      "max_ms": round(ms[2], 4), "copy_ms": round(copy[0], 4), "copy_bytes_per_pixel_moved": 2 * per_pixel,
+                      "over_copy": round(ms[0] / copy[0], 2), "pixels_with_history": round(found, 4)})
+    art.set_option("denoise_lds", 0)
+    ws = torch.empty(art.denoise_workspace_bytes(nx, ny), dtype=torch.uint8, device=dev)
+    totals = [median_ms(lambda: art.denoise(t[1]["color"], t[1]["albedo"], t[1]["normal"], t[1]["depth"], out=out, workspace=ws, stream=stream,
+                                            blocking=False, **dict(art.DENOISE_DEFAULTS, iterations=k)))[0] for k in (1, 2, 3)]
+    art.reset_options()
+    lines.append({"what": "rt_denoise unstaged iteration", "nx": nx, "ny": ny, "totals_ms_K1_K2_K3": [round(x, 4) for x in totals],
+                  "iteration_ms_s2": round(totals[1] - totals[0], 4), "iteration_ms_s4": round(totals[2] - totals[1], 4),
+                  "reproject_all_guides_over_iteration_s2": round(lines[0]["median_ms"] / (totals[1] - totals[0]), 3)})
+    ds.close()
+
+    # ---- (b) the stale prior
+    cam = orbited(20.0, nx, ny)
+    moved = art.HostScene("random_scene", nx, ny)
+    moved.desc.camera = cam
+    t0 = time.perf_counter()
+    scenes = {"fresh": art.DeviceScene(moved)}
+    create_ms = (time.perf_counter() - t0) * 1e3
+    set_ms = {}
+    for name, recal in (("stale", False), ("recalibrated", True)):
+        scenes[name] = art.DeviceScene(hs)
+        t0 = time.perf_counter()
+        scenes[name].set_camera(cam, recalibrate=recal)
+        set_ms[name] = (time.perf_counter() - t0) * 1e3
+    f = hs.frame(nx=nx, ny=ny, ns=args.ns)
+    fb = torch.empty((ny, nx, 3), dtype=torch.float32, device=dev)
+    ms = {k: [] for k in scenes}
+    rays = {}
+    for it in range(args.frames + 1):           # the first round warms up
+        for name, s in scenes.items():
+            _, st = s.render(f, out=fb.data_ptr())
+            rays[name] = st.rays
+            if it:
+                ms[name].append(st.ms_render)
+    assert len(set(rays.values())) == 1, rays
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    lines.append({"what": "rt_render after a 20 degree set_camera", "scene": "random_scene", "nx": nx, "ny": ny, "ns": args.ns, "frames": args.frames,
+                  "median_ms": {k: round(v, 3) for k, v in med.items()}, "min_ms": {k: round(min(v), 3) for k, v in ms.items()},
+                  "max_ms": {k: round(max(v), 3) for k, v in ms.items()}, "stale_over_fresh": round(med["stale"] / med["fresh"], 4),
+                  "recalibrated_over_fresh": round(med["recalibrated"] / med["fresh"], 4), "rays": rays["fresh"],
+                  "host_ms": {"rt_scene_create": round(create_ms, 2), "set_camera": round(set_ms["stale"], 3),
+                              "set_camera_recalibrate": round(set_ms["recalibrated"], 3)}})
+    for s in scenes.values():
+        s.close()
+    for line in lines:
+        print(json.dumps(line))
+    if args.out:
+        with open(args.out, "a") as fh:
+            for line in lines:
+                fh.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
