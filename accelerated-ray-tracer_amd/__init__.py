@@ -114,6 +114,10 @@ class RtReprojectDesc(C.Structure):
                 ("alpha_min", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_float)]
 
 
+class RtSphereUpdate(C.Structure):
+    _fields_ = [("count", C.c_int32), ("first", C.c_int32), ("indices", C.c_void_p), ("spheres", C.c_void_p)]
+
+
 RT_TRACE_CLOSEST, RT_TRACE_ANY = 0, 1
 RT_PRIM_SPHERE, RT_PRIM_QUAD, RT_PRIM_BOX, RT_PRIM_INSTANCE, RT_PRIM_MEDIUM = range(5)
 
@@ -165,7 +169,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_plan_walk_array", "rt_regroup_leaves", "rt_trace_rays", "rt_render_adaptive",
                   "rt_radiance_rays", "rt_render_aov", "rt_render_aov_through", "rt_denoise_workspace_bytes", "rt_denoise", "rt_render_variance",
                   "rt_denoise_variance", "rt_scene_set_camera", "rt_scene_get_camera", "rt_multi_set_camera", "rt_reproject",
-                  "rt_reproject_matrix", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info"]
+                  "rt_reproject_matrix", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info",
+                  "rt_scene_update_spheres", "rt_scene_get_spheres", "rt_multi_update_spheres", "rt_refit_nodes", "rt_debug_scene_boxes"]
 
 _rt = None
 _host = None
@@ -255,6 +260,11 @@ def rt_lib():
         L.rt_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera), C.c_int]
         L.rt_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera)]
         L.rt_multi_set_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera), C.c_int]
+        L.rt_scene_update_spheres.argtypes = [C.c_void_p, C.POINTER(RtSphereUpdate), C.c_int, C.c_int, C.c_void_p]
+        L.rt_scene_get_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.rt_multi_update_spheres.argtypes = [C.c_void_p, C.POINTER(RtSphereUpdate), C.c_int]
+        L.rt_refit_nodes.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(RtSphereUpdate), C.c_void_p, C.c_void_p]
+        L.rt_debug_scene_boxes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_reproject.argtypes = [C.POINTER(RtReprojectDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_reproject_matrix.argtypes = [C.POINTER(RtCamera), C.POINTER(C.c_float)]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
@@ -649,6 +659,44 @@ def _chain_args(max_bounces, fuzz_limit):
     return int(max_bounces), fuzz_limit
 
 
+def _sphere_update(spheres, indices, first):
+    """An RtSphereUpdate over host records and what keeps its arrays alive.  ValueError for malformed arguments."""
+    if not isinstance(spheres, np.ndarray) or spheres.dtype != SPHERE_DTYPE or spheres.ndim != 1:
+        raise ValueError("spheres: a one-dimensional numpy array of SPHERE_DTYPE is expected")
+    rec = np.ascontiguousarray(spheres)
+    u = RtSphereUpdate()
+    u.count, u.first = len(rec), int(first)
+    u.spheres = rec.ctypes.data
+    idx = _update_indices(indices, len(rec), u)
+    return u, (rec, idx)
+
+
+def _update_indices(indices, count, u):
+    if indices is None:
+        return None
+    idx = np.asarray(indices)
+    if idx.ndim != 1 or len(idx) != count or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError(f"indices: {count} integers are expected, one per record")
+    if len(idx) and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+        raise ValueError("indices: sphere index out of range")
+    idx = np.ascontiguousarray(idx, np.int32)
+    u.indices = idx.ctypes.data
+    return idx
+
+
+def refit_nodes(desc: RtSceneDesc, spheres, indices=None, first: int = 0):
+    """rt_refit_nodes, host only: the description that DeviceScene.update_spheres(spheres, indices, first) is equivalent to.
+    Returns (nodes, spheres) of it as NODE_DTYPE / SPHERE_DTYPE arrays.  ValueError when the update is refused."""
+    u, keep = _sphere_update(spheres, indices, first)
+    nodes, out = np.zeros(desc.n_nodes, NODE_DTYPE), np.zeros(desc.n_spheres, SPHERE_DTYPE)
+    L = rt_lib()
+    st = L.rt_refit_nodes(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data)
+    if st == 1:
+        raise ValueError(L.rt_last_error_detail().decode())
+    _check(st, "rt_refit_nodes")
+    return nodes, out
+
+
 class DeviceScene:
     """rt_scene*: the flattened scene resident in HBM."""
 
@@ -676,6 +724,61 @@ class DeviceScene:
         c = RtCamera()
         _check(rt_lib().rt_scene_get_camera(self._p, C.byref(c)), "rt_scene_get_camera")
         return c
+
+    def update_spheres(self, spheres, indices=None, first: int = 0, recalibrate: bool = False, stream=None) -> None:
+        """New records for spheres of the scene as it stands on the device (rt_scene_update_spheres): record k replaces sphere
+        indices[k], or sphere first + k without indices; the boxes that depend on them are refit on the device and every
+        later frame and query is what a scene created from the changed description gives.  recalibrate=True also renders
+        the small calibration frame again for the cost prior; without it the prior stays, which costs time and never a pixel.
+
+        spheres: a numpy array of SPHERE_DTYPE -- copied to the device -- or a contiguous torch tensor of shape (count, 8)
+        with a 4-byte dtype on the scene's device, read in place: the eight words of rt_sphere per row (view the tensor as
+        int32 to set `mat`).  With a tensor the work is enqueued on `stream` (a torch.cuda.Stream; default: the current
+        stream); a `stream` other than the current one first waits for the current stream's work.  Either way the call returns
+        when the update is complete.  indices: integers, host memory always.  Malformed arguments, an index out of range or
+        given twice, a non-finite record, a material out of range and a sphere under an instance raise ValueError before
+        anything is launched; a bad record in a device tensor raises it after the others were applied."""
+        L = rt_lib()
+        if isinstance(spheres, np.ndarray):
+            if stream is not None:
+                raise ValueError("stream: only a device tensor is enqueued on a torch stream")
+            u, keep = _sphere_update(spheres, indices, first)
+            on_device, stream_p = 0, None
+        else:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if not isinstance(spheres, torch.Tensor):
+                raise ValueError("spheres: a numpy array of SPHERE_DTYPE or a torch tensor is expected")
+            if spheres.device != dev:
+                raise ValueError(f"spheres: tensor on {spheres.device}, the scene is on {dev}")
+            if spheres.ndim != 2 or spheres.shape[1] != 8 or spheres.element_size() != 4:
+                raise ValueError(f"spheres: shape {tuple(spheres.shape)} of {spheres.dtype}, expected (count, 8) of a 4-byte dtype")
+            if not spheres.is_contiguous():
+                raise ValueError("spheres: a contiguous tensor is expected (it is read in place)")
+            u = RtSphereUpdate()
+            u.count, u.first = int(spheres.shape[0]), int(first)
+            u.spheres = spheres.data_ptr() if u.count else None
+            keep = (spheres, _update_indices(indices, u.count, u))
+            if u.count == 0:
+                return
+            current = torch.cuda.current_stream(dev)
+            if stream is None:
+                stream = current
+            elif stream != current:
+                stream.wait_stream(current)
+                spheres.record_stream(stream)
+            on_device, stream_p = 1, C.c_void_p(stream.cuda_stream)
+        st = L.rt_scene_update_spheres(self._p, C.byref(u), on_device, 1 if recalibrate else 0, stream_p)
+        del keep
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_scene_update_spheres")
+
+    def spheres(self) -> np.ndarray:
+        """The sphere records the next frame uses (rt_scene_get_spheres): the description's, with every update applied."""
+        out = np.zeros(self.host.desc.n_spheres, SPHERE_DTYPE)
+        _check(rt_lib().rt_scene_get_spheres(self._p, out.ctypes.data, len(out)), "rt_scene_get_spheres")
+        return out
 
     def render(self, frame: RtFrameDesc, out=None, stream: int = 0, blocking: bool = True):
         """Render into `out`: a float32 numpy array (host) or an integer device pointer.  Returns (array|None, stats)."""
@@ -1241,6 +1344,16 @@ class MultiScene:
         if st == 1:
             raise ValueError(L.rt_last_error_detail().decode())
         _check(st, "rt_multi_set_camera")
+
+    def update_spheres(self, spheres, indices=None, first: int = 0, recalibrate: bool = False) -> None:
+        """DeviceScene.update_spheres with host records on every replica (rt_multi_update_spheres)."""
+        L = rt_lib()
+        u, keep = _sphere_update(spheres, indices, first)
+        st = L.rt_multi_update_spheres(self._p, C.byref(u), 1 if recalibrate else 0)
+        del keep
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_multi_update_spheres")
 
     def render(self, frame: RtFrameDesc, tile_rows: int = 4):
         """The whole frame as float32[ny][nx][3] in host memory, and the summed statistics."""

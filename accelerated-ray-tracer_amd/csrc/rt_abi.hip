@@ -1,7 +1,8 @@
 // rt_abi.hip -- implementation of include/rt_abi.h: device bookkeeping, scene
 // validation + upload, the walk-array planner, tier data and cost prior, frame
 // launch, statistics.  The kernels are in rt_kernel_pixel.hip, rt_staged_*.hip
-// (rt_kernel_staged.h), rt_tier_*.hip (rt_kernel_tier.h) and rt_rank.hip.
+// (rt_kernel_staged.h), rt_tier_*.hip (rt_kernel_tier.h), rt_rank.hip and, for
+// rt_scene_update_spheres, rt_kernel_refit.hip (host half: rt_refit_host.h).
 // There is no CPU render path here or anywhere else in the
 // library: without a HIP device every entry point fails with
 // RT_ERR_NO_DEVICE / RT_ERR_HIP.
@@ -19,6 +20,7 @@
 
 #include "../../include/rt_abi.h"
 #include "rt_device.h"
+#include "rt_refit_host.h"
 
 namespace {
 
@@ -223,6 +225,19 @@ struct rt_scene {
     // image in d_adapt_spp: 4 bytes per pixel either way)
     double* d_var_acc = nullptr;
     size_t var_capacity = 0;                     // in doubles: three per pixel
+    // rt_scene_update_spheres: the lookup tables of the refit kernels, built on the scene's first update from a
+    // read-back of the node arrays, so that a scene that never moves pays nothing; refit.block holds all of them
+    int32_t n_instances = 0, n_media = 0;        // of the description (rt_scene_dev carries neither)
+    struct refit_tables {
+        bool ready = false;
+        void* block = nullptr;                   // one allocation, cut into the arrays of `p`
+        rt_refit_params p;                       // the per-scene half of the kernels' argument, filled once
+        std::vector<char> instanced;             // per sphere: the child of an instance (kept from rt_scene_create, host only)
+        uint32_t epoch = 0;
+        int32_t* d_indices = nullptr;            // the update's index list and (host records) its records on the device
+        rt_sphere* d_records = nullptr;
+        size_t indices_capacity = 0, records_capacity = 0;
+    } refit;
 };
 
 // Progressive accumulation (rt_render_window): the parked pixels of one frame description between windows.
@@ -741,6 +756,7 @@ rt_status rt_scene_destroy(rt_scene* s) {
     if (s->d_rank) (void)hipFree(s->d_rank);
     if (s->d_handoff) (void)hipFree(s->d_handoff);
     if (s->d_cal_cost) (void)hipFree(s->d_cal_cost);
+    for (void* p : {s->refit.block, (void*)s->refit.d_indices, (void*)s->refit.d_records}) if (p) (void)hipFree(p);
     for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue,
                     (void*)s->d_adapt_spp, (void*)s->d_adapt_count, (void*)s->d_adapt_rank, (void*)s->d_var_acc})
         if (p) (void)hipFree(p);
@@ -1097,6 +1113,8 @@ rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_sce
     s->dev.bound_pad = 0.0f;
     s->dev.nodes = s->dev.nodes_ref; s->dev.n_nodes = d->n_nodes;     // until the walk array is built below
     s->dev.n_spheres = d->n_spheres;
+    s->n_instances = d->n_instances; s->n_media = d->n_media;
+    s->refit.instanced = rt_refit::instanced_spheres(d->instances, d->n_instances, d->n_spheres);   // (host only: an update's checks need no HIP call)
     s->dev.n_materials = d->n_materials; s->dev.n_textures = d->n_textures;
     s->shade_bytes = (size_t)d->n_materials * sizeof(rt_material) + (size_t)d->n_textures * sizeof(rt_texture);
     s->dev.camera = d->camera;
@@ -1363,6 +1381,199 @@ rt_status plan_resident(const rt_scene* s, size_t node_bytes, int option, long l
     return RT_OK;
 }
 }  // namespace
+
+// ---- rt_scene_update_spheres (include/rt_abi.h).  Nothing of the scene's topology changes: the kernels of
+// rt_kernel_refit.hip store the records and recompute, where they live, the boxes that depend on them.
+namespace {
+// The lookup tables, once per scene: the node arrays are read back (the device holds the only copy of the walk array) and every
+// node's subtree -- nodes [i, skip[i]) of a depth-first array -- becomes a range of leaf ordinals.
+rt_status build_refit_tables(rt_scene* s) {
+    rt_scene::refit_tables& t = s->refit;
+    if (t.ready) return RT_OK;
+    const bool own_walk = s->dev.nodes != s->dev.nodes_ref;
+    const int n_ref = s->dev.n_nodes_ref, n_walk = own_walk ? s->dev.n_nodes : 0, n_spheres = s->dev.n_spheres;
+    std::vector<rt_node> ref((size_t)n_ref), walk((size_t)n_walk);
+    std::vector<rt_medium> media((size_t)s->n_media);
+    if (n_ref) HIPCHK(hipMemcpy(ref.data(), s->dev.nodes_ref, ref.size() * sizeof(rt_node), hipMemcpyDeviceToHost));
+    if (n_walk) HIPCHK(hipMemcpy(walk.data(), s->dev.nodes, walk.size() * sizeof(rt_node), hipMemcpyDeviceToHost));
+    if (s->n_media) HIPCHK(hipMemcpy(media.data(), s->dev.media, media.size() * sizeof(rt_medium), hipMemcpyDeviceToHost));
+
+    // leaves by ordinal, and one job per interior node: (node, first leaf, end leaf, array)
+    std::vector<int32_t> leaf_sphere, leaf_node_ref, leaf_node_walk;
+    std::vector<float> box_lo, box_hi;
+    std::vector<int4> jobs;
+    auto scan = [&](const std::vector<rt_node>& nodes, int which, std::vector<int32_t>& leaf_node) -> bool {
+        const int n = (int)nodes.size();
+        std::vector<int32_t> before((size_t)n + 1, 0);             // leaves among nodes [0, i)
+        for (int i = 0; i < n; ++i) before[(size_t)i + 1] = before[(size_t)i] + (nodes[i].prim >= 0 ? 1 : 0);
+        for (int i = 0; i < n; ++i) {
+            const int skip = RT_NODE_SKIP(nodes[i].skip);
+            if (skip <= i || skip > n) return false;
+            if (nodes[i].prim >= 0) leaf_node.push_back(i);
+            else jobs.push_back(make_int4(i, before[(size_t)i], before[(size_t)skip], which));
+        }
+        return true;
+    };
+    if (!scan(ref, 0, leaf_node_ref) || !scan(walk, 1, leaf_node_walk)) return invalid("rt_scene_update_spheres: the scene's node links are damaged");
+    const int m = (int)leaf_node_ref.size();
+    if (own_walk && (int)leaf_node_walk.size() != m) return invalid("rt_scene_update_spheres: the walk array does not hold the reference tree's leaves");
+    if (s->dev.leaf_lo && s->dev.n_leaves != m) return invalid("rt_scene_update_spheres: the tier data do not hold the reference tree's leaves");
+    const int slots = (m + 63) / 64;
+    leaf_sphere.assign((size_t)m, -1);
+    box_lo.assign((size_t)slots * 64 * 4, 0.0f); box_hi.assign((size_t)slots * 64 * 4, 0.0f);
+    for (int q = 0; q < m; ++q) {
+        const rt_node& n = ref[(size_t)leaf_node_ref[(size_t)q]];
+        if (own_walk && walk[(size_t)leaf_node_walk[(size_t)q]].prim != n.prim) return invalid("rt_scene_update_spheres: the walk array's leaves are not in the reference tree's order");
+        leaf_sphere[(size_t)q] = rt_refit::leaf_sphere(n.prim, media.data(), s->n_media, n_spheres);
+        for (int c = 0; c < 3; ++c) { box_lo[(size_t)q * 4 + c] = n.bmin[c]; box_hi[(size_t)q * 4 + c] = n.bmax[c]; }
+    }
+    if (!own_walk) leaf_node_walk.clear();
+
+    // one block, every piece 256-byte aligned: stamps, the three leaf tables, the canonical boxes, slot unions and maxima, jobs, result
+    const bool tier = s->dev.slot_ranges != nullptr;
+    struct piece { size_t bytes; const void* src; void** dst; };
+    uint32_t* stamp = nullptr; int32_t *d_ls = nullptr, *d_lr = nullptr, *d_lw = nullptr; float4 *d_lo = nullptr, *d_hi = nullptr;
+    float *d_slot = nullptr, *d_abs = nullptr, *d_result = nullptr; int4* d_jobs = nullptr;
+    const piece pieces[] = {
+        {(size_t)n_spheres * 4, nullptr, (void**)&stamp},
+        {leaf_sphere.size() * 4, leaf_sphere.data(), (void**)&d_ls},
+        {leaf_node_ref.size() * 4, leaf_node_ref.data(), (void**)&d_lr},
+        {leaf_node_walk.size() * 4, leaf_node_walk.data(), (void**)&d_lw},
+        {box_lo.size() * 4, box_lo.data(), (void**)&d_lo},
+        {box_hi.size() * 4, box_hi.data(), (void**)&d_hi},
+        {tier ? 0 : (size_t)slots * 32, nullptr, (void**)&d_slot},
+        {(size_t)slots * 16, nullptr, (void**)&d_abs},
+        {jobs.size() * sizeof(int4), jobs.data(), (void**)&d_jobs},
+        {16, nullptr, (void**)&d_result},
+    };
+    size_t total = 0;
+    for (const piece& pc : pieces) total += call_memory::rounded(pc.bytes ? pc.bytes : 1);
+    void* block = nullptr;
+    HIPCHK(hipMalloc(&block, total));
+    hipError_t e = hipMemset(block, 0, total);                         // stamps 0 (epochs start at 1), padding boxes 0
+    char* at = static_cast<char*>(block);
+    for (const piece& pc : pieces) {
+        *pc.dst = call_memory::take(at, pc.bytes ? pc.bytes : 1);
+        if (e == hipSuccess && pc.src && pc.bytes) e = hipMemcpy(*pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { (void)hipFree(block); HIPCHK(e); }
+    t.block = block;
+    rt_refit_params& p = t.p;
+    memset(&p, 0, sizeof(p));
+    p.n_materials = s->dev.n_materials;
+    p.stamp = stamp; p.spheres = const_cast<rt_sphere*>(s->dev.spheres);
+    p.n_leaves = m; p.n_slots = slots;
+    p.leaf_sphere = d_ls; p.leaf_node_ref = d_lr; p.leaf_node_walk = d_lw;
+    p.box_lo = d_lo; p.box_hi = d_hi;
+    p.tier_lo = const_cast<float4*>(s->dev.leaf_lo); p.tier_hi = const_cast<float4*>(s->dev.leaf_hi);
+    p.nodes_ref = const_cast<rt_node*>(s->dev.nodes_ref);
+    p.nodes_walk = own_walk ? const_cast<rt_node*>(s->dev.nodes) : nullptr;
+    p.slot_box = tier ? const_cast<float*>(s->dev.slot_ranges) : d_slot;
+    p.slot_abs = d_abs;
+    p.jobs = d_jobs; p.n_jobs = (int32_t)jobs.size();
+    p.result = d_result;
+    t.ready = true;
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_scene_update_spheres(rt_scene* s, const rt_sphere_update* u, int spheres_on_device, int recalibrate, void* stream_v) {
+    const std::string who = "rt_scene_update_spheres: ";
+    if (!s) return invalid((who + "null scene").c_str());
+    if (!u) return invalid((who + "null update").c_str());
+    if (u->count < 0) return invalid((who + "count is negative").c_str());
+    if (u->count > 0 && !u->spheres) return invalid((who + "null sphere records").c_str());
+    rt_scene::refit_tables& t = s->refit;
+    const std::string why = rt_refit::check_update(u, !spheres_on_device, s->dev.n_spheres, s->dev.n_materials, t.instanced);
+    if (!why.empty()) return invalid((who + why).c_str());
+    if (u->count == 0) return RT_OK;
+    RT_TRY(use_device(s->device));
+    RT_TRY(build_refit_tables(s));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (spheres_on_device) {
+        const traced_ptr records[] = {{u->spheres, (size_t)u->count * sizeof(rt_sphere), "spheres", 4}};
+        RT_TRY(check_trace_ptrs(records, s->device, "rt_scene_update_spheres"));
+    }
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
+    rt_refit_params p = t.p;
+    p.count = u->count; p.first = u->first;
+    if (++t.epoch == 0) { HIPCHK(hipMemsetAsync(p.stamp, 0, (size_t)s->dev.n_spheres * 4, stream)); t.epoch = 1; }
+    p.epoch = t.epoch;
+    if (u->indices) {
+        RT_TRY(grow(t.d_indices, t.indices_capacity, (size_t)u->count));
+        HIPCHK(hipMemcpyAsync(t.d_indices, u->indices, (size_t)u->count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        p.indices = t.d_indices;
+    }
+    if (spheres_on_device) p.records = u->spheres;
+    else {
+        RT_TRY(grow(t.d_records, t.records_capacity, (size_t)u->count));
+        HIPCHK(hipMemcpyAsync(t.d_records, u->spheres, (size_t)u->count * sizeof(rt_sphere), hipMemcpyHostToDevice, stream));
+        p.records = t.d_records;
+    }
+    HIPCHK(hipMemsetAsync(p.result, 0, 16, stream));
+    HIPCHK(rt_launch_refit(p, stream));
+    float result[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    HIPCHK(hipMemcpyAsync(result, p.result, sizeof(result), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int c = 0; c < 3; ++c) s->dev.bound[c] = result[c];
+    uint32_t refused = 0;
+    memcpy(&refused, &result[3], 4);
+    if (recalibrate && s->d_cal_cost) {   // as rt_scene_set_camera: the cost half of the calibration alone
+        std::vector<double> pass;
+        double rays = 0.0;
+        RT_TRY(measure_pass_counts(s, s->dev.nodes_ref, s->dev.n_nodes_ref, pass, rays, nullptr, 0, /*keep_cost=*/true));
+    }
+    if (refused) return invalid((who + "a device-resident record has a non-finite field or a material out of range; it was not stored, every other record was").c_str());
+    return RT_OK;
+}
+
+rt_status rt_scene_get_spheres(const rt_scene* s, rt_sphere* out, int32_t cap) {
+    if (!s) return invalid("rt_scene_get_spheres: null scene");
+    if (!out) return invalid("rt_scene_get_spheres: null output pointer");
+    if (cap < s->dev.n_spheres) return invalid("rt_scene_get_spheres: cap is below the scene's sphere count");
+    RT_TRY(use_device(s->device));
+    if (s->dev.n_spheres) HIPCHK(hipMemcpy(out, s->dev.spheres, (size_t)s->dev.n_spheres * sizeof(rt_sphere), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status rt_refit_nodes(const rt_scene_desc* d, const rt_sphere_update* u, rt_node* nodes_out, rt_sphere* spheres_out) {
+    bool so = false, uv = false;
+    int tx = 0;
+    RT_TRY(validate(d, so, tx, uv));
+    const std::string why = rt_refit::check_update(u, true, d->n_spheres, d->n_materials, rt_refit::instanced_spheres(d->instances, d->n_instances, d->n_spheres));
+    if (!why.empty()) return invalid(("rt_refit_nodes: " + why).c_str());
+    std::vector<rt_sphere> spheres(d->spheres, d->spheres + d->n_spheres);
+    std::vector<char> moved((size_t)d->n_spheres, 0);
+    for (int32_t k = 0; k < u->count; ++k) {
+        const int32_t i = u->indices ? u->indices[k] : u->first + k;
+        spheres[(size_t)i] = u->spheres[k];
+        moved[(size_t)i] = 1;
+    }
+    if (nodes_out) {
+        std::vector<rt_node> nodes(d->nodes, d->nodes + d->n_nodes);
+        rt_refit::refit_nodes(nodes.data(), d->n_nodes, spheres.data(), d->n_spheres, d->media, d->n_media, moved);
+        if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
+    }
+    if (spheres_out && d->n_spheres) memcpy(spheres_out, spheres.data(), spheres.size() * sizeof(rt_sphere));
+    return RT_OK;
+}
+
+rt_status rt_debug_scene_boxes(const rt_scene* s, int32_t which, void* out, size_t cap, size_t* n) {
+    if (!s || !n || which < 0 || which > 5) return invalid("rt_debug_scene_boxes: bad argument");
+    const void* src = nullptr;
+    size_t bytes = 0;
+    if (which == 0) { src = s->dev.nodes_ref; bytes = (size_t)s->dev.n_nodes_ref * sizeof(rt_node); }
+    else if (which == 1) { src = s->dev.nodes; bytes = (size_t)s->dev.n_nodes * sizeof(rt_node); }
+    else if (which == 2 || which == 3) { src = which == 2 ? s->dev.leaf_lo : s->dev.leaf_hi; bytes = src ? (size_t)s->dev.n_slots * 64 * sizeof(float4) : 0; }
+    else if (which == 4) { src = s->dev.slot_ranges; bytes = src ? (size_t)s->dev.n_slots * 32 : 0; }
+    *n = which == 5 ? 12 : bytes;
+    const size_t take = std::min(*n, cap);
+    if (!out || take == 0) return RT_OK;
+    if (which == 5) { memcpy(out, s->dev.bound, take); return RT_OK; }
+    RT_TRY(use_device(s->device));
+    HIPCHK(hipMemcpy(out, src, take, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
 
 rt_status rt_trace_rays(rt_scene* s, const rt_ray_batch* b, void* stream_v, int blocking) {
     // argument checks: no HIP call and no look at the scene before they pass

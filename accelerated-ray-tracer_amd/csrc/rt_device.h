@@ -422,3 +422,36 @@ struct rt_reproject_params {
     float alpha_min, depth_tol, normal_min, max_history;
 };
 hipError_t rt_launch_reproject(bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp, hipStream_t st);
+
+// rt_scene_update_spheres (rt_kernel_refit.hip; include/rt_abi.h): the moved spheres' records, their leaves'
+// boxes in every array that holds them, the per-64-leaf unions, the scene's coordinate bound and every interior box of both
+// node arrays, as four small launches on one stream.  The lookup tables are built by rt_abi.hip on a scene's first update.
+#define RT_REFIT_THREADS 256
+struct rt_refit_params {
+    // the update: record k replaces sphere indices[k] (indices null: first + k); the indices were checked on the host
+    const rt_sphere* records;
+    const int32_t* indices;
+    int32_t count, first;
+    int32_t n_materials;
+    uint32_t epoch;                       // stamp[i] == epoch: sphere i was replaced by this update
+    uint32_t* stamp;                      // per sphere
+    rt_sphere* spheres;                   // the scene's (rt_scene_dev.spheres)
+    // the leaves, by ordinal q (depth-first order, the same in both node arrays)
+    int32_t n_leaves, n_slots;
+    const int32_t* leaf_sphere;           // the sphere leaf q's box follows, or -1
+    const int32_t* leaf_node_ref;         // leaf q's index in nodes_ref ...
+    const int32_t* leaf_node_walk;        // ... and in the walk array
+    float4* box_lo;                       // canonical leaf boxes, padded to whole slots (padding: zeros, in no union)
+    float4* box_hi;
+    float4* tier_lo;                      // rt_scene_dev.leaf_lo / leaf_hi, or null: xyz follow, .w is not written
+    float4* tier_hi;
+    rt_node* nodes_ref;
+    rt_node* nodes_walk;                  // null when the scene walks nodes_ref itself
+    float* slot_box;                      // per slot 8 floats: lo, hi, 0, 0 (rt_scene_dev.slot_ranges when the scene has tier data)
+    float* slot_abs;                      // per slot 4 floats: max(|lo|, |hi|) per axis over its leaves
+    // one job per interior node of either array: (node index, first leaf, end leaf, 0 = nodes_ref / 1 = walk array)
+    const int4* jobs;
+    int32_t n_jobs;
+    float* result;                        // [0..2] the scene's bound, [3] (as uint32) != 0: a record was refused on the device
+};
+hipError_t rt_launch_refit(const rt_refit_params& p, hipStream_t st);

@@ -124,8 +124,11 @@ DEV bool sphere_test(const rt_sphere& s, const Ray& r, float tmin, float tmax, f
 }
 
 // A record whose address is the same in every lane (scan mode, tier loops), read through the constant address space:
-// the scene arrays are written by the host before the launch and never by a kernel, so the load may go through the
-// scalar cache into SGPRs (s_load_dwordx*) instead of 64 identical vector loads.
+// no kernel that reads the scene arrays this way runs while they are written, so the load may go through the scalar
+// cache into SGPRs (s_load_dwordx*) instead of 64 identical vector loads.  The arrays are written by the host before the
+// first launch and, since rt_scene_update_spheres, by the refit kernels (rt_kernel_refit.hip): separate dispatches with
+// vector stores that complete before any reader starts, and the scalar cache does not outlive a dispatch
+// (tests/test_update_spheres.py renders scenes scanned this way after an update).
 template <typename T>
 DEV T uniform_load(const T* p) {
     static_assert(sizeof(T) % 4 == 0, "records are whole dwords");

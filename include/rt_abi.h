@@ -611,6 +611,69 @@ rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_varianc
 rt_status rt_scene_set_camera(rt_scene* scene, const rt_camera* camera, int recalibrate);
 rt_status rt_scene_get_camera(const rt_scene* scene, rt_camera* out);
 
+/* ---- moving spheres: new sphere records for a scene that stays on the device ----
+ * rt_scene_update_spheres replaces sphere records of a resident scene and refits every box that depends on them, on the device,
+ * so that a simulation, a turntable with a moving light or an editor dragging a sphere renders step after step without a second
+ * rt_scene_create (upload, three tree builds, four calibration passes, the collapse search).
+ *
+ * The update.  Record k of `spheres` replaces sphere indices[k], or sphere first + k when indices is null.  indices is host
+ * memory always; spheres is host memory, or, with spheres_on_device != 0, device (or managed) memory of the scene's device (the
+ * positions of a simulation that lives there; nothing is copied).  count == 0 is a successful no-op.
+ *
+ * Contract.  Let D' be the scene's description with those records replaced and its node boxes refit as below.  From the call on,
+ * every frame entry -- rt_render, rt_render_window, rt_render_adaptive, rt_render_variance, rt_render_aov,
+ * rt_render_aov_through -- and both query entries -- rt_trace_rays, rt_radiance_rays -- write, bit for bit, what they write on
+ * rt_scene_create(D'), and report the same rays and samples.  The topology of every array on the device is kept: any hierarchy
+ * over the same leaves in the same order gives the reference's results for any ray as long as every interior box contains the
+ * boxes below it.
+ *   Leaves that change.  A leaf is recomputed when its primitive is an updated sphere, or a constant_medium whose boundary is an
+ *     updated sphere directly.  Every other leaf keeps its box, whatever rule made it.
+ *   Box rule, as ordered binary32 operations, each rounded once, per axis:  r = |radius|,  a = c0 + 0 vel,  b = c0 + 1 vel,
+ *     lo = min(a - r, b - r),  hi = max(a + r, b + r).  For radius >= 0 this is, value for value, the box the host library's
+ *     sphere constructors give (the reference's sphere.cuh:21-38); for a negative radius it is a box that contains the shell.
+ *   Refit.  Every interior node of the reference's tree and of the walk array becomes the float min / max union of the leaf boxes
+ *     in its subtree; the tier data follow (leaf boxes and the per-64-leaf unions; padding leaves stay zero and take part in no
+ *     union).  The scene's coordinate bound becomes, per axis, the maximum over all leaves of max(|bmin|, |bmax|) -- what
+ *     rt_scene_create(D') computes; it may shrink.  The link words of a node (skip, prim) are never written.  Float min / max are
+ *     exact, so boxes do not depend on the order of any reduction (up to the sign of a zero).
+ *   What goes stale.  The walk array's choice of interior nodes and the cost prior were measured on the old positions; that
+ *     changes time and never a pixel.  recalibrate != 0 redoes the cost half of the calibration exactly as rt_scene_set_camera
+ *     does (the calibration frame at 4 spp, its per-pixel costs kept).
+ * A pending non-blocking rt_render of the scene is finished first.  Progressive states behave as after a camera change: later
+ * windows see the new spheres.  The work -- four small launches -- is enqueued on `stream` (a hipStream_t, 0 = default stream),
+ * after whatever the stream already holds; other streams still reading the scene are the caller's to order.  The call is
+ * SYNCHRONOUS: it returns after the work has completed, because it reads 16 bytes back (the new bound and the flag below).
+ *
+ * Refusals.  Each of these is RT_ERR_INVALID before any HIP call, with rt_last_error_detail() naming the check, and leaves the
+ * scene untouched: a null scene, update or record array; count < 0; an index out of range; an index that appears twice; with
+ * host records, a non-finite c0, vel or radius, or a mat outside the scene's materials; an updated sphere that is the child
+ * of an instance -- reached as leaf -> instance or medium -> instance: the box rule of an instance (its rotated, translated
+ * child box) is not redone here, so such a sphere cannot move yet while direct spheres and sphere-bounded media can.
+ * Device-resident records cannot be checked on the host: the kernel that stores them checks each, stores nothing for a record
+ * with a non-finite field or a bad mat and raises a flag that is read back with the bound; the call then returns RT_ERR_INVALID
+ * with every record that passed applied and every box and union consistent with the spheres actually stored.  No address
+ * depends on record data; the only data-derived addresses come from `indices`, which the host has checked.
+ *
+ * rt_scene_get_spheres copies the records the next frame will use to `out` (host memory, cap >= the scene's sphere count, else
+ * RT_ERR_INVALID).  rt_multi_update_spheres applies host records to every replica of an rt_multi.
+ * rt_refit_nodes is the host-only statement of D' (no device needed): nodes_out receives desc->n_nodes nodes -- the
+ * description's with the leaves above recomputed and every interior box refit --, spheres_out desc->n_spheres records; either
+ * may be null.  It makes rt_scene_create's checks of `desc` and the refusals above, and writes nothing when it refuses.
+ * rt_debug_scene_boxes (tests): a device array of the scene as it stands, copied to host memory -- which = 0 the reference's
+ * tree, 1 the walk array (both in the device's link encoding: skip holds ~skip, an interior prim ~(index + 1)), 2 / 3 the tier
+ * leaf arrays, 4 the per-64-leaf unions (8 floats each), 5 the bound (3 floats).  *n = its bytes (0: the scene has none); at
+ * most cap bytes are written. */
+typedef struct rt_sphere_update {
+    int32_t count;             /* records in `spheres` */
+    int32_t first;             /* used when indices == NULL: record k replaces sphere first + k */
+    const int32_t* indices;    /* or NULL; host memory always; each index at most once */
+    const rt_sphere* spheres;  /* host memory, or device memory when spheres_on_device != 0 */
+} rt_sphere_update; /* 24 B */
+rt_status rt_scene_update_spheres(rt_scene* scene, const rt_sphere_update* update, int spheres_on_device, int recalibrate, void* stream);
+rt_status rt_scene_get_spheres(const rt_scene* scene, rt_sphere* out, int32_t cap);
+rt_status rt_refit_nodes(const rt_scene_desc* desc, const rt_sphere_update* update, rt_node* nodes_out, rt_sphere* spheres_out);   /* host only, no device */
+rt_status rt_debug_scene_boxes(const rt_scene* scene, int32_t which, void* out, size_t cap, size_t* n);
+
 /* ---- temporal reprojection: the current frame blended into the reprojected history of the previous one ----
  * With a camera that moves, the samples of one frame can be reused in the next: rt_reproject finds, for every pixel of the
  * current frame, where its surface point was in the previous frame (through the depth rt_render_aov writes and the two
@@ -701,6 +764,7 @@ rt_status rt_multi_create(const rt_scene_desc* desc, int n_gpus, rt_multi** out)
 rt_status rt_multi_render(rt_multi* m, const rt_frame_desc* f, float* fb, int fb_on_device, int tile_rows, rt_stats* stats);
 rt_status rt_multi_destroy(rt_multi* m);
 rt_status rt_multi_set_camera(rt_multi* m, const rt_camera* camera, int recalibrate);   /* rt_scene_set_camera on every replica */
+rt_status rt_multi_update_spheres(rt_multi* m, const rt_sphere_update* update, int recalibrate);   /* rt_scene_update_spheres, host records, on every replica */
 int32_t rt_multi_device_count(const rt_multi* m);
 /* the row partition rt_multi_render uses: which device renders global row j and at which row of its compact buffer
  * (the inverse of rt_local_to_global_row for tile_first = device, tile_stride = n_gpus) */

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Wall time of rt_scene_update_spheres per call -- one moved sphere, and every direct sphere moved, from host records and from a
+device tensor -- beside the wall time of rt_scene_create of the same scene (tools/scene_create_time.py's method: the call alone,
+the best of a few, the first reported apart).  One JSON line per measurement.
+
+    python tools/scene_update_time.py                       # this tree: creation and updates
+    python tools/scene_update_time.py --create-only --root DIR --label parent
+                                                            # creation alone, with the package of another checkout (the parent
+                                                            # commit, built in DIR), for the comparison DESIGN.md 4.15 quotes
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="checkout whose package is imported")
+ap.add_argument("--create-only", action="store_true")
+ap.add_argument("--label", default="this tree")
+ap.add_argument("--calls", type=int, default=40, help="timed update calls per measurement (the median is reported)")
+ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
+
+import numpy as np  # noqa: E402
+import accelerated_ray_tracer_amd as art  # noqa: E402
+
+# the random scene (488 spheres), Book-2 final (1008 spheres, every one direct in this flattening: the cluster's rotation and
+# translation are baked into its centres) and a 4096-leaf scene
+SCENES = (("random_scene", 1200, 800), ("final", 800, 800), ("crowd_4096", 64, 64))
+
+
+def emit(**rec):
+    line = json.dumps(dict(rec, label=args.label))
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+
+
+def direct_spheres(hs):
+    """The spheres some leaf's box follows -- a leaf's own sphere, or the direct boundary of a leaf's medium -- that no instance holds."""
+    nodes, media, inst, n = hs.nodes(), hs.media(), hs.instances(), hs.desc.n_spheres
+    prim = nodes["prim"][nodes["prim"] >= 0].astype(np.int64)
+    is_medium = (prim >> 28) == art.RT_PRIM_MEDIUM
+    if is_medium.any():
+        prim[is_medium] = media["boundary"][prim[is_medium] & 0x0FFFFFFF]
+    direct = np.unique(prim[(prim >= 0) & ((prim >> 28) == art.RT_PRIM_SPHERE)] & 0x0FFFFFFF)
+    child = inst["child"].astype(np.int64) if len(inst) else np.zeros(0, np.int64)
+    under = np.unique(child[(child >= 0) & ((child >> 28) == art.RT_PRIM_SPHERE)] & 0x0FFFFFFF)
+    return np.setdiff1d(direct[direct < n], under).astype(np.int32)
+
+
+def time_create(hs, scene):
+    ts = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        ds = art.DeviceScene(hs)
+        ts.append((time.perf_counter() - t0) * 1e3)
+        info = ds.walk_info()
+        ds.close()
+    emit(what="rt_scene_create", scene=scene, ms_min=round(min(ts), 3), ms_first=round(ts[0], 3), spheres=hs.desc.n_spheres,
+         nodes_reference=info["nodes_reference"], nodes_walked=info["nodes_walked"])
+
+
+def time_updates(hs, scene):
+    import torch
+    L = art.rt_lib()
+    ds = art.DeviceScene(hs)
+    direct, sph = direct_spheres(hs), hs.spheres()
+    rng = np.random.default_rng(1)
+
+    def call(u, on_device):
+        t0 = time.perf_counter()
+        st = L.rt_scene_update_spheres(ds._p, C.byref(u), on_device, 0, None)
+        dt = (time.perf_counter() - t0) * 1e3
+        assert st == 0, L.rt_last_error_detail().decode()
+        return dt
+
+    first_call = None
+    for size, idx in (("one", direct[len(direct) // 2:len(direct) // 2 + 1]), ("all", direct)):
+        for source in ("host", "device"):
+            ts = []
+            for k in range(5 + args.calls):                                      # five warm-up calls, then the timed ones
+                rec = sph[idx]
+                rec["c0"] += rng.uniform(-0.2, 0.2, (len(idx), 3)).astype(np.float32)
+                u = art.RtSphereUpdate()
+                u.count, u.indices = len(idx), idx.ctypes.data
+                if source == "device":
+                    t = torch.from_numpy(rec.view(np.float32).reshape(-1, 8).copy()).cuda()
+                    torch.cuda.synchronize()
+                    u.spheres = t.data_ptr()
+                else:
+                    u.spheres = rec.ctypes.data
+                dt = call(u, 1 if source == "device" else 0)
+                if first_call is None:
+                    first_call = dt                                              # builds the scene's lookup tables
+                elif k >= 5:
+                    ts.append(dt)
+            emit(what="rt_scene_update_spheres", scene=scene, moved=size, records=source, count=int(len(idx)), calls=len(ts),
+                 ms_median=round(statistics.median(ts), 4), ms_min=round(min(ts), 4), ms_max=round(max(ts), 4))
+    emit(what="rt_scene_update_spheres, first call of the scene (builds the lookup tables)", scene=scene, ms=round(first_call, 3))
+    f = hs.frame(nx=min(hs.nx, 240), ny=min(hs.ny, 160), ns=4)
+    _, st = ds.render(f)                                                         # the moved scene still renders
+    assert st.rays > 0
+    ds.close()
+
+
+if not args.create_only:
+    import torch
+    if not torch.cuda.is_available():                                            # (before rt_init, as the test suite does)
+        raise SystemExit("no GPU visible to torch: the device-tensor measurements need one")
+art.init(0)
+for scene, nx, ny in SCENES:
+    img, iw, ih = art.default_texture(scene)
+    hs = art.HostScene(scene, nx, ny, img, iw, ih)
+    time_create(hs, scene)
+    if not args.create_only:
+        time_updates(hs, scene)
+    hs.close()
