@@ -114,6 +114,11 @@ class RtReprojectDesc(C.Structure):
                 ("alpha_min", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_float)]
 
 
+class RtReprojectMotionDesc(C.Structure):
+    _fields_ = [("n_spheres", C.c_int32), ("n_media", C.c_int32), ("spheres", C.c_void_p), ("prev_spheres", C.c_void_p),
+                ("media", C.c_void_p), ("time", C.c_float), ("prev_time", C.c_float)]
+
+
 class RtSphereUpdate(C.Structure):
     _fields_ = [("count", C.c_int32), ("first", C.c_int32), ("indices", C.c_void_p), ("spheres", C.c_void_p)]
 
@@ -170,7 +175,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_radiance_rays", "rt_render_aov", "rt_render_aov_through", "rt_denoise_workspace_bytes", "rt_denoise", "rt_render_variance",
                   "rt_denoise_variance", "rt_scene_set_camera", "rt_scene_get_camera", "rt_multi_set_camera", "rt_reproject",
                   "rt_reproject_matrix", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info",
-                  "rt_scene_update_spheres", "rt_scene_get_spheres", "rt_multi_update_spheres", "rt_refit_nodes", "rt_debug_scene_boxes"]
+                  "rt_scene_update_spheres", "rt_scene_get_spheres", "rt_multi_update_spheres", "rt_refit_nodes", "rt_debug_scene_boxes",
+                  "rt_reproject_moving"]
 
 _rt = None
 _host = None
@@ -267,6 +273,7 @@ def rt_lib():
         L.rt_debug_scene_boxes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_reproject.argtypes = [C.POINTER(RtReprojectDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_reproject_matrix.argtypes = [C.POINTER(RtCamera), C.POINTER(C.c_float)]
+        L.rt_reproject_moving.argtypes = [C.POINTER(RtReprojectDesc), C.POINTER(RtReprojectMotionDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.rt_debug_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_debug_prior.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -557,7 +564,8 @@ def reproject_matrix(prev: RtCamera) -> np.ndarray:
 def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, prim=None, history=None, history_len=None,
               prev_depth=None, prev_alpha=None, prev_normal=None, prev_prim=None, *, out=None, out_len=None, motion=False,
               alpha_min=REPROJECT_DEFAULTS["alpha_min"], depth_tol=REPROJECT_DEFAULTS["depth_tol"],
-              normal_min=REPROJECT_DEFAULTS["normal_min"], max_history=REPROJECT_DEFAULTS["max_history"], stream=0, blocking=True):
+              normal_min=REPROJECT_DEFAULTS["normal_min"], max_history=REPROJECT_DEFAULTS["max_history"], stream=0, blocking=True,
+              spheres=None, prev_spheres=None, media=None, time=None, prev_time=None):
     """Temporal reprojection (rt_reproject, include/rt_abi.h): the current linear frame `color` (ny, nx, 3) blended into the
     history of the previous frame, fetched where each pixel's surface point -- from `depth` and `alpha` (ny, nx) of
     render_aov and the cameras `cur` and `prev` -- was in that frame.  history (ny, nx, 3) and history_len (ny, nx) are the
@@ -569,7 +577,15 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     enqueued on `stream` (a hipStream_t as an integer or a torch.cuda.Stream) and waited for only with blocking=True.  out /
     out_len: None (made like color) or arrays / tensors of the same kind; they may overlap no input.  motion: False, True (a
     (ny, nx, 2) buffer is made) or such a buffer.  Returns a ReprojectResult (out, length, motion).  Malformed arguments raise
-    ValueError before anything is launched."""
+    ValueError before anything is launched.
+
+    spheres / prev_spheres (rt_reproject_moving): the sphere records the current and the previous frame were rendered with
+    (DeviceScene.spheres() after and before update_spheres).  A surface pixel on a sphere whose record differs -- or in a
+    medium bounded by one; `media` is the scene's media() -- is first carried back to where that surface point was, so the
+    history follows the sphere and `motion` holds its motion too.  prim and prev_prim are then required.  With numpy buffers
+    the tables are arrays of SPHERE_DTYPE / MEDIUM_DTYPE; with tensors they are contiguous (n, 8) / (n, 4) tensors of a
+    4-byte dtype on the device, as update_spheres takes them.  time / prev_time: the instants at which centres c0 + t vel
+    are taken; default: the shutter centre of `cur` / `prev`.  With spheres=None the other four must be None too."""
     on_host = isinstance(color, np.ndarray)
     if not on_host and not hasattr(color, "data_ptr"):
         raise ValueError("color: a numpy array or a torch tensor is expected")
@@ -612,6 +628,43 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     elif motion is False:
         motion = None
 
+    md = None
+    if spheres is None:
+        if any(x is not None for x in (prev_spheres, media, time, prev_time)):
+            raise ValueError("prev_spheres, media, time and prev_time need spheres")
+    else:
+        if prev_spheres is None:
+            raise ValueError("spheres needs prev_spheres")
+        if prim is None or prev_prim is None:
+            raise ValueError("spheres: prim and prev_prim are required to follow spheres")
+        md = RtReprojectMotionDesc()
+        keep_tables = []
+
+        def table(x, name, dtype, words):
+            if on_host:
+                if not isinstance(x, np.ndarray) or x.dtype != dtype or x.ndim != 1:
+                    raise ValueError(f"{name}: a one-dimensional numpy array of {'MEDIUM' if words == 4 else 'SPHERE'}_DTYPE is expected (color is one)")
+                x = np.ascontiguousarray(x)
+                keep_tables.append(x)
+                return len(x), (x.ctypes.data if len(x) else None)
+            if not isinstance(x, torch.Tensor):
+                raise ValueError(f"{name}: a torch tensor is expected (color is one)")
+            if x.ndim != 2 or x.shape[1] != words or x.element_size() != 4 or not x.is_contiguous() or x.device != dev:
+                raise ValueError(f"{name}: a contiguous (n, {words}) tensor of a 4-byte dtype on {dev} is expected")
+            return int(x.shape[0]), (x.data_ptr() if x.shape[0] else None)
+        md.n_spheres, md.spheres = table(spheres, "spheres", SPHERE_DTYPE, 8)
+        n_prev, md.prev_spheres = table(prev_spheres, "prev_spheres", SPHERE_DTYPE, 8)
+        if n_prev != md.n_spheres:
+            raise ValueError(f"prev_spheres: {n_prev} records, spheres has {md.n_spheres}")
+        if media is not None:
+            md.n_media, md.media = table(media, "media", MEDIUM_DTYPE, 4)
+        if md.n_spheres >= 1 << 28 or md.n_media >= 1 << 28:
+            raise ValueError("spheres / media: 2^28 records or more")
+        md.time = float(np.float32(0.5 * (cur.time0 + cur.time1))) if time is None else float(np.float32(time))
+        md.prev_time = float(np.float32(0.5 * (prev.time0 + prev.time1))) if prev_time is None else float(np.float32(prev_time))
+        if not np.isfinite(md.time) or not np.isfinite(md.prev_time):
+            raise ValueError("time and prev_time must be finite")
+
     def ptr(x, name, shape, integer=False):
         if x is None:
             return None
@@ -642,10 +695,15 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     if hasattr(stream, "cuda_stream"):
         stream = stream.cuda_stream
     L = rt_lib()
-    st = L.rt_reproject(C.byref(d), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None, 1 if blocking else 0)
+    stream_p = C.c_void_p(int(stream)) if stream else None
+    if md is None:
+        st = L.rt_reproject(C.byref(d), 0 if on_host else 1, stream_p, 1 if blocking else 0)
+    else:
+        st = L.rt_reproject_moving(C.byref(d), C.byref(md), 0 if on_host else 1, stream_p, 1 if blocking else 0)
+        del keep_tables
     if st == 1:
         raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_reproject")
+    _check(st, "rt_reproject" if md is None else "rt_reproject_moving")
     return ReprojectResult(out, out_len, motion)
 
 
@@ -1285,9 +1343,14 @@ class TemporalAccumulator:
     kept from the last push into the new view (reproject(), normals and ids on) and keeps the result and the buffers for the
     next push.  Returns the accumulated linear frame (ny, nx, 3) as a numpy array -- with denoise=True filtered by denoise()
     with the albedo, normal and depth of the same pass; the history itself stays unfiltered.  **params: thresholds of
-    REPROJECT_DEFAULTS.  `frame` must be the whole image.  `length` holds the last push's per-pixel history length."""
+    REPROJECT_DEFAULTS.  `frame` must be the whole image.  `length` holds the last push's per-pixel history length.
 
-    def __init__(self, scene: "DeviceScene", frame: RtFrameDesc, denoise: bool = False, **params):
+    follow_spheres=True: the history follows spheres that moved between two pushes (reproject(spheres=...)).  push() then also
+    takes an update (spheres, indices, first: DeviceScene.update_spheres' arguments) that it applies first, reads the scene's
+    records back (32 bytes per sphere) and reprojects with them, the previous push's records and the scene's media; updates
+    the caller made on the scene between two pushes are followed just the same."""
+
+    def __init__(self, scene: "DeviceScene", frame: RtFrameDesc, denoise: bool = False, follow_spheres: bool = False, **params):
         unknown = set(params) - set(REPROJECT_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown parameter(s) {sorted(unknown)}: one of {', '.join(REPROJECT_DEFAULTS)} is expected")
@@ -1296,6 +1359,7 @@ class TemporalAccumulator:
         if frame.tile_first != 0 or frame.tile_stride != 1 or frame.tile_rows < frame.ny:
             raise ValueError("TemporalAccumulator needs the whole frame (tile_rows >= ny, tile_first = 0, tile_stride = 1)")
         self.scene, self.denoise, self.params = scene, bool(denoise), dict(REPROJECT_DEFAULTS, **params)
+        self.follow_spheres = bool(follow_spheres)
         self.frame = RtFrameDesc.from_buffer_copy(frame)
         self.frame.gamma = 1.0
         self.aov_frame = RtFrameDesc.from_buffer_copy(self.frame)
@@ -1307,7 +1371,14 @@ class TemporalAccumulator:
         self._prev = None
         self.length = None
 
-    def push(self, camera: RtCamera, recalibrate: bool = False) -> np.ndarray:
+    def push(self, camera: RtCamera, recalibrate: bool = False, spheres=None, indices=None, first: int = 0) -> np.ndarray:
+        records = None
+        if self.follow_spheres:
+            if spheres is not None:
+                self.scene.update_spheres(spheres, indices, first)
+            records = self.scene.spheres()
+        elif spheres is not None or indices is not None or first != 0:
+            raise ValueError("spheres, indices and first need follow_spheres=True")
         self.scene.set_camera(camera, recalibrate)
         color, _ = self.scene.render(self.frame)
         aov = self.scene.render_aov(self.aov_frame, albedo=self.denoise, ids=True)
@@ -1316,10 +1387,13 @@ class TemporalAccumulator:
         if p is None:
             r = reproject(color, aov["depth"], aov["alpha"], cam, cam, **self.params)
         else:
+            follow = {}
+            if records is not None:
+                follow = dict(spheres=records, prev_spheres=p["spheres"], media=self.scene.host.media())
             r = reproject(color, aov["depth"], aov["alpha"], cam, p["camera"], aov["normal"], aov["prim"], p["out"], p["length"],
-                          p["depth"], p["alpha"], p["normal"], p["prim"], **self.params)
+                          p["depth"], p["alpha"], p["normal"], p["prim"], **self.params, **follow)
         self._prev = {"camera": cam, "out": r.out, "length": r.length, "depth": aov["depth"], "alpha": aov["alpha"],
-                      "normal": aov["normal"], "prim": aov["prim"]}
+                      "normal": aov["normal"], "prim": aov["prim"], "spheres": records}
         self.length = r.length
         if self.denoise:
             return denoise(r.out, aov["albedo"], aov["normal"], aov["depth"])

@@ -1900,9 +1900,11 @@ rt_status rt_reproject_matrix(const rt_camera* prev, float m[9]) {
     return RT_OK;
 }
 
-rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* stream_v, int blocking) {
+namespace {
+// rt_reproject (m == null) and rt_reproject_moving: the checks, the staging of host buffers and the parameter block are one
+rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, const char* who, int buffers_on_device, void* stream_v, int blocking) {
     // argument checks: no HIP call before they pass
-    auto bad = [&](const char* why) { return invalid((std::string("rt_reproject: ") + why).c_str()); };
+    auto bad = [&](const char* why) { return invalid((std::string(who) + ": " + why).c_str()); };
     if (!d) return bad("null description");
     if (d->nx < 1 || d->ny < 1) return bad("nx and ny must be positive");
     if ((long long)d->nx * d->ny >= (1ll << 31)) return bad("frame too large");
@@ -1920,35 +1922,49 @@ rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* 
     } else if (d->history_len || d->prev_depth || d->prev_alpha) {
         return bad("history_len, prev_depth and prev_alpha need history");
     }
+    if (m) {
+        if (!d->prim || !d->prev_prim) return bad("prim and prev_prim are required: they say which sphere a pixel shows");
+        if (m->n_spheres < 0 || m->n_media < 0) return bad("n_spheres and n_media must not be negative");
+        if (m->n_spheres >= (1 << 28) || m->n_media >= (1 << 28)) return bad("n_spheres and n_media must be below 2^28");
+        if (m->n_spheres > 0 && (!m->spheres || !m->prev_spheres)) return bad("n_spheres > 0 needs spheres and prev_spheres");
+        if (m->n_media > 0 && !m->media) return bad("n_media > 0 needs media");
+        if (!std::isfinite(m->time) || !std::isfinite(m->prev_time)) return bad("time and prev_time must be finite");
+    }
     rt_reproject_params rp;
     memset(&rp, 0, sizeof(rp));
     if (rt_reproject_matrix(&d->prev, rp.m) != RT_OK) return bad("prev: the camera's basis is singular or its inverse is not finite");
     const size_t pixels = (size_t)d->nx * d->ny;
     struct buffer : traced_ptr { bool input; };
-    enum { COLOR = 0, DEPTH, ALPHA, NORMAL, PRIM, HISTORY, HISTORY_LEN, PREV_DEPTH, PREV_ALPHA, PREV_NORMAL, PREV_PRIM, OUT, OUT_LEN, MOTION, N_BUFS };
+    enum { COLOR = 0, DEPTH, ALPHA, NORMAL, PRIM, HISTORY, HISTORY_LEN, PREV_DEPTH, PREV_ALPHA, PREV_NORMAL, PREV_PRIM, OUT, OUT_LEN, MOTION,
+           SPHERES, PREV_SPHERES, MEDIA, N_BUFS };   // the three tables: rt_reproject_moving only, inputs behind the outputs
     const size_t f1 = pixels * sizeof(float), f3 = 3 * f1;
+    const size_t sphere_bytes = m ? (size_t)m->n_spheres * sizeof(rt_sphere) : 0, medium_bytes = m ? (size_t)m->n_media * sizeof(rt_medium) : 0;
     const buffer bufs[N_BUFS] = {{{d->color, f3, "color", 4}, true}, {{d->depth, f1, "depth", 4}, true}, {{d->alpha, f1, "alpha", 4}, true},
                                  {{d->normal, f3, "normal", 4}, true}, {{d->prim, f1, "prim", 4}, true}, {{d->history, f3, "history", 4}, true},
                                  {{d->history_len, f1, "history_len", 4}, true}, {{d->prev_depth, f1, "prev_depth", 4}, true},
                                  {{d->prev_alpha, f1, "prev_alpha", 4}, true}, {{d->prev_normal, f3, "prev_normal", 4}, true},
                                  {{d->prev_prim, f1, "prev_prim", 4}, true}, {{d->out, f3, "out", 4}, false}, {{d->out_len, f1, "out_len", 4}, false},
-                                 {{d->motion, 2 * f1, "motion", 4}, false}};
-    for (int o = OUT; o < N_BUFS; ++o)     // an output shares no byte with any other buffer
+                                 {{d->motion, 2 * f1, "motion", 4}, false},
+                                 {{sphere_bytes ? m->spheres : nullptr, sphere_bytes, "spheres", 4}, true},
+                                 {{sphere_bytes ? m->prev_spheres : nullptr, sphere_bytes, "prev_spheres", 4}, true},
+                                 {{medium_bytes ? m->media : nullptr, medium_bytes, "media", 4}, true}};
+    for (int o = OUT; o <= MOTION; ++o)     // an output shares no byte with any other buffer
         for (int k = 0; k < N_BUFS; ++k) {
             const uintptr_t pa = (uintptr_t)bufs[o].p, pb = (uintptr_t)bufs[k].p;
             if (k != o && bufs[o].p && bufs[k].p && pa < pb + bufs[k].bytes && pb < pa + bufs[o].bytes)
                 return bad((std::string(bufs[o].what) + " overlaps " + bufs[k].what).c_str());
         }
     RT_TRY(use_device(g_device));
-    if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, g_device, "rt_reproject"));
+    if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, g_device, who));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
 
     // (without a history no tap is read: the tests on taps are then off whatever guides were given)
-    const bool normals_on = d->history && d->normal && d->prev_normal, ids_on = d->history && d->prim && d->prev_prim, motion_on = d->motion != nullptr;
+    const bool normals_on = d->history && d->normal && d->prev_normal, ids_on = m || (d->history && d->prim && d->prev_prim), motion_on = d->motion != nullptr;
     auto used = [&](int k) {   // what the kernel reads or writes
         if (!bufs[k].p) return false;
         if (k == NORMAL || k == PREV_NORMAL) return normals_on;
-        if (k == PRIM || k == PREV_PRIM) return ids_on;
+        if (k == PRIM) return ids_on;
+        if (k == PREV_PRIM) return ids_on && d->history;
         return true;
     };
     const void* dev[N_BUFS];
@@ -1978,12 +1994,31 @@ rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* 
         rp.prev_origin[c] = d->prev.origin[c];
     }
     rp.alpha_min = d->alpha_min; rp.depth_tol = d->depth_tol; rp.normal_min = d->normal_min; rp.max_history = d->max_history;
-    HIPCHK(rt_launch_reproject(normals_on, ids_on, motion_on, rp, stream));
+    if (m) {
+        rt_reproject_follow_params fp;
+        memset(&fp, 0, sizeof(fp));
+        fp.spheres = static_cast<const rt_sphere*>(dev[SPHERES]); fp.prev_spheres = static_cast<const rt_sphere*>(dev[PREV_SPHERES]);
+        fp.media = static_cast<const rt_medium*>(dev[MEDIA]);
+        fp.n_spheres = m->n_spheres; fp.n_media = m->n_media; fp.time = m->time; fp.prev_time = m->prev_time;
+        HIPCHK(rt_launch_reproject_moving(normals_on, motion_on, rp, fp, stream));
+    } else {
+        HIPCHK(rt_launch_reproject(normals_on, ids_on, motion_on, rp, stream));
+    }
     if (!buffers_on_device)
-        for (int k = OUT; k < N_BUFS; ++k) if (bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
+        for (int k = OUT; k <= MOTION; ++k) if (bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
     if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
     mem.settled();
     return RT_OK;
+}
+}  // namespace
+
+rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* stream_v, int blocking) {
+    return reproject_impl(d, nullptr, "rt_reproject", buffers_on_device, stream_v, blocking);
+}
+
+rt_status rt_reproject_moving(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, int buffers_on_device, void* stream_v, int blocking) {
+    if (!m) return invalid("rt_reproject_moving: null motion description");
+    return reproject_impl(d, m, "rt_reproject_moving", buffers_on_device, stream_v, blocking);
 }
 
 // Tail hand-off of the last frame (diagnostics, every build): [0] pixels the main kernel handed to the tail launches, summed over

@@ -422,6 +422,17 @@ struct rt_reproject_params {
     float alpha_min, depth_tol, normal_min, max_history;
 };
 hipError_t rt_launch_reproject(bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp, hipStream_t st);
+// rt_reproject_moving: a second kernel argument beside rt_reproject_params, which rt_reproject's kernels keep as it is -- the
+// sphere records of both frames and the media, whose boundaries say which sphere a fog ball follows.  The id test is always
+// on (prim and prev_prim are required).  A table is null exactly when its count is 0.
+struct rt_reproject_follow_params {
+    const rt_sphere* spheres;        // n_spheres records of the current frame
+    const rt_sphere* prev_spheres;   // ... and of the previous frame, same order
+    const rt_medium* media;          // n_media
+    int32_t n_spheres, n_media;
+    float time, prev_time;           // c = c0 + time * vel
+};
+hipError_t rt_launch_reproject_moving(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_params& fp, hipStream_t st);
 
 // rt_scene_update_spheres (rt_kernel_refit.hip; include/rt_abi.h): the moved spheres' records, their leaves'
 // boxes in every array that holds them, the per-64-leaf unions, the scene's coordinate bound and every interior box of both

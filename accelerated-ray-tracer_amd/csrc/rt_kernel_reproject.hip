@@ -12,6 +12,12 @@
 // own data, then the taps), which is why the taps' loads are all issued before the first of them is looked at.
 // Specialised on (normal test, id test, motion output) so that a guide that is off costs neither loads nor registers.
 //
+// rt_reproject_moving ("temporal reprojection that follows moved spheres") launches the same kernel with its
+// tables as a second argument: a surface pixel on a sphere whose record changed is carried back to where that surface point was
+// before it is projected.  That is a third dependent memory phase between the two -- the pixel's prim, then at most one medium
+// record and, issued together, the two 32-byte sphere records -- whose lines the lanes of one sphere share; the instantiations
+// without the argument are, instruction for instruction, what they were before it existed.
+//
 // The arithmetic is the contract's, statement by statement (-ffp-contract=off: no FMA is formed).
 //
 // Bounds.  The pixel's own index is tested against the frame before any address is formed.  A tap address is formed only from
@@ -19,7 +25,9 @@
 // integer coordinates have compared as inside the image (unsigned: -1 wraps and compares as outside).  Every plane of the
 // previous frame holds ny * nx pixels, so every load of a tap that is inside the image is inside its buffer, whatever the
 // other buffers hold; a tap outside the image reads at the pixel's own index instead and is not counted.  The loads of all
-// four taps are issued together, ahead of the tests that decide whether a tap counts.
+// four taps are issued together, ahead of the tests that decide whether a tap counts.  The follow step forms two more kinds of
+// address from data: media[index] after index < n_media and spheres[k] / prev_spheres[k] after k < n_spheres, both compared
+// unsigned; what the records hold is only ever arithmetic.
 #include "rt_device.h"
 #include "rt_launch.h"
 
@@ -29,8 +37,15 @@ constexpr int TILE = RT_REPROJECT_TILE;
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
-template <bool NRM, bool IDS, bool MOT>
-__global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_reproject_params rp) {
+// the kernel's optional second argument (the FOL branch is not instantiated without one)
+__device__ __forceinline__ const rt_reproject_follow_params& follow_tables(const rt_reproject_follow_params& fp) { return fp; }
+
+// rt_reproject launches <NRM, IDS, MOT> with no second argument.  rt_reproject_moving passes its tables as one: FOL, step 1 gains
+// its tail (a surface pixel on a sphere whose record changed is carried back to where that surface point was) and prim[p] is read
+// whatever IDS says.
+template <bool NRM, bool IDS, bool MOT, class... Follow>
+__global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_reproject_params rp, Follow... follow) {
+    constexpr bool FOL = sizeof...(Follow) > 0;
     const int tid = threadIdx.x;
     const int nx = rp.nx, ny = rp.ny;
     const unsigned by = blockIdx.x / (unsigned)rp.tiles_x, bx = blockIdx.x - by * (unsigned)rp.tiles_x;
@@ -43,7 +58,7 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
     float npx = 0.f, npy = 0.f, npz = 0.f;
     if (NRM) { npx = rp.normal[3 * p]; npy = rp.normal[3 * p + 1]; npz = rp.normal[3 * p + 2]; }
     int32_t idp = 0;
-    if (IDS) idp = rp.prim[p];
+    if (IDS || FOL) idp = rp.prim[p];
 
     // 1. the pixel's centre ray and its world point (or, for sky, its direction: a point at infinity)
     const float fi = (float)(int)i, fj = (float)(int)j, fnx = (float)nx, fny = (float)ny;
@@ -54,10 +69,45 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
     const bool surface = al >= rp.alpha_min;
     if (surface) {
         const float z = dep / al;
+        float P[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float P = rp.origin[c] + z * q[c];
-            q[c] = P - rp.prev_origin[c];
+            P[c] = rp.origin[c] + z * q[c];
+            q[c] = P[c] - rp.prev_origin[c];
+        }
+        if constexpr (FOL) {
+            const rt_reproject_follow_params& fp = follow_tables(follow...);
+            // 1a. which sphere: the pixel's own, or the one that bounds its medium.  Both table indices are compared unsigned
+            // against the tables' lengths before an address is formed; nothing loaded from a record reaches an address.
+            unsigned k = 0xFFFFFFFFu;
+            if (idp >= 0) {
+                const unsigned kind = (unsigned)idp >> 28, index = (unsigned)idp & 0x0FFFFFFFu;
+                if (kind == (unsigned)RT_PRIM_SPHERE) {
+                    k = index;
+                } else if (kind == (unsigned)RT_PRIM_MEDIUM && index < (unsigned)fp.n_media) {
+                    const int32_t b = fp.media[index].boundary;
+                    if (b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_SPHERE) k = (unsigned)b & 0x0FFFFFFFu;
+                }
+            }
+            if (k < (unsigned)fp.n_spheres) {
+                // 1b. both records' loads are issued together (one round trip), ahead of the taps' phase
+                const rt_sphere S = fp.spheres[k], T = fp.prev_spheres[k];
+                float cc[3], cp[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    cc[c] = S.c0[c] + fp.time * S.vel[c];
+                    cp[c] = T.c0[c] + fp.prev_time * T.vel[c];
+                }
+                const bool moved = cc[0] != cp[0] || cc[1] != cp[1] || cc[2] != cp[2] || S.radius != T.radius;
+                if (moved) {   // 1c. the carry: the similarity that takes the sphere's surface onto its previous self
+                    const float ratio = T.radius / S.radius;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float Pp = cp[c] + (P[c] - cc[c]) * ratio;
+                        q[c] = Pp - rp.prev_origin[c];
+                    }
+                }
+            }
         }
     }
 
@@ -147,6 +197,12 @@ hipError_t launch(const rt_reproject_params& rp, hipStream_t st) {
     const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
     return rt_launch_kernel(rt_reproject_kernel<NRM, IDS, MOT>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp);
 }
+// rt_reproject_moving: ids are always on (the entry requires prim and prev_prim; without a history no tap is read)
+template <bool NRM, bool MOT>
+hipError_t launch_moving(const rt_reproject_params& rp, const rt_reproject_follow_params& fp, hipStream_t st) {
+    const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
+    return rt_launch_kernel(rt_reproject_kernel<NRM, true, MOT, rt_reproject_follow_params>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, fp);
+}
 template <bool NRM, bool IDS>
 hipError_t launch_motion(bool motion_on, const rt_reproject_params& rp, hipStream_t st) {
     return motion_on ? launch<NRM, IDS, true>(rp, st) : launch<NRM, IDS, false>(rp, st);
@@ -157,4 +213,9 @@ hipError_t launch_motion(bool motion_on, const rt_reproject_params& rp, hipStrea
 hipError_t rt_launch_reproject(bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp, hipStream_t st) {
     if (normals_on) return ids_on ? launch_motion<true, true>(motion_on, rp, st) : launch_motion<true, false>(motion_on, rp, st);
     return ids_on ? launch_motion<false, true>(motion_on, rp, st) : launch_motion<false, false>(motion_on, rp, st);
+}
+
+hipError_t rt_launch_reproject_moving(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_params& fp, hipStream_t st) {
+    if (normals_on) return motion_on ? launch_moving<true, true>(rp, fp, st) : launch_moving<true, false>(rp, fp, st);
+    return motion_on ? launch_moving<false, true>(rp, fp, st) : launch_moving<false, false>(rp, fp, st);
 }

@@ -9,7 +9,7 @@
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
 //             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K] [--denoise-variance [B]]] [--list]
 //             [--aov-through PREFIX] [--through-bounces N] [--through-fuzz F] [--denoise-through]
-//             [--orbit FRAMES DEGREES --out PREFIX [--temporal]]
+//             [--orbit FRAMES DEGREES --out PREFIX [--temporal] [--bounce HEIGHT]]
 //
 // --orbit FRAMES DEGREES renders a turntable: FRAMES frames of one device scene, the scene's lookfrom rotated about the vertical
 // axis through its lookat in equal steps of DEGREES / FRAMES (frame k at k steps; every other camera argument kept), each
@@ -18,6 +18,11 @@
 // the frames so far (rt_reproject with the binding's defaults, normals and ids on, guided by rt_render_aov at min(ns, 16)
 // samples): the frames are rendered at gamma 1 and the gamma is applied on the host afterwards, as --denoise does.  Not with
 // --gpus > 1, --progressive, --adaptive, --denoise, --aov or --aov-through.
+// --bounce HEIGHT (only with --orbit; HEIGHT finite and >= 0; DEGREES may be 0 for a still camera) also moves the small spheres:
+// before frame k every sphere i of the description whose radius is in (0, 0.5) gets
+//   c0.y = (float)((double)base_y + HEIGHT * fabs(sin(pi * ((double)k / FRAMES + 0.61803398875 * i))))
+// (in double, libm's sin) through rt_scene_update_spheres.  With --temporal the accumulation follows them (rt_reproject_moving
+// with the records of this frame and of the previous one).  A scene with instances is refused: some of its spheres cannot move.
 //
 // --denoise [K] filters the frame with rt_denoise (K iterations, 5 when K is left out; the binding's other defaults): the frame
 // is rendered at gamma 1, the feature pass (albedo, normal, depth at min(ns, 16) samples) guides the filter, and the frame's
@@ -70,7 +75,8 @@ int main(int argc, char** argv) {
     int min_spp = 0, denoise = 0, batches = -1;   // batches: -1 = no --denoise-variance, 0 = B left out
     int orbit_frames = 0;
     double orbit_degrees = 0.0;
-    bool temporal = false;
+    bool temporal = false, bounce = false;
+    double bounce_height = 0.0;
     std::string out_prefix;
     unsigned long long seed = 1984ull;
     for (int a = 1; a < argc; ++a) {
@@ -118,6 +124,11 @@ int main(int argc, char** argv) {
         }
         else if (k == "--out") out_prefix = val();
         else if (k == "--temporal") temporal = true;
+        else if (k == "--bounce") {
+            bounce = true;
+            bounce_height = strtod(val(), nullptr);
+            if (!std::isfinite(bounce_height) || bounce_height < 0.0) { fprintf(stderr, "--bounce HEIGHT: HEIGHT must be finite and >= 0\n"); return 2; }
+        }
         else if (k == "--list") { int n = 0; const char* const* v = rtw::scene_names(&n); for (int i = 0; i < n; ++i) printf("%s\n", v[i]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); return 2; }
     }
@@ -133,6 +144,7 @@ int main(int argc, char** argv) {
     if (min_spp > 0 && !adaptive) { fprintf(stderr, "--min-spp needs --adaptive\n"); return 2; }
     if (orbit_frames > 0 && out_prefix.empty()) { fprintf(stderr, "--orbit needs --out PREFIX\n"); return 2; }
     if (orbit_frames == 0 && (temporal || !out_prefix.empty())) { fprintf(stderr, "--temporal and --out need --orbit\n"); return 2; }
+    if (orbit_frames == 0 && bounce) { fprintf(stderr, "--bounce needs --orbit\n"); return 2; }
     if (orbit_frames > 0 && (gpus > 1 || progressive > 0 || adaptive || denoise || !aov_prefix.empty() || !through_prefix.empty())) {
         fprintf(stderr, "--orbit cannot be combined with --gpus > 1, --progressive, --adaptive, --denoise, --aov or --aov-through\n");
         return 2;
@@ -162,6 +174,10 @@ int main(int argc, char** argv) {
     rt_status st = rtw::flatten(scene->world, *scene->cam, flat, err, scene->created.data(), (int)scene->created.size());
     if (st != RT_OK) { fprintf(stderr, "flatten: %s\n", err.c_str()); return 2; }
     const rt_scene_desc desc = flat.desc();
+    if (bounce && !flat.instances.empty()) {
+        fprintf(stderr, "--bounce: scene '%s' has instances, and a sphere under an instance cannot move (rt_scene_update_spheres)\n", scene_name.c_str());
+        return 2;
+    }
 
     fprintf(stderr, "Rendering a %dx%d image in 8x8 blocks.\n", scene->nx, scene->ny);
     rt_frame_desc f;
@@ -190,8 +206,21 @@ int main(int argc, char** argv) {
         std::vector<float> acc[2] = {std::vector<float>(px * 3), std::vector<float>(px * 3)}, len[2] = {std::vector<float>(px), std::vector<float>(px)};
         rt_camera prev_cam;
         memset(&prev_cam, 0, sizeof(prev_cam));
+        std::vector<rt_sphere> records[2] = {flat.spheres, flat.spheres};   // --bounce: the records of this frame and of the previous one
         double ms = 0.0;
         for (int k = 0; k < orbit_frames; ++k) {
+            if (bounce && !flat.spheres.empty()) {
+                std::vector<rt_sphere>& now = records[k & 1];
+                for (size_t i = 0; i < now.size(); ++i) {
+                    const rt_sphere& base = flat.spheres[i];
+                    if (!(base.radius > 0.f && base.radius < 0.5f)) continue;
+                    now[i].c0[1] = (float)((double)base.c0[1] + bounce_height * fabs(sin(3.14159265358979323846 * ((double)k / orbit_frames + 0.61803398875 * (double)i))));
+                }
+                rt_sphere_update up;
+                memset(&up, 0, sizeof(up));
+                up.count = (int32_t)now.size(); up.first = 0; up.spheres = now.data();
+                check(rt_scene_update_spheres(dev_scene, &up, /*spheres_on_device=*/0, /*recalibrate=*/0, /*stream=*/nullptr), "rt_scene_update_spheres");
+            }
             const double th = (double)k * orbit_degrees / (double)orbit_frames * 3.14159265358979323846 / 180.0;
             const double dx = (double)c0.lookfrom.x() - c0.lookat.x(), dz = (double)c0.lookfrom.z() - c0.lookat.z();
             const rtw::vec3 eye((float)(c0.lookat.x() + cos(th) * dx + sin(th) * dz), c0.lookfrom.y(), (float)(c0.lookat.z() - sin(th) * dx + cos(th) * dz));
@@ -219,7 +248,17 @@ int main(int argc, char** argv) {
                 }
                 rd.out = acc[k & 1].data(); rd.out_len = len[k & 1].data();
                 rd.alpha_min = 0.5f; rd.depth_tol = 0.05f; rd.normal_min = 0.5f; rd.max_history = 32.0f;   // the binding's REPROJECT_DEFAULTS
-                check(rt_reproject(&rd, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_reproject");
+                if (bounce && k) {   // the history follows the spheres that moved since the previous frame
+                    rt_reproject_motion_desc md;
+                    memset(&md, 0, sizeof(md));
+                    md.n_spheres = (int32_t)flat.spheres.size(); md.n_media = (int32_t)flat.media.size();
+                    md.spheres = md.n_spheres ? records[k & 1].data() : nullptr; md.prev_spheres = md.n_spheres ? records[(k + 1) & 1].data() : nullptr;
+                    md.media = md.n_media ? flat.media.data() : nullptr;
+                    md.time = (float)(0.5 * (cam.time0 + cam.time1)); md.prev_time = (float)(0.5 * (prev_cam.time0 + prev_cam.time1));   // the binding's default
+                    check(rt_reproject_moving(&rd, &md, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_reproject_moving");
+                } else {
+                    check(rt_reproject(&rd, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_reproject");
+                }
                 prev_cam = cam;
                 fb = acc[k & 1];
                 if (scene->gamma != 1.0f) for (float& c : fb) c = powf(c, 1.0f / scene->gamma);

@@ -708,8 +708,10 @@ rt_status rt_debug_scene_boxes(const rt_scene* scene, int32_t which, void* out, 
  *      out.ch = h.ch + (color.ch - h.ch) g.  No history, or a null `history` (the first frame): out = color, out_len = 1.
  *      motion = (x - (float)i, y - (float)j) whenever step 2 produced x and y (a > 0), else (0, 0); it does not need a history.
  * tests/reproject_expect.py restates this in NumPy; the device result equals it bit for bit.
- * Limits.  The centre ray ignores the lens and the shutter: under defocus, or with moving spheres, the reprojection is
- * approximate (the geometry test then rejects more).  depth and alpha must be rt_render_aov's; rt_render_aov_through's depth
+ * Limits.  The centre ray ignores the lens and the shutter: under defocus, or with spheres that have a velocity, the
+ * reprojection is approximate (the geometry test then rejects more).  rt_reproject assumes that the world stood still between
+ * the two frames: a sphere whose record changed (rt_scene_update_spheres) is rejected by the tap tests, not followed --
+ * rt_reproject_moving, below, follows it.  depth and alpha must be rt_render_aov's; rt_render_aov_through's depth
  * runs along a bent path and is not geometric.  Normals are on iff normal and prev_normal are both non-null, ids iff prim and
  * prev_prim are.
  * Memory safety.  No address depends on a value that has not passed the comparisons of steps 2 and 3; no value of any input
@@ -742,6 +744,53 @@ typedef struct rt_reproject_desc {
 } rt_reproject_desc;
 rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* stream, int blocking);
 rt_status rt_reproject_matrix(const rt_camera* prev, float m[9]);   /* host only, no device */
+
+/* ---- temporal reprojection that follows moved spheres ----
+ * rt_reproject_moving is rt_reproject with one more step: a surface pixel whose first-hit primitive is a sphere whose record
+ * changed between the two frames (rt_scene_update_spheres) -- or a constant_medium bounded directly by such a sphere -- is
+ * carried back to where that surface point was in the previous frame, and only then projected into the previous camera.  A
+ * sphere that translates and changes its radius maps its surface onto itself by a similarity (P - c) r' / r + c', which is
+ * exact for the sphere's own surface and an approximation for a scattering point inside a fog ball.
+ *
+ * The numerical contract extends rt_reproject's and keeps its rules: binary32, every written operation rounded once, nothing
+ * contracted, the operand order as written.  Ids are required: d->prim and d->prev_prim must be non-null (without them nothing
+ * says which sphere a pixel shows, and nothing rejects the background a sphere uncovered); the id test of a tap is always on.
+ * Steps 2-4 are rt_reproject's.  Step 1 gains a tail for surface pixels only (sky never follows):
+ *   1a. Which sphere.  ref = prim[p], k = none.  ref >= 0 and ref >> 28 == RT_PRIM_SPHERE: k = ref & 0x0FFFFFFF.  ref >= 0,
+ *       ref >> 28 == RT_PRIM_MEDIUM and (ref & 0x0FFFFFFF) < n_media: b = media[ref & 0x0FFFFFFF].boundary, and if b >= 0 and
+ *       b >> 28 == RT_PRIM_SPHERE then k = b & 0x0FFFFFFF.  Unless k < n_spheres (compared unsigned, before any address is
+ *       formed) the pixel is static.
+ *   1b. The two centres.  S = spheres[k], S' = prev_spheres[k];  cc.c = S.c0.c + time S.vel.c,  cp.c = S'.c0.c + prev_time S'.vel.c
+ *       per component;  moved = cc.x != cp.x || cc.y != cp.y || cc.z != cp.z || S.radius != S'.radius (a NaN compares as moved).
+ *       Unless moved the pixel is static: its q is rt_reproject's, bit for bit.
+ *   1c. The carry.  ratio = S'.radius / S.radius;  P'.c = cp.c + (P.c - cc.c) ratio;  q.c = P'.c - O'.c.  A zero or non-finite
+ *       radius yields a non-finite q, which the a > 0 test and the float comparisons of step 2 end with no history.
+ * motion is written as before from the x, y of step 2: for a followed pixel it is the object's motion plus the camera's.
+ * So with n_spheres == 0, or with tables in which no record moved, the outputs are rt_reproject's bit for bit; and a sphere
+ * under an instance, which cannot be updated, never differs: its pixel (prim = the sphere, inst >= 0) takes the static path
+ * and no inst buffer is needed.  tests/reproject_moving_expect.py restates this in NumPy; the device result equals it bit for bit.
+ * Limits.  As before the centre ray ignores the lens and the shutter; a sphere with vel != 0 is followed at one instant per
+ * frame (`time`, `prev_time`; the binding's default is each camera's shutter centre, (float)(0.5 (time0 + time1))).  Quads, boxes
+ * and instances do not move in this project yet.  Reflections of a moved sphere in other surfaces are not followed.
+ * Memory safety.  Two kinds of data-derived addresses are added: media[...] after the unsigned compare against n_media, and
+ * spheres[k] / prev_spheres[k] after the unsigned compare against n_spheres.  Nothing loaded from a record reaches an address;
+ * no value in any buffer or table makes the call fault.
+ *
+ * Parameters: everything rt_reproject refuses, and a null m, a null prim or prev_prim, a negative count, n_spheres > 0 with a
+ * null spheres or prev_spheres, n_media > 0 with a null media, a count of 2^28 or more, a non-finite time or prev_time and an
+ * output that overlaps one of the tables are RT_ERR_INVALID before any HIP call; rt_last_error_detail() names the check and
+ * starts with "rt_reproject_moving".  The tables obey buffers_on_device like every other buffer (device or managed memory of
+ * the device, checked with hipPointerGetAttributes; host memory is staged); a table whose count is 0 is not looked at.  Stream
+ * and blocking: rt_reproject's rules. */
+typedef struct rt_reproject_motion_desc {
+    int32_t n_spheres, n_media;       /* lengths of the tables; 0 with null tables is allowed */
+    const rt_sphere* spheres;         /* the records the CURRENT frame was rendered with */
+    const rt_sphere* prev_spheres;    /* the records the PREVIOUS frame was rendered with, same count and order */
+    const rt_medium* media;           /* the scene's media (their boundaries say which sphere a fog ball follows), or null */
+    float time, prev_time;            /* the instants at which centres are evaluated: c = c0 + time * vel */
+} rt_reproject_motion_desc;
+rt_status rt_reproject_moving(const rt_reproject_desc* d, const rt_reproject_motion_desc* m,
+                              int buffers_on_device, void* stream, int blocking);
 
 /* ---- several GPUs of one node from one host thread ----
  * The reference is single-GPU (one render<<<>>> launch, main.cu:707); these entry points are what its host function

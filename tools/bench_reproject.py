@@ -14,6 +14,12 @@
 and exits: the run to put under `rocprofv3 --kernel-trace --stats`, whose per-kernel averages are the device times -- between
 events a single call of either is dominated by the host side of the call (argument and pointer checks, the launch).
 --kernel-stats FILE reads that run's kernel_stats.csv and prints / appends the rows of the two kernels as one JSON line.
+--moving-loop N --moved {none,all} is the moving mode (rt_reproject_moving, profiles/reproject_moving_mi355x.jsonl): the headline
+scene at 1200 x 800 under the two cameras, the second frame rendered after every small sphere (radius < 0.5) was lifted by
+update_spheres; N times rt_reproject with every guide and rt_reproject_moving with every guide, alternating, on those same
+buffers -- with `none` the tables hold the second frame's records twice (no sphere moved: every pixel takes the static path
+after the records were read), with `all` the records of both frames.  It exits after the loop: the run to put under
+`rocprofv3 --kernel-trace --stats`; --kernel-stats FILE --moved X then appends the two kernels' rows and their ratio.
 One JSON line per measurement goes to stdout and, with --out, is appended to that file (profiles/reproject_mi355x.jsonl).
 """
 import argparse
@@ -54,6 +60,46 @@ def median_ms(fn, calls=20, warmup=3):
     return statistics.median(times), min(times), max(times)
 
 
+def moving_loop(args, hs, dev):
+    """The moving mode: see the module's text."""
+    nx, ny = args.nx, args.ny
+    ds = art.DeviceScene(hs)
+    f4 = hs.frame(nx=nx, ny=ny, ns=4, gamma=1.0)
+    cams = [orbited(0.0, nx, ny), orbited(3.0, nx, ny)]
+    before = ds.spheres()
+    small = (before["radius"] > 0) & (before["radius"] < 0.5)
+    after = before.copy()
+    after["c0"][small, 1] += np.float32(0.3)
+    host = []
+    for k, cam in enumerate(cams):
+        if k:
+            ds.update_spheres(after)
+        ds.set_camera(cam)
+        color, _ = ds.render(f4)
+        host.append(dict(ds.render_aov(f4, ids=True), color=color))
+    t = [{k: torch.from_numpy(v).to(dev) for k, v in h.items()} for h in host]
+    words = lambda rec: torch.from_numpy(np.ascontiguousarray(rec).view(np.int32).reshape(len(rec), -1).copy()).to(dev)   # noqa: E731
+    cur_records, prev_records = words(after), words(before if args.moved == "all" else after)
+    media = words(hs.media()) if len(hs.media()) else None
+    first = art.reproject(t[0]["color"], t[0]["depth"], t[0]["alpha"], cams[0], cams[0])
+    out, out_len = torch.empty_like(first.out), torch.empty_like(first.length)
+    motion = torch.empty((ny, nx, 2), dtype=torch.float32, device=dev)
+    kw = dict(history=first.out, history_len=first.length, prev_depth=t[0]["depth"], prev_alpha=t[0]["alpha"], out=out, out_len=out_len,
+              stream=torch.cuda.current_stream(dev).cuda_stream, blocking=False, normal=t[1]["normal"], prim=t[1]["prim"],
+              prev_normal=t[0]["normal"], prev_prim=t[0]["prim"], motion=motion)
+    on_small = np.isin(host[1]["prim"], np.flatnonzero(small)) & (host[1]["alpha"] >= 0.5)
+    for _ in range(args.moving_loop):
+        art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], **kw)
+        static_found = float((out_len > 1).float().mean().item())
+        art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], spheres=cur_records, prev_spheres=prev_records, media=media, **kw)
+        moving_found = float((out_len > 1).float().mean().item())
+    torch.cuda.synchronize()
+    print(json.dumps({"what": "rt_reproject_moving loop", "spheres_moved": args.moved, "calls_each": args.moving_loop, "spheres": int(len(before)),
+                      "small_spheres": int(small.sum()), "pixels_on_small_spheres": round(float(on_small.mean()), 4),
+                      "pixels_with_history_static": round(static_found, 4), "pixels_with_history_moving": round(moving_found, 4)}))
+    ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nx", type=int, default=1200)
@@ -63,6 +109,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernel-loop", type=int, default=0)
     ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("--moving-loop", type=int, default=0)
+    ap.add_argument("--moved", choices=["none", "all"], default=None)
     args = ap.parse_args()
     nx, ny = args.nx, args.ny
     if args.kernel_stats:
@@ -76,6 +124,12 @@ def main():
                         "calls": int(r["Calls"]), "average_us": round(float(r["AverageNs"]) / 1e3, 3), "min_us": round(float(r["MinNs"]) / 1e3, 3),
                         "max_us": round(float(r["MaxNs"]) / 1e3, 3)}
         line = {"what": "device time per kernel (rocprofv3 --kernel-trace --stats)", "nx": nx, "ny": ny, "kernels": rows}
+        if args.moved:
+            static = rows.get("rt_reproject_kernel<true, true, true>")
+            moving = rows.get("rt_reproject_kernel<true, true, true, rt_reproject_follow_params>")
+            line["spheres_moved"] = args.moved
+            if static and moving:
+                line["moving_over_static"] = round(moving["average_us"] / static["average_us"], 4)
         print(json.dumps(line))
         if args.out:
             with open(args.out, "a") as fh:
@@ -85,6 +139,10 @@ def main():
     dev = torch.device("cuda", 0)
     hs = art.HostScene("random_scene", nx, ny)
     lines = []
+
+    if args.moving_loop:
+        moving_loop(args, hs, dev)
+        return
 
     # ---- (a) the kernel
     ds = art.DeviceScene(hs)
