@@ -176,7 +176,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_denoise_variance", "rt_scene_set_camera", "rt_scene_get_camera", "rt_multi_set_camera", "rt_reproject",
                   "rt_reproject_matrix", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info",
                   "rt_scene_update_spheres", "rt_scene_get_spheres", "rt_multi_update_spheres", "rt_refit_nodes", "rt_debug_scene_boxes",
-                  "rt_reproject_moving"]
+                  "rt_reproject_moving", "rt_debug_cost_map", "rt_debug_set_cost_map"]
 
 _rt = None
 _host = None
@@ -280,6 +280,9 @@ def rt_lib():
                                      C.POINTER(C.c_uint64)]
         L.rt_debug_cal_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_debug_rank_info.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_debug_cost_map"):   # (absent from an older library measured through RT_LIB_OVERRIDE)
+            L.rt_debug_cost_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
+            L.rt_debug_set_cost_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.rt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _rt = L
     return _rt
@@ -837,6 +840,27 @@ class DeviceScene:
         out = np.zeros(self.host.desc.n_spheres, SPHERE_DTYPE)
         _check(rt_lib().rt_scene_get_spheres(self._p, out.ctypes.data, len(out)), "rt_scene_get_spheres")
         return out
+
+    COST_MAP_STATES = ("none", "exact", "stale")
+
+    def cost_map(self):
+        """The scene's cost map (rt_debug_cost_map): (state, map, parts) -- state "none", "exact" or "stale" for the scene and the
+        options as they are now, map the rays per local pixel of the last ranked frame as a (local_rows, nx) uint32 array (None
+        with "none"), parts the number of parts the last ranked frame ran as.  Closes a pending frame."""
+        L = rt_lib()
+        info = (C.c_int32 * 4)()
+        _check(L.rt_debug_cost_map(self._p, None, 0, info), "rt_debug_cost_map")
+        if info[0] == 0:
+            return "none", None, int(info[3])
+        out = np.zeros((int(info[2]), int(info[1])), np.uint32)
+        _check(L.rt_debug_cost_map(self._p, out.ctypes.data, out.size, info), "rt_debug_cost_map")
+        return self.COST_MAP_STATES[info[0]], out, int(info[3])
+
+    def set_cost_map(self, costs) -> None:
+        """Install `costs` (one uint32 per local pixel of the last ranked frame) as that frame geometry's exact cost map
+        (rt_debug_set_cost_map).  Any map schedules the next frame; none changes a pixel."""
+        a = np.ascontiguousarray(costs, np.uint32)
+        _check(rt_lib().rt_debug_set_cost_map(self._p, a.ctypes.data, a.size), "rt_debug_set_cost_map")
 
     def render(self, frame: RtFrameDesc, out=None, stream: int = 0, blocking: bool = True):
         """Render into `out`: a float32 numpy array (host) or an integer device pointer.  Returns (array|None, stats)."""

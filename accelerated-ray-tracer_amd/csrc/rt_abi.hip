@@ -88,6 +88,7 @@ struct rt_options {
     int scan_nodes = 24;         // scenes whose walk array has at most this many nodes are scanned in lockstep (lds_mode 4); 0 = never
     int multi_force_rccl = 0;    // rt_multi_render: go through the RCCL gather even with one device (tests the path on a one-GPU box)
     int lpt = 1;                 // cost prepass + longest-first tile order (staged kernel, ns >= 2 * split_samples)
+    int cost_map = 1;            // ranked frames leave and use the scene's cost map (struct rt_scene); 0 = neither
     int trace_lds = -1;          // rt_trace_rays: -1 = auto, 0 = scene through L1/L2, 1 = nodes in LDS, 2 = nodes and spheres in LDS
     int trace_tree = 1;          // rt_trace_rays: 1 = the walk array, 0 = the reference's full tree
     int radiance_lds = -1;       // rt_radiance_rays: as trace_lds
@@ -99,6 +100,8 @@ struct rt_options {
                                  // (DESIGN.md 4.8), 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit
 };
 rt_options g_opt;
+// bumped by every rt_set_option / rt_reset_options call: a cost map recorded under another value counts as stale (struct rt_scene)
+unsigned long long g_opt_epoch = 0;
 
 // the reference's checkCudaErrors (main.cu:23-35) records "<code> at file:line 'expr'"; it then
 // exits with 99, which a library must not do, so the status is returned instead.
@@ -199,6 +202,29 @@ struct rt_scene {
     rt_rank_info* d_rank = nullptr;               // tier sizes of the next ranked launch (written and read on the device only)
     unsigned int* d_cal_cost = nullptr;           // cost prior: rays per pixel of the calibration frame (cal_nx x cal_ny at 4 spp)
     int cal_nx = 0, cal_ny = 0;
+    // The cost map: the rays every local pixel cost over all its samples, written by the last launches of the last ranked frame
+    // (rt_frame_params::cost_out) and valid once rt_frame_finish has closed that frame.  A pixel's cost depends on the scene, the
+    // camera, the frame geometry and the row partition -- `key` and `scene_epoch` -- and not on the seed or the sample count.
+    // Rendering the same view again (key and both epochs equal: the map is EXACT) therefore needs no first look: the frame is
+    // ranked on the map and runs as one part.  After rt_scene_set_camera / rt_scene_update_spheres without recalibration, or any
+    // option call, the map is STALE: it replaces the calibration frame as the prior of part 1.  Scheduling only.
+    struct cost_map_key {
+        int32_t nx = 0, ny = 0, tile_rows = 0, tile_first = 0, tile_stride = 0, local_rows = 0, kernel_variant = 0;
+        bool operator==(const cost_map_key& o) const {
+            return nx == o.nx && ny == o.ny && tile_rows == o.tile_rows && tile_first == o.tile_first && tile_stride == o.tile_stride &&
+                   local_rows == o.local_rows && kernel_variant == o.kernel_variant;
+        }
+    };
+    struct cost_map_state {
+        unsigned int* d = nullptr;                // one word per local pixel, grown like the ranked buffers
+        size_t capacity = 0;
+        bool valid = false, pending = false;      // pending: the frame in flight writes it
+        cost_map_key key, last_key;               // of the map; of the last ranked frame (rt_debug_set_cost_map)
+        bool have_last_key = false;
+        unsigned long long scene_epoch = 0, opt_epoch = 0, total = 0;   // of the map; total = the sum of its words (0: not used)
+        int last_parts = 0;                       // parts of the last ranked frame
+    } cost_map;
+    unsigned long long scene_epoch = 0;           // bumped when the camera or a sphere changes
     hipStream_t tier_stream = nullptr;            // the tier kernel's stream (forked from / joined to the caller's stream by events)
     hipEvent_t ev_fork[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
     bool ranked_frame = false;                    // the pending frame used the cost-aware schedule
@@ -670,6 +696,7 @@ rt_status rt_shutdown(void) {
 }
 
 rt_status rt_reset_options(void) {
+    ++g_opt_epoch;
     g_opt = rt_options();
     return RT_OK;
 }
@@ -689,6 +716,7 @@ const char* rt_last_error_detail(void) { return g_detail.c_str(); }
 
 rt_status rt_set_option(const char* key, int value) {
     if (!key) return invalid("null option key");
+    ++g_opt_epoch;
     const std::string k(key);
     if (k == "kernel") { if (value != RT_KERNEL_PIXEL && value != RT_KERNEL_STAGED) return invalid("kernel: 0 (pixel) or 3 (staged)"); g_opt.kernel = value; }
     else if (k == "leaf_threshold") { if (value < 1 || value > 64) return invalid("leaf_threshold: 1..64"); g_opt.leaf_threshold = value; }
@@ -724,6 +752,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "bvh_collapse") { if (value < 0 || value > 3) return invalid("bvh_collapse: 0..3 (read by rt_scene_create)"); g_opt.bvh_collapse = value; }
     else if (k == "scan_nodes") { if (value < 0 || value > 64) return invalid("scan_nodes: 0..64"); g_opt.scan_nodes = value; }
     else if (k == "multi_force_rccl") { if (value < 0 || value > 1) return invalid("multi_force_rccl: 0 or 1"); g_opt.multi_force_rccl = value; }
+    else if (k == "cost_map") { if (value < 0 || value > 1) return invalid("cost_map: 0 or 1"); g_opt.cost_map = value; }
     else if (k == "lpt") { if (value < 0 || value > 1) return invalid("lpt: 0 or 1"); g_opt.lpt = value; }
     else if (k == "threads") { if (value != 0 && (value < 64 || value > 768 || (value % 64))) return invalid("threads: 0 (per kernel family) or a multiple of 64 up to 768 (512 for the lean spheres-only kernels)"); g_opt.threads = value; }
     else if (k == "lds_mode") { if (value < -1 || value > 4) return invalid("lds_mode: -1..4"); g_opt.lds_mode = value; }
@@ -756,6 +785,7 @@ rt_status rt_scene_destroy(rt_scene* s) {
     if (s->d_rank) (void)hipFree(s->d_rank);
     if (s->d_handoff) (void)hipFree(s->d_handoff);
     if (s->d_cal_cost) (void)hipFree(s->d_cal_cost);
+    if (s->cost_map.d) (void)hipFree(s->cost_map.d);
     for (void* p : {s->refit.block, (void*)s->refit.d_indices, (void*)s->refit.d_records}) if (p) (void)hipFree(p);
     for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue,
                     (void*)s->d_adapt_spp, (void*)s->d_adapt_count, (void*)s->d_adapt_rank, (void*)s->d_var_acc})
@@ -1265,6 +1295,9 @@ rt_status rt_frame_finish(rt_scene* s, rt_stats* stats) {
         s->pending_stats.reserved = (int32_t)inf.heavy_items;
     }
     s->frame_pending = false;
+    if (s->cost_map.pending) {   // the frame that wrote the cost map is complete
+        s->cost_map.pending = false; s->cost_map.valid = rays > 0; s->cost_map.total = rays;
+    }
     if (stats) *stats = s->pending_stats;
     return RT_OK;
 }
@@ -1292,6 +1325,8 @@ rt_status rt_scene_set_camera(rt_scene* s, const rt_camera* camera, int recalibr
     RT_TRY(use_device(s->device));
     if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
     s->dev.camera = *camera;
+    ++s->scene_epoch;                                // the cost map is stale ...
+    if (recalibrate) s->cost_map.valid = false;      // ... or, with a fresh calibration prior asked for, dropped
     if (recalibrate && s->d_cal_cost) {   // (a scene that kept no prior at creation gets none: a fresh scene would have none either)
         std::vector<double> pass;
         double rays = 0.0;
@@ -1495,6 +1530,8 @@ rt_status rt_scene_update_spheres(rt_scene* s, const rt_sphere_update* u, int sp
         RT_TRY(check_trace_ptrs(records, s->device, "rt_scene_update_spheres"));
     }
     if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
+    ++s->scene_epoch;                                // the cost map: as rt_scene_set_camera
+    if (recalibrate) s->cost_map.valid = false;
     rt_refit_params p = t.p;
     p.count = u->count; p.first = u->first;
     if (++t.epoch == 0) { HIPCHK(hipMemsetAsync(p.stamp, 0, (size_t)s->dev.n_spheres * 4, stream)); t.epoch = 1; }
@@ -2182,6 +2219,41 @@ rt_status rt_debug_cal_cost(rt_scene* s, uint32_t* out, int32_t cap, int32_t* nx
     return RT_OK;
 }
 
+rt_status rt_debug_cost_map(rt_scene* s, uint32_t* out, int64_t cap, int32_t* info4) {
+    if (!s) return invalid("rt_debug_cost_map: null scene");
+    if (!info4 || (!out && cap != 0)) return invalid("rt_debug_cost_map: null argument");
+    RT_TRY(use_device(s->device));
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
+    const rt_scene::cost_map_state& cm = s->cost_map;
+    const bool have = g_opt.cost_map && cm.valid;
+    info4[0] = !have ? 0 : (cm.scene_epoch == s->scene_epoch && cm.opt_epoch == g_opt_epoch ? 1 : 2);
+    info4[1] = have ? cm.key.nx : 0; info4[2] = have ? cm.key.local_rows : 0; info4[3] = cm.last_parts;
+    if (!have || !out) return RT_OK;
+    const long long n = (long long)cm.key.nx * cm.key.local_rows;
+    if ((long long)cap < n) return invalid("rt_debug_cost_map: cap is smaller than the map (info is set)");
+    HIPCHK(hipMemcpy(out, cm.d, (size_t)n * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status rt_debug_set_cost_map(rt_scene* s, const uint32_t* in, int64_t n) {
+    if (!s) return invalid("rt_debug_set_cost_map: null scene");
+    if (!in) return invalid("rt_debug_set_cost_map: null argument");
+    if (!g_opt.cost_map) return invalid("rt_debug_set_cost_map: option cost_map is 0");
+    rt_scene::cost_map_state& cm = s->cost_map;
+    if (!cm.have_last_key) return invalid("rt_debug_set_cost_map: the scene has rendered no ranked frame");
+    if ((long long)n != (long long)cm.last_key.nx * cm.last_key.local_rows) return invalid("rt_debug_set_cost_map: n is not the last ranked frame's local pixel count");
+    RT_TRY(use_device(s->device));
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
+    std::vector<unsigned int> words((size_t)n);
+    unsigned long long total = 0;
+    for (size_t k = 0; k < (size_t)n; ++k) { words[k] = in[k] & 0x7FFFFFFFu; total += words[k]; }
+    cm.valid = false;
+    RT_TRY(grow(cm.d, cm.capacity, (size_t)n));
+    HIPCHK(hipMemcpy(cm.d, words.data(), (size_t)n * sizeof(unsigned int), hipMemcpyHostToDevice));
+    cm.key = cm.last_key; cm.scene_epoch = s->scene_epoch; cm.opt_epoch = g_opt_epoch; cm.total = total; cm.valid = true;
+    return RT_OK;
+}
+
 rt_status rt_debug_rank_info(rt_scene* s, uint32_t* out13) {
     if (!s) return invalid("rt_debug_rank_info: null scene");
     if (!out13) return invalid("rt_debug_rank_info: null argument");
@@ -2565,6 +2637,19 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     } else if (g_opt.lpt && kernel == RT_KERNEL_STAGED && f->ns >= 2 * g_opt.split_samples && n_tiles >= 64 && n_pixels < (1ull << 31)) {
         // ---- buffers
         RT_TRY(grow_ranked_buffers(s, n_tiles, n_pixels));
+        // ---- the scene's cost map (struct rt_scene): exact -- this very view was rendered last, under these options --, stale, or of no use
+        rt_scene::cost_map_state& cm = s->cost_map;
+        rt_scene::cost_map_key key;
+        key.nx = f->nx; key.ny = f->ny; key.tile_rows = f->tile_rows; key.tile_first = f->tile_first; key.tile_stride = f->tile_stride;
+        key.local_rows = g.local_rows; key.kernel_variant = out.kernel_variant;
+        if (g_opt.cost_map && cm.capacity < n_pixels) { cm.valid = false; RT_TRY(grow(cm.d, cm.capacity, n_pixels)); }
+        // The map is read by the lean family and by scenes without tier 1 (scanned in lockstep, or no tier data).  Where tier workgroups
+        // take main workgroups' slots (the other families with tier 1) it is written and not read: Book-2 final 800x800 @ 200 measured
+        // 246-249 ms in two parts and 251-262 ms in one (profiles/cost_map_mi355x.jsonl): its tier-1 chain
+        // bounds the frame either way.
+        const bool map_read = lean_family || !tier_possible;
+        const bool map_usable = g_opt.cost_map && g_opt.prior && map_read && cm.valid && cm.total > 0 && cm.key == key;
+        const bool map_exact = map_usable && cm.scene_epoch == s->scene_epoch && cm.opt_epoch == g_opt_epoch;
         if (tail_grid > 0) {
             // tail hand-off (rt_device.h): a lane hands off at most one pixel per launch, so the queue holds one entry per resident lane
             RT_TRY(grow(s->d_handoff, s->handoff_capacity, (size_t)g_num_cu * (size_t)per_cu_resident * (size_t)block.x));
@@ -2620,44 +2705,66 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
             RT_TRY(rank_pixels(q, grid_q, s->d_ray_counter));
             return launch_part(q, grid_q, true);
         };
-        // ---- part 1: samples [0, S_a); S_a = presplit_samples, or S0.  Nothing has been measured yet; with the cost prior
-        // (rt_prior_kernel: the calibration frame's rays per pixel, scaled to this frame) the part is ranked all the same,
-        // so that the dearest chains start on tier waves at sample 0 instead of running at an ordinary lane's pace.
-        const int first_end = (g_opt.presplit_samples > 0 && g_opt.presplit_samples < g_opt.split_samples) ? g_opt.presplit_samples : g_opt.split_samples;
-        HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));
-        rt_frame_params p1 = fp;
-        dim3 grid1 = grid;
-        p1.sample_end = first_end; p1.state_out = s->d_state; p1.tile_cost = s->d_tile_cost;
-        bool ranked1 = false;
-        if (g_opt.prior && s->d_cal_cost && s->cal_nx > 0 && s->cal_ny > 0) {
+        // the cost prior of a fresh part into d_state and d_tile_cost, its sum into d_ray_counter[3]: from the cost map, pixel for
+        // pixel, or from the calibration frame
+        auto launch_prior = [&](bool from_map) -> rt_status {
             rt_prior_params pp;
             memset(&pp, 0, sizeof(pp));
             pp.state = s->d_state; pp.tile_cost = s->d_tile_cost; pp.total = s->d_ray_counter + 3;
-            pp.cal_cost = s->d_cal_cost; pp.cal_nx = s->cal_nx; pp.cal_ny = s->cal_ny;
+            pp.cal_cost = from_map ? cm.d : s->d_cal_cost; pp.cal_nx = s->cal_nx; pp.cal_ny = s->cal_ny;
             pp.nx = f->nx; pp.ny = f->ny; pp.local_rows = g.local_rows; pp.tiles_x = g.tiles_x;
             pp.tile_rows = f->tile_rows; pp.tile_first = f->tile_first; pp.tile_stride = f->tile_stride;
-            HIPCHK(rt_launch_prior(pp, stream));
-            p1.state_in = s->d_state; p1.fresh = 1;
-            RT_TRY(rank_pixels(p1, grid1, s->d_ray_counter + 3));
-            HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));   // from here on: measured rays
-            ranked1 = true;
+            HIPCHK(from_map ? rt_launch_prior_map(pp, stream) : rt_launch_prior(pp, stream));
+            return RT_OK;
+        };
+        if (map_exact) {
+            // ---- one part: the map holds what every pixel of this view cost over a whole frame, measured -- better than any first look of
+            // this frame could -- so samples [0, ns) run as a single fresh part ranked on it: no parking, no second ranking, one tail
+            HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));
+            RT_TRY(launch_prior(true));
+            fp.state_in = s->d_state; fp.fresh = 1;
+            RT_TRY(rank_pixels(fp, grid, s->d_ray_counter + 3));
+        } else {
+            // ---- part 1: samples [0, S_a); S_a = presplit_samples, or S0.  Nothing has been measured yet; with the cost prior
+            // (rt_prior_kernel: the calibration frame's rays per pixel, scaled to this frame) the part is ranked all the same,
+            // so that the dearest chains start on tier waves at sample 0 instead of running at an ordinary lane's pace.
+            const int first_end = (g_opt.presplit_samples > 0 && g_opt.presplit_samples < g_opt.split_samples) ? g_opt.presplit_samples : g_opt.split_samples;
+            HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));
+            rt_frame_params p1 = fp;
+            dim3 grid1 = grid;
+            p1.sample_end = first_end; p1.state_out = s->d_state; p1.tile_cost = s->d_tile_cost;
+            bool ranked1 = false;
+            // A stale map (the camera or a sphere has moved since, or an option was set) is still the better prior: measured, at this
+            // frame's own resolution.
+            if (map_usable || (g_opt.prior && s->d_cal_cost && s->cal_nx > 0 && s->cal_ny > 0)) {
+                RT_TRY(launch_prior(map_usable));
+                p1.state_in = s->d_state; p1.fresh = 1;
+                RT_TRY(rank_pixels(p1, grid1, s->d_ray_counter + 3));
+                HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));   // from here on: measured rays
+                ranked1 = true;
+            }
+            RT_TRY(launch_part(p1, grid1, ranked1));
+            // ---- part 1b: samples [S_a, S0), with tiers ranked on the first S_a samples.
+            if (first_end < g_opt.split_samples) RT_TRY(ranked_part(first_end, g_opt.split_samples));
+            // ---- part 1c (optional): samples [S0, S1), ranked on the first S0 samples; the last part is then ranked again on
+            // S1 samples.  A pixel's cost over 32 samples is a noisy estimate of its cost over 500 (paths through glass are
+            // heavy-tailed): pixels that look cheap and are not start late and end the frame (tools/diag_wave_ends.py).
+            int last_begin = g_opt.split_samples;
+            if (g_opt.resplit_samples > g_opt.split_samples && f->ns >= 2 * g_opt.resplit_samples) {
+                RT_TRY(ranked_part(g_opt.split_samples, g_opt.resplit_samples));
+                last_begin = g_opt.resplit_samples;
+            }
+            // ---- last part: samples [S1 or S0, ns), ranked on everything rendered so far
+            fp.state_in = s->d_state; fp.sample_begin = last_begin;
+            RT_TRY(rank_pixels(fp, grid, s->d_ray_counter));
         }
-        RT_TRY(launch_part(p1, grid1, ranked1));
-        // ---- part 1b: samples [S_a, S0), with tiers ranked on the first S_a samples.
-        if (first_end < g_opt.split_samples) RT_TRY(ranked_part(first_end, g_opt.split_samples));
-        // ---- part 1c (optional): samples [S0, S1), ranked on the first S0 samples; the last part is then ranked again on
-        // S1 samples.  A pixel's cost over 32 samples is a noisy estimate of its cost over 500 (paths through glass are
-        // heavy-tailed): pixels that look cheap and are not start late and end the frame (tools/diag_wave_ends.py).
-        int last_begin = g_opt.split_samples;
-        if (g_opt.resplit_samples > g_opt.split_samples && f->ns >= 2 * g_opt.resplit_samples) {
-            RT_TRY(ranked_part(g_opt.split_samples, g_opt.resplit_samples));
-            last_begin = g_opt.resplit_samples;
-        }
-        // ---- last part: samples [S1 or S0, ns), ranked on everything rendered so far
-        fp.state_in = s->d_state; fp.sample_begin = last_begin;
-        RT_TRY(rank_pixels(fp, grid, s->d_ray_counter));
         out.workgroups = (int)grid.x;
         s->ranked_frame = true;
+        cm.last_key = key; cm.have_last_key = true;
+        if (g_opt.cost_map) {   // the last part's launches leave the next map; it counts from rt_frame_finish on
+            fp.cost_out = cm.d;
+            cm.valid = false; cm.key = key; cm.scene_epoch = s->scene_epoch; cm.opt_epoch = g_opt_epoch;
+        }
     }
 #ifdef RT_DIAG
     // wave-end histograms of the frame's last launch only (rt_debug_wave_ends)
@@ -2665,9 +2772,11 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     HIPCHK(hipMemsetAsync(s->d_ray_counter + RT_DIAG_HIST_SLOT, 0, (size_t)(2 * RT_DIAG_BINS + 7 + 2 * RT_DIAG_MAX_WAVES) * 8, stream));
 #endif
     RT_TRY(launch_part(fp, grid, s->ranked_frame));
+    if (s->ranked_frame) s->cost_map.last_parts = part_index;
     // ---- finish
     HIPCHK(hipEventRecord(s->ev_stop, stream));
     s->frame_pending = true;
+    s->cost_map.pending = fp.cost_out != nullptr;   // only a frame that was enqueued whole makes its map count (rt_frame_finish)
     s->pending_stream = stream;
     s->pending_stats = out;
     if (!fb_on_device) {

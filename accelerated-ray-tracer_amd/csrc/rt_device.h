@@ -157,6 +157,8 @@ struct rt_frame_params {
     int32_t handoff_pixels;
     int32_t handoff_poll_ticks;           // ... looked for this often (10 ns ticks of s_memrealtime)
     int32_t tail_mode;                    // tier kernel: serve handoff_queue instead of tier 1 of the heavy list
+    unsigned int* cost_out;               // last part of a ranked frame: every launch that writes a pixel's colour also writes the rays of its samples
+                                          // [0, ns) here, bit 31 clear (the scene's cost map, rt_abi.hip); null = not written
     uint64_t seed_base;
     int32_t nx, ny, ns;
     float gamma;
@@ -191,6 +193,8 @@ struct rt_prior_params {
     int32_t tile_rows, tile_first, tile_stride;
 };
 hipError_t rt_launch_prior(const rt_prior_params& pp, hipStream_t st);
+// the same from the scene's cost map (rt_abi.hip): `cal_cost` holds one word per local pixel of THIS frame geometry (cal_nx, cal_ny are not read)
+hipError_t rt_launch_prior_map(const rt_prior_params& pp, hipStream_t st);
 // bytes of the tier kernel's LDS image (rt_kernel_tier.h stages exactly this): leaf arrays + slot unions, then -- where the
 // launch plan (rt_abi.hip) says so -- spheres, materials and textures
 static inline size_t rt_tier_lds_bytes(int n_slots, int n_spheres, int n_materials, int n_textures, bool scene) {

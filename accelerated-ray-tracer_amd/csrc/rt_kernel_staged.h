@@ -413,6 +413,10 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                             } else if (fp.store_parked) store_pixel(fp, px_i, px_lrow, col);   // a progressive window: the frame so far
                         } else {
                             store_pixel(fp, px_i, px_lrow, col);
+                            if (fp.cost_out) {   // the scene's cost map: the pixel's rays over all its samples
+                                const size_t at = (size_t)px_lrow * fp.nx + px_i;
+                                fp.cost_out[at] = ((rays - rays_at_pixel_start) + ((fp.state_in && !fp.fresh) ? fp.state_in[at].cost : 0u)) & 0x7FFFFFFFu;
+                            }
                         }
                         have_pixel = false;
                     }

@@ -79,10 +79,12 @@ __global__ void __launch_bounds__(RANK_THREADS) rt_rank_tiles_kernel(rt_rank_par
         rt_rank_info inf;
         inf.heavy_items = 0u; inf.heavy_threshold = 0xFFFFFFFFu; inf.tier1_items = 0u; inf.tier2_items = 0u;
         inf.tier1_wgs = 0; inf.main_skip_wgs = 0; inf.sparse_wgs = 0; inf.sparse_stride = 1; inf.semi_wgs = 0; inf.semi_stride = 1;
-        inf.threshold1 = (unsigned int)(mean * (double)rp.tier1_factor + 0.999);
-        inf.threshold2 = (unsigned int)(mean * (double)rp.sparse_factor + 0.999);
+        // (costs are below 2^31, a multiple of their mean need not be: a map installed by rt_debug_set_cost_map may hold anything)
+        auto threshold = [mean](float factor) -> unsigned int { const double t = mean * (double)factor + 0.999; return t < 4294967295.0 ? (unsigned int)t : 0xFFFFFFFFu; };
+        inf.threshold1 = threshold(rp.tier1_factor);
+        inf.threshold2 = threshold(rp.sparse_factor);
         inf.collected = 0u;
-        if (rp.sparse_stride > 0) inf.heavy_threshold = (unsigned int)(mean * (double)rp.heavy_factor + 0.999);
+        if (rp.sparse_stride > 0) inf.heavy_threshold = threshold(rp.heavy_factor);
         *rp.info = inf;
     }
     const unsigned int* cost = rp.tile_cost;
@@ -250,11 +252,34 @@ __global__ void rt_prior_kernel(rt_prior_params pp) {
     if ((threadIdx.x & 63) == 0 && sum) atomicAdd(pp.total, sum);
 }
 
+// The same from the scene's cost map (rt_abi.hip): the rays every local pixel of this very frame geometry cost in the last ranked
+// frame, all its samples.  One word per local pixel, so the pixel's own word is its estimate: no resampling, no 3 x 3 maximum.
+__global__ void rt_prior_map_kernel(rt_prior_params pp) {
+    const unsigned int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned int n = (unsigned int)pp.local_rows * (unsigned int)pp.nx;
+    unsigned int est = 0u;
+    if (p < n) {
+        const unsigned int lrow = p / (unsigned int)pp.nx, i = p - lrow * (unsigned int)pp.nx;
+        est = pp.cal_cost[p] & 0x7FFFFFFFu;
+        pp.state[p].cost = est;
+        atomicAdd(&pp.tile_cost[(lrow >> 3) * (unsigned int)pp.tiles_x + (i >> 3)], est);
+    }
+    unsigned long long sum = est;
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(pp.total, sum);
+}
+
 }  // namespace
 
 hipError_t rt_launch_prior(const rt_prior_params& pp, hipStream_t st) {
     const unsigned int n = (unsigned int)pp.local_rows * (unsigned int)pp.nx;
     hipLaunchKernelGGL(rt_prior_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, pp);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_prior_map(const rt_prior_params& pp, hipStream_t st) {
+    const unsigned int n = (unsigned int)pp.local_rows * (unsigned int)pp.nx;
+    hipLaunchKernelGGL(rt_prior_map_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, pp);
     return hipGetLastError();
 }
 

@@ -849,6 +849,26 @@ rt_status rt_debug_prior(const uint32_t* cal_cost, int32_t cal_nx, int32_t cal_n
                          int32_t tile_stride, uint32_t* cost_out, uint32_t* tile_cost_out, uint64_t* total_out);
 rt_status rt_debug_cal_cost(rt_scene* scene, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny);
 rt_status rt_debug_rank_info(rt_scene* scene, uint32_t* out13);
+/* The cost map (option cost_map).  The last launches of a ranked frame leave, per local pixel, the rays the
+ * pixel cost over all its samples.  A pixel's cost depends on the scene, the camera, the frame geometry and the row partition,
+ * not on seed_base or ns, so the next ranked frame of the same scene uses the map once rt_frame_finish has closed the frame
+ * that wrote it:
+ *   exact -- same nx, ny, tile_rows, tile_first, tile_stride and kernel family, no rt_scene_set_camera / rt_scene_update_spheres
+ *            and no rt_set_option / rt_reset_options call since: the frame is ranked on the map and runs as ONE part;
+ *   stale -- same geometry, but the camera or a sphere was changed without recalibration, or an option call was made: the map
+ *            replaces the calibration frame as the prior of part 1 of the usual two parts.
+ * Kernel families whose tier workgroups take main workgroups' slots (scenes that are not spheres-only, or carry noise / image
+ * textures, and have tier 1) write the map and do not read it: they measured slower in one part.
+ * A change with recalibrate != 0 drops the map; a frame of another geometry does not use it and replaces it.  Unranked
+ * frames, windows, adaptive and variance frames neither read nor write it.  Scheduling only: no pixel changes.
+ * rt_debug_cost_map: a pending frame is closed first.  info[0] = 0 none / 1 exact / 2 stale (relative to the scene and the options
+ * as they are now; 0 while option cost_map is 0), info[1] = the map's nx, info[2] = its local rows, info[3] = the parts the last
+ * ranked frame ran as.  out[info[2]][info[1]] receives the map when it is not "none" and cap words hold it; a smaller cap is
+ * RT_ERR_INVALID (info is set).  out may be null with cap = 0: info only.
+ * rt_debug_set_cost_map: installs in[n] (bit 31 is cleared) as the exact map of the last ranked frame's geometry; n must be that
+ * frame's local pixel count.  RT_ERR_INVALID when the scene has rendered no ranked frame or option cost_map is 0. */
+rt_status rt_debug_cost_map(rt_scene* scene, uint32_t* out, int64_t cap, int32_t* info4);
+rt_status rt_debug_set_cost_map(rt_scene* scene, const uint32_t* in, int64_t n);
 
 /* Tuning knobs (for A/B measurements; defaults are what ships).  Unknown keys
  * return RT_ERR_INVALID.  The knobs are process-wide; rt_reset_options()

@@ -20,6 +20,10 @@ update_spheres; N times rt_reproject with every guide and rt_reproject_moving wi
 buffers -- with `none` the tables hold the second frame's records twice (no sphere moved: every pixel takes the static path
 after the records were read), with `all` the records of both frames.  It exits after the loop: the run to put under
 `rocprofv3 --kernel-trace --stats`; --kernel-stats FILE --moved X then appends the two kernels' rows and their ratio.
+--orbit-pair N is the stale prior in an animation loop: ONE scene, its camera switched between the 0 and the 20 degree view
+(recalibrate 0) before every frame, 2 N + 2 frames, the first two left out.  Since the cost map a scene that
+renders one view again runs warm, one-part frames, so (b)'s three scenes no longer show what a stale prior costs; here every
+frame's prior is the other view's -- the stale map, or, with a library from before the map, the stale calibration frame.
 One JSON line per measurement goes to stdout and, with --out, is appended to that file (profiles/reproject_mi355x.jsonl).
 """
 import argparse
@@ -111,6 +115,7 @@ def main():
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--moving-loop", type=int, default=0)
     ap.add_argument("--moved", choices=["none", "all"], default=None)
+    ap.add_argument("--orbit-pair", type=int, default=0)
     args = ap.parse_args()
     nx, ny = args.nx, args.ny
     if args.kernel_stats:
@@ -142,6 +147,29 @@ def main():
 
     if args.moving_loop:
         moving_loop(args, hs, dev)
+        return
+
+    if args.orbit_pair:
+        ds = art.DeviceScene(hs)
+        cams = [orbited(0.0, nx, ny), orbited(20.0, nx, ny)]
+        f = hs.frame(nx=nx, ny=ny, ns=args.ns)
+        fb = torch.empty((ny, nx, 3), dtype=torch.float32, device=dev)
+        ms = []
+        for it in range(2 * args.orbit_pair + 2):
+            ds.set_camera(cams[it & 1])
+            _, st = ds.render(f, out=fb.data_ptr())
+            if it >= 2:
+                ms.append(st.ms_render)
+        line = {"what": "rt_render, the camera switched between two views 20 degrees apart before every frame, recalibrate 0", "scene": "random_scene",
+                "nx": nx, "ny": ny, "ns": args.ns, "frames": len(ms), "median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3),
+                "max_ms": round(max(ms), 3), "library": "RT_LIB_OVERRIDE" if os.environ.get("RT_LIB_OVERRIDE") else "this build"}
+        if hasattr(ds, "cost_map") and hasattr(art.rt_lib(), "rt_debug_cost_map"):
+            line["parts_of_the_last_frame"] = ds.cost_map()[2]
+        ds.close()
+        print(json.dumps(line))
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(json.dumps(line) + "\n")
         return
 
     # ---- (a) the kernel

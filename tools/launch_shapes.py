@@ -7,6 +7,9 @@ hand-off took pixels, the passes of an adaptive frame, and the SHA-256 of the ou
   RT_LIB_OVERRIDE=<library of the parent commit> python tools/launch_shapes.py > parent.jsonl
   python tools/launch_shapes.py > new.jsonl && diff parent.jsonl new.jsonl
 
+RT_OPTS=key=value,... sets knobs for the whole run: with cost_map=0 (the cost map off, DESIGN.md 4.3c: the second render of a
+scene is ranked like its first) the output is that of a library from before the map.
+
 profiles/abi_refactor_launch_shapes.jsonl is this tool's output on an MI355X."""
 import ctypes as C
 import hashlib
@@ -22,6 +25,16 @@ sys.path.insert(0, ROOT)
 import accelerated_ray_tracer_amd as art   # noqa: E402
 
 art.init(0)
+
+
+def shipped_options():
+    art.reset_options()
+    for kv in filter(None, os.environ.get("RT_OPTS", "").split(",")):
+        k, v = kv.split("=")
+        art.set_option(k, int(v))
+
+
+shipped_options()
 L = art.rt_lib()
 L.rt_debug_handoff.argtypes = [C.c_void_p, C.c_void_p]
 
@@ -95,7 +108,7 @@ for scene in ("random_scene", "cornell"):
                 digest = sha(t.cpu().numpy(), ts.cpu().numpy())
             passes = [[p["route"], p["active"], p["samples"][0], p["samples"][1]] for p in ds.adaptive_passes()]
             emit(f"{scene} rt_render_adaptive 4..32 adaptive_tier={tier} {where} fb", fb_sha256=digest, passes=passes, **stats_dict(st))
-    art.reset_options()
+    shipped_options()
 
     for where in ("host", "device"):
         fv = hs.frame(nx=64, ny=64, ns=16)

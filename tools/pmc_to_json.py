@@ -11,6 +11,9 @@ dispatches / dispatches per step; counter passes serialise the kernels, so the t
 HBM bytes per step = (2 x FETCH_SIZE + WRITE_SIZE) x 1024: FETCH_SIZE is doubled as MI355X_MICROARCH.md (section HBM)
 prescribes for gfx950 (uncalibrated for this access pattern -- the traffic is 0.01 % of the roof either way).  The same sum
 over EVERY kernel of the frame, by kernel, is recorded as hbm_bytes_by_kernel: the accounting of the frame's HBM traffic.
+Since the cost map the first frame of a bench.py process is a cold, two-part frame and every later one a warm,
+one-part frame: leading frames with another number of main-kernel dispatches than the last frame are left out of every pass
+(from the process's start up to the cost-prior kernel that opens the first frame kept), and the record says so in `frames`.
 """
 import csv, glob, json, os, sys, collections
 
@@ -20,7 +23,7 @@ RENDER_KERNELS = ("rt_render_staged_kernel", "rt_tier_kernel")
 
 
 def short(name):
-    for key in ("rt_tier_kernel", "rt_render_staged_kernel", "rt_rank_tiles", "rt_collect_heavy", "rt_rank_heavy", "rt_prior_kernel", "fillBuffer", "copyBuffer"):
+    for key in ("rt_tier_kernel", "rt_render_staged_kernel", "rt_rank_tiles", "rt_collect_heavy", "rt_rank_heavy", "rt_prior_kernel", "rt_prior_map_kernel", "fillBuffer", "copyBuffer"):
         if key in name:
             return key
     return name.split("(")[0][:48]
@@ -36,7 +39,13 @@ def per_frame(sub):
     if not f:
         return {}, 0
     acc, disp = collections.defaultdict(float), set()
-    for r in csv.DictReader(open(f)):
+    rows_c = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Dispatch_Id"]))
+    if cold_main:   # leave the leading cold frames out: everything before the prior kernel that follows their last main dispatch
+        main_ids = sorted({int(r["Dispatch_Id"]) for r in rows_c if KERNEL in r["Kernel_Name"]})
+        cut = main_ids[cold_main - 1]
+        start = min((int(r["Dispatch_Id"]) for r in rows_c if int(r["Dispatch_Id"]) > cut and "rt_prior" in r["Kernel_Name"]), default=cut + 1)
+        rows_c = [r for r in rows_c if int(r["Dispatch_Id"]) >= start]
+    for r in rows_c:
         by_kernel[short(r["Kernel_Name"])][r["Counter_Name"]] += float(r["Counter_Value"])
         if not any(k in r["Kernel_Name"] for k in RENDER_KERNELS):
             continue
@@ -47,12 +56,13 @@ def per_frame(sub):
 
 
 by_kernel = collections.defaultdict(lambda: collections.defaultdict(float))
+cold_main = 0   # main-kernel dispatches of the leading frames left out (set below, from the kernel trace)
 
 
 out = {"workload": key, "source_dir": os.path.basename(d.rstrip("/")), "kernel": " + ".join(RENDER_KERNELS)}
 kt = find("trace", "*kernel_trace.csv")
 all_rows = list(csv.DictReader(open(kt)))
-rows = [r for r in all_rows if KERNEL in r["Kernel_Name"]]
+rows = sorted((r for r in all_rows if KERNEL in r["Kernel_Name"]), key=lambda r: int(r["Start_Timestamp"]))
 tier_rows = [r for r in all_rows if "rt_tier_kernel" in r["Kernel_Name"]]
 durs = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows]
 # dispatches per frame: a frame's last dispatch is its longest; frames = count of local maxima pattern -> use the argument or infer 3 / 1
@@ -60,6 +70,21 @@ durs = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in row
 long_ones = sum(1 for x in durs if x >= 0.5 * max(durs))
 per = int(sys.argv[3]) if len(sys.argv) > 3 else (len(durs) // long_ones if long_ones and len(durs) % long_ones == 0 else 1)
 frames = len(durs) // per
+if len(sys.argv) <= 3 and long_ones and len(durs) % long_ones != 0:
+    # frames of unequal shape: a frame ends with its long dispatch; keep the frames shaped like the last one
+    groups, cur = [], []
+    for x in durs:
+        cur.append(x)
+        if x >= 0.5 * max(durs):
+            groups.append(cur); cur = []
+    per = len(groups[-1])
+    n_cold = 0
+    while n_cold < len(groups) and len(groups[n_cold]) != per:
+        n_cold += 1
+    assert all(len(g) == per for g in groups[n_cold:]) and not cur, [len(g) for g in groups]
+    cold_main = sum(len(g) for g in groups[:n_cold])
+    durs, rows, frames = durs[cold_main:], rows[cold_main:], len(groups) - n_cold
+    out["frames"] = f"warm (one-part) frames: the first {n_cold} frame(s) of each run, ranked without the cost map, are left out"
 out["dispatches_per_step"] = per
 out["frames_profiled"] = frames
 out["kernel_ms_per_step_traced"] = round(sum(durs) / frames, 3)
