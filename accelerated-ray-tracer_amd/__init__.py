@@ -123,6 +123,11 @@ class RtSphereUpdate(C.Structure):
     _fields_ = [("count", C.c_int32), ("first", C.c_int32), ("indices", C.c_void_p), ("spheres", C.c_void_p)]
 
 
+class RtInstanceUpdate(C.Structure):
+    _fields_ = [("count", C.c_int32), ("first", C.c_int32), ("indices", C.c_void_p), ("instances", C.c_void_p)]
+
+
+RT_INST_ROTATE_Y, RT_INST_TRANSLATE = 1, 2
 RT_TRACE_CLOSEST, RT_TRACE_ANY = 0, 1
 RT_PRIM_SPHERE, RT_PRIM_QUAD, RT_PRIM_BOX, RT_PRIM_INSTANCE, RT_PRIM_MEDIUM = range(5)
 
@@ -176,7 +181,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_denoise_variance", "rt_scene_set_camera", "rt_scene_get_camera", "rt_multi_set_camera", "rt_reproject",
                   "rt_reproject_matrix", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info",
                   "rt_scene_update_spheres", "rt_scene_get_spheres", "rt_multi_update_spheres", "rt_refit_nodes", "rt_debug_scene_boxes",
-                  "rt_reproject_moving", "rt_debug_cost_map", "rt_debug_set_cost_map"]
+                  "rt_reproject_moving", "rt_debug_cost_map", "rt_debug_set_cost_map",
+                  "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances"]
 
 _rt = None
 _host = None
@@ -209,6 +215,7 @@ def host_lib():
         L.rtw_scene_defaults.restype = C.c_float
         L.rtw_scene_defaults.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]
         L.rtw_scene_leaf_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rtw_rotation.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.rtw_write_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.rtw_load_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rtw_camera_init.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float,
@@ -270,6 +277,10 @@ def rt_lib():
         L.rt_scene_get_spheres.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.rt_multi_update_spheres.argtypes = [C.c_void_p, C.POINTER(RtSphereUpdate), C.c_int]
         L.rt_refit_nodes.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(RtSphereUpdate), C.c_void_p, C.c_void_p]
+        L.rt_scene_update_instances.argtypes = [C.c_void_p, C.POINTER(RtInstanceUpdate), C.c_int, C.c_int, C.c_void_p]
+        L.rt_scene_get_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.rt_multi_update_instances.argtypes = [C.c_void_p, C.POINTER(RtInstanceUpdate), C.c_int]
+        L.rt_refit_instances.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(RtInstanceUpdate), C.c_void_p, C.c_void_p]
         L.rt_debug_scene_boxes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_reproject.argtypes = [C.POINTER(RtReprojectDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_reproject_matrix.argtypes = [C.POINTER(RtCamera), C.POINTER(C.c_float)]
@@ -720,26 +731,36 @@ def _chain_args(max_bounces, fuzz_limit):
     return int(max_bounces), fuzz_limit
 
 
-def _sphere_update(spheres, indices, first):
-    """An RtSphereUpdate over host records and what keeps its arrays alive.  ValueError for malformed arguments."""
-    if not isinstance(spheres, np.ndarray) or spheres.dtype != SPHERE_DTYPE or spheres.ndim != 1:
-        raise ValueError("spheres: a one-dimensional numpy array of SPHERE_DTYPE is expected")
-    rec = np.ascontiguousarray(spheres)
-    u = RtSphereUpdate()
+# the two kinds of record update: the argument's name, its dtype and its structure (whose record pointer carries the name)
+_SPHERES = ("spheres", "sphere", SPHERE_DTYPE, "SPHERE_DTYPE", RtSphereUpdate)
+_INSTANCES = ("instances", "instance", INSTANCE_DTYPE, "INSTANCE_DTYPE", RtInstanceUpdate)
+
+
+def _record_update(kind, records, indices, first):
+    """An RtSphereUpdate / RtInstanceUpdate over host records and what keeps its arrays alive.  ValueError for malformed arguments."""
+    name, one, dtype, dtype_name, struct = kind
+    if not isinstance(records, np.ndarray) or records.dtype != dtype or records.ndim != 1:
+        raise ValueError(f"{name}: a one-dimensional numpy array of {dtype_name} is expected")
+    rec = np.ascontiguousarray(records)
+    u = struct()
     u.count, u.first = len(rec), int(first)
-    u.spheres = rec.ctypes.data
-    idx = _update_indices(indices, len(rec), u)
+    setattr(u, name, rec.ctypes.data)
+    idx = _update_indices(indices, len(rec), u, one)
     return u, (rec, idx)
 
 
-def _update_indices(indices, count, u):
+def _sphere_update(spheres, indices, first):
+    return _record_update(_SPHERES, spheres, indices, first)
+
+
+def _update_indices(indices, count, u, one="sphere"):
     if indices is None:
         return None
     idx = np.asarray(indices)
     if idx.ndim != 1 or len(idx) != count or not np.issubdtype(idx.dtype, np.integer):
         raise ValueError(f"indices: {count} integers are expected, one per record")
     if len(idx) and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
-        raise ValueError("indices: sphere index out of range")
+        raise ValueError(f"indices: {one} index out of range")
     idx = np.ascontiguousarray(idx, np.int32)
     u.indices = idx.ctypes.data
     return idx
@@ -756,6 +777,40 @@ def refit_nodes(desc: RtSceneDesc, spheres, indices=None, first: int = 0):
         raise ValueError(L.rt_last_error_detail().decode())
     _check(st, "rt_refit_nodes")
     return nodes, out
+
+
+def refit_instances(desc: RtSceneDesc, instances, indices=None, first: int = 0):
+    """rt_refit_instances, host only: the description that DeviceScene.update_instances(instances, indices, first) is equivalent
+    to.  Returns (nodes, instances) of it as NODE_DTYPE / INSTANCE_DTYPE arrays.  ValueError when the update is refused."""
+    u, keep = _record_update(_INSTANCES, instances, indices, first)
+    nodes, out = np.zeros(desc.n_nodes, NODE_DTYPE), np.zeros(desc.n_instances, INSTANCE_DTYPE)
+    L = rt_lib()
+    st = L.rt_refit_instances(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data)
+    if st == 1:
+        raise ValueError(L.rt_last_error_detail().decode())
+    _check(st, "rt_refit_instances")
+    return nodes, out
+
+
+def instance_record(child: int, angle_degrees=None, offset=None) -> np.ndarray:
+    """One INSTANCE_DTYPE record (shape (1,)) of translate(rotate_y(child, angle_degrees), offset), either half left out when
+    its argument is None -- at least one must be given.  sin_t and cos_t come from the reference's own float arithmetic
+    (rad = angle * 0.017453292519943295769f, then libm's sinf / cosf, through the host library): what a flattened scene with
+    that rotation holds.  child: the prim ref the scene holds for the instance (DeviceScene.instances()[i]["child"])."""
+    if angle_degrees is None and offset is None:
+        raise ValueError("instance_record: an angle, an offset or both are expected")
+    rec = np.zeros(1, INSTANCE_DTYPE)
+    rec["cos_t"], rec["child"] = 1.0, child
+    if angle_degrees is not None:
+        s, c = C.c_float(), C.c_float()
+        if host_lib().rtw_rotation(float(angle_degrees), C.byref(s), C.byref(c)) != 0:
+            raise RtError("rtw_rotation failed")
+        rec["sin_t"], rec["cos_t"] = s.value, c.value
+        rec["flags"] |= RT_INST_ROTATE_Y
+    if offset is not None:
+        rec["offset"] = np.asarray(offset, np.float32).reshape(3)
+        rec["flags"] |= RT_INST_TRANSLATE
+    return rec
 
 
 class DeviceScene:
@@ -799,27 +854,44 @@ class DeviceScene:
         when the update is complete.  indices: integers, host memory always.  Malformed arguments, an index out of range or
         given twice, a non-finite record, a material out of range and a sphere under an instance raise ValueError before
         anything is launched; a bad record in a device tensor raises it after the others were applied."""
+        self._update_records(_SPHERES, "rt_scene_update_spheres", spheres, indices, first, recalibrate, stream)
+
+    def update_instances(self, instances, indices=None, first: int = 0, recalibrate: bool = False, stream=None) -> None:
+        """New records for instances of the scene as it stands on the device (rt_scene_update_instances): record k replaces
+        instance indices[k], or instance first + k without indices; sin_t, cos_t, offset and flags (1, 2 or 3) may change, child
+        must be the scene's own (see instance_record).  The boxes that depend on them are refit on the device and every later
+        frame and query is what a scene created from the changed description gives.  recalibrate: as update_spheres.
+
+        instances: a numpy array of INSTANCE_DTYPE -- copied to the device -- or a contiguous torch tensor of shape (count, 8),
+        float32 or int32, on the scene's device, read in place: the eight words of rt_instance per row.  stream, indices and the
+        argument errors are update_spheres'.  An index out of range or given twice, a non-finite record, bad flags and another
+        child raise ValueError before anything is launched; a bad record in a device tensor raises it after the others were
+        applied."""
+        self._update_records(_INSTANCES, "rt_scene_update_instances", instances, indices, first, recalibrate, stream)
+
+    def _update_records(self, kind, entry, records, indices, first, recalibrate, stream):
+        name, one, _, dtype_name, struct = kind
         L = rt_lib()
-        if isinstance(spheres, np.ndarray):
+        if isinstance(records, np.ndarray):
             if stream is not None:
                 raise ValueError("stream: only a device tensor is enqueued on a torch stream")
-            u, keep = _sphere_update(spheres, indices, first)
+            u, keep = _record_update(kind, records, indices, first)
             on_device, stream_p = 0, None
         else:
             import torch
             dev = torch.device("cuda", self.device)
-            if not isinstance(spheres, torch.Tensor):
-                raise ValueError("spheres: a numpy array of SPHERE_DTYPE or a torch tensor is expected")
-            if spheres.device != dev:
-                raise ValueError(f"spheres: tensor on {spheres.device}, the scene is on {dev}")
-            if spheres.ndim != 2 or spheres.shape[1] != 8 or spheres.element_size() != 4:
-                raise ValueError(f"spheres: shape {tuple(spheres.shape)} of {spheres.dtype}, expected (count, 8) of a 4-byte dtype")
-            if not spheres.is_contiguous():
-                raise ValueError("spheres: a contiguous tensor is expected (it is read in place)")
-            u = RtSphereUpdate()
-            u.count, u.first = int(spheres.shape[0]), int(first)
-            u.spheres = spheres.data_ptr() if u.count else None
-            keep = (spheres, _update_indices(indices, u.count, u))
+            if not isinstance(records, torch.Tensor):
+                raise ValueError(f"{name}: a numpy array of {dtype_name} or a torch tensor is expected")
+            if records.device != dev:
+                raise ValueError(f"{name}: tensor on {records.device}, the scene is on {dev}")
+            if records.ndim != 2 or records.shape[1] != 8 or records.element_size() != 4:
+                raise ValueError(f"{name}: shape {tuple(records.shape)} of {records.dtype}, expected (count, 8) of a 4-byte dtype")
+            if not records.is_contiguous():
+                raise ValueError(f"{name}: a contiguous tensor is expected (it is read in place)")
+            u = struct()
+            u.count, u.first = int(records.shape[0]), int(first)
+            setattr(u, name, records.data_ptr() if u.count else None)
+            keep = (records, _update_indices(indices, u.count, u, one))
             if u.count == 0:
                 return
             current = torch.cuda.current_stream(dev)
@@ -827,18 +899,24 @@ class DeviceScene:
                 stream = current
             elif stream != current:
                 stream.wait_stream(current)
-                spheres.record_stream(stream)
+                records.record_stream(stream)
             on_device, stream_p = 1, C.c_void_p(stream.cuda_stream)
-        st = L.rt_scene_update_spheres(self._p, C.byref(u), on_device, 1 if recalibrate else 0, stream_p)
+        st = getattr(L, entry)(self._p, C.byref(u), on_device, 1 if recalibrate else 0, stream_p)
         del keep
         if st == 1:
             raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_scene_update_spheres")
+        _check(st, entry)
 
     def spheres(self) -> np.ndarray:
         """The sphere records the next frame uses (rt_scene_get_spheres): the description's, with every update applied."""
         out = np.zeros(self.host.desc.n_spheres, SPHERE_DTYPE)
         _check(rt_lib().rt_scene_get_spheres(self._p, out.ctypes.data, len(out)), "rt_scene_get_spheres")
+        return out
+
+    def instances(self) -> np.ndarray:
+        """The instance records the next frame uses (rt_scene_get_instances): the description's, with every update applied."""
+        out = np.zeros(self.host.desc.n_instances, INSTANCE_DTYPE)
+        _check(rt_lib().rt_scene_get_instances(self._p, out.ctypes.data, len(out)), "rt_scene_get_instances")
         return out
 
     COST_MAP_STATES = ("none", "exact", "stale")
@@ -1452,6 +1530,16 @@ class MultiScene:
         if st == 1:
             raise ValueError(L.rt_last_error_detail().decode())
         _check(st, "rt_multi_update_spheres")
+
+    def update_instances(self, instances, indices=None, first: int = 0, recalibrate: bool = False) -> None:
+        """DeviceScene.update_instances with host records on every replica (rt_multi_update_instances)."""
+        L = rt_lib()
+        u, keep = _record_update(_INSTANCES, instances, indices, first)
+        st = L.rt_multi_update_instances(self._p, C.byref(u), 1 if recalibrate else 0)
+        del keep
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_multi_update_instances")
 
     def render(self, frame: RtFrameDesc, tile_rows: int = 4):
         """The whole frame as float32[ny][nx][3] in host memory, and the summed statistics."""

@@ -251,7 +251,7 @@ struct rt_scene {
     // image in d_adapt_spp: 4 bytes per pixel either way)
     double* d_var_acc = nullptr;
     size_t var_capacity = 0;                     // in doubles: three per pixel
-    // rt_scene_update_spheres: the lookup tables of the refit kernels, built on the scene's first update from a
+    // rt_scene_update_spheres, rt_scene_update_instances: the lookup tables of the refit kernels, built on the scene's first update from a
     // read-back of the node arrays, so that a scene that never moves pays nothing; refit.block holds all of them
     int32_t n_instances = 0, n_media = 0;        // of the description (rt_scene_dev carries neither)
     struct refit_tables {
@@ -259,9 +259,10 @@ struct rt_scene {
         void* block = nullptr;                   // one allocation, cut into the arrays of `p`
         rt_refit_params p;                       // the per-scene half of the kernels' argument, filled once
         std::vector<char> instanced;             // per sphere: the child of an instance (kept from rt_scene_create, host only)
-        uint32_t epoch = 0;
+        std::vector<int32_t> inst_child;         // per instance: its child, which no update changes (the same)
+        uint32_t epoch = 0, inst_epoch = 0;      // of the spheres' and of the instances' stamps
         int32_t* d_indices = nullptr;            // the update's index list and (host records) its records on the device
-        rt_sphere* d_records = nullptr;
+        rt_sphere* d_records = nullptr;          // (32-byte records of either kind)
         size_t indices_capacity = 0, records_capacity = 0;
     } refit;
 };
@@ -1145,6 +1146,7 @@ rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_sce
     s->dev.n_spheres = d->n_spheres;
     s->n_instances = d->n_instances; s->n_media = d->n_media;
     s->refit.instanced = rt_refit::instanced_spheres(d->instances, d->n_instances, d->n_spheres);   // (host only: an update's checks need no HIP call)
+    for (int i = 0; i < d->n_instances; ++i) s->refit.inst_child.push_back(d->instances[i].child);
     s->dev.n_materials = d->n_materials; s->dev.n_textures = d->n_textures;
     s->shade_bytes = (size_t)d->n_materials * sizeof(rt_material) + (size_t)d->n_textures * sizeof(rt_texture);
     s->dev.camera = d->camera;
@@ -1434,7 +1436,7 @@ rt_status build_refit_tables(rt_scene* s) {
     if (s->n_media) HIPCHK(hipMemcpy(media.data(), s->dev.media, media.size() * sizeof(rt_medium), hipMemcpyDeviceToHost));
 
     // leaves by ordinal, and one job per interior node: (node, first leaf, end leaf, array)
-    std::vector<int32_t> leaf_sphere, leaf_node_ref, leaf_node_walk;
+    std::vector<int32_t> leaf_sphere, leaf_instance, leaf_node_ref, leaf_node_walk;
     std::vector<float> box_lo, box_hi;
     std::vector<int4> jobs;
     auto scan = [&](const std::vector<rt_node>& nodes, int which, std::vector<int32_t>& leaf_node) -> bool {
@@ -1455,23 +1457,27 @@ rt_status build_refit_tables(rt_scene* s) {
     if (s->dev.leaf_lo && s->dev.n_leaves != m) return invalid("rt_scene_update_spheres: the tier data do not hold the reference tree's leaves");
     const int slots = (m + 63) / 64;
     leaf_sphere.assign((size_t)m, -1);
+    leaf_instance.assign((size_t)m, -1);
     box_lo.assign((size_t)slots * 64 * 4, 0.0f); box_hi.assign((size_t)slots * 64 * 4, 0.0f);
     for (int q = 0; q < m; ++q) {
         const rt_node& n = ref[(size_t)leaf_node_ref[(size_t)q]];
         if (own_walk && walk[(size_t)leaf_node_walk[(size_t)q]].prim != n.prim) return invalid("rt_scene_update_spheres: the walk array's leaves are not in the reference tree's order");
         leaf_sphere[(size_t)q] = rt_refit::leaf_sphere(n.prim, media.data(), s->n_media, n_spheres);
+        leaf_instance[(size_t)q] = rt_refit::leaf_instance(n.prim, media.data(), s->n_media, s->n_instances);
         for (int c = 0; c < 3; ++c) { box_lo[(size_t)q * 4 + c] = n.bmin[c]; box_hi[(size_t)q * 4 + c] = n.bmax[c]; }
     }
     if (!own_walk) leaf_node_walk.clear();
 
-    // one block, every piece 256-byte aligned: stamps, the three leaf tables, the canonical boxes, slot unions and maxima, jobs, result
+    // one block, every piece 256-byte aligned: both stamp arrays, the four leaf tables, the canonical boxes, slot unions and maxima, jobs, result
     const bool tier = s->dev.slot_ranges != nullptr;
     struct piece { size_t bytes; const void* src; void** dst; };
-    uint32_t* stamp = nullptr; int32_t *d_ls = nullptr, *d_lr = nullptr, *d_lw = nullptr; float4 *d_lo = nullptr, *d_hi = nullptr;
+    uint32_t *stamp = nullptr, *inst_stamp = nullptr; int32_t *d_ls = nullptr, *d_li = nullptr, *d_lr = nullptr, *d_lw = nullptr; float4 *d_lo = nullptr, *d_hi = nullptr;
     float *d_slot = nullptr, *d_abs = nullptr, *d_result = nullptr; int4* d_jobs = nullptr;
     const piece pieces[] = {
         {(size_t)n_spheres * 4, nullptr, (void**)&stamp},
+        {(size_t)s->n_instances * 4, nullptr, (void**)&inst_stamp},
         {leaf_sphere.size() * 4, leaf_sphere.data(), (void**)&d_ls},
+        {leaf_instance.size() * 4, leaf_instance.data(), (void**)&d_li},
         {leaf_node_ref.size() * 4, leaf_node_ref.data(), (void**)&d_lr},
         {leaf_node_walk.size() * 4, leaf_node_walk.data(), (void**)&d_lw},
         {box_lo.size() * 4, box_lo.data(), (void**)&d_lo},
@@ -1507,7 +1513,29 @@ rt_status build_refit_tables(rt_scene* s) {
     p.slot_abs = d_abs;
     p.jobs = d_jobs; p.n_jobs = (int32_t)jobs.size();
     p.result = d_result;
+    p.inst_stamp = inst_stamp; p.instances = const_cast<rt_instance*>(s->dev.instances); p.leaf_instance = d_li;
+    p.quads = s->dev.quads; p.boxes = s->dev.boxes;
     t.ready = true;
+    return RT_OK;
+}
+
+// The launches of an update whose records and indices are in place, the read-back of the bound and the flag, and the cost half
+// of the calibration when asked for (as rt_scene_set_camera)
+rt_status run_refit(rt_scene* s, const rt_refit_params& p, bool instances, hipStream_t stream, int recalibrate, bool& refused) {
+    HIPCHK(hipMemsetAsync(p.result, 0, 16, stream));
+    HIPCHK(instances ? rt_launch_refit_instances(p, stream) : rt_launch_refit(p, stream));
+    float result[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    HIPCHK(hipMemcpyAsync(result, p.result, sizeof(result), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int c = 0; c < 3; ++c) s->dev.bound[c] = result[c];
+    uint32_t flag = 0;
+    memcpy(&flag, &result[3], 4);
+    refused = flag != 0;
+    if (recalibrate && s->d_cal_cost) {
+        std::vector<double> pass;
+        double rays = 0.0;
+        RT_TRY(measure_pass_counts(s, s->dev.nodes_ref, s->dev.n_nodes_ref, pass, rays, nullptr, 0, /*keep_cost=*/true));
+    }
     return RT_OK;
 }
 }  // namespace
@@ -1547,19 +1575,8 @@ rt_status rt_scene_update_spheres(rt_scene* s, const rt_sphere_update* u, int sp
         HIPCHK(hipMemcpyAsync(t.d_records, u->spheres, (size_t)u->count * sizeof(rt_sphere), hipMemcpyHostToDevice, stream));
         p.records = t.d_records;
     }
-    HIPCHK(hipMemsetAsync(p.result, 0, 16, stream));
-    HIPCHK(rt_launch_refit(p, stream));
-    float result[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    HIPCHK(hipMemcpyAsync(result, p.result, sizeof(result), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    for (int c = 0; c < 3; ++c) s->dev.bound[c] = result[c];
-    uint32_t refused = 0;
-    memcpy(&refused, &result[3], 4);
-    if (recalibrate && s->d_cal_cost) {   // as rt_scene_set_camera: the cost half of the calibration alone
-        std::vector<double> pass;
-        double rays = 0.0;
-        RT_TRY(measure_pass_counts(s, s->dev.nodes_ref, s->dev.n_nodes_ref, pass, rays, nullptr, 0, /*keep_cost=*/true));
-    }
+    bool refused = false;
+    RT_TRY(run_refit(s, p, /*instances=*/false, stream, recalibrate, refused));
     if (refused) return invalid((who + "a device-resident record has a non-finite field or a material out of range; it was not stored, every other record was").c_str());
     return RT_OK;
 }
@@ -1592,6 +1609,81 @@ rt_status rt_refit_nodes(const rt_scene_desc* d, const rt_sphere_update* u, rt_n
         if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
     }
     if (spheres_out && d->n_spheres) memcpy(spheres_out, spheres.data(), spheres.size() * sizeof(rt_sphere));
+    return RT_OK;
+}
+
+// ---- rt_scene_update_instances (include/rt_abi.h): the same tables and the same unions; the records kernel and
+// the leaf kernel are the instances' own.  The scene holds one copy of the instance records, s->dev.instances, which every
+// kernel reads through its scene view; nothing is staged from them at creation or at launch time.
+rt_status rt_scene_update_instances(rt_scene* s, const rt_instance_update* u, int instances_on_device, int recalibrate, void* stream_v) {
+    static_assert(sizeof(rt_instance) == sizeof(rt_sphere), "the staging buffer of an update holds 32-byte records of either kind");
+    const std::string who = "rt_scene_update_instances: ";
+    if (!s) return invalid((who + "null scene").c_str());
+    rt_scene::refit_tables& t = s->refit;
+    const std::string why = rt_refit::check_instance_update(u, !instances_on_device, t.inst_child.data(), s->n_instances);
+    if (!why.empty()) return invalid((who + why).c_str());
+    if (u->count == 0) return RT_OK;
+    RT_TRY(use_device(s->device));
+    RT_TRY(build_refit_tables(s));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (instances_on_device) {
+        const traced_ptr records[] = {{u->instances, (size_t)u->count * sizeof(rt_instance), "instances", 4}};
+        RT_TRY(check_trace_ptrs(records, s->device, "rt_scene_update_instances"));
+    }
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
+    ++s->scene_epoch;                                // the cost map: as rt_scene_update_spheres
+    if (recalibrate) s->cost_map.valid = false;
+    rt_refit_params p = t.p;
+    p.count = u->count; p.first = u->first;
+    if (++t.inst_epoch == 0) { HIPCHK(hipMemsetAsync(p.inst_stamp, 0, (size_t)s->n_instances * 4, stream)); t.inst_epoch = 1; }
+    p.inst_epoch = t.inst_epoch;
+    if (u->indices) {
+        RT_TRY(grow(t.d_indices, t.indices_capacity, (size_t)u->count));
+        HIPCHK(hipMemcpyAsync(t.d_indices, u->indices, (size_t)u->count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        p.indices = t.d_indices;
+    }
+    if (instances_on_device) p.inst_records = u->instances;
+    else {
+        RT_TRY(grow(t.d_records, t.records_capacity, (size_t)u->count));
+        HIPCHK(hipMemcpyAsync(t.d_records, u->instances, (size_t)u->count * sizeof(rt_instance), hipMemcpyHostToDevice, stream));
+        p.inst_records = reinterpret_cast<const rt_instance*>(t.d_records);
+    }
+    bool refused = false;
+    RT_TRY(run_refit(s, p, /*instances=*/true, stream, recalibrate, refused));
+    if (refused) return invalid((who + "a device-resident record has a non-finite field, flags outside 1..3 or a child other than the scene's; it was not stored, every other record was").c_str());
+    return RT_OK;
+}
+
+rt_status rt_scene_get_instances(const rt_scene* s, rt_instance* out, int32_t cap) {
+    if (!s) return invalid("rt_scene_get_instances: null scene");
+    if (!out) return invalid("rt_scene_get_instances: null output pointer");
+    if (cap < s->n_instances) return invalid("rt_scene_get_instances: cap is below the scene's instance count");
+    RT_TRY(use_device(s->device));
+    if (s->n_instances) HIPCHK(hipMemcpy(out, s->dev.instances, (size_t)s->n_instances * sizeof(rt_instance), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status rt_refit_instances(const rt_scene_desc* d, const rt_instance_update* u, rt_node* nodes_out, rt_instance* instances_out) {
+    bool so = false, uv = false;
+    int tx = 0;
+    RT_TRY(validate(d, so, tx, uv));
+    std::vector<int32_t> children;
+    for (int i = 0; i < d->n_instances; ++i) children.push_back(d->instances[i].child);
+    const std::string why = rt_refit::check_instance_update(u, true, children.data(), d->n_instances);
+    if (!why.empty()) return invalid(("rt_refit_instances: " + why).c_str());
+    std::vector<rt_instance> instances(d->instances, d->instances + d->n_instances);
+    std::vector<char> moved((size_t)d->n_instances, 0);
+    for (int32_t k = 0; k < u->count; ++k) {
+        const int32_t i = u->indices ? u->indices[k] : u->first + k;
+        instances[(size_t)i] = u->instances[k];
+        moved[(size_t)i] = 1;
+    }
+    if (nodes_out) {
+        std::vector<rt_node> nodes(d->nodes, d->nodes + d->n_nodes);
+        rt_refit::refit_instance_nodes(nodes.data(), d, instances.data(), moved);
+        if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
+    }
+    if (instances_out && d->n_instances) memcpy(instances_out, instances.data(), instances.size() * sizeof(rt_instance));
     return RT_OK;
 }
 

@@ -441,6 +441,7 @@ hipError_t rt_launch_reproject_moving(bool normals_on, bool motion_on, const rt_
 // rt_scene_update_spheres (rt_kernel_refit.hip; include/rt_abi.h): the moved spheres' records, their leaves'
 // boxes in every array that holds them, the per-64-leaf unions, the scene's coordinate bound and every interior box of both
 // node arrays, as four small launches on one stream.  The lookup tables are built by rt_abi.hip on a scene's first update.
+// rt_scene_update_instances runs on the same tables with a records and a leaf kernel of its own.
 #define RT_REFIT_THREADS 256
 struct rt_refit_params {
     // the update: record k replaces sphere indices[k] (indices null: first + k); the indices were checked on the host
@@ -468,5 +469,14 @@ struct rt_refit_params {
     const int4* jobs;
     int32_t n_jobs;
     float* result;                        // [0..2] the scene's bound, [3] (as uint32) != 0: a record was refused on the device
+    // rt_scene_update_instances: count, first, indices as above; record k replaces instance indices[k]
+    const rt_instance* inst_records;
+    uint32_t inst_epoch;                  // inst_stamp[i] == inst_epoch: instance i was replaced by this update
+    uint32_t* inst_stamp;                 // per instance; apart from the spheres' stamps, with an epoch of its own
+    rt_instance* instances;               // the scene's (rt_scene_dev.instances)
+    const int32_t* leaf_instance;         // the instance leaf q's box follows, or -1
+    const rt_quad* quads;                 // the scene's: an instance's child box is computed from the records where they live
+    const rt_box* boxes;
 };
-hipError_t rt_launch_refit(const rt_refit_params& p, hipStream_t st);
+hipError_t rt_launch_refit(const rt_refit_params& p, hipStream_t st);             // a sphere update
+hipError_t rt_launch_refit_instances(const rt_refit_params& p, hipStream_t st);   // an instance update: two kernels of its own, then the same unions

@@ -1,5 +1,6 @@
-// rt_kernel_refit.hip -- the device half of rt_scene_update_spheres (include/rt_abi.h): spheres of a resident
-// scene are replaced and every box that depends on them is recomputed where it lives, with the topology of every array kept.
+// rt_kernel_refit.hip -- the device half of rt_scene_update_spheres and rt_scene_update_instances (include/rt_abi.h; DESIGN.md
+// 4.15, 4.17): spheres or instances of a resident scene are replaced and every box that depends on them is recomputed where it
+// lives, with the topology of every array kept.
 //
 // Four launches on one stream, each complete before the next starts (that order is the only synchronisation there is):
 //   1. records   one lane per record: check it (device-resident records reach no host check), store it, stamp its sphere;
@@ -9,6 +10,8 @@
 //   4. interior  one wave per interior node of either array: the union over its leaf range [a, b) as partial head leaves, whole
 //                slots from step 3 and partial tail leaves -- at most 126 + (b - a) / 64 reads whatever the tree's shape --;
 //                one further wave reduces the slots' largest coordinates to the scene's bound.
+// An instance update runs steps 1 and 2 as kernels of its own (rt_refit_instance_records_kernel, _leaves_kernel) and steps 3 and
+// 4 unchanged.
 // Float min / max are exact, so no result depends on the order of a reduction (up to the sign of a zero).  No address depends
 // on record data: every index comes from the host's tables or from the index list the host has checked.
 // The render kernels read some of these arrays through the scalar cache (uniform_load, rt_device_funcs.h); that stays correct
@@ -57,13 +60,8 @@ __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_records_kernel(cons
     p.stamp[i] = p.epoch;
 }
 
-__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_leaves_kernel(const rt_refit_params p) {
-    const int q = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
-    if (q >= p.n_leaves) return;
-    const int si = p.leaf_sphere[q];
-    if (si < 0 || p.stamp[si] != p.epoch) return;
-    float lo[3], hi[3];
-    rt_refit::sphere_box(p.spheres[si], lo, hi);
+// leaf q's new box, everywhere it lives: the canonical arrays, the tier arrays (xyz only) and the leaf's node in both node arrays
+__device__ inline void store_leaf(const rt_refit_params& p, int q, const float lo[3], const float hi[3]) {
     p.box_lo[q] = make_float4(lo[0], lo[1], lo[2], 0.0f);
     p.box_hi[q] = make_float4(hi[0], hi[1], hi[2], 0.0f);
     if (p.tier_lo) {
@@ -77,6 +75,44 @@ __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_leaves_kernel(const
         n = p.nodes_walk + p.leaf_node_walk[q];
         for (int c = 0; c < 3; ++c) { n->bmin[c] = lo[c]; n->bmax[c] = hi[c]; }
     }
+}
+
+__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_leaves_kernel(const rt_refit_params p) {
+    const int q = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
+    if (q >= p.n_leaves) return;
+    const int si = p.leaf_sphere[q];
+    if (si < 0 || p.stamp[si] != p.epoch) return;
+    float lo[3], hi[3];
+    rt_refit::sphere_box(p.spheres[si], lo, hi);
+    store_leaf(p, q, lo, hi);
+}
+
+// An instance record is stored when it passes the checks and names the child the scene holds for that instance, so the stored
+// child never changes: it stays the reference rt_scene_create validated, and the leaf kernel forms addresses from nothing else.
+__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_instance_records_kernel(const rt_refit_params p) {
+    const int k = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
+    if (k >= p.count) return;
+    const int i = p.indices ? p.indices[k] : p.first + k;                 // checked on the host: in range, each at most once
+    const rt_instance rec = p.inst_records[k];
+    if (!rt_refit::instance_record_ok(rec, p.instances[i].child)) {
+        atomicOr(reinterpret_cast<unsigned int*>(p.result) + 3, 1u);    // refused: the instance, its stamp and its boxes stay
+        return;
+    }
+    p.instances[i] = rec;
+    p.inst_stamp[i] = p.inst_epoch;
+}
+
+// One lane per leaf: the child's box from the records on the device (a sphere, a quad, or the six quads of a box), then the rule.
+__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_instance_leaves_kernel(const rt_refit_params p) {
+    const int q = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
+    if (q >= p.n_leaves) return;
+    const int ii = p.leaf_instance[q];
+    if (ii < 0 || p.inst_stamp[ii] != p.inst_epoch) return;
+    const rt_instance in = p.instances[ii];
+    float lo[3], hi[3];
+    rt_refit::child_box(in.child, p.spheres, p.quads, p.boxes, lo, hi);
+    rt_refit::instance_box(in, lo, hi);
+    store_leaf(p, q, lo, hi);
 }
 
 __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_slots_kernel(const rt_refit_params p) {
@@ -139,12 +175,25 @@ inline unsigned int blocks_for(long long items, int per_block) { return (unsigne
 
 }  // namespace
 
-hipError_t rt_launch_refit(const rt_refit_params& p, hipStream_t st) {
+// steps 3 and 4: they do not care why a leaf's box changed
+static void launch_unions(const rt_refit_params& p, hipStream_t st) {
     const int waves = RT_REFIT_THREADS / 64;
+    if (p.n_slots > 0) hipLaunchKernelGGL(rt_refit_slots_kernel, dim3(blocks_for(p.n_slots, waves)), dim3(RT_REFIT_THREADS), 0, st, p);
+    hipLaunchKernelGGL(rt_refit_interior_kernel, dim3(blocks_for((long long)p.n_jobs + 1, waves)), dim3(RT_REFIT_THREADS), 0, st, p);
+}
+
+hipError_t rt_launch_refit(const rt_refit_params& p, hipStream_t st) {
     if (p.count > 0) hipLaunchKernelGGL(rt_refit_records_kernel, dim3(blocks_for(p.count, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
     if (p.count > 0 && p.n_leaves > 0)
         hipLaunchKernelGGL(rt_refit_leaves_kernel, dim3(blocks_for(p.n_leaves, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
-    if (p.n_slots > 0) hipLaunchKernelGGL(rt_refit_slots_kernel, dim3(blocks_for(p.n_slots, waves)), dim3(RT_REFIT_THREADS), 0, st, p);
-    hipLaunchKernelGGL(rt_refit_interior_kernel, dim3(blocks_for((long long)p.n_jobs + 1, waves)), dim3(RT_REFIT_THREADS), 0, st, p);
+    launch_unions(p, st);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_refit_instances(const rt_refit_params& p, hipStream_t st) {
+    if (p.count > 0) hipLaunchKernelGGL(rt_refit_instance_records_kernel, dim3(blocks_for(p.count, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
+    if (p.count > 0 && p.n_leaves > 0)
+        hipLaunchKernelGGL(rt_refit_instance_leaves_kernel, dim3(blocks_for(p.n_leaves, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
+    launch_unions(p, st);
     return hipGetLastError();
 }

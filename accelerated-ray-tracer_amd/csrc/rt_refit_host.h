@@ -1,8 +1,9 @@
-// rt_refit_host.h -- the host half of rt_scene_update_spheres (include/rt_abi.h): the box rule, the checks of
-// an update and the refit of a node array in the description's link encoding.  Plain C++ with no HIP call, so that
+// rt_refit_host.h -- the host half of rt_scene_update_spheres and rt_scene_update_instances (include/rt_abi.h; DESIGN.md 4.15,
+// 4.17): the box rules, the checks of an update and the refit of a node array in the description's link encoding.  Plain C++ with no HIP call, so that
 // rt_refit_nodes needs no device and the same text compiles into a stand-alone host program; rt_kernel_refit.hip takes the
 // box rule from here too, so host and device cannot drift apart.
 #pragma once
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 
@@ -91,16 +92,116 @@ inline std::string check_update(const rt_sphere_update* u, bool host_records, in
     return "";
 }
 
-// Refit of a node array in the description's encoding (skip = index of the next node when the box is missed, prim < 0 =
-// interior, depth-first pre-order): the leaves whose sphere is marked in `moved` take the box rule's box of spheres[...],
-// then every interior node becomes the float min / max union of its children's boxes, children before parents (a node's
-// children are i + 1 and the nodes its skip chain reaches below skip[i]).  Link words are not written.
-inline void refit_nodes(rt_node* nodes, int32_t n, const rt_sphere* spheres, int32_t n_spheres, const rt_medium* media, int32_t n_media,
-                        const std::vector<char>& moved) {
-    for (int32_t i = 0; i < n; ++i) {
-        const int32_t si = leaf_sphere(nodes[i].prim, media, n_media, n_spheres);
-        if (si >= 0 && moved[(size_t)si]) sphere_box(spheres[si], nodes[i].bmin, nodes[i].bmax);
+// ---- instances (rt_scene_update_instances).  The rule is the host library's constructors restated operation by
+// operation (host/rtw.cpp: quad::quad, compound6, rotate_y::rotate_y; rtw.h: translate), every operation a binary32 one rounded
+// once; the only fused operations are the two fmaf of the rotation, which the constructor writes the same way.
+
+// quad::quad: the padded union of the two diagonals' boxes
+RT_REFIT_HD inline void quad_box(const rt_quad& q, float lo[3], float hi[3]) {
+    for (int c = 0; c < 3; ++c) {
+        const float a = q.Q[c] + q.u[c], b = q.Q[c] + q.v[c], p = a + q.v[c];
+        lo[c] = fminf(fminf(q.Q[c], p), fminf(a, b)) - 1e-3f;
+        hi[c] = fmaxf(fmaxf(q.Q[c], p), fmaxf(a, b)) + 1e-3f;
     }
+}
+
+// compound6: the six faces' boxes in array order.  first_quad's high bits are the device's marks (rt_scene_create) and masked off.
+RT_REFIT_HD inline void box_box(const rt_box& b, const rt_quad* quads, float lo[3], float hi[3]) {
+    const int32_t first = b.first_quad & 0x3FFFFFFF;
+    quad_box(quads[first], lo, hi);
+    for (int f = 1; f < 6; ++f) {
+        float l[3], h[3];
+        quad_box(quads[first + f], l, h);
+        for (int c = 0; c < 3; ++c) { lo[c] = fminf(lo[c], l[c]); hi[c] = fmaxf(hi[c], h[c]); }
+    }
+}
+
+// The box of an instance's child in object space.  `child` is a reference rt_scene_create has validated: a sphere, quad or box
+// inside its array (a box's six quads inside theirs).  Anything else -- which validation excludes -- reads nothing.
+RT_REFIT_HD inline void child_box(int32_t child, const rt_sphere* spheres, const rt_quad* quads, const rt_box* boxes, float lo[3], float hi[3]) {
+    const int kind = child < 0 ? -1 : (int)RT_PRIM_KIND(child), i = (int)RT_PRIM_INDEX(child);
+    if (kind == RT_PRIM_SPHERE) sphere_box(spheres[i], lo, hi);
+    else if (kind == RT_PRIM_QUAD) quad_box(quads[i], lo, hi);
+    else if (kind == RT_PRIM_BOX) box_box(boxes[i], quads, lo, hi);
+    else for (int c = 0; c < 3; ++c) { lo[c] = 0.0f; hi[c] = 0.0f; }
+}
+
+// translate(rotate_y(child box)): the eight corners in the constructor's order (x outer, z inner), then the offset
+RT_REFIT_HD inline void instance_box(const rt_instance& in, float lo[3], float hi[3]) {
+    if (in.flags & RT_INST_ROTATE_Y) {
+        float l[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, h[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+        for (int i = 0; i < 2; ++i)
+            for (int j = 0; j < 2; ++j)
+                for (int k = 0; k < 2; ++k) {
+                    const float x = i ? hi[0] : lo[0], y = j ? hi[1] : lo[1], z = k ? hi[2] : lo[2];
+                    const float r[3] = {fmaf(in.cos_t, x, in.sin_t * z), y, fmaf(in.cos_t, z, -(in.sin_t * x))};
+                    for (int c = 0; c < 3; ++c) { l[c] = fminf(l[c], r[c]); h[c] = fmaxf(h[c], r[c]); }
+                }
+        for (int c = 0; c < 3; ++c) { lo[c] = l[c]; hi[c] = h[c]; }
+    }
+    if (in.flags & RT_INST_TRANSLATE)
+        for (int c = 0; c < 3; ++c) { lo[c] = lo[c] + in.offset[c]; hi[c] = hi[c] + in.offset[c]; }
+}
+
+// what the checks allow of an instance record: sin_t, cos_t and offset finite, flags 1, 2 or 3, child the scene's own
+RT_REFIT_HD inline bool instance_finite(const rt_instance& in) {
+    bool finite = (in.sin_t - in.sin_t == 0.0f) && (in.cos_t - in.cos_t == 0.0f);
+    for (int c = 0; c < 3; ++c) finite = finite && (in.offset[c] - in.offset[c] == 0.0f);
+    return finite;
+}
+RT_REFIT_HD inline bool instance_record_ok(const rt_instance& in, int32_t scene_child) {
+    return instance_finite(in) && in.flags >= 1 && in.flags <= 3 && in.child == scene_child;
+}
+
+// The instance a leaf's box follows: the leaf's own instance, or the instance that is the boundary of the leaf's constant_medium
+// directly; -1 for every other leaf.
+inline int32_t leaf_instance(int32_t prim, const rt_medium* media, int32_t n_media, int32_t n_instances) {
+    if (prim < 0) return -1;
+    if (RT_PRIM_KIND(prim) == RT_PRIM_MEDIUM) {
+        const int m = RT_PRIM_INDEX(prim);
+        if (m >= n_media) return -1;
+        prim = media[m].boundary;
+        if (prim < 0) return -1;
+    }
+    if (RT_PRIM_KIND(prim) != RT_PRIM_INSTANCE) return -1;
+    const int i = RT_PRIM_INDEX(prim);
+    return i < n_instances ? i : -1;
+}
+
+// The refusals of an instance update (rt_abi.h), as check_update.  children: per instance, the child the scene holds.
+inline std::string check_instance_update(const rt_instance_update* u, bool host_records, const int32_t* children, int32_t n_instances) {
+    if (!u) return "null update";
+    if (u->count < 0) return "count is negative";
+    if (u->count == 0) return "";
+    if (!u->instances) return "null instance records";
+    if (u->count > n_instances) return "more records than the scene has instances (an index is out of range or appears twice)";
+    std::vector<char> seen((size_t)n_instances, 0);
+    for (int32_t k = 0; k < u->count; ++k) {
+        const long long i = u->indices ? (long long)u->indices[k] : (long long)u->first + k;
+        if (i < 0 || i >= n_instances) return "instance index out of range";
+        if (seen[(size_t)i]) return "an instance index appears twice";
+        seen[(size_t)i] = 1;
+    }
+    if (host_records) {   // (after every index has passed: a record is compared with the instance it names)
+        for (int32_t k = 0; k < u->count; ++k) {
+            const int32_t i = u->indices ? u->indices[k] : u->first + k;
+            const rt_instance& in = u->instances[k];
+            if (!instance_finite(in)) return "an instance record has a non-finite sin_t, cos_t or offset";
+            if (in.flags < 1 || in.flags > 3) return "instance flags must be 1, 2 or 3";
+            if (in.child != children[(size_t)i]) return "an instance record's child is not the child the scene holds (the child of an instance cannot change)";
+        }
+    }
+    return "";
+}
+
+// Refit of a node array in the description's encoding (skip = index of the next node when the box is missed, prim < 0 =
+// interior, depth-first pre-order): leaf_rule(prim, bmin, bmax) is called for every leaf and rewrites the box of those it
+// recomputes, then every interior node becomes the float min / max union of its children's boxes, children before parents (a
+// node's children are i + 1 and the nodes its skip chain reaches below skip[i]).  Link words are not written.
+template <class LeafRule>
+inline void refit_nodes(rt_node* nodes, int32_t n, LeafRule&& leaf_rule) {
+    for (int32_t i = 0; i < n; ++i)
+        if (nodes[i].prim >= 0) leaf_rule(nodes[i].prim, nodes[i].bmin, nodes[i].bmax);
     for (int32_t i = n - 1; i >= 0; --i) {
         if (nodes[i].prim >= 0) continue;
         bool first = true;
@@ -112,6 +213,26 @@ inline void refit_nodes(rt_node* nodes, int32_t n, const rt_sphere* spheres, int
             first = false;
         }
     }
+}
+
+// the leaves whose sphere is marked in `moved` take the sphere rule's box of spheres[...]
+inline void refit_nodes(rt_node* nodes, int32_t n, const rt_sphere* spheres, int32_t n_spheres, const rt_medium* media, int32_t n_media,
+                        const std::vector<char>& moved) {
+    refit_nodes(nodes, n, [&](int32_t prim, float* lo, float* hi) {
+        const int32_t si = leaf_sphere(prim, media, n_media, n_spheres);
+        if (si >= 0 && moved[(size_t)si]) sphere_box(spheres[si], lo, hi);
+    });
+}
+
+// the leaves whose instance is marked in `moved` take the instance rule's box of instances[...] (of the description `d`, whose
+// references rt_scene_create's checks have validated)
+inline void refit_instance_nodes(rt_node* nodes, const rt_scene_desc* d, const rt_instance* instances, const std::vector<char>& moved) {
+    refit_nodes(nodes, d->n_nodes, [&](int32_t prim, float* lo, float* hi) {
+        const int32_t ii = leaf_instance(prim, d->media, d->n_media, d->n_instances);
+        if (ii < 0 || !moved[(size_t)ii]) return;
+        child_box(instances[ii].child, d->spheres, d->quads, d->boxes, lo, hi);
+        instance_box(instances[ii], lo, hi);
+    });
 }
 
 }  // namespace rt_refit

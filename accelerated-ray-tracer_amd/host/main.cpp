@@ -9,7 +9,7 @@
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
 //             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K] [--denoise-variance [B]]] [--list]
 //             [--aov-through PREFIX] [--through-bounces N] [--through-fuzz F] [--denoise-through]
-//             [--orbit FRAMES DEGREES --out PREFIX [--temporal] [--bounce HEIGHT]]
+//             [--orbit FRAMES DEGREES --out PREFIX [--temporal] [--bounce HEIGHT] [--spin DEGREES]]
 //
 // --orbit FRAMES DEGREES renders a turntable: FRAMES frames of one device scene, the scene's lookfrom rotated about the vertical
 // axis through its lookat in equal steps of DEGREES / FRAMES (frame k at k steps; every other camera argument kept), each
@@ -23,6 +23,10 @@
 //   c0.y = (float)((double)base_y + HEIGHT * fabs(sin(pi * ((double)k / FRAMES + 0.61803398875 * i))))
 // (in double, libm's sin) through rt_scene_update_spheres.  With --temporal the accumulation follows them (rt_reproject_moving
 // with the records of this frame and of the previous one).  A scene with instances is refused: some of its spheres cannot move.
+// --spin DEGREES (only with --orbit; DEGREES finite) turns the rotated instances: before frame k every instance of the description
+// with RT_INST_ROTATE_Y takes the angle  atan2((double)sin_t, (double)cos_t) + k * DEGREES * pi / 180  of its flattened record,
+// sin and cos evaluated in double and rounded to float, through rt_scene_update_instances.  A scene without a rotated instance
+// is refused, and so is --temporal: the reprojection does not follow a moved instance.
 //
 // --denoise [K] filters the frame with rt_denoise (K iterations, 5 when K is left out; the binding's other defaults): the frame
 // is rendered at gamma 1, the feature pass (albedo, normal, depth at min(ns, 16) samples) guides the filter, and the frame's
@@ -75,8 +79,8 @@ int main(int argc, char** argv) {
     int min_spp = 0, denoise = 0, batches = -1;   // batches: -1 = no --denoise-variance, 0 = B left out
     int orbit_frames = 0;
     double orbit_degrees = 0.0;
-    bool temporal = false, bounce = false;
-    double bounce_height = 0.0;
+    bool temporal = false, bounce = false, spin = false;
+    double bounce_height = 0.0, spin_degrees = 0.0;
     std::string out_prefix;
     unsigned long long seed = 1984ull;
     for (int a = 1; a < argc; ++a) {
@@ -129,6 +133,11 @@ int main(int argc, char** argv) {
             bounce_height = strtod(val(), nullptr);
             if (!std::isfinite(bounce_height) || bounce_height < 0.0) { fprintf(stderr, "--bounce HEIGHT: HEIGHT must be finite and >= 0\n"); return 2; }
         }
+        else if (k == "--spin") {
+            spin = true;
+            spin_degrees = strtod(val(), nullptr);
+            if (!std::isfinite(spin_degrees)) { fprintf(stderr, "--spin DEGREES: DEGREES must be finite\n"); return 2; }
+        }
         else if (k == "--list") { int n = 0; const char* const* v = rtw::scene_names(&n); for (int i = 0; i < n; ++i) printf("%s\n", v[i]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); return 2; }
     }
@@ -145,6 +154,8 @@ int main(int argc, char** argv) {
     if (orbit_frames > 0 && out_prefix.empty()) { fprintf(stderr, "--orbit needs --out PREFIX\n"); return 2; }
     if (orbit_frames == 0 && (temporal || !out_prefix.empty())) { fprintf(stderr, "--temporal and --out need --orbit\n"); return 2; }
     if (orbit_frames == 0 && bounce) { fprintf(stderr, "--bounce needs --orbit\n"); return 2; }
+    if (orbit_frames == 0 && spin) { fprintf(stderr, "--spin needs --orbit\n"); return 2; }
+    if (spin && temporal) { fprintf(stderr, "--spin cannot be combined with --temporal: the reprojection does not follow a moved instance\n"); return 2; }
     if (orbit_frames > 0 && (gpus > 1 || progressive > 0 || adaptive || denoise || !aov_prefix.empty() || !through_prefix.empty())) {
         fprintf(stderr, "--orbit cannot be combined with --gpus > 1, --progressive, --adaptive, --denoise, --aov or --aov-through\n");
         return 2;
@@ -177,6 +188,11 @@ int main(int argc, char** argv) {
     if (bounce && !flat.instances.empty()) {
         fprintf(stderr, "--bounce: scene '%s' has instances, and a sphere under an instance cannot move (rt_scene_update_spheres)\n", scene_name.c_str());
         return 2;
+    }
+    if (spin) {
+        bool rotated = false;
+        for (const rt_instance& in : flat.instances) rotated = rotated || (in.flags & RT_INST_ROTATE_Y);
+        if (!rotated) { fprintf(stderr, "--spin: scene '%s' has no rotated instance\n", scene_name.c_str()); return 2; }
     }
 
     fprintf(stderr, "Rendering a %dx%d image in 8x8 blocks.\n", scene->nx, scene->ny);
@@ -220,6 +236,18 @@ int main(int argc, char** argv) {
                 memset(&up, 0, sizeof(up));
                 up.count = (int32_t)now.size(); up.first = 0; up.spheres = now.data();
                 check(rt_scene_update_spheres(dev_scene, &up, /*spheres_on_device=*/0, /*recalibrate=*/0, /*stream=*/nullptr), "rt_scene_update_spheres");
+            }
+            if (spin) {
+                std::vector<rt_instance> now = flat.instances;
+                for (rt_instance& in : now) {
+                    if (!(in.flags & RT_INST_ROTATE_Y)) continue;
+                    const double a = atan2((double)in.sin_t, (double)in.cos_t) + (double)k * spin_degrees * 3.14159265358979323846 / 180.0;
+                    in.sin_t = (float)sin(a); in.cos_t = (float)cos(a);
+                }
+                rt_instance_update up;
+                memset(&up, 0, sizeof(up));
+                up.count = (int32_t)now.size(); up.first = 0; up.instances = now.data();
+                check(rt_scene_update_instances(dev_scene, &up, /*instances_on_device=*/0, /*recalibrate=*/0, /*stream=*/nullptr), "rt_scene_update_instances");
             }
             const double th = (double)k * orbit_degrees / (double)orbit_frames * 3.14159265358979323846 / 180.0;
             const double dx = (double)c0.lookfrom.x() - c0.lookat.x(), dz = (double)c0.lookfrom.z() - c0.lookat.z();

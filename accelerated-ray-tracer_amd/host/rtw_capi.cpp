@@ -80,6 +80,16 @@ int rtw_camera_init(const float* lookfrom, const float* lookat, const float* vup
     return 0;
 }
 
+// hittable.cuh:89-93 through rotate_y's own float arithmetic: the (sin_t, cos_t) a reference scene function's rotate_y(p, degrees)
+// holds, which is what an rt_instance record of that rotation carries
+int rtw_rotation(float degrees, float* sin_t, float* cos_t) {
+    if (!sin_t || !cos_t) return -1;
+    const float rad = degrees * 0.017453292519943295769f;
+    *sin_t = sinf(rad);
+    *cos_t = cosf(rad);
+    return 0;
+}
+
 int rtw_load_ppm(const char* path, unsigned char* out, int cap, int* w, int* h) {
     std::vector<unsigned char> px;
     if (!rtw::load_ppm(path, px, *w, *h)) return -1;

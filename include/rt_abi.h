@@ -647,8 +647,9 @@ rt_status rt_scene_get_camera(const rt_scene* scene, rt_camera* out);
  * Refusals.  Each of these is RT_ERR_INVALID before any HIP call, with rt_last_error_detail() naming the check, and leaves the
  * scene untouched: a null scene, update or record array; count < 0; an index out of range; an index that appears twice; with
  * host records, a non-finite c0, vel or radius, or a mat outside the scene's materials; an updated sphere that is the child
- * of an instance -- reached as leaf -> instance or medium -> instance: the box rule of an instance (its rotated, translated
- * child box) is not redone here, so such a sphere cannot move yet while direct spheres and sphere-bounded media can.
+ * of an instance -- reached as leaf -> instance or medium -> instance: its leaf's box follows the instance's rule, which a
+ * sphere update does not redo.  Such a sphere still cannot change its own record; it moves with its instance instead
+ * (rt_scene_update_instances, below), as direct spheres and sphere-bounded media move here.
  * Device-resident records cannot be checked on the host: the kernel that stores them checks each, stores nothing for a record
  * with a non-finite field or a bad mat and raises a flag that is read back with the bound; the call then returns RT_ERR_INVALID
  * with every record that passed applied and every box and union consistent with the spheres actually stored.  No address
@@ -673,6 +674,71 @@ rt_status rt_scene_update_spheres(rt_scene* scene, const rt_sphere_update* updat
 rt_status rt_scene_get_spheres(const rt_scene* scene, rt_sphere* out, int32_t cap);
 rt_status rt_refit_nodes(const rt_scene_desc* desc, const rt_sphere_update* update, rt_node* nodes_out, rt_sphere* spheres_out);   /* host only, no device */
 rt_status rt_debug_scene_boxes(const rt_scene* scene, int32_t which, void* out, size_t cap, size_t* n);
+
+/* ---- moving instances: new instance records for a scene that stays on the device ----
+ * rt_scene_update_instances replaces instance records -- translate(rotate_y(child)) -- of a resident scene and refits every box
+ * that depends on them, on the device: the blocks of a Cornell box turn, a fog volume bounded by an instance drifts, a crowd of
+ * rotated boxes moves at once, frame after frame without a second rt_scene_create.
+ *
+ * The update.  Record k of `instances` replaces instance indices[k], or instance first + k when indices is null.  indices is
+ * host memory always; instances is host memory, or, with instances_on_device != 0, device (or managed) memory of the scene's
+ * device (nothing is copied).  count == 0 is a successful no-op.
+ *
+ * Contract.  Let D' be the scene's description with those records replaced and its node boxes refit as below.  From the call on,
+ * every frame entry -- rt_render, rt_render_window, rt_render_adaptive, rt_render_variance, rt_render_aov,
+ * rt_render_aov_through -- and both query entries -- rt_trace_rays, rt_radiance_rays -- write, bit for bit, what they write on
+ * rt_scene_create(D'), and report the same rays and samples.  Topology, link words, the walk array's choice of nodes and the
+ * tier arrays' .w words are never written.
+ *   What a record may change.  sin_t, cos_t, offset and flags.  flags must be 1, 2 or 3 (RT_INST_ROTATE_Y, RT_INST_TRANSLATE or
+ *     both): rt_scene_create's kernels and the oracle know nothing else.  child must equal the child the scene holds for that
+ *     instance: the tier arrays and the per-kind passes were built on it.  pad is not looked at (and stored as given).
+ *   Leaves that change.  A leaf is recomputed when its primitive is an updated instance, or a constant_medium whose boundary is
+ *     an updated instance directly.  Every other leaf keeps its box, whatever rule made it (a generated description may carry
+ *     outward-rounded boxes; an instance's leaf keeps such a box until that instance is updated).
+ *   Box rule, as ordered binary32 operations, each rounded once, nothing contracted except the two fmaf written here.
+ *     1. The child's box (lo, hi) in object space.  Sphere: the sphere rule above.  Quad:  p = (Q + u) + v,
+ *        lo = min(min(Q, p), min(Q + u, Q + v)) - 1e-3f,  hi = max(max(Q, p), max(Q + u, Q + v)) + 1e-3f  per axis.  Box: the
+ *        min / max of the quad rule over its six quads first_quad .. first_quad + 5, in that order.
+ *     2. flags & RT_INST_ROTATE_Y:  from lo' = FLT_MAX, hi' = -FLT_MAX, the eight corners (x, y, z) of the child's box in the
+ *        order i, j, k = 0..1 (x outer, z inner; 0 takes lo, 1 takes hi):  rx = fmaf(cos_t, x, sin_t * z),  ry = y,
+ *        rz = fmaf(cos_t, z, -(sin_t * x)),  then lo' = min(lo', r), hi' = max(hi', r).
+ *     3. flags & RT_INST_TRANSLATE:  lo + offset,  hi + offset.
+ *     This is, value for value, what the host library's constructors give (quad::quad, compound6, rotate_y::rotate_y and
+ *     translate in host/rtw.cpp and rtw.h; the reference's quad.cuh:29-54, 108-122 and hittable.cuh:40-116), so that writing a
+ *     flattened scene's own records back changes no box; tests/test_update_instances_host.py pins that on five named scenes.
+ *     With a (sin_t, cos_t) that is no sine / cosine pair the box need not contain the object -- which is what
+ *     rt_scene_create of such a description gives too, so the contract holds all the same.
+ *   Refit.  As after a sphere update: interior boxes of both node arrays, the tier leaf boxes and per-64-leaf unions, the bound.
+ *   What goes stale.  The cost prior and the cost map, exactly as after a sphere update; recalibrate != 0 redoes the cost half
+ *     of the calibration and drops the map.
+ * A pending non-blocking rt_render of the scene is finished first.  The work -- four small launches -- is enqueued on `stream`
+ * after whatever it holds.  The call is SYNCHRONOUS: it reads 16 bytes back (the new bound and the flag below).
+ *
+ * Refusals.  Each of these is RT_ERR_INVALID before any HIP call, with rt_last_error_detail() naming the check after
+ * "rt_scene_update_instances: " (or "rt_refit_instances: "), and leaves the scene untouched: a null scene, update or record
+ * array; count < 0; an index out of range; an index that appears twice; with host records, a non-finite sin_t, cos_t or offset,
+ * flags outside 1..3, or a child other than the scene's.
+ * Device-resident records are checked by the kernel that stores them: a record with a non-finite field, bad flags or another
+ * child is not stored, a flag is read back with the bound, and the call returns RT_ERR_INVALID with every record that passed
+ * applied and every box consistent with the records actually stored.  No address depends on record data: the child a box is
+ * computed from is the scene's own, validated at creation, never the incoming record's; the only data-derived addresses come
+ * from `indices`, which the host has checked.
+ *
+ * What still cannot move: a quad or box that is not under an instance (their records cannot change), a sphere record under an
+ * instance (rt_scene_update_spheres refuses it; the sphere moves with its instance), and an instance's child.
+ * rt_scene_get_instances copies the records the next frame will use (cap >= the scene's instance count, else RT_ERR_INVALID).
+ * rt_multi_update_instances applies host records to every replica of an rt_multi.  rt_refit_instances is the host-only statement
+ * of D' (no device needed), as rt_refit_nodes: nodes_out receives desc->n_nodes nodes, instances_out desc->n_instances records;
+ * either may be null; it makes rt_scene_create's checks of `desc` and the refusals above and writes nothing when it refuses. */
+typedef struct rt_instance_update {
+    int32_t count;                 /* records in `instances` */
+    int32_t first;                 /* used when indices == NULL: record k replaces instance first + k */
+    const int32_t* indices;        /* or NULL; host memory always; each index at most once */
+    const rt_instance* instances;  /* host memory, or device memory when instances_on_device != 0 */
+} rt_instance_update; /* 24 B */
+rt_status rt_scene_update_instances(rt_scene* scene, const rt_instance_update* update, int instances_on_device, int recalibrate, void* stream);
+rt_status rt_scene_get_instances(const rt_scene* scene, rt_instance* out, int32_t cap);
+rt_status rt_refit_instances(const rt_scene_desc* desc, const rt_instance_update* update, rt_node* nodes_out, rt_instance* instances_out);   /* host only, no device */
 
 /* ---- temporal reprojection: the current frame blended into the reprojected history of the previous one ----
  * With a camera that moves, the samples of one frame can be reused in the next: rt_reproject finds, for every pixel of the
@@ -770,8 +836,10 @@ rt_status rt_reproject_matrix(const rt_camera* prev, float m[9]);   /* host only
  * under an instance, which cannot be updated, never differs: its pixel (prim = the sphere, inst >= 0) takes the static path
  * and no inst buffer is needed.  tests/reproject_moving_expect.py restates this in NumPy; the device result equals it bit for bit.
  * Limits.  As before the centre ray ignores the lens and the shutter; a sphere with vel != 0 is followed at one instant per
- * frame (`time`, `prev_time`; the binding's default is each camera's shutter centre, (float)(0.5 (time0 + time1))).  Quads, boxes
- * and instances do not move in this project yet.  Reflections of a moved sphere in other surfaces are not followed.
+ * frame (`time`, `prev_time`; the binding's default is each camera's shutter centre, (float)(0.5 (time0 + time1))).  A quad or
+ * box that is not under an instance and a sphere record under an instance do not move in this project; an instance does
+ * (rt_scene_update_instances), but its motion is not followed here: a pixel on a moved instance takes the static path, and the
+ * taps' depth, normal and id tests decide whether its history survives.  Reflections of a moved sphere in other surfaces are not followed.
  * Memory safety.  Two kinds of data-derived addresses are added: media[...] after the unsigned compare against n_media, and
  * spheres[k] / prev_spheres[k] after the unsigned compare against n_spheres.  Nothing loaded from a record reaches an address;
  * no value in any buffer or table makes the call fault.
@@ -814,6 +882,7 @@ rt_status rt_multi_render(rt_multi* m, const rt_frame_desc* f, float* fb, int fb
 rt_status rt_multi_destroy(rt_multi* m);
 rt_status rt_multi_set_camera(rt_multi* m, const rt_camera* camera, int recalibrate);   /* rt_scene_set_camera on every replica */
 rt_status rt_multi_update_spheres(rt_multi* m, const rt_sphere_update* update, int recalibrate);   /* rt_scene_update_spheres, host records, on every replica */
+rt_status rt_multi_update_instances(rt_multi* m, const rt_instance_update* update, int recalibrate);   /* rt_scene_update_instances, host records, on every replica */
 int32_t rt_multi_device_count(const rt_multi* m);
 /* the row partition rt_multi_render uses: which device renders global row j and at which row of its compact buffer
  * (the inverse of rt_local_to_global_row for tile_first = device, tile_stride = n_gpus) */

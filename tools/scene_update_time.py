@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Wall time of rt_scene_update_spheres per call -- one moved sphere, and every direct sphere moved, from host records and from a
 device tensor -- beside the wall time of rt_scene_create of the same scene (tools/scene_create_time.py's method: the call alone,
-the best of a few, the first reported apart).  One JSON line per measurement.
+the best of a few, the first reported apart); and of rt_scene_update_instances -- one instance, and every instance -- beside
+rt_scene_update_spheres and rt_scene_create on scenes with instances.  One JSON line per measurement.
 
     python tools/scene_update_time.py                       # this tree: creation and updates
+    python tools/scene_update_time.py --only instances      # the scenes with instances alone
     python tools/scene_update_time.py --create-only --root DIR --label parent
                                                             # creation alone, with the package of another checkout (the parent
                                                             # commit, built in DIR), for the comparison DESIGN.md 4.15 quotes
@@ -21,6 +23,7 @@ ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspat
 ap.add_argument("--create-only", action="store_true")
 ap.add_argument("--label", default="this tree")
 ap.add_argument("--calls", type=int, default=40, help="timed update calls per measurement (the median is reported)")
+ap.add_argument("--only", choices=("spheres", "instances"), default=None, help="one of the two scene lists")
 ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
@@ -31,6 +34,8 @@ import accelerated_ray_tracer_amd as art  # noqa: E402
 # the random scene (488 spheres), Book-2 final (1008 spheres, every one direct in this flattening: the cluster's rotation and
 # translation are baked into its centres) and a 4096-leaf scene
 SCENES = (("random_scene", 1200, 800), ("final", 800, 800), ("crowd_4096", 64, 64))
+# the Cornell box (two rotated blocks), every instance kind (18 instances, 128 leaves) and 1 200 rotated boxes among 8 401 leaves
+INSTANCE_SCENES = (("cornell", 600, 600), ("instanced", 64, 64), ("crowd_big", 64, 64))
 
 
 def emit(**rec):
@@ -66,11 +71,16 @@ def time_create(hs, scene):
          nodes_reference=info["nodes_reference"], nodes_walked=info["nodes_walked"])
 
 
-def time_updates(hs, scene):
+def time_updates(hs, scene, ds=None):
     import torch
     L = art.rt_lib()
-    ds = art.DeviceScene(hs)
-    direct, sph = direct_spheres(hs), hs.spheres()
+    keep = ds is not None
+    ds = ds or art.DeviceScene(hs)
+    direct = direct_spheres(hs)
+    if len(direct) == 0:
+        emit(what="rt_scene_update_spheres", scene=scene, note="no direct sphere")
+        return
+    sph = hs.spheres()
     rng = np.random.default_rng(1)
 
     def call(u, on_device):
@@ -106,6 +116,49 @@ def time_updates(hs, scene):
     f = hs.frame(nx=min(hs.nx, 240), ny=min(hs.ny, 160), ns=4)
     _, st = ds.render(f)                                                         # the moved scene still renders
     assert st.rays > 0
+    if not keep:
+        ds.close()
+
+
+def time_instance_updates(hs, scene):
+    """rt_scene_update_instances: one instance and every instance, a new offset and (for the rotated ones) a new angle per call."""
+    import torch
+    L = art.rt_lib()
+    ds = art.DeviceScene(hs)
+    inst = hs.instances()
+    every = np.arange(len(inst), dtype=np.int32)
+    rng = np.random.default_rng(2)
+    first_call = None
+    for size, idx in (("one", every[len(every) // 2:len(every) // 2 + 1]), ("all", every)):
+        for source in ("host", "device"):
+            ts = []
+            for k in range(5 + args.calls):
+                rec = inst[idx]
+                a = np.arctan2(rec["sin_t"].astype(np.float64), rec["cos_t"].astype(np.float64)) + rng.uniform(-0.3, 0.3, len(idx))
+                rot = (rec["flags"] & art.RT_INST_ROTATE_Y) != 0
+                rec["sin_t"][rot], rec["cos_t"][rot] = np.sin(a)[rot], np.cos(a)[rot]
+                tr = (rec["flags"] & art.RT_INST_TRANSLATE) != 0
+                rec["offset"][tr] += rng.uniform(-0.2, 0.2, (int(tr.sum()), 3)).astype(np.float32)
+                u = art.RtInstanceUpdate()
+                u.count, u.indices = len(idx), idx.ctypes.data
+                if source == "device":
+                    t = torch.from_numpy(rec.view(np.float32).reshape(-1, 8).copy()).cuda()
+                    torch.cuda.synchronize()
+                    u.instances = t.data_ptr()
+                else:
+                    u.instances = rec.ctypes.data
+                t0 = time.perf_counter()
+                st = L.rt_scene_update_instances(ds._p, C.byref(u), 1 if source == "device" else 0, 0, None)
+                dt = (time.perf_counter() - t0) * 1e3
+                assert st == 0, L.rt_last_error_detail().decode()
+                if first_call is None:
+                    first_call = dt                                              # builds the scene's lookup tables
+                elif k >= 5:
+                    ts.append(dt)
+            emit(what="rt_scene_update_instances", scene=scene, moved=size, records=source, count=int(len(idx)), calls=len(ts),
+                 ms_median=round(statistics.median(ts), 4), ms_min=round(min(ts), 4), ms_max=round(max(ts), 4))
+    emit(what="rt_scene_update_instances, first call of the scene (builds the lookup tables)", scene=scene, ms=round(first_call, 3))
+    time_updates(hs, scene, ds)                                                  # the sphere update of the same scene, same tables
     ds.close()
 
 
@@ -114,10 +167,17 @@ if not args.create_only:
     if not torch.cuda.is_available():                                            # (before rt_init, as the test suite does)
         raise SystemExit("no GPU visible to torch: the device-tensor measurements need one")
 art.init(0)
-for scene, nx, ny in SCENES:
+for scene, nx, ny in SCENES if args.only != "instances" else ():
     img, iw, ih = art.default_texture(scene)
     hs = art.HostScene(scene, nx, ny, img, iw, ih)
     time_create(hs, scene)
     if not args.create_only:
         time_updates(hs, scene)
+    hs.close()
+for scene, nx, ny in INSTANCE_SCENES if args.only != "spheres" else ():
+    img, iw, ih = art.default_texture(scene)
+    hs = art.HostScene(scene, nx, ny, img, iw, ih)
+    time_create(hs, scene)
+    if not args.create_only:
+        time_instance_updates(hs, scene)
     hs.close()
