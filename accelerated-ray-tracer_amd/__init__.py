@@ -182,7 +182,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_reproject_matrix", "rt_debug_rank", "rt_debug_prior", "rt_debug_cal_cost", "rt_debug_rank_info",
                   "rt_scene_update_spheres", "rt_scene_get_spheres", "rt_multi_update_spheres", "rt_refit_nodes", "rt_debug_scene_boxes",
                   "rt_reproject_moving", "rt_debug_cost_map", "rt_debug_set_cost_map",
-                  "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances"]
+                  "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances",
+                  "rt_debug_box_tests"]
 
 _rt = None
 _host = None
@@ -294,6 +295,8 @@ def rt_lib():
         if hasattr(L, "rt_debug_cost_map"):   # (absent from an older library measured through RT_LIB_OVERRIDE)
             L.rt_debug_cost_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
             L.rt_debug_set_cost_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        if hasattr(L, "rt_debug_box_tests"):   # (likewise)
+            L.rt_debug_box_tests.argtypes = [C.c_int32] + [C.c_void_p] * 8
         L.rt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _rt = L
     return _rt

@@ -2299,6 +2299,33 @@ rt_status rt_debug_prior(const uint32_t* cal_cost, int32_t cal_nx, int32_t cal_n
     return RT_OK;
 }
 
+rt_status rt_debug_box_tests(int32_t n, const float* bmin, const float* bmax, const float* origins, const float* directions,
+                             const float* tmin, const float* tmax, const float* bound3, uint8_t* flags) {
+    if (!bmin || !bmax || !origins || !directions || !tmin || !tmax || !bound3 || !flags) return invalid("rt_debug_box_tests: null argument");
+    if (n < 1 || n > (1 << 24)) return invalid("rt_debug_box_tests: n must be 1 .. 2^24");
+    for (int k = 0; k < 3; ++k)
+        if (!(bound3[k] >= 0.f) || !std::isfinite(bound3[k])) return invalid("rt_debug_box_tests: bound3 must be finite and not negative");
+    RT_TRY(use_device(g_device));
+    rt_box_test_params bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.n = n;
+    for (int k = 0; k < 3; ++k) bp.bound[k] = bound3[k];
+    const size_t n3 = (size_t)n * 3 * sizeof(float), n1 = (size_t)n * sizeof(float);
+    call_memory mem;
+    const struct { const float** dev; const float* host; size_t bytes; } in[] = {
+        {&bp.bmin, bmin, n3}, {&bp.bmax, bmax, n3}, {&bp.origins, origins, n3}, {&bp.directions, directions, n3}, {&bp.tmin, tmin, n1}, {&bp.tmax, tmax, n1}};
+    for (const auto& b : in) {
+        HIPCHK(mem.get((void**)b.dev, b.bytes));
+        HIPCHK(hipMemcpy((void*)*b.dev, b.host, b.bytes, hipMemcpyHostToDevice));
+    }
+    HIPCHK(mem.get((void**)&bp.flags, (size_t)n * 4));
+    HIPCHK(hipMemset(bp.flags, 0xFF, (size_t)n * 4));   // a case the kernel skipped would show as 255
+    HIPCHK(rt_launch_box_tests(bp, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(flags, bp.flags, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 rt_status rt_debug_cal_cost(rt_scene* s, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny) {
     if (!s) return invalid("rt_debug_cal_cost: null scene");
     if (!out || !nx || !ny) return invalid("rt_debug_cal_cost: null argument");

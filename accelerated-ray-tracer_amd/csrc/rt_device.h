@@ -195,6 +195,19 @@ struct rt_prior_params {
 hipError_t rt_launch_prior(const rt_prior_params& pp, hipStream_t st);
 // the same from the scene's cost map (rt_abi.hip): `cal_cost` holds one word per local pixel of THIS frame geometry (cal_nx, cal_ny are not read)
 hipError_t rt_launch_prior_map(const rt_prior_params& pp, hipStream_t st);
+// rt_debug_box_tests (rt_kernel_boxtest.hip): n cases, one per thread; device pointers, flags[n][4]
+struct rt_box_test_params {
+    int32_t n;
+    const float* bmin;
+    const float* bmax;
+    const float* origins;
+    const float* directions;
+    const float* tmin;
+    const float* tmax;
+    float bound[3];
+    uint8_t* flags;
+};
+hipError_t rt_launch_box_tests(const rt_box_test_params& bp, hipStream_t st);
 // bytes of the tier kernel's LDS image (rt_kernel_tier.h stages exactly this): leaf arrays + slot unions, then -- where the
 // launch plan (rt_abi.hip) says so -- spheres, materials and textures
 static inline size_t rt_tier_lds_bytes(int n_slots, int n_spheres, int n_materials, int n_textures, bool scene) {

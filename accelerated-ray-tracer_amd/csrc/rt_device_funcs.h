@@ -723,17 +723,30 @@ DEV void slab_interval(const float4 lo_skip, const float4 hi_prim, const f3 o, c
     t_enter = tmin; t_exit = tmax;
 }
 
+// !b for a lane condition b that is a comparison, with the complement taken on the wave's 64-bit mask (s_not / s_andn2 on the
+// scalar side) and not by a second vector compare: given `!b` or the opposite comparison next to b itself, the compiler emits
+// one v_cmp for each.  Take it into a variable of its own before any `&&`: inside a short-circuit it is compiled under a branch.
+DEV bool lane_not(bool b) { return __builtin_amdgcn_inverse_ballot_w64(~__builtin_amdgcn_ballot_w64(b)); }
+
+// The three slabs of aabb::hit cut out of (tmin, tmax), for slab values that are numbers (no NaN): is anything left?  One
+// v_med3_f32 per axis and end instead of min + max per axis and two max3 / min3 chains (6 instructions for 10).  Exact, not a
+// superset: lo = clamp(tmin), hi = clamp(tmax) to the axis' [min(t0, t1), max(t0, t1)], so while [lo, hi] is not empty
+// med3(lo, t0, t1) = max(lo, min(t0, t1)) and med3(hi, t0, t1) = min(hi, max(t0, t1)) -- the reference's two updates -- and once
+// an axis leaves hi <= lo (both chains: tmax <= tmin there too) clamping, being monotone, keeps hi <= lo to the end.  tmin > tmax
+// starts that way and fails, as in the reference.
+DEV bool slab_interval_open(float tmin, float tmax, float x0, float x1, float y0, float y1, float z0, float z1) {
+    float lo = __builtin_amdgcn_fmed3f(tmin, x0, x1), hi = __builtin_amdgcn_fmed3f(tmax, x0, x1);
+    lo = __builtin_amdgcn_fmed3f(lo, y0, y1); hi = __builtin_amdgcn_fmed3f(hi, y0, y1);
+    lo = __builtin_amdgcn_fmed3f(lo, z0, z1); hi = __builtin_amdgcn_fmed3f(hi, z0, z1);
+    return !(hi <= lo);
+}
+
 // aabb::hit for rays whose 1/d components are all finite: identical result to slab_test()
 DEV bool slab_test_finite(const float4 lo_skip, const float4 hi_prim, const f3 o, const f3 inv, float tmin, float tmax) {
     const float x0 = (lo_skip.x - o.x) * inv.x, x1 = (hi_prim.x - o.x) * inv.x;
     const float y0 = (lo_skip.y - o.y) * inv.y, y1 = (hi_prim.y - o.y) * inv.y;
     const float z0 = (lo_skip.z - o.z) * inv.z, z1 = (hi_prim.z - o.z) * inv.z;
-    const float nearx = fminf(x0, x1), farx = fmaxf(x0, x1);
-    const float neary = fminf(y0, y1), fary = fmaxf(y0, y1);
-    const float nearz = fminf(z0, z1), farz = fmaxf(z0, z1);
-    const float t_in = fmaxf(fmaxf(fmaxf(nearx, neary), nearz), tmin);
-    const float t_out = fminf(fminf(fminf(farx, fary), farz), tmax);
-    return !(t_out <= t_in);
+    return slab_interval_open(tmin, tmax, x0, x1, y0, y1, z0, z1);
 }
 
 // ------------------------------------------------------------------ the walk loop's box test (round 3)
@@ -748,7 +761,7 @@ DEV bool slab_test_finite(const float4 lo_skip, const float4 hi_prim, const f3 o
 // (three times that).  The lower bound of an axis gets - e, the upper + e -- which of lo / hi is which depends on the sign of x.
 // Rays for which |x| (|o| + B) could overflow (a direction component below ~1e-27 of the others) take the reference's own
 // form instead, like rays with a zero component (loose_ok() is part of `finite_inv`).  A false pass costs one box step; a NaN
-// cannot occur (no product overflows), so fmin / fmax see numbers only.
+// cannot occur (no product overflows), so the medians of slab_interval_open see numbers only.
 struct LooseRay { f3 clo, chi; };   // per axis: the addend for the box's bmin and for its bmax
 DEV bool loose_ok(const f3 inv, const f3 o, const float* bound) {
     const float ex = fabsf(inv.x) * (fabsf(o.x) + bound[0]), ey = fabsf(inv.y) * (fabsf(o.y) + bound[1]), ez = fabsf(inv.z) * (fabsf(o.z) + bound[2]);
@@ -768,12 +781,7 @@ DEV bool slab_test_loose(const float4 lo_skip, const float4 hi_prim, const f3 in
     const float x0 = fmaf(lo_skip.x, inv.x, lr.clo.x), x1 = fmaf(hi_prim.x, inv.x, lr.chi.x);
     const float y0 = fmaf(lo_skip.y, inv.y, lr.clo.y), y1 = fmaf(hi_prim.y, inv.y, lr.chi.y);
     const float z0 = fmaf(lo_skip.z, inv.z, lr.clo.z), z1 = fmaf(hi_prim.z, inv.z, lr.chi.z);
-    const float nearx = fminf(x0, x1), farx = fmaxf(x0, x1);
-    const float neary = fminf(y0, y1), fary = fmaxf(y0, y1);
-    const float nearz = fminf(z0, z1), farz = fmaxf(z0, z1);
-    const float t_in = fmaxf(fmaxf(fmaxf(nearx, neary), nearz), tmin);
-    const float t_out = fminf(fminf(fminf(farx, fary), farz), tmax);
-    return !(t_out <= t_in);
+    return slab_interval_open(tmin, tmax, x0, x1, y0, y1, z0, z1);
 }
 
 }  // namespace

@@ -34,8 +34,9 @@ DEV int walk_step(const SceneView& sc, const float4* nodes4, int node, const Ray
     const bool pass = loose ? slab_test_loose(a, b, inv, lr, tmin, best.t) : slab_test(a, b, r.o, inv, tmin, best.t);
     // device encoding of the links (rt_device.h, RT_NODE_SKIP): a.w = ~skip; b.w = ~(node + 1) inside, the object id at a leaf
     const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);
-    int next = ~((pass && link < 0) ? link : nskip);
-    if (pass && link >= 0 && (!loose || slab_test_finite(a, b, r.o, inv, tmin, best.t))) {
+    const bool is_leaf = link >= 0, inner = lane_not(is_leaf);   // compared once: the complement is mask logic
+    int next = ~((pass && inner) ? link : nskip);
+    if (pass && is_leaf && (!loose || slab_test_finite(a, b, r.o, inv, tmin, best.t))) {
         leaf_test<SPHERES_ONLY>(sc, link, r, tmin, best);
         if (ANY && best.prim >= 0) next = sc.n_nodes;
     }

@@ -182,10 +182,14 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                         // an interior node and the object id (>= 0) at a leaf -- "where next" is one select and one
                         // NOT, and the stopped form ~skip is a.w as stored
                         const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);
-                        const bool at_leaf = pass && link >= 0;
-                        const bool stop = at_leaf && pend >= 0;
-                        const int next = ~((pass && link < 0) ? link : nskip);
-                        pend = (at_leaf && pend < 0) ? node : pend;
+                        // each condition is compared once; its complement is mask logic on the scalar side (lane_not,
+                        // rt_device_funcs.h) -- written `link < 0` / `pend < 0` they cost a second v_cmp each
+                        const bool is_leaf = link >= 0, noted = pend >= 0;
+                        const bool inner = lane_not(is_leaf), clear = lane_not(noted);
+                        const bool at_leaf = pass && is_leaf;
+                        const bool stop = at_leaf && noted;
+                        const int next = ~((pass && inner) ? link : nskip);
+                        pend = (at_leaf && clear) ? node : pend;
                         parked = stop ? node : parked;
                         node = stop ? nskip : next;
                     }

@@ -918,6 +918,16 @@ rt_status rt_debug_prior(const uint32_t* cal_cost, int32_t cal_nx, int32_t cal_n
                          int32_t tile_stride, uint32_t* cost_out, uint32_t* tile_cost_out, uint64_t* total_out);
 rt_status rt_debug_cal_cost(rt_scene* scene, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny);
 rt_status rt_debug_rank_info(rt_scene* scene, uint32_t* out13);
+/* diagnostics of the box tests (tests/test_box_tests.py): the walk's three forms of aabb::hit (rt_device_funcs.h: slab_test, the
+ * reference's own; slab_test_finite, its equal for rays whose 1/d is finite; slab_test_loose, the walk loop's widened one) run
+ * once, one thread per case, on caller-supplied HOST buffers: boxes bmin[n][3] / bmax[n][3], rays origins[n][3] /
+ * directions[n][3], windows tmin[n] / tmax[n], and bound3 = the scene bound the widening is taken from (every box coordinate
+ * within +-bound3[axis]; finite, not negative).  1/d and the loose terms are set up as the render sets them up.  Out:
+ * flags[n][4] = slab_test, slab_test_finite, slab_test_loose, finite_inv (1/d finite and loose_ok: the rays the render gives the
+ * two faster forms; for the others their flags are computed all the same and mean nothing).  n = 1 .. 2^24.  Needs rt_init and
+ * no scene; every argument check runs before any HIP call; null stream, synchronous. */
+rt_status rt_debug_box_tests(int32_t n, const float* bmin, const float* bmax, const float* origins, const float* directions,
+                             const float* tmin, const float* tmax, const float* bound3, uint8_t* flags);
 /* The cost map (option cost_map).  The last launches of a ranked frame leave, per local pixel, the rays the
  * pixel cost over all its samples.  A pixel's cost depends on the scene, the camera, the frame geometry and the row partition,
  * not on seed_base or ns, so the next ranked frame of the same scene uses the map once rt_frame_finish has closed the frame

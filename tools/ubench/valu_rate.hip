@@ -19,6 +19,7 @@ __global__ void k(float* out, int iters) {
         if (OP == 5) { REP16(asm volatile("v_cmp_lt_f32 vcc, %0, %4\n v_cndmask_b32 %1, %1, %4, vcc\n v_cmp_lt_f32 vcc, %2, %4\n v_cndmask_b32 %3, %3, %4, vcc" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b) : "vcc");) }
         if (OP == 6) { REP16(asm volatile("v_rcp_f32 %0, %0\n v_sqrt_f32 %1, %1\n v_rcp_f32 %2, %2\n v_sqrt_f32 %3, %3" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));) }
         if (OP == 7) { REP16(asm volatile("v_xor_b32 %0, %0, %4\n v_lshlrev_b32 %1, 3, %1\n v_add_u32 %2, %2, %4\n v_xad_u32 %3, %3, %4, %5" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b), "v"(c));) }
+        if (OP == 8) { REP16(asm volatile("v_med3_f32 %0, %0, %4, %5\n v_med3_f32 %1, %1, %4, %5\n v_med3_f32 %2, %2, %4, %5\n v_med3_f32 %3, %3, %4, %5" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b), "v"(c));) }
     }
     out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + p0.x + p0.y + p1.x + p1.y + p2.x + p3.y;
 }
@@ -45,5 +46,6 @@ int main() {
     float* d; hipMalloc(&d, 1 << 24);
     run<0>("v_fma_f32", d); run<1>("v_pk_fma_f32", d); run<2>("v_add/v_mul_f32", d); run<3>("v_pk_add/v_pk_mul_f32", d);
     run<4>("v_min/max/min3/max3_f32", d); run<5>("v_cmp+v_cndmask", d); run<6>("v_rcp/v_sqrt", d); run<7>("int xor/shl/add/xor3", d);
+    run<8>("v_med3_f32", d);
     return 0;
 }
