@@ -91,6 +91,12 @@ struct rt_rank_params {
 // `prim` holds ~(own index + 1) at an interior node (still < 0) and the object id (>= 0) at a leaf.  The walk's "where
 // next" is then ~((pass && prim < 0) ? prim : skip) -- one select, one NOT -- and the staged kernel's stopped state
 // ~skip is the stored word itself.
+// The main kernel's LDS image differs from these arrays: with its nodes in LDS (lds_mode 1-3) it walks LDS addresses, and
+// while it stages the array it rewrites the two words for that walk (stage_scene<.., true>, rt_device_funcs.h) -- skip =
+// LDS address of the skip target, prim = LDS address of the next record at an interior node and ~(object id) (< 0) at a
+// leaf.  "Where next" is then (pass && (inner || a leaf is noted)) ? prim : skip -- one select, no NOT, no address
+// arithmetic before the reads.  Nothing outside that kernel sees the image: the device arrays, every other kernel, the
+// refit kernels and rt_debug_scene_boxes keep the encoding above, as does the main kernel with lds_mode 0 and 4.
 #define RT_NODE_SKIP(stored) (~(stored))
 
 // device-resident scene: the rt_scene_desc arrays after upload

@@ -641,8 +641,22 @@ DEV void store_pixel(const rt_frame_params& fp, int i, int lrow, f3 col) {   // 
     px[2] = apply_gamma(col.z, fp.gamma);
 }
 
+// the 32-bit LDS address of a pointer into the workgroup's LDS (what ds_read takes), and a 16-byte load from such an address
+// (which: 0 or 1, the record's first or second 16 bytes -- an immediate offset of the read)
+typedef float lds_native_float4 __attribute__((ext_vector_type(4)));
+DEV int32_t lds_address(const void* p) { return (int32_t)(uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
+DEV float4 lds_load_float4(int32_t address, int which) {
+    const lds_native_float4 q = ((const __attribute__((address_space(3))) lds_native_float4*)(uintptr_t)(uint32_t)address)[which];
+    return make_float4(q.x, q.y, q.z, q.w);
+}
+DEV int32_t lds_load_word(int32_t address, int word) { return ((const __attribute__((address_space(3))) int32_t*)(uintptr_t)(uint32_t)address)[word]; }
+
 // stage nodes (+ spheres) into LDS; returns the view the traversal should use
-template <int LDS_MODE>
+// WALK_LINKS (the main kernel only, rt_kernel_staged.h): the two link words of the LDS image are re-encoded for a walk whose
+// state is a record's LDS address -- skip = address of the skip target (image base + 32 * n_nodes past the last record), prim =
+// address of the first child (the next record, >= 0) at an interior node and ~(object id) (< 0) at a leaf.  The device arrays
+// themselves (rt_device.h, RT_NODE_SKIP) are not touched.
+template <int LDS_MODE, bool WALK_LINKS = false>
 DEV SceneView stage_scene(const rt_scene_dev& sd, unsigned char* lds) {
     SceneView v;
     v.nodes = sd.nodes; v.spheres = sd.spheres; v.quads = sd.quads; v.boxes = sd.boxes; v.instances = sd.instances;
@@ -651,7 +665,18 @@ DEV SceneView stage_scene(const rt_scene_dev& sd, unsigned char* lds) {
         float4* dst = reinterpret_cast<float4*>(lds);
         const float4* src = reinterpret_cast<const float4*>(sd.nodes);
         const int n16 = sd.n_nodes * 2;
-        for (int k = threadIdx.x; k < n16; k += blockDim.x) dst[k] = src[k];
+        if (WALK_LINKS) {
+            const int32_t base = lds_address(lds);
+            for (int k = threadIdx.x; k < n16; k += blockDim.x) {
+                float4 q = src[k];
+                const int32_t w = __float_as_int(q.w);
+                // stored < 0: ~(a node index) -- every skip link, and an interior node's prim = ~(own index + 1); else a leaf's object id
+                q.w = __int_as_float(w < 0 ? base + 32 * RT_NODE_SKIP(w) : ~w);
+                dst[k] = q;
+            }
+        } else {
+            for (int k = threadIdx.x; k < n16; k += blockDim.x) dst[k] = src[k];
+        }
         v.nodes = reinterpret_cast<const rt_node*>(lds);
         if (LDS_MODE >= 2) {
             float4* dst2 = dst + n16;

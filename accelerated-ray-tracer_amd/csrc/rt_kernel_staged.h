@@ -17,9 +17,13 @@
 // shows the SIMDs are close to issue-bound at ~3-4 cycles per VALU
 // wave-instruction, so instructions issued for idle lanes are the cost.
 //
-// Here a lane's state is encoded in `node`:
-//   0 <= node < n      walking the BVH (next box test)
-//   node < 0           parked at a leaf; ~node is where the walk resumes
+// Here a lane's state is encoded in `node`.  With the nodes in global memory or scanned (LDS_MODE 0 and 4) the walk state
+// is a node index and n = n_nodes; with the nodes in LDS (LDS_MODE 1-3) it is the record's LDS byte address, n = image base
+// + 32 * n_nodes, and the links of the LDS image are addresses too (stage_scene<.., true>, rt_device_funcs.h): the step
+// reads its record at `node` itself and takes the next state from a link word as stored.
+//   0 <= node < n      walking the BVH (next box test); the root is 0 / the image base
+//   node < 0           parked at a leaf (`parked`); index form: ~node is where the walk resumes; address form: node is the
+//                      leaf's link word ~(object id) and the walk resumes at the parked record's skip link
 //   node == n + 0      traversal finished, hit/miss not yet classified
 //   node == n + 1      path ended: needs accumulate + next sample / pixel + camera ray
 //   node == n + 2      dielectric hit waiting for the (rare, long) dielectric stage
@@ -72,10 +76,18 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
     // main_skip_wgs workgroups leave at once and their slots are taken by tier workgroups.
     const int wg = (int)blockIdx.x - rk.main_skip_wgs;
     if (wg < 0) return;
-    const SceneView sc = stage_scene<LDS_MODE>(sd, lds);
+    // LDS_MODE 1-3: the walk runs on LDS addresses over an image whose links stage_scene re-encoded for it (see above)
+    constexpr bool ADDR = LDS_MODE >= 1 && LDS_MODE <= 3;
+    const SceneView sc = stage_scene<LDS_MODE, ADDR>(sd, lds);
     const float4* nodes4 = reinterpret_cast<const float4*>(sc.nodes);
     const int n_nodes = sc.n_nodes;
-    const int ST_DONE = n_nodes, ST_NEWPATH = n_nodes + 1, ST_DIEL = n_nodes + 2, ST_SETUP = n_nodes + 3, ST_DEAD = n_nodes + 4;
+    const int root = ADDR ? lds_address(lds) : 0;
+    const int limit = ADDR ? __builtin_amdgcn_readfirstlane(root + 32 * n_nodes) : n_nodes;   // (scalar: a VGPR less)
+    const int ST_DONE = limit, ST_NEWPATH = limit + 1, ST_DIEL = limit + 2, ST_SETUP = limit + 3, ST_DEAD = limit + 4;
+    // a node's two float4 and a leaf's object id, from a walk state / a noted leaf in either form
+    auto node_lo = [&](int at) -> float4 { return ADDR ? lds_load_float4(at, 0) : nodes4[2 * at]; };
+    auto node_hi = [&](int at) -> float4 { return ADDR ? lds_load_float4(at, 1) : nodes4[2 * at + 1]; };
+    auto leaf_prim = [](const float4 hi) -> int32_t { return ADDR ? ~__float_as_int(hi.w) : __float_as_int(hi.w); };
     const float tmin = 0.001f;
 
     rt_xorwow g = {0, 0, 0, 0, 0, 0};
@@ -162,7 +174,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
         // limit.  Walking with a stale (larger) limit therefore visits a superset of the leaves, and the re-test in
         // stage B keeps exactly the reference's.  Rays with a zero direction component (no monotonicity: 0 * inf) stop
         // at every leaf, as before.
-        if (__ballot(!finite_inv && (unsigned)node < (unsigned)n_nodes) == 0ull) {
+        if (__ballot(!finite_inv && (unsigned)node < (unsigned)limit) == 0ull) {
             // two node steps per check: "nobody left walking" (all stopped or finished) ends the trip -- this is what
             // keeps the latency of a wave's last few live lanes near one node step per step (end of frame, small
             // multi-GPU partitions); checking every other step halves the loop's scalar overhead
@@ -171,43 +183,68 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
             // aabb::hit's passes, which is all the walk needs -- stage B tests every noted leaf's own box again, exactly
             const LooseRay lr = loose_setup(inv, cur.o, sd.bound);
             for (int pair = 0; pair < trip_pairs; ++pair) {
-                if (__ballot((unsigned)node < (unsigned)n_nodes) == 0ull) break;
+                if (__ballot((unsigned)node < (unsigned)limit) == 0ull) break;
 #pragma unroll
                 for (int half = 0; half < RT_STEP_UNROLL; ++half) {
-                    DIAG_ADD(1, 1); DIAG_ADD(2, __popcll(__ballot((unsigned)node < (unsigned)n_nodes)));
-                    if ((unsigned)node < (unsigned)n_nodes) {
-                        const float4 a = nodes4[2 * node], b = nodes4[2 * node + 1];
+                    DIAG_ADD(1, 1); DIAG_ADD(2, __popcll(__ballot((unsigned)node < (unsigned)limit)));
+                    if ((unsigned)node < (unsigned)limit) {
+                        const float4 a = node_lo(node), b = node_hi(node);
                         const bool pass = slab_test_loose(a, b, inv, lr, tmin, best.t);
-                        // device encoding of the links (rt_device.h, RT_NODE_SKIP): a.w = ~skip, b.w = ~(node + 1) for
-                        // an interior node and the object id (>= 0) at a leaf -- "where next" is one select and one
-                        // NOT, and the stopped form ~skip is a.w as stored
-                        const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);
-                        // each condition is compared once; its complement is mask logic on the scalar side (lane_not,
-                        // rt_device_funcs.h) -- written `link < 0` / `pend < 0` they cost a second v_cmp each
-                        const bool is_leaf = link >= 0, noted = pend >= 0;
-                        const bool inner = lane_not(is_leaf), clear = lane_not(noted);
-                        const bool at_leaf = pass && is_leaf;
-                        const bool stop = at_leaf && noted;
-                        const int next = ~((pass && inner) ? link : nskip);
-                        pend = (at_leaf && clear) ? node : pend;
-                        parked = stop ? node : parked;
-                        node = stop ? nskip : next;
+                        // In both forms each condition is compared once; its complement is mask logic on the scalar side
+                        // (lane_not, rt_device_funcs.h) -- written as the opposite comparison it costs a second v_cmp.
+                        if (ADDR) {
+                            // the LDS image's links (stage_scene): a.w = address of the skip target, b.w = address of the
+                            // first child (>= 0) at an interior node and ~(object id) (< 0) at a leaf, which is the stopped
+                            // state as stored -- "where next" is one select between the two words: down on a pass inside,
+                            // stopped on a pass at a second leaf, else (failed, or a first leaf noted) on to the skip
+                            // target.  `node` is written last, in place: the two selects before it still read the old one.
+                            const int32_t link = __float_as_int(b.w), skip = __float_as_int(a.w);
+                            const bool is_leaf = link < 0, noted = pend >= 0;
+                            const bool inner = lane_not(is_leaf), clear = lane_not(noted);
+                            const bool at_leaf = pass && is_leaf;
+                            const bool stop = at_leaf && noted;
+                            pend = (at_leaf && clear) ? node : pend;
+                            parked = stop ? node : parked;
+                            node = (pass && (inner || noted)) ? link : skip;
+                        } else {
+                            // device encoding of the links (rt_device.h, RT_NODE_SKIP): a.w = ~skip, b.w = ~(node + 1) for
+                            // an interior node and the object id (>= 0) at a leaf -- "where next" is one select and one
+                            // NOT, and the stopped form ~skip is a.w as stored
+                            const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);
+                            const bool is_leaf = link >= 0, noted = pend >= 0;
+                            const bool inner = lane_not(is_leaf), clear = lane_not(noted);
+                            const bool at_leaf = pass && is_leaf;
+                            const bool stop = at_leaf && noted;
+                            const int next = ~((pass && inner) ? link : nskip);
+                            pend = (at_leaf && clear) ? node : pend;
+                            parked = stop ? node : parked;
+                            node = stop ? nskip : next;
+                        }
                     }
                 }
             }
         } else {   // a lane's ray has a zero direction component: the reference's own slab form for this trip
             for (int step = 0; step < fp.steps_per_trip; ++step) {
-                if (__ballot((unsigned)node < (unsigned)n_nodes) == 0ull) break;
-                if ((unsigned)node < (unsigned)n_nodes) {
-                    const float4 a = nodes4[2 * node], b = nodes4[2 * node + 1];
+                if (__ballot((unsigned)node < (unsigned)limit) == 0ull) break;
+                if ((unsigned)node < (unsigned)limit) {
+                    const float4 a = node_lo(node), b = node_hi(node);
                     const bool pass = slab_test(a, b, cur.o, inv, tmin, best.t);
-                    const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);
-                    const bool at_leaf = pass && link >= 0;
-                    const bool stop = at_leaf && (pend >= 0 || !finite_inv);
-                    const int next = ~((pass && link < 0) ? link : nskip);
-                    pend = (at_leaf && !stop) ? node : pend;
-                    parked = stop ? node : parked;
-                    node = stop ? nskip : next;
+                    if (ADDR) {   // (links as in the loop above)
+                        const int32_t link = __float_as_int(b.w), skip = __float_as_int(a.w);
+                        const bool at_leaf = pass && link < 0;
+                        const bool stop = at_leaf && (pend >= 0 || !finite_inv);
+                        pend = (at_leaf && !stop) ? node : pend;
+                        parked = stop ? node : parked;
+                        node = (pass && (link >= 0 || stop)) ? link : skip;
+                    } else {
+                        const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);
+                        const bool at_leaf = pass && link >= 0;
+                        const bool stop = at_leaf && (pend >= 0 || !finite_inv);
+                        const int next = ~((pass && link < 0) ? link : nskip);
+                        pend = (at_leaf && !stop) ? node : pend;
+                        parked = stop ? node : parked;
+                        node = stop ? nskip : next;
+                    }
                 }
             }
         }
@@ -219,7 +256,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
         for (;;) {
             const int cand = pend >= 0 ? pend : (node < 0 ? parked : -1);
             const unsigned long long due_mask = __ballot(cand >= 0);
-            const bool nobody_steps = __ballot((unsigned)node < (unsigned)n_nodes) == 0ull;
+            const bool nobody_steps = __ballot((unsigned)node < (unsigned)limit) == 0ull;
             const int live_b = __popcll(__ballot(node != ST_DEAD));
             if (due_mask != 0ull && (nobody_steps || sparse || __popcll(due_mask) >= 1 + ((fp.leaf_threshold - 1) * live_b >> 6))) {
                 DIAG_ADD(3, 1); DIAG_ADD(4, __popcll(due_mask));
@@ -227,8 +264,8 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                 int32_t prim = -1;
                 bool box_ok = false;
                 if (cand >= 0) {
-                    const float4 a = nodes4[2 * cand], b = nodes4[2 * cand + 1];
-                    prim = __float_as_int(b.w);
+                    const float4 a = node_lo(cand), b = node_hi(cand);
+                    prim = leaf_prim(b);
                     kind = SPHERES_ONLY ? RT_PRIM_SPHERE : RT_PRIM_KIND(prim);
                     // the leaf's own box against the limit of THIS moment (see stage A); a ray with a zero direction
                     // component stopped right at the leaf, so its walk-time result still stands
@@ -272,10 +309,15 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                     }
                 }
                 if (tested) {
-                    if (node < 0) { pend = pend >= 0 ? parked : -1; parked = -1; node = ~node; }
+                    if (node < 0) {
+                        // (address form: the stopped state does not hold the way on; the parked leaf's skip link does --
+                        // `cand` was the noted leaf, not this one, when both were due)
+                        node = ADDR ? lds_load_word(parked, 3) : ~node;
+                        pend = pend >= 0 ? parked : -1; parked = -1;
+                    }
                     else pend = -1;
                 }
-                if (nobody_steps && __ballot((unsigned)node < (unsigned)n_nodes) == 0ull && __ballot(pend >= 0 || node < 0) != 0ull) continue;
+                if (nobody_steps && __ballot((unsigned)node < (unsigned)limit) == 0ull && __ballot(pend >= 0 || node < 0) != 0ull) continue;
             }
             break;
         }
@@ -286,7 +328,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
             radiance = fma3(throughput, miss_color(fp, cur), radiance);
             node = ST_NEWPATH;
         }
-        const unsigned long long walking = __ballot(node < n_nodes);
+        const unsigned long long walking = __ballot(node < limit);
         const bool force = walking == 0ull;
         const int n_done = __popcll(__ballot(node == ST_DONE && pend < 0));
         bool ran_stage = false;
@@ -502,7 +544,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                 finite_inv = inv_is_finite(inv) && loose_ok(inv, cur.o, sd.bound);   // (else: the reference's own slab form, leaf by leaf)
                 cur_a = dot(cur.d, cur.d);
                 best.t = FLT_MAX; best.prim = -1; best.inst = -1;
-                node = n_nodes > 0 ? 0 : ST_DONE;
+                node = n_nodes > 0 ? root : ST_DONE;
                 ++rays;
             }
         } else if (force) {
