@@ -119,6 +119,11 @@ class RtReprojectMotionDesc(C.Structure):
                 ("media", C.c_void_p), ("time", C.c_float), ("prev_time", C.c_float)]
 
 
+class RtReprojectInstanceDesc(C.Structure):
+    _fields_ = [("n_instances", C.c_int32), ("reserved", C.c_int32), ("instances", C.c_void_p), ("prev_instances", C.c_void_p),
+                ("inst", C.c_void_p), ("prev_inst", C.c_void_p)]
+
+
 class RtSphereUpdate(C.Structure):
     _fields_ = [("count", C.c_int32), ("first", C.c_int32), ("indices", C.c_void_p), ("spheres", C.c_void_p)]
 
@@ -183,7 +188,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_scene_update_spheres", "rt_scene_get_spheres", "rt_multi_update_spheres", "rt_refit_nodes", "rt_debug_scene_boxes",
                   "rt_reproject_moving", "rt_debug_cost_map", "rt_debug_set_cost_map",
                   "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances",
-                  "rt_debug_box_tests"]
+                  "rt_debug_box_tests", "rt_reproject_instances"]
 
 _rt = None
 _host = None
@@ -286,6 +291,9 @@ def rt_lib():
         L.rt_reproject.argtypes = [C.POINTER(RtReprojectDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_reproject_matrix.argtypes = [C.POINTER(RtCamera), C.POINTER(C.c_float)]
         L.rt_reproject_moving.argtypes = [C.POINTER(RtReprojectDesc), C.POINTER(RtReprojectMotionDesc), C.c_int, C.c_void_p, C.c_int]
+        if hasattr(L, "rt_reproject_instances"):   # (absent from an older library measured through RT_LIB_OVERRIDE)
+            L.rt_reproject_instances.argtypes = [C.POINTER(RtReprojectDesc), C.POINTER(RtReprojectMotionDesc), C.POINTER(RtReprojectInstanceDesc),
+                                                 C.c_int, C.c_void_p, C.c_int]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.rt_debug_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_debug_prior.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -582,7 +590,8 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
               prev_depth=None, prev_alpha=None, prev_normal=None, prev_prim=None, *, out=None, out_len=None, motion=False,
               alpha_min=REPROJECT_DEFAULTS["alpha_min"], depth_tol=REPROJECT_DEFAULTS["depth_tol"],
               normal_min=REPROJECT_DEFAULTS["normal_min"], max_history=REPROJECT_DEFAULTS["max_history"], stream=0, blocking=True,
-              spheres=None, prev_spheres=None, media=None, time=None, prev_time=None):
+              spheres=None, prev_spheres=None, media=None, time=None, prev_time=None,
+              inst=None, prev_inst=None, instances=None, prev_instances=None):
     """Temporal reprojection (rt_reproject, include/rt_abi.h): the current linear frame `color` (ny, nx, 3) blended into the
     history of the previous frame, fetched where each pixel's surface point -- from `depth` and `alpha` (ny, nx) of
     render_aov and the cameras `cur` and `prev` -- was in that frame.  history (ny, nx, 3) and history_len (ny, nx) are the
@@ -602,7 +611,14 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     history follows the sphere and `motion` holds its motion too.  prim and prev_prim are then required.  With numpy buffers
     the tables are arrays of SPHERE_DTYPE / MEDIUM_DTYPE; with tensors they are contiguous (n, 8) / (n, 4) tensors of a
     4-byte dtype on the device, as update_spheres takes them.  time / prev_time: the instants at which centres c0 + t vel
-    are taken; default: the shutter centre of `cur` / `prev`.  With spheres=None the other four must be None too."""
+    are taken; default: the shutter centre of `cur` / `prev`.  With spheres=None and instances=None the other four must be None too.
+
+    instances / prev_instances (rt_reproject_instances): the instance records the current and the previous frame were rendered
+    with (DeviceScene.instances() after and before update_instances), arrays of INSTANCE_DTYPE or (n, 8) tensors.  A surface
+    pixel on an instance whose record differs -- or in a medium bounded by one -- is carried back through the two records, its
+    normal with it.  inst (ny, nx) int32, render_aov's `inst` of the current frame, is then required beside prim and prev_prim,
+    and prev_inst exactly when history is given; a tap must show the pixel's instance.  The sphere arguments stay optional
+    beside these.  With instances=None the other three must be None too."""
     on_host = isinstance(color, np.ndarray)
     if not on_host and not hasattr(color, "data_ptr"):
         raise ValueError("color: a numpy array or a torch tensor is expected")
@@ -645,22 +661,27 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     elif motion is False:
         motion = None
 
-    md = None
-    if spheres is None:
+    md, imd = None, None
+    if instances is None and any(x is not None for x in (inst, prev_inst, prev_instances)):
+        raise ValueError("inst, prev_inst and prev_instances need instances")
+    if spheres is None and instances is None:
         if any(x is not None for x in (prev_spheres, media, time, prev_time)):
-            raise ValueError("prev_spheres, media, time and prev_time need spheres")
+            raise ValueError("prev_spheres, media, time and prev_time need spheres or instances")
     else:
-        if prev_spheres is None:
+        if spheres is None and prev_spheres is not None:
+            raise ValueError("prev_spheres needs spheres")
+        if spheres is not None and prev_spheres is None:
             raise ValueError("spheres needs prev_spheres")
         if prim is None or prev_prim is None:
-            raise ValueError("spheres: prim and prev_prim are required to follow spheres")
+            raise ValueError("spheres / instances: prim and prev_prim are required to follow what moved")
         md = RtReprojectMotionDesc()
         keep_tables = []
+        dtype_names = {id(SPHERE_DTYPE): "SPHERE", id(MEDIUM_DTYPE): "MEDIUM", id(INSTANCE_DTYPE): "INSTANCE"}
 
         def table(x, name, dtype, words):
             if on_host:
                 if not isinstance(x, np.ndarray) or x.dtype != dtype or x.ndim != 1:
-                    raise ValueError(f"{name}: a one-dimensional numpy array of {'MEDIUM' if words == 4 else 'SPHERE'}_DTYPE is expected (color is one)")
+                    raise ValueError(f"{name}: a one-dimensional numpy array of {dtype_names[id(dtype)]}_DTYPE is expected (color is one)")
                 x = np.ascontiguousarray(x)
                 keep_tables.append(x)
                 return len(x), (x.ctypes.data if len(x) else None)
@@ -669,10 +690,11 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             if x.ndim != 2 or x.shape[1] != words or x.element_size() != 4 or not x.is_contiguous() or x.device != dev:
                 raise ValueError(f"{name}: a contiguous (n, {words}) tensor of a 4-byte dtype on {dev} is expected")
             return int(x.shape[0]), (x.data_ptr() if x.shape[0] else None)
-        md.n_spheres, md.spheres = table(spheres, "spheres", SPHERE_DTYPE, 8)
-        n_prev, md.prev_spheres = table(prev_spheres, "prev_spheres", SPHERE_DTYPE, 8)
-        if n_prev != md.n_spheres:
-            raise ValueError(f"prev_spheres: {n_prev} records, spheres has {md.n_spheres}")
+        if spheres is not None:
+            md.n_spheres, md.spheres = table(spheres, "spheres", SPHERE_DTYPE, 8)
+            n_prev, md.prev_spheres = table(prev_spheres, "prev_spheres", SPHERE_DTYPE, 8)
+            if n_prev != md.n_spheres:
+                raise ValueError(f"prev_spheres: {n_prev} records, spheres has {md.n_spheres}")
         if media is not None:
             md.n_media, md.media = table(media, "media", MEDIUM_DTYPE, 4)
         if md.n_spheres >= 1 << 28 or md.n_media >= 1 << 28:
@@ -681,6 +703,20 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
         md.prev_time = float(np.float32(0.5 * (prev.time0 + prev.time1))) if prev_time is None else float(np.float32(prev_time))
         if not np.isfinite(md.time) or not np.isfinite(md.prev_time):
             raise ValueError("time and prev_time must be finite")
+        if instances is not None:
+            if prev_instances is None:
+                raise ValueError("instances needs prev_instances")
+            if inst is None:
+                raise ValueError("instances: inst is required, it says which instance a pixel shows")
+            if (prev_inst is None) != (history is None):
+                raise ValueError("instances: prev_inst is required exactly when history is given")
+            imd = RtReprojectInstanceDesc()
+            imd.n_instances, imd.instances = table(instances, "instances", INSTANCE_DTYPE, 8)
+            n_prev, imd.prev_instances = table(prev_instances, "prev_instances", INSTANCE_DTYPE, 8)
+            if n_prev != imd.n_instances:
+                raise ValueError(f"prev_instances: {n_prev} records, instances has {imd.n_instances}")
+            if imd.n_instances >= 1 << 28:
+                raise ValueError("instances: 2^28 records or more")
 
     def ptr(x, name, shape, integer=False):
         if x is None:
@@ -709,18 +745,23 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     d.prev_normal, d.prev_prim = ptr(prev_normal, "prev_normal", rgb), ptr(prev_prim, "prev_prim", one, True)
     d.out, d.out_len, d.motion = ptr(out, "out", rgb), ptr(out_len, "out_len", one), ptr(motion, "motion", (ny, nx, 2))
     d.alpha_min, d.depth_tol, d.normal_min, d.max_history = alpha_min, depth_tol, normal_min, max_history
+    if imd is not None:
+        imd.inst, imd.prev_inst = ptr(inst, "inst", one, True), ptr(prev_inst, "prev_inst", one, True)
     if hasattr(stream, "cuda_stream"):
         stream = stream.cuda_stream
     L = rt_lib()
     stream_p = C.c_void_p(int(stream)) if stream else None
     if md is None:
         st = L.rt_reproject(C.byref(d), 0 if on_host else 1, stream_p, 1 if blocking else 0)
-    else:
+    elif imd is None:
         st = L.rt_reproject_moving(C.byref(d), C.byref(md), 0 if on_host else 1, stream_p, 1 if blocking else 0)
+        del keep_tables
+    else:
+        st = L.rt_reproject_instances(C.byref(d), C.byref(md), C.byref(imd), 0 if on_host else 1, stream_p, 1 if blocking else 0)
         del keep_tables
     if st == 1:
         raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_reproject" if md is None else "rt_reproject_moving")
+    _check(st, "rt_reproject" if md is None else "rt_reproject_moving" if imd is None else "rt_reproject_instances")
     return ReprojectResult(out, out_len, motion)
 
 
@@ -1453,9 +1494,15 @@ class TemporalAccumulator:
     follow_spheres=True: the history follows spheres that moved between two pushes (reproject(spheres=...)).  push() then also
     takes an update (spheres, indices, first: DeviceScene.update_spheres' arguments) that it applies first, reads the scene's
     records back (32 bytes per sphere) and reprojects with them, the previous push's records and the scene's media; updates
-    the caller made on the scene between two pushes are followed just the same."""
+    the caller made on the scene between two pushes are followed just the same.
 
-    def __init__(self, scene: "DeviceScene", frame: RtFrameDesc, denoise: bool = False, follow_spheres: bool = False, **params):
+    follow_instances=True: likewise for instances (reproject(instances=...)).  push() takes an update (instances,
+    instance_indices, instance_first: DeviceScene.update_instances' arguments) that it applies first, reads the scene's instance
+    records back, keeps them and render_aov's `inst` with the push, and reprojects with both pushes' records and planes.  The two
+    flags combine."""
+
+    def __init__(self, scene: "DeviceScene", frame: RtFrameDesc, denoise: bool = False, follow_spheres: bool = False,
+                 follow_instances: bool = False, **params):
         unknown = set(params) - set(REPROJECT_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown parameter(s) {sorted(unknown)}: one of {', '.join(REPROJECT_DEFAULTS)} is expected")
@@ -1464,7 +1511,7 @@ class TemporalAccumulator:
         if frame.tile_first != 0 or frame.tile_stride != 1 or frame.tile_rows < frame.ny:
             raise ValueError("TemporalAccumulator needs the whole frame (tile_rows >= ny, tile_first = 0, tile_stride = 1)")
         self.scene, self.denoise, self.params = scene, bool(denoise), dict(REPROJECT_DEFAULTS, **params)
-        self.follow_spheres = bool(follow_spheres)
+        self.follow_spheres, self.follow_instances = bool(follow_spheres), bool(follow_instances)
         self.frame = RtFrameDesc.from_buffer_copy(frame)
         self.frame.gamma = 1.0
         self.aov_frame = RtFrameDesc.from_buffer_copy(self.frame)
@@ -1476,8 +1523,15 @@ class TemporalAccumulator:
         self._prev = None
         self.length = None
 
-    def push(self, camera: RtCamera, recalibrate: bool = False, spheres=None, indices=None, first: int = 0) -> np.ndarray:
-        records = None
+    def push(self, camera: RtCamera, recalibrate: bool = False, spheres=None, indices=None, first: int = 0, instances=None,
+             instance_indices=None, instance_first: int = 0) -> np.ndarray:
+        records, instance_records = None, None
+        if self.follow_instances:
+            if instances is not None:
+                self.scene.update_instances(instances, instance_indices, instance_first)
+            instance_records = self.scene.instances()
+        elif instances is not None or instance_indices is not None or instance_first != 0:
+            raise ValueError("instances, instance_indices and instance_first need follow_instances=True")
         if self.follow_spheres:
             if spheres is not None:
                 self.scene.update_spheres(spheres, indices, first)
@@ -1495,10 +1549,13 @@ class TemporalAccumulator:
             follow = {}
             if records is not None:
                 follow = dict(spheres=records, prev_spheres=p["spheres"], media=self.scene.host.media())
+            if instance_records is not None:
+                follow.update(instances=instance_records, prev_instances=p["instances"], inst=aov["inst"], prev_inst=p["inst"],
+                              media=self.scene.host.media())
             r = reproject(color, aov["depth"], aov["alpha"], cam, p["camera"], aov["normal"], aov["prim"], p["out"], p["length"],
                           p["depth"], p["alpha"], p["normal"], p["prim"], **self.params, **follow)
         self._prev = {"camera": cam, "out": r.out, "length": r.length, "depth": aov["depth"], "alpha": aov["alpha"],
-                      "normal": aov["normal"], "prim": aov["prim"], "spheres": records}
+                      "normal": aov["normal"], "prim": aov["prim"], "spheres": records, "instances": instance_records, "inst": aov["inst"]}
         self.length = r.length
         if self.denoise:
             return denoise(r.out, aov["albedo"], aov["normal"], aov["depth"])

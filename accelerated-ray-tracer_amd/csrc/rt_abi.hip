@@ -2030,8 +2030,10 @@ rt_status rt_reproject_matrix(const rt_camera* prev, float m[9]) {
 }
 
 namespace {
-// rt_reproject (m == null) and rt_reproject_moving: the checks, the staging of host buffers and the parameter block are one
-rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, const char* who, int buffers_on_device, void* stream_v, int blocking) {
+// rt_reproject (m == null), rt_reproject_moving and rt_reproject_instances (im != null, with m): the checks, the staging of host
+// buffers and the parameter block are one
+rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, const rt_reproject_instance_desc* im, const char* who,
+                         int buffers_on_device, void* stream_v, int blocking) {
     // argument checks: no HIP call before they pass
     auto bad = [&](const char* why) { return invalid((std::string(who) + ": " + why).c_str()); };
     if (!d) return bad("null description");
@@ -2059,15 +2061,24 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
         if (m->n_media > 0 && !m->media) return bad("n_media > 0 needs media");
         if (!std::isfinite(m->time) || !std::isfinite(m->prev_time)) return bad("time and prev_time must be finite");
     }
+    if (im) {
+        if (!im->inst) return bad("null inst: it says which instance a pixel shows");
+        if (d->history ? !im->prev_inst : im->prev_inst != nullptr) return bad("prev_inst must be non-null exactly when history is");
+        if (im->n_instances < 0) return bad("n_instances must not be negative");
+        if (im->n_instances >= (1 << 28)) return bad("n_instances must be below 2^28");
+        if (im->n_instances > 0 && (!im->instances || !im->prev_instances)) return bad("n_instances > 0 needs instances and prev_instances");
+    }
     rt_reproject_params rp;
     memset(&rp, 0, sizeof(rp));
     if (rt_reproject_matrix(&d->prev, rp.m) != RT_OK) return bad("prev: the camera's basis is singular or its inverse is not finite");
     const size_t pixels = (size_t)d->nx * d->ny;
     struct buffer : traced_ptr { bool input; };
     enum { COLOR = 0, DEPTH, ALPHA, NORMAL, PRIM, HISTORY, HISTORY_LEN, PREV_DEPTH, PREV_ALPHA, PREV_NORMAL, PREV_PRIM, OUT, OUT_LEN, MOTION,
-           SPHERES, PREV_SPHERES, MEDIA, N_BUFS };   // the three tables: rt_reproject_moving only, inputs behind the outputs
+           SPHERES, PREV_SPHERES, MEDIA,            // the three tables: rt_reproject_moving and up, inputs behind the outputs
+           INSTANCES, PREV_INSTANCES, INST, PREV_INST, N_BUFS };   // rt_reproject_instances only
     const size_t f1 = pixels * sizeof(float), f3 = 3 * f1;
     const size_t sphere_bytes = m ? (size_t)m->n_spheres * sizeof(rt_sphere) : 0, medium_bytes = m ? (size_t)m->n_media * sizeof(rt_medium) : 0;
+    const size_t instance_bytes = im ? (size_t)im->n_instances * sizeof(rt_instance) : 0;
     const buffer bufs[N_BUFS] = {{{d->color, f3, "color", 4}, true}, {{d->depth, f1, "depth", 4}, true}, {{d->alpha, f1, "alpha", 4}, true},
                                  {{d->normal, f3, "normal", 4}, true}, {{d->prim, f1, "prim", 4}, true}, {{d->history, f3, "history", 4}, true},
                                  {{d->history_len, f1, "history_len", 4}, true}, {{d->prev_depth, f1, "prev_depth", 4}, true},
@@ -2076,7 +2087,10 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
                                  {{d->motion, 2 * f1, "motion", 4}, false},
                                  {{sphere_bytes ? m->spheres : nullptr, sphere_bytes, "spheres", 4}, true},
                                  {{sphere_bytes ? m->prev_spheres : nullptr, sphere_bytes, "prev_spheres", 4}, true},
-                                 {{medium_bytes ? m->media : nullptr, medium_bytes, "media", 4}, true}};
+                                 {{medium_bytes ? m->media : nullptr, medium_bytes, "media", 4}, true},
+                                 {{instance_bytes ? im->instances : nullptr, instance_bytes, "instances", 4}, true},
+                                 {{instance_bytes ? im->prev_instances : nullptr, instance_bytes, "prev_instances", 4}, true},
+                                 {{im ? im->inst : nullptr, f1, "inst", 4}, true}, {{im ? im->prev_inst : nullptr, f1, "prev_inst", 4}, true}};
     for (int o = OUT; o <= MOTION; ++o)     // an output shares no byte with any other buffer
         for (int k = 0; k < N_BUFS; ++k) {
             const uintptr_t pa = (uintptr_t)bufs[o].p, pb = (uintptr_t)bufs[k].p;
@@ -2124,12 +2138,20 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
     }
     rp.alpha_min = d->alpha_min; rp.depth_tol = d->depth_tol; rp.normal_min = d->normal_min; rp.max_history = d->max_history;
     if (m) {
-        rt_reproject_follow_params fp;
-        memset(&fp, 0, sizeof(fp));
+        rt_reproject_follow_instance_params ip;
+        memset(&ip, 0, sizeof(ip));
+        rt_reproject_follow_params& fp = ip;
         fp.spheres = static_cast<const rt_sphere*>(dev[SPHERES]); fp.prev_spheres = static_cast<const rt_sphere*>(dev[PREV_SPHERES]);
         fp.media = static_cast<const rt_medium*>(dev[MEDIA]);
         fp.n_spheres = m->n_spheres; fp.n_media = m->n_media; fp.time = m->time; fp.prev_time = m->prev_time;
-        HIPCHK(rt_launch_reproject_moving(normals_on, motion_on, rp, fp, stream));
+        if (im) {
+            ip.instances = static_cast<const rt_instance*>(dev[INSTANCES]); ip.prev_instances = static_cast<const rt_instance*>(dev[PREV_INSTANCES]);
+            ip.inst = iptr(INST); ip.prev_inst = iptr(PREV_INST);
+            ip.n_instances = im->n_instances;
+            HIPCHK(rt_launch_reproject_instances(normals_on, motion_on, rp, ip, stream));
+        } else {
+            HIPCHK(rt_launch_reproject_moving(normals_on, motion_on, rp, fp, stream));
+        }
     } else {
         HIPCHK(rt_launch_reproject(normals_on, ids_on, motion_on, rp, stream));
     }
@@ -2142,12 +2164,19 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
 }  // namespace
 
 rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* stream_v, int blocking) {
-    return reproject_impl(d, nullptr, "rt_reproject", buffers_on_device, stream_v, blocking);
+    return reproject_impl(d, nullptr, nullptr, "rt_reproject", buffers_on_device, stream_v, blocking);
 }
 
 rt_status rt_reproject_moving(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, int buffers_on_device, void* stream_v, int blocking) {
     if (!m) return invalid("rt_reproject_moving: null motion description");
-    return reproject_impl(d, m, "rt_reproject_moving", buffers_on_device, stream_v, blocking);
+    return reproject_impl(d, m, nullptr, "rt_reproject_moving", buffers_on_device, stream_v, blocking);
+}
+
+rt_status rt_reproject_instances(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, const rt_reproject_instance_desc* im,
+                                 int buffers_on_device, void* stream_v, int blocking) {
+    if (!m) return invalid("rt_reproject_instances: null motion description");
+    if (!im) return invalid("rt_reproject_instances: null instance description");
+    return reproject_impl(d, m, im, "rt_reproject_instances", buffers_on_device, stream_v, blocking);
 }
 
 // Tail hand-off of the last frame (diagnostics, every build): [0] pixels the main kernel handed to the tail launches, summed over

@@ -456,6 +456,16 @@ struct rt_reproject_follow_params {
     float time, prev_time;           // c = c0 + time * vel
 };
 hipError_t rt_launch_reproject_moving(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_params& fp, hipStream_t st);
+// rt_reproject_instances: the third form of that argument -- the sphere tables (n_spheres may be 0) and, beside them, the instance
+// records of both frames and the two inst planes of rt_render_aov.  prev_inst is null exactly when rp.history is.
+struct rt_reproject_follow_instance_params : rt_reproject_follow_params {
+    const rt_instance* instances;        // n_instances records of the current frame
+    const rt_instance* prev_instances;   // ... and of the previous frame, same order
+    const int32_t* inst;                 // ny * nx, current
+    const int32_t* prev_inst;            // ny * nx, previous
+    int32_t n_instances, pad;
+};
+hipError_t rt_launch_reproject_instances(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_instance_params& ip, hipStream_t st);
 
 // rt_scene_update_spheres (rt_kernel_refit.hip; include/rt_abi.h): the moved spheres' records, their leaves'
 // boxes in every array that holds them, the per-64-leaf unions, the scene's coordinate bound and every interior box of both

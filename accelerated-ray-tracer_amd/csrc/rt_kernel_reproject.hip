@@ -18,6 +18,13 @@
 // record and, issued together, the two 32-byte sphere records -- whose lines the lanes of one sphere share; the instantiations
 // without the argument are, instruction for instruction, what they were before it existed.
 //
+// rt_reproject_instances ("temporal reprojection that follows moved instances") passes a third form of that
+// argument, the sphere tables extended by the instance records of both frames and the two inst planes.  inst[p] is loaded with
+// the pixel's own data; the follow phase is still one round trip -- at most one medium record, then either the two 32-byte
+// instance records or the two sphere records, issued together -- and prev_inst is one more plane among the taps.  A pixel on a
+// moved instance has its point and, with normals on, its normal taken through the current record's world -> object map and the
+// previous record's object -> world map.  The twelve other instantiations are again what they were.
+//
 // The arithmetic is the contract's, statement by statement (-ffp-contract=off: no FMA is formed).
 //
 // Bounds.  The pixel's own index is tested against the frame before any address is formed.  A tap address is formed only from
@@ -27,7 +34,8 @@
 // other buffers hold; a tap outside the image reads at the pixel's own index instead and is not counted.  The loads of all
 // four taps are issued together, ahead of the tests that decide whether a tap counts.  The follow step forms two more kinds of
 // address from data: media[index] after index < n_media and spheres[k] / prev_spheres[k] after k < n_spheres, both compared
-// unsigned; what the records hold is only ever arithmetic.
+// unsigned; what the records hold is only ever arithmetic.  The instance form adds instances[i] / prev_instances[i] after
+// i < n_instances, compared unsigned, and inst / prev_inst at the pixel and tap indices bounded above; flag bits are only tested.
 #include "rt_device.h"
 #include "rt_launch.h"
 
@@ -39,13 +47,17 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 
 // the kernel's optional second argument (the FOL branch is not instantiated without one)
 __device__ __forceinline__ const rt_reproject_follow_params& follow_tables(const rt_reproject_follow_params& fp) { return fp; }
+__device__ __forceinline__ const rt_reproject_follow_instance_params& instance_tables(const rt_reproject_follow_instance_params& ip) { return ip; }
+template <class... Follow> struct follows_instances { static constexpr bool value = false; };
+template <> struct follows_instances<rt_reproject_follow_instance_params> { static constexpr bool value = true; };
 
 // rt_reproject launches <NRM, IDS, MOT> with no second argument.  rt_reproject_moving passes its tables as one: FOL, step 1 gains
 // its tail (a surface pixel on a sphere whose record changed is carried back to where that surface point was) and prim[p] is read
-// whatever IDS says.
+// whatever IDS says.  rt_reproject_instances passes rt_reproject_follow_instance_params: INS, the tail looks for an instance first
+// and a tap must also show the pixel's inst.
 template <bool NRM, bool IDS, bool MOT, class... Follow>
 __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_reproject_params rp, Follow... follow) {
-    constexpr bool FOL = sizeof...(Follow) > 0;
+    constexpr bool FOL = sizeof...(Follow) > 0, INS = follows_instances<Follow...>::value;
     const int tid = threadIdx.x;
     const int nx = rp.nx, ny = rp.ny;
     const unsigned by = blockIdx.x / (unsigned)rp.tiles_x, bx = blockIdx.x - by * (unsigned)rp.tiles_x;
@@ -59,6 +71,8 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
     if (NRM) { npx = rp.normal[3 * p]; npy = rp.normal[3 * p + 1]; npz = rp.normal[3 * p + 2]; }
     int32_t idp = 0;
     if (IDS || FOL) idp = rp.prim[p];
+    int32_t insp = 0;
+    if constexpr (INS) insp = instance_tables(follow...).inst[p];
 
     // 1. the pixel's centre ray and its world point (or, for sky, its direction: a point at infinity)
     const float fi = (float)(int)i, fj = (float)(int)j, fnx = (float)nx, fny = (float)ny;
@@ -80,7 +94,65 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
             // 1a. which sphere: the pixel's own, or the one that bounds its medium.  Both table indices are compared unsigned
             // against the tables' lengths before an address is formed; nothing loaded from a record reaches an address.
             unsigned k = 0xFFFFFFFFu;
-            if (idp >= 0) {
+            if constexpr (INS) {
+                // 1a'. which instance: the pixel's own, or the one that bounds its medium -- the one medium record this step
+                // loads serves the sphere rule as well.  An instance in range takes the pixel: the sphere steps are skipped.
+                const rt_reproject_follow_instance_params& ip = instance_tables(follow...);
+                unsigned ii = 0xFFFFFFFFu;
+                if (insp >= 0) ii = (unsigned)insp;
+                if (idp >= 0) {
+                    const unsigned kind = (unsigned)idp >> 28, index = (unsigned)idp & 0x0FFFFFFFu;
+                    if (kind == (unsigned)RT_PRIM_SPHERE) {
+                        k = index;
+                    } else if (kind == (unsigned)RT_PRIM_MEDIUM && index < (unsigned)fp.n_media) {
+                        const int32_t b = fp.media[index].boundary;
+                        if (b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_SPHERE) k = (unsigned)b & 0x0FFFFFFFu;
+                        if (insp < 0 && b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_INSTANCE) ii = (unsigned)b & 0x0FFFFFFFu;
+                    }
+                }
+                if (ii < (unsigned)ip.n_instances) {
+                    k = 0xFFFFFFFFu;
+                    // 1b'. both records' loads are issued together; only their floats and flag bits are used
+                    const rt_instance I = ip.instances[ii], J = ip.prev_instances[ii];
+                    const bool moved = I.sin_t != J.sin_t || I.cos_t != J.cos_t || I.offset[0] != J.offset[0] || I.offset[1] != J.offset[1] ||
+                                       I.offset[2] != J.offset[2] || I.flags != J.flags;
+                    if (moved) {   // 1c'. world -> object by the current record, object -> previous world by the previous one
+                        float A[3] = {P[0], P[1], P[2]};
+                        if (I.flags & RT_INST_TRANSLATE) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) A[c] = P[c] - I.offset[c];
+                        }
+                        float B[3] = {A[0], A[1], A[2]};
+                        if (I.flags & RT_INST_ROTATE_Y) {
+                            B[0] = I.cos_t * A[0] - I.sin_t * A[2];
+                            B[2] = I.sin_t * A[0] + I.cos_t * A[2];
+                        }
+                        float Cc[3] = {B[0], B[1], B[2]};
+                        if (J.flags & RT_INST_ROTATE_Y) {
+                            Cc[0] = J.cos_t * B[0] + J.sin_t * B[2];
+                            Cc[2] = J.cos_t * B[2] - J.sin_t * B[0];
+                        }
+                        if (J.flags & RT_INST_TRANSLATE) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) Cc[c] = Cc[c] + J.offset[c];
+                        }
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) q[c] = Cc[c] - rp.prev_origin[c];
+                        if (NRM) {   // the normal turns with the surface: the same two rotations, no translation
+                            float bx = npx, bz = npz;
+                            if (I.flags & RT_INST_ROTATE_Y) {
+                                bx = I.cos_t * npx - I.sin_t * npz;
+                                bz = I.sin_t * npx + I.cos_t * npz;
+                            }
+                            npx = bx; npz = bz;
+                            if (J.flags & RT_INST_ROTATE_Y) {
+                                npx = J.cos_t * bx + J.sin_t * bz;
+                                npz = J.cos_t * bz - J.sin_t * bx;
+                            }
+                        }
+                    }
+                }
+            } else if (idp >= 0) {
                 const unsigned kind = (unsigned)idp >> 28, index = (unsigned)idp & 0x0FFFFFFFu;
                 if (kind == (unsigned)RT_PRIM_SPHERE) {
                     k = index;
@@ -140,13 +212,14 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                 o[k] = inside[k] ? (size_t)qy * nx + qx : p;
             }
             float hl[4], pa[4], pd[4], hr[4], hg[4], hb[4], nqx[4] = {}, nqy[4] = {}, nqz[4] = {};
-            int32_t idq[4] = {};
+            int32_t idq[4] = {}, insq[4] = {};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 hl[k] = rp.history_len[o[k]]; pa[k] = rp.prev_alpha[o[k]]; pd[k] = rp.prev_depth[o[k]];
                 hr[k] = rp.history[3 * o[k]]; hg[k] = rp.history[3 * o[k] + 1]; hb[k] = rp.history[3 * o[k] + 2];
                 if (NRM) { nqx[k] = rp.prev_normal[3 * o[k]]; nqy[k] = rp.prev_normal[3 * o[k] + 1]; nqz[k] = rp.prev_normal[3 * o[k] + 2]; }
                 if (IDS) idq[k] = rp.prev_prim[o[k]];
+                if constexpr (INS) insq[k] = instance_tables(follow...).prev_inst[o[k]];
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -159,6 +232,7 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                     counts = counts && pa[k] < rp.alpha_min;
                 }
                 if (IDS) counts = counts && idp == idq[k];
+                if constexpr (INS) counts = counts && insp == insq[k];
                 if (counts) {
                     const float w = w4[k];
                     W = W + w;
@@ -203,6 +277,12 @@ hipError_t launch_moving(const rt_reproject_params& rp, const rt_reproject_follo
     const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
     return rt_launch_kernel(rt_reproject_kernel<NRM, true, MOT, rt_reproject_follow_params>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, fp);
 }
+// rt_reproject_instances: likewise, with the instance form of the second argument
+template <bool NRM, bool MOT>
+hipError_t launch_instances(const rt_reproject_params& rp, const rt_reproject_follow_instance_params& ip, hipStream_t st) {
+    const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
+    return rt_launch_kernel(rt_reproject_kernel<NRM, true, MOT, rt_reproject_follow_instance_params>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, ip);
+}
 template <bool NRM, bool IDS>
 hipError_t launch_motion(bool motion_on, const rt_reproject_params& rp, hipStream_t st) {
     return motion_on ? launch<NRM, IDS, true>(rp, st) : launch<NRM, IDS, false>(rp, st);
@@ -218,4 +298,9 @@ hipError_t rt_launch_reproject(bool normals_on, bool ids_on, bool motion_on, con
 hipError_t rt_launch_reproject_moving(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_params& fp, hipStream_t st) {
     if (normals_on) return motion_on ? launch_moving<true, true>(rp, fp, st) : launch_moving<true, false>(rp, fp, st);
     return motion_on ? launch_moving<false, true>(rp, fp, st) : launch_moving<false, false>(rp, fp, st);
+}
+
+hipError_t rt_launch_reproject_instances(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_instance_params& ip, hipStream_t st) {
+    if (normals_on) return motion_on ? launch_instances<true, true>(rp, ip, st) : launch_instances<true, false>(rp, ip, st);
+    return motion_on ? launch_instances<false, true>(rp, ip, st) : launch_instances<false, false>(rp, ip, st);
 }

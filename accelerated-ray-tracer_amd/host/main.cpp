@@ -9,7 +9,7 @@
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
 //             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K] [--denoise-variance [B]]] [--list]
 //             [--aov-through PREFIX] [--through-bounces N] [--through-fuzz F] [--denoise-through]
-//             [--orbit FRAMES DEGREES --out PREFIX [--temporal] [--bounce HEIGHT] [--spin DEGREES]]
+//             [--orbit FRAMES DEGREES --out PREFIX [--temporal] [--bounce HEIGHT] [--spin DEGREES [--follow-instances]]]
 //
 // --orbit FRAMES DEGREES renders a turntable: FRAMES frames of one device scene, the scene's lookfrom rotated about the vertical
 // axis through its lookat in equal steps of DEGREES / FRAMES (frame k at k steps; every other camera argument kept), each
@@ -27,6 +27,10 @@
 // with RT_INST_ROTATE_Y takes the angle  atan2((double)sin_t, (double)cos_t) + k * DEGREES * pi / 180  of its flattened record,
 // sin and cos evaluated in double and rounded to float, through rt_scene_update_instances.  A scene without a rotated instance
 // is refused, and so is --temporal: the reprojection does not follow a moved instance.
+// --follow-instances (only with --orbit ... --spin) turns the accumulation on as --temporal does and lets it follow the turning
+// instances: rt_render_aov's inst plane is kept with each frame, the instance records are read back after the update
+// (rt_scene_get_instances), and from the second frame on the history comes from rt_reproject_instances with the records and inst
+// planes of this frame and of the previous one (no sphere table, the scene's media, the binding's default times).
 //
 // --denoise [K] filters the frame with rt_denoise (K iterations, 5 when K is left out; the binding's other defaults): the frame
 // is rendered at gamma 1, the feature pass (albedo, normal, depth at min(ns, 16) samples) guides the filter, and the frame's
@@ -79,7 +83,7 @@ int main(int argc, char** argv) {
     int min_spp = 0, denoise = 0, batches = -1;   // batches: -1 = no --denoise-variance, 0 = B left out
     int orbit_frames = 0;
     double orbit_degrees = 0.0;
-    bool temporal = false, bounce = false, spin = false;
+    bool temporal = false, bounce = false, spin = false, follow_instances = false;
     double bounce_height = 0.0, spin_degrees = 0.0;
     std::string out_prefix;
     unsigned long long seed = 1984ull;
@@ -128,6 +132,7 @@ int main(int argc, char** argv) {
         }
         else if (k == "--out") out_prefix = val();
         else if (k == "--temporal") temporal = true;
+        else if (k == "--follow-instances") follow_instances = true;
         else if (k == "--bounce") {
             bounce = true;
             bounce_height = strtod(val(), nullptr);
@@ -156,6 +161,7 @@ int main(int argc, char** argv) {
     if (orbit_frames == 0 && bounce) { fprintf(stderr, "--bounce needs --orbit\n"); return 2; }
     if (orbit_frames == 0 && spin) { fprintf(stderr, "--spin needs --orbit\n"); return 2; }
     if (spin && temporal) { fprintf(stderr, "--spin cannot be combined with --temporal: the reprojection does not follow a moved instance\n"); return 2; }
+    if (follow_instances && !spin) { fprintf(stderr, "--follow-instances needs --orbit FRAMES DEGREES --spin DEGREES: it accumulates the frames and follows the instances --spin turns\n"); return 2; }
     if (orbit_frames > 0 && (gpus > 1 || progressive > 0 || adaptive || denoise || !aov_prefix.empty() || !through_prefix.empty())) {
         fprintf(stderr, "--orbit cannot be combined with --gpus > 1, --progressive, --adaptive, --denoise, --aov or --aov-through\n");
         return 2;
@@ -215,14 +221,16 @@ int main(int argc, char** argv) {
         check(rt_init(device), "rt_init");
         check(rt_scene_create(&desc, &dev_scene), "rt_scene_create");
         const rtw::camera& c0 = *scene->cam;
-        if (temporal) f.gamma = 1.0f;
-        struct features { std::vector<float> normal, depth, alpha; std::vector<int32_t> prim; };
+        const bool accumulate = temporal || follow_instances;
+        if (accumulate) f.gamma = 1.0f;
+        struct features { std::vector<float> normal, depth, alpha; std::vector<int32_t> prim, inst; };
         features feat[2];
-        for (features& x : feat) { x.normal.resize(px * 3); x.depth.resize(px); x.alpha.resize(px); x.prim.resize(px); }
+        for (features& x : feat) { x.normal.resize(px * 3); x.depth.resize(px); x.alpha.resize(px); x.prim.resize(px); if (follow_instances) x.inst.resize(px); }
         std::vector<float> acc[2] = {std::vector<float>(px * 3), std::vector<float>(px * 3)}, len[2] = {std::vector<float>(px), std::vector<float>(px)};
         rt_camera prev_cam;
         memset(&prev_cam, 0, sizeof(prev_cam));
         std::vector<rt_sphere> records[2] = {flat.spheres, flat.spheres};   // --bounce: the records of this frame and of the previous one
+        std::vector<rt_instance> inst_records[2] = {flat.instances, flat.instances};   // --follow-instances: likewise, as the scene holds them
         double ms = 0.0;
         for (int k = 0; k < orbit_frames; ++k) {
             if (bounce && !flat.spheres.empty()) {
@@ -248,6 +256,7 @@ int main(int argc, char** argv) {
                 memset(&up, 0, sizeof(up));
                 up.count = (int32_t)now.size(); up.first = 0; up.instances = now.data();
                 check(rt_scene_update_instances(dev_scene, &up, /*instances_on_device=*/0, /*recalibrate=*/0, /*stream=*/nullptr), "rt_scene_update_instances");
+                if (follow_instances) check(rt_scene_get_instances(dev_scene, inst_records[k & 1].data(), (int32_t)inst_records[k & 1].size()), "rt_scene_get_instances");
             }
             const double th = (double)k * orbit_degrees / (double)orbit_frames * 3.14159265358979323846 / 180.0;
             const double dx = (double)c0.lookfrom.x() - c0.lookat.x(), dz = (double)c0.lookfrom.z() - c0.lookat.z();
@@ -256,7 +265,7 @@ int main(int argc, char** argv) {
             check(rt_scene_set_camera(dev_scene, &cam, /*recalibrate=*/0), "rt_scene_set_camera");
             check(rt_render(dev_scene, &f, fb.data(), /*fb_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1, &stats), "rt_render");
             ms += stats.ms_render;
-            if (temporal) {
+            if (accumulate) {
                 features& cur = feat[k & 1];
                 const features& old = feat[(k + 1) & 1];
                 rt_frame_desc ff = f;
@@ -264,6 +273,7 @@ int main(int argc, char** argv) {
                 rt_aov_desc aov;
                 memset(&aov, 0, sizeof(aov));
                 aov.normal = cur.normal.data(); aov.depth = cur.depth.data(); aov.alpha = cur.alpha.data(); aov.prim = cur.prim.data();
+                if (follow_instances) aov.inst = cur.inst.data();
                 check(rt_render_aov(dev_scene, &ff, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
                 rt_reproject_desc rd;
                 memset(&rd, 0, sizeof(rd));
@@ -284,6 +294,18 @@ int main(int argc, char** argv) {
                     md.media = md.n_media ? flat.media.data() : nullptr;
                     md.time = (float)(0.5 * (cam.time0 + cam.time1)); md.prev_time = (float)(0.5 * (prev_cam.time0 + prev_cam.time1));   // the binding's default
                     check(rt_reproject_moving(&rd, &md, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_reproject_moving");
+                } else if (follow_instances && k) {   // ... the instances that turned
+                    rt_reproject_motion_desc md;
+                    memset(&md, 0, sizeof(md));
+                    md.n_media = (int32_t)flat.media.size();
+                    md.media = md.n_media ? flat.media.data() : nullptr;
+                    md.time = (float)(0.5 * (cam.time0 + cam.time1)); md.prev_time = (float)(0.5 * (prev_cam.time0 + prev_cam.time1));
+                    rt_reproject_instance_desc id;
+                    memset(&id, 0, sizeof(id));
+                    id.n_instances = (int32_t)flat.instances.size();
+                    id.instances = inst_records[k & 1].data(); id.prev_instances = inst_records[(k + 1) & 1].data();
+                    id.inst = cur.inst.data(); id.prev_inst = old.inst.data();
+                    check(rt_reproject_instances(&rd, &md, &id, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_reproject_instances");
                 } else {
                     check(rt_reproject(&rd, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_reproject");
                 }

@@ -838,8 +838,9 @@ rt_status rt_reproject_matrix(const rt_camera* prev, float m[9]);   /* host only
  * Limits.  As before the centre ray ignores the lens and the shutter; a sphere with vel != 0 is followed at one instant per
  * frame (`time`, `prev_time`; the binding's default is each camera's shutter centre, (float)(0.5 (time0 + time1))).  A quad or
  * box that is not under an instance and a sphere record under an instance do not move in this project; an instance does
- * (rt_scene_update_instances), but its motion is not followed here: a pixel on a moved instance takes the static path, and the
- * taps' depth, normal and id tests decide whether its history survives.  Reflections of a moved sphere in other surfaces are not followed.
+ * (rt_scene_update_instances), but its motion is not followed by this entry: a pixel on a moved instance takes the static path, and the
+ * taps' depth, normal and id tests decide whether its history survives -- rt_reproject_instances, below, follows it.  Reflections
+ * of a moved sphere in other surfaces are not followed.
  * Memory safety.  Two kinds of data-derived addresses are added: media[...] after the unsigned compare against n_media, and
  * spheres[k] / prev_spheres[k] after the unsigned compare against n_spheres.  Nothing loaded from a record reaches an address;
  * no value in any buffer or table makes the call fault.
@@ -859,6 +860,62 @@ typedef struct rt_reproject_motion_desc {
 } rt_reproject_motion_desc;
 rt_status rt_reproject_moving(const rt_reproject_desc* d, const rt_reproject_motion_desc* m,
                               int buffers_on_device, void* stream, int blocking);
+
+/* ---- temporal reprojection that follows moved instances ----
+ * rt_reproject_instances is rt_reproject_moving with one more rule: a surface pixel that shows an instance whose record changed
+ * between the two frames (rt_scene_update_instances) -- or a constant_medium bounded directly by such an instance -- is carried
+ * back to where that surface point was in the previous frame: into the instance's object space by the current record, out of it
+ * by the previous one.  An instance rotates, so the pixel's normal is carried the same way before the normal test; and one child
+ * can sit under several instances, so the primitive id alone does not say which object a pixel shows: the entry takes the two
+ * `inst` planes of rt_render_aov and a tap must show the pixel's instance.
+ *
+ * m is required: it supplies the media table, the two times and the sphere tables, and may have n_spheres = 0.  The numerical
+ * contract is rt_reproject_moving's (binary32, every written operation rounded once, nothing contracted -- the walk that renders
+ * an instance uses fmaf for the same maps, this entry does not) with these changes to step 1's tail (surface pixels only) and
+ * to step 3:
+ *   1a'. Which instance.  i = none.  inst[p] >= 0: i = inst[p].  Otherwise, if ref = prim[p] has ref >= 0, ref >> 28 ==
+ *        RT_PRIM_MEDIUM and (ref & 0x0FFFFFFF) < n_media (unsigned): b = media[ref & 0x0FFFFFFF].boundary, and if b >= 0 and
+ *        b >> 28 == RT_PRIM_INSTANCE then i = b & 0x0FFFFFFF.  If i < n_instances (compared unsigned, before any address is
+ *        formed) the pixel takes the instance path and steps 1a-1c are skipped: a sphere under an instance holds object-space
+ *        records, for which a world-space sphere carry would be wrong.  Otherwise steps 1a-1c of rt_reproject_moving apply
+ *        unchanged.
+ *   1b'. Moved.  I = instances[i], I' = prev_instances[i].  moved = any of sin_t, cos_t, offset[0..2] compares != or the flags
+ *        differ (a NaN compares as moved; child and pad are not looked at).  Unless moved the pixel is static: its q and its
+ *        normal are rt_reproject's, bit for bit.
+ *   1c'. The carry.  A = P;  I.flags & RT_INST_TRANSLATE: A.c = P.c - I.offset.c.
+ *        B = A;  I.flags & RT_INST_ROTATE_Y: B.x = I.cos_t A.x - I.sin_t A.z,  B.z = I.sin_t A.x + I.cos_t A.z  (world -> object).
+ *        C = B;  I'.flags & RT_INST_ROTATE_Y: C.x = I'.cos_t B.x + I'.sin_t B.z,  C.z = I'.cos_t B.z - I'.sin_t B.x  (object ->
+ *        previous world).  P' = C;  I'.flags & RT_INST_TRANSLATE: P'.c = C.c + I'.offset.c.  q.c = P'.c - O'.c.
+ *        With normals on, N = normal[p] goes through the same two rotations (B and C with N in A's place, no translation), and
+ *        step 3's normal test reads dot(N_carried, prev_normal[q]) >= normal_min.  Flag bits are only tested: flags outside
+ *        1..3 reach no address.  A non-finite record yields a non-finite q, which step 2 ends with no history.
+ *   3.   A tap must also satisfy inst[p] == prev_inst[q].  This test is always on, as the prim test is in rt_reproject_moving:
+ *        it is what tells two instances of one child apart.
+ * So with n_instances == 0, or with tables in which no record differs and inst equal to -1 everywhere, the outputs are
+ * rt_reproject_moving's bit for bit, and by that entry's own identity rt_reproject's.  tests/reproject_instances_expect.py
+ * restates this in NumPy; the device result equals it bit for bit.
+ * Limits.  The carry is exact for a rigid surface and an approximation for a scattering point in a fog volume bounded by an
+ * instance, as the sphere carry is for a fog ball.  A quad's normal is oriented to face the ray, and that orientation can flip
+ * between two frames: the normal test then rejects the tap.  Reflections of a moved instance in other surfaces are not followed.
+ * The centre ray ignores the lens and the shutter, as before.
+ * Memory safety.  The data-derived addresses that are added are instances[i] and prev_instances[i] after the unsigned compare
+ * against n_instances, and inst[...] / prev_inst[...] at the pixel and tap indices that rt_reproject's rules already bound.
+ * Nothing loaded from a record reaches an address; no value in any buffer or table makes the call fault.
+ *
+ * Parameters: everything rt_reproject_moving refuses, and a null im, a null inst, a prev_inst that is null while history is not
+ * (or the reverse), a negative n_instances or one of 2^28 or more, n_instances > 0 with a null instances or prev_instances, and
+ * an output that overlaps one of the new tables or planes are RT_ERR_INVALID before any HIP call; rt_last_error_detail() names
+ * the check and starts with "rt_reproject_instances".  The tables and planes obey buffers_on_device like every other buffer; a
+ * table whose count is 0 is not looked at.  Stream and blocking: rt_reproject's rules. */
+typedef struct rt_reproject_instance_desc {
+    int32_t n_instances, reserved;
+    const rt_instance* instances;        /* records the CURRENT frame was rendered with */
+    const rt_instance* prev_instances;   /* records the PREVIOUS frame was rendered with, same count and order */
+    const int32_t* inst;                 /* ny*nx current rt_render_aov `inst`, required */
+    const int32_t* prev_inst;            /* ny*nx previous; required iff d->history */
+} rt_reproject_instance_desc;
+rt_status rt_reproject_instances(const rt_reproject_desc* d, const rt_reproject_motion_desc* m,
+                                 const rt_reproject_instance_desc* im, int buffers_on_device, void* stream, int blocking);
 
 /* ---- several GPUs of one node from one host thread ----
  * The reference is single-GPU (one render<<<>>> launch, main.cu:707); these entry points are what its host function

@@ -20,6 +20,13 @@ update_spheres; N times rt_reproject with every guide and rt_reproject_moving wi
 buffers -- with `none` the tables hold the second frame's records twice (no sphere moved: every pixel takes the static path
 after the records were read), with `all` the records of both frames.  It exits after the loop: the run to put under
 `rocprofv3 --kernel-trace --stats`; --kernel-stats FILE --moved X then appends the two kernels' rows and their ratio.
+--instances-loop N --moved {none,all} [--scene NAME] is the instance mode (rt_reproject_instances,
+profiles/reproject_instances_mi355x.jsonl): an instanced scene (default cornell) at 1200 x 800 under its own camera and one 3
+degrees further round, the second frame rendered after every rotated instance was turned by 6 degrees through update_instances; N
+times rt_reproject_moving (no sphere table, the scene's media) and rt_reproject_instances with every guide, alternating, on those
+same buffers -- with `none` the tables hold the second frame's records twice (every instance pixel takes the static path after the
+records were read), with `all` the records of both frames.  It exits after the loop; --kernel-stats FILE --moved X --instances
+then appends the two kernels' rows and their ratio.
 --orbit-pair N is the stale prior in an animation loop: ONE scene, its camera switched between the 0 and the 20 degree view
 (recalibrate 0) before every frame, 2 N + 2 frames, the first two left out.  Since the cost map a scene that
 renders one view again runs warm, one-part frames, so (b)'s three scenes no longer show what a stale prior costs; here every
@@ -104,6 +111,63 @@ def moving_loop(args, hs, dev):
     ds.close()
 
 
+CORNELL_EYE, CORNELL_LOOKAT = (278.0, 278.0, -800.0), (278.0, 278.0, 0.0)      # host/rtw_scenes.cpp, cornell_camera
+
+
+def instances_loop(args, dev):
+    """The instance mode: see the module's text."""
+    nx, ny = args.nx, args.ny
+    hs = art.HostScene(args.scene, nx, ny)
+    ds = art.DeviceScene(hs)
+    f4 = hs.frame(nx=nx, ny=ny, ns=4, gamma=1.0)
+    built = art.RtCamera.from_buffer_copy(hs.desc.camera)
+    if args.scene.startswith("cornell"):
+        th = np.radians(3.0)
+        d = np.subtract(CORNELL_EYE, CORNELL_LOOKAT)
+        eye = np.add(CORNELL_LOOKAT, (np.cos(th) * d[0] + np.sin(th) * d[2], d[1], -np.sin(th) * d[0] + np.cos(th) * d[2]))
+        cams = [built, art.make_camera(eye, CORNELL_LOOKAT, (0, 1, 0), 40.0, nx / ny, 0.0, 800.0, 0.0, 1.0)]
+    else:
+        cams = [built, built]
+    before = ds.instances()
+    rotated = (before["flags"] & art.RT_INST_ROTATE_Y) != 0
+    after = before.copy()
+    a = np.arctan2(before["sin_t"].astype(np.float64), before["cos_t"].astype(np.float64)) + np.radians(6.0)
+    after["sin_t"][rotated], after["cos_t"][rotated] = np.sin(a)[rotated], np.cos(a)[rotated]
+    host = []
+    for k, cam in enumerate(cams):
+        if k:
+            ds.update_instances(after)
+        ds.set_camera(cam)
+        color, _ = ds.render(f4)
+        host.append(dict(ds.render_aov(f4, ids=True), color=color))
+    t = [{k: torch.from_numpy(v).to(dev) for k, v in h.items()} for h in host]
+    words = lambda rec: torch.from_numpy(np.ascontiguousarray(rec).view(np.int32).reshape(len(rec), -1).copy()).to(dev)   # noqa: E731
+    cur_records, prev_records = words(after), words(before if args.moved == "all" else after)
+    media = words(hs.media()) if len(hs.media()) else None
+    no_spheres = torch.empty((0, 8), dtype=torch.int32, device=dev)
+    first = art.reproject(t[0]["color"], t[0]["depth"], t[0]["alpha"], cams[0], cams[0])
+    out, out_len = torch.empty_like(first.out), torch.empty_like(first.length)
+    motion = torch.empty((ny, nx, 2), dtype=torch.float32, device=dev)
+    kw = dict(history=first.out, history_len=first.length, prev_depth=t[0]["depth"], prev_alpha=t[0]["alpha"], out=out, out_len=out_len,
+              stream=torch.cuda.current_stream(dev).cuda_stream, blocking=False, normal=t[1]["normal"], prim=t[1]["prim"],
+              prev_normal=t[0]["normal"], prev_prim=t[0]["prim"], motion=motion, media=media)
+    on_rotated = np.isin(host[1]["inst"], np.flatnonzero(rotated)) & (host[1]["alpha"] >= 0.5)
+    sel = torch.from_numpy(on_rotated).to(dev)
+    for _ in range(args.instances_loop):
+        art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], spheres=no_spheres, prev_spheres=no_spheres, **kw)
+        moving_found, moving_on = float((out_len > 1).float().mean().item()), float((out_len[sel] > 1).float().mean().item())
+        art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], instances=cur_records, prev_instances=prev_records,
+                      inst=t[1]["inst"], prev_inst=t[0]["inst"], **kw)
+        inst_found, inst_on = float((out_len > 1).float().mean().item()), float((out_len[sel] > 1).float().mean().item())
+    torch.cuda.synchronize()
+    print(json.dumps({"what": "rt_reproject_instances loop", "scene": args.scene, "instances_moved": args.moved, "calls_each": args.instances_loop,
+                      "instances": int(len(before)), "rotated_instances": int(rotated.sum()), "pixels_on_rotated_instances": round(float(on_rotated.mean()), 4),
+                      "pixels_with_history_moving": round(moving_found, 4), "pixels_with_history_instances": round(inst_found, 4),
+                      "of_rotated_instance_pixels_moving": round(moving_on, 4), "of_rotated_instance_pixels_instances": round(inst_on, 4)}))
+    ds.close()
+    hs.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nx", type=int, default=1200)
@@ -116,6 +180,9 @@ def main():
     ap.add_argument("--moving-loop", type=int, default=0)
     ap.add_argument("--moved", choices=["none", "all"], default=None)
     ap.add_argument("--orbit-pair", type=int, default=0)
+    ap.add_argument("--instances-loop", type=int, default=0)
+    ap.add_argument("--instances", action="store_true", help="with --kernel-stats: the instance mode's two kernels")
+    ap.add_argument("--scene", default="cornell")
     args = ap.parse_args()
     nx, ny = args.nx, args.ny
     if args.kernel_stats:
@@ -129,7 +196,13 @@ def main():
                         "calls": int(r["Calls"]), "average_us": round(float(r["AverageNs"]) / 1e3, 3), "min_us": round(float(r["MinNs"]) / 1e3, 3),
                         "max_us": round(float(r["MaxNs"]) / 1e3, 3)}
         line = {"what": "device time per kernel (rocprofv3 --kernel-trace --stats)", "nx": nx, "ny": ny, "kernels": rows}
-        if args.moved:
+        if args.moved and args.instances:
+            moving = rows.get("rt_reproject_kernel<true, true, true, rt_reproject_follow_params>")
+            following = rows.get("rt_reproject_kernel<true, true, true, rt_reproject_follow_instance_params>")
+            line["instances_moved"], line["scene"] = args.moved, args.scene
+            if moving and following:
+                line["instances_over_moving"] = round(following["average_us"] / moving["average_us"], 4)
+        elif args.moved:
             static = rows.get("rt_reproject_kernel<true, true, true>")
             moving = rows.get("rt_reproject_kernel<true, true, true, rt_reproject_follow_params>")
             line["spheres_moved"] = args.moved
@@ -142,6 +215,9 @@ def main():
         return
     art.init(0)
     dev = torch.device("cuda", 0)
+    if args.instances_loop:
+        instances_loop(args, dev)
+        return
     hs = art.HostScene("random_scene", nx, ny)
     lines = []
 
