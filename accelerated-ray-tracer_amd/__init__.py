@@ -132,6 +132,10 @@ class RtInstanceUpdate(C.Structure):
     _fields_ = [("count", C.c_int32), ("first", C.c_int32), ("indices", C.c_void_p), ("instances", C.c_void_p)]
 
 
+class RtQuadUpdate(C.Structure):
+    _fields_ = [("count", C.c_int32), ("first", C.c_int32), ("indices", C.c_void_p), ("quads", C.c_void_p)]
+
+
 RT_INST_ROTATE_Y, RT_INST_TRANSLATE = 1, 2
 RT_TRACE_CLOSEST, RT_TRACE_ANY = 0, 1
 RT_PRIM_SPHERE, RT_PRIM_QUAD, RT_PRIM_BOX, RT_PRIM_INSTANCE, RT_PRIM_MEDIUM = range(5)
@@ -188,7 +192,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_scene_update_spheres", "rt_scene_get_spheres", "rt_multi_update_spheres", "rt_refit_nodes", "rt_debug_scene_boxes",
                   "rt_reproject_moving", "rt_debug_cost_map", "rt_debug_set_cost_map",
                   "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances",
-                  "rt_debug_box_tests", "rt_reproject_instances"]
+                  "rt_debug_box_tests", "rt_reproject_instances",
+                  "rt_scene_update_quads", "rt_scene_get_quads", "rt_refit_quads", "rt_multi_update_quads", "rt_debug_scene_quads"]
 
 _rt = None
 _host = None
@@ -222,6 +227,8 @@ def host_lib():
         L.rtw_scene_defaults.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]
         L.rtw_scene_leaf_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.rtw_rotation.argtypes = [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.rtw_quad_record.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_void_p]
+        L.rtw_box_records.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_void_p]
         L.rtw_write_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.rtw_load_ppm.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rtw_camera_init.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float,
@@ -287,6 +294,12 @@ def rt_lib():
         L.rt_scene_get_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.rt_multi_update_instances.argtypes = [C.c_void_p, C.POINTER(RtInstanceUpdate), C.c_int]
         L.rt_refit_instances.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(RtInstanceUpdate), C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_scene_update_quads"):   # (absent from an older library measured through RT_LIB_OVERRIDE)
+            L.rt_scene_update_quads.argtypes = [C.c_void_p, C.POINTER(RtQuadUpdate), C.c_int, C.c_int, C.c_void_p]
+            L.rt_scene_get_quads.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+            L.rt_multi_update_quads.argtypes = [C.c_void_p, C.POINTER(RtQuadUpdate), C.c_int]
+            L.rt_refit_quads.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(RtQuadUpdate), C.c_void_p, C.c_void_p]
+            L.rt_debug_scene_quads.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.rt_debug_scene_boxes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_reproject.argtypes = [C.POINTER(RtReprojectDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_reproject_matrix.argtypes = [C.POINTER(RtCamera), C.POINTER(C.c_float)]
@@ -775,13 +788,14 @@ def _chain_args(max_bounces, fuzz_limit):
     return int(max_bounces), fuzz_limit
 
 
-# the two kinds of record update: the argument's name, its dtype and its structure (whose record pointer carries the name)
+# the three kinds of record update: the argument's name, its dtype and its structure (whose record pointer carries the name)
 _SPHERES = ("spheres", "sphere", SPHERE_DTYPE, "SPHERE_DTYPE", RtSphereUpdate)
 _INSTANCES = ("instances", "instance", INSTANCE_DTYPE, "INSTANCE_DTYPE", RtInstanceUpdate)
+_QUADS = ("quads", "quad", QUAD_DTYPE, "QUAD_DTYPE", RtQuadUpdate)
 
 
 def _record_update(kind, records, indices, first):
-    """An RtSphereUpdate / RtInstanceUpdate over host records and what keeps its arrays alive.  ValueError for malformed arguments."""
+    """An RtSphereUpdate / RtInstanceUpdate / RtQuadUpdate over host records and what keeps its arrays alive.  ValueError for malformed arguments."""
     name, one, dtype, dtype_name, struct = kind
     if not isinstance(records, np.ndarray) or records.dtype != dtype or records.ndim != 1:
         raise ValueError(f"{name}: a one-dimensional numpy array of {dtype_name} is expected")
@@ -834,6 +848,45 @@ def refit_instances(desc: RtSceneDesc, instances, indices=None, first: int = 0):
         raise ValueError(L.rt_last_error_detail().decode())
     _check(st, "rt_refit_instances")
     return nodes, out
+
+
+def refit_quads(desc: RtSceneDesc, quads, indices=None, first: int = 0):
+    """rt_refit_quads, host only: the description that DeviceScene.update_quads(quads, indices, first) is equivalent to.
+    Returns (nodes, quads) of it as NODE_DTYPE / QUAD_DTYPE arrays.  ValueError when the update is refused."""
+    u, keep = _record_update(_QUADS, quads, indices, first)
+    nodes, out = np.zeros(desc.n_nodes, NODE_DTYPE), np.zeros(desc.n_quads, QUAD_DTYPE)
+    L = rt_lib()
+    st = L.rt_refit_quads(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data)
+    if st == 1:
+        raise ValueError(L.rt_last_error_detail().decode())
+    _check(st, "rt_refit_quads")
+    return nodes, out
+
+
+def _float3(x, name):
+    a = np.asarray(x, np.float32)
+    if a.shape != (3,):
+        raise ValueError(f"{name}: three numbers are expected")
+    return (C.c_float * 3)(*[float(c) for c in a])
+
+
+def quad_record(Q, u, v, mat: int) -> np.ndarray:
+    """One QUAD_DTYPE record (shape (1,)) of quad(Q, u, v) with material index `mat`: D, w and the unit normal come from the
+    host library's own quad constructor (the reference's float arithmetic), so the record is what a flattened scene with that
+    quad holds.  What DeviceScene.update_quads takes for a quad that moves or changes shape."""
+    rec = np.zeros(1, QUAD_DTYPE)
+    if host_lib().rtw_quad_record(_float3(Q, "Q"), _float3(u, "u"), _float3(v, "v"), int(mat), rec.ctypes.data) != 0:
+        raise RtError("rtw_quad_record failed")
+    return rec
+
+
+def box_records(a, b, mat: int) -> np.ndarray:
+    """The six QUAD_DTYPE records, in face order, of make_box(a, b) with material index `mat`, through the host library's own
+    make_box: what replaces quads first_quad .. first_quad + 5 of a box that changes size (DeviceScene.update_quads)."""
+    rec = np.zeros(6, QUAD_DTYPE)
+    if host_lib().rtw_box_records(_float3(a, "a"), _float3(b, "b"), int(mat), rec.ctypes.data) != 0:
+        raise RtError("rtw_box_records failed")
+    return rec
 
 
 def instance_record(child: int, angle_degrees=None, offset=None) -> np.ndarray:
@@ -913,8 +966,23 @@ class DeviceScene:
         applied."""
         self._update_records(_INSTANCES, "rt_scene_update_instances", instances, indices, first, recalibrate, stream)
 
+    def update_quads(self, quads, indices=None, first: int = 0, recalibrate: bool = False, stream=None) -> None:
+        """New records for quads of the scene as it stands on the device (rt_scene_update_quads): record k replaces quad
+        indices[k], or quad first + k without indices -- free quads and the faces of boxes (quads first_quad .. first_quad + 5),
+        under an instance or not.  Q, D, u, v, w, n and mat may change; D, w and n are the caller's, as in a description (see
+        quad_record and box_records).  The boxes that depend on the quads are refit on the device, the axis-aligned marks the
+        scene keeps follow, and every later frame and query is what a scene created from the changed description gives.
+        recalibrate: as update_spheres.
+
+        quads: a numpy array of QUAD_DTYPE -- copied to the device -- or a contiguous torch tensor of shape (count, 20) with a
+        4-byte dtype on the scene's device, read in place: the twenty words of rt_quad per row.  stream, indices and the argument
+        errors are update_spheres'.  An index out of range or given twice, a non-finite record and a material out of range raise
+        ValueError before anything is launched; a bad record in a device tensor raises it after the others were applied."""
+        self._update_records(_QUADS, "rt_scene_update_quads", quads, indices, first, recalibrate, stream)
+
     def _update_records(self, kind, entry, records, indices, first, recalibrate, stream):
-        name, one, _, dtype_name, struct = kind
+        name, one, dtype, dtype_name, struct = kind
+        words = dtype.itemsize // 4                                  # 4-byte words per record: 8, or 20 for a quad
         L = rt_lib()
         if isinstance(records, np.ndarray):
             if stream is not None:
@@ -928,8 +996,8 @@ class DeviceScene:
                 raise ValueError(f"{name}: a numpy array of {dtype_name} or a torch tensor is expected")
             if records.device != dev:
                 raise ValueError(f"{name}: tensor on {records.device}, the scene is on {dev}")
-            if records.ndim != 2 or records.shape[1] != 8 or records.element_size() != 4:
-                raise ValueError(f"{name}: shape {tuple(records.shape)} of {records.dtype}, expected (count, 8) of a 4-byte dtype")
+            if records.ndim != 2 or records.shape[1] != words or records.element_size() != 4:
+                raise ValueError(f"{name}: shape {tuple(records.shape)} of {records.dtype}, expected (count, {words}) of a 4-byte dtype")
             if not records.is_contiguous():
                 raise ValueError(f"{name}: a contiguous tensor is expected (it is read in place)")
             u = struct()
@@ -962,6 +1030,20 @@ class DeviceScene:
         out = np.zeros(self.host.desc.n_instances, INSTANCE_DTYPE)
         _check(rt_lib().rt_scene_get_instances(self._p, out.ctypes.data, len(out)), "rt_scene_get_instances")
         return out
+
+    def quads(self) -> np.ndarray:
+        """The quad records the next frame uses (rt_scene_get_quads): the description's, with every update applied; pad0 is 0."""
+        out = np.zeros(self.host.desc.n_quads, QUAD_DTYPE)
+        _check(rt_lib().rt_scene_get_quads(self._p, out.ctypes.data, len(out)), "rt_scene_get_quads")
+        return out
+
+    def debug_quads(self):
+        """rt_debug_scene_quads (tests): the device's quad records and box words raw -- pad0 holds the axis code as integer bits,
+        bit 30 of a box word the canonical mark.  Returns (QUAD_DTYPE array, int32 array)."""
+        quads, boxes = np.zeros(self.host.desc.n_quads, QUAD_DTYPE), np.zeros(self.host.desc.n_boxes, np.int32)
+        _check(rt_lib().rt_debug_scene_quads(self._p, quads.ctypes.data if len(quads) else None, len(quads),
+                                             boxes.ctypes.data if len(boxes) else None, len(boxes)), "rt_debug_scene_quads")
+        return quads, boxes
 
     COST_MAP_STATES = ("none", "exact", "stale")
 
@@ -1600,6 +1682,16 @@ class MultiScene:
         if st == 1:
             raise ValueError(L.rt_last_error_detail().decode())
         _check(st, "rt_multi_update_instances")
+
+    def update_quads(self, quads, indices=None, first: int = 0, recalibrate: bool = False) -> None:
+        """DeviceScene.update_quads with host records on every replica (rt_multi_update_quads)."""
+        L = rt_lib()
+        u, keep = _record_update(_QUADS, quads, indices, first)
+        st = L.rt_multi_update_quads(self._p, C.byref(u), 1 if recalibrate else 0)
+        del keep
+        if st == 1:
+            raise ValueError(L.rt_last_error_detail().decode())
+        _check(st, "rt_multi_update_quads")
 
     def render(self, frame: RtFrameDesc, tile_rows: int = 4):
         """The whole frame as float32[ny][nx][3] in host memory, and the summed statistics."""

@@ -254,6 +254,7 @@ struct rt_scene {
     // rt_scene_update_spheres, rt_scene_update_instances: the lookup tables of the refit kernels, built on the scene's first update from a
     // read-back of the node arrays, so that a scene that never moves pays nothing; refit.block holds all of them
     int32_t n_instances = 0, n_media = 0;        // of the description (rt_scene_dev carries neither)
+    int32_t n_quads = 0, n_boxes = 0;            // (the same; rt_scene_update_quads)
     struct refit_tables {
         bool ready = false;
         void* block = nullptr;                   // one allocation, cut into the arrays of `p`
@@ -261,8 +262,9 @@ struct rt_scene {
         std::vector<char> instanced;             // per sphere: the child of an instance (kept from rt_scene_create, host only)
         std::vector<int32_t> inst_child;         // per instance: its child, which no update changes (the same)
         uint32_t epoch = 0, inst_epoch = 0;      // of the spheres' and of the instances' stamps
+        uint32_t quad_epoch = 0;                 // ... and of the quads'
         int32_t* d_indices = nullptr;            // the update's index list and (host records) its records on the device
-        rt_sphere* d_records = nullptr;          // (32-byte records of either kind)
+        rt_sphere* d_records = nullptr;          // (in 32-byte units: a sphere or an instance is one, a quad two and a half)
         size_t indices_capacity = 0, records_capacity = 0;
     } refit;
 };
@@ -1085,26 +1087,15 @@ rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_sce
     UP(spheres, d->n_spheres);
     {   // quads and boxes: mark the axis-aligned ones (quad_test_axis, rt_device_funcs.h).  A quad qualifies when its unit
         // normal is exactly +-e_C and u, v, w each have exactly one non-zero component on the fitting axes; a box when its
-        // six faces do, with normals along z, x, z, x, y, y (make_box's order, quad.cuh:145-162).
+        // six faces do, with normals along z, x, z, x, y, y (make_box's order, quad.cuh:145-162).  Both rules live in
+        // rt_refit_host.h, where rt_scene_update_quads takes them from too.
         std::vector<rt_quad> quads(d->quads, d->quads + d->n_quads);
-        auto axis_of = [](const rt_quad& q) -> int {
-            for (int c = 0; c < 3; ++c) {
-                const int a = (c + 1) % 3, b = (c + 2) % 3;
-                if (!((q.n[c] == 1.0f || q.n[c] == -1.0f) && q.n[a] == 0.0f && q.n[b] == 0.0f)) continue;
-                if (!(q.w[a] == 0.0f && q.w[b] == 0.0f && q.w[c] != 0.0f && q.u[c] == 0.0f && q.v[c] == 0.0f)) continue;
-                const bool u_on_a = q.u[a] != 0.0f && q.u[b] == 0.0f, u_on_b = q.u[b] != 0.0f && q.u[a] == 0.0f;
-                const bool v_on_a = q.v[a] != 0.0f && q.v[b] == 0.0f, v_on_b = q.v[b] != 0.0f && q.v[a] == 0.0f;
-                if ((u_on_a && v_on_b) || (u_on_b && v_on_a)) return c;
-            }
-            return -1;
-        };
-        for (rt_quad& q : quads) { const int c = axis_of(q); const int32_t code = c >= 0 ? 1 + c : 0; memcpy(&q.pad0, &code, 4); }
+        for (rt_quad& q : quads) { const int32_t code = rt_refit::axis_code(q); memcpy(&q.pad0, &code, 4); }
         std::vector<rt_box> boxes(d->boxes, d->boxes + d->n_boxes);
-        static const int face_axis[6] = {2, 0, 2, 0, 1, 1};
         for (rt_box& b : boxes) {
-            bool canonical = true;
-            for (int f = 0; f < 6 && canonical; ++f) canonical = axis_of(quads[(size_t)b.first_quad + f]) == face_axis[f];
-            if (canonical) b.first_quad |= 0x40000000;
+            int32_t codes[6];
+            for (int f = 0; f < 6; ++f) codes[f] = rt_refit::axis_code(quads[(size_t)b.first_quad + f]);
+            if (rt_refit::canonical_codes(codes)) b.first_quad |= RT_BOX_CANONICAL;
         }
         st = upload(quads.data(), quads.size(), &s->dev.quads);
         if (st != RT_OK) { rt_scene_destroy(s); return st; }
@@ -1145,6 +1136,7 @@ rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_sce
     s->dev.nodes = s->dev.nodes_ref; s->dev.n_nodes = d->n_nodes;     // until the walk array is built below
     s->dev.n_spheres = d->n_spheres;
     s->n_instances = d->n_instances; s->n_media = d->n_media;
+    s->n_quads = d->n_quads; s->n_boxes = d->n_boxes;
     s->refit.instanced = rt_refit::instanced_spheres(d->instances, d->n_instances, d->n_spheres);   // (host only: an update's checks need no HIP call)
     for (int i = 0; i < d->n_instances; ++i) s->refit.inst_child.push_back(d->instances[i].child);
     s->dev.n_materials = d->n_materials; s->dev.n_textures = d->n_textures;
@@ -1436,7 +1428,7 @@ rt_status build_refit_tables(rt_scene* s) {
     if (s->n_media) HIPCHK(hipMemcpy(media.data(), s->dev.media, media.size() * sizeof(rt_medium), hipMemcpyDeviceToHost));
 
     // leaves by ordinal, and one job per interior node: (node, first leaf, end leaf, array)
-    std::vector<int32_t> leaf_sphere, leaf_instance, leaf_node_ref, leaf_node_walk;
+    std::vector<int32_t> leaf_sphere, leaf_instance, leaf_solid, leaf_node_ref, leaf_node_walk;
     std::vector<float> box_lo, box_hi;
     std::vector<int4> jobs;
     auto scan = [&](const std::vector<rt_node>& nodes, int which, std::vector<int32_t>& leaf_node) -> bool {
@@ -1458,26 +1450,30 @@ rt_status build_refit_tables(rt_scene* s) {
     const int slots = (m + 63) / 64;
     leaf_sphere.assign((size_t)m, -1);
     leaf_instance.assign((size_t)m, -1);
+    leaf_solid.assign((size_t)m, -1);
     box_lo.assign((size_t)slots * 64 * 4, 0.0f); box_hi.assign((size_t)slots * 64 * 4, 0.0f);
     for (int q = 0; q < m; ++q) {
         const rt_node& n = ref[(size_t)leaf_node_ref[(size_t)q]];
         if (own_walk && walk[(size_t)leaf_node_walk[(size_t)q]].prim != n.prim) return invalid("rt_scene_update_spheres: the walk array's leaves are not in the reference tree's order");
         leaf_sphere[(size_t)q] = rt_refit::leaf_sphere(n.prim, media.data(), s->n_media, n_spheres);
         leaf_instance[(size_t)q] = rt_refit::leaf_instance(n.prim, media.data(), s->n_media, s->n_instances);
+        leaf_solid[(size_t)q] = rt_refit::leaf_solid(n.prim, media.data(), s->n_media, n_spheres, s->n_quads, s->n_boxes, s->n_instances);
         for (int c = 0; c < 3; ++c) { box_lo[(size_t)q * 4 + c] = n.bmin[c]; box_hi[(size_t)q * 4 + c] = n.bmax[c]; }
     }
     if (!own_walk) leaf_node_walk.clear();
 
-    // one block, every piece 256-byte aligned: both stamp arrays, the four leaf tables, the canonical boxes, slot unions and maxima, jobs, result
+    // one block, every piece 256-byte aligned: the three stamp arrays, the five leaf tables, the canonical boxes, slot unions and maxima, jobs, result
     const bool tier = s->dev.slot_ranges != nullptr;
     struct piece { size_t bytes; const void* src; void** dst; };
-    uint32_t *stamp = nullptr, *inst_stamp = nullptr; int32_t *d_ls = nullptr, *d_li = nullptr, *d_lr = nullptr, *d_lw = nullptr; float4 *d_lo = nullptr, *d_hi = nullptr;
+    uint32_t *stamp = nullptr, *inst_stamp = nullptr, *quad_stamp = nullptr; int32_t *d_ls = nullptr, *d_li = nullptr, *d_lq = nullptr, *d_lr = nullptr, *d_lw = nullptr; float4 *d_lo = nullptr, *d_hi = nullptr;
     float *d_slot = nullptr, *d_abs = nullptr, *d_result = nullptr; int4* d_jobs = nullptr;
     const piece pieces[] = {
         {(size_t)n_spheres * 4, nullptr, (void**)&stamp},
         {(size_t)s->n_instances * 4, nullptr, (void**)&inst_stamp},
+        {(size_t)s->n_quads * 4, nullptr, (void**)&quad_stamp},
         {leaf_sphere.size() * 4, leaf_sphere.data(), (void**)&d_ls},
         {leaf_instance.size() * 4, leaf_instance.data(), (void**)&d_li},
+        {leaf_solid.size() * 4, leaf_solid.data(), (void**)&d_lq},
         {leaf_node_ref.size() * 4, leaf_node_ref.data(), (void**)&d_lr},
         {leaf_node_walk.size() * 4, leaf_node_walk.data(), (void**)&d_lw},
         {box_lo.size() * 4, box_lo.data(), (void**)&d_lo},
@@ -1515,15 +1511,18 @@ rt_status build_refit_tables(rt_scene* s) {
     p.result = d_result;
     p.inst_stamp = inst_stamp; p.instances = const_cast<rt_instance*>(s->dev.instances); p.leaf_instance = d_li;
     p.quads = s->dev.quads; p.boxes = s->dev.boxes;
+    p.quad_stamp = quad_stamp; p.leaf_solid = d_lq; p.n_boxes = s->n_boxes;
+    p.quads_rw = const_cast<rt_quad*>(s->dev.quads); p.boxes_rw = const_cast<rt_box*>(s->dev.boxes);
     t.ready = true;
     return RT_OK;
 }
 
 // The launches of an update whose records and indices are in place, the read-back of the bound and the flag, and the cost half
 // of the calibration when asked for (as rt_scene_set_camera)
-rt_status run_refit(rt_scene* s, const rt_refit_params& p, bool instances, hipStream_t stream, int recalibrate, bool& refused) {
+enum refit_kind { REFIT_SPHERES, REFIT_INSTANCES, REFIT_QUADS };
+rt_status run_refit(rt_scene* s, const rt_refit_params& p, refit_kind kind, hipStream_t stream, int recalibrate, bool& refused) {
     HIPCHK(hipMemsetAsync(p.result, 0, 16, stream));
-    HIPCHK(instances ? rt_launch_refit_instances(p, stream) : rt_launch_refit(p, stream));
+    HIPCHK(kind == REFIT_QUADS ? rt_launch_refit_quads(p, stream) : kind == REFIT_INSTANCES ? rt_launch_refit_instances(p, stream) : rt_launch_refit(p, stream));
     float result[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     HIPCHK(hipMemcpyAsync(result, p.result, sizeof(result), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -1576,7 +1575,7 @@ rt_status rt_scene_update_spheres(rt_scene* s, const rt_sphere_update* u, int sp
         p.records = t.d_records;
     }
     bool refused = false;
-    RT_TRY(run_refit(s, p, /*instances=*/false, stream, recalibrate, refused));
+    RT_TRY(run_refit(s, p, REFIT_SPHERES, stream, recalibrate, refused));
     if (refused) return invalid((who + "a device-resident record has a non-finite field or a material out of range; it was not stored, every other record was").c_str());
     return RT_OK;
 }
@@ -1616,7 +1615,7 @@ rt_status rt_refit_nodes(const rt_scene_desc* d, const rt_sphere_update* u, rt_n
 // the leaf kernel are the instances' own.  The scene holds one copy of the instance records, s->dev.instances, which every
 // kernel reads through its scene view; nothing is staged from them at creation or at launch time.
 rt_status rt_scene_update_instances(rt_scene* s, const rt_instance_update* u, int instances_on_device, int recalibrate, void* stream_v) {
-    static_assert(sizeof(rt_instance) == sizeof(rt_sphere), "the staging buffer of an update holds 32-byte records of either kind");
+    static_assert(sizeof(rt_instance) == sizeof(rt_sphere), "the staging buffer of an update is counted in 32-byte units: one per sphere or instance");
     const std::string who = "rt_scene_update_instances: ";
     if (!s) return invalid((who + "null scene").c_str());
     rt_scene::refit_tables& t = s->refit;
@@ -1649,7 +1648,7 @@ rt_status rt_scene_update_instances(rt_scene* s, const rt_instance_update* u, in
         p.inst_records = reinterpret_cast<const rt_instance*>(t.d_records);
     }
     bool refused = false;
-    RT_TRY(run_refit(s, p, /*instances=*/true, stream, recalibrate, refused));
+    RT_TRY(run_refit(s, p, REFIT_INSTANCES, stream, recalibrate, refused));
     if (refused) return invalid((who + "a device-resident record has a non-finite field, flags outside 1..3 or a child other than the scene's; it was not stored, every other record was").c_str());
     return RT_OK;
 }
@@ -1684,6 +1683,91 @@ rt_status rt_refit_instances(const rt_scene_desc* d, const rt_instance_update* u
         if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
     }
     if (instances_out && d->n_instances) memcpy(instances_out, instances.data(), instances.size() * sizeof(rt_instance));
+    return RT_OK;
+}
+
+// ---- rt_scene_update_quads (include/rt_abi.h): the same tables and the same unions; a records kernel, a
+// box-marks kernel and a leaf kernel of its own.  The scene holds one copy of the quad and box records, s->dev.quads and
+// s->dev.boxes, which every kernel reads through its scene view: the tier arrays hold references to them (lo.w / hi.w), the
+// staged kernels copy at launch time.  What rt_scene_create derives from quad records lives inside those two arrays (pad0, bit 30
+// of first_quad) and follows the update there.
+rt_status rt_scene_update_quads(rt_scene* s, const rt_quad_update* u, int quads_on_device, int recalibrate, void* stream_v) {
+    static_assert(sizeof(rt_quad) == 80 && sizeof(rt_quad) % 16 == 0, "the staging buffer holds a quad in two and a half 32-byte units");
+    const std::string who = "rt_scene_update_quads: ";
+    if (!s) return invalid((who + "null scene").c_str());
+    rt_scene::refit_tables& t = s->refit;
+    const std::string why = rt_refit::check_quad_update(u, !quads_on_device, s->n_quads, s->dev.n_materials);
+    if (!why.empty()) return invalid((who + why).c_str());
+    if (u->count == 0) return RT_OK;
+    RT_TRY(use_device(s->device));
+    RT_TRY(build_refit_tables(s));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (quads_on_device) {
+        const traced_ptr records[] = {{u->quads, (size_t)u->count * sizeof(rt_quad), "quads", 4}};
+        RT_TRY(check_trace_ptrs(records, s->device, "rt_scene_update_quads"));
+    }
+    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
+    ++s->scene_epoch;                                // the cost map: as rt_scene_update_spheres
+    if (recalibrate) s->cost_map.valid = false;
+    rt_refit_params p = t.p;
+    p.count = u->count; p.first = u->first;
+    if (++t.quad_epoch == 0) { HIPCHK(hipMemsetAsync(p.quad_stamp, 0, (size_t)s->n_quads * 4, stream)); t.quad_epoch = 1; }
+    p.quad_epoch = t.quad_epoch;
+    if (u->indices) {
+        RT_TRY(grow(t.d_indices, t.indices_capacity, (size_t)u->count));
+        HIPCHK(hipMemcpyAsync(t.d_indices, u->indices, (size_t)u->count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        p.indices = t.d_indices;
+    }
+    if (quads_on_device) p.quad_records = u->quads;
+    else {
+        const size_t bytes = (size_t)u->count * sizeof(rt_quad);
+        RT_TRY(grow(t.d_records, t.records_capacity, (bytes + sizeof(rt_sphere) - 1) / sizeof(rt_sphere)));
+        HIPCHK(hipMemcpyAsync(t.d_records, u->quads, bytes, hipMemcpyHostToDevice, stream));
+        p.quad_records = reinterpret_cast<const rt_quad*>(t.d_records);
+    }
+    bool refused = false;
+    RT_TRY(run_refit(s, p, REFIT_QUADS, stream, recalibrate, refused));
+    if (refused) return invalid((who + "a device-resident record has a non-finite field or a material out of range; it was not stored, every other record was").c_str());
+    return RT_OK;
+}
+
+rt_status rt_debug_scene_quads(const rt_scene* s, rt_quad* quads_out, int32_t quad_cap, rt_box* boxes_out, int32_t box_cap) {
+    if (!s) return invalid("rt_debug_scene_quads: null scene");
+    if ((quads_out && quad_cap < s->n_quads) || (boxes_out && box_cap < s->n_boxes)) return invalid("rt_debug_scene_quads: a cap is below the scene's count");
+    RT_TRY(use_device(s->device));
+    if (quads_out && s->n_quads) HIPCHK(hipMemcpy(quads_out, s->dev.quads, (size_t)s->n_quads * sizeof(rt_quad), hipMemcpyDeviceToHost));
+    if (boxes_out && s->n_boxes) HIPCHK(hipMemcpy(boxes_out, s->dev.boxes, (size_t)s->n_boxes * sizeof(rt_box), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status rt_scene_get_quads(const rt_scene* s, rt_quad* out, int32_t cap) {
+    if (!s) return invalid("rt_scene_get_quads: null scene");
+    if (!out) return invalid("rt_scene_get_quads: null output pointer");
+    if (cap < s->n_quads) return invalid("rt_scene_get_quads: cap is below the scene's quad count");
+    RT_TRY(rt_debug_scene_quads(s, out, cap, nullptr, 0));
+    for (int32_t i = 0; i < s->n_quads; ++i) out[i].pad0 = 0.0f;        // (the device keeps the axis code there)
+    return RT_OK;
+}
+
+rt_status rt_refit_quads(const rt_scene_desc* d, const rt_quad_update* u, rt_node* nodes_out, rt_quad* quads_out) {
+    bool so = false, uv = false;
+    int tx = 0;
+    RT_TRY(validate(d, so, tx, uv));
+    const std::string why = rt_refit::check_quad_update(u, true, d->n_quads, d->n_materials);
+    if (!why.empty()) return invalid(("rt_refit_quads: " + why).c_str());
+    std::vector<rt_quad> quads(d->quads, d->quads + d->n_quads);
+    std::vector<char> moved((size_t)d->n_quads, 0);
+    for (int32_t k = 0; k < u->count; ++k) {
+        const int32_t i = u->indices ? u->indices[k] : u->first + k;
+        quads[(size_t)i] = u->quads[k];
+        moved[(size_t)i] = 1;
+    }
+    if (nodes_out) {
+        std::vector<rt_node> nodes(d->nodes, d->nodes + d->n_nodes);
+        rt_refit::refit_quad_nodes(nodes.data(), d, quads.data(), moved);
+        if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
+    }
+    if (quads_out && d->n_quads) memcpy(quads_out, quads.data(), quads.size() * sizeof(rt_quad));
     return RT_OK;
 }
 

@@ -506,6 +506,15 @@ struct rt_refit_params {
     const int32_t* leaf_instance;         // the instance leaf q's box follows, or -1
     const rt_quad* quads;                 // the scene's: an instance's child box is computed from the records where they live
     const rt_box* boxes;
+    // rt_scene_update_quads: count, first, indices as above; record k replaces quad indices[k]
+    const rt_quad* quad_records;
+    uint32_t quad_epoch;                  // quad_stamp[i] == quad_epoch: quad i was replaced by this update
+    int32_t n_boxes;
+    uint32_t* quad_stamp;                 // per quad; apart from the other two stamp arrays, with an epoch of its own
+    rt_quad* quads_rw;                    // the scene's quads and boxes again, writable: the records kernel stores quads (pad0 = the
+    rt_box* boxes_rw;                     // axis code), the marks kernel bit 30 of first_quad and nothing else
+    const int32_t* leaf_solid;            // the solid leaf q's box follows (its primitive or its medium's boundary), or -1
 };
 hipError_t rt_launch_refit(const rt_refit_params& p, hipStream_t st);             // a sphere update
 hipError_t rt_launch_refit_instances(const rt_refit_params& p, hipStream_t st);   // an instance update: two kernels of its own, then the same unions
+hipError_t rt_launch_refit_quads(const rt_refit_params& p, hipStream_t st);       // a quad update: records, box marks, leaves, then the same unions

@@ -11,7 +11,9 @@
 //                slots from step 3 and partial tail leaves -- at most 126 + (b - a) / 64 reads whatever the tree's shape --;
 //                one further wave reduces the slots' largest coordinates to the scene's bound.
 // An instance update runs steps 1 and 2 as kernels of its own (rt_refit_instance_records_kernel, _leaves_kernel) and steps 3 and
-// 4 unchanged.
+// 4 unchanged.  A quad update (rt_scene_update_quads) does the same with rt_refit_quad_records_kernel and
+// rt_refit_quad_leaves_kernel and, between them, rt_refit_box_marks_kernel: the data rt_scene_create derives from quad records
+// (the axis code in pad0, the canonical mark in bit 30 of first_quad) follow the records.
 // Float min / max are exact, so no result depends on the order of a reduction (up to the sign of a zero).  No address depends
 // on record data: every index comes from the host's tables or from the index list the host has checked.
 // The render kernels read some of these arrays through the scalar cache (uniform_load, rt_device_funcs.h); that stays correct
@@ -115,6 +117,49 @@ __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_instance_leaves_ker
     store_leaf(p, q, lo, hi);
 }
 
+// ---- rt_scene_update_quads
+// One lane per record: the checks, the axis code rt_scene_create would have derived (the same function), the store, the stamp.
+__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_quad_records_kernel(const rt_refit_params p) {
+    const int k = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
+    if (k >= p.count) return;
+    rt_quad rec = p.quad_records[k];
+    if (!rt_refit::quad_record_ok(rec, p.n_materials)) {
+        atomicOr(reinterpret_cast<unsigned int*>(p.result) + 3, 1u);    // refused: the quad, its stamp, its boxes and marks stay
+        return;
+    }
+    const int i = p.indices ? p.indices[k] : p.first + k;                 // checked on the host: in range, each at most once
+    rec.pad0 = __int_as_float(rt_refit::axis_code(rec));
+    p.quads_rw[i] = rec;
+    p.quad_stamp[i] = p.quad_epoch;
+}
+
+// One lane per box, after every record is stored (a launch of its own: box ranges may overlap, and a lane that stores one face
+// cannot know whether another has been stored): bit 30 of first_quad from the six faces' codes.  Nothing else of the word changes.
+__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_box_marks_kernel(const rt_refit_params p) {
+    const int b = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
+    if (b >= p.n_boxes) return;
+    const int32_t word = p.boxes_rw[b].first_quad, first = word & RT_BOX_FIRST_MASK;
+    int32_t codes[6];
+#pragma unroll
+    for (int f = 0; f < 6; ++f) codes[f] = __float_as_int(p.quads[first + f].pad0);
+    const int32_t marked = rt_refit::canonical_codes(codes) ? (word | RT_BOX_CANONICAL) : (word & ~RT_BOX_CANONICAL);
+    if (marked != word) p.boxes_rw[b].first_quad = marked;
+}
+
+// One lane per leaf: a leaf whose solid depends on a quad with this update's stamp takes its rule's box from the records where
+// they live.  Addresses: leaf_solid (the host's table), the stored instance child, first_quad with its marks masked.
+__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_quad_leaves_kernel(const rt_refit_params p) {
+    const int q = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
+    if (q >= p.n_leaves) return;
+    const int32_t solid = p.leaf_solid[q];
+    const uint32_t* stamp = p.quad_stamp;
+    const uint32_t epoch = p.quad_epoch;
+    if (!rt_refit::solid_moved(solid, p.boxes, p.instances, [=](int i) { return stamp[i] == epoch; })) return;
+    float lo[3], hi[3];
+    rt_refit::solid_box(solid, p.spheres, p.quads, p.boxes, p.instances, lo, hi);
+    store_leaf(p, q, lo, hi);
+}
+
 __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_slots_kernel(const rt_refit_params p) {
     const int k = (int)(blockIdx.x * (RT_REFIT_THREADS / 64) + threadIdx.x / 64), lane = (int)(threadIdx.x & 63);
     if (k >= p.n_slots) return;                                         // (whole waves leave together)
@@ -194,6 +239,16 @@ hipError_t rt_launch_refit_instances(const rt_refit_params& p, hipStream_t st) {
     if (p.count > 0) hipLaunchKernelGGL(rt_refit_instance_records_kernel, dim3(blocks_for(p.count, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
     if (p.count > 0 && p.n_leaves > 0)
         hipLaunchKernelGGL(rt_refit_instance_leaves_kernel, dim3(blocks_for(p.n_leaves, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
+    launch_unions(p, st);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_refit_quads(const rt_refit_params& p, hipStream_t st) {
+    if (p.count > 0) hipLaunchKernelGGL(rt_refit_quad_records_kernel, dim3(blocks_for(p.count, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
+    if (p.count > 0 && p.n_boxes > 0)
+        hipLaunchKernelGGL(rt_refit_box_marks_kernel, dim3(blocks_for(p.n_boxes, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
+    if (p.count > 0 && p.n_leaves > 0)
+        hipLaunchKernelGGL(rt_refit_quad_leaves_kernel, dim3(blocks_for(p.n_leaves, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
     launch_unions(p, st);
     return hipGetLastError();
 }

@@ -202,6 +202,16 @@ rt_status rt_multi_update_instances(rt_multi* m, const rt_instance_update* updat
     return RT_OK;
 }
 
+// rt_scene_update_quads with host records on every replica, as rt_multi_update_spheres
+rt_status rt_multi_update_quads(rt_multi* m, const rt_quad_update* update, int recalibrate) {
+    if (!m) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_update_quads: null rt_multi"); return RT_ERR_INVALID; }
+    for (int d = m->n - 1; d >= 0; --d) {
+        const rt_status st = rt_scene_update_quads(m->scenes[d], update, 0, recalibrate, nullptr);
+        if (st != RT_OK) return st;
+    }
+    return RT_OK;
+}
+
 rt_status rt_multi_row_owner(int32_t global_row, int32_t tile_rows, int32_t n_gpus, int32_t* device, int32_t* local_row) {
     if (global_row < 0 || tile_rows <= 0 || n_gpus <= 0 || !device || !local_row) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_row_owner: bad argument"); return RT_ERR_INVALID; }
     int r, l;

@@ -1,5 +1,5 @@
-// rt_refit_host.h -- the host half of rt_scene_update_spheres and rt_scene_update_instances (include/rt_abi.h; DESIGN.md 4.15,
-// 4.17): the box rules, the checks of an update and the refit of a node array in the description's link encoding.  Plain C++ with no HIP call, so that
+// rt_refit_host.h -- the host half of rt_scene_update_spheres, rt_scene_update_instances and rt_scene_update_quads
+// (include/rt_abi.h): the box rules, the checks of an update and the refit of a node array in the description's link encoding.  Plain C++ with no HIP call, so that
 // rt_refit_nodes needs no device and the same text compiles into a stand-alone host program; rt_kernel_refit.hip takes the
 // box rule from here too, so host and device cannot drift apart.
 #pragma once
@@ -107,7 +107,7 @@ RT_REFIT_HD inline void quad_box(const rt_quad& q, float lo[3], float hi[3]) {
 
 // compound6: the six faces' boxes in array order.  first_quad's high bits are the device's marks (rt_scene_create) and masked off.
 RT_REFIT_HD inline void box_box(const rt_box& b, const rt_quad* quads, float lo[3], float hi[3]) {
-    const int32_t first = b.first_quad & 0x3FFFFFFF;
+    const int32_t first = b.first_quad & 0x3FFFFFFF;   // (RT_BOX_FIRST_MASK, below)
     quad_box(quads[first], lo, hi);
     for (int f = 1; f < 6; ++f) {
         float l[3], h[3];
@@ -232,6 +232,115 @@ inline void refit_instance_nodes(rt_node* nodes, const rt_scene_desc* d, const r
         if (ii < 0 || !moved[(size_t)ii]) return;
         child_box(instances[ii].child, d->spheres, d->quads, d->boxes, lo, hi);
         instance_box(instances[ii], lo, hi);
+    });
+}
+
+// ---- quads and boxes (rt_scene_update_quads).  The boxes are quad_box / box_box / child_box / instance_box above;
+// what is new is the data rt_scene_create derives from quad records and keeps on the device -- the axis code in rt_quad.pad0 and
+// the canonical-box mark, bit 30 of rt_box.first_quad (quad_test_axis and the six-face fast path, rt_device_funcs.h) --, which
+// creation and update take from the same two functions here.
+
+// The axis of an axis-aligned quad, or -1: its unit normal is exactly +-e_C and u, v, w each have exactly one non-zero component
+// on the fitting axes.
+RT_REFIT_HD inline int axis_of(const rt_quad& q) {
+    for (int c = 0; c < 3; ++c) {
+        const int a = (c + 1) % 3, b = (c + 2) % 3;
+        if (!((q.n[c] == 1.0f || q.n[c] == -1.0f) && q.n[a] == 0.0f && q.n[b] == 0.0f)) continue;
+        if (!(q.w[a] == 0.0f && q.w[b] == 0.0f && q.w[c] != 0.0f && q.u[c] == 0.0f && q.v[c] == 0.0f)) continue;
+        const bool u_on_a = q.u[a] != 0.0f && q.u[b] == 0.0f, u_on_b = q.u[b] != 0.0f && q.u[a] == 0.0f;
+        const bool v_on_a = q.v[a] != 0.0f && q.v[b] == 0.0f, v_on_b = q.v[b] != 0.0f && q.v[a] == 0.0f;
+        if ((u_on_a && v_on_b) || (u_on_b && v_on_a)) return c;
+    }
+    return -1;
+}
+// the word rt_quad.pad0 holds on the device: 1 + axis, 0 for any other quad
+RT_REFIT_HD inline int32_t axis_code(const rt_quad& q) { const int c = axis_of(q); return c >= 0 ? 1 + c : 0; }
+#define RT_BOX_CANONICAL 0x40000000
+#define RT_BOX_FIRST_MASK 0x3FFFFFFF
+// A box is canonical when its six faces are axis-aligned with normals along z, x, z, x, y, y (make_box's order, the reference's
+// quad.cuh:145-162): codes[f] is the axis code of face f.
+RT_REFIT_HD inline bool canonical_codes(const int32_t codes[6]) {
+    return codes[0] == 3 && codes[1] == 1 && codes[2] == 3 && codes[3] == 1 && codes[4] == 2 && codes[5] == 2;
+}
+
+// what the checks allow of a quad record: Q, D, u, v, w, n finite, mat one of the scene's materials (pad0..2 are not looked at)
+RT_REFIT_HD inline bool quad_finite(const rt_quad& q) {
+    bool finite = q.D - q.D == 0.0f;
+    for (int c = 0; c < 3; ++c)
+        finite = finite && (q.Q[c] - q.Q[c] == 0.0f) && (q.u[c] - q.u[c] == 0.0f) && (q.v[c] - q.v[c] == 0.0f) && (q.w[c] - q.w[c] == 0.0f) &&
+                 (q.n[c] - q.n[c] == 0.0f);
+    return finite;
+}
+RT_REFIT_HD inline bool quad_record_ok(const rt_quad& q, int32_t n_materials) { return quad_finite(q) && q.mat >= 0 && q.mat < n_materials; }
+
+// The solid a leaf's box follows: the leaf's primitive, or the boundary of the leaf's constant_medium -- a reference to a sphere,
+// quad, box or instance inside its array, or -1.
+inline int32_t leaf_solid(int32_t prim, const rt_medium* media, int32_t n_media, int32_t n_spheres, int32_t n_quads, int32_t n_boxes, int32_t n_instances) {
+    if (prim < 0) return -1;
+    if (RT_PRIM_KIND(prim) == RT_PRIM_MEDIUM) {
+        const int m = RT_PRIM_INDEX(prim);
+        if (m >= n_media) return -1;
+        prim = media[m].boundary;
+        if (prim < 0) return -1;
+    }
+    const int kind = RT_PRIM_KIND(prim), i = RT_PRIM_INDEX(prim);
+    const int32_t n = kind == RT_PRIM_SPHERE ? n_spheres : kind == RT_PRIM_QUAD ? n_quads : kind == RT_PRIM_BOX ? n_boxes : kind == RT_PRIM_INSTANCE ? n_instances : 0;
+    return i < n ? prim : -1;
+}
+
+// Whether a solid depends on a quad for which moved(i) holds: a quad by itself, a box by any of its six faces, an instance by the
+// same test of its stored child.  Every reference is one rt_scene_create has validated (or leaf_solid has bounded).
+template <class Moved>
+RT_REFIT_HD inline bool solid_moved(int32_t solid, const rt_box* boxes, const rt_instance* instances, Moved&& moved) {
+    if (solid < 0) return false;
+    if (RT_PRIM_KIND(solid) == RT_PRIM_INSTANCE) solid = instances[RT_PRIM_INDEX(solid)].child;
+    if (solid < 0) return false;
+    const int kind = RT_PRIM_KIND(solid), i = RT_PRIM_INDEX(solid);
+    if (kind == RT_PRIM_QUAD) return moved(i);
+    if (kind != RT_PRIM_BOX) return false;
+    const int32_t first = boxes[i].first_quad & RT_BOX_FIRST_MASK;
+    bool any = false;
+    for (int f = 0; f < 6; ++f) any = any || moved(first + f);
+    return any;
+}
+// the box of a solid by the rules of rt_abi.h: the sphere, quad and box rules, and the instance rule over its child's box
+RT_REFIT_HD inline void solid_box(int32_t solid, const rt_sphere* spheres, const rt_quad* quads, const rt_box* boxes, const rt_instance* instances,
+                                  float lo[3], float hi[3]) {
+    if (RT_PRIM_KIND(solid) == RT_PRIM_INSTANCE) {
+        const rt_instance in = instances[RT_PRIM_INDEX(solid)];
+        child_box(in.child, spheres, quads, boxes, lo, hi);
+        instance_box(in, lo, hi);
+    } else child_box(solid, spheres, quads, boxes, lo, hi);
+}
+
+// The refusals of a quad update (rt_abi.h), as check_update.
+inline std::string check_quad_update(const rt_quad_update* u, bool host_records, int32_t n_quads, int32_t n_materials) {
+    if (!u) return "null update";
+    if (u->count < 0) return "count is negative";
+    if (u->count == 0) return "";
+    if (!u->quads) return "null quad records";
+    if (u->count > n_quads) return "more records than the scene has quads (an index is out of range or appears twice)";
+    std::vector<char> seen((size_t)n_quads, 0);
+    for (int32_t k = 0; k < u->count; ++k) {
+        const long long i = u->indices ? (long long)u->indices[k] : (long long)u->first + k;
+        if (i < 0 || i >= n_quads) return "quad index out of range";
+        if (seen[(size_t)i]) return "a quad index appears twice";
+        seen[(size_t)i] = 1;
+        if (host_records) {
+            if (!quad_finite(u->quads[k])) return "a quad record has a non-finite Q, D, u, v, w or n";
+            if (u->quads[k].mat < 0 || u->quads[k].mat >= n_materials) return "quad material out of range";
+        }
+    }
+    return "";
+}
+
+// the leaves whose solid depends on a quad marked in `moved` take their rule's box over quads[...] (of the description `d`, whose
+// references rt_scene_create's checks have validated)
+inline void refit_quad_nodes(rt_node* nodes, const rt_scene_desc* d, const rt_quad* quads, const std::vector<char>& moved) {
+    refit_nodes(nodes, d->n_nodes, [&](int32_t prim, float* lo, float* hi) {
+        const int32_t solid = leaf_solid(prim, d->media, d->n_media, d->n_spheres, d->n_quads, d->n_boxes, d->n_instances);
+        if (!solid_moved(solid, d->boxes, d->instances, [&](int i) { return moved[(size_t)i] != 0; })) return;
+        solid_box(solid, d->spheres, quads, d->boxes, d->instances, lo, hi);
     });
 }
 

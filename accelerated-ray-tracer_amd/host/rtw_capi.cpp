@@ -90,6 +90,39 @@ int rtw_rotation(float degrees, float* sin_t, float* cos_t) {
     return 0;
 }
 
+// quad.cuh:29-54 through the host library's own quad constructor: the rt_quad record a reference scene function's
+// quad(Q, u, v, material) flattens to -- its D, w and unit normal in the constructor's float arithmetic --, with `mat` as given
+// (an index into the scene's materials).  What rt_scene_update_quads takes for a quad that moves or changes shape.
+static void quad_record_of(const rtw::quad& q, int mat, rt_quad* out) {
+    memset(out, 0, sizeof(*out));
+    const rtw::vec3* src[5] = {&q.Q, &q.u, &q.v, &q.w, &q.normal};
+    float* dst[5] = {out->Q, out->u, out->v, out->w, out->n};
+    for (int k = 0; k < 5; ++k) { dst[k][0] = src[k]->x(); dst[k][1] = src[k]->y(); dst[k][2] = src[k]->z(); }
+    out->D = q.D;
+    out->mat = mat;
+}
+int rtw_quad_record(const float* Q, const float* u, const float* v, int mat, rt_quad* out) {
+    if (!Q || !u || !v || !out) return -1;
+    const rtw::quad q(rtw::vec3(Q[0], Q[1], Q[2]), rtw::vec3(u[0], u[1], u[2]), rtw::vec3(v[0], v[1], v[2]), nullptr);
+    quad_record_of(q, mat, out);
+    return 0;
+}
+
+// quad.cuh:145-162 through the host library's own make_box: the six rt_quad records, in face order, of make_box(a, b, material)
+int rtw_box_records(const float* a, const float* b, int mat, rt_quad* out6) {
+    if (!a || !b || !out6) return -1;
+    std::unique_ptr<rtw::hittable> box(rtw::make_box(rtw::vec3(a[0], a[1], a[2]), rtw::vec3(b[0], b[1], b[2]), nullptr));
+    const rtw::compound6* c = dynamic_cast<const rtw::compound6*>(box.get());
+    if (!c) return -1;
+    int bad = 0;
+    for (int f = 0; f < 6; ++f) {
+        const rtw::quad* q = dynamic_cast<const rtw::quad*>(c->faces[f]);
+        if (q) quad_record_of(*q, mat, out6 + f); else bad = -1;
+        delete c->faces[f];                                           // (compound6 does not own its faces)
+    }
+    return bad;
+}
+
 int rtw_load_ppm(const char* path, unsigned char* out, int cap, int* w, int* h) {
     std::vector<unsigned char> px;
     if (!rtw::load_ppm(path, px, *w, *h)) return -1;

@@ -724,8 +724,8 @@ rt_status rt_debug_scene_boxes(const rt_scene* scene, int32_t which, void* out, 
  * computed from is the scene's own, validated at creation, never the incoming record's; the only data-derived addresses come
  * from `indices`, which the host has checked.
  *
- * What still cannot move: a quad or box that is not under an instance (their records cannot change), a sphere record under an
- * instance (rt_scene_update_spheres refuses it; the sphere moves with its instance), and an instance's child.
+ * What still cannot move: a sphere record under an instance (rt_scene_update_spheres refuses it; the sphere moves with its
+ * instance), and an instance's child.  Quads and boxes, under an instance or not, change through rt_scene_update_quads (below).
  * rt_scene_get_instances copies the records the next frame will use (cap >= the scene's instance count, else RT_ERR_INVALID).
  * rt_multi_update_instances applies host records to every replica of an rt_multi.  rt_refit_instances is the host-only statement
  * of D' (no device needed), as rt_refit_nodes: nodes_out receives desc->n_nodes nodes, instances_out desc->n_instances records;
@@ -739,6 +739,75 @@ typedef struct rt_instance_update {
 rt_status rt_scene_update_instances(rt_scene* scene, const rt_instance_update* update, int instances_on_device, int recalibrate, void* stream);
 rt_status rt_scene_get_instances(const rt_scene* scene, rt_instance* out, int32_t cap);
 rt_status rt_refit_instances(const rt_scene_desc* desc, const rt_instance_update* update, rt_node* nodes_out, rt_instance* instances_out);   /* host only, no device */
+
+/* ---- moving quads and boxes: new quad records for a scene that stays on the device ----
+ * rt_scene_update_quads replaces quad records of a resident scene -- free quads, the six faces of a box, either of them under an
+ * instance or around a constant_medium -- and refits every box that depends on them, on the device: the light and the walls of a
+ * Cornell box, a door, a ground plate, a lid that opens, a box that changes size, frame after frame without a second
+ * rt_scene_create.
+ *
+ * The update.  Record k of `quads` replaces quad indices[k], or quad first + k when indices is null.  indices is host memory
+ * always; quads is host memory, or, with quads_on_device != 0, device (or managed) memory of the scene's device (nothing is
+ * copied).  count == 0 is a successful no-op.  A box changes through its faces: quads first_quad .. first_quad + 5.
+ *
+ * Contract.  Let D' be the scene's description with those records replaced and its node boxes refit as below.  From the call on,
+ * every frame entry -- rt_render, rt_render_window, rt_render_adaptive, rt_render_variance, rt_render_aov,
+ * rt_render_aov_through -- and both query entries -- rt_trace_rays, rt_radiance_rays -- write, bit for bit, what they write on
+ * rt_scene_create(D'), and report the same rays and samples.  Topology, link words, the walk array's choice of nodes and the
+ * tier arrays' .w words are never written.
+ *   What a record may change.  Every geometric field (Q, D, u, v, w, n) and mat.  The caller supplies the derived fields D, w
+ *     and n as a description does (n the unit normal, D = n . Q, w = (u x v) / |u x v|^2); their consistency with Q, u, v is not
+ *     checked, exactly as rt_scene_create does not check it.  pad0 is not looked at; pad1 and pad2 are stored as given.
+ *   Derived device data.  rt_scene_create keeps two things it derives from quad records: the axis code of every quad (in the
+ *     device copy's pad0: 1 + C for a quad whose unit normal is exactly +-e_C and whose u, v, w each have exactly one non-zero
+ *     component on the fitting axes, else 0) and the canonical mark of every box (bit 30 of the device copy's first_quad: its six
+ *     faces carry the codes 3, 1, 3, 1, 2, 2 -- normals along z, x, z, x, y, y -- in order).  They select the axis-aligned quad
+ *     test and the six-face fast path.  The update stores the axis code of every incoming record by the same function creation
+ *     uses, and, after all records are stored, recomputes the mark of every box from its six faces (box ranges may overlap, so
+ *     the decision is per box, in a launch of its own after the one that stores).  rt_scene_get_quads returns pad0 as +0.0f.
+ *   Leaves that change.  Call a leaf's solid its primitive, or, for a constant_medium, that medium's boundary.  A leaf is
+ *     recomputed when its solid is an updated quad, a box with at least one updated face, or an instance whose child is either
+ *     of those (one box under several instances recomputes every one of those leaves).  Every other leaf keeps its box, whatever
+ *     rule made it (a generated description may carry outward-rounded boxes; such a leaf keeps its box until something under it
+ *     is updated).
+ *   Box rule.  The quad rule, the box rule and the instance rule over the child's box, as stated for rt_scene_update_instances
+ *     above: value for value what the host library's constructors give (quad::quad, compound6, rotate_y, translate), so that
+ *     writing a flattened scene's own records back changes no box; tests/test_update_quads_host.py pins that on named scenes.
+ *   Refit, what goes stale, recalibrate, a pending frame, progressive states, the cost map: as after a sphere update.
+ * The work -- five small launches -- is enqueued on `stream` after whatever it holds.  The call is SYNCHRONOUS: it reads 16 bytes
+ * back (the new bound and the flag below).
+ *
+ * Refusals.  Each of these is RT_ERR_INVALID before any HIP call, with rt_last_error_detail() naming the check after
+ * "rt_scene_update_quads: " (or "rt_refit_quads: "), and leaves the scene untouched: a null scene, update or record array;
+ * count < 0; an index out of range; an index that appears twice; with host records, a non-finite Q, D, u, v, w or n, or a mat
+ * outside the scene's materials.  A quad under an instance is allowed.
+ * Device-resident records are checked by the kernel that stores them: a record with a non-finite field or a bad mat is neither
+ * stored nor stamped, a flag is read back with the bound, and the call returns RT_ERR_INVALID with every other record applied
+ * and every box and mark consistent with the records actually stored.
+ * Memory safety.  No address depends on record data.  Addresses come only from the index list, which the host has checked; from a
+ * per-leaf table the host makes from the scene's own leaves (the solid each leaf follows); from the scene's stored instance
+ * child; and from boxes[..].first_quad with its mark bits masked -- all validated by rt_scene_create and never written from an
+ * incoming record (the update writes bit 30 of first_quad only).
+ *
+ * What it does not do: rt_reproject and its followers do not follow a moved quad; their tap tests reject such pixels, which
+ * then restart their history.
+ * rt_scene_get_quads copies the records the next frame will use, pad0 zeroed (cap >= the scene's quad count, else
+ * RT_ERR_INVALID).  rt_multi_update_quads applies host records to every replica of an rt_multi.  rt_refit_quads is the host-only
+ * statement of D' (no device needed), as rt_refit_nodes: nodes_out receives desc->n_nodes nodes, quads_out desc->n_quads records
+ * (the incoming records as given, pad0 included); either may be null; it makes rt_scene_create's checks of `desc` and the
+ * refusals above and writes nothing when it refuses.
+ * rt_debug_scene_quads (tests): the device's quad and box records raw, marks included -- pad0 holds the axis code as an integer,
+ * first_quad bit 30 the canonical mark; quad_cap / box_cap >= the scene's counts, else RT_ERR_INVALID; either output may be null. */
+typedef struct rt_quad_update {
+    int32_t count;            /* records in `quads` */
+    int32_t first;            /* used when indices == NULL: record k replaces quad first + k */
+    const int32_t* indices;   /* or NULL; host memory always; each index at most once */
+    const rt_quad* quads;     /* host memory, or device memory when quads_on_device != 0 */
+} rt_quad_update; /* 24 B */
+rt_status rt_scene_update_quads(rt_scene* scene, const rt_quad_update* update, int quads_on_device, int recalibrate, void* stream);
+rt_status rt_scene_get_quads(const rt_scene* scene, rt_quad* out, int32_t cap);
+rt_status rt_refit_quads(const rt_scene_desc* desc, const rt_quad_update* update, rt_node* nodes_out, rt_quad* quads_out);   /* host only, no device */
+rt_status rt_debug_scene_quads(const rt_scene* scene, rt_quad* quads_out, int32_t quad_cap, rt_box* boxes_out, int32_t box_cap);
 
 /* ---- temporal reprojection: the current frame blended into the reprojected history of the previous one ----
  * With a camera that moves, the samples of one frame can be reused in the next: rt_reproject finds, for every pixel of the
@@ -940,6 +1009,7 @@ rt_status rt_multi_destroy(rt_multi* m);
 rt_status rt_multi_set_camera(rt_multi* m, const rt_camera* camera, int recalibrate);   /* rt_scene_set_camera on every replica */
 rt_status rt_multi_update_spheres(rt_multi* m, const rt_sphere_update* update, int recalibrate);   /* rt_scene_update_spheres, host records, on every replica */
 rt_status rt_multi_update_instances(rt_multi* m, const rt_instance_update* update, int recalibrate);   /* rt_scene_update_instances, host records, on every replica */
+rt_status rt_multi_update_quads(rt_multi* m, const rt_quad_update* update, int recalibrate);           /* rt_scene_update_quads, host records, on every replica */
 int32_t rt_multi_device_count(const rt_multi* m);
 /* the row partition rt_multi_render uses: which device renders global row j and at which row of its compact buffer
  * (the inverse of rt_local_to_global_row for tile_first = device, tile_stride = n_gpus) */
