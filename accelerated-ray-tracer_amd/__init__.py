@@ -124,6 +124,10 @@ class RtReprojectInstanceDesc(C.Structure):
                 ("inst", C.c_void_p), ("prev_inst", C.c_void_p)]
 
 
+class RtReprojectQuadDesc(C.Structure):
+    _fields_ = [("n_quads", C.c_int32), ("reserved", C.c_int32), ("quads", C.c_void_p), ("prev_quads", C.c_void_p)]
+
+
 class RtSphereUpdate(C.Structure):
     _fields_ = [("count", C.c_int32), ("first", C.c_int32), ("indices", C.c_void_p), ("spheres", C.c_void_p)]
 
@@ -193,7 +197,8 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_reproject_moving", "rt_debug_cost_map", "rt_debug_set_cost_map",
                   "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances",
                   "rt_debug_box_tests", "rt_reproject_instances",
-                  "rt_scene_update_quads", "rt_scene_get_quads", "rt_refit_quads", "rt_multi_update_quads", "rt_debug_scene_quads"]
+                  "rt_scene_update_quads", "rt_scene_get_quads", "rt_refit_quads", "rt_multi_update_quads", "rt_debug_scene_quads",
+                  "rt_reproject_quads"]
 
 _rt = None
 _host = None
@@ -307,6 +312,9 @@ def rt_lib():
         if hasattr(L, "rt_reproject_instances"):   # (absent from an older library measured through RT_LIB_OVERRIDE)
             L.rt_reproject_instances.argtypes = [C.POINTER(RtReprojectDesc), C.POINTER(RtReprojectMotionDesc), C.POINTER(RtReprojectInstanceDesc),
                                                  C.c_int, C.c_void_p, C.c_int]
+        if hasattr(L, "rt_reproject_quads"):
+            L.rt_reproject_quads.argtypes = [C.POINTER(RtReprojectDesc), C.POINTER(RtReprojectMotionDesc), C.POINTER(RtReprojectInstanceDesc),
+                                             C.POINTER(RtReprojectQuadDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_debug_adaptive_passes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.rt_debug_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rt_debug_prior.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -604,7 +612,7 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
               alpha_min=REPROJECT_DEFAULTS["alpha_min"], depth_tol=REPROJECT_DEFAULTS["depth_tol"],
               normal_min=REPROJECT_DEFAULTS["normal_min"], max_history=REPROJECT_DEFAULTS["max_history"], stream=0, blocking=True,
               spheres=None, prev_spheres=None, media=None, time=None, prev_time=None,
-              inst=None, prev_inst=None, instances=None, prev_instances=None):
+              inst=None, prev_inst=None, instances=None, prev_instances=None, quads=None, prev_quads=None):
     """Temporal reprojection (rt_reproject, include/rt_abi.h): the current linear frame `color` (ny, nx, 3) blended into the
     history of the previous frame, fetched where each pixel's surface point -- from `depth` and `alpha` (ny, nx) of
     render_aov and the cameras `cur` and `prev` -- was in that frame.  history (ny, nx, 3) and history_len (ny, nx) are the
@@ -631,7 +639,14 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     pixel on an instance whose record differs -- or in a medium bounded by one -- is carried back through the two records, its
     normal with it.  inst (ny, nx) int32, render_aov's `inst` of the current frame, is then required beside prim and prev_prim,
     and prev_inst exactly when history is given; a tap must show the pixel's instance.  The sphere arguments stay optional
-    beside these.  With instances=None the other three must be None too."""
+    beside these.  With instances=None and quads=None the other three must be None too.
+
+    quads / prev_quads (rt_reproject_quads): the quad records the current and the previous frame were rendered with
+    (DeviceScene.quads() after and before update_quads), arrays of QUAD_DTYPE or (n, 20) tensors.  A surface pixel on a quad --
+    a face of a box is one -- whose Q, u or v differ is carried back through its planar coordinates, in the object space of
+    its instance when it has one, and its normal becomes the previous record's.  inst is required (and prev_inst exactly when
+    history is given) beside prim and prev_prim; instances / prev_instances and the sphere arguments stay optional beside
+    these, with no record when absent -- but a quad under an instance is followed only with that instance's records given."""
     on_host = isinstance(color, np.ndarray)
     if not on_host and not hasattr(color, "data_ptr"):
         raise ValueError("color: a numpy array or a torch tensor is expected")
@@ -674,10 +689,14 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     elif motion is False:
         motion = None
 
-    md, imd = None, None
-    if instances is None and any(x is not None for x in (inst, prev_inst, prev_instances)):
+    md, imd, qmd = None, None, None
+    if quads is None and prev_quads is not None:
+        raise ValueError("prev_quads needs quads")
+    if instances is None and quads is None and any(x is not None for x in (inst, prev_inst, prev_instances)):
         raise ValueError("inst, prev_inst and prev_instances need instances")
-    if spheres is None and instances is None:
+    if instances is None and prev_instances is not None:
+        raise ValueError("prev_instances needs instances")
+    if spheres is None and instances is None and quads is None:
         if any(x is not None for x in (prev_spheres, media, time, prev_time)):
             raise ValueError("prev_spheres, media, time and prev_time need spheres or instances")
     else:
@@ -689,7 +708,7 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             raise ValueError("spheres / instances: prim and prev_prim are required to follow what moved")
         md = RtReprojectMotionDesc()
         keep_tables = []
-        dtype_names = {id(SPHERE_DTYPE): "SPHERE", id(MEDIUM_DTYPE): "MEDIUM", id(INSTANCE_DTYPE): "INSTANCE"}
+        dtype_names = {id(SPHERE_DTYPE): "SPHERE", id(MEDIUM_DTYPE): "MEDIUM", id(INSTANCE_DTYPE): "INSTANCE", id(QUAD_DTYPE): "QUAD"}
 
         def table(x, name, dtype, words):
             if on_host:
@@ -730,6 +749,22 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
                 raise ValueError(f"prev_instances: {n_prev} records, instances has {imd.n_instances}")
             if imd.n_instances >= 1 << 28:
                 raise ValueError("instances: 2^28 records or more")
+        if quads is not None:
+            if prev_quads is None:
+                raise ValueError("quads needs prev_quads")
+            if inst is None:
+                raise ValueError("quads: inst is required, it says in whose object space a quad's record lives")
+            if (prev_inst is None) != (history is None):
+                raise ValueError("quads: prev_inst is required exactly when history is given")
+            if imd is None:
+                imd = RtReprojectInstanceDesc()
+            qmd = RtReprojectQuadDesc()
+            qmd.n_quads, qmd.quads = table(quads, "quads", QUAD_DTYPE, 20)
+            n_prev, qmd.prev_quads = table(prev_quads, "prev_quads", QUAD_DTYPE, 20)
+            if n_prev != qmd.n_quads:
+                raise ValueError(f"prev_quads: {n_prev} records, quads has {qmd.n_quads}")
+            if qmd.n_quads >= 1 << 28:
+                raise ValueError("quads: 2^28 records or more")
 
     def ptr(x, name, shape, integer=False):
         if x is None:
@@ -769,12 +804,15 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     elif imd is None:
         st = L.rt_reproject_moving(C.byref(d), C.byref(md), 0 if on_host else 1, stream_p, 1 if blocking else 0)
         del keep_tables
-    else:
+    elif qmd is None:
         st = L.rt_reproject_instances(C.byref(d), C.byref(md), C.byref(imd), 0 if on_host else 1, stream_p, 1 if blocking else 0)
+        del keep_tables
+    else:
+        st = L.rt_reproject_quads(C.byref(d), C.byref(md), C.byref(imd), C.byref(qmd), 0 if on_host else 1, stream_p, 1 if blocking else 0)
         del keep_tables
     if st == 1:
         raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_reproject" if md is None else "rt_reproject_moving" if imd is None else "rt_reproject_instances")
+    _check(st, "rt_reproject" if md is None else "rt_reproject_moving" if imd is None else "rt_reproject_instances" if qmd is None else "rt_reproject_quads")
     return ReprojectResult(out, out_len, motion)
 
 
@@ -1581,10 +1619,16 @@ class TemporalAccumulator:
     follow_instances=True: likewise for instances (reproject(instances=...)).  push() takes an update (instances,
     instance_indices, instance_first: DeviceScene.update_instances' arguments) that it applies first, reads the scene's instance
     records back, keeps them and render_aov's `inst` with the push, and reprojects with both pushes' records and planes.  The two
-    flags combine."""
+    flags combine.
+
+    follow_quads=True: likewise for quads and the faces of boxes (reproject(quads=...)).  push() takes an update (quads,
+    quad_indices, quad_first: DeviceScene.update_quads' arguments) that it applies first, reads the scene's quad records back
+    and keeps them with the push.  It reads the instance records and `inst` as follow_instances does, whether or not that flag
+    is set: a quad under an instance is carried in that instance's object space even when the instance stands still (and an
+    instance the caller moved is then followed as well).  The three flags combine."""
 
     def __init__(self, scene: "DeviceScene", frame: RtFrameDesc, denoise: bool = False, follow_spheres: bool = False,
-                 follow_instances: bool = False, **params):
+                 follow_instances: bool = False, follow_quads: bool = False, **params):
         unknown = set(params) - set(REPROJECT_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown parameter(s) {sorted(unknown)}: one of {', '.join(REPROJECT_DEFAULTS)} is expected")
@@ -1593,7 +1637,7 @@ class TemporalAccumulator:
         if frame.tile_first != 0 or frame.tile_stride != 1 or frame.tile_rows < frame.ny:
             raise ValueError("TemporalAccumulator needs the whole frame (tile_rows >= ny, tile_first = 0, tile_stride = 1)")
         self.scene, self.denoise, self.params = scene, bool(denoise), dict(REPROJECT_DEFAULTS, **params)
-        self.follow_spheres, self.follow_instances = bool(follow_spheres), bool(follow_instances)
+        self.follow_spheres, self.follow_instances, self.follow_quads = bool(follow_spheres), bool(follow_instances), bool(follow_quads)
         self.frame = RtFrameDesc.from_buffer_copy(frame)
         self.frame.gamma = 1.0
         self.aov_frame = RtFrameDesc.from_buffer_copy(self.frame)
@@ -1606,20 +1650,28 @@ class TemporalAccumulator:
         self.length = None
 
     def push(self, camera: RtCamera, recalibrate: bool = False, spheres=None, indices=None, first: int = 0, instances=None,
-             instance_indices=None, instance_first: int = 0) -> np.ndarray:
-        records, instance_records = None, None
+             instance_indices=None, instance_first: int = 0, quads=None, quad_indices=None, quad_first: int = 0) -> np.ndarray:
+        records, instance_records, quad_records = None, None, None
+        if not self.follow_instances and (instances is not None or instance_indices is not None or instance_first != 0):
+            raise ValueError("instances, instance_indices and instance_first need follow_instances=True")
+        if not self.follow_quads and (quads is not None or quad_indices is not None or quad_first != 0):
+            raise ValueError("quads, quad_indices and quad_first need follow_quads=True")
+        if not self.follow_spheres and (spheres is not None or indices is not None or first != 0):
+            raise ValueError("spheres, indices and first need follow_spheres=True")
         if self.follow_instances:
             if instances is not None:
                 self.scene.update_instances(instances, instance_indices, instance_first)
             instance_records = self.scene.instances()
-        elif instances is not None or instance_indices is not None or instance_first != 0:
-            raise ValueError("instances, instance_indices and instance_first need follow_instances=True")
+        if self.follow_quads:
+            if quads is not None:
+                self.scene.update_quads(quads, quad_indices, quad_first)
+            quad_records = self.scene.quads()
+            if instance_records is None:
+                instance_records = self.scene.instances()
         if self.follow_spheres:
             if spheres is not None:
                 self.scene.update_spheres(spheres, indices, first)
             records = self.scene.spheres()
-        elif spheres is not None or indices is not None or first != 0:
-            raise ValueError("spheres, indices and first need follow_spheres=True")
         self.scene.set_camera(camera, recalibrate)
         color, _ = self.scene.render(self.frame)
         aov = self.scene.render_aov(self.aov_frame, albedo=self.denoise, ids=True)
@@ -1634,10 +1686,13 @@ class TemporalAccumulator:
             if instance_records is not None:
                 follow.update(instances=instance_records, prev_instances=p["instances"], inst=aov["inst"], prev_inst=p["inst"],
                               media=self.scene.host.media())
+            if quad_records is not None:
+                follow.update(quads=quad_records, prev_quads=p["quads"])
             r = reproject(color, aov["depth"], aov["alpha"], cam, p["camera"], aov["normal"], aov["prim"], p["out"], p["length"],
                           p["depth"], p["alpha"], p["normal"], p["prim"], **self.params, **follow)
         self._prev = {"camera": cam, "out": r.out, "length": r.length, "depth": aov["depth"], "alpha": aov["alpha"],
-                      "normal": aov["normal"], "prim": aov["prim"], "spheres": records, "instances": instance_records, "inst": aov["inst"]}
+                      "normal": aov["normal"], "prim": aov["prim"], "spheres": records, "instances": instance_records, "inst": aov["inst"],
+                      "quads": quad_records}
         self.length = r.length
         if self.denoise:
             return denoise(r.out, aov["albedo"], aov["normal"], aov["depth"])

@@ -2114,10 +2114,10 @@ rt_status rt_reproject_matrix(const rt_camera* prev, float m[9]) {
 }
 
 namespace {
-// rt_reproject (m == null), rt_reproject_moving and rt_reproject_instances (im != null, with m): the checks, the staging of host
-// buffers and the parameter block are one
-rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, const rt_reproject_instance_desc* im, const char* who,
-                         int buffers_on_device, void* stream_v, int blocking) {
+// rt_reproject (m == null), rt_reproject_moving, rt_reproject_instances (im != null, with m) and rt_reproject_quads (qm != null, with
+// both): the checks, the staging of host buffers and the parameter block are one
+rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, const rt_reproject_instance_desc* im,
+                         const rt_reproject_quad_desc* qm, const char* who, int buffers_on_device, void* stream_v, int blocking) {
     // argument checks: no HIP call before they pass
     auto bad = [&](const char* why) { return invalid((std::string(who) + ": " + why).c_str()); };
     if (!d) return bad("null description");
@@ -2152,6 +2152,11 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
         if (im->n_instances >= (1 << 28)) return bad("n_instances must be below 2^28");
         if (im->n_instances > 0 && (!im->instances || !im->prev_instances)) return bad("n_instances > 0 needs instances and prev_instances");
     }
+    if (qm) {
+        if (qm->n_quads < 0) return bad("n_quads must not be negative");
+        if (qm->n_quads >= (1 << 28)) return bad("n_quads must be below 2^28");
+        if (qm->n_quads > 0 && (!qm->quads || !qm->prev_quads)) return bad("n_quads > 0 needs quads and prev_quads");
+    }
     rt_reproject_params rp;
     memset(&rp, 0, sizeof(rp));
     if (rt_reproject_matrix(&d->prev, rp.m) != RT_OK) return bad("prev: the camera's basis is singular or its inverse is not finite");
@@ -2159,10 +2164,11 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
     struct buffer : traced_ptr { bool input; };
     enum { COLOR = 0, DEPTH, ALPHA, NORMAL, PRIM, HISTORY, HISTORY_LEN, PREV_DEPTH, PREV_ALPHA, PREV_NORMAL, PREV_PRIM, OUT, OUT_LEN, MOTION,
            SPHERES, PREV_SPHERES, MEDIA,            // the three tables: rt_reproject_moving and up, inputs behind the outputs
-           INSTANCES, PREV_INSTANCES, INST, PREV_INST, N_BUFS };   // rt_reproject_instances only
+           INSTANCES, PREV_INSTANCES, INST, PREV_INST,   // rt_reproject_instances and up
+           QUADS, PREV_QUADS, N_BUFS };                  // rt_reproject_quads only
     const size_t f1 = pixels * sizeof(float), f3 = 3 * f1;
     const size_t sphere_bytes = m ? (size_t)m->n_spheres * sizeof(rt_sphere) : 0, medium_bytes = m ? (size_t)m->n_media * sizeof(rt_medium) : 0;
-    const size_t instance_bytes = im ? (size_t)im->n_instances * sizeof(rt_instance) : 0;
+    const size_t instance_bytes = im ? (size_t)im->n_instances * sizeof(rt_instance) : 0, quad_bytes = qm ? (size_t)qm->n_quads * sizeof(rt_quad) : 0;
     const buffer bufs[N_BUFS] = {{{d->color, f3, "color", 4}, true}, {{d->depth, f1, "depth", 4}, true}, {{d->alpha, f1, "alpha", 4}, true},
                                  {{d->normal, f3, "normal", 4}, true}, {{d->prim, f1, "prim", 4}, true}, {{d->history, f3, "history", 4}, true},
                                  {{d->history_len, f1, "history_len", 4}, true}, {{d->prev_depth, f1, "prev_depth", 4}, true},
@@ -2174,7 +2180,9 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
                                  {{medium_bytes ? m->media : nullptr, medium_bytes, "media", 4}, true},
                                  {{instance_bytes ? im->instances : nullptr, instance_bytes, "instances", 4}, true},
                                  {{instance_bytes ? im->prev_instances : nullptr, instance_bytes, "prev_instances", 4}, true},
-                                 {{im ? im->inst : nullptr, f1, "inst", 4}, true}, {{im ? im->prev_inst : nullptr, f1, "prev_inst", 4}, true}};
+                                 {{im ? im->inst : nullptr, f1, "inst", 4}, true}, {{im ? im->prev_inst : nullptr, f1, "prev_inst", 4}, true},
+                                 {{quad_bytes ? qm->quads : nullptr, quad_bytes, "quads", 4}, true},
+                                 {{quad_bytes ? qm->prev_quads : nullptr, quad_bytes, "prev_quads", 4}, true}};
     for (int o = OUT; o <= MOTION; ++o)     // an output shares no byte with any other buffer
         for (int k = 0; k < N_BUFS; ++k) {
             const uintptr_t pa = (uintptr_t)bufs[o].p, pb = (uintptr_t)bufs[k].p;
@@ -2222,8 +2230,9 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
     }
     rp.alpha_min = d->alpha_min; rp.depth_tol = d->depth_tol; rp.normal_min = d->normal_min; rp.max_history = d->max_history;
     if (m) {
-        rt_reproject_follow_instance_params ip;
-        memset(&ip, 0, sizeof(ip));
+        rt_reproject_follow_quad_params qp;
+        memset(&qp, 0, sizeof(qp));
+        rt_reproject_follow_instance_params& ip = qp;
         rt_reproject_follow_params& fp = ip;
         fp.spheres = static_cast<const rt_sphere*>(dev[SPHERES]); fp.prev_spheres = static_cast<const rt_sphere*>(dev[PREV_SPHERES]);
         fp.media = static_cast<const rt_medium*>(dev[MEDIA]);
@@ -2232,7 +2241,13 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
             ip.instances = static_cast<const rt_instance*>(dev[INSTANCES]); ip.prev_instances = static_cast<const rt_instance*>(dev[PREV_INSTANCES]);
             ip.inst = iptr(INST); ip.prev_inst = iptr(PREV_INST);
             ip.n_instances = im->n_instances;
-            HIPCHK(rt_launch_reproject_instances(normals_on, motion_on, rp, ip, stream));
+            if (qm) {
+                qp.quads = static_cast<const rt_quad*>(dev[QUADS]); qp.prev_quads = static_cast<const rt_quad*>(dev[PREV_QUADS]);
+                qp.n_quads = qm->n_quads;
+                HIPCHK(rt_launch_reproject_quads(normals_on, motion_on, rp, qp, stream));
+            } else {
+                HIPCHK(rt_launch_reproject_instances(normals_on, motion_on, rp, ip, stream));
+            }
         } else {
             HIPCHK(rt_launch_reproject_moving(normals_on, motion_on, rp, fp, stream));
         }
@@ -2248,19 +2263,27 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
 }  // namespace
 
 rt_status rt_reproject(const rt_reproject_desc* d, int buffers_on_device, void* stream_v, int blocking) {
-    return reproject_impl(d, nullptr, nullptr, "rt_reproject", buffers_on_device, stream_v, blocking);
+    return reproject_impl(d, nullptr, nullptr, nullptr, "rt_reproject", buffers_on_device, stream_v, blocking);
 }
 
 rt_status rt_reproject_moving(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, int buffers_on_device, void* stream_v, int blocking) {
     if (!m) return invalid("rt_reproject_moving: null motion description");
-    return reproject_impl(d, m, nullptr, "rt_reproject_moving", buffers_on_device, stream_v, blocking);
+    return reproject_impl(d, m, nullptr, nullptr, "rt_reproject_moving", buffers_on_device, stream_v, blocking);
 }
 
 rt_status rt_reproject_instances(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, const rt_reproject_instance_desc* im,
                                  int buffers_on_device, void* stream_v, int blocking) {
     if (!m) return invalid("rt_reproject_instances: null motion description");
     if (!im) return invalid("rt_reproject_instances: null instance description");
-    return reproject_impl(d, m, im, "rt_reproject_instances", buffers_on_device, stream_v, blocking);
+    return reproject_impl(d, m, im, nullptr, "rt_reproject_instances", buffers_on_device, stream_v, blocking);
+}
+
+rt_status rt_reproject_quads(const rt_reproject_desc* d, const rt_reproject_motion_desc* m, const rt_reproject_instance_desc* im,
+                             const rt_reproject_quad_desc* qm, int buffers_on_device, void* stream_v, int blocking) {
+    if (!m) return invalid("rt_reproject_quads: null motion description");
+    if (!im) return invalid("rt_reproject_quads: null instance description");
+    if (!qm) return invalid("rt_reproject_quads: null quad description");
+    return reproject_impl(d, m, im, qm, "rt_reproject_quads", buffers_on_device, stream_v, blocking);
 }
 
 // Tail hand-off of the last frame (diagnostics, every build): [0] pixels the main kernel handed to the tail launches, summed over

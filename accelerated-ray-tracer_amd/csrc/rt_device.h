@@ -466,6 +466,13 @@ struct rt_reproject_follow_instance_params : rt_reproject_follow_params {
     int32_t n_instances, pad;
 };
 hipError_t rt_launch_reproject_instances(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_instance_params& ip, hipStream_t st);
+// rt_reproject_quads: the fourth form -- the instance form (n_instances may be 0) and, beside it, the quad records of both frames
+struct rt_reproject_follow_quad_params : rt_reproject_follow_instance_params {
+    const rt_quad* quads;        // n_quads records of the current frame
+    const rt_quad* prev_quads;   // ... and of the previous frame, same order
+    int32_t n_quads, pad_q;
+};
+hipError_t rt_launch_reproject_quads(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_quad_params& qp, hipStream_t st);
 
 // rt_scene_update_spheres (rt_kernel_refit.hip; include/rt_abi.h): the moved spheres' records, their leaves'
 // boxes in every array that holds them, the per-64-leaf unions, the scene's coordinate bound and every interior box of both

@@ -25,6 +25,14 @@
 // moved instance has its point and, with normals on, its normal taken through the current record's world -> object map and the
 // previous record's object -> world map.  The twelve other instantiations are again what they were.
 //
+// rt_reproject_quads ("temporal reprojection that follows moved quads and boxes") passes a fourth form, the
+// instance form extended by the quad records of both frames.  A surface pixel whose prim is a quad of the tables (a face of a box
+// is one) and whose inst is none or in range loads the two 80-byte quad records and, under an instance, the two instance records,
+// all issued together: still one round trip, and such a pixel needs no medium record.  When Q, u or v differ the point goes into
+// object space by the current instance record (moved or not), onto the previous record's plane through its planar coordinates
+// in the current one, and out by the previous instance record; its normal becomes the previous record's n, on the side the pixel
+// saw.  Every line of that sits under if constexpr (QUA); the sixteen other instantiations are again what they were.
+//
 // The arithmetic is the contract's, statement by statement (-ffp-contract=off: no FMA is formed).
 //
 // Bounds.  The pixel's own index is tested against the frame before any address is formed.  A tap address is formed only from
@@ -36,6 +44,7 @@
 // address from data: media[index] after index < n_media and spheres[k] / prev_spheres[k] after k < n_spheres, both compared
 // unsigned; what the records hold is only ever arithmetic.  The instance form adds instances[i] / prev_instances[i] after
 // i < n_instances, compared unsigned, and inst / prev_inst at the pixel and tap indices bounded above; flag bits are only tested.
+// The quad form adds quads[g] / prev_quads[g] after g < n_quads, compared unsigned.
 #include "rt_device.h"
 #include "rt_launch.h"
 
@@ -50,14 +59,19 @@ __device__ __forceinline__ const rt_reproject_follow_params& follow_tables(const
 __device__ __forceinline__ const rt_reproject_follow_instance_params& instance_tables(const rt_reproject_follow_instance_params& ip) { return ip; }
 template <class... Follow> struct follows_instances { static constexpr bool value = false; };
 template <> struct follows_instances<rt_reproject_follow_instance_params> { static constexpr bool value = true; };
+template <> struct follows_instances<rt_reproject_follow_quad_params> { static constexpr bool value = true; };
+__device__ __forceinline__ const rt_reproject_follow_quad_params& quad_tables(const rt_reproject_follow_quad_params& qp) { return qp; }
+template <class... Follow> struct follows_quads { static constexpr bool value = false; };
+template <> struct follows_quads<rt_reproject_follow_quad_params> { static constexpr bool value = true; };
 
 // rt_reproject launches <NRM, IDS, MOT> with no second argument.  rt_reproject_moving passes its tables as one: FOL, step 1 gains
 // its tail (a surface pixel on a sphere whose record changed is carried back to where that surface point was) and prim[p] is read
 // whatever IDS says.  rt_reproject_instances passes rt_reproject_follow_instance_params: INS, the tail looks for an instance first
-// and a tap must also show the pixel's inst.
+// and a tap must also show the pixel's inst.  rt_reproject_quads passes rt_reproject_follow_quad_params: INS and QUA, a pixel on
+// a quad of the tables takes the quad path, which shares the instance path's two maps.
 template <bool NRM, bool IDS, bool MOT, class... Follow>
 __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_reproject_params rp, Follow... follow) {
-    constexpr bool FOL = sizeof...(Follow) > 0, INS = follows_instances<Follow...>::value;
+    constexpr bool FOL = sizeof...(Follow) > 0, INS = follows_instances<Follow...>::value, QUA = follows_quads<Follow...>::value;
     const int tid = threadIdx.x;
     const int nx = rp.nx, ny = rp.ny;
     const unsigned by = blockIdx.x / (unsigned)rp.tiles_x, bx = blockIdx.x - by * (unsigned)rp.tiles_x;
@@ -110,12 +124,46 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                         if (insp < 0 && b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_INSTANCE) ii = (unsigned)b & 0x0FFFFFFFu;
                     }
                 }
-                if (ii < (unsigned)ip.n_instances) {
+                bool ipath = ii < (unsigned)ip.n_instances;
+                // 1a''. which quad: the pixel's own prim, when the tables hold it and its inst is none or in range (a quad's prim
+                // is no medium, so ii is inst[p] or none here).  Such a pixel takes this block with or without an instance.
+                bool qpath = false;
+                unsigned g = 0;
+                if constexpr (QUA) {
+                    if (idp >= 0 && ((unsigned)idp >> 28) == (unsigned)RT_PRIM_QUAD) {
+                        g = (unsigned)idp & 0x0FFFFFFFu;
+                        qpath = g < (unsigned)quad_tables(follow...).n_quads && (insp < 0 || ipath);
+                    }
+                }
+                if (ipath || qpath) {
                     k = 0xFFFFFFFFu;
                     // 1b'. both records' loads are issued together; only their floats and flag bits are used
-                    const rt_instance I = ip.instances[ii], J = ip.prev_instances[ii];
-                    const bool moved = I.sin_t != J.sin_t || I.cos_t != J.cos_t || I.offset[0] != J.offset[0] || I.offset[1] != J.offset[1] ||
-                                       I.offset[2] != J.offset[2] || I.flags != J.flags;
+                    rt_instance I, J;
+                    if constexpr (QUA) {   // 1b''. ... and with them the two quad records of a quad pixel
+                        I.sin_t = I.cos_t = I.offset[0] = I.offset[1] = I.offset[2] = 0.f; I.flags = 0;
+                        J = I;
+                        if (ipath) { I = ip.instances[ii]; J = ip.prev_instances[ii]; }
+                    } else {
+                        I = ip.instances[ii]; J = ip.prev_instances[ii];
+                    }
+                    float GQ[3] = {}, Gu[3] = {}, Gv[3] = {}, Gw[3] = {}, Gn[3] = {}, HQ[3] = {}, Hu[3] = {}, Hv[3] = {}, Hn[3] = {};
+                    bool qmoved = false;
+                    if constexpr (QUA) {
+                        if (qpath) {
+                            const rt_quad* G = quad_tables(follow...).quads + g;
+                            const rt_quad* H = quad_tables(follow...).prev_quads + g;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {
+                                GQ[c] = G->Q[c]; Gu[c] = G->u[c]; Gv[c] = G->v[c]; Gw[c] = G->w[c]; HQ[c] = H->Q[c]; Hu[c] = H->u[c]; Hv[c] = H->v[c];
+                                if (NRM) { Gn[c] = G->n[c]; Hn[c] = H->n[c]; }
+                            }
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) qmoved = qmoved || GQ[c] != HQ[c] || Gu[c] != Hu[c] || Gv[c] != Hv[c];
+                        }
+                    }
+                    bool moved = I.sin_t != J.sin_t || I.cos_t != J.cos_t || I.offset[0] != J.offset[0] || I.offset[1] != J.offset[1] ||
+                                 I.offset[2] != J.offset[2] || I.flags != J.flags;
+                    if constexpr (QUA) moved = moved || qmoved;
                     if (moved) {   // 1c'. world -> object by the current record, object -> previous world by the previous one
                         float A[3] = {P[0], P[1], P[2]};
                         if (I.flags & RT_INST_TRANSLATE) {
@@ -126,6 +174,17 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                         if (I.flags & RT_INST_ROTATE_Y) {
                             B[0] = I.cos_t * A[0] - I.sin_t * A[2];
                             B[2] = I.sin_t * A[0] + I.cos_t * A[2];
+                        }
+                        if constexpr (QUA) {
+                            if (qmoved) {   // 1c''. onto the previous record's plane by the planar coordinates in the current one
+                                const float h[3] = {B[0] - GQ[0], B[1] - GQ[1], B[2] - GQ[2]};
+                                const float x[3] = {h[1] * Gv[2] - h[2] * Gv[1], h[2] * Gv[0] - h[0] * Gv[2], h[0] * Gv[1] - h[1] * Gv[0]};
+                                const float y[3] = {Gu[1] * h[2] - Gu[2] * h[1], Gu[2] * h[0] - Gu[0] * h[2], Gu[0] * h[1] - Gu[1] * h[0]};
+                                const float alpha = dot3(Gw[0], Gw[1], Gw[2], x[0], x[1], x[2]);
+                                const float beta = dot3(Gw[0], Gw[1], Gw[2], y[0], y[1], y[2]);
+#pragma unroll
+                                for (int c = 0; c < 3; ++c) B[c] = (HQ[c] + alpha * Hu[c]) + beta * Hv[c];
+                            }
                         }
                         float Cc[3] = {B[0], B[1], B[2]};
                         if (J.flags & RT_INST_ROTATE_Y) {
@@ -143,6 +202,12 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                             if (I.flags & RT_INST_ROTATE_Y) {
                                 bx = I.cos_t * npx - I.sin_t * npz;
                                 bz = I.sin_t * npx + I.cos_t * npz;
+                            }
+                            if constexpr (QUA) {
+                                if (qmoved) {   // the previous record's normal, on the side the pixel saw and of its length
+                                    const float side = dot3(bx, npy, bz, Gn[0], Gn[1], Gn[2]);
+                                    bx = side * Hn[0]; npy = side * Hn[1]; bz = side * Hn[2];
+                                }
                             }
                             npx = bx; npz = bz;
                             if (J.flags & RT_INST_ROTATE_Y) {
@@ -283,6 +348,12 @@ hipError_t launch_instances(const rt_reproject_params& rp, const rt_reproject_fo
     const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
     return rt_launch_kernel(rt_reproject_kernel<NRM, true, MOT, rt_reproject_follow_instance_params>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, ip);
 }
+// rt_reproject_quads: likewise, with the quad form
+template <bool NRM, bool MOT>
+hipError_t launch_quads(const rt_reproject_params& rp, const rt_reproject_follow_quad_params& qp, hipStream_t st) {
+    const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
+    return rt_launch_kernel(rt_reproject_kernel<NRM, true, MOT, rt_reproject_follow_quad_params>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, qp);
+}
 template <bool NRM, bool IDS>
 hipError_t launch_motion(bool motion_on, const rt_reproject_params& rp, hipStream_t st) {
     return motion_on ? launch<NRM, IDS, true>(rp, st) : launch<NRM, IDS, false>(rp, st);
@@ -303,4 +374,9 @@ hipError_t rt_launch_reproject_moving(bool normals_on, bool motion_on, const rt_
 hipError_t rt_launch_reproject_instances(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_instance_params& ip, hipStream_t st) {
     if (normals_on) return motion_on ? launch_instances<true, true>(rp, ip, st) : launch_instances<true, false>(rp, ip, st);
     return motion_on ? launch_instances<false, true>(rp, ip, st) : launch_instances<false, false>(rp, ip, st);
+}
+
+hipError_t rt_launch_reproject_quads(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_quad_params& qp, hipStream_t st) {
+    if (normals_on) return motion_on ? launch_quads<true, true>(rp, qp, st) : launch_quads<true, false>(rp, qp, st);
+    return motion_on ? launch_quads<false, true>(rp, qp, st) : launch_quads<false, false>(rp, qp, st);
 }

@@ -9,7 +9,8 @@
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
 //             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K] [--denoise-variance [B]]] [--list]
 //             [--aov-through PREFIX] [--through-bounces N] [--through-fuzz F] [--denoise-through]
-//             [--orbit FRAMES DEGREES --out PREFIX [--temporal] [--bounce HEIGHT] [--spin DEGREES [--follow-instances]]]
+//             [--orbit FRAMES DEGREES --out PREFIX [--temporal] [--bounce HEIGHT] [--spin DEGREES [--follow-instances]]
+//                                                  [--grow AMOUNT [--follow-quads]]]
 //
 // --orbit FRAMES DEGREES renders a turntable: FRAMES frames of one device scene, the scene's lookfrom rotated about the vertical
 // axis through its lookat in equal steps of DEGREES / FRAMES (frame k at k steps; every other camera argument kept), each
@@ -31,6 +32,16 @@
 // instances: rt_render_aov's inst plane is kept with each frame, the instance records are read back after the update
 // (rt_scene_get_instances), and from the second frame on the history comes from rt_reproject_instances with the records and inst
 // planes of this frame and of the previous one (no sphere table, the scene's media, the binding's default times).
+// --grow AMOUNT (only with --orbit; AMOUNT finite, |AMOUNT| < 1) changes the height of the boxes: before frame k every box of the
+// description is rebuilt by the host library's make_box(a, b', material of its first face) and sent through
+// rt_scene_update_quads, where a and b are the per-axis min / max over the corners Q, Q + u, Q + v, (Q + u) + v of its six
+// original faces, b' = b on x and z and
+//   b'.y = (float)((double)a.y + ((double)b.y - a.y) * (1 + AMOUNT * sin(2 pi k / FRAMES)))
+// (in double, libm's sin).  A scene without a box is refused, and so is --temporal: the plain accumulation does not follow a box
+// that changes size.
+// --follow-quads (only with --orbit ... --grow) turns the accumulation on and lets it follow the faces: the quad records are read
+// back after the update (rt_scene_get_quads), the inst plane and the instance records are kept as --follow-instances keeps them,
+// and from the second frame on the history comes from rt_reproject_quads.  It combines with --spin ... --follow-instances.
 //
 // --denoise [K] filters the frame with rt_denoise (K iterations, 5 when K is left out; the binding's other defaults): the frame
 // is rendered at gamma 1, the feature pass (albedo, normal, depth at min(ns, 16) samples) guides the filter, and the frame's
@@ -64,6 +75,8 @@
 #include "../../include/rt_abi.h"
 #include "rtw_scenes.h"
 
+extern "C" int rtw_box_records(const float* a, const float* b, int mat, rt_quad* out6);   // librtw_host: the six faces of make_box(a, b)
+
 // checkCudaErrors (main.cu:23-35): message to stderr, exit code 99
 static void check(rt_status st, const char* what) {
     if (st == RT_OK) return;
@@ -83,8 +96,8 @@ int main(int argc, char** argv) {
     int min_spp = 0, denoise = 0, batches = -1;   // batches: -1 = no --denoise-variance, 0 = B left out
     int orbit_frames = 0;
     double orbit_degrees = 0.0;
-    bool temporal = false, bounce = false, spin = false, follow_instances = false;
-    double bounce_height = 0.0, spin_degrees = 0.0;
+    bool temporal = false, bounce = false, spin = false, follow_instances = false, grow = false, follow_quads = false;
+    double bounce_height = 0.0, spin_degrees = 0.0, grow_amount = 0.0;
     std::string out_prefix;
     unsigned long long seed = 1984ull;
     for (int a = 1; a < argc; ++a) {
@@ -143,6 +156,12 @@ int main(int argc, char** argv) {
             spin_degrees = strtod(val(), nullptr);
             if (!std::isfinite(spin_degrees)) { fprintf(stderr, "--spin DEGREES: DEGREES must be finite\n"); return 2; }
         }
+        else if (k == "--grow") {
+            grow = true;
+            grow_amount = strtod(val(), nullptr);
+            if (!std::isfinite(grow_amount) || !(fabs(grow_amount) < 1.0)) { fprintf(stderr, "--grow AMOUNT: AMOUNT must be finite and |AMOUNT| < 1\n"); return 2; }
+        }
+        else if (k == "--follow-quads") follow_quads = true;
         else if (k == "--list") { int n = 0; const char* const* v = rtw::scene_names(&n); for (int i = 0; i < n; ++i) printf("%s\n", v[i]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); return 2; }
     }
@@ -162,6 +181,9 @@ int main(int argc, char** argv) {
     if (orbit_frames == 0 && spin) { fprintf(stderr, "--spin needs --orbit\n"); return 2; }
     if (spin && temporal) { fprintf(stderr, "--spin cannot be combined with --temporal: the reprojection does not follow a moved instance\n"); return 2; }
     if (follow_instances && !spin) { fprintf(stderr, "--follow-instances needs --orbit FRAMES DEGREES --spin DEGREES: it accumulates the frames and follows the instances --spin turns\n"); return 2; }
+    if (orbit_frames == 0 && grow) { fprintf(stderr, "--grow needs --orbit\n"); return 2; }
+    if (grow && temporal) { fprintf(stderr, "--grow cannot be combined with --temporal: the plain accumulation does not follow a box that changes size (--follow-quads does)\n"); return 2; }
+    if (follow_quads && !grow) { fprintf(stderr, "--follow-quads needs --orbit FRAMES DEGREES --grow AMOUNT: it accumulates the frames and follows the faces of the boxes --grow resizes\n"); return 2; }
     if (orbit_frames > 0 && (gpus > 1 || progressive > 0 || adaptive || denoise || !aov_prefix.empty() || !through_prefix.empty())) {
         fprintf(stderr, "--orbit cannot be combined with --gpus > 1, --progressive, --adaptive, --denoise, --aov or --aov-through\n");
         return 2;
@@ -201,6 +223,8 @@ int main(int argc, char** argv) {
         if (!rotated) { fprintf(stderr, "--spin: scene '%s' has no rotated instance\n", scene_name.c_str()); return 2; }
     }
 
+    if (grow && flat.boxes.empty()) { fprintf(stderr, "--grow: scene '%s' has no box\n", scene_name.c_str()); return 2; }
+
     fprintf(stderr, "Rendering a %dx%d image in 8x8 blocks.\n", scene->nx, scene->ny);
     rt_frame_desc f;
     memset(&f, 0, sizeof(f));
@@ -221,18 +245,40 @@ int main(int argc, char** argv) {
         check(rt_init(device), "rt_init");
         check(rt_scene_create(&desc, &dev_scene), "rt_scene_create");
         const rtw::camera& c0 = *scene->cam;
-        const bool accumulate = temporal || follow_instances;
+        const bool accumulate = temporal || follow_instances || follow_quads, keep_inst = follow_instances || follow_quads;
         if (accumulate) f.gamma = 1.0f;
         struct features { std::vector<float> normal, depth, alpha; std::vector<int32_t> prim, inst; };
         features feat[2];
-        for (features& x : feat) { x.normal.resize(px * 3); x.depth.resize(px); x.alpha.resize(px); x.prim.resize(px); if (follow_instances) x.inst.resize(px); }
+        for (features& x : feat) { x.normal.resize(px * 3); x.depth.resize(px); x.alpha.resize(px); x.prim.resize(px); if (keep_inst) x.inst.resize(px); }
         std::vector<float> acc[2] = {std::vector<float>(px * 3), std::vector<float>(px * 3)}, len[2] = {std::vector<float>(px), std::vector<float>(px)};
         rt_camera prev_cam;
         memset(&prev_cam, 0, sizeof(prev_cam));
         std::vector<rt_sphere> records[2] = {flat.spheres, flat.spheres};   // --bounce: the records of this frame and of the previous one
         std::vector<rt_instance> inst_records[2] = {flat.instances, flat.instances};   // --follow-instances: likewise, as the scene holds them
+        std::vector<rt_quad> quad_records[2] = {flat.quads, flat.quads};   // --follow-quads: likewise
         double ms = 0.0;
         for (int k = 0; k < orbit_frames; ++k) {
+            if (grow) {
+                std::vector<rt_quad> now = flat.quads;
+                for (const rt_box& box : flat.boxes) {
+                    const rt_quad* face = &flat.quads[(size_t)box.first_quad];
+                    float lo[3], hi[3];
+                    for (int c = 0; c < 3; ++c) { lo[c] = INFINITY; hi[c] = -INFINITY; }
+                    for (int fc = 0; fc < 6; ++fc)
+                        for (int c = 0; c < 3; ++c) {
+                            const float qu = face[fc].Q[c] + face[fc].u[c];
+                            const float corner[4] = {face[fc].Q[c], qu, face[fc].Q[c] + face[fc].v[c], qu + face[fc].v[c]};
+                            for (float x : corner) { lo[c] = fminf(lo[c], x); hi[c] = fmaxf(hi[c], x); }
+                        }
+                    hi[1] = (float)((double)lo[1] + ((double)hi[1] - (double)lo[1]) * (1.0 + grow_amount * sin(2.0 * 3.14159265358979323846 * (double)k / (double)orbit_frames)));
+                    if (rtw_box_records(lo, hi, face[0].mat, &now[(size_t)box.first_quad]) != 0) { fprintf(stderr, "--grow: make_box failed\n"); return 1; }
+                }
+                rt_quad_update up;
+                memset(&up, 0, sizeof(up));
+                up.count = (int32_t)now.size(); up.first = 0; up.quads = now.data();
+                check(rt_scene_update_quads(dev_scene, &up, /*quads_on_device=*/0, /*recalibrate=*/0, /*stream=*/nullptr), "rt_scene_update_quads");
+                if (follow_quads) check(rt_scene_get_quads(dev_scene, quad_records[k & 1].data(), (int32_t)quad_records[k & 1].size()), "rt_scene_get_quads");
+            }
             if (bounce && !flat.spheres.empty()) {
                 std::vector<rt_sphere>& now = records[k & 1];
                 for (size_t i = 0; i < now.size(); ++i) {
@@ -256,7 +302,7 @@ int main(int argc, char** argv) {
                 memset(&up, 0, sizeof(up));
                 up.count = (int32_t)now.size(); up.first = 0; up.instances = now.data();
                 check(rt_scene_update_instances(dev_scene, &up, /*instances_on_device=*/0, /*recalibrate=*/0, /*stream=*/nullptr), "rt_scene_update_instances");
-                if (follow_instances) check(rt_scene_get_instances(dev_scene, inst_records[k & 1].data(), (int32_t)inst_records[k & 1].size()), "rt_scene_get_instances");
+                if (keep_inst) check(rt_scene_get_instances(dev_scene, inst_records[k & 1].data(), (int32_t)inst_records[k & 1].size()), "rt_scene_get_instances");
             }
             const double th = (double)k * orbit_degrees / (double)orbit_frames * 3.14159265358979323846 / 180.0;
             const double dx = (double)c0.lookfrom.x() - c0.lookat.x(), dz = (double)c0.lookfrom.z() - c0.lookat.z();
@@ -273,7 +319,7 @@ int main(int argc, char** argv) {
                 rt_aov_desc aov;
                 memset(&aov, 0, sizeof(aov));
                 aov.normal = cur.normal.data(); aov.depth = cur.depth.data(); aov.alpha = cur.alpha.data(); aov.prim = cur.prim.data();
-                if (follow_instances) aov.inst = cur.inst.data();
+                if (keep_inst) aov.inst = cur.inst.data();
                 check(rt_render_aov(dev_scene, &ff, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
                 rt_reproject_desc rd;
                 memset(&rd, 0, sizeof(rd));
@@ -286,7 +332,27 @@ int main(int argc, char** argv) {
                 }
                 rd.out = acc[k & 1].data(); rd.out_len = len[k & 1].data();
                 rd.alpha_min = 0.5f; rd.depth_tol = 0.05f; rd.normal_min = 0.5f; rd.max_history = 32.0f;   // the binding's REPROJECT_DEFAULTS
-                if (bounce && k) {   // the history follows the spheres that moved since the previous frame
+                if (follow_quads && k) {   // the history follows the faces that moved since the previous frame, and whatever else did
+                    rt_reproject_motion_desc md;
+                    memset(&md, 0, sizeof(md));
+                    if (bounce) {
+                        md.n_spheres = (int32_t)flat.spheres.size();
+                        md.spheres = md.n_spheres ? records[k & 1].data() : nullptr; md.prev_spheres = md.n_spheres ? records[(k + 1) & 1].data() : nullptr;
+                    }
+                    md.n_media = (int32_t)flat.media.size();
+                    md.media = md.n_media ? flat.media.data() : nullptr;
+                    md.time = (float)(0.5 * (cam.time0 + cam.time1)); md.prev_time = (float)(0.5 * (prev_cam.time0 + prev_cam.time1));
+                    rt_reproject_instance_desc id;
+                    memset(&id, 0, sizeof(id));
+                    id.n_instances = (int32_t)flat.instances.size();
+                    id.instances = id.n_instances ? inst_records[k & 1].data() : nullptr; id.prev_instances = id.n_instances ? inst_records[(k + 1) & 1].data() : nullptr;
+                    id.inst = cur.inst.data(); id.prev_inst = old.inst.data();
+                    rt_reproject_quad_desc qd;
+                    memset(&qd, 0, sizeof(qd));
+                    qd.n_quads = (int32_t)flat.quads.size();
+                    qd.quads = quad_records[k & 1].data(); qd.prev_quads = quad_records[(k + 1) & 1].data();
+                    check(rt_reproject_quads(&rd, &md, &id, &qd, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_reproject_quads");
+                } else if (bounce && k) {   // the history follows the spheres that moved since the previous frame
                     rt_reproject_motion_desc md;
                     memset(&md, 0, sizeof(md));
                     md.n_spheres = (int32_t)flat.spheres.size(); md.n_media = (int32_t)flat.media.size();

@@ -789,8 +789,8 @@ rt_status rt_refit_instances(const rt_scene_desc* desc, const rt_instance_update
  * child; and from boxes[..].first_quad with its mark bits masked -- all validated by rt_scene_create and never written from an
  * incoming record (the update writes bit 30 of first_quad only).
  *
- * What it does not do: rt_reproject and its followers do not follow a moved quad; their tap tests reject such pixels, which
- * then restart their history.
+ * What it does not do: rt_reproject, rt_reproject_moving and rt_reproject_instances do not follow a moved quad; their tap tests
+ * reject such pixels, which then restart their history.  rt_reproject_quads, below, follows it.
  * rt_scene_get_quads copies the records the next frame will use, pad0 zeroed (cap >= the scene's quad count, else
  * RT_ERR_INVALID).  rt_multi_update_quads applies host records to every replica of an rt_multi.  rt_refit_quads is the host-only
  * statement of D' (no device needed), as rt_refit_nodes: nodes_out receives desc->n_nodes nodes, quads_out desc->n_quads records
@@ -985,6 +985,64 @@ typedef struct rt_reproject_instance_desc {
 } rt_reproject_instance_desc;
 rt_status rt_reproject_instances(const rt_reproject_desc* d, const rt_reproject_motion_desc* m,
                                  const rt_reproject_instance_desc* im, int buffers_on_device, void* stream, int blocking);
+
+/* ---- temporal reprojection that follows moved quads and boxes ----
+ * rt_reproject_quads is rt_reproject_instances with one more rule: a surface pixel that shows a quad whose record changed between
+ * the two frames (rt_scene_update_quads) -- a free quad or a face of a box, in world space or under an instance -- is carried back
+ * to where that point of the quad was in the previous frame.  A quad maps onto its previous self by an affine map of its own
+ * plane: the point keeps its planar coordinates (alpha, beta), those of quad::hit, and is rebuilt from the previous record's Q, u
+ * and v.  A quad under an instance holds object-space records, so the carry happens between the two instance maps of
+ * rt_reproject_instances, whether or not the instance itself moved.  The stored normal changes with the record: the carried
+ * normal is the previous record's n, on the side of the quad the pixel saw.  A box follows face by face: prim names the face.
+ *
+ * m and im are required: m may hold no sphere and im no instance record, but im->inst stays required -- it says in whose object
+ * space a quad's record lives.  The numerical contract is rt_reproject_instances' (binary32, every written operation rounded
+ * once, nothing contracted, operands in the order written, only + - * / and comparisons; dot and cross as defined above) with
+ * this rule in front of step 1's tail (surface pixels only):
+ *   1a''. Which quad.  ref = prim[p].  If ref >= 0 and ref >> 28 == RT_PRIM_QUAD: g = ref & 0x0FFFFFFF.  The pixel takes the quad
+ *        path iff g < n_quads (compared unsigned, before any address is formed) and inst[p] < 0 or inst[p] < n_instances
+ *        (unsigned).  An inst[p] >= n_instances means object-space records of an instance the tables do not describe: such a
+ *        pixel does not take the quad path.  Every other pixel follows rt_reproject_instances' step 1 unchanged -- a pixel
+ *        whose prim is a medium included: a fog volume bounded by a quad, a box or an instance of one does not say which face
+ *        a scattering point belongs to.
+ *   1b''. Moved.  G = quads[g], G' = prev_quads[g].  qmoved = any component of Q, u or v compares != (a NaN compares as moved;
+ *        D, w, n, mat and the pads do not enter).  With an instance i = inst[p] in range, imoved is the `moved` of 1b'.  Neither: the
+ *        pixel's q and normal are rt_reproject's, bit for bit.  imoved only: step 1c', bit for bit.
+ *   1c''. The carry, when qmoved.  B is the object-space point: with i in range, A and B of 1c' by the current record I (applied
+ *        whether or not the instance moved); otherwise B = P.
+ *        h.c = B.c - G.Q.c;  x = cross(h, G.v);  y = cross(G.u, h);  alpha = dot(G.w, x);  beta = dot(G.w, y)  (not clamped).
+ *        B'.c = (G'.Q.c + alpha G'.u.c) + beta G'.v.c.
+ *        With i in range P' comes from B' by the previous record I' (C and P' of 1c' with B' in B's place); otherwise P' = B'.
+ *        q.c = P'.c - O'.c.
+ *        With normals on: Nb = normal[p] through I's rotation (B of 1c' with N in A's place; normal[p] itself with no instance),
+ *        s = dot(Nb, G.n), Nb'.c = s G'.n.c -- the side of the quad the pixel saw and its sample-averaged length -- and Nb'
+ *        goes through the previous record's rotation (C of 1c') before step 3 tests it.
+ *        A non-finite record yields a non-finite q, which step 2 ends with no history.  A zero w yields P' = G'.Q: finite,
+ *        wrong and harmless.
+ *   3.   rt_reproject_instances': the prim and inst tests are always on, so a tap must show the same quad of the same instance.
+ * So with n_quads == 0, or with tables in which no record differs in Q, u or v, the outputs are rt_reproject_instances' bit for
+ * bit, and by that entry's identities rt_reproject_moving's and rt_reproject's.  tests/reproject_quads_expect.py restates this in
+ * NumPy; the device result equals it bit for bit.
+ * Limits.  Media are not followed by this rule.  A quad's normal is oriented to face the ray, and that orientation can flip
+ * between two frames: the normal test then rejects the tap.  Reflections of a moved quad in other surfaces are not followed.
+ * The centre ray ignores the lens and the shutter, as before.  The carry is exact for points of the quad's plane; for a depth
+ * that is a mean over samples it is the projection along n.
+ * Memory safety.  The only data-derived addresses that are added are quads[g] and prev_quads[g], formed after the unsigned
+ * compare against n_quads.  Nothing loaded from a record reaches an address; no value in any buffer or table makes the call
+ * fault.
+ *
+ * Parameters: everything rt_reproject_instances refuses, and a null qm, a negative n_quads or one of 2^28 or more, n_quads > 0
+ * with a null quads or prev_quads, and an output that overlaps one of the two tables are RT_ERR_INVALID before any HIP call;
+ * rt_last_error_detail() names the check and starts with "rt_reproject_quads".  The tables obey buffers_on_device like every
+ * other buffer; host memory is staged, and a table whose count is 0 is not looked at.  Stream and blocking: rt_reproject's rules. */
+typedef struct rt_reproject_quad_desc {
+    int32_t n_quads, reserved;
+    const rt_quad* quads;        /* records the CURRENT frame was rendered with (rt_scene_get_quads) */
+    const rt_quad* prev_quads;   /* records the PREVIOUS frame was rendered with, same count and order */
+} rt_reproject_quad_desc; /* 24 B */
+rt_status rt_reproject_quads(const rt_reproject_desc* d, const rt_reproject_motion_desc* m,
+                             const rt_reproject_instance_desc* im, const rt_reproject_quad_desc* qm,
+                             int buffers_on_device, void* stream, int blocking);
 
 /* ---- several GPUs of one node from one host thread ----
  * The reference is single-GPU (one render<<<>>> launch, main.cu:707); these entry points are what its host function

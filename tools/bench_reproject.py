@@ -27,6 +27,12 @@ times rt_reproject_moving (no sphere table, the scene's media) and rt_reproject_
 same buffers -- with `none` the tables hold the second frame's records twice (every instance pixel takes the static path after the
 records were read), with `all` the records of both frames.  It exits after the loop; --kernel-stats FILE --moved X --instances
 then appends the two kernels' rows and their ratio.
+--quads-loop N --moved {none,all} [--scene NAME] is the quad mode (rt_reproject_quads, profiles/reproject_quads_mi355x.jsonl): a
+scene with boxes (default cornell) at 1200 x 800 under its own camera and one 3 degrees further round, the second frame rendered
+after every box was made a fifth taller through update_quads; N times rt_reproject_instances (no sphere table, the scene's media,
+the scene's unmoved instance records) and rt_reproject_quads with every guide, alternating, on those same buffers -- with `none`
+the quad tables hold the second frame's records twice, with `all` the records of both frames.  It exits after the loop;
+--kernel-stats FILE --moved X --quads then appends the two kernels' rows and their ratio.
 --orbit-pair N is the stale prior in an animation loop: ONE scene, its camera switched between the 0 and the 20 degree view
 (recalibrate 0) before every frame, 2 N + 2 frames, the first two left out.  Since the cost map a scene that
 renders one view again runs warm, one-part frames, so (b)'s three scenes no longer show what a stale prior costs; here every
@@ -168,6 +174,78 @@ def instances_loop(args, dev):
     hs.close()
 
 
+def box_firsts(quads):
+    """The first quad of every six consecutive records that are the faces of one axis-aligned box in make_box's order."""
+    axis = [int(np.flatnonzero(q["n"])[0]) if np.count_nonzero(q["n"]) == 1 else -1 for q in quads]
+    return [f for f in range(len(quads) - 5) if axis[f:f + 6] == [2, 0, 2, 0, 1, 1] and len(set(quads["mat"][f:f + 6].tolist())) == 1]
+
+
+def grown_boxes(quads, factor):
+    """`quads` with every box rebuilt by the host library's make_box at `factor` times its height (rayTracer --grow's rule)."""
+    rec = quads.copy()
+    for f in box_firsts(quads):
+        six = quads[f:f + 6]
+        corners = np.concatenate([six["Q"], six["Q"] + six["u"], six["Q"] + six["v"], (six["Q"] + six["u"]) + six["v"]])
+        a, b = corners.min(axis=0), corners.max(axis=0)
+        b[1] = np.float32(float(a[1]) + (float(b[1]) - float(a[1])) * factor)
+        rec[f:f + 6] = art.box_records(a, b, int(six["mat"][0]))
+    return rec
+
+
+def quads_loop(args, dev):
+    """The quad mode: see the module's text."""
+    nx, ny = args.nx, args.ny
+    hs = art.HostScene(args.scene, nx, ny)
+    ds = art.DeviceScene(hs)
+    f4 = hs.frame(nx=nx, ny=ny, ns=4, gamma=1.0)
+    built = art.RtCamera.from_buffer_copy(hs.desc.camera)
+    if args.scene.startswith("cornell"):
+        th = np.radians(3.0)
+        d = np.subtract(CORNELL_EYE, CORNELL_LOOKAT)
+        eye = np.add(CORNELL_LOOKAT, (np.cos(th) * d[0] + np.sin(th) * d[2], d[1], -np.sin(th) * d[0] + np.cos(th) * d[2]))
+        cams = [built, art.make_camera(eye, CORNELL_LOOKAT, (0, 1, 0), 40.0, nx / ny, 0.0, 800.0, 0.0, 1.0)]
+    else:
+        cams = [built, built]
+    before = ds.quads()
+    after = grown_boxes(before, 1.2)
+    faces = [q for f in box_firsts(before) for q in range(f, f + 6)]
+    host = []
+    for k, cam in enumerate(cams):
+        if k:
+            ds.update_quads(after)
+            after = ds.quads()
+        ds.set_camera(cam)
+        color, _ = ds.render(f4)
+        host.append(dict(ds.render_aov(f4, ids=True), color=color))
+    t = [{k: torch.from_numpy(v).to(dev) for k, v in h.items()} for h in host]
+    words = lambda rec: torch.from_numpy(np.ascontiguousarray(rec).view(np.int32).reshape(len(rec), -1).copy()).to(dev)   # noqa: E731
+    cur_records, prev_records = words(after), words(before if args.moved == "all" else after)
+    instances = words(ds.instances())
+    media = words(hs.media()) if len(hs.media()) else None
+    first = art.reproject(t[0]["color"], t[0]["depth"], t[0]["alpha"], cams[0], cams[0])
+    out, out_len = torch.empty_like(first.out), torch.empty_like(first.length)
+    motion = torch.empty((ny, nx, 2), dtype=torch.float32, device=dev)
+    kw = dict(history=first.out, history_len=first.length, prev_depth=t[0]["depth"], prev_alpha=t[0]["alpha"], out=out, out_len=out_len,
+              stream=torch.cuda.current_stream(dev).cuda_stream, blocking=False, normal=t[1]["normal"], prim=t[1]["prim"],
+              prev_normal=t[0]["normal"], prev_prim=t[0]["prim"], motion=motion, media=media, instances=instances, prev_instances=instances,
+              inst=t[1]["inst"], prev_inst=t[0]["inst"])
+    prim = host[1]["prim"].astype(np.int64)
+    on_faces = (prim >= 0) & ((prim >> 28) == art.RT_PRIM_QUAD) & np.isin(prim & 0x0FFFFFFF, faces) & (host[1]["alpha"] >= 0.5)
+    sel = torch.from_numpy(on_faces).to(dev)
+    for _ in range(args.quads_loop):
+        art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], **kw)
+        inst_found, inst_on = float((out_len > 1).float().mean().item()), float((out_len[sel] > 1).float().mean().item())
+        art.reproject(t[1]["color"], t[1]["depth"], t[1]["alpha"], cams[1], cams[0], quads=cur_records, prev_quads=prev_records, **kw)
+        quad_found, quad_on = float((out_len > 1).float().mean().item()), float((out_len[sel] > 1).float().mean().item())
+    torch.cuda.synchronize()
+    print(json.dumps({"what": "rt_reproject_quads loop", "scene": args.scene, "quads_moved": args.moved, "calls_each": args.quads_loop,
+                      "quads": int(len(before)), "box_faces": len(faces), "pixels_on_box_faces": round(float(on_faces.mean()), 4),
+                      "pixels_with_history_instances": round(inst_found, 4), "pixels_with_history_quads": round(quad_found, 4),
+                      "of_box_face_pixels_instances": round(inst_on, 4), "of_box_face_pixels_quads": round(quad_on, 4)}))
+    ds.close()
+    hs.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nx", type=int, default=1200)
@@ -182,6 +260,8 @@ def main():
     ap.add_argument("--orbit-pair", type=int, default=0)
     ap.add_argument("--instances-loop", type=int, default=0)
     ap.add_argument("--instances", action="store_true", help="with --kernel-stats: the instance mode's two kernels")
+    ap.add_argument("--quads-loop", type=int, default=0)
+    ap.add_argument("--quads", action="store_true", help="with --kernel-stats: the quad mode's two kernels")
     ap.add_argument("--scene", default="cornell")
     args = ap.parse_args()
     nx, ny = args.nx, args.ny
@@ -196,7 +276,13 @@ def main():
                         "calls": int(r["Calls"]), "average_us": round(float(r["AverageNs"]) / 1e3, 3), "min_us": round(float(r["MinNs"]) / 1e3, 3),
                         "max_us": round(float(r["MaxNs"]) / 1e3, 3)}
         line = {"what": "device time per kernel (rocprofv3 --kernel-trace --stats)", "nx": nx, "ny": ny, "kernels": rows}
-        if args.moved and args.instances:
+        if args.moved and args.quads:
+            instances = rows.get("rt_reproject_kernel<true, true, true, rt_reproject_follow_instance_params>")
+            following = rows.get("rt_reproject_kernel<true, true, true, rt_reproject_follow_quad_params>")
+            line["quads_moved"], line["scene"] = args.moved, args.scene
+            if instances and following:
+                line["quads_over_instances"] = round(following["average_us"] / instances["average_us"], 4)
+        elif args.moved and args.instances:
             moving = rows.get("rt_reproject_kernel<true, true, true, rt_reproject_follow_params>")
             following = rows.get("rt_reproject_kernel<true, true, true, rt_reproject_follow_instance_params>")
             line["instances_moved"], line["scene"] = args.moved, args.scene
@@ -217,6 +303,9 @@ def main():
     dev = torch.device("cuda", 0)
     if args.instances_loop:
         instances_loop(args, dev)
+        return
+    if args.quads_loop:
+        quads_loop(args, dev)
         return
     hs = art.HostScene("random_scene", nx, ny)
     lines = []
