@@ -2462,6 +2462,44 @@ rt_status rt_debug_box_tests(int32_t n, const float* bmin, const float* bmax, co
     return RT_OK;
 }
 
+rt_status rt_debug_arith_tests(int32_t mode, int64_t n, const float* a, const float* b, const float* bound3, uint8_t* path, uint64_t* out3) {
+    if (mode < RT_ARITH_UNIFORM || mode > RT_ARITH_LOOSE) return invalid("rt_debug_arith_tests: unknown mode");
+    const bool draws = mode == RT_ARITH_UNIFORM || mode == RT_ARITH_SIGNED;
+    if (!out3 || (!draws && (!a || !b || !bound3))) return invalid("rt_debug_arith_tests: null argument");
+    if (draws && path) return invalid("rt_debug_arith_tests: the draw modes report no path");
+    if (draws ? (n < 1 || n > (1ll << 32)) : (n < 1 || n > (1 << 24))) return invalid(draws ? "rt_debug_arith_tests: n must be 1 .. 2^32" : "rt_debug_arith_tests: n must be 1 .. 2^24");
+    if (!draws)
+        for (int k = 0; k < 3; ++k)
+            if (!(bound3[k] >= 0.f) || !std::isfinite(bound3[k])) return invalid("rt_debug_arith_tests: bound3 must be finite and not negative");
+    RT_TRY(use_device(g_device));
+    rt_arith_test_params ap;
+    memset(&ap, 0, sizeof(ap));
+    ap.mode = mode; ap.n = n;
+    call_memory mem;
+    if (!draws) {
+        for (int k = 0; k < 3; ++k) ap.bound[k] = bound3[k];
+        const size_t n3 = (size_t)n * 3 * sizeof(float);
+        HIPCHK(mem.get((void**)&ap.a, n3));
+        HIPCHK(hipMemcpy((void*)ap.a, a, n3, hipMemcpyHostToDevice));
+        HIPCHK(mem.get((void**)&ap.b, n3));
+        HIPCHK(hipMemcpy((void*)ap.b, b, n3, hipMemcpyHostToDevice));
+        if (path) {
+            HIPCHK(mem.get((void**)&ap.path, (size_t)n));
+            HIPCHK(hipMemset(ap.path, 0xFF, (size_t)n));   // a case the kernel skipped would show as 255
+        }
+    }
+    const unsigned long long init[3] = {0ull, ~0ull, 0ull};
+    HIPCHK(mem.get((void**)&ap.out, sizeof(init)));
+    HIPCHK(hipMemcpy(ap.out, init, sizeof(init), hipMemcpyHostToDevice));
+    HIPCHK(rt_launch_arith_tests(ap, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long got[3];
+    HIPCHK(hipMemcpy(got, ap.out, sizeof(got), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k) out3[k] = got[k];
+    if (path) HIPCHK(hipMemcpy(path, ap.path, (size_t)n, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 rt_status rt_debug_cal_cost(rt_scene* s, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny) {
     if (!s) return invalid("rt_debug_cal_cost: null scene");
     if (!out || !nx || !ny) return invalid("rt_debug_cal_cost: null argument");

@@ -9,10 +9,10 @@
 #define RT_PERSISTENT_THREADS 512   // default workgroup size of the staged kernel
 // Register budgets of the staged kernel families, as launch bounds (threads per workgroup the code may be launched
 // with, waves per SIMD it must leave room for).  "Lean" = spheres-only scenes without procedural / image textures (the
-// headline kernel): 97 VGPRs (allocated in eights: 104), no scratch (profiles/r03_kernel_resources.md) -- the double-precision
+// headline kernel): 101 VGPRs (allocated in eights: 104), no scratch (profiles/r03_kernel_resources.md) -- the double-precision
 // transcendentals are out of line and the one-pixel-per-wave loops live in their own kernel (rt_kernel_tier.h).  It is launched
 // 2 x 512 threads per CU = 4 waves per SIMD: 4 x 104 registers leave 96 of a SIMD's 512 for one co-resident wave of the tier
-// kernel (76, allocated 80).  104 is therefore this kernel's ceiling, not the 128 the launch bounds would allow.
+// kernel (78, allocated 80).  104 is therefore this kernel's ceiling, not the 128 the launch bounds would allow.
 // Everything else (quads / boxes / media, Perlin / image textures) is budgeted 168 VGPRs: 3 waves per SIMD.
 #ifndef RT_LEAN_MIN_WAVES
 #define RT_LEAN_MIN_WAVES 4
@@ -214,6 +214,19 @@ struct rt_box_test_params {
     uint8_t* flags;
 };
 hipError_t rt_launch_box_tests(const rt_box_test_params& bp, hipStream_t st);
+// rt_debug_arith_tests (rt_kernel_arithtest.hip): device pointers; the modes are include/rt_abi.h's RT_ARITH_*.  The two draw
+// modes run words [0, n), RT_ARITH_WORDS_PER_THREAD a thread, and read no array; RT_ARITH_LOOSE runs one ray per thread
+#define RT_ARITH_WORDS_PER_THREAD 256u
+struct rt_arith_test_params {
+    int32_t mode;
+    long long n;
+    const float* a;
+    const float* b;
+    float bound[3];
+    uint8_t* path;                // [n], or null: RT_ARITH_LOOSE's finite_inv per ray
+    unsigned long long* out;      // [3], zeroed / ~0 / zeroed by the caller: mismatching cases, the first of them, rays with finite_inv
+};
+hipError_t rt_launch_arith_tests(const rt_arith_test_params& ap, hipStream_t st);
 // bytes of the tier kernel's LDS image (rt_kernel_tier.h stages exactly this): leaf arrays + slot unions, then -- where the
 // launch plan (rt_abi.hip) says so -- spheres, materials and textures
 static inline size_t rt_tier_lds_bytes(int n_slots, int n_spheres, int n_materials, int n_textures, bool scene) {

@@ -493,9 +493,9 @@ DEV f3 texture_value(const SceneView& sc, int tex, float u, float v, f3 p) {
 // ------------------------------------------------------------------ materials (material.cuh:10-201)
 DEV f3 random_in_unit_sphere(rt_xorwow& g) {
     for (;;) {
-        const float a = 2.0f * rt_xorwow_uniform(g) - 1.0f;
-        const float b = 2.0f * rt_xorwow_uniform(g) - 1.0f;
-        const float c = 2.0f * rt_xorwow_uniform(g) - 1.0f;
+        const float a = rt_xorwow_signed(g);   // 2.0f * curand_uniform - 1.0f
+        const float b = rt_xorwow_signed(g);
+        const float c = rt_xorwow_signed(g);
         const f3 p = mk3(a, b, c);
         if (dot(p, p) < 1.0f) return p;
     }
@@ -583,9 +583,9 @@ DEV bool shade(const SceneView& sc, const Ray& in, const HitRec& rec, rt_xorwow&
 DEV Ray camera_get_ray(const rt_camera& c, float s, float t, rt_xorwow& g) {
     f3 p;
     do {
-        const float a = rt_xorwow_uniform(g);
-        const float b = rt_xorwow_uniform(g);
-        p = 2.0f * mk3(a, b, 0.0f) - mk3(1.0f, 1.0f, 0.0f);
+        const float a = rt_xorwow_signed(g);
+        const float b = rt_xorwow_signed(g);
+        p = mk3(a, b, 0.0f);   // 2.0f * vec3(u0, u1, 0) - vec3(1, 1, 0): the z component is 2 * 0 - 0
     } while (dot(p, p) >= 1.0f);
     const f3 rd = c.lens_radius * p;
     const f3 cu = ld3(c.u), cv = ld3(c.v);
@@ -794,12 +794,14 @@ DEV bool loose_ok(const f3 inv, const f3 o, const float* bound) {
 }
 DEV LooseRay loose_setup(const f3 inv, const f3 o, const float* bound) {
     const float k = 9.5367431640625e-07f;   // 2^-20
-    const float ex = k * (fabsf(inv.x) * (fabsf(o.x) + bound[0])), ey = k * (fabsf(inv.y) * (fabsf(o.y) + bound[1])), ez = k * (fabsf(inv.z) * (fabsf(o.z) + bound[2]));
+    // x > 0: bmin gives the near bound (- e), bmax the far one (+ e); x < 0: the other way round.  The widening carries that
+    // sign itself: multiplication is sign-symmetric, so s = k * (x * (|o| + B)) is exactly e with the sign of x, and c - s,
+    // c + s are the values a select on x < 0 between c + e and c - e gives (rt_kernel_arithtest.hip keeps that form) -- no compare, no select.
+    const float sx = k * (inv.x * (fabsf(o.x) + bound[0])), sy = k * (inv.y * (fabsf(o.y) + bound[1])), sz = k * (inv.z * (fabsf(o.z) + bound[2]));
     const float cx = -(o.x * inv.x), cy = -(o.y * inv.y), cz = -(o.z * inv.z);
     LooseRay r;
-    // x > 0: bmin gives the near bound (- e), bmax the far one (+ e); x < 0: the other way round
-    r.clo = mk3(inv.x < 0.0f ? cx + ex : cx - ex, inv.y < 0.0f ? cy + ey : cy - ey, inv.z < 0.0f ? cz + ez : cz - ez);
-    r.chi = mk3(inv.x < 0.0f ? cx - ex : cx + ex, inv.y < 0.0f ? cy - ey : cy + ey, inv.z < 0.0f ? cz - ez : cz + ez);
+    r.clo = mk3(cx - sx, cy - sy, cz - sz);
+    r.chi = mk3(cx + sx, cy + sy, cz + sz);
     return r;
 }
 DEV bool slab_test_loose(const float4 lo_skip, const float4 hi_prim, const f3 inv, const LooseRay& lr, float tmin, float tmax) {

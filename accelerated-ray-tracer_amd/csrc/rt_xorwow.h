@@ -52,7 +52,32 @@ RT_HD uint32_t rt_xorwow_next(rt_xorwow& s) {
 
 // curand_uniform(&state): (0, 1].  Separate multiply and add (no FMA): the
 // whole path is built with -ffp-contract=off.
-RT_HD float rt_xorwow_uniform(rt_xorwow& s) {
-    const uint32_t x = rt_xorwow_next(s);
+// RT_DRAW_ONE_FMA (device code of the translation units that define it): the same float from one fma.  The two constants are
+// exactly 2^-32 and 2^-33, so the product (float)x * 2^-32 is exact and the fma's single rounding is the addition's
+// (tests/test_exact_arith.py runs all 2^32 words).  An fma takes its addend from a register where the multiply and the add
+// take 32-bit literals, so the form holds two more VGPRs for the four constants' sake: only the lean spheres-only kernels,
+// which have them to spare, define it (every other kernel would lose occupancy or spill, profiles/r03_kernel_resources.md).
+// The host side keeps the reference's two operations: the oracle must not share the device's form.
+#if defined(__HIP_DEVICE_COMPILE__) && defined(RT_DRAW_ONE_FMA)
+#define RT_DRAW_FMA_HERE 1
+#endif
+RT_HD float rt_uniform_from_word(uint32_t x) {
+#ifdef RT_DRAW_FMA_HERE
+    return __builtin_fmaf((float)x, 0x1p-32f, 0x1p-33f);
+#else
     return (float)x * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
+#endif
 }
+RT_HD float rt_xorwow_uniform(rt_xorwow& s) { return rt_uniform_from_word(rt_xorwow_next(s)); }
+
+// 2.0f * curand_uniform(&state) - 1.0f, the draw of the rejection loops (material.cuh:12-18, camera.cuh:36-40).  With
+// RT_DRAW_ONE_FMA 3 float instructions for 5: scaling by two commutes with rounding (nothing here is subnormal or overflows),
+// so 2u is the same fma with both constants doubled.
+RT_HD float rt_signed_from_word(uint32_t x) {
+#ifdef RT_DRAW_FMA_HERE
+    return __builtin_fmaf((float)x, 0x1p-31f, 0x1p-32f) - 1.0f;
+#else
+    return 2.0f * rt_uniform_from_word(x) - 1.0f;
+#endif
+}
+RT_HD float rt_xorwow_signed(rt_xorwow& s) { return rt_signed_from_word(rt_xorwow_next(s)); }

@@ -1113,6 +1113,19 @@ rt_status rt_debug_rank_info(rt_scene* scene, uint32_t* out13);
  * no scene; every argument check runs before any HIP call; null stream, synchronous. */
 rt_status rt_debug_box_tests(int32_t n, const float* bmin, const float* bmax, const float* origins, const float* directions,
                              const float* tmin, const float* tmax, const float* bound3, uint8_t* flags);
+/* diagnostics of the exact cheaper arithmetic (tests/test_exact_arith.py): each mode runs a helper of the render
+ * path and, inside the kernel, the plain expression it replaces, and compares the two bit for bit.
+ *   RT_ARITH_UNIFORM  words 0 .. n - 1 (n = 1 .. 2^32): the one-fma draw against (float)x * 2^-32 + 2^-33; reads no array
+ *   RT_ARITH_SIGNED   the same for the rejection loops' 2u - 1
+ *   RT_ARITH_LOOSE    the walk loop's loose_setup for rays a[n][3] (origins), b[n][3] (directions) and the scene bound bound3
+ *                     (finite, not negative) against its form with selects; compared where finite_inv holds.  n = 1 .. 2^24
+ * a, b, path are HOST buffers; the draw modes take them null.  path (RT_ARITH_LOOSE only, may be null) receives finite_inv per
+ * ray.  out3 = mismatching cases, index of the first of them (~0 when none), rays with finite_inv (0 for the draw modes).
+ * Needs rt_init and no scene; every argument check runs before any HIP call; null stream, synchronous. */
+#define RT_ARITH_UNIFORM 0
+#define RT_ARITH_SIGNED 1
+#define RT_ARITH_LOOSE 2
+rt_status rt_debug_arith_tests(int32_t mode, int64_t n, const float* a, const float* b, const float* bound3, uint8_t* path, uint64_t* out3);
 /* The cost map (option cost_map).  The last launches of a ranked frame leave, per local pixel, the rays the
  * pixel cost over all its samples.  A pixel's cost depends on the scene, the camera, the frame geometry and the row partition,
  * not on seed_base or ns, so the next ranked frame of the same scene uses the map once rt_frame_finish has closed the frame
