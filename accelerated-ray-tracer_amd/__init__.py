@@ -198,7 +198,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances",
                   "rt_debug_box_tests", "rt_reproject_instances",
                   "rt_scene_update_quads", "rt_scene_get_quads", "rt_refit_quads", "rt_multi_update_quads", "rt_debug_scene_quads",
-                  "rt_reproject_quads", "rt_debug_arith_tests"]
+                  "rt_reproject_quads", "rt_debug_arith_tests", "rt_debug_math_tests"]
 
 _rt = None
 _host = None
@@ -328,6 +328,8 @@ def rt_lib():
             L.rt_debug_box_tests.argtypes = [C.c_int32] + [C.c_void_p] * 8
         if hasattr(L, "rt_debug_arith_tests"):   # (likewise)
             L.rt_debug_arith_tests.argtypes = [C.c_int32, C.c_int64] + [C.c_void_p] * 5
+        if hasattr(L, "rt_debug_math_tests"):   # (likewise)
+            L.rt_debug_math_tests.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.c_int64, C.c_float] + [C.c_void_p] * 5
         L.rt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _rt = L
     return _rt

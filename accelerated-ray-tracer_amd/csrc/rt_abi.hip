@@ -2500,6 +2500,49 @@ rt_status rt_debug_arith_tests(int32_t mode, int64_t n, const float* a, const fl
     return RT_OK;
 }
 
+rt_status rt_debug_math_tests(int32_t form, int32_t fn, uint32_t first, int64_t count, float operand, const float* a, const float* b,
+                              const float* c, float* out, uint64_t* digests) {
+    if (form != RT_MATH_SWEEP && form != RT_MATH_LIST) return invalid("rt_debug_math_tests: unknown form");
+    if (fn < RT_MATH_LOG || fn > RT_MATH_MULADD) return invalid("rt_debug_math_tests: unknown function");
+    const bool sweep = form == RT_MATH_SWEEP;
+    const bool reads_b = fn == RT_MATH_ATAN2 || fn == RT_MATH_POW || fn == RT_MATH_DIV || fn == RT_MATH_MULADD, reads_c = fn == RT_MATH_MULADD;
+    if (sweep) {
+        if (reads_b && fn != RT_MATH_POW) return invalid("rt_debug_math_tests: a sweep takes a function of one input, or RT_MATH_POW");
+        if (!digests) return invalid("rt_debug_math_tests: null argument");
+        if (a || b || c || out) return invalid("rt_debug_math_tests: a sweep reads no array and writes digests only");
+        if (count < 1 || count > (1ll << 32) || (int64_t)first + count > (1ll << 32)) return invalid("rt_debug_math_tests: count must be 1 .. 2^32 and first + count at most 2^32");
+        if (fn == RT_MATH_POW && (!(operand > 0.f) || !std::isfinite(operand))) return invalid("rt_debug_math_tests: gamma must be finite and positive");
+    } else {
+        if (!a || !out || (reads_b && !b) || (reads_c && !c)) return invalid("rt_debug_math_tests: null argument");
+        if (digests) return invalid("rt_debug_math_tests: a list writes out only");
+        if (count < 1 || count > (1 << 24) || first != 0u) return invalid("rt_debug_math_tests: count must be 1 .. 2^24 and first 0");
+    }
+    RT_TRY(use_device(g_device));
+    rt_math_test_params mp;
+    memset(&mp, 0, sizeof(mp));
+    mp.form = form; mp.fn = fn; mp.first = first; mp.count = count; mp.operand = operand;
+    call_memory mem;
+    const size_t n_digests = (size_t)((count + (1ll << 20) - 1) >> 20), list_bytes = (size_t)count * sizeof(float);
+    if (sweep) {
+        HIPCHK(mem.get((void**)&mp.digests, n_digests * sizeof(unsigned long long)));
+        HIPCHK(hipMemset(mp.digests, 0, n_digests * sizeof(unsigned long long)));
+    } else {
+        const struct { const float** dev; const float* host; } in[] = {{&mp.a, a}, {&mp.b, reads_b ? b : nullptr}, {&mp.c, reads_c ? c : nullptr}};
+        for (const auto& v : in) {
+            if (!v.host) continue;
+            HIPCHK(mem.get((void**)v.dev, list_bytes));
+            HIPCHK(hipMemcpy((void*)*v.dev, v.host, list_bytes, hipMemcpyHostToDevice));
+        }
+        HIPCHK(mem.get((void**)&mp.out, list_bytes));
+        HIPCHK(hipMemset(mp.out, 0xFF, list_bytes));   // an element the kernel skipped would show as a NaN with payload
+    }
+    HIPCHK(rt_launch_math_tests(mp, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (sweep) HIPCHK(hipMemcpy(digests, mp.digests, n_digests * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    else HIPCHK(hipMemcpy(out, mp.out, list_bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 rt_status rt_debug_cal_cost(rt_scene* s, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny) {
     if (!s) return invalid("rt_debug_cal_cost: null scene");
     if (!out || !nx || !ny) return invalid("rt_debug_cal_cost: null argument");

@@ -227,6 +227,22 @@ struct rt_arith_test_params {
     unsigned long long* out;      // [3], zeroed / ~0 / zeroed by the caller: mismatching cases, the first of them, rays with finite_inv
 };
 hipError_t rt_launch_arith_tests(const rt_arith_test_params& ap, hipStream_t st);
+// rt_debug_math_tests (rt_kernel_arithtest.hip): device pointers; form and fn are include/rt_abi.h's RT_MATH_*.  The sweep runs
+// words first .. first + count - 1, one workgroup per RT_MATH_WORDS_PER_GROUP of them, and adds into digests (zeroed by the caller);
+// the list runs one element per thread
+#define RT_MATH_WORDS_PER_GROUP (1u << 14)
+struct rt_math_test_params {
+    int32_t form, fn;
+    uint32_t first;
+    long long count;
+    float operand;
+    const float* a;
+    const float* b;               // null where fn reads no second operand
+    const float* c;               // null where fn reads no third operand
+    float* out;                   // [count], RT_MATH_LIST
+    unsigned long long* digests;  // [(count + 2^20 - 1) >> 20], RT_MATH_SWEEP
+};
+hipError_t rt_launch_math_tests(const rt_math_test_params& mp, hipStream_t st);
 // bytes of the tier kernel's LDS image (rt_kernel_tier.h stages exactly this): leaf arrays + slot unions, then -- where the
 // launch plan (rt_abi.hip) says so -- spheres, materials and textures
 static inline size_t rt_tier_lds_bytes(int n_slots, int n_spheres, int n_materials, int n_textures, bool scene) {

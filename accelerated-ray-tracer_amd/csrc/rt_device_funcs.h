@@ -65,7 +65,17 @@ DEV f3 fma3(f3 t, f3 v, f3 a) { return mk3(fmaf(t.x, v.x, a.x), fmaf(t.y, v.y, a
 DEV f3 unit_vector(f3 v) { return sdiv(v, length(v)); }
 
 // correctly rounded fp32 transcendentals via double
-__device__ __attribute__((noinline)) float cr_pow(float x, float y) { return (float)pow((double)x, (double)y); }
+// The device library's double functions are not correctly rounded, so "rounded once" can miss where the true value lies within
+// a double ulp of a float rounding boundary.  tests/test_device_math.py compares every wrapper here with the oracle's (glibc)
+// input by input, mpmath the arbiter.  Over every float of [0, +inf] at the default gamma 2.2 there is one miss:
+// pow(0x7BFC1A2A = 2.6e36, 1 / 2.2f) is 0x5AFE3873 + 0.499999999 ulp and the library's double lands above the half.  That input
+// is answered with its lower neighbour's power, 0x5AFE3873 + 0.04 ulp: the same float, far from any boundary.  The input is
+// exchanged BEFORE pow on purpose: a flag or a copy of x kept through pow's body costs this function a register, and the main
+// kernels, which call it, a wave of occupancy or their scalar allocation (both were tried; profiles/device_math_bench.jsonl).
+__device__ __attribute__((noinline)) float cr_pow(float x, float y) {
+    if (__float_as_uint(x) == 0x7BFC1A2Au && __float_as_uint(y) == 0x3EE8BA2Eu) x = __uint_as_float(0x7BFC1A29u);
+    return (float)pow((double)x, (double)y);
+}
 DEV float cr_pow5(float x) { double d = (double)x; return (float)(d * d * d * d * d); }
 __device__ __attribute__((noinline)) float cr_log(float x) { return (float)log((double)x); }
 __device__ __attribute__((noinline)) float cr_sin(float x) { return (float)sin((double)x); }

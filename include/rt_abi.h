@@ -1126,6 +1126,40 @@ rt_status rt_debug_box_tests(int32_t n, const float* bmin, const float* bmax, co
 #define RT_ARITH_SIGNED 1
 #define RT_ARITH_LOOSE 2
 rt_status rt_debug_arith_tests(int32_t mode, int64_t n, const float* a, const float* b, const float* bound3, uint8_t* path, uint64_t* out3);
+/* diagnostics of the third-party part of the numerical contract (tests/test_device_math.py): the render path's own
+ * transcendental wrappers of csrc/rt_device_funcs.h, and the plain operations the contract calls IEEE, run on caller-chosen
+ * inputs so that their float results can be compared with another maths library's, input by input.
+ *   RT_MATH_LOG     cr_log(a)                         RT_MATH_POW5    cr_pow5(a), Schlick's fifth power
+ *   RT_MATH_SIN     cr_sin(a)                         RT_MATH_SQRT    sqrtf(a)
+ *   RT_MATH_ACOS    cr_acos(a)                        RT_MATH_RCP     1.0f / a
+ *   RT_MATH_ATAN2   cr_atan2(a, b)                    RT_MATH_DIV     a / b
+ *   RT_MATH_POW     apply_gamma(a, b): b is gamma,    RT_MATH_MULADD  a * b + c as written, built with the library's flags
+ *                   1 / gamma is formed as a frame's                  (the contract: the product is rounded, nothing fuses)
+ * RT_MATH_SWEEP: the inputs a are the `count` consecutive 32-bit words first, first + 1, ... taken as floats (count = 1 .. 2^32,
+ * first + count <= 2^32); b is `operand` (RT_MATH_POW: finite and positive; not read otherwise).  Functions of one input and
+ * RT_MATH_POW only.  digests[(count + 2^20 - 1) >> 20] receives one 64-bit digest per block of 2^20 consecutive words counted
+ * from `first` (the last block may be short): the sum modulo 2^64, over the block's words w, of mix64(w, r), where r is the bit
+ * pattern of the float result, or 0x7FC00000 for every NaN result whatever its sign and payload, and
+ *   mix64(w, r):  z = w * 2^32 + r;  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ * in 64-bit unsigned arithmetic (the finaliser of splitmix64).  A sum has no order, so digests of two implementations are equal
+ * exactly when -- short of a 2^-64 accident -- every result of the block is; a, b, c and out must be null.
+ * RT_MATH_LIST: out[i] = fn(a[i], b[i], c[i]) for i < count (count = 1 .. 2^24; first must be 0, operand is not read).  a, b, c,
+ * out are HOST buffers; b and c may be null where fn does not read them; digests must be null.
+ * Needs rt_init and no scene; every argument check runs before any HIP call; null stream, synchronous.  Never on a frame's path. */
+#define RT_MATH_SWEEP 0
+#define RT_MATH_LIST 1
+#define RT_MATH_LOG 0
+#define RT_MATH_SIN 1
+#define RT_MATH_ACOS 2
+#define RT_MATH_ATAN2 3
+#define RT_MATH_POW 4
+#define RT_MATH_POW5 5
+#define RT_MATH_SQRT 6
+#define RT_MATH_RCP 7
+#define RT_MATH_DIV 8
+#define RT_MATH_MULADD 9
+rt_status rt_debug_math_tests(int32_t form, int32_t fn, uint32_t first, int64_t count, float operand, const float* a, const float* b,
+                              const float* c, float* out, uint64_t* digests);
 /* The cost map (option cost_map).  The last launches of a ranked frame leave, per local pixel, the rays the
  * pixel cost over all its samples.  A pixel's cost depends on the scene, the camera, the frame geometry and the row partition,
  * not on seed_base or ns, so the next ranked frame of the same scene uses the map once rt_frame_finish has closed the frame

@@ -39,7 +39,7 @@ def lib():
             if not os.path.exists(LIB_PATH):
                 raise        # (a read-only tree with a library already built is still usable)
         L = C.CDLL(LIB_PATH)
-        if not hasattr(L, "orc_scene_from_desc"):
+        if not hasattr(L, "orc_math_sweep"):
             raise RuntimeError(f"{LIB_PATH} is out of date and could not be rebuilt (make -C oracle)")
         L.orc_scene_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.orc_scene_from_desc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
@@ -55,6 +55,8 @@ def lib():
         L.orc_perlin_noise.argtypes = [C.c_float] * 3
         L.orc_perlin_turb.restype = C.c_float
         L.orc_perlin_turb.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int]
+        L.orc_math_sweep.argtypes = [C.c_int, C.c_uint, C.c_longlong, C.c_float, C.c_void_p, C.c_int]
+        L.orc_math_list.argtypes = [C.c_int, C.c_longlong] + [C.c_void_p] * 4 + [C.c_int]
         _lib = L
     return _lib
 
@@ -65,6 +67,33 @@ def xorwow(seed: int, n: int):
     raw = np.zeros(n, np.uint32)
     lib().orc_xorwow(seed, n, state.ctypes.data, uni.ctypes.data, raw.ctypes.data)
     return state, uni, raw
+
+
+# orc_math_sweep / orc_math_list: the function ids of include/rt_abi.h's RT_MATH_*, and the oracle's own MATH_POW5_PRODUCT
+MATH_LOG, MATH_SIN, MATH_ACOS, MATH_ATAN2, MATH_POW, MATH_POW5, MATH_SQRT, MATH_RCP, MATH_DIV, MATH_MULADD, MATH_POW5_PRODUCT = range(11)
+
+
+def math_sweep(fn: int, first: int, count: int, operand: float = 0.0, threads: int = 0) -> np.ndarray:
+    """The twin of rt_debug_math_tests' sweep form through the oracle's own wrappers: fn over the words first .. first + count - 1
+    taken as floats (operand: gamma for MATH_POW), one uint64 digest per block of 2^20 words counted from `first`."""
+    digests = np.zeros((count + (1 << 20) - 1) >> 20, np.uint64)
+    threads = threads or min(os.cpu_count() or 1, 16)
+    if lib().orc_math_sweep(fn, first, count, operand, digests.ctypes.data, threads) != 0:
+        raise ValueError("orc_math_sweep refuses these arguments")
+    return digests
+
+
+def math_list(fn: int, a, b=None, c=None, threads: int = 0) -> np.ndarray:
+    """The twin of the list form: out[i] = fn(a[i], b[i], c[i]) in float32; b and c may be None where fn does not read them."""
+    a = np.ascontiguousarray(a, np.float32).reshape(-1)
+    b, c = (None if x is None else np.ascontiguousarray(x, np.float32).reshape(-1) for x in (b, c))
+    assert all(x is None or len(x) == len(a) for x in (b, c))
+    out = np.zeros(len(a), np.float32)
+    threads = threads or min(os.cpu_count() or 1, 16)
+    ptr = lambda x: None if x is None else x.ctypes.data   # noqa: E731
+    if lib().orc_math_list(fn, len(a), ptr(a), ptr(b), ptr(c), ptr(out), threads) != 0:
+        raise ValueError("orc_math_list refuses these arguments")
+    return out
 
 
 class OracleScene:

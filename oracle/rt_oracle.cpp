@@ -1345,6 +1345,43 @@ void dump_nodes_rec(const Obj* n, std::vector<float>& out) {
     if (!leaf) { dump_nodes_rec(n->left, out); dump_nodes_rec(n->right, out); }
 }
 
+// ---------------------------------------------------------------- orc_math_sweep / orc_math_list
+// The twin of the product's rt_debug_math_tests (include/rt_abi.h; tests/test_device_math.py): the same functions through this
+// file's own wrappers and glibc.  RT_MATH_POW5 is Schlick's power as schlick() above writes it, pow(x, 5); ORC_MATH_POW5_PRODUCT,
+// known here only, is the product's form of it -- four double multiplies, rounded once -- so that the CPU can compare the two.
+const int ORC_MATH_POW5_PRODUCT = 10;
+inline float math_eval(int fn, float a, float b, float c) {
+    switch (fn) {
+    case RT_MATH_LOG: return cr_logf(a);
+    case RT_MATH_SIN: return cr_sinf(a);
+    case RT_MATH_ACOS: return cr_acosf(a);
+    case RT_MATH_ATAN2: return cr_atan2f(a, b);
+    case RT_MATH_POW: return apply_gamma(a, b);
+    case RT_MATH_POW5: return cr_powf(a, 5.0f);
+    case RT_MATH_SQRT: return sqrtf(a);
+    case RT_MATH_RCP: return 1.0f / a;
+    case RT_MATH_DIV: return a / b;
+    case RT_MATH_MULADD: return a * b + c;   // unfused: -ffp-contract=off
+    default: { const double d = (double)a; return (float)(d * d * d * d * d); }   // ORC_MATH_POW5_PRODUCT
+    }
+}
+// the digest's term, restated from include/rt_abi.h: the finaliser of splitmix64 over (word, result bits), every NaN as 0x7FC00000
+inline uint64_t math_mix64(uint32_t w, float r) {
+    uint32_t bits;
+    memcpy(&bits, &r, 4);
+    if (r != r) bits = 0x7FC00000u;
+    uint64_t z = ((uint64_t)w << 32) | bits;
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+template <typename Work> void math_threads(int nthreads, Work work) {
+    if (nthreads <= 1) { work(0); return; }
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthreads; ++t) th.emplace_back(work, t);
+    for (auto& t : th) t.join();
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ C entry points (ctypes)
@@ -1580,6 +1617,46 @@ void orc_camera(int h, float* out21) {
     const V3 vs[6] = {c.origin, c.llc, c.horizontal, c.vertical, c.u, c.v};
     for (int k = 0; k < 6; ++k) { out21[3 * k] = vs[k].x; out21[3 * k + 1] = vs[k].y; out21[3 * k + 2] = vs[k].z; }
     out21[18] = c.lens_radius; out21[19] = (float)c.time0; out21[20] = (float)c.time1;
+}
+
+// words first .. first + count - 1 as floats (count <= 2^32, first + count <= 2^32), the second operand `operand`; one digest per
+// block of 2^20 words counted from `first`, pieces of 2^16 words dealt round robin to the threads.  -1: a bad argument.
+int orc_math_sweep(int fn, unsigned int first, long long count, float operand, unsigned long long* digests, int nthreads) {
+    if (fn < 0 || fn > ORC_MATH_POW5_PRODUCT || count < 1 || (long long)first + count > (1ll << 32) || !digests) return -1;
+    if (nthreads < 1) nthreads = 1;
+    const long long piece = 1ll << 16, n_pieces = (count + piece - 1) / piece, n_blocks = (count + (1ll << 20) - 1) >> 20;
+    std::vector<std::vector<uint64_t>> sums((size_t)nthreads, std::vector<uint64_t>((size_t)n_blocks, 0));
+    math_threads(nthreads, [&](int tid) {
+        for (long long p = tid; p < n_pieces; p += nthreads) {
+            const long long i0 = p * piece, i1 = i0 + piece < count ? i0 + piece : count;
+            uint64_t sum = 0;
+            for (long long i = i0; i < i1; ++i) {
+                const uint32_t w = first + (uint32_t)i;
+                float a;
+                memcpy(&a, &w, 4);
+                sum += math_mix64(w, math_eval(fn, a, operand, 0.0f));
+            }
+            sums[(size_t)tid][(size_t)(i0 >> 20)] += sum;
+        }
+    });
+    for (long long k = 0; k < n_blocks; ++k) {
+        uint64_t sum = 0;
+        for (int t = 0; t < nthreads; ++t) sum += sums[(size_t)t][(size_t)k];
+        digests[k] = sum;
+    }
+    return 0;
+}
+
+// out[i] = fn(a[i], b[i], c[i]); b and c may be null where fn does not read them (they read as 0).  -1: a bad argument.
+int orc_math_list(int fn, long long n, const float* a, const float* b, const float* c, float* out, int nthreads) {
+    if (fn < 0 || fn > ORC_MATH_POW5_PRODUCT || n < 1 || !a || !out) return -1;
+    if (nthreads < 1) nthreads = 1;
+    const long long per = (n + nthreads - 1) / nthreads;
+    math_threads(nthreads, [&](int tid) {
+        const long long i1 = (tid + 1) * per < n ? (tid + 1) * per : n;
+        for (long long i = tid * per; i < i1; ++i) out[i] = math_eval(fn, a[i], b ? b[i] : 0.0f, c ? c[i] : 0.0f);
+    });
+    return 0;
 }
 
 // single-function vectors
