@@ -849,10 +849,6 @@ def _record_update(kind, records, indices, first):
     return u, (rec, idx)
 
 
-def _sphere_update(spheres, indices, first):
-    return _record_update(_SPHERES, spheres, indices, first)
-
-
 def _update_indices(indices, count, u, one="sphere"):
     if indices is None:
         return None
@@ -866,43 +862,34 @@ def _update_indices(indices, count, u, one="sphere"):
     return idx
 
 
+def _refit(kind, entry, desc, records, indices, first):
+    """rt_refit_nodes / rt_refit_instances / rt_refit_quads: (nodes, records) of the description the update is equivalent to."""
+    u, keep = _record_update(kind, records, indices, first)
+    nodes, out = np.zeros(desc.n_nodes, NODE_DTYPE), np.zeros(getattr(desc, "n_" + kind[0]), kind[2])
+    L = rt_lib()
+    st = getattr(L, entry)(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data)
+    if st == 1:
+        raise ValueError(L.rt_last_error_detail().decode())
+    _check(st, entry)
+    return nodes, out
+
+
 def refit_nodes(desc: RtSceneDesc, spheres, indices=None, first: int = 0):
     """rt_refit_nodes, host only: the description that DeviceScene.update_spheres(spheres, indices, first) is equivalent to.
     Returns (nodes, spheres) of it as NODE_DTYPE / SPHERE_DTYPE arrays.  ValueError when the update is refused."""
-    u, keep = _sphere_update(spheres, indices, first)
-    nodes, out = np.zeros(desc.n_nodes, NODE_DTYPE), np.zeros(desc.n_spheres, SPHERE_DTYPE)
-    L = rt_lib()
-    st = L.rt_refit_nodes(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data)
-    if st == 1:
-        raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_refit_nodes")
-    return nodes, out
+    return _refit(_SPHERES, "rt_refit_nodes", desc, spheres, indices, first)
 
 
 def refit_instances(desc: RtSceneDesc, instances, indices=None, first: int = 0):
     """rt_refit_instances, host only: the description that DeviceScene.update_instances(instances, indices, first) is equivalent
     to.  Returns (nodes, instances) of it as NODE_DTYPE / INSTANCE_DTYPE arrays.  ValueError when the update is refused."""
-    u, keep = _record_update(_INSTANCES, instances, indices, first)
-    nodes, out = np.zeros(desc.n_nodes, NODE_DTYPE), np.zeros(desc.n_instances, INSTANCE_DTYPE)
-    L = rt_lib()
-    st = L.rt_refit_instances(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data)
-    if st == 1:
-        raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_refit_instances")
-    return nodes, out
+    return _refit(_INSTANCES, "rt_refit_instances", desc, instances, indices, first)
 
 
 def refit_quads(desc: RtSceneDesc, quads, indices=None, first: int = 0):
     """rt_refit_quads, host only: the description that DeviceScene.update_quads(quads, indices, first) is equivalent to.
     Returns (nodes, quads) of it as NODE_DTYPE / QUAD_DTYPE arrays.  ValueError when the update is refused."""
-    u, keep = _record_update(_QUADS, quads, indices, first)
-    nodes, out = np.zeros(desc.n_nodes, NODE_DTYPE), np.zeros(desc.n_quads, QUAD_DTYPE)
-    L = rt_lib()
-    st = L.rt_refit_quads(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data)
-    if st == 1:
-        raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_refit_quads")
-    return nodes, out
+    return _refit(_QUADS, "rt_refit_quads", desc, quads, indices, first)
 
 
 def _float3(x, name):
@@ -1724,33 +1711,24 @@ class MultiScene:
 
     def update_spheres(self, spheres, indices=None, first: int = 0, recalibrate: bool = False) -> None:
         """DeviceScene.update_spheres with host records on every replica (rt_multi_update_spheres)."""
-        L = rt_lib()
-        u, keep = _sphere_update(spheres, indices, first)
-        st = L.rt_multi_update_spheres(self._p, C.byref(u), 1 if recalibrate else 0)
-        del keep
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_multi_update_spheres")
+        self._update_records(_SPHERES, "rt_multi_update_spheres", spheres, indices, first, recalibrate)
 
     def update_instances(self, instances, indices=None, first: int = 0, recalibrate: bool = False) -> None:
         """DeviceScene.update_instances with host records on every replica (rt_multi_update_instances)."""
-        L = rt_lib()
-        u, keep = _record_update(_INSTANCES, instances, indices, first)
-        st = L.rt_multi_update_instances(self._p, C.byref(u), 1 if recalibrate else 0)
-        del keep
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_multi_update_instances")
+        self._update_records(_INSTANCES, "rt_multi_update_instances", instances, indices, first, recalibrate)
 
     def update_quads(self, quads, indices=None, first: int = 0, recalibrate: bool = False) -> None:
         """DeviceScene.update_quads with host records on every replica (rt_multi_update_quads)."""
+        self._update_records(_QUADS, "rt_multi_update_quads", quads, indices, first, recalibrate)
+
+    def _update_records(self, kind, entry, records, indices, first, recalibrate):
         L = rt_lib()
-        u, keep = _record_update(_QUADS, quads, indices, first)
-        st = L.rt_multi_update_quads(self._p, C.byref(u), 1 if recalibrate else 0)
+        u, keep = _record_update(kind, records, indices, first)
+        st = getattr(L, entry)(self._p, C.byref(u), 1 if recalibrate else 0)
         del keep
         if st == 1:
             raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_multi_update_quads")
+        _check(st, entry)
 
     def render(self, frame: RtFrameDesc, tile_rows: int = 4):
         """The whole frame as float32[ny][nx][3] in host memory, and the summed statistics."""

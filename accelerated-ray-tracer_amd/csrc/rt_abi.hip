@@ -251,21 +251,22 @@ struct rt_scene {
     // image in d_adapt_spp: 4 bytes per pixel either way)
     double* d_var_acc = nullptr;
     size_t var_capacity = 0;                     // in doubles: three per pixel
-    // rt_scene_update_spheres, rt_scene_update_instances: the lookup tables of the refit kernels, built on the scene's first update from a
-    // read-back of the node arrays, so that a scene that never moves pays nothing; refit.block holds all of them
+    // rt_scene_update_spheres, _instances and _quads: the lookup tables of the refit kernels, built on
+    // the scene's first update from a read-back of the node arrays, so that a scene that never moves pays nothing; refit.block
+    // holds all of them
     int32_t n_instances = 0, n_media = 0;        // of the description (rt_scene_dev carries neither)
-    int32_t n_quads = 0, n_boxes = 0;            // (the same; rt_scene_update_quads)
+    int32_t n_quads = 0, n_boxes = 0;
     struct refit_tables {
         bool ready = false;
-        void* block = nullptr;                   // one allocation, cut into the arrays of `p`
+        void* block = nullptr;                   // one allocation, cut into the arrays of `p` and the stamps
         rt_refit_params p;                       // the per-scene half of the kernels' argument, filled once
         std::vector<char> instanced;             // per sphere: the child of an instance (kept from rt_scene_create, host only)
         std::vector<int32_t> inst_child;         // per instance: its child, which no update changes (the same)
-        uint32_t epoch = 0, inst_epoch = 0;      // of the spheres' and of the instances' stamps
-        uint32_t quad_epoch = 0;                 // ... and of the quads'
+        uint32_t* stamp[rt_refit::KINDS] = {};   // per kind (the kinds index different arrays): one word per record ...
+        uint32_t epoch[rt_refit::KINDS] = {};    // ... equal to this after the update that last replaced the record
         int32_t* d_indices = nullptr;            // the update's index list and (host records) its records on the device
-        rt_sphere* d_records = nullptr;          // (in 32-byte units: a sphere or an instance is one, a quad two and a half)
-        size_t indices_capacity = 0, records_capacity = 0;
+        char* d_records = nullptr;
+        size_t indices_capacity = 0, records_capacity = 0;   // in indices, in bytes
     } refit;
 };
 
@@ -1411,8 +1412,9 @@ rt_status plan_resident(const rt_scene* s, size_t node_bytes, int option, long l
 }
 }  // namespace
 
-// ---- rt_scene_update_spheres (include/rt_abi.h).  Nothing of the scene's topology changes: the kernels of
-// rt_kernel_refit.hip store the records and recompute, where they live, the boxes that depend on them.
+// ---- rt_scene_update_spheres, rt_scene_update_instances, rt_scene_update_quads (include/rt_abi.h).
+// Nothing of the scene's topology changes: the kernels of rt_kernel_refit.hip store the records and recompute, where they live, the
+// boxes that depend on them.  The three kinds share the tables, the launches and the body below (update_records).
 namespace {
 // The lookup tables, once per scene: the node arrays are read back (the device holds the only copy of the walk array) and every
 // node's subtree -- nodes [i, skip[i]) of a depth-first array -- becomes a range of leaf ordinals.
@@ -1420,7 +1422,7 @@ rt_status build_refit_tables(rt_scene* s) {
     rt_scene::refit_tables& t = s->refit;
     if (t.ready) return RT_OK;
     const bool own_walk = s->dev.nodes != s->dev.nodes_ref;
-    const int n_ref = s->dev.n_nodes_ref, n_walk = own_walk ? s->dev.n_nodes : 0, n_spheres = s->dev.n_spheres;
+    const int n_ref = s->dev.n_nodes_ref, n_walk = own_walk ? s->dev.n_nodes : 0;
     std::vector<rt_node> ref((size_t)n_ref), walk((size_t)n_walk);
     std::vector<rt_medium> media((size_t)s->n_media);
     if (n_ref) HIPCHK(hipMemcpy(ref.data(), s->dev.nodes_ref, ref.size() * sizeof(rt_node), hipMemcpyDeviceToHost));
@@ -1428,7 +1430,7 @@ rt_status build_refit_tables(rt_scene* s) {
     if (s->n_media) HIPCHK(hipMemcpy(media.data(), s->dev.media, media.size() * sizeof(rt_medium), hipMemcpyDeviceToHost));
 
     // leaves by ordinal, and one job per interior node: (node, first leaf, end leaf, array)
-    std::vector<int32_t> leaf_sphere, leaf_instance, leaf_solid, leaf_node_ref, leaf_node_walk;
+    std::vector<int32_t> leaf_solid, leaf_node_ref, leaf_node_walk;
     std::vector<float> box_lo, box_hi;
     std::vector<int4> jobs;
     auto scan = [&](const std::vector<rt_node>& nodes, int which, std::vector<int32_t>& leaf_node) -> bool {
@@ -1448,31 +1450,25 @@ rt_status build_refit_tables(rt_scene* s) {
     if (own_walk && (int)leaf_node_walk.size() != m) return invalid("rt_scene_update_spheres: the walk array does not hold the reference tree's leaves");
     if (s->dev.leaf_lo && s->dev.n_leaves != m) return invalid("rt_scene_update_spheres: the tier data do not hold the reference tree's leaves");
     const int slots = (m + 63) / 64;
-    leaf_sphere.assign((size_t)m, -1);
-    leaf_instance.assign((size_t)m, -1);
     leaf_solid.assign((size_t)m, -1);
     box_lo.assign((size_t)slots * 64 * 4, 0.0f); box_hi.assign((size_t)slots * 64 * 4, 0.0f);
     for (int q = 0; q < m; ++q) {
         const rt_node& n = ref[(size_t)leaf_node_ref[(size_t)q]];
         if (own_walk && walk[(size_t)leaf_node_walk[(size_t)q]].prim != n.prim) return invalid("rt_scene_update_spheres: the walk array's leaves are not in the reference tree's order");
-        leaf_sphere[(size_t)q] = rt_refit::leaf_sphere(n.prim, media.data(), s->n_media, n_spheres);
-        leaf_instance[(size_t)q] = rt_refit::leaf_instance(n.prim, media.data(), s->n_media, s->n_instances);
-        leaf_solid[(size_t)q] = rt_refit::leaf_solid(n.prim, media.data(), s->n_media, n_spheres, s->n_quads, s->n_boxes, s->n_instances);
+        leaf_solid[(size_t)q] = rt_refit::leaf_solid(n.prim, media.data(), s->n_media, s->dev.n_spheres, s->n_quads, s->n_boxes, s->n_instances);
         for (int c = 0; c < 3; ++c) { box_lo[(size_t)q * 4 + c] = n.bmin[c]; box_hi[(size_t)q * 4 + c] = n.bmax[c]; }
     }
     if (!own_walk) leaf_node_walk.clear();
 
-    // one block, every piece 256-byte aligned: the three stamp arrays, the five leaf tables, the canonical boxes, slot unions and maxima, jobs, result
+    // one block, every piece 256-byte aligned: the three stamp arrays, the three leaf tables, the canonical boxes, slot unions and maxima, jobs, result
     const bool tier = s->dev.slot_ranges != nullptr;
     struct piece { size_t bytes; const void* src; void** dst; };
-    uint32_t *stamp = nullptr, *inst_stamp = nullptr, *quad_stamp = nullptr; int32_t *d_ls = nullptr, *d_li = nullptr, *d_lq = nullptr, *d_lr = nullptr, *d_lw = nullptr; float4 *d_lo = nullptr, *d_hi = nullptr;
+    int32_t *d_lq = nullptr, *d_lr = nullptr, *d_lw = nullptr; float4 *d_lo = nullptr, *d_hi = nullptr;
     float *d_slot = nullptr, *d_abs = nullptr, *d_result = nullptr; int4* d_jobs = nullptr;
     const piece pieces[] = {
-        {(size_t)n_spheres * 4, nullptr, (void**)&stamp},
-        {(size_t)s->n_instances * 4, nullptr, (void**)&inst_stamp},
-        {(size_t)s->n_quads * 4, nullptr, (void**)&quad_stamp},
-        {leaf_sphere.size() * 4, leaf_sphere.data(), (void**)&d_ls},
-        {leaf_instance.size() * 4, leaf_instance.data(), (void**)&d_li},
+        {(size_t)s->dev.n_spheres * 4, nullptr, (void**)&t.stamp[rt_refit::SPHERES]},
+        {(size_t)s->n_instances * 4, nullptr, (void**)&t.stamp[rt_refit::INSTANCES]},
+        {(size_t)s->n_quads * 4, nullptr, (void**)&t.stamp[rt_refit::QUADS]},
         {leaf_solid.size() * 4, leaf_solid.data(), (void**)&d_lq},
         {leaf_node_ref.size() * 4, leaf_node_ref.data(), (void**)&d_lr},
         {leaf_node_walk.size() * 4, leaf_node_walk.data(), (void**)&d_lw},
@@ -1498,9 +1494,10 @@ rt_status build_refit_tables(rt_scene* s) {
     rt_refit_params& p = t.p;
     memset(&p, 0, sizeof(p));
     p.n_materials = s->dev.n_materials;
-    p.stamp = stamp; p.spheres = const_cast<rt_sphere*>(s->dev.spheres);
+    p.spheres = const_cast<rt_sphere*>(s->dev.spheres); p.instances = const_cast<rt_instance*>(s->dev.instances);
+    p.quads = const_cast<rt_quad*>(s->dev.quads); p.boxes = const_cast<rt_box*>(s->dev.boxes); p.n_boxes = s->n_boxes;
     p.n_leaves = m; p.n_slots = slots;
-    p.leaf_sphere = d_ls; p.leaf_node_ref = d_lr; p.leaf_node_walk = d_lw;
+    p.leaf_solid = d_lq; p.leaf_node_ref = d_lr; p.leaf_node_walk = d_lw;
     p.box_lo = d_lo; p.box_hi = d_hi;
     p.tier_lo = const_cast<float4*>(s->dev.leaf_lo); p.tier_hi = const_cast<float4*>(s->dev.leaf_hi);
     p.nodes_ref = const_cast<rt_node*>(s->dev.nodes_ref);
@@ -1509,20 +1506,15 @@ rt_status build_refit_tables(rt_scene* s) {
     p.slot_abs = d_abs;
     p.jobs = d_jobs; p.n_jobs = (int32_t)jobs.size();
     p.result = d_result;
-    p.inst_stamp = inst_stamp; p.instances = const_cast<rt_instance*>(s->dev.instances); p.leaf_instance = d_li;
-    p.quads = s->dev.quads; p.boxes = s->dev.boxes;
-    p.quad_stamp = quad_stamp; p.leaf_solid = d_lq; p.n_boxes = s->n_boxes;
-    p.quads_rw = const_cast<rt_quad*>(s->dev.quads); p.boxes_rw = const_cast<rt_box*>(s->dev.boxes);
     t.ready = true;
     return RT_OK;
 }
 
 // The launches of an update whose records and indices are in place, the read-back of the bound and the flag, and the cost half
 // of the calibration when asked for (as rt_scene_set_camera)
-enum refit_kind { REFIT_SPHERES, REFIT_INSTANCES, REFIT_QUADS };
-rt_status run_refit(rt_scene* s, const rt_refit_params& p, refit_kind kind, hipStream_t stream, int recalibrate, bool& refused) {
+rt_status run_refit(rt_scene* s, const rt_refit_params& p, int kind, hipStream_t stream, int recalibrate, bool& refused) {
     HIPCHK(hipMemsetAsync(p.result, 0, 16, stream));
-    HIPCHK(kind == REFIT_QUADS ? rt_launch_refit_quads(p, stream) : kind == REFIT_INSTANCES ? rt_launch_refit_instances(p, stream) : rt_launch_refit(p, stream));
+    HIPCHK(rt_launch_refit(p, kind, stream));
     float result[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     HIPCHK(hipMemcpyAsync(result, p.result, sizeof(result), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -1537,197 +1529,128 @@ rt_status run_refit(rt_scene* s, const rt_refit_params& p, refit_kind kind, hipS
     }
     return RT_OK;
 }
-}  // namespace
 
-rt_status rt_scene_update_spheres(rt_scene* s, const rt_sphere_update* u, int spheres_on_device, int recalibrate, void* stream_v) {
-    const std::string who = "rt_scene_update_spheres: ";
-    if (!s) return invalid((who + "null scene").c_str());
-    if (!u) return invalid((who + "null update").c_str());
-    if (u->count < 0) return invalid((who + "count is negative").c_str());
-    if (u->count > 0 && !u->spheres) return invalid((who + "null sphere records").c_str());
-    rt_scene::refit_tables& t = s->refit;
-    const std::string why = rt_refit::check_update(u, !spheres_on_device, s->dev.n_spheres, s->dev.n_materials, t.instanced);
+// What an update of one kind names: its entry, the size of a record and the tail of the refusal of a device-resident record.
+struct update_words { const char* entry; size_t record_bytes; const char* refused; };
+const update_words UPDATE_WORDS[rt_refit::KINDS] = {
+    {"rt_scene_update_spheres", sizeof(rt_sphere), "a non-finite field or a material out of range"},
+    {"rt_scene_update_instances", sizeof(rt_instance), "a non-finite field, flags outside 1..3 or a child other than the scene's"},
+    {"rt_scene_update_quads", sizeof(rt_quad), "a non-finite field or a material out of range"},
+};
+
+// The one body of rt_scene_update_spheres, _instances and _quads.  `why` is the answer of the kind's host check (rt_refit_host.h),
+// made before any HIP call; n the scene's count of the kind.  The scene holds one copy of every record array (s->dev.spheres,
+// .instances, .quads, .boxes), which every kernel reads through its scene view: the tier arrays hold references to the quads and
+// boxes (lo.w / hi.w), the staged kernels copy at launch time, nothing is staged from the instances.  What rt_scene_create derives
+// from quad records lives inside those arrays (pad0, bit 30 of first_quad) and follows the update there.
+extern "C++" template <class Update>
+rt_status update_records(rt_scene* s, int kind, const Update* u, const std::string& why, int32_t n, int on_device, int recalibrate, void* stream_v) {
+    const update_words& w = UPDATE_WORDS[kind];
+    const std::string who = std::string(w.entry) + ": ";
     if (!why.empty()) return invalid((who + why).c_str());
     if (u->count == 0) return RT_OK;
     RT_TRY(use_device(s->device));
     RT_TRY(build_refit_tables(s));
+    rt_scene::refit_tables& t = s->refit;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (spheres_on_device) {
-        const traced_ptr records[] = {{u->spheres, (size_t)u->count * sizeof(rt_sphere), "spheres", 4}};
-        RT_TRY(check_trace_ptrs(records, s->device, "rt_scene_update_spheres"));
+    const size_t bytes = (size_t)u->count * w.record_bytes;
+    if (on_device) {
+        const traced_ptr records[] = {{rt_refit::records_of(*u), bytes, rt_refit::NOUNS[kind].many, 4}};
+        RT_TRY(check_trace_ptrs(records, s->device, w.entry));
     }
     if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
     ++s->scene_epoch;                                // the cost map: as rt_scene_set_camera
     if (recalibrate) s->cost_map.valid = false;
     rt_refit_params p = t.p;
     p.count = u->count; p.first = u->first;
-    if (++t.epoch == 0) { HIPCHK(hipMemsetAsync(p.stamp, 0, (size_t)s->dev.n_spheres * 4, stream)); t.epoch = 1; }
-    p.epoch = t.epoch;
+    p.stamp = t.stamp[kind];
+    if (++t.epoch[kind] == 0) { HIPCHK(hipMemsetAsync(p.stamp, 0, (size_t)n * 4, stream)); t.epoch[kind] = 1; }
+    p.epoch = t.epoch[kind];
     if (u->indices) {
         RT_TRY(grow(t.d_indices, t.indices_capacity, (size_t)u->count));
         HIPCHK(hipMemcpyAsync(t.d_indices, u->indices, (size_t)u->count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
         p.indices = t.d_indices;
     }
-    if (spheres_on_device) p.records = u->spheres;
+    if (on_device) p.records = rt_refit::records_of(*u);
     else {
-        RT_TRY(grow(t.d_records, t.records_capacity, (size_t)u->count));
-        HIPCHK(hipMemcpyAsync(t.d_records, u->spheres, (size_t)u->count * sizeof(rt_sphere), hipMemcpyHostToDevice, stream));
+        RT_TRY(grow(t.d_records, t.records_capacity, bytes));
+        HIPCHK(hipMemcpyAsync(t.d_records, rt_refit::records_of(*u), bytes, hipMemcpyHostToDevice, stream));
         p.records = t.d_records;
     }
     bool refused = false;
-    RT_TRY(run_refit(s, p, REFIT_SPHERES, stream, recalibrate, refused));
-    if (refused) return invalid((who + "a device-resident record has a non-finite field or a material out of range; it was not stored, every other record was").c_str());
+    RT_TRY(run_refit(s, p, kind, stream, recalibrate, refused));
+    if (refused) return invalid((who + "a device-resident record has " + w.refused + "; it was not stored, every other record was").c_str());
     return RT_OK;
+}
+
+// rt_scene_get_spheres, _instances, _quads: the scene's n records of the kind, as they stand on the device
+extern "C++" template <class Record>
+rt_status get_records(const rt_scene* s, int kind, const char* entry, const Record* records, int32_t n, Record* out, int32_t cap) {
+    const std::string who = std::string(entry) + ": ";
+    if (!out) return invalid((who + "null output pointer").c_str());
+    if (cap < n) return invalid((who + "cap is below the scene's " + rt_refit::NOUNS[kind].one + " count").c_str());
+    RT_TRY(use_device(s->device));
+    if (n) HIPCHK(hipMemcpy(out, records, (size_t)n * sizeof(Record), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// The one body of rt_refit_nodes, rt_refit_instances and rt_refit_quads, after the kind's check has passed: the description's
+// records of the kind with the update's in place (`changed`, which is one of the three arrays handed to the refit), the nodes refit.
+extern "C++" template <class Update, class Record>
+void restate(const rt_scene_desc* d, int kind, const Update* u, std::vector<Record>& changed, const rt_sphere* spheres, const rt_instance* instances,
+             const rt_quad* quads, rt_node* nodes_out, Record* records_out) {
+    std::vector<char> moved(changed.size(), 0);
+    for (int32_t k = 0; k < u->count; ++k) {
+        const int32_t i = u->indices ? u->indices[k] : u->first + k;
+        changed[(size_t)i] = rt_refit::records_of(*u)[k];
+        moved[(size_t)i] = 1;
+    }
+    if (nodes_out) {
+        std::vector<rt_node> nodes(d->nodes, d->nodes + d->n_nodes);
+        rt_refit::refit_nodes(nodes.data(), d, spheres, instances, quads, kind, moved);
+        if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
+    }
+    if (records_out && !changed.empty()) memcpy(records_out, changed.data(), changed.size() * sizeof(Record));
+}
+rt_status validate_desc(const rt_scene_desc* d) {
+    bool so = false, uv = false;
+    int tx = 0;
+    return validate(d, so, tx, uv);
+}
+}  // namespace
+
+rt_status rt_scene_update_spheres(rt_scene* s, const rt_sphere_update* u, int spheres_on_device, int recalibrate, void* stream_v) {
+    if (!s) return invalid("rt_scene_update_spheres: null scene");
+    const std::string why = rt_refit::check_update(u, !spheres_on_device, s->dev.n_spheres, s->dev.n_materials, s->refit.instanced);
+    return update_records(s, rt_refit::SPHERES, u, why, s->dev.n_spheres, spheres_on_device, recalibrate, stream_v);
+}
+
+rt_status rt_scene_update_instances(rt_scene* s, const rt_instance_update* u, int instances_on_device, int recalibrate, void* stream_v) {
+    if (!s) return invalid("rt_scene_update_instances: null scene");
+    const std::string why = rt_refit::check_instance_update(u, !instances_on_device, s->refit.inst_child.data(), s->n_instances);
+    return update_records(s, rt_refit::INSTANCES, u, why, s->n_instances, instances_on_device, recalibrate, stream_v);
+}
+
+rt_status rt_scene_update_quads(rt_scene* s, const rt_quad_update* u, int quads_on_device, int recalibrate, void* stream_v) {
+    if (!s) return invalid("rt_scene_update_quads: null scene");
+    const std::string why = rt_refit::check_quad_update(u, !quads_on_device, s->n_quads, s->dev.n_materials);
+    return update_records(s, rt_refit::QUADS, u, why, s->n_quads, quads_on_device, recalibrate, stream_v);
 }
 
 rt_status rt_scene_get_spheres(const rt_scene* s, rt_sphere* out, int32_t cap) {
     if (!s) return invalid("rt_scene_get_spheres: null scene");
-    if (!out) return invalid("rt_scene_get_spheres: null output pointer");
-    if (cap < s->dev.n_spheres) return invalid("rt_scene_get_spheres: cap is below the scene's sphere count");
-    RT_TRY(use_device(s->device));
-    if (s->dev.n_spheres) HIPCHK(hipMemcpy(out, s->dev.spheres, (size_t)s->dev.n_spheres * sizeof(rt_sphere), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-rt_status rt_refit_nodes(const rt_scene_desc* d, const rt_sphere_update* u, rt_node* nodes_out, rt_sphere* spheres_out) {
-    bool so = false, uv = false;
-    int tx = 0;
-    RT_TRY(validate(d, so, tx, uv));
-    const std::string why = rt_refit::check_update(u, true, d->n_spheres, d->n_materials, rt_refit::instanced_spheres(d->instances, d->n_instances, d->n_spheres));
-    if (!why.empty()) return invalid(("rt_refit_nodes: " + why).c_str());
-    std::vector<rt_sphere> spheres(d->spheres, d->spheres + d->n_spheres);
-    std::vector<char> moved((size_t)d->n_spheres, 0);
-    for (int32_t k = 0; k < u->count; ++k) {
-        const int32_t i = u->indices ? u->indices[k] : u->first + k;
-        spheres[(size_t)i] = u->spheres[k];
-        moved[(size_t)i] = 1;
-    }
-    if (nodes_out) {
-        std::vector<rt_node> nodes(d->nodes, d->nodes + d->n_nodes);
-        rt_refit::refit_nodes(nodes.data(), d->n_nodes, spheres.data(), d->n_spheres, d->media, d->n_media, moved);
-        if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
-    }
-    if (spheres_out && d->n_spheres) memcpy(spheres_out, spheres.data(), spheres.size() * sizeof(rt_sphere));
-    return RT_OK;
-}
-
-// ---- rt_scene_update_instances (include/rt_abi.h): the same tables and the same unions; the records kernel and
-// the leaf kernel are the instances' own.  The scene holds one copy of the instance records, s->dev.instances, which every
-// kernel reads through its scene view; nothing is staged from them at creation or at launch time.
-rt_status rt_scene_update_instances(rt_scene* s, const rt_instance_update* u, int instances_on_device, int recalibrate, void* stream_v) {
-    static_assert(sizeof(rt_instance) == sizeof(rt_sphere), "the staging buffer of an update is counted in 32-byte units: one per sphere or instance");
-    const std::string who = "rt_scene_update_instances: ";
-    if (!s) return invalid((who + "null scene").c_str());
-    rt_scene::refit_tables& t = s->refit;
-    const std::string why = rt_refit::check_instance_update(u, !instances_on_device, t.inst_child.data(), s->n_instances);
-    if (!why.empty()) return invalid((who + why).c_str());
-    if (u->count == 0) return RT_OK;
-    RT_TRY(use_device(s->device));
-    RT_TRY(build_refit_tables(s));
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (instances_on_device) {
-        const traced_ptr records[] = {{u->instances, (size_t)u->count * sizeof(rt_instance), "instances", 4}};
-        RT_TRY(check_trace_ptrs(records, s->device, "rt_scene_update_instances"));
-    }
-    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
-    ++s->scene_epoch;                                // the cost map: as rt_scene_update_spheres
-    if (recalibrate) s->cost_map.valid = false;
-    rt_refit_params p = t.p;
-    p.count = u->count; p.first = u->first;
-    if (++t.inst_epoch == 0) { HIPCHK(hipMemsetAsync(p.inst_stamp, 0, (size_t)s->n_instances * 4, stream)); t.inst_epoch = 1; }
-    p.inst_epoch = t.inst_epoch;
-    if (u->indices) {
-        RT_TRY(grow(t.d_indices, t.indices_capacity, (size_t)u->count));
-        HIPCHK(hipMemcpyAsync(t.d_indices, u->indices, (size_t)u->count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        p.indices = t.d_indices;
-    }
-    if (instances_on_device) p.inst_records = u->instances;
-    else {
-        RT_TRY(grow(t.d_records, t.records_capacity, (size_t)u->count));
-        HIPCHK(hipMemcpyAsync(t.d_records, u->instances, (size_t)u->count * sizeof(rt_instance), hipMemcpyHostToDevice, stream));
-        p.inst_records = reinterpret_cast<const rt_instance*>(t.d_records);
-    }
-    bool refused = false;
-    RT_TRY(run_refit(s, p, REFIT_INSTANCES, stream, recalibrate, refused));
-    if (refused) return invalid((who + "a device-resident record has a non-finite field, flags outside 1..3 or a child other than the scene's; it was not stored, every other record was").c_str());
-    return RT_OK;
+    return get_records(s, rt_refit::SPHERES, "rt_scene_get_spheres", s->dev.spheres, s->dev.n_spheres, out, cap);
 }
 
 rt_status rt_scene_get_instances(const rt_scene* s, rt_instance* out, int32_t cap) {
     if (!s) return invalid("rt_scene_get_instances: null scene");
-    if (!out) return invalid("rt_scene_get_instances: null output pointer");
-    if (cap < s->n_instances) return invalid("rt_scene_get_instances: cap is below the scene's instance count");
-    RT_TRY(use_device(s->device));
-    if (s->n_instances) HIPCHK(hipMemcpy(out, s->dev.instances, (size_t)s->n_instances * sizeof(rt_instance), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return get_records(s, rt_refit::INSTANCES, "rt_scene_get_instances", s->dev.instances, s->n_instances, out, cap);
 }
 
-rt_status rt_refit_instances(const rt_scene_desc* d, const rt_instance_update* u, rt_node* nodes_out, rt_instance* instances_out) {
-    bool so = false, uv = false;
-    int tx = 0;
-    RT_TRY(validate(d, so, tx, uv));
-    std::vector<int32_t> children;
-    for (int i = 0; i < d->n_instances; ++i) children.push_back(d->instances[i].child);
-    const std::string why = rt_refit::check_instance_update(u, true, children.data(), d->n_instances);
-    if (!why.empty()) return invalid(("rt_refit_instances: " + why).c_str());
-    std::vector<rt_instance> instances(d->instances, d->instances + d->n_instances);
-    std::vector<char> moved((size_t)d->n_instances, 0);
-    for (int32_t k = 0; k < u->count; ++k) {
-        const int32_t i = u->indices ? u->indices[k] : u->first + k;
-        instances[(size_t)i] = u->instances[k];
-        moved[(size_t)i] = 1;
-    }
-    if (nodes_out) {
-        std::vector<rt_node> nodes(d->nodes, d->nodes + d->n_nodes);
-        rt_refit::refit_instance_nodes(nodes.data(), d, instances.data(), moved);
-        if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
-    }
-    if (instances_out && d->n_instances) memcpy(instances_out, instances.data(), instances.size() * sizeof(rt_instance));
-    return RT_OK;
-}
-
-// ---- rt_scene_update_quads (include/rt_abi.h): the same tables and the same unions; a records kernel, a
-// box-marks kernel and a leaf kernel of its own.  The scene holds one copy of the quad and box records, s->dev.quads and
-// s->dev.boxes, which every kernel reads through its scene view: the tier arrays hold references to them (lo.w / hi.w), the
-// staged kernels copy at launch time.  What rt_scene_create derives from quad records lives inside those two arrays (pad0, bit 30
-// of first_quad) and follows the update there.
-rt_status rt_scene_update_quads(rt_scene* s, const rt_quad_update* u, int quads_on_device, int recalibrate, void* stream_v) {
-    static_assert(sizeof(rt_quad) == 80 && sizeof(rt_quad) % 16 == 0, "the staging buffer holds a quad in two and a half 32-byte units");
-    const std::string who = "rt_scene_update_quads: ";
-    if (!s) return invalid((who + "null scene").c_str());
-    rt_scene::refit_tables& t = s->refit;
-    const std::string why = rt_refit::check_quad_update(u, !quads_on_device, s->n_quads, s->dev.n_materials);
-    if (!why.empty()) return invalid((who + why).c_str());
-    if (u->count == 0) return RT_OK;
-    RT_TRY(use_device(s->device));
-    RT_TRY(build_refit_tables(s));
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (quads_on_device) {
-        const traced_ptr records[] = {{u->quads, (size_t)u->count * sizeof(rt_quad), "quads", 4}};
-        RT_TRY(check_trace_ptrs(records, s->device, "rt_scene_update_quads"));
-    }
-    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
-    ++s->scene_epoch;                                // the cost map: as rt_scene_update_spheres
-    if (recalibrate) s->cost_map.valid = false;
-    rt_refit_params p = t.p;
-    p.count = u->count; p.first = u->first;
-    if (++t.quad_epoch == 0) { HIPCHK(hipMemsetAsync(p.quad_stamp, 0, (size_t)s->n_quads * 4, stream)); t.quad_epoch = 1; }
-    p.quad_epoch = t.quad_epoch;
-    if (u->indices) {
-        RT_TRY(grow(t.d_indices, t.indices_capacity, (size_t)u->count));
-        HIPCHK(hipMemcpyAsync(t.d_indices, u->indices, (size_t)u->count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        p.indices = t.d_indices;
-    }
-    if (quads_on_device) p.quad_records = u->quads;
-    else {
-        const size_t bytes = (size_t)u->count * sizeof(rt_quad);
-        RT_TRY(grow(t.d_records, t.records_capacity, (bytes + sizeof(rt_sphere) - 1) / sizeof(rt_sphere)));
-        HIPCHK(hipMemcpyAsync(t.d_records, u->quads, bytes, hipMemcpyHostToDevice, stream));
-        p.quad_records = reinterpret_cast<const rt_quad*>(t.d_records);
-    }
-    bool refused = false;
-    RT_TRY(run_refit(s, p, REFIT_QUADS, stream, recalibrate, refused));
-    if (refused) return invalid((who + "a device-resident record has a non-finite field or a material out of range; it was not stored, every other record was").c_str());
+rt_status rt_scene_get_quads(const rt_scene* s, rt_quad* out, int32_t cap) {
+    if (!s) return invalid("rt_scene_get_quads: null scene");
+    RT_TRY(get_records(s, rt_refit::QUADS, "rt_scene_get_quads", s->dev.quads, s->n_quads, out, cap));
+    for (int32_t i = 0; i < s->n_quads; ++i) out[i].pad0 = 0.0f;        // (the device keeps the axis code there)
     return RT_OK;
 }
 
@@ -1740,34 +1663,32 @@ rt_status rt_debug_scene_quads(const rt_scene* s, rt_quad* quads_out, int32_t qu
     return RT_OK;
 }
 
-rt_status rt_scene_get_quads(const rt_scene* s, rt_quad* out, int32_t cap) {
-    if (!s) return invalid("rt_scene_get_quads: null scene");
-    if (!out) return invalid("rt_scene_get_quads: null output pointer");
-    if (cap < s->n_quads) return invalid("rt_scene_get_quads: cap is below the scene's quad count");
-    RT_TRY(rt_debug_scene_quads(s, out, cap, nullptr, 0));
-    for (int32_t i = 0; i < s->n_quads; ++i) out[i].pad0 = 0.0f;        // (the device keeps the axis code there)
+rt_status rt_refit_nodes(const rt_scene_desc* d, const rt_sphere_update* u, rt_node* nodes_out, rt_sphere* spheres_out) {
+    RT_TRY(validate_desc(d));
+    const std::string why = rt_refit::check_update(u, true, d->n_spheres, d->n_materials, rt_refit::instanced_spheres(d->instances, d->n_instances, d->n_spheres));
+    if (!why.empty()) return invalid(("rt_refit_nodes: " + why).c_str());
+    std::vector<rt_sphere> spheres(d->spheres, d->spheres + d->n_spheres);
+    restate(d, rt_refit::SPHERES, u, spheres, spheres.data(), d->instances, d->quads, nodes_out, spheres_out);
+    return RT_OK;
+}
+
+rt_status rt_refit_instances(const rt_scene_desc* d, const rt_instance_update* u, rt_node* nodes_out, rt_instance* instances_out) {
+    RT_TRY(validate_desc(d));
+    std::vector<int32_t> children;
+    for (int i = 0; i < d->n_instances; ++i) children.push_back(d->instances[i].child);
+    const std::string why = rt_refit::check_instance_update(u, true, children.data(), d->n_instances);
+    if (!why.empty()) return invalid(("rt_refit_instances: " + why).c_str());
+    std::vector<rt_instance> instances(d->instances, d->instances + d->n_instances);
+    restate(d, rt_refit::INSTANCES, u, instances, d->spheres, instances.data(), d->quads, nodes_out, instances_out);
     return RT_OK;
 }
 
 rt_status rt_refit_quads(const rt_scene_desc* d, const rt_quad_update* u, rt_node* nodes_out, rt_quad* quads_out) {
-    bool so = false, uv = false;
-    int tx = 0;
-    RT_TRY(validate(d, so, tx, uv));
+    RT_TRY(validate_desc(d));
     const std::string why = rt_refit::check_quad_update(u, true, d->n_quads, d->n_materials);
     if (!why.empty()) return invalid(("rt_refit_quads: " + why).c_str());
     std::vector<rt_quad> quads(d->quads, d->quads + d->n_quads);
-    std::vector<char> moved((size_t)d->n_quads, 0);
-    for (int32_t k = 0; k < u->count; ++k) {
-        const int32_t i = u->indices ? u->indices[k] : u->first + k;
-        quads[(size_t)i] = u->quads[k];
-        moved[(size_t)i] = 1;
-    }
-    if (nodes_out) {
-        std::vector<rt_node> nodes(d->nodes, d->nodes + d->n_nodes);
-        rt_refit::refit_quad_nodes(nodes.data(), d, quads.data(), moved);
-        if (d->n_nodes) memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(rt_node));
-    }
-    if (quads_out && d->n_quads) memcpy(quads_out, quads.data(), quads.size() * sizeof(rt_quad));
+    restate(d, rt_refit::QUADS, u, quads, d->spheres, d->instances, quads.data(), nodes_out, quads_out);
     return RT_OK;
 }
 

@@ -503,23 +503,30 @@ struct rt_reproject_follow_quad_params : rt_reproject_follow_instance_params {
 };
 hipError_t rt_launch_reproject_quads(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_quad_params& qp, hipStream_t st);
 
-// rt_scene_update_spheres (rt_kernel_refit.hip; include/rt_abi.h): the moved spheres' records, their leaves'
-// boxes in every array that holds them, the per-64-leaf unions, the scene's coordinate bound and every interior box of both
-// node arrays, as four small launches on one stream.  The lookup tables are built by rt_abi.hip on a scene's first update.
-// rt_scene_update_instances runs on the same tables with a records and a leaf kernel of its own.
+// rt_scene_update_spheres, _instances and _quads (rt_kernel_refit.hip; include/rt_abi.h): the replaced
+// records, their leaves' boxes in every array that holds them, the per-64-leaf unions, the scene's coordinate bound and every
+// interior box of both node arrays, as a few small launches on one stream.  The lookup tables are built by rt_abi.hip on a
+// scene's first update.  One block serves the three kinds: `records`, `stamp` and `epoch` are those of the kind being updated
+// (rt_refit::kind, rt_refit_host.h), everything else is the scene's.
 #define RT_REFIT_THREADS 256
 struct rt_refit_params {
-    // the update: record k replaces sphere indices[k] (indices null: first + k); the indices were checked on the host
-    const rt_sphere* records;
+    // the update: record k replaces record indices[k] of its kind (indices null: first + k); the indices were checked on the host
+    const void* records;                  // rt_sphere, rt_instance or rt_quad: cast once, in the records kernel of the kind
     const int32_t* indices;
     int32_t count, first;
     int32_t n_materials;
-    uint32_t epoch;                       // stamp[i] == epoch: sphere i was replaced by this update
-    uint32_t* stamp;                      // per sphere
-    rt_sphere* spheres;                   // the scene's (rt_scene_dev.spheres)
+    uint32_t epoch;                       // stamp[i] == epoch: record i was replaced by this update
+    uint32_t* stamp;                      // per record of the kind; each kind has a stamp array and an epoch of its own
+    // the scene's records (rt_scene_dev), writable: a records kernel stores into the array of its kind (a quad with pad0 = the
+    // axis code), the marks kernel bit 30 of first_quad and nothing else; a leaf's box is computed from the records where they live
+    rt_sphere* spheres;
+    rt_instance* instances;
+    rt_quad* quads;
+    rt_box* boxes;
+    int32_t n_boxes;
     // the leaves, by ordinal q (depth-first order, the same in both node arrays)
     int32_t n_leaves, n_slots;
-    const int32_t* leaf_sphere;           // the sphere leaf q's box follows, or -1
+    const int32_t* leaf_solid;            // the solid leaf q's box follows (its primitive or its medium's boundary), or -1
     const int32_t* leaf_node_ref;         // leaf q's index in nodes_ref ...
     const int32_t* leaf_node_walk;        // ... and in the walk array
     float4* box_lo;                       // canonical leaf boxes, padded to whole slots (padding: zeros, in no union)
@@ -534,23 +541,6 @@ struct rt_refit_params {
     const int4* jobs;
     int32_t n_jobs;
     float* result;                        // [0..2] the scene's bound, [3] (as uint32) != 0: a record was refused on the device
-    // rt_scene_update_instances: count, first, indices as above; record k replaces instance indices[k]
-    const rt_instance* inst_records;
-    uint32_t inst_epoch;                  // inst_stamp[i] == inst_epoch: instance i was replaced by this update
-    uint32_t* inst_stamp;                 // per instance; apart from the spheres' stamps, with an epoch of its own
-    rt_instance* instances;               // the scene's (rt_scene_dev.instances)
-    const int32_t* leaf_instance;         // the instance leaf q's box follows, or -1
-    const rt_quad* quads;                 // the scene's: an instance's child box is computed from the records where they live
-    const rt_box* boxes;
-    // rt_scene_update_quads: count, first, indices as above; record k replaces quad indices[k]
-    const rt_quad* quad_records;
-    uint32_t quad_epoch;                  // quad_stamp[i] == quad_epoch: quad i was replaced by this update
-    int32_t n_boxes;
-    uint32_t* quad_stamp;                 // per quad; apart from the other two stamp arrays, with an epoch of its own
-    rt_quad* quads_rw;                    // the scene's quads and boxes again, writable: the records kernel stores quads (pad0 = the
-    rt_box* boxes_rw;                     // axis code), the marks kernel bit 30 of first_quad and nothing else
-    const int32_t* leaf_solid;            // the solid leaf q's box follows (its primitive or its medium's boundary), or -1
 };
-hipError_t rt_launch_refit(const rt_refit_params& p, hipStream_t st);             // a sphere update
-hipError_t rt_launch_refit_instances(const rt_refit_params& p, hipStream_t st);   // an instance update: two kernels of its own, then the same unions
-hipError_t rt_launch_refit_quads(const rt_refit_params& p, hipStream_t st);       // a quad update: records, box marks, leaves, then the same unions
+// kind: rt_refit::kind.  Records, (quads: box marks,) leaves, slots, interior
+hipError_t rt_launch_refit(const rt_refit_params& p, int kind, hipStream_t st);

@@ -1,19 +1,21 @@
-// rt_kernel_refit.hip -- the device half of rt_scene_update_spheres and rt_scene_update_instances (include/rt_abi.h; DESIGN.md
-// 4.15, 4.17): spheres or instances of a resident scene are replaced and every box that depends on them is recomputed where it
-// lives, with the topology of every array kept.
+// rt_kernel_refit.hip -- the device half of rt_scene_update_spheres, rt_scene_update_instances and rt_scene_update_quads
+// (include/rt_abi.h): spheres, instances or quads of a resident scene are replaced and every box that
+// depends on them is recomputed where it lives, with the topology of every array kept.
 //
-// Four launches on one stream, each complete before the next starts (that order is the only synchronisation there is):
-//   1. records   one lane per record: check it (device-resident records reach no host check), store it, stamp its sphere;
-//   2. leaves    one lane per leaf: a leaf whose sphere carries this update's stamp takes the box rule's box, written to the
-//                canonical leaf arrays, the tier arrays (xyz only) and the leaf's node in both node arrays;
+// One path for the three kinds: launches on one stream, each complete before the next starts (that order is the only
+// synchronisation there is):
+//   1. records   one lane per record: check it (device-resident records reach no host check), store it, stamp the record it
+//                replaces.  A kernel per kind: they differ in what they check and in what they store beside the record;
+//   1b. marks    quads only, one lane per box: the data rt_scene_create derives from quad records (the axis code in pad0, which
+//                the records kernel stores, and the canonical mark in bit 30 of first_quad) follow the records;
+//   2. leaves    one lane per leaf: a leaf whose solid depends on a record with this update's stamp (rt_refit::depends_on) takes
+//                its rule's box (rt_refit::solid_box), written to the canonical leaf arrays, the tier arrays (xyz only) and the
+//                leaf's node in both node arrays.  One kernel, instantiated per kind;
 //   3. slots     one wave per 64 leaves: the union of their boxes and their largest |coordinate|, by cross-lane min / max;
 //   4. interior  one wave per interior node of either array: the union over its leaf range [a, b) as partial head leaves, whole
 //                slots from step 3 and partial tail leaves -- at most 126 + (b - a) / 64 reads whatever the tree's shape --;
 //                one further wave reduces the slots' largest coordinates to the scene's bound.
-// An instance update runs steps 1 and 2 as kernels of its own (rt_refit_instance_records_kernel, _leaves_kernel) and steps 3 and
-// 4 unchanged.  A quad update (rt_scene_update_quads) does the same with rt_refit_quad_records_kernel and
-// rt_refit_quad_leaves_kernel and, between them, rt_refit_box_marks_kernel: the data rt_scene_create derives from quad records
-// (the axis code in pad0, the canonical mark in bit 30 of first_quad) follow the records.
+// Steps 3 and 4 do not care why a leaf's box changed.
 // Float min / max are exact, so no result depends on the order of a reduction (up to the sign of a zero).  No address depends
 // on record data: every index comes from the host's tables or from the index list the host has checked.
 // The render kernels read some of these arrays through the scalar cache (uniform_load, rt_device_funcs.h); that stays correct
@@ -52,7 +54,7 @@ __device__ inline void wave_union(box6& b) {
 __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_records_kernel(const rt_refit_params p) {
     const int k = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
     if (k >= p.count) return;
-    const rt_sphere rec = p.records[k];
+    const rt_sphere rec = static_cast<const rt_sphere*>(p.records)[k];
     if (!rt_refit::record_ok(rec, p.n_materials)) {
         atomicOr(reinterpret_cast<unsigned int*>(p.result) + 3, 1u);    // refused: the sphere, its stamp and its boxes stay
         return;
@@ -79,13 +81,19 @@ __device__ inline void store_leaf(const rt_refit_params& p, int q, const float l
     }
 }
 
+// One lane per leaf: a leaf whose solid depends on a record of KIND with this update's stamp takes its rule's box from the records
+// where they live (a sphere, a quad, the six quads of a box, or the instance rule over one of these).  Addresses: leaf_solid (the
+// host's table), the stored instance child, first_quad with its marks masked.
+template <int KIND>
 __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_leaves_kernel(const rt_refit_params p) {
     const int q = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
     if (q >= p.n_leaves) return;
-    const int si = p.leaf_sphere[q];
-    if (si < 0 || p.stamp[si] != p.epoch) return;
+    const int32_t solid = p.leaf_solid[q];
+    const uint32_t* stamp = p.stamp;
+    const uint32_t epoch = p.epoch;
+    if (!rt_refit::depends_on(KIND, solid, p.boxes, p.instances, [=](int i) { return stamp[i] == epoch; })) return;
     float lo[3], hi[3];
-    rt_refit::sphere_box(p.spheres[si], lo, hi);
+    rt_refit::solid_box(solid, p.spheres, p.quads, p.boxes, p.instances, lo, hi);
     store_leaf(p, q, lo, hi);
 }
 
@@ -95,26 +103,13 @@ __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_instance_records_ke
     const int k = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
     if (k >= p.count) return;
     const int i = p.indices ? p.indices[k] : p.first + k;                 // checked on the host: in range, each at most once
-    const rt_instance rec = p.inst_records[k];
+    const rt_instance rec = static_cast<const rt_instance*>(p.records)[k];
     if (!rt_refit::instance_record_ok(rec, p.instances[i].child)) {
         atomicOr(reinterpret_cast<unsigned int*>(p.result) + 3, 1u);    // refused: the instance, its stamp and its boxes stay
         return;
     }
     p.instances[i] = rec;
-    p.inst_stamp[i] = p.inst_epoch;
-}
-
-// One lane per leaf: the child's box from the records on the device (a sphere, a quad, or the six quads of a box), then the rule.
-__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_instance_leaves_kernel(const rt_refit_params p) {
-    const int q = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
-    if (q >= p.n_leaves) return;
-    const int ii = p.leaf_instance[q];
-    if (ii < 0 || p.inst_stamp[ii] != p.inst_epoch) return;
-    const rt_instance in = p.instances[ii];
-    float lo[3], hi[3];
-    rt_refit::child_box(in.child, p.spheres, p.quads, p.boxes, lo, hi);
-    rt_refit::instance_box(in, lo, hi);
-    store_leaf(p, q, lo, hi);
+    p.stamp[i] = p.epoch;
 }
 
 // ---- rt_scene_update_quads
@@ -122,15 +117,15 @@ __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_instance_leaves_ker
 __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_quad_records_kernel(const rt_refit_params p) {
     const int k = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
     if (k >= p.count) return;
-    rt_quad rec = p.quad_records[k];
+    rt_quad rec = static_cast<const rt_quad*>(p.records)[k];
     if (!rt_refit::quad_record_ok(rec, p.n_materials)) {
         atomicOr(reinterpret_cast<unsigned int*>(p.result) + 3, 1u);    // refused: the quad, its stamp, its boxes and marks stay
         return;
     }
     const int i = p.indices ? p.indices[k] : p.first + k;                 // checked on the host: in range, each at most once
     rec.pad0 = __int_as_float(rt_refit::axis_code(rec));
-    p.quads_rw[i] = rec;
-    p.quad_stamp[i] = p.quad_epoch;
+    p.quads[i] = rec;
+    p.stamp[i] = p.epoch;
 }
 
 // One lane per box, after every record is stored (a launch of its own: box ranges may overlap, and a lane that stores one face
@@ -138,26 +133,12 @@ __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_quad_records_kernel
 __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_box_marks_kernel(const rt_refit_params p) {
     const int b = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
     if (b >= p.n_boxes) return;
-    const int32_t word = p.boxes_rw[b].first_quad, first = word & RT_BOX_FIRST_MASK;
+    const int32_t word = p.boxes[b].first_quad, first = word & RT_BOX_FIRST_MASK;
     int32_t codes[6];
 #pragma unroll
     for (int f = 0; f < 6; ++f) codes[f] = __float_as_int(p.quads[first + f].pad0);
     const int32_t marked = rt_refit::canonical_codes(codes) ? (word | RT_BOX_CANONICAL) : (word & ~RT_BOX_CANONICAL);
-    if (marked != word) p.boxes_rw[b].first_quad = marked;
-}
-
-// One lane per leaf: a leaf whose solid depends on a quad with this update's stamp takes its rule's box from the records where
-// they live.  Addresses: leaf_solid (the host's table), the stored instance child, first_quad with its marks masked.
-__global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_quad_leaves_kernel(const rt_refit_params p) {
-    const int q = (int)(blockIdx.x * RT_REFIT_THREADS + threadIdx.x);
-    if (q >= p.n_leaves) return;
-    const int32_t solid = p.leaf_solid[q];
-    const uint32_t* stamp = p.quad_stamp;
-    const uint32_t epoch = p.quad_epoch;
-    if (!rt_refit::solid_moved(solid, p.boxes, p.instances, [=](int i) { return stamp[i] == epoch; })) return;
-    float lo[3], hi[3];
-    rt_refit::solid_box(solid, p.spheres, p.quads, p.boxes, p.instances, lo, hi);
-    store_leaf(p, q, lo, hi);
+    if (marked != word) p.boxes[b].first_quad = marked;
 }
 
 __global__ __launch_bounds__(RT_REFIT_THREADS) void rt_refit_slots_kernel(const rt_refit_params p) {
@@ -220,35 +201,17 @@ inline unsigned int blocks_for(long long items, int per_block) { return (unsigne
 
 }  // namespace
 
-// steps 3 and 4: they do not care why a leaf's box changed
-static void launch_unions(const rt_refit_params& p, hipStream_t st) {
-    const int waves = RT_REFIT_THREADS / 64;
-    if (p.n_slots > 0) hipLaunchKernelGGL(rt_refit_slots_kernel, dim3(blocks_for(p.n_slots, waves)), dim3(RT_REFIT_THREADS), 0, st, p);
-    hipLaunchKernelGGL(rt_refit_interior_kernel, dim3(blocks_for((long long)p.n_jobs + 1, waves)), dim3(RT_REFIT_THREADS), 0, st, p);
-}
-
-hipError_t rt_launch_refit(const rt_refit_params& p, hipStream_t st) {
-    if (p.count > 0) hipLaunchKernelGGL(rt_refit_records_kernel, dim3(blocks_for(p.count, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
-    if (p.count > 0 && p.n_leaves > 0)
-        hipLaunchKernelGGL(rt_refit_leaves_kernel, dim3(blocks_for(p.n_leaves, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
-    launch_unions(p, st);
-    return hipGetLastError();
-}
-
-hipError_t rt_launch_refit_instances(const rt_refit_params& p, hipStream_t st) {
-    if (p.count > 0) hipLaunchKernelGGL(rt_refit_instance_records_kernel, dim3(blocks_for(p.count, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
-    if (p.count > 0 && p.n_leaves > 0)
-        hipLaunchKernelGGL(rt_refit_instance_leaves_kernel, dim3(blocks_for(p.n_leaves, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
-    launch_unions(p, st);
-    return hipGetLastError();
-}
-
-hipError_t rt_launch_refit_quads(const rt_refit_params& p, hipStream_t st) {
-    if (p.count > 0) hipLaunchKernelGGL(rt_refit_quad_records_kernel, dim3(blocks_for(p.count, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
-    if (p.count > 0 && p.n_boxes > 0)
-        hipLaunchKernelGGL(rt_refit_box_marks_kernel, dim3(blocks_for(p.n_boxes, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
-    if (p.count > 0 && p.n_leaves > 0)
-        hipLaunchKernelGGL(rt_refit_quad_leaves_kernel, dim3(blocks_for(p.n_leaves, RT_REFIT_THREADS)), dim3(RT_REFIT_THREADS), 0, st, p);
-    launch_unions(p, st);
+hipError_t rt_launch_refit(const rt_refit_params& p, int kind, hipStream_t st) {
+    const dim3 threads(RT_REFIT_THREADS);
+    const auto records = kind == rt_refit::QUADS ? rt_refit_quad_records_kernel : kind == rt_refit::INSTANCES ? rt_refit_instance_records_kernel : rt_refit_records_kernel;
+    const auto leaves = kind == rt_refit::QUADS ? rt_refit_leaves_kernel<rt_refit::QUADS>
+                        : kind == rt_refit::INSTANCES ? rt_refit_leaves_kernel<rt_refit::INSTANCES> : rt_refit_leaves_kernel<rt_refit::SPHERES>;
+    if (p.count > 0) hipLaunchKernelGGL(records, dim3(blocks_for(p.count, RT_REFIT_THREADS)), threads, 0, st, p);
+    if (kind == rt_refit::QUADS && p.count > 0 && p.n_boxes > 0)
+        hipLaunchKernelGGL(rt_refit_box_marks_kernel, dim3(blocks_for(p.n_boxes, RT_REFIT_THREADS)), threads, 0, st, p);
+    if (p.count > 0 && p.n_leaves > 0) hipLaunchKernelGGL(leaves, dim3(blocks_for(p.n_leaves, RT_REFIT_THREADS)), threads, 0, st, p);
+    const int waves = RT_REFIT_THREADS / 64;                            // steps 3 and 4
+    if (p.n_slots > 0) hipLaunchKernelGGL(rt_refit_slots_kernel, dim3(blocks_for(p.n_slots, waves)), threads, 0, st, p);
+    hipLaunchKernelGGL(rt_refit_interior_kernel, dim3(blocks_for((long long)p.n_jobs + 1, waves)), threads, 0, st, p);
     return hipGetLastError();
 }

@@ -170,46 +170,31 @@ rt_status rt_multi_create(const rt_scene_desc* desc, int n_gpus, rt_multi** out)
 
 int32_t rt_multi_device_count(const rt_multi* m) { return m ? m->n : 0; }
 
-// rt_scene_set_camera on every replica (its checks run in the first of these calls, before any HIP call); device 0 last, so
-// that it stays the current device
+// One call on every replica; device 0 last, so that it stays the current device.  The call's checks run in the first of these
+// calls, before any HIP call, and a refusal there leaves every replica untouched.
+extern "C++" template <class Call>
+static rt_status on_every_replica(rt_multi* m, const char* null_handle, Call&& call) {
+    if (!m) { rt_internal_set_error(RT_ERR_INVALID, 0, null_handle); return RT_ERR_INVALID; }
+    for (int d = m->n - 1; d >= 0; --d) {
+        const rt_status st = call(m->scenes[d]);
+        if (st != RT_OK) return st;
+    }
+    return RT_OK;
+}
+
 rt_status rt_multi_set_camera(rt_multi* m, const rt_camera* camera, int recalibrate) {
-    if (!m) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_set_camera: null rt_multi"); return RT_ERR_INVALID; }
-    for (int d = m->n - 1; d >= 0; --d) {
-        const rt_status st = rt_scene_set_camera(m->scenes[d], camera, recalibrate);
-        if (st != RT_OK) return st;
-    }
-    return RT_OK;
+    return on_every_replica(m, "rt_multi_set_camera: null rt_multi", [&](rt_scene* s) { return rt_scene_set_camera(s, camera, recalibrate); });
 }
 
-// rt_scene_update_spheres with host records on every replica (its checks run in the first of these calls, before any HIP call,
-// and a refusal there leaves every replica untouched); each replica's default stream; device 0 last, so that it stays current
+// rt_scene_update_spheres, _instances, _quads with host records on every replica; each replica's default stream
 rt_status rt_multi_update_spheres(rt_multi* m, const rt_sphere_update* update, int recalibrate) {
-    if (!m) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_update_spheres: null rt_multi"); return RT_ERR_INVALID; }
-    for (int d = m->n - 1; d >= 0; --d) {
-        const rt_status st = rt_scene_update_spheres(m->scenes[d], update, 0, recalibrate, nullptr);
-        if (st != RT_OK) return st;
-    }
-    return RT_OK;
+    return on_every_replica(m, "rt_multi_update_spheres: null rt_multi", [&](rt_scene* s) { return rt_scene_update_spheres(s, update, 0, recalibrate, nullptr); });
 }
-
-// rt_scene_update_instances with host records on every replica, as rt_multi_update_spheres
 rt_status rt_multi_update_instances(rt_multi* m, const rt_instance_update* update, int recalibrate) {
-    if (!m) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_update_instances: null rt_multi"); return RT_ERR_INVALID; }
-    for (int d = m->n - 1; d >= 0; --d) {
-        const rt_status st = rt_scene_update_instances(m->scenes[d], update, 0, recalibrate, nullptr);
-        if (st != RT_OK) return st;
-    }
-    return RT_OK;
+    return on_every_replica(m, "rt_multi_update_instances: null rt_multi", [&](rt_scene* s) { return rt_scene_update_instances(s, update, 0, recalibrate, nullptr); });
 }
-
-// rt_scene_update_quads with host records on every replica, as rt_multi_update_spheres
 rt_status rt_multi_update_quads(rt_multi* m, const rt_quad_update* update, int recalibrate) {
-    if (!m) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_update_quads: null rt_multi"); return RT_ERR_INVALID; }
-    for (int d = m->n - 1; d >= 0; --d) {
-        const rt_status st = rt_scene_update_quads(m->scenes[d], update, 0, recalibrate, nullptr);
-        if (st != RT_OK) return st;
-    }
-    return RT_OK;
+    return on_every_replica(m, "rt_multi_update_quads: null rt_multi", [&](rt_scene* s) { return rt_scene_update_quads(s, update, 0, recalibrate, nullptr); });
 }
 
 rt_status rt_multi_row_owner(int32_t global_row, int32_t tile_rows, int32_t n_gpus, int32_t* device, int32_t* local_row) {

@@ -1,7 +1,8 @@
 // rt_refit_host.h -- the host half of rt_scene_update_spheres, rt_scene_update_instances and rt_scene_update_quads
-// (include/rt_abi.h): the box rules, the checks of an update and the refit of a node array in the description's link encoding.  Plain C++ with no HIP call, so that
-// rt_refit_nodes needs no device and the same text compiles into a stand-alone host program; rt_kernel_refit.hip takes the
-// box rule from here too, so host and device cannot drift apart.
+// (include/rt_abi.h): the box rules, the checks of an update and the refit of a node array in the
+// description's link encoding.  Plain C++ with no HIP call, so that rt_refit_nodes needs no device and the same text compiles
+// into a stand-alone host program; rt_kernel_refit.hip takes the box rules and the question "does this leaf follow a replaced
+// record?" from here too, so host and device cannot drift apart.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -19,6 +20,16 @@
 #endif
 
 namespace rt_refit {
+
+// The kinds of record an update replaces.  One path serves all three (the checks below, refit_nodes, the kernels of
+// rt_kernel_refit.hip, update_records of rt_abi.hip); what differs per kind is what a record must satisfy, what is stored beside
+// it, and which leaves follow it (depends_on).
+enum kind { SPHERES, INSTANCES, QUADS, KINDS };
+struct noun { const char *one, *a_one, *many; };
+static const noun NOUNS[KINDS] = {{"sphere", "a sphere", "spheres"}, {"instance", "an instance", "instances"}, {"quad", "a quad", "quads"}};
+inline const rt_sphere* records_of(const rt_sphere_update& u) { return u.spheres; }
+inline const rt_instance* records_of(const rt_instance_update& u) { return u.instances; }
+inline const rt_quad* records_of(const rt_quad_update& u) { return u.quads; }
 
 // The box rule (rt_abi.h): r = |radius|, a = c0 + 0 vel, b = c0 + 1 vel, lo = min(a - r, b - r), hi = max(a + r, b + r), every
 // operation a binary32 one rounded once (the build has contraction off; a contracted form would round the same: 0 vel and
@@ -41,21 +52,6 @@ RT_REFIT_HD inline bool record_ok(const rt_sphere& s, int32_t n_materials) {
     return finite && s.mat >= 0 && s.mat < n_materials;
 }
 
-// The sphere a leaf's box follows: the leaf's own sphere, or the sphere that is the boundary of the leaf's constant_medium
-// directly; -1 for every other leaf (quads, boxes, instances, media bounded by anything else), which keeps its box.
-inline int32_t leaf_sphere(int32_t prim, const rt_medium* media, int32_t n_media, int32_t n_spheres) {
-    if (prim < 0) return -1;
-    if (RT_PRIM_KIND(prim) == RT_PRIM_MEDIUM) {
-        const int m = RT_PRIM_INDEX(prim);
-        if (m >= n_media) return -1;
-        prim = media[m].boundary;
-        if (prim < 0) return -1;
-    }
-    if (RT_PRIM_KIND(prim) != RT_PRIM_SPHERE) return -1;
-    const int i = RT_PRIM_INDEX(prim);
-    return i < n_spheres ? i : -1;
-}
-
 // per sphere: whether it is the child of an instance (its box then follows the instance's rule, which an update does not redo)
 inline std::vector<char> instanced_spheres(const rt_instance* instances, int32_t n_instances, int32_t n_spheres) {
     std::vector<char> under((size_t)(n_spheres > 0 ? n_spheres : 0), 0);
@@ -66,30 +62,41 @@ inline std::vector<char> instanced_spheres(const rt_instance* instances, int32_t
     return under;
 }
 
-// The refusals of an update (rt_abi.h), none of which needs a device: null or empty text = fine.  host_records: the records
-// can be read here (their values are checked); device-resident records are checked by the leaf kernel instead.
-inline std::string check_update(const rt_sphere_update* u, bool host_records, int32_t n_spheres, int32_t n_materials,
-                                const std::vector<char>& instanced) {
+// The refusals every kind of update shares (rt_abi.h), none of which needs a device: null or empty text = fine.  n: the scene's
+// count of the kind.  per_record(record, i) is asked about record k, which replaces record i of the scene, as soon as index k
+// has passed -- before index k + 1 is looked at -- and answers with the refusal's text or null (no string is built per record:
+// an update may carry every record of a large scene).
+template <class Update, class PerRecord>
+inline std::string check_indices(const Update* u, const noun& w, int32_t n, PerRecord&& per_record) {
     if (!u) return "null update";
     if (u->count < 0) return "count is negative";
     if (u->count == 0) return "";
-    if (!u->spheres) return "null sphere records";
-    if (u->count > n_spheres) return "more records than the scene has spheres (an index is out of range or appears twice)";
-    std::vector<char> seen((size_t)n_spheres, 0);
+    if (!records_of(*u)) return std::string("null ") + w.one + " records";
+    if (u->count > n) return std::string("more records than the scene has ") + w.many + " (an index is out of range or appears twice)";
+    std::vector<char> seen((size_t)n, 0);
     for (int32_t k = 0; k < u->count; ++k) {
         const long long i = u->indices ? (long long)u->indices[k] : (long long)u->first + k;
-        if (i < 0 || i >= n_spheres) return "sphere index out of range";
-        if (seen[(size_t)i]) return "a sphere index appears twice";
+        if (i < 0 || i >= n) return std::string(w.one) + " index out of range";
+        if (seen[(size_t)i]) return std::string(w.a_one) + " index appears twice";
         seen[(size_t)i] = 1;
-        if (instanced[(size_t)i]) return "an updated sphere is the child of an instance (its box follows the instance's rule)";
-        if (host_records) {
-            const rt_sphere& s = u->spheres[k];
-            const rt_sphere geometry = {{s.c0[0], s.c0[1], s.c0[2]}, s.radius, {s.vel[0], s.vel[1], s.vel[2]}, 0};
-            if (!record_ok(geometry, 1)) return "a sphere record has a non-finite c0, vel or radius";
-            if (s.mat < 0 || s.mat >= n_materials) return "sphere material out of range";
-        }
+        if (const char* why = per_record(records_of(*u)[k], (int32_t)i)) return why;
     }
     return "";
+}
+
+// The refusals of a sphere update.  host_records: the records can be read here (their values are checked); device-resident
+// records are checked by the records kernel instead.
+inline std::string check_update(const rt_sphere_update* u, bool host_records, int32_t n_spheres, int32_t n_materials,
+                                const std::vector<char>& instanced) {
+    const char* under = instanced.data();
+    return check_indices(u, NOUNS[SPHERES], n_spheres, [=](const rt_sphere& s, int32_t i) -> const char* {
+        if (under[i]) return "an updated sphere is the child of an instance (its box follows the instance's rule)";
+        if (!host_records) return nullptr;
+        const rt_sphere geometry = {{s.c0[0], s.c0[1], s.c0[2]}, s.radius, {s.vel[0], s.vel[1], s.vel[2]}, 0};
+        if (!record_ok(geometry, 1)) return "a sphere record has a non-finite c0, vel or radius";
+        if (s.mat < 0 || s.mat >= n_materials) return "sphere material out of range";
+        return nullptr;
+    });
 }
 
 // ---- instances (rt_scene_update_instances).  The rule is the host library's constructors restated operation by
@@ -153,43 +160,16 @@ RT_REFIT_HD inline bool instance_record_ok(const rt_instance& in, int32_t scene_
     return instance_finite(in) && in.flags >= 1 && in.flags <= 3 && in.child == scene_child;
 }
 
-// The instance a leaf's box follows: the leaf's own instance, or the instance that is the boundary of the leaf's constant_medium
-// directly; -1 for every other leaf.
-inline int32_t leaf_instance(int32_t prim, const rt_medium* media, int32_t n_media, int32_t n_instances) {
-    if (prim < 0) return -1;
-    if (RT_PRIM_KIND(prim) == RT_PRIM_MEDIUM) {
-        const int m = RT_PRIM_INDEX(prim);
-        if (m >= n_media) return -1;
-        prim = media[m].boundary;
-        if (prim < 0) return -1;
-    }
-    if (RT_PRIM_KIND(prim) != RT_PRIM_INSTANCE) return -1;
-    const int i = RT_PRIM_INDEX(prim);
-    return i < n_instances ? i : -1;
-}
-
 // The refusals of an instance update (rt_abi.h), as check_update.  children: per instance, the child the scene holds.
 inline std::string check_instance_update(const rt_instance_update* u, bool host_records, const int32_t* children, int32_t n_instances) {
-    if (!u) return "null update";
-    if (u->count < 0) return "count is negative";
-    if (u->count == 0) return "";
-    if (!u->instances) return "null instance records";
-    if (u->count > n_instances) return "more records than the scene has instances (an index is out of range or appears twice)";
-    std::vector<char> seen((size_t)n_instances, 0);
-    for (int32_t k = 0; k < u->count; ++k) {
-        const long long i = u->indices ? (long long)u->indices[k] : (long long)u->first + k;
-        if (i < 0 || i >= n_instances) return "instance index out of range";
-        if (seen[(size_t)i]) return "an instance index appears twice";
-        seen[(size_t)i] = 1;
-    }
-    if (host_records) {   // (after every index has passed: a record is compared with the instance it names)
-        for (int32_t k = 0; k < u->count; ++k) {
-            const int32_t i = u->indices ? u->indices[k] : u->first + k;
-            const rt_instance& in = u->instances[k];
-            if (!instance_finite(in)) return "an instance record has a non-finite sin_t, cos_t or offset";
-            if (in.flags < 1 || in.flags > 3) return "instance flags must be 1, 2 or 3";
-            if (in.child != children[(size_t)i]) return "an instance record's child is not the child the scene holds (the child of an instance cannot change)";
-        }
+    const std::string why = check_indices(u, NOUNS[INSTANCES], n_instances, [](const rt_instance&, int32_t) -> const char* { return nullptr; });
+    if (!why.empty() || !u || u->count <= 0 || !host_records) return why;
+    for (int32_t k = 0; k < u->count; ++k) {   // (after every index has passed: a record is compared with the instance it names)
+        const int32_t i = u->indices ? u->indices[k] : u->first + k;
+        const rt_instance& in = u->instances[k];
+        if (!instance_finite(in)) return "an instance record has a non-finite sin_t, cos_t or offset";
+        if (in.flags < 1 || in.flags > 3) return "instance flags must be 1, 2 or 3";
+        if (in.child != children[(size_t)i]) return "an instance record's child is not the child the scene holds (the child of an instance cannot change)";
     }
     return "";
 }
@@ -213,26 +193,6 @@ inline void refit_nodes(rt_node* nodes, int32_t n, LeafRule&& leaf_rule) {
             first = false;
         }
     }
-}
-
-// the leaves whose sphere is marked in `moved` take the sphere rule's box of spheres[...]
-inline void refit_nodes(rt_node* nodes, int32_t n, const rt_sphere* spheres, int32_t n_spheres, const rt_medium* media, int32_t n_media,
-                        const std::vector<char>& moved) {
-    refit_nodes(nodes, n, [&](int32_t prim, float* lo, float* hi) {
-        const int32_t si = leaf_sphere(prim, media, n_media, n_spheres);
-        if (si >= 0 && moved[(size_t)si]) sphere_box(spheres[si], lo, hi);
-    });
-}
-
-// the leaves whose instance is marked in `moved` take the instance rule's box of instances[...] (of the description `d`, whose
-// references rt_scene_create's checks have validated)
-inline void refit_instance_nodes(rt_node* nodes, const rt_scene_desc* d, const rt_instance* instances, const std::vector<char>& moved) {
-    refit_nodes(nodes, d->n_nodes, [&](int32_t prim, float* lo, float* hi) {
-        const int32_t ii = leaf_instance(prim, d->media, d->n_media, d->n_instances);
-        if (ii < 0 || !moved[(size_t)ii]) return;
-        child_box(instances[ii].child, d->spheres, d->quads, d->boxes, lo, hi);
-        instance_box(instances[ii], lo, hi);
-    });
 }
 
 // ---- quads and boxes (rt_scene_update_quads).  The boxes are quad_box / box_box / child_box / instance_box above;
@@ -303,6 +263,14 @@ RT_REFIT_HD inline bool solid_moved(int32_t solid, const rt_box* boxes, const rt
     for (int f = 0; f < 6; ++f) any = any || moved(first + f);
     return any;
 }
+// Whether a solid depends on a record of `kind` for which moved(i) holds.  A sphere update moves the solid that is that sphere
+// and never looks through an instance (check_update refuses an instanced sphere: its box follows the instance's rule); an
+// instance update moves the solid that is that instance; a quad update moves what solid_moved says.
+template <class Moved>
+RT_REFIT_HD inline bool depends_on(int kind, int32_t solid, const rt_box* boxes, const rt_instance* instances, Moved&& moved) {
+    if (kind == QUADS) return solid_moved(solid, boxes, instances, moved);
+    return solid >= 0 && (int)RT_PRIM_KIND(solid) == (kind == SPHERES ? RT_PRIM_SPHERE : RT_PRIM_INSTANCE) && moved((int)RT_PRIM_INDEX(solid));
+}
 // the box of a solid by the rules of rt_abi.h: the sphere, quad and box rules, and the instance rule over its child's box
 RT_REFIT_HD inline void solid_box(int32_t solid, const rt_sphere* spheres, const rt_quad* quads, const rt_box* boxes, const rt_instance* instances,
                                   float lo[3], float hi[3]) {
@@ -315,32 +283,23 @@ RT_REFIT_HD inline void solid_box(int32_t solid, const rt_sphere* spheres, const
 
 // The refusals of a quad update (rt_abi.h), as check_update.
 inline std::string check_quad_update(const rt_quad_update* u, bool host_records, int32_t n_quads, int32_t n_materials) {
-    if (!u) return "null update";
-    if (u->count < 0) return "count is negative";
-    if (u->count == 0) return "";
-    if (!u->quads) return "null quad records";
-    if (u->count > n_quads) return "more records than the scene has quads (an index is out of range or appears twice)";
-    std::vector<char> seen((size_t)n_quads, 0);
-    for (int32_t k = 0; k < u->count; ++k) {
-        const long long i = u->indices ? (long long)u->indices[k] : (long long)u->first + k;
-        if (i < 0 || i >= n_quads) return "quad index out of range";
-        if (seen[(size_t)i]) return "a quad index appears twice";
-        seen[(size_t)i] = 1;
-        if (host_records) {
-            if (!quad_finite(u->quads[k])) return "a quad record has a non-finite Q, D, u, v, w or n";
-            if (u->quads[k].mat < 0 || u->quads[k].mat >= n_materials) return "quad material out of range";
-        }
-    }
-    return "";
+    return check_indices(u, NOUNS[QUADS], n_quads, [=](const rt_quad& q, int32_t) -> const char* {
+        if (!host_records) return nullptr;
+        if (!quad_finite(q)) return "a quad record has a non-finite Q, D, u, v, w or n";
+        if (q.mat < 0 || q.mat >= n_materials) return "quad material out of range";
+        return nullptr;
+    });
 }
 
-// the leaves whose solid depends on a quad marked in `moved` take their rule's box over quads[...] (of the description `d`, whose
-// references rt_scene_create's checks have validated)
-inline void refit_quad_nodes(rt_node* nodes, const rt_scene_desc* d, const rt_quad* quads, const std::vector<char>& moved) {
+// The leaves whose solid depends on a record of `kind` marked in `moved` take their rule's box over spheres[...], instances[...]
+// and quads[...]: the arrays of the description `d`, whose references rt_scene_create's checks have validated, with the update's
+// records in place.
+inline void refit_nodes(rt_node* nodes, const rt_scene_desc* d, const rt_sphere* spheres, const rt_instance* instances, const rt_quad* quads,
+                        int kind, const std::vector<char>& moved) {
     refit_nodes(nodes, d->n_nodes, [&](int32_t prim, float* lo, float* hi) {
         const int32_t solid = leaf_solid(prim, d->media, d->n_media, d->n_spheres, d->n_quads, d->n_boxes, d->n_instances);
-        if (!solid_moved(solid, d->boxes, d->instances, [&](int i) { return moved[(size_t)i] != 0; })) return;
-        solid_box(solid, d->spheres, quads, d->boxes, d->instances, lo, hi);
+        if (!depends_on(kind, solid, d->boxes, instances, [&](int i) { return moved[(size_t)i] != 0; })) return;
+        solid_box(solid, spheres, quads, d->boxes, instances, lo, hi);
     });
 }
 

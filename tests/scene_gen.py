@@ -489,6 +489,20 @@ def _limits(name, rng, nx, ny, seed):
     return b.finish(name, _camera(rng, nx, ny, lens=False, shutter=(0.0, 1.0)), nx, ny, gradient=1)
 
 
+def tiny(nx: int = 48, ny: int = 32) -> GenScene:
+    """Three sphere leaves, three instances (each of a quad of its own) and a free quad: three spheres, three instances, four quads."""
+    rng = np.random.default_rng(0)
+    b = Builder(rng)
+    mat = b.lambertian()
+    for k in range(3):
+        b.leaf(b.sphere((k - 1.0, 0.4, 0.0), 0.4, mat))
+    for k in range(3):
+        child = b.quad((-0.3, 0, 0), (0.6 + 0.1 * k, 0, 0), (0, 0.6, 0), mat)
+        b.leaf(b.instance(child, ROTATE_Y | TRANSLATE, 20.0 * k, (k - 1.0, 0, 1.5)))
+    b.leaf(b.quad((-2, 0.05, -2), (4, 0, 0), (0, 0, 4), mat))
+    return b.finish("tiny", _camera(rng, nx, ny), nx, ny)
+
+
 def generate(recipe: str, seed: int, nx: int = 48, ny: int = 32) -> GenScene:
     rng = np.random.default_rng([RECIPES.index(recipe), seed])
     name = f"{recipe}/{seed}"

@@ -144,40 +144,55 @@ def test_refusals_name_the_check_and_write_nothing(art):
     ids = ri.followed(scene)
     nodes_out, inst_out = np.full(len(scene.nodes()), 7, np.uint8).repeat(32), np.full(len(inst), 7, np.uint8).repeat(32)
 
-    def refused(match, rec, idx=None, first=0, count=None):
+    def refused(why, rec, idx=None, first=0, count=None, on=scene):
         u = art.RtInstanceUpdate()
         rec = np.ascontiguousarray(rec)
         u.count, u.first = len(rec) if count is None else count, first
         u.instances = rec.ctypes.data if len(rec) else None
         keep = None if idx is None else np.ascontiguousarray(idx, np.int32)
         u.indices = None if keep is None else keep.ctypes.data
-        assert L.rt_refit_instances(C.byref(scene.desc), C.byref(u), nodes_out.ctypes.data, inst_out.ctypes.data) == 1
-        detail = L.rt_last_error_detail().decode()
-        assert detail.startswith("rt_refit_instances: ") and match in detail, detail
+        assert L.rt_refit_instances(C.byref(on.desc), C.byref(u), nodes_out.ctypes.data, inst_out.ctypes.data) == 1
+        assert L.rt_last_error_detail().decode() == why
         assert (nodes_out == 7).all() and (inst_out == 7).all()
 
+    NON_FINITE, FLAGS = "rt_refit_instances: an instance record has a non-finite sin_t, cos_t or offset", "rt_refit_instances: instance flags must be 1, 2 or 3"
+    CHILD = "rt_refit_instances: an instance record's child is not the child the scene holds (the child of an instance cannot change)"
+    RANGE, TWICE = "rt_refit_instances: instance index out of range", "rt_refit_instances: an instance index appears twice"
+    MORE = "rt_refit_instances: more records than the scene has instances (an index is out of range or appears twice)"
     one = inst[ids[:1]]
     assert L.rt_refit_instances(C.byref(scene.desc), None, nodes_out.ctypes.data, inst_out.ctypes.data) == 1
-    assert "null update" in L.rt_last_error_detail().decode()
+    assert L.rt_last_error_detail().decode() == "rt_refit_instances: null update"
     assert L.rt_refit_instances(None, None, None, None) == 1
-    refused("count is negative", one, count=-1)
-    refused("null instance records", inst[:0], count=1)
-    refused("out of range", one, idx=[len(inst)])
-    refused("out of range", one, idx=[-1])
-    refused("out of range", inst[:2], first=len(inst) - 1)
-    refused("twice", inst[ids[[0, 1, 0]]], idx=ids[[0, 1, 0]])
+    refused("rt_refit_instances: count is negative", one, count=-1)
+    refused("rt_refit_instances: null instance records", inst[:0], count=1)
+    refused(RANGE, one, idx=[len(inst)])
+    refused(RANGE, one, idx=[-1])
+    refused(RANGE, inst[:2], first=len(inst) - 1)
+    refused(TWICE, inst[ids[[0, 1, 0]]], idx=ids[[0, 1, 0]])
     for field, value in (("sin_t", np.nan), ("cos_t", np.inf), ("offset", -np.inf)):
         bad = one.copy()
         bad[field] = value
-        refused("non-finite", bad, idx=ids[:1])
+        refused(NON_FINITE, bad, idx=ids[:1])
     for flags in (0, 4, -1):
         bad = one.copy()
         bad["flags"] = flags
-        refused("flags must be 1, 2 or 3", bad, idx=ids[:1])
+        refused(FLAGS, bad, idx=ids[:1])
+    # two faults at once, on three instances: records are looked at after every index has passed, the count before any index
+    tiny = sg.tiny()
+    few = tiny.instances()
+    assert len(few) == 3 and len(set(few["child"])) == 3
+    for field, value in (("sin_t", np.nan), ("flags", 0), ("child", few["child"][2])):
+        bad = few[[0, 1]]
+        bad[field][0] = value
+        refused(RANGE, bad, idx=[0, 3], on=tiny)                      # record 0 is bad, index 1 is out of range
+        bad = few[[0, 1, 0]]
+        bad[field][1] = value
+        refused(TWICE, bad, idx=[0, 1, 0], on=tiny)                   # record 1 is bad, index 0 comes again as index 2
+    refused(MORE, few[[0, 0, 1, 2]], idx=[3, 0, 1, 2], on=tiny)       # too many records, index 0 is out of range
     bad = one.copy()
     bad["child"] = inst["child"][ids[1]] if inst["child"][ids[1]] != one["child"][0] else inst["child"][ids[2]]
     assert bad["child"][0] != one["child"][0]
-    refused("child", bad, idx=ids[:1])
+    refused(CHILD, bad, idx=ids[:1])
     with pytest.raises(ValueError, match="child"):
         art.refit_instances(scene.desc, bad, ids[:1])
     with pytest.raises(ValueError, match="INSTANCE_DTYPE"):

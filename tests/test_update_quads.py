@@ -278,8 +278,10 @@ def test_every_other_entry_equals_a_fresh_scene(gpu, orc, name):
 
 
 # per case: whether the scene has tier data (None: a generated scene says so itself).  instanced: 128 leaves in two tier slots,
-# so that the root meets whole slots; crowd_big: head, whole-slot and tail paths of the interior kernel, no tier data
-ARRAY_CASES = {"general": None, "limits": None, "cornell": True, "instanced": True, "crowd_big": False}
+# so that the root meets whole slots; crowd_big: head, whole-slot and tail paths of the interior kernel, no tier data.  Between them
+# the cases update a leaf of every way a solid depends on a quad -- general: a free quad, a box face, an instance of a quad, an
+# instance of a box, a medium bounded by a box; general4 (40 leaves): a medium bounded by an instance of a box
+ARRAY_CASES = {"general": None, "general4": None, "limits": None, "cornell": True, "instanced": True, "crowd_big": False}
 
 
 @pytest.mark.parametrize("name", list(ARRAY_CASES))

@@ -188,39 +188,52 @@ def test_refusals_name_the_check_and_write_nothing(art):
     quads = scene.quads()
     nodes_out, quads_out = np.full(len(scene.nodes()), 7, np.uint8).repeat(32), np.full(len(quads), 7, np.uint8).repeat(80)
 
-    def refused(match, rec, idx=None, first=0, count=None):
+    def refused(why, rec, idx=None, first=0, count=None, on=scene):
         u = art.RtQuadUpdate()
         rec = np.ascontiguousarray(rec)
         u.count, u.first = len(rec) if count is None else count, first
         u.quads = rec.ctypes.data if len(rec) else None
         keep = None if idx is None else np.ascontiguousarray(idx, np.int32)
         u.indices = None if keep is None else keep.ctypes.data
-        assert L.rt_refit_quads(C.byref(scene.desc), C.byref(u), nodes_out.ctypes.data, quads_out.ctypes.data) == 1
-        detail = L.rt_last_error_detail().decode()
-        assert detail.startswith("rt_refit_quads: ") and match in detail, detail
+        assert L.rt_refit_quads(C.byref(on.desc), C.byref(u), nodes_out.ctypes.data, quads_out.ctypes.data) == 1
+        assert L.rt_last_error_detail().decode() == why
         assert (nodes_out == 7).all() and (quads_out == 7).all()
 
+    NON_FINITE, MATERIAL = "rt_refit_quads: a quad record has a non-finite Q, D, u, v, w or n", "rt_refit_quads: quad material out of range"
+    RANGE, TWICE = "rt_refit_quads: quad index out of range", "rt_refit_quads: a quad index appears twice"
+    MORE = "rt_refit_quads: more records than the scene has quads (an index is out of range or appears twice)"
     one = quads[3:4]
     assert L.rt_refit_quads(C.byref(scene.desc), None, nodes_out.ctypes.data, quads_out.ctypes.data) == 1
-    assert "null update" in L.rt_last_error_detail().decode()
+    assert L.rt_last_error_detail().decode() == "rt_refit_quads: null update"
     assert L.rt_refit_quads(None, None, None, None) == 1
-    refused("count is negative", one, count=-1)
-    refused("null quad records", quads[:0], count=1)
-    refused("out of range", one, idx=[len(quads)])
-    refused("out of range", one, idx=[-1])
-    refused("out of range", quads[:2], first=len(quads) - 1)
-    refused("twice", quads[[0, 1, 0]], idx=[0, 1, 0])
+    refused("rt_refit_quads: count is negative", one, count=-1)
+    refused("rt_refit_quads: null quad records", quads[:0], count=1)
+    refused(RANGE, one, idx=[len(quads)])
+    refused(RANGE, one, idx=[-1])
+    refused(RANGE, quads[:2], first=len(quads) - 1)
+    refused(TWICE, quads[[0, 1, 0]], idx=[0, 1, 0])
     for field, value in (("Q", np.nan), ("D", np.inf), ("u", -np.inf), ("v", np.nan), ("w", np.inf), ("n", np.nan)):
         bad = one.copy()
         if field == "D":
             bad[field] = value
         else:
             bad[field][0, 1] = value
-        refused("non-finite", bad, idx=[3])
+        refused(NON_FINITE, bad, idx=[3])
+    # two faults at once, on four quads: a record is looked at as soon as its index has passed, the count before any index
+    tiny = sg.tiny()
+    few = tiny.quads()
+    assert len(few) == 4
+    bad = few[[0, 1]]
+    bad["Q"][0, 1] = np.nan
+    refused(NON_FINITE, bad, idx=[0, 4], on=tiny)                     # record 0 is bad, index 1 is out of range
+    bad = few[[0, 1, 0]]
+    bad["n"][1, 2] = np.nan
+    refused(NON_FINITE, bad, idx=[0, 1, 0], on=tiny)                  # record 1 is bad, index 0 comes again as index 2
+    refused(MORE, few[[0, 0, 1, 2, 3]], idx=[4, 0, 1, 2, 3], on=tiny) # too many records, index 0 is out of range
     for mat in (-1, scene.desc.n_materials):
         bad = one.copy()
         bad["mat"] = mat
-        refused("quad material out of range", bad, idx=[3])
+        refused(MATERIAL, bad, idx=[3])
     with pytest.raises(ValueError, match="material"):
         art.refit_quads(scene.desc, bad, [3])
     with pytest.raises(ValueError, match="QUAD_DTYPE"):

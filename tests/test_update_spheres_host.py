@@ -111,36 +111,51 @@ def test_refusals_name_the_check_and_write_nothing(art):
     assert len(under) > 0
     nodes_out, sph_out = np.full(len(scene.nodes()), 7, np.uint8).repeat(32), np.full(len(sph), 7, np.uint8).repeat(32)
 
-    def refused(match, rec, idx=None, first=0, count=None):
+    def refused(why, rec, idx=None, first=0, count=None, on=scene):
         u = art.RtSphereUpdate()
         rec = np.ascontiguousarray(rec)
         u.count, u.first = len(rec) if count is None else count, first
         u.spheres = rec.ctypes.data if len(rec) else None
         keep = None if idx is None else np.ascontiguousarray(idx, np.int32)
         u.indices = None if keep is None else keep.ctypes.data
-        assert L.rt_refit_nodes(C.byref(scene.desc), C.byref(u), nodes_out.ctypes.data, sph_out.ctypes.data) == 1
-        assert match in L.rt_last_error_detail().decode(), L.rt_last_error_detail().decode()
+        assert L.rt_refit_nodes(C.byref(on.desc), C.byref(u), nodes_out.ctypes.data, sph_out.ctypes.data) == 1
+        assert L.rt_last_error_detail().decode() == why
         assert (nodes_out == 7).all() and (sph_out == 7).all()
 
+    NON_FINITE = "rt_refit_nodes: a sphere record has a non-finite c0, vel or radius"
+    RANGE, TWICE, MATERIAL = "rt_refit_nodes: sphere index out of range", "rt_refit_nodes: a sphere index appears twice", "rt_refit_nodes: sphere material out of range"
+    MORE = "rt_refit_nodes: more records than the scene has spheres (an index is out of range or appears twice)"
+    INSTANCED = "rt_refit_nodes: an updated sphere is the child of an instance (its box follows the instance's rule)"
     one = sph[direct[:1]]
     assert L.rt_refit_nodes(C.byref(scene.desc), None, nodes_out.ctypes.data, sph_out.ctypes.data) == 1
-    assert "null update" in L.rt_last_error_detail().decode()
+    assert L.rt_last_error_detail().decode() == "rt_refit_nodes: null update"
     assert L.rt_refit_nodes(None, None, None, None) == 1
-    refused("count is negative", one, count=-1)
-    refused("null sphere records", sph[:0], count=1)
-    refused("out of range", one, idx=[len(sph)])
-    refused("out of range", one, idx=[-1])
-    refused("out of range", sph[:2], first=len(sph) - 1)
-    refused("twice", sph[direct[[0, 1, 0]]], idx=direct[[0, 1, 0]])
+    refused("rt_refit_nodes: count is negative", one, count=-1)
+    refused("rt_refit_nodes: null sphere records", sph[:0], count=1)
+    refused(RANGE, one, idx=[len(sph)])
+    refused(RANGE, one, idx=[-1])
+    refused(RANGE, sph[:2], first=len(sph) - 1)
+    refused(TWICE, sph[direct[[0, 1, 0]]], idx=direct[[0, 1, 0]])
     for field, value in (("c0", np.nan), ("vel", np.inf), ("radius", -np.inf)):
         bad = one.copy()
         bad[field] = value
-        refused("non-finite", bad, idx=direct[:1])
+        refused(NON_FINITE, bad, idx=direct[:1])
     for mat in (-1, len(scene.materials())):
         bad = one.copy()
         bad["mat"] = mat
-        refused("material out of range", bad, idx=direct[:1])
-    refused("child of an instance", sph[under[:1]], idx=under[:1])
+        refused(MATERIAL, bad, idx=direct[:1])
+    refused(INSTANCED, sph[under[:1]], idx=under[:1])
+    # two faults at once, on three spheres: a record is looked at as soon as its index has passed, the count before any index
+    tiny = sg.tiny()
+    few = tiny.spheres()
+    assert len(few) == 3
+    bad = few[[0, 1]]
+    bad["c0"][0] = np.nan
+    refused(NON_FINITE, bad, idx=[0, 3], on=tiny)                     # record 0 is bad, index 1 is out of range
+    bad = few[[0, 1, 0]]
+    bad["vel"][1] = np.nan
+    refused(NON_FINITE, bad, idx=[0, 1, 0], on=tiny)                  # record 1 is bad, index 0 comes again as index 2
+    refused(MORE, few[[0, 0, 1, 2]], idx=[3, 0, 1, 2], on=tiny)       # too many records, index 0 is out of range
     with pytest.raises(ValueError, match="child of an instance"):
         art.refit_nodes(scene.desc, sph[under[:1]], under[:1])
     with pytest.raises(ValueError, match="SPHERE_DTYPE"):
