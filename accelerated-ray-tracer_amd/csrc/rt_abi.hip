@@ -2539,19 +2539,21 @@ rt_status plan_main_launch(const rt_scene* s, int kernel, size_t n_pixels, rt_fr
     int lds_mode = g_opt.lds_mode;
     const bool lean_family = s->spheres_only && s->tex_level < 2;
     const size_t budget1 = g_lds_per_cu - 2048;   // one workgroup per CU
+    // the staged kernel's image of the nodes carries a word per record behind them (the leaves' object references: rt_device.h)
+    const size_t image_bytes = s->node_bytes + (kernel == RT_KERNEL_STAGED ? (size_t)RT_WALK_PRIM_TABLE_BYTES(s->dev.n_nodes) : 0);
     if (lds_mode < 0) {
         // nodes + spheres where they fit a CU at all (several workgroups each with its own image, or one big workgroup
         // sharing one: see the workgroup shapes below), else nodes only, else everything through L1 / L2
         // (lds_mode 3 -- materials and textures in LDS too -- is selectable but measured no faster: profiles/r01_sweep34)
-        if (s->node_bytes + s->sphere_bytes <= budget1) lds_mode = 2;
-        else if (s->node_bytes <= budget1) lds_mode = 1;
+        if (image_bytes + s->sphere_bytes <= budget1) lds_mode = 2;
+        else if (image_bytes <= budget1) lds_mode = 1;
         else lds_mode = 0;
     }
     if (g_opt.lds_mode < 0 && kernel == RT_KERNEL_STAGED && g_opt.scan_nodes > 0 && s->dev.n_nodes <= g_opt.scan_nodes) lds_mode = 4;   // lockstep scan of a tiny scene
     if (lds_mode >= 3 && kernel != RT_KERNEL_STAGED) lds_mode = 2;
     if (kernel == RT_KERNEL_PIXEL) lds_mode = 0;   // the cross-check kernel reads the scene through L1/L2
     size_t lds_bytes = 0;
-    if (lds_mode >= 1 && lds_mode <= 3) lds_bytes += s->node_bytes;
+    if (lds_mode >= 1 && lds_mode <= 3) lds_bytes += image_bytes;
     if (lds_mode >= 2 && lds_mode <= 3) lds_bytes += s->sphere_bytes;
     if (lds_mode == 3) lds_bytes += s->shade_bytes;
     if (lds_bytes > budget1) return invalid("requested lds_mode does not fit the CU's LDS");

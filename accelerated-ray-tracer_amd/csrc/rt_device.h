@@ -93,11 +93,14 @@ struct rt_rank_params {
 // ~skip is the stored word itself.
 // The main kernel's LDS image differs from these arrays: with its nodes in LDS (lds_mode 1-3) it walks LDS addresses, and
 // while it stages the array it rewrites the two words for that walk (stage_scene<.., true>, rt_device_funcs.h) -- skip =
-// LDS address of the skip target, prim = LDS address of the next record at an interior node and ~(object id) (< 0) at a
-// leaf.  "Where next" is then (pass && (inner || a leaf is noted)) ? prim : skip -- one select, no NOT, no address
-// arithmetic before the reads.  Nothing outside that kernel sees the image: the device arrays, every other kernel, the
+// LDS address of the skip target, prim = LDS address of the next record at an interior node and ~(the record's own LDS
+// address) (< 0) at a leaf, whose object reference moves to a word table behind the image (4 bytes a record, padded to 16:
+// RT_WALK_PRIM_TABLE_BYTES, part of the launch's LDS size).  "Where next" is then (pass && (inner || a leaf is noted)) ?
+// prim : skip -- one select, no NOT, no address arithmetic before the reads -- and a lane stopped at a leaf holds that
+// leaf's address in its state.  Nothing outside that kernel sees the image: the device arrays, every other kernel, the
 // refit kernels and rt_debug_scene_boxes keep the encoding above, as does the main kernel with lds_mode 0 and 4.
 #define RT_NODE_SKIP(stored) (~(stored))
+#define RT_WALK_PRIM_TABLE_BYTES(n_nodes) ((4 * (n_nodes) + 15) & ~15)
 
 // device-resident scene: the rt_scene_desc arrays after upload
 struct rt_scene_dev {

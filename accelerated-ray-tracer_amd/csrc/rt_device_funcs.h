@@ -664,8 +664,11 @@ DEV int32_t lds_load_word(int32_t address, int word) { return ((const __attribut
 // stage nodes (+ spheres) into LDS; returns the view the traversal should use
 // WALK_LINKS (the main kernel only, rt_kernel_staged.h): the two link words of the LDS image are re-encoded for a walk whose
 // state is a record's LDS address -- skip = address of the skip target (image base + 32 * n_nodes past the last record), prim =
-// address of the first child (the next record, >= 0) at an interior node and ~(object id) (< 0) at a leaf.  The device arrays
-// themselves (rt_device.h, RT_NODE_SKIP) are not touched.
+// address of the first child (the next record, >= 0) at an interior node and ~(the record's own address) (< 0) at a leaf: a
+// lane that stops at a leaf carries, in that one word, where it stopped.  The leaf's object reference (all 32 bits of an
+// RT_PRIM_REF: no room beside an address) goes to a word table behind the image, prim_of[record] at image base + 32 * n_nodes
+// + 4 * record, padded to 16 bytes (RT_WALK_PRIM_TABLE_BYTES; rt_abi.hip counts it in the launch's LDS size).  The device
+// arrays themselves (rt_device.h, RT_NODE_SKIP) are not touched.
 template <int LDS_MODE, bool WALK_LINKS = false>
 DEV SceneView stage_scene(const rt_scene_dev& sd, unsigned char* lds) {
     SceneView v;
@@ -677,19 +680,22 @@ DEV SceneView stage_scene(const rt_scene_dev& sd, unsigned char* lds) {
         const int n16 = sd.n_nodes * 2;
         if (WALK_LINKS) {
             const int32_t base = lds_address(lds);
+            int32_t* prim_of = reinterpret_cast<int32_t*>(dst + n16);
             for (int k = threadIdx.x; k < n16; k += blockDim.x) {
                 float4 q = src[k];
                 const int32_t w = __float_as_int(q.w);
-                // stored < 0: ~(a node index) -- every skip link, and an interior node's prim = ~(own index + 1); else a leaf's object id
-                q.w = __int_as_float(w < 0 ? base + 32 * RT_NODE_SKIP(w) : ~w);
+                // stored < 0: ~(a node index) -- every skip link, and an interior node's prim = ~(own index + 1); else a leaf's
+                // object id (the second half of record k >> 1, whose address is base + 16 * (k - 1))
+                q.w = __int_as_float(w < 0 ? base + 32 * RT_NODE_SKIP(w) : ~(base + 16 * (k - 1)));
                 dst[k] = q;
+                if (k & 1) prim_of[k >> 1] = w;   // (an interior record's entry is never read)
             }
         } else {
             for (int k = threadIdx.x; k < n16; k += blockDim.x) dst[k] = src[k];
         }
         v.nodes = reinterpret_cast<const rt_node*>(lds);
         if (LDS_MODE >= 2) {
-            float4* dst2 = dst + n16;
+            float4* dst2 = dst + n16 + (WALK_LINKS ? RT_WALK_PRIM_TABLE_BYTES(sd.n_nodes) / 16 : 0);
             const float4* src2 = reinterpret_cast<const float4*>(sd.spheres);
             const int m16 = sd.n_spheres * 2;
             for (int k = threadIdx.x; k < m16; k += blockDim.x) dst2[k] = src2[k];

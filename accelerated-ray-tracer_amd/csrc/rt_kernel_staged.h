@@ -22,8 +22,9 @@
 // + 32 * n_nodes, and the links of the LDS image are addresses too (stage_scene<.., true>, rt_device_funcs.h): the step
 // reads its record at `node` itself and takes the next state from a link word as stored.
 //   0 <= node < n      walking the BVH (next box test); the root is 0 / the image base
-//   node < 0           parked at a leaf (`parked`); index form: ~node is where the walk resumes; address form: node is the
-//                      leaf's link word ~(object id) and the walk resumes at the parked record's skip link
+//   node < 0           stopped at a second leaf; index form: ~node is where the walk resumes and `parked` is the leaf;
+//                      address form: node is the leaf's link word ~(the leaf record's own address), so the state itself
+//                      names the leaf, and the walk resumes at that record's skip link
 //   node == n + 0      traversal finished, hit/miss not yet classified
 //   node == n + 1      path ended: needs accumulate + next sample / pixel + camera ray
 //   node == n + 2      dielectric hit waiting for the (rare, long) dielectric stage
@@ -87,7 +88,9 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
     // a node's two float4 and a leaf's object id, from a walk state / a noted leaf in either form
     auto node_lo = [&](int at) -> float4 { return ADDR ? lds_load_float4(at, 0) : nodes4[2 * at]; };
     auto node_hi = [&](int at) -> float4 { return ADDR ? lds_load_float4(at, 1) : nodes4[2 * at + 1]; };
-    auto leaf_prim = [](const float4 hi) -> int32_t { return ADDR ? ~__float_as_int(hi.w) : __float_as_int(hi.w); };
+    // (address form: the object reference is in the word table behind the image, 4 bytes a record: limit + (at - root) / 8)
+    const int prim_of = ADDR ? limit - (root >> 3) : 0;
+    auto leaf_prim = [&](int at, const float4 hi) -> int32_t { return ADDR ? lds_load_word(prim_of + (at >> 3), 0) : __float_as_int(hi.w); };
     const float tmin = 0.001f;
 
     rt_xorwow g = {0, 0, 0, 0, 0, 0};
@@ -97,7 +100,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
     f3 inv = mk3(1, 1, 1);
     HitInfo best; best.t = FLT_MAX; best.prim = -1; best.inst = -1;
     int node = ST_NEWPATH;       // every lane starts by asking for a pixel
-    int32_t parked = -1;         // leaf node the lane stopped at (node < 0)
+    int32_t parked = -1;         // index form only: leaf node the lane stopped at (node < 0)
     int32_t pend = -1;           // leaf node whose box passed during the walk and whose object test is still due
     float cur_a = 1.f;           // dot(d, d) of the current ray (sphere.cuh:58), hoisted out of the sphere tests
     bool have_pixel = false, first = true, finite_inv = true;
@@ -165,7 +168,8 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
         } else {
         // ---------------- stage A: node steps
         // A lane whose box test passes at a leaf does not stop there: it notes the leaf (`pend`) and walks on with the
-        // limit it has; only a second leaf while the first is still due stops it (node = ~resume, `parked` = that leaf).
+        // limit it has; only a second leaf while the first is still due stops it (index form: node = ~resume, `parked` =
+        // that leaf; address form: node = ~(that leaf's address)).
         // Stage B tests the noted leaves in visiting order, each against its own box AGAIN with the limit of that
         // moment.  This is the reference's walk exactly: bvh_node::hit (bvh.cuh:95-106) reaches an object iff every
         // ancestor box and the object's own box (its single-object node, bvh.cuh:38-43) pass with the closest hit so
@@ -190,22 +194,26 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                     if ((unsigned)node < (unsigned)limit) {
                         const float4 a = node_lo(node), b = node_hi(node);
                         const bool pass = slab_test_loose(a, b, inv, lr, tmin, best.t);
-                        // In both forms each condition is compared once; its complement is mask logic on the scalar side
-                        // (lane_not, rt_device_funcs.h) -- written as the opposite comparison it costs a second v_cmp.
+                        // In both forms each condition is compared once; a complement is mask logic on the scalar side (the
+                        // index form's lane_not, rt_device_funcs.h) -- written as the opposite comparison it costs a second v_cmp.
                         if (ADDR) {
                             // the LDS image's links (stage_scene): a.w = address of the skip target, b.w = address of the
-                            // first child (>= 0) at an interior node and ~(object id) (< 0) at a leaf, which is the stopped
-                            // state as stored -- "where next" is one select between the two words: down on a pass inside,
-                            // stopped on a pass at a second leaf, else (failed, or a first leaf noted) on to the skip
-                            // target.  `node` is written last, in place: the two selects before it still read the old one.
+                            // first child (>= 0) at an interior node and ~(own address) (< 0) at a leaf, which is the stopped
+                            // state as stored and all that stage B needs of a stop -- "where next" is one select between the
+                            // two words: down on a pass inside, stopped on a pass at a second leaf (`take`), else (failed, or
+                            // a first leaf noted) on to the skip target.  `node` is written last, in place: the select before
+                            // it still reads the old one.
+                            // The step's whole bookkeeping is three mask operations and two selects.  "Inside, or a leaf is
+                            // noted" is ONE comparison: both words carry their condition in the sign bit, so it is
+                            // (link & pend) >= 0.  A pass that does not take the link word is a first leaf: pass != take, an
+                            // exclusive or of masks, no complement.  `&` and `|`, not `&&` and `||`: a short circuit here is
+                            // compiled as a branch.  (A lane mask for "noted" carried through the trip takes the v_and away
+                            // and was slower: the merges with exec at each join of the unrolled pair cost more)
                             const int32_t link = __float_as_int(b.w), skip = __float_as_int(a.w);
-                            const bool is_leaf = link < 0, noted = pend >= 0;
-                            const bool inner = lane_not(is_leaf), clear = lane_not(noted);
-                            const bool at_leaf = pass && is_leaf;
-                            const bool stop = at_leaf && noted;
-                            pend = (at_leaf && clear) ? node : pend;
-                            parked = stop ? node : parked;
-                            node = (pass && (inner || noted)) ? link : skip;
+                            const bool inner = link >= 0, noted = pend >= 0;
+                            const bool take = pass & (inner | noted);
+                            pend = (pass != take) ? node : pend;
+                            node = take ? link : skip;
                         } else {
                             // device encoding of the links (rt_device.h, RT_NODE_SKIP): a.w = ~skip, b.w = ~(node + 1) for
                             // an interior node and the object id (>= 0) at a leaf -- "where next" is one select and one
@@ -234,7 +242,6 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                         const bool at_leaf = pass && link < 0;
                         const bool stop = at_leaf && (pend >= 0 || !finite_inv);
                         pend = (at_leaf && !stop) ? node : pend;
-                        parked = stop ? node : parked;
                         node = (pass && (link >= 0 || stop)) ? link : skip;
                     } else {
                         const int32_t link = __float_as_int(b.w), nskip = __float_as_int(a.w);
@@ -254,7 +261,9 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
         // step either, the pass runs again at once (a wave must never reach the stage logic below with a test due and
         // nothing walking: "nothing walking, no stage ran" is the loop's exit condition).
         for (;;) {
-            const int cand = pend >= 0 ? pend : (node < 0 ? parked : -1);
+            // the leaf a stopped lane (node < 0) stopped at; address form: the stopped state is ~(its address)
+            const int32_t stopped_at = ADDR ? ~node : parked;
+            const int cand = pend >= 0 ? pend : (node < 0 ? stopped_at : -1);
             const unsigned long long due_mask = __ballot(cand >= 0);
             const bool nobody_steps = __ballot((unsigned)node < (unsigned)limit) == 0ull;
             const int live_b = __popcll(__ballot(node != ST_DEAD));
@@ -265,7 +274,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                 bool box_ok = false;
                 if (cand >= 0) {
                     const float4 a = node_lo(cand), b = node_hi(cand);
-                    prim = leaf_prim(b);
+                    prim = leaf_prim(cand, b);
                     kind = SPHERES_ONLY ? RT_PRIM_SPHERE : RT_PRIM_KIND(prim);
                     // the leaf's own box against the limit of THIS moment (see stage A); a ray with a zero direction
                     // component stopped right at the leaf, so its walk-time result still stands
@@ -310,10 +319,10 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                 }
                 if (tested) {
                     if (node < 0) {
-                        // (address form: the stopped state does not hold the way on; the parked leaf's skip link does --
+                        // (address form: the stopped state does not hold the way on; the stopped-at leaf's skip link does --
                         // `cand` was the noted leaf, not this one, when both were due)
-                        node = ADDR ? lds_load_word(parked, 3) : ~node;
-                        pend = pend >= 0 ? parked : -1; parked = -1;
+                        node = ADDR ? lds_load_word(stopped_at, 3) : ~node;
+                        pend = pend >= 0 ? stopped_at : -1; parked = -1;
                     }
                     else pend = -1;
                 }
