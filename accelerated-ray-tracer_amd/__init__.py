@@ -341,6 +341,125 @@ def _check(st: int, what: str) -> None:
         raise RtError(f"{what}: {L.rt_strerror(st).decode()} -- {L.rt_last_error_detail().decode()}")
 
 
+def _status(st: int, entry: str) -> None:
+    """_check for the entries that refuse their arguments: RT_ERR_INVALID is a ValueError that carries the library's detail."""
+    if st == 1:
+        raise ValueError(rt_lib().rt_last_error_detail().decode())
+    _check(st, entry)
+
+
+def _stream_arg(stream):
+    """What the C entries take as a stream: 0 / None (the null stream), a hipStream_t as an integer or a torch.cuda.Stream."""
+    if hasattr(stream, "cuda_stream"):
+        stream = stream.cuda_stream
+    return C.c_void_p(int(stream)) if stream else None
+
+
+def _enqueue_on(dev, stream, tensors):
+    """The torch stream a call that touches `tensors` is launched on: `stream`, or the current stream of `dev` for None.
+    Without tensors (a call that launches nothing) there is nothing to hand over."""
+    import torch
+    current = torch.cuda.current_stream(dev)
+    if stream is None:
+        return current
+    if stream == current or not tensors:
+        return stream
+    # The inputs' contiguous copies and the outputs were made on the current stream: `stream` waits for that
+    # work (and for whatever last used the outputs' blocks there) before the call writes, and the caching
+    # allocator must not hand any of them out again before `stream` is done with them.
+    stream.wait_stream(current)
+    for x in tensors:
+        if x is not None:
+            x.record_stream(stream)
+    return stream
+
+
+_TORCH_DTYPE_NAMES = {}   # torch.float32 -> "float32", filled as dtypes are met (str() of one is slow)
+
+
+class _Buffers:
+    """The one rule for the buffers of a call.  Built once per call from its anchor argument `name`: whether that is a numpy
+    array decides whether the call is a host call (numpy arrays) or a device call (torch tensors on cuda:`device`, or the
+    device of init() for None), and every other buffer must be of the anchor's kind.  Each refusal is a ValueError that
+    starts with the argument's name; no check allocates or copies anything."""
+    __slots__ = ("on_host", "anchor", "device", "dev")
+
+    def __init__(self, on_host, name, device):
+        self.on_host, self.anchor, self.device, self.dev = on_host, name, device, None
+
+    def torch_device(self):
+        """The torch device of a device call (torch is imported only when a tensor is looked at or made)."""
+        if self.dev is None:
+            import torch
+            self.dev = torch.device("cuda", 0 if self.device is None else self.device)
+        return self.dev
+
+    def wrong_kind(self, name, array, pointer=False):
+        """The refusal of an argument that is no buffer of the call's kind (the anchor itself may be of either)."""
+        kinds = [array] if self.on_host or name == self.anchor else []
+        if not self.on_host:
+            kinds += ["a torch tensor", "an integer device pointer"] if pointer else ["a torch tensor"]
+        return ValueError(f"{name}: {' or '.join(kinds)} is expected" + ("" if name == self.anchor else f" ({self.anchor} is one)"))
+
+    def address(self, x, name, dtypes=("float32",), shape=None, count=None, strided=False, pointer=False):
+        """The address of x checked: None, or an array / tensor of one of `dtypes` (names; None: any) with exactly `shape` or
+        `count` elements, contiguous unless `strided` -- or, in a device call with `pointer`, device memory as an integer."""
+        if x is None:
+            return None
+        on_host = self.on_host
+        if on_host:
+            if not isinstance(x, np.ndarray):
+                raise self.wrong_kind(name, "a numpy array")
+            dtype, contiguous = x.dtype.name, x.flags["C_CONTIGUOUS"]
+        elif hasattr(x, "data_ptr"):
+            if x.device != (self.dev or self.torch_device()):
+                raise ValueError(f"{name}: tensor on {x.device}, expected on {self.dev}")
+            dtype = _TORCH_DTYPE_NAMES.get(x.dtype) or _TORCH_DTYPE_NAMES.setdefault(x.dtype, str(x.dtype)[6:])
+            contiguous = x.is_contiguous()
+        elif pointer and isinstance(x, (int, np.integer)) and not isinstance(x, bool):
+            return int(x)
+        else:
+            raise self.wrong_kind(name, "a numpy array", pointer)
+        if dtypes is not None and dtype not in dtypes:
+            raise ValueError(f"{name}: {' or '.join(dtypes)} expected, got {dtype}")
+        if shape is not None and x.shape != shape:
+            raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {shape}")
+        if count is not None and (x.size if on_host else x.numel()) != count:
+            raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {count} elements")
+        if not (strided or contiguous):
+            raise ValueError(f"{name}: a {'C-contiguous array' if on_host else 'contiguous tensor'} is expected")
+        return x.ctypes.data if on_host else x.data_ptr()
+
+    def empty(self, shape, dtype="float32"):
+        """A new buffer of the anchor's kind: a numpy array, or a tensor on the device."""
+        if self.on_host:
+            return np.empty(shape, dtype)
+        import torch
+        return torch.empty(shape, dtype=getattr(torch, dtype), device=self.torch_device())
+
+    def table(self, x, name, dtype, dtype_name):
+        """A table of records: a one-dimensional numpy array of `dtype` (made contiguous), or in a device call a contiguous
+        (n, dtype.itemsize // 4) tensor of a 4-byte dtype, read in place.  Returns (count, its address or None without a
+        record, what must stay referenced until the C call has returned): the caller stores the third on something that
+        outlives the call -- here as an attribute of the ctypes structure that holds the address, which a Structure
+        instance allows beside its fields and which lives as long as the structure does."""
+        words = dtype.itemsize // 4
+        if self.on_host:
+            if not isinstance(x, np.ndarray) or x.dtype != dtype or x.ndim != 1:
+                raise self.wrong_kind(name, f"a one-dimensional numpy array of {dtype_name}")
+            x = np.ascontiguousarray(x)
+            return len(x), (x.ctypes.data if len(x) else None), x
+        if not hasattr(x, "data_ptr"):
+            raise self.wrong_kind(name, f"a one-dimensional numpy array of {dtype_name}")
+        if x.device != self.torch_device():
+            raise ValueError(f"{name}: tensor on {x.device}, expected on {self.dev}")
+        if x.ndim != 2 or x.shape[1] != words or x.element_size() != 4:
+            raise ValueError(f"{name}: shape {tuple(x.shape)} of {x.dtype}, expected (n, {words}) of a 4-byte dtype")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: a contiguous tensor is expected (it is read in place)")
+        return int(x.shape[0]), (x.data_ptr() if x.shape[0] else None), x
+
+
 def load_ppm(path: str):
     """Texture pixels from a PPM file -> (uint8 array h*w*3, w, h)."""
     L = host_lib()
@@ -449,6 +568,19 @@ class HostScene:
             pass
 
 
+def _frame_buffers(color):
+    """The buffer rule of denoise() and reproject(), whose anchor is the frame `color` (ny, nx, 3) on the device of init(), and (nx, ny)."""
+    bufs = _Buffers(isinstance(color, np.ndarray), "color", _initialised_device)
+    if not (bufs.on_host or hasattr(color, "data_ptr")):
+        raise bufs.wrong_kind("color", "a numpy array")
+    if color.ndim != 3 or color.shape[2] != 3 or color.shape[0] < 1 or color.shape[1] < 1:
+        raise ValueError(f"color: shape {tuple(color.shape)}, expected (ny, nx, 3)")
+    ny, nx = int(color.shape[0]), int(color.shape[1])
+    if nx * ny >= 1 << 31:
+        raise ValueError("frame too large")
+    return bufs, nx, ny
+
+
 _initialised_device = None
 
 
@@ -507,14 +639,7 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_D
             raise ValueError("sigma_variance must be in [1e-6, 1e6]")
         if not (np.isfinite(variance_floor) and 0 < np.float32(variance_floor) < np.inf):
             raise ValueError("variance_floor must be finite and positive")
-    on_host = isinstance(color, np.ndarray)
-    if not on_host and not hasattr(color, "data_ptr"):
-        raise ValueError("color: a numpy array or a torch tensor is expected")
-    if color.ndim != 3 or color.shape[2] != 3 or color.shape[0] < 1 or color.shape[1] < 1:
-        raise ValueError(f"color: shape {tuple(color.shape)}, expected (ny, nx, 3)")
-    ny, nx = int(color.shape[0]), int(color.shape[1])
-    if nx * ny >= 1 << 31:
-        raise ValueError("frame too large")
+    bufs, nx, ny = _frame_buffers(color)
     for k, v, lo, hi in (("iterations", iterations, 1, 8), ("normal_sharpness", normal_sharpness, 0, 10)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
             raise ValueError(f"{k} must be an integer in {lo}..{hi}")
@@ -528,55 +653,32 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_D
         demodulate = albedo is not None
     if demodulate and albedo is None:
         raise ValueError("demodulate needs albedo")
-    if on_host:
-        if workspace is not None:
-            raise ValueError("workspace: device memory goes with device tensors; pass None with numpy arrays")
-        dev = None
-    else:
-        import torch
-        dev = torch.device("cuda", 0 if _initialised_device is None else _initialised_device)
-    if out is None:
-        out = np.empty_like(color, order="C") if on_host else __import__("torch").empty_like(color)
-
-    def ptr(x, name, shape):
-        if x is None:
-            return None
-        if on_host:
-            if not isinstance(x, np.ndarray):
-                raise ValueError(f"{name}: a numpy array is expected (color is one)")
-            if x.dtype != np.float32 or tuple(x.shape) != shape or not x.flags["C_CONTIGUOUS"]:
-                raise ValueError(f"{name}: a C-contiguous float32 array of shape {shape} is expected")
-            return x.ctypes.data
-        if not isinstance(x, torch.Tensor):
-            raise ValueError(f"{name}: a torch tensor is expected (color is one)")
-        if x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f"{name}: a contiguous float32 tensor of shape {shape} on {dev} is expected")
-        return x.data_ptr()
-
+    if bufs.on_host and workspace is not None:
+        raise ValueError("workspace: device memory goes with device tensors; pass None with numpy arrays")
+    rgb, one = (ny, nx, 3), (ny, nx)
     d = RtDenoiseDesc()
     d.nx, d.ny = nx, ny
-    d.color, d.albedo, d.normal = ptr(color, "color", (ny, nx, 3)), ptr(albedo, "albedo", (ny, nx, 3)), ptr(normal, "normal", (ny, nx, 3))
-    d.depth, d.out = ptr(depth, "depth", (ny, nx)), ptr(out, "out", (ny, nx, 3))
+    d.color, d.albedo, d.normal = (bufs.address(x, k, shape=rgb) for k, x in (("color", color), ("albedo", albedo), ("normal", normal)))
+    d.depth, d.out = bufs.address(depth, "depth", shape=one), bufs.address(out, "out", shape=rgb)
     if workspace is not None:
-        if not isinstance(workspace, torch.Tensor) or not workspace.is_contiguous() or workspace.device != dev:
-            raise ValueError(f"workspace: a contiguous torch tensor on {dev} is expected")
-        d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+        d.workspace = bufs.address(workspace, "workspace", None)
+        d.workspace_bytes = workspace.numel() * workspace.element_size()
     d.iterations, d.normal_sharpness, d.demodulate = int(iterations), int(normal_sharpness), 1 if demodulate else 0
     d.sigma_color, d.color_floor, d.sigma_depth = sigma_color, color_floor, sigma_depth
-    if hasattr(stream, "cuda_stream"):
-        stream = stream.cuda_stream
+    args = (0 if bufs.on_host else 1, _stream_arg(stream), 1 if blocking else 0)
+    if variance is not None:
+        vd = RtDenoiseVarianceDesc()
+        vd.variance, vd.variance_out = bufs.address(variance, "variance", shape=one), bufs.address(variance_out, "variance_out", shape=one)
+        vd.sigma_variance, vd.variance_floor = sigma_variance, variance_floor
+    if out is None:   # (made last: every check has passed)
+        out = bufs.empty(rgb)
+        d.out = bufs.address(out, "out", shape=rgb)
     L = rt_lib()
     if variance is None:
-        st = L.rt_denoise(C.byref(d), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None, 1 if blocking else 0)
+        st = L.rt_denoise(C.byref(d), *args)
     else:
-        vd = RtDenoiseVarianceDesc()
-        vd.variance, vd.variance_out = ptr(variance, "variance", (ny, nx)), ptr(variance_out, "variance_out", (ny, nx))
-        vd.sigma_variance, vd.variance_floor = sigma_variance, variance_floor
-        st = L.rt_denoise_variance(C.byref(d), C.byref(vd), 0 if on_host else 1, C.c_void_p(int(stream)) if stream else None,
-                                   1 if blocking else 0)
-    if st == 1:
-        raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_denoise" if variance is None else "rt_denoise_variance")
+        st = L.rt_denoise_variance(C.byref(d), C.byref(vd), *args)
+    _status(st, "rt_denoise" if variance is None else "rt_denoise_variance")
     return out
 
 
@@ -603,11 +705,7 @@ def reproject_matrix(prev: RtCamera) -> np.ndarray:
     """rt_reproject_matrix: the 3 x 3 float32 matrix that takes a vector from `prev`'s origin to (a, a s, a t), its ray
     parameter and frame coordinates in `prev` (include/rt_abi.h).  Host only.  A singular camera is ValueError."""
     m = (C.c_float * 9)()
-    L = rt_lib()
-    st = L.rt_reproject_matrix(C.byref(prev), m)
-    if st == 1:
-        raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_reproject_matrix")
+    _status(rt_lib().rt_reproject_matrix(C.byref(prev), m), "rt_reproject_matrix")
     return np.array(m, np.float32).reshape(3, 3)
 
 
@@ -651,14 +749,7 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
     its instance when it has one, and its normal becomes the previous record's.  inst is required (and prev_inst exactly when
     history is given) beside prim and prev_prim; instances / prev_instances and the sphere arguments stay optional beside
     these, with no record when absent -- but a quad under an instance is followed only with that instance's records given."""
-    on_host = isinstance(color, np.ndarray)
-    if not on_host and not hasattr(color, "data_ptr"):
-        raise ValueError("color: a numpy array or a torch tensor is expected")
-    if color.ndim != 3 or color.shape[2] != 3 or color.shape[0] < 1 or color.shape[1] < 1:
-        raise ValueError(f"color: shape {tuple(color.shape)}, expected (ny, nx, 3)")
-    ny, nx = int(color.shape[0]), int(color.shape[1])
-    if nx * ny >= 1 << 31:
-        raise ValueError("frame too large")
+    bufs, nx, ny = _frame_buffers(color)
     alpha_min, depth_tol, normal_min, max_history = (float(np.float32(x)) for x in (alpha_min, depth_tol, normal_min, max_history))
     if not 0 < alpha_min <= 1:
         raise ValueError("alpha_min must be in (0, 1]")
@@ -677,22 +768,6 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             raise ValueError("history_len, prev_depth and prev_alpha need history")
     elif any(x is None for x in (history_len, prev_depth, prev_alpha)):
         raise ValueError("history needs history_len, prev_depth and prev_alpha")
-    if on_host:
-        dev = None
-        make = lambda shape: np.empty(shape, np.float32)   # noqa: E731
-    else:
-        import torch
-        dev = torch.device("cuda", 0 if _initialised_device is None else _initialised_device)
-        make = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
-    if out is None:
-        out = make((ny, nx, 3))
-    if out_len is None:
-        out_len = make((ny, nx))
-    if motion is True:
-        motion = make((ny, nx, 2))
-    elif motion is False:
-        motion = None
-
     md, imd, qmd = None, None, None
     if quads is None and prev_quads is not None:
         raise ValueError("prev_quads needs quads")
@@ -710,29 +785,15 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             raise ValueError("spheres needs prev_spheres")
         if prim is None or prev_prim is None:
             raise ValueError("spheres / instances: prim and prev_prim are required to follow what moved")
+        # (each structure keeps what its pointers point to: a numpy table is referenced until the C call has returned)
         md = RtReprojectMotionDesc()
-        keep_tables = []
-        dtype_names = {id(SPHERE_DTYPE): "SPHERE", id(MEDIUM_DTYPE): "MEDIUM", id(INSTANCE_DTYPE): "INSTANCE", id(QUAD_DTYPE): "QUAD"}
-
-        def table(x, name, dtype, words):
-            if on_host:
-                if not isinstance(x, np.ndarray) or x.dtype != dtype or x.ndim != 1:
-                    raise ValueError(f"{name}: a one-dimensional numpy array of {dtype_names[id(dtype)]}_DTYPE is expected (color is one)")
-                x = np.ascontiguousarray(x)
-                keep_tables.append(x)
-                return len(x), (x.ctypes.data if len(x) else None)
-            if not isinstance(x, torch.Tensor):
-                raise ValueError(f"{name}: a torch tensor is expected (color is one)")
-            if x.ndim != 2 or x.shape[1] != words or x.element_size() != 4 or not x.is_contiguous() or x.device != dev:
-                raise ValueError(f"{name}: a contiguous (n, {words}) tensor of a 4-byte dtype on {dev} is expected")
-            return int(x.shape[0]), (x.data_ptr() if x.shape[0] else None)
         if spheres is not None:
-            md.n_spheres, md.spheres = table(spheres, "spheres", SPHERE_DTYPE, 8)
-            n_prev, md.prev_spheres = table(prev_spheres, "prev_spheres", SPHERE_DTYPE, 8)
+            md.n_spheres, md.spheres, md.keep_spheres = bufs.table(spheres, "spheres", SPHERE_DTYPE, "SPHERE_DTYPE")
+            n_prev, md.prev_spheres, md.keep_prev_spheres = bufs.table(prev_spheres, "prev_spheres", SPHERE_DTYPE, "SPHERE_DTYPE")
             if n_prev != md.n_spheres:
                 raise ValueError(f"prev_spheres: {n_prev} records, spheres has {md.n_spheres}")
         if media is not None:
-            md.n_media, md.media = table(media, "media", MEDIUM_DTYPE, 4)
+            md.n_media, md.media, md.keep_media = bufs.table(media, "media", MEDIUM_DTYPE, "MEDIUM_DTYPE")
         if md.n_spheres >= 1 << 28 or md.n_media >= 1 << 28:
             raise ValueError("spheres / media: 2^28 records or more")
         md.time = float(np.float32(0.5 * (cur.time0 + cur.time1))) if time is None else float(np.float32(time))
@@ -747,8 +808,8 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             if (prev_inst is None) != (history is None):
                 raise ValueError("instances: prev_inst is required exactly when history is given")
             imd = RtReprojectInstanceDesc()
-            imd.n_instances, imd.instances = table(instances, "instances", INSTANCE_DTYPE, 8)
-            n_prev, imd.prev_instances = table(prev_instances, "prev_instances", INSTANCE_DTYPE, 8)
+            imd.n_instances, imd.instances, imd.keep_instances = bufs.table(instances, "instances", INSTANCE_DTYPE, "INSTANCE_DTYPE")
+            n_prev, imd.prev_instances, imd.keep_prev_instances = bufs.table(prev_instances, "prev_instances", INSTANCE_DTYPE, "INSTANCE_DTYPE")
             if n_prev != imd.n_instances:
                 raise ValueError(f"prev_instances: {n_prev} records, instances has {imd.n_instances}")
             if imd.n_instances >= 1 << 28:
@@ -763,60 +824,40 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             if imd is None:
                 imd = RtReprojectInstanceDesc()
             qmd = RtReprojectQuadDesc()
-            qmd.n_quads, qmd.quads = table(quads, "quads", QUAD_DTYPE, 20)
-            n_prev, qmd.prev_quads = table(prev_quads, "prev_quads", QUAD_DTYPE, 20)
+            qmd.n_quads, qmd.quads, qmd.keep_quads = bufs.table(quads, "quads", QUAD_DTYPE, "QUAD_DTYPE")
+            n_prev, qmd.prev_quads, qmd.keep_prev_quads = bufs.table(prev_quads, "prev_quads", QUAD_DTYPE, "QUAD_DTYPE")
             if n_prev != qmd.n_quads:
                 raise ValueError(f"prev_quads: {n_prev} records, quads has {qmd.n_quads}")
             if qmd.n_quads >= 1 << 28:
                 raise ValueError("quads: 2^28 records or more")
 
-    def ptr(x, name, shape, integer=False):
-        if x is None:
-            return None
-        if on_host:
-            want = np.int32 if integer else np.float32
-            if not isinstance(x, np.ndarray):
-                raise ValueError(f"{name}: a numpy array is expected (color is one)")
-            if x.dtype != want or tuple(x.shape) != shape or not x.flags["C_CONTIGUOUS"]:
-                raise ValueError(f"{name}: a C-contiguous {np.dtype(want).name} array of shape {shape} is expected")
-            return x.ctypes.data
-        want = torch.int32 if integer else torch.float32
-        if not isinstance(x, torch.Tensor):
-            raise ValueError(f"{name}: a torch tensor is expected (color is one)")
-        if x.dtype != want or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f"{name}: a contiguous {want} tensor of shape {shape} on {dev} is expected")
-        return x.data_ptr()
-
     d = RtReprojectDesc()
     d.nx, d.ny, d.cur, d.prev = nx, ny, cur, prev
     rgb, one = (ny, nx, 3), (ny, nx)
-    d.color, d.depth, d.alpha = ptr(color, "color", rgb), ptr(depth, "depth", one), ptr(alpha, "alpha", one)
-    d.normal, d.prim = ptr(normal, "normal", rgb), ptr(prim, "prim", one, True)
-    d.history, d.history_len = ptr(history, "history", rgb), ptr(history_len, "history_len", one)
-    d.prev_depth, d.prev_alpha = ptr(prev_depth, "prev_depth", one), ptr(prev_alpha, "prev_alpha", one)
-    d.prev_normal, d.prev_prim = ptr(prev_normal, "prev_normal", rgb), ptr(prev_prim, "prev_prim", one, True)
-    d.out, d.out_len, d.motion = ptr(out, "out", rgb), ptr(out_len, "out_len", one), ptr(motion, "motion", (ny, nx, 2))
+    adr, f32, i32 = bufs.address, ("float32",), ("int32",)
+    d.color, d.depth, d.alpha = adr(color, "color", f32, rgb), adr(depth, "depth", f32, one), adr(alpha, "alpha", f32, one)
+    d.normal, d.prim = adr(normal, "normal", f32, rgb), adr(prim, "prim", i32, one)
+    d.history, d.history_len = adr(history, "history", f32, rgb), adr(history_len, "history_len", f32, one)
+    d.prev_depth, d.prev_alpha = adr(prev_depth, "prev_depth", f32, one), adr(prev_alpha, "prev_alpha", f32, one)
+    d.prev_normal, d.prev_prim = adr(prev_normal, "prev_normal", f32, rgb), adr(prev_prim, "prev_prim", i32, one)
+    if out is None:
+        out = bufs.empty(rgb)
+    if out_len is None:
+        out_len = bufs.empty(one)
+    motion = bufs.empty((ny, nx, 2)) if motion is True else None if motion is False else motion
+    d.out, d.out_len, d.motion = adr(out, "out", f32, rgb), adr(out_len, "out_len", f32, one), adr(motion, "motion", f32, (ny, nx, 2))
     d.alpha_min, d.depth_tol, d.normal_min, d.max_history = alpha_min, depth_tol, normal_min, max_history
     if imd is not None:
-        imd.inst, imd.prev_inst = ptr(inst, "inst", one, True), ptr(prev_inst, "prev_inst", one, True)
-    if hasattr(stream, "cuda_stream"):
-        stream = stream.cuda_stream
-    L = rt_lib()
-    stream_p = C.c_void_p(int(stream)) if stream else None
+        imd.inst, imd.prev_inst = adr(inst, "inst", i32, one), adr(prev_inst, "prev_inst", i32, one)
+    L, args = rt_lib(), (0 if bufs.on_host else 1, _stream_arg(stream), 1 if blocking else 0)
     if md is None:
-        st = L.rt_reproject(C.byref(d), 0 if on_host else 1, stream_p, 1 if blocking else 0)
+        _status(L.rt_reproject(C.byref(d), *args), "rt_reproject")
     elif imd is None:
-        st = L.rt_reproject_moving(C.byref(d), C.byref(md), 0 if on_host else 1, stream_p, 1 if blocking else 0)
-        del keep_tables
+        _status(L.rt_reproject_moving(C.byref(d), C.byref(md), *args), "rt_reproject_moving")
     elif qmd is None:
-        st = L.rt_reproject_instances(C.byref(d), C.byref(md), C.byref(imd), 0 if on_host else 1, stream_p, 1 if blocking else 0)
-        del keep_tables
+        _status(L.rt_reproject_instances(C.byref(d), C.byref(md), C.byref(imd), *args), "rt_reproject_instances")
     else:
-        st = L.rt_reproject_quads(C.byref(d), C.byref(md), C.byref(imd), C.byref(qmd), 0 if on_host else 1, stream_p, 1 if blocking else 0)
-        del keep_tables
-    if st == 1:
-        raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, "rt_reproject" if md is None else "rt_reproject_moving" if imd is None else "rt_reproject_instances" if qmd is None else "rt_reproject_quads")
+        _status(L.rt_reproject_quads(C.byref(d), C.byref(md), C.byref(imd), C.byref(qmd), *args), "rt_reproject_quads")
     return ReprojectResult(out, out_len, motion)
 
 
@@ -836,41 +877,31 @@ _INSTANCES = ("instances", "instance", INSTANCE_DTYPE, "INSTANCE_DTYPE", RtInsta
 _QUADS = ("quads", "quad", QUAD_DTYPE, "QUAD_DTYPE", RtQuadUpdate)
 
 
-def _record_update(kind, records, indices, first):
-    """An RtSphereUpdate / RtInstanceUpdate / RtQuadUpdate over host records and what keeps its arrays alive.  ValueError for malformed arguments."""
+def _record_update(kind, records, indices, first, device=None):
+    """An RtSphereUpdate / RtInstanceUpdate / RtQuadUpdate over `records` -- host records, or with a `device` a tensor on it as
+    well -- and whether they are on the device.  The structure keeps its arrays alive.  ValueError for malformed arguments."""
     name, one, dtype, dtype_name, struct = kind
-    if not isinstance(records, np.ndarray) or records.dtype != dtype or records.ndim != 1:
-        raise ValueError(f"{name}: a one-dimensional numpy array of {dtype_name} is expected")
-    rec = np.ascontiguousarray(records)
+    bufs = _Buffers(device is None or isinstance(records, np.ndarray), name, device)
     u = struct()
-    u.count, u.first = len(rec), int(first)
-    setattr(u, name, rec.ctypes.data)
-    idx = _update_indices(indices, len(rec), u, one)
-    return u, (rec, idx)
-
-
-def _update_indices(indices, count, u, one="sphere"):
-    if indices is None:
-        return None
-    idx = np.asarray(indices)
-    if idx.ndim != 1 or len(idx) != count or not np.issubdtype(idx.dtype, np.integer):
-        raise ValueError(f"indices: {count} integers are expected, one per record")
-    if len(idx) and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
-        raise ValueError(f"indices: {one} index out of range")
-    idx = np.ascontiguousarray(idx, np.int32)
-    u.indices = idx.ctypes.data
-    return idx
+    u.count, address, u.keep_records = bufs.table(records, name, dtype, dtype_name)
+    u.first = int(first)
+    setattr(u, name, address)
+    if indices is not None:
+        idx = np.asarray(indices)
+        if idx.ndim != 1 or len(idx) != u.count or not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError(f"indices: {u.count} integers are expected, one per record")
+        if len(idx) and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+            raise ValueError(f"indices: {one} index out of range")
+        u.keep_indices = np.ascontiguousarray(idx, np.int32)
+        u.indices = u.keep_indices.ctypes.data
+    return u, not bufs.on_host
 
 
 def _refit(kind, entry, desc, records, indices, first):
     """rt_refit_nodes / rt_refit_instances / rt_refit_quads: (nodes, records) of the description the update is equivalent to."""
-    u, keep = _record_update(kind, records, indices, first)
+    u, _ = _record_update(kind, records, indices, first)
     nodes, out = np.zeros(desc.n_nodes, NODE_DTYPE), np.zeros(getattr(desc, "n_" + kind[0]), kind[2])
-    L = rt_lib()
-    st = getattr(L, entry)(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data)
-    if st == 1:
-        raise ValueError(L.rt_last_error_detail().decode())
-    _check(st, entry)
+    _status(getattr(rt_lib(), entry)(C.byref(desc), C.byref(u), nodes.ctypes.data, out.ctypes.data), entry)
     return nodes, out
 
 
@@ -955,11 +986,7 @@ class DeviceScene:
         would write on a scene created with this camera.  recalibrate=True also renders the small calibration frame again
         for the cost prior of ranked frames; without it the old prior stays, which costs time and never a pixel.  A
         non-finite field or time1 < time0 is ValueError."""
-        L = rt_lib()
-        st = L.rt_scene_set_camera(self._p, C.byref(camera), 1 if recalibrate else 0)
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_scene_set_camera")
+        _status(rt_lib().rt_scene_set_camera(self._p, C.byref(camera), 1 if recalibrate else 0), "rt_scene_set_camera")
 
     def camera(self) -> RtCamera:
         """The camera the next frame uses (rt_scene_get_camera): the description's, or the last one set."""
@@ -1010,43 +1037,15 @@ class DeviceScene:
         self._update_records(_QUADS, "rt_scene_update_quads", quads, indices, first, recalibrate, stream)
 
     def _update_records(self, kind, entry, records, indices, first, recalibrate, stream):
-        name, one, dtype, dtype_name, struct = kind
-        words = dtype.itemsize // 4                                  # 4-byte words per record: 8, or 20 for a quad
-        L = rt_lib()
-        if isinstance(records, np.ndarray):
-            if stream is not None:
-                raise ValueError("stream: only a device tensor is enqueued on a torch stream")
-            u, keep = _record_update(kind, records, indices, first)
-            on_device, stream_p = 0, None
-        else:
-            import torch
-            dev = torch.device("cuda", self.device)
-            if not isinstance(records, torch.Tensor):
-                raise ValueError(f"{name}: a numpy array of {dtype_name} or a torch tensor is expected")
-            if records.device != dev:
-                raise ValueError(f"{name}: tensor on {records.device}, the scene is on {dev}")
-            if records.ndim != 2 or records.shape[1] != words or records.element_size() != 4:
-                raise ValueError(f"{name}: shape {tuple(records.shape)} of {records.dtype}, expected (count, {words}) of a 4-byte dtype")
-            if not records.is_contiguous():
-                raise ValueError(f"{name}: a contiguous tensor is expected (it is read in place)")
-            u = struct()
-            u.count, u.first = int(records.shape[0]), int(first)
-            setattr(u, name, records.data_ptr() if u.count else None)
-            keep = (records, _update_indices(indices, u.count, u, one))
+        if isinstance(records, np.ndarray) and stream is not None:
+            raise ValueError("stream: only a device tensor is enqueued on a torch stream")
+        u, on_device = _record_update(kind, records, indices, first, self.device)
+        stream_p = None
+        if on_device:
             if u.count == 0:
                 return
-            current = torch.cuda.current_stream(dev)
-            if stream is None:
-                stream = current
-            elif stream != current:
-                stream.wait_stream(current)
-                records.record_stream(stream)
-            on_device, stream_p = 1, C.c_void_p(stream.cuda_stream)
-        st = getattr(L, entry)(self._p, C.byref(u), on_device, 1 if recalibrate else 0, stream_p)
-        del keep
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, entry)
+            stream_p = C.c_void_p(_enqueue_on(records.device, stream, [records]).cuda_stream)
+        _status(getattr(rt_lib(), entry)(self._p, C.byref(u), 1 if on_device else 0, 1 if recalibrate else 0, stream_p), entry)
 
     def spheres(self) -> np.ndarray:
         """The sphere records the next frame uses (rt_scene_get_spheres): the description's, with every update applied."""
@@ -1111,6 +1110,17 @@ class DeviceScene:
         _check(L.rt_render(self._p, C.byref(frame), C.c_void_p(int(out)), 1, stream, 1 if blocking else 0, C.byref(stats)), "rt_render")
         return None, stats
 
+    def _ray_buffers(self, origins, directions):
+        """The buffer rule of trace() and radiance(), whose anchor is `origins` (N, 3) on this scene's device, and N."""
+        bufs = _Buffers(isinstance(origins, np.ndarray), "origins", self.device)
+        if not (bufs.on_host or hasattr(origins, "data_ptr")):
+            raise bufs.wrong_kind("origins", "a numpy array")
+        if origins.ndim != 2 or origins.shape[1] != 3:
+            raise ValueError(f"origins: shape {tuple(origins.shape)}, expected (N, 3)")
+        if directions is None:
+            raise ValueError("directions are required")
+        return bufs, int(origins.shape[0])
+
     def trace(self, origins, directions, times=None, tmin: float = 0.001, tmax=None, any_hit: bool = False, record: bool = False,
               stream=None):
         """Batched ray queries (rt_trace_rays): the closest hit -- or, with any_hit, whether anything is hit -- of every ray
@@ -1126,44 +1136,16 @@ class DeviceScene:
         ValueError before anything is launched.  A ray whose tmax is NaN, or with a NaN or infinite component in its origin,
         direction or time, is a miss."""
         import torch
-        on_host = isinstance(origins, np.ndarray)
-        dev = torch.device("cuda", self.device)
-
-        def prep(x, name, cols):
-            if x is None:
-                return None
-            if on_host:
-                if not isinstance(x, np.ndarray):
-                    raise ValueError(f"{name}: a numpy array is expected (origins is one)")
-                if x.dtype != np.float32:
-                    raise ValueError(f"{name}: float32 expected, got {x.dtype}")
-            else:
-                if not isinstance(x, torch.Tensor):
-                    raise ValueError(f"{name}: a torch tensor is expected (origins is one)")
-                if x.dtype != torch.float32:
-                    raise ValueError(f"{name}: float32 expected, got {x.dtype}")
-                if x.device != dev:
-                    raise ValueError(f"{name}: tensor on {x.device}, the scene is on {dev}")
-            want = (n, 3) if cols == 3 else (n,)
-            if tuple(x.shape) != want:
-                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {want}")
-            return x
-
         if any_hit and record:
             raise ValueError("any_hit returns hit flags only: record=True needs a closest-hit query")
-        if not on_host and not isinstance(origins, torch.Tensor):
-            raise ValueError("origins: a numpy array or a torch tensor is expected")
-        if origins.ndim != 2 or origins.shape[1] != 3:
-            raise ValueError(f"origins: shape {tuple(origins.shape)}, expected (N, 3)")
-        n = int(origins.shape[0])
-        if directions is None:
-            raise ValueError("directions are required")
+        bufs, n = self._ray_buffers(origins, directions)
+        on_host, dev = bufs.on_host, bufs.torch_device()
         if not np.isfinite(tmin):
             raise ValueError("tmin must be finite")
-        ins = [prep(origins, "origins", 3), prep(directions, "directions", 3), prep(times, "times", 1), prep(tmax, "tmax", 1)]
+        ins = [origins, directions, times, tmax]
+        for k, x in zip(("origins", "directions", "times", "tmax"), ins):
+            bufs.address(x, k, shape=(n, 3) if k in ("origins", "directions") else (n,), strided=True)
         ins = [None if x is None else (torch.from_numpy(np.ascontiguousarray(x)).to(dev) if on_host else x.contiguous()) for x in ins]
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
 
         def empty(shape, dtype):
             return torch.empty(shape, dtype=dtype, device=dev)
@@ -1174,6 +1156,7 @@ class DeviceScene:
             if record:
                 outs.update(point_out=empty((n, 3), torch.float32), normal_out=empty((n, 3), torch.float32),
                             uv_out=empty((n, 2), torch.float32), mat_out=empty((n,), torch.int32))
+        stream = _enqueue_on(dev, stream, ins + list(outs.values()) if n > 0 else ())
         if n > 0:
             b = RtRayBatch()
             b.n = n
@@ -1182,15 +1165,6 @@ class DeviceScene:
             b.mode = RT_TRACE_ANY if any_hit else RT_TRACE_CLOSEST
             for k, v in outs.items():
                 setattr(b, k, v.data_ptr())
-            current = torch.cuda.current_stream(dev)
-            if stream != current:
-                # The inputs' contiguous copies and the outputs were made on the current stream: `stream` waits for that
-                # work (and for whatever last used the outputs' blocks there) before the trace writes, and the caching
-                # allocator must not hand any of them out again before `stream` is done with them.
-                stream.wait_stream(current)
-                for x in ins + list(outs.values()):
-                    if x is not None:
-                        x.record_stream(stream)
             _check(rt_lib().rt_trace_rays(self._p, C.byref(b), C.c_void_p(stream.cuda_stream), 0), "rt_trace_rays")
         if on_host:
             stream.synchronize()
@@ -1213,38 +1187,8 @@ class DeviceScene:
         is launched.  A ray with a NaN or infinite component in its origin, direction or time, or with a zero direction,
         gets zeros and 0 rays."""
         import torch
-        on_host = isinstance(origins, np.ndarray)
-        dev = torch.device("cuda", self.device)
-        if not on_host and not isinstance(origins, torch.Tensor):
-            raise ValueError("origins: a numpy array or a torch tensor is expected")
-        if origins.ndim != 2 or origins.shape[1] != 3:
-            raise ValueError(f"origins: shape {tuple(origins.shape)}, expected (N, 3)")
-        n = int(origins.shape[0])
-        if directions is None:
-            raise ValueError("directions are required")
-
-        def prep(x, name, cols, np_types, torch_types):
-            if x is None:
-                return None
-            if on_host:
-                if not isinstance(x, np.ndarray):
-                    raise ValueError(f"{name}: a numpy array is expected (origins is one)")
-                if x.dtype not in np_types:
-                    raise ValueError(f"{name}: {' or '.join(np.dtype(t).name for t in np_types)} expected, got {x.dtype}")
-            else:
-                if not isinstance(x, torch.Tensor):
-                    raise ValueError(f"{name}: a torch tensor is expected (origins is one)")
-                if x.dtype not in torch_types:
-                    raise ValueError(f"{name}: {' or '.join(str(t) for t in torch_types)} expected, got {x.dtype}")
-                if x.device != dev:
-                    raise ValueError(f"{name}: tensor on {x.device}, the scene is on {dev}")
-            want = (n, 3) if cols == 3 else (n,)
-            if tuple(x.shape) != want:
-                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {want}")
-            return x
-
-        f32, t32 = (np.dtype(np.float32),), (torch.float32,)
-        i64, t64 = (np.dtype(np.int64), np.dtype(np.uint64)), (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
+        bufs, n = self._ray_buffers(origins, directions)
+        on_host, dev = bufs.on_host, bufs.torch_device()
         if isinstance(ns, bool) or not isinstance(ns, (int, np.integer)) or not 1 <= int(ns) <= 1 << 20:
             raise ValueError("ns must be an integer in 1 .. 1 << 20")
         if isinstance(seed_base, bool) or not isinstance(seed_base, (int, np.integer)) or not 0 <= int(seed_base) < 1 << 64:
@@ -1253,18 +1197,18 @@ class DeviceScene:
         if len(bg) != 3:
             raise ValueError("background: three floats are expected")
         gradient = self.host.use_gradient_bg if gradient is None else gradient
-        ins = [prep(origins, "origins", 3, f32, t32), prep(directions, "directions", 3, f32, t32), prep(times, "times", 1, f32, t32),
-               prep(seeds, "seeds", 1, i64, t64)]
+        ins = [origins, directions, times, seeds]
+        for k, x in zip(("origins", "directions", "times", "seeds"), ins):
+            bufs.address(x, k, ("int64", "uint64") if k == "seeds" else ("float32",), (n, 3) if k in ("origins", "directions") else (n,), strided=True)
         if on_host:   # (torch has no uint64 arithmetic to speak of: the seeds travel as their int64 bits)
             ins = [None if x is None else torch.from_numpy(np.ascontiguousarray(x).view(np.int64) if x.dtype == np.uint64 else np.ascontiguousarray(x)).to(dev)
                    for x in ins]
         else:
             ins = [None if x is None else x.contiguous() for x in ins]
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
         outs = {"rgb_out": torch.empty((n, 3), dtype=torch.float32, device=dev)}
         if count_rays:
             outs["rays_out"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        stream = _enqueue_on(dev, stream, ins + list(outs.values()) if n > 0 else ())
         if n > 0:
             b = RtRadianceBatch()
             b.n = n
@@ -1274,16 +1218,7 @@ class DeviceScene:
             b.use_gradient_bg = 1 if gradient else 0
             for k, v in outs.items():
                 setattr(b, k, v.data_ptr())
-            current = torch.cuda.current_stream(dev)
-            if stream != current:   # as in trace(): `stream` waits for the copies and buffers made on the current stream
-                stream.wait_stream(current)
-                for x in ins + list(outs.values()):
-                    if x is not None:
-                        x.record_stream(stream)
-            st = rt_lib().rt_radiance_rays(self._p, C.byref(b), C.c_void_p(stream.cuda_stream), 0)
-            if st == 1:
-                raise ValueError(rt_lib().rt_last_error_detail().decode())
-            _check(st, "rt_radiance_rays")
+            _status(rt_lib().rt_radiance_rays(self._p, C.byref(b), C.c_void_p(stream.cuda_stream), 0), "rt_radiance_rays")
         if on_host:
             stream.synchronize()
             outs = {k: v.cpu().numpy() for k, v in outs.items()}
@@ -1315,36 +1250,22 @@ class DeviceScene:
             out = {k: np.empty((rows, frame.nx, 3) if table[k][0] == 3 else (rows, frame.nx), table[k][1]) for k in names}
         if not isinstance(out, dict) or not out:
             raise ValueError("no output is requested")
-        on_host = all(isinstance(v, np.ndarray) for v in out.values())
+        bufs = _Buffers(all(isinstance(v, np.ndarray) for v in out.values()), "out", self.device)
         a, t = RtAovDesc(), RtAovThroughDesc()
         for k, v in out.items():
             if k not in table:
                 raise ValueError(f"unknown output '{k}': one of {', '.join(table)} is expected")
+            if not bufs.on_host and not hasattr(v, "data_ptr"):
+                raise ValueError("out: all numpy arrays or all torch tensors are expected")
             ch, dtype = table[k]
-            size = rows * frame.nx * ch
-            if on_host:
-                if v.dtype != dtype or v.size != size or not v.flags["C_CONTIGUOUS"]:
-                    raise ValueError(f"{k}: a C-contiguous {np.dtype(dtype).name} array of {size} elements is expected")
-                setattr(a if k in AOV_OUTPUTS else t, k, v.ctypes.data)
-            else:
-                import torch
-                want = torch.float32 if dtype == np.float32 else torch.int32
-                if not isinstance(v, torch.Tensor):
-                    raise ValueError("out: all numpy arrays or all torch tensors are expected")
-                if v.dtype != want or v.numel() != size or not v.is_contiguous() or v.device != torch.device("cuda", self.device):
-                    raise ValueError(f"{k}: a contiguous {want} tensor of {size} elements on cuda:{self.device} is expected")
-                setattr(a if k in AOV_OUTPUTS else t, k, v.data_ptr())
-        if hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        args = (0 if on_host else 1, C.c_void_p(int(stream)) if stream else None, 1 if blocking else 0)
+            setattr(a if k in AOV_OUTPUTS else t, k, bufs.address(v, k, (np.dtype(dtype).name,), count=rows * frame.nx * ch))
+        args = (0 if bufs.on_host else 1, _stream_arg(stream), 1 if blocking else 0)
         if chain is None:
             st = L.rt_render_aov(self._p, C.byref(frame), C.byref(a), *args)
         else:
             t.max_bounces, t.fuzz_limit = chain
             st = L.rt_render_aov_through(self._p, C.byref(frame), C.byref(a), C.byref(t), *args)
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_render_aov" if chain is None else "rt_render_aov_through")
+        _status(st, "rt_render_aov" if chain is None else "rt_render_aov_through")
         return out
 
     def render_aov_through(self, frame: RtFrameDesc, max_bounces: int = AOV_THROUGH_DEFAULTS["max_bounces"],
@@ -1437,34 +1358,15 @@ class DeviceScene:
             variance_out = np.empty((rows, frame.nx), np.float32)
         if out is None or variance_out is None:
             raise ValueError("out and variance_out go together: pass both or neither")
-        on_host = isinstance(out, np.ndarray)
-        if isinstance(variance_out, np.ndarray) != on_host:
+        bufs = _Buffers(isinstance(out, np.ndarray), "out", self.device)
+        if isinstance(variance_out, np.ndarray) != bufs.on_host:
             raise ValueError("out and variance_out must both be host (numpy) or both device memory")
-
-        def ptr(x, size, name):
-            if isinstance(x, np.ndarray):
-                if x.dtype != np.float32 or x.size != size or not x.flags["C_CONTIGUOUS"]:
-                    raise ValueError(f"{name}: a C-contiguous float32 array of {size} elements is expected")
-                return x.ctypes.data
-            if hasattr(x, "data_ptr"):
-                import torch
-                if x.dtype != torch.float32 or x.numel() != size or not x.is_contiguous() or x.device != torch.device("cuda", self.device):
-                    raise ValueError(f"{name}: a contiguous float32 tensor of {size} elements on cuda:{self.device} is expected")
-                return x.data_ptr()
-            if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-                raise ValueError(f"{name}: a numpy array, a torch tensor or an integer device pointer is expected")
-            return int(x)
-        p_fb = ptr(out, rows * frame.nx * 3, "out")
-        p_var = ptr(variance_out, rows * frame.nx, "variance_out")
-        if hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        p_fb = bufs.address(out, "out", count=rows * frame.nx * 3, pointer=True)
+        p_var = bufs.address(variance_out, "variance_out", count=rows * frame.nx, pointer=True)
         v = RtVarianceDesc(batches, 0)
         stats = RtStats()
-        st = L.rt_render_variance(self._p, C.byref(frame), C.byref(v), C.c_void_p(p_fb), 0 if on_host else 1, C.c_void_p(p_var),
-                                  C.c_void_p(int(stream)) if stream else None, C.byref(stats))
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_render_variance")
+        _status(L.rt_render_variance(self._p, C.byref(frame), C.byref(v), C.c_void_p(p_fb), 0 if bufs.on_host else 1, C.c_void_p(p_var),
+                                     _stream_arg(stream), C.byref(stats)), "rt_render_variance")
         ret = lambda x: x if (isinstance(x, np.ndarray) or hasattr(x, "data_ptr")) else None   # noqa: E731
         return ret(out), ret(variance_out), stats
 
@@ -1500,35 +1402,15 @@ class DeviceScene:
             out = np.empty((rows, frame.nx, 3), np.float32)
             if spp_out is None:
                 spp_out = np.empty((rows, frame.nx), np.int32)
-        on_host = isinstance(out, np.ndarray)
-        if spp_out is not None and isinstance(spp_out, np.ndarray) != on_host:
+        bufs = _Buffers(isinstance(out, np.ndarray), "out", self.device)
+        if spp_out is not None and isinstance(spp_out, np.ndarray) != bufs.on_host:
             raise ValueError("out and spp_out must both be host (numpy) or both device memory")
-
-        def ptr(x, dtype, size, name):
-            if x is None:
-                return None
-            if isinstance(x, np.ndarray):
-                if x.dtype != dtype or x.size != size or not x.flags["C_CONTIGUOUS"]:
-                    raise ValueError(f"{name}: a C-contiguous {np.dtype(dtype).name} array of {size} elements is expected")
-                return x.ctypes.data
-            if hasattr(x, "data_ptr"):
-                import torch
-                want = torch.float32 if dtype == np.float32 else torch.int32
-                if x.dtype != want or x.numel() != size or not x.is_contiguous() or x.device != torch.device("cuda", self.device):
-                    raise ValueError(f"{name}: a contiguous {want} tensor of {size} elements on cuda:{self.device} is expected")
-                return x.data_ptr()
-            return int(x)
-        p_fb = ptr(out, np.float32, rows * frame.nx * 3, "out")
-        p_spp = ptr(spp_out, np.int32, rows * frame.nx, "spp_out")
-        if hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        p_fb = bufs.address(out, "out", count=rows * frame.nx * 3, pointer=True)
+        p_spp = bufs.address(spp_out, "spp_out", ("int32",), count=rows * frame.nx, pointer=True)
         a = RtAdaptiveDesc(min_spp, max_spp, threshold, floor)
         stats = RtStats()
-        st = L.rt_render_adaptive(self._p, C.byref(frame), C.byref(a), C.c_void_p(p_fb), 0 if on_host else 1, C.c_void_p(p_spp) if p_spp else None,
-                                  C.c_void_p(int(stream)) if stream else None, C.byref(stats))
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_render_adaptive")
+        _status(L.rt_render_adaptive(self._p, C.byref(frame), C.byref(a), C.c_void_p(p_fb), 0 if bufs.on_host else 1,
+                                     C.c_void_p(p_spp) if p_spp else None, _stream_arg(stream), C.byref(stats)), "rt_render_adaptive")
         ret = lambda x: x if (x is None or isinstance(x, np.ndarray) or hasattr(x, "data_ptr")) else None   # noqa: E731
         return ret(out), ret(spp_out), stats
 
@@ -1703,11 +1585,7 @@ class MultiScene:
 
     def set_camera(self, camera: RtCamera, recalibrate: bool = False) -> None:
         """DeviceScene.set_camera on every replica (rt_multi_set_camera)."""
-        L = rt_lib()
-        st = L.rt_multi_set_camera(self._p, C.byref(camera), 1 if recalibrate else 0)
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, "rt_multi_set_camera")
+        _status(rt_lib().rt_multi_set_camera(self._p, C.byref(camera), 1 if recalibrate else 0), "rt_multi_set_camera")
 
     def update_spheres(self, spheres, indices=None, first: int = 0, recalibrate: bool = False) -> None:
         """DeviceScene.update_spheres with host records on every replica (rt_multi_update_spheres)."""
@@ -1722,13 +1600,8 @@ class MultiScene:
         self._update_records(_QUADS, "rt_multi_update_quads", quads, indices, first, recalibrate)
 
     def _update_records(self, kind, entry, records, indices, first, recalibrate):
-        L = rt_lib()
-        u, keep = _record_update(kind, records, indices, first)
-        st = getattr(L, entry)(self._p, C.byref(u), 1 if recalibrate else 0)
-        del keep
-        if st == 1:
-            raise ValueError(L.rt_last_error_detail().decode())
-        _check(st, entry)
+        u, _ = _record_update(kind, records, indices, first)
+        _status(getattr(rt_lib(), entry)(self._p, C.byref(u), 1 if recalibrate else 0), entry)
 
     def render(self, frame: RtFrameDesc, tile_rows: int = 4):
         """The whole frame as float32[ny][nx][3] in host memory, and the summed statistics."""
