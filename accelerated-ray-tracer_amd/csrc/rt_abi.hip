@@ -3032,6 +3032,10 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
 #endif
     RT_TRY(launch_part(fp, grid, s->ranked_frame));
     if (s->ranked_frame) s->cost_map.last_parts = part_index;
+    // ---- the finishing pass (rt_kernel_finish.hip): the main and tier kernels have left every local pixel's colour sum in the
+    // frame, each written once by the last part's main, tier or tail launch, all of which the stream has joined; kernel 0 has
+    // stored finished pixels.  Inside ev_start .. ev_stop: it is part of the frame's time.
+    if (kernel != RT_KERNEL_PIXEL) HIPCHK(rt_launch_finish(fp.fb, floats, frame_ns, f->gamma, stream));
     // ---- finish
     HIPCHK(hipEventRecord(s->ev_stop, stream));
     s->frame_pending = true;

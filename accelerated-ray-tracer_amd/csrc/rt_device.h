@@ -437,6 +437,11 @@ struct rt_variance_params {
 };
 hipError_t rt_launch_variance(const rt_variance_params& p, hipStream_t st);
 
+// The finishing pass of rt_render and rt_render_window (rt_kernel_finish.hip): the main kernel and the tier kernel store each
+// pixel's colour sum; this turns the frame's `floats` values into store_pixel's, in place: the scaling by 1 / ns, then gamma.
+#define RT_FINISH_THREADS 256
+hipError_t rt_launch_finish(float* fb, size_t floats, int32_t ns, float gamma, hipStream_t st);
+
 // rt_render_aov_through (rt_kernel_aov_through.hip): the feature pass that follows the specular chain of every sample
 // (include/rt_abi.h).  A second kernel argument beside rt_aov_params, which rt_kernel_aov.hip keeps as it is.
 struct rt_aov_through_params {

@@ -651,6 +651,14 @@ DEV void store_pixel(const rt_frame_params& fp, int i, int lrow, f3 col) {   // 
     px[2] = apply_gamma(col.z, fp.gamma);
 }
 
+// The main kernel and the tier kernel leave the pixel's colour sum in the frame as it is; rt_finish_kernel (rt_kernel_finish.hip)
+// applies store_pixel's scaling and gamma to the whole frame afterwards.  The end of a pixel is an event of one lane: the three
+// out-of-line cr_pow calls there were issued for that lane alone.
+DEV void store_sum(const rt_frame_params& fp, int i, int lrow, f3 col) {
+    float* px = fp.fb + ((size_t)lrow * fp.nx + i) * 3;
+    px[0] = col.x; px[1] = col.y; px[2] = col.z;
+}
+
 // the 32-bit LDS address of a pointer into the workgroup's LDS (what ds_read takes), and a 16-byte load from such an address
 // (which: 0 or 1, the record's first or second 16 bytes -- an immediate offset of the read)
 typedef float lds_native_float4 __attribute__((ext_vector_type(4)));

@@ -332,9 +332,12 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
         }
         }
         DIAG_T(1);
-        // a finished walk that hit nothing (main.cu:57-68) needs no stage: add the background and end the path now
+        // a finished walk that hit nothing (main.cu:57-68) needs no stage: the path ends now.  Its background term is due, and
+        // stage E adds it: this point is passed in every trip by the few lanes that have just missed, stage E once they are many,
+        // and the lane's ray, throughput and radiance stay as they are until then.  The mark is a negative `bounce`, which no other
+        // path end leaves and stage E resets.
         if (node == ST_DONE && pend < 0 && best.prim < 0) {
-            radiance = fma3(throughput, miss_color(fp, cur), radiance);
+            bounce = -1;
             node = ST_NEWPATH;
         }
         const unsigned long long walking = __ballot(node < limit);
@@ -440,6 +443,11 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                 }
                 bool ran_dry = false;      // this lane found its queue empty
                 if (node == ST_NEWPATH) {
+                    // the background term of a path that ended in a miss (marked after stage B), before the sample is added and
+                    // the pixel stored, parked or handed off.  The mark goes for every lane here, one that runs dry included: it
+                    // may be back with `first` set when its wave turns ordinary.
+                    if (bounce < 0) radiance = fma3(throughput, miss_color(fp, cur), radiance);
+                    bounce = 0;
                     if (!first) { col = col + radiance; ++sample; }
                     first = false;
                     bool alive = true;
@@ -465,9 +473,9 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                             if (hand) {
                                 fp.handoff_queue[slot] = ((unsigned long long)(uint32_t)sample << 32) | (unsigned long long)at;
                                 alive = false;
-                            } else if (fp.store_parked) store_pixel(fp, px_i, px_lrow, col);   // a progressive window: the frame so far
+                            } else if (fp.store_parked) store_sum(fp, px_i, px_lrow, col);   // a progressive window: the frame so far
                         } else {
-                            store_pixel(fp, px_i, px_lrow, col);
+                            store_sum(fp, px_i, px_lrow, col);   // (scaled and gamma-corrected by the frame's finishing pass)
                             if (fp.cost_out) {   // the scene's cost map: the pixel's rays over all its samples
                                 const size_t at = (size_t)px_lrow * fp.nx + px_i;
                                 fp.cost_out[at] = ((rays - rays_at_pixel_start) + ((fp.state_in && !fp.fresh) ? fp.state_in[at].cost : 0u)) & 0x7FFFFFFFu;
@@ -525,7 +533,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                         const float u = ((float)px_i + rt_xorwow_uniform(g)) / (float)fp.nx;
                         const float v = ((float)px_j + rt_xorwow_uniform(g)) / (float)fp.ny;
                         cur = camera_get_ray(sd.camera, u, v, g);
-                        throughput = mk3(1, 1, 1); radiance = mk3(0, 0, 0); bounce = 0;
+                        throughput = mk3(1, 1, 1); radiance = mk3(0, 0, 0);
                         node = ST_SETUP;
                     } else {
                         node = ST_DEAD;

@@ -378,7 +378,7 @@ __global__ void __launch_bounds__(RT_TIER_THREADS, (SPHERES_ONLY && TEX < 2) ? 4
                 fp.state_out[pix] = so;
                 if (fp.tile_cost) atomicAdd(&fp.tile_cost[(lrow >> 3) * fp.tiles_x + (i >> 3)], pixel_rays);
             } else {
-                store_pixel(fp, i, lrow, pcol);
+                store_sum(fp, i, lrow, pcol);   // (scaled and gamma-corrected by the frame's finishing pass)
                 if (fp.cost_out) fp.cost_out[pix] = (cost_before + pixel_rays) & 0x7FFFFFFFu;   // the scene's cost map
             }
             rays += pixel_rays;

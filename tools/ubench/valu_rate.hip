@@ -1,4 +1,4 @@
-// Microbenchmark: issue rate of plain vs packed fp32 VALU ops on gfx950 at 1..8 waves per SIMD.
+// Microbenchmark: issue rate of plain vs packed fp32 VALU ops (and of f64 fma / add, what cr_pow is made of) on gfx950 at 1..8 waves per SIMD.
 // Build: hipcc --offload-arch=gfx950 -O3 valu_rate.hip -o valu_rate ; run on the GPU box.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -10,6 +10,7 @@ __global__ void k(float* out, int iters) {
     float b = 1.0001f, c = 0.5f;
     typedef float f2 __attribute__((ext_vector_type(2)));
     f2 p0 = {a0, a1}, p1 = {a2, a3}, p2 = {a4, a5}, p3 = {a6, a7}, pb = {b, b}, pc = {c, c};
+    double d0 = a0, d1 = a1, d2 = a2, d3 = a3, db = 1.0001, dc = 0.5;
     for (int i = 0; i < iters; ++i) {
         if (OP == 0) { REP16(asm volatile("v_fma_f32 %0, %0, %4, %5\n v_fma_f32 %1, %1, %4, %5\n v_fma_f32 %2, %2, %4, %5\n v_fma_f32 %3, %3, %4, %5" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b), "v"(c));) }
         if (OP == 1) { REP16(asm volatile("v_pk_fma_f32 %0, %0, %4, %5\n v_pk_fma_f32 %1, %1, %4, %5\n v_pk_fma_f32 %2, %2, %4, %5\n v_pk_fma_f32 %3, %3, %4, %5" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3) : "v"(pb), "v"(pc));) }
@@ -20,8 +21,10 @@ __global__ void k(float* out, int iters) {
         if (OP == 6) { REP16(asm volatile("v_rcp_f32 %0, %0\n v_sqrt_f32 %1, %1\n v_rcp_f32 %2, %2\n v_sqrt_f32 %3, %3" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));) }
         if (OP == 7) { REP16(asm volatile("v_xor_b32 %0, %0, %4\n v_lshlrev_b32 %1, 3, %1\n v_add_u32 %2, %2, %4\n v_xad_u32 %3, %3, %4, %5" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b), "v"(c));) }
         if (OP == 8) { REP16(asm volatile("v_med3_f32 %0, %0, %4, %5\n v_med3_f32 %1, %1, %4, %5\n v_med3_f32 %2, %2, %4, %5\n v_med3_f32 %3, %3, %4, %5" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b), "v"(c));) }
+        if (OP == 9) { REP16(asm volatile("v_fma_f64 %0, %0, %4, %5\n v_fma_f64 %1, %1, %4, %5\n v_fma_f64 %2, %2, %4, %5\n v_fma_f64 %3, %3, %4, %5" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3) : "v"(db), "v"(dc));) }
+        if (OP == 10) { REP16(asm volatile("v_add_f64 %0, %0, %4\n v_add_f64 %1, %1, %4\n v_add_f64 %2, %2, %4\n v_add_f64 %3, %3, %4" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3) : "v"(db));) }
     }
-    out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + p0.x + p0.y + p1.x + p1.y + p2.x + p3.y;
+    out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + p0.x + p0.y + p1.x + p1.y + p2.x + p3.y + (float)(d0 + d1 + d2 + d3);
 }
 template <int OP> void run(const char* name, float* d) {
     for (int waves_per_simd : {1, 2, 4, 8}) {
@@ -46,6 +49,6 @@ int main() {
     float* d; hipMalloc(&d, 1 << 24);
     run<0>("v_fma_f32", d); run<1>("v_pk_fma_f32", d); run<2>("v_add/v_mul_f32", d); run<3>("v_pk_add/v_pk_mul_f32", d);
     run<4>("v_min/max/min3/max3_f32", d); run<5>("v_cmp+v_cndmask", d); run<6>("v_rcp/v_sqrt", d); run<7>("int xor/shl/add/xor3", d);
-    run<8>("v_med3_f32", d);
+    run<8>("v_med3_f32", d); run<9>("v_fma_f64", d); run<10>("v_add_f64", d);
     return 0;
 }
