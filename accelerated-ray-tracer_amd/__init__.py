@@ -94,6 +94,13 @@ class RtDenoiseDesc(C.Structure):
                 ("sigma_color", C.c_float), ("color_floor", C.c_float), ("sigma_depth", C.c_float), ("pad", C.c_float)]
 
 
+class RtUpscaleDesc(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("factor", C.c_int32), ("normal_sharpness", C.c_int32), ("demodulate", C.c_int32),
+                ("reserved", C.c_int32), ("sigma_depth", C.c_float), ("min_weight", C.c_float), ("color_lo", C.c_void_p),
+                ("albedo_lo", C.c_void_p), ("normal_lo", C.c_void_p), ("depth_lo", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p),
+                ("depth", C.c_void_p), ("out", C.c_void_p), ("weight_out", C.c_void_p)]
+
+
 class RtAdaptiveDesc(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
 
@@ -167,6 +174,8 @@ AOV_THROUGH_DEFAULTS = {"max_bounces": 8, "fuzz_limit": 0.0}
 DENOISE_DEFAULTS = {"iterations": 5, "normal_sharpness": 4, "sigma_depth": 0.2, "sigma_color": 2.0, "color_floor": 0.01}
 # denoise(variance=...): the keyword defaults of the variance factor, settled by a sweep on the same frames
 DENOISE_VARIANCE_DEFAULTS = {"sigma_variance": 3.0, "variance_floor": 1e-4}
+# upscale(): the keyword defaults
+UPSCALE_DEFAULTS = dict(normal_sharpness=4, sigma_depth=0.2, min_weight=2**-6)
 # reproject() / TemporalAccumulator: the keyword defaults of rt_reproject's four thresholds
 REPROJECT_DEFAULTS = {"alpha_min": 0.5, "depth_tol": 0.05, "normal_min": 0.5, "max_history": 32.0}
 # reproject(): out is the accumulated frame (the next call's history), length its per-pixel history length, motion the
@@ -198,7 +207,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances",
                   "rt_debug_box_tests", "rt_reproject_instances",
                   "rt_scene_update_quads", "rt_scene_get_quads", "rt_refit_quads", "rt_multi_update_quads", "rt_debug_scene_quads",
-                  "rt_reproject_quads", "rt_debug_arith_tests", "rt_debug_math_tests"]
+                  "rt_reproject_quads", "rt_debug_arith_tests", "rt_debug_math_tests", "rt_upscale"]
 
 _rt = None
 _host = None
@@ -288,6 +297,8 @@ def rt_lib():
         L.rt_render_variance.argtypes = [C.c_void_p, C.POINTER(RtFrameDesc), C.POINTER(RtVarianceDesc), C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.POINTER(RtStats)]
         L.rt_denoise_variance.argtypes = [C.POINTER(RtDenoiseDesc), C.POINTER(RtDenoiseVarianceDesc), C.c_int, C.c_void_p, C.c_int]
+        if hasattr(L, "rt_upscale"):   # (absent from an older library measured through RT_LIB_OVERRIDE)
+            L.rt_upscale.argtypes = [C.POINTER(RtUpscaleDesc), C.c_int, C.c_void_p, C.c_int]
         L.rt_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera), C.c_int]
         L.rt_scene_get_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera)]
         L.rt_multi_set_camera.argtypes = [C.c_void_p, C.POINTER(RtCamera), C.c_int]
@@ -680,6 +691,67 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations=DENOISE_D
         st = L.rt_denoise_variance(C.byref(d), C.byref(vd), *args)
     _status(st, "rt_denoise" if variance is None else "rt_denoise_variance")
     return out
+
+
+def upscale(color_lo, factor, albedo_lo=None, normal_lo=None, depth_lo=None, albedo=None, normal=None, depth=None, *,
+            normal_sharpness=UPSCALE_DEFAULTS["normal_sharpness"], sigma_depth=UPSCALE_DEFAULTS["sigma_depth"],
+            min_weight=UPSCALE_DEFAULTS["min_weight"], demodulate=None, out=None, weight_out=None, stream=0, blocking=True):
+    """The guided upscaler of rt_upscale (include/rt_abi.h): a coarse linear frame `color_lo` (ly, lx, 3) -- render() at gamma 1
+    of the nx/factor x ny/factor frame of a camera -- rebuilt at `factor` times the size, guided by the feature buffers of
+    render_aov on both grids: albedo_lo, normal_lo (ly, lx, 3) and depth_lo (ly, lx) of the coarse frame, albedo, normal
+    (ny, nx, 3) and depth (ny, nx) of the full one, each optional; a normal or a depth takes part only when given on both
+    grids, and one given on one grid only is a ValueError.  It runs on the device of init().
+
+    Either all numpy float32 arrays (C-contiguous; the call waits) or all contiguous float32 torch tensors on that device:
+    zero-copy, enqueued on `stream` (a hipStream_t as an integer or a torch.cuda.Stream) and waited for only with
+    blocking=True.  The output is (factor ly, factor lx, 3); a full-resolution guide must have that size.  out: None (an
+    array or tensor is made) or one of that shape; weight_out: None or (ny, nx), receives W / W0, the share of the spline's
+    weight the guides let through.  demodulate=None means "when both albedos are given".  Returns out.  Malformed arguments
+    raise ValueError before anything is launched."""
+    bufs = _Buffers(isinstance(color_lo, np.ndarray), "color_lo", _initialised_device)
+    if not (bufs.on_host or hasattr(color_lo, "data_ptr")):
+        raise bufs.wrong_kind("color_lo", "a numpy array")
+    if color_lo.ndim != 3 or color_lo.shape[2] != 3 or color_lo.shape[0] < 1 or color_lo.shape[1] < 1:
+        raise ValueError(f"color_lo: shape {tuple(color_lo.shape)}, expected (ly, lx, 3)")
+    if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or not 2 <= int(factor) <= 8:
+        raise ValueError("factor must be an integer in 2..8")
+    if isinstance(normal_sharpness, bool) or not isinstance(normal_sharpness, (int, np.integer)) or not 0 <= int(normal_sharpness) <= 10:
+        raise ValueError("normal_sharpness must be an integer in 0..10")
+    sigma_depth, min_weight = float(sigma_depth), float(min_weight)
+    if not (sigma_depth == 0 or (np.isfinite(sigma_depth) and np.float32(1e-6) <= np.float32(sigma_depth) <= np.float32(1e6))):
+        raise ValueError("sigma_depth must be 0 or in [1e-6, 1e6]")
+    if not (np.isfinite(min_weight) and 0 <= min_weight <= 1):
+        raise ValueError("min_weight must be in [0, 1]")
+    factor, ly, lx = int(factor), int(color_lo.shape[0]), int(color_lo.shape[1])
+    ny, nx = factor * ly, factor * lx
+    if nx * ny >= 1 << 31:
+        raise ValueError("frame too large")
+    for k, v in (("albedo", albedo), ("normal", normal), ("depth", depth)):
+        if v is not None and hasattr(v, "shape") and tuple(v.shape[:2]) != (ny, nx):
+            raise ValueError(f"{k}: shape {tuple(v.shape)}, but factor {factor} times the coarse frame is {ny} x {nx}")
+    for k, a, b in (("normal", normal, normal_lo), ("depth", depth, depth_lo)):
+        if (a is None) != (b is None):
+            raise ValueError(f"{k} and {k}_lo must both be given or both be left out")
+    if demodulate is None:
+        demodulate = albedo_lo is not None and albedo is not None
+    if demodulate and (albedo_lo is None or albedo is None):
+        raise ValueError("demodulate needs albedo_lo and albedo")
+    rgb_lo, one_lo, rgb, one = (ly, lx, 3), (ly, lx), (ny, nx, 3), (ny, nx)
+    d = RtUpscaleDesc()
+    d.nx, d.ny, d.factor, d.normal_sharpness, d.demodulate = nx, ny, factor, int(normal_sharpness), 1 if demodulate else 0
+    d.sigma_depth, d.min_weight = sigma_depth, min_weight
+    d.color_lo, d.albedo_lo, d.normal_lo = (bufs.address(x, k, shape=rgb_lo) for k, x in (("color_lo", color_lo), ("albedo_lo", albedo_lo), ("normal_lo", normal_lo)))
+    d.depth_lo = bufs.address(depth_lo, "depth_lo", shape=one_lo)
+    d.albedo, d.normal, d.depth = bufs.address(albedo, "albedo", shape=rgb), bufs.address(normal, "normal", shape=rgb), bufs.address(depth, "depth", shape=one)
+    d.out, d.weight_out = bufs.address(out, "out", shape=rgb), bufs.address(weight_out, "weight_out", shape=one)
+    if out is None:   # (made last: every check has passed)
+        out = bufs.empty(rgb)
+        d.out = bufs.address(out, "out", shape=rgb)
+    _status(rt_lib().rt_upscale(C.byref(d), 0 if bufs.on_host else 1, _stream_arg(stream), 1 if blocking else 0), "rt_upscale")
+    return out
+
+
+_denoise = denoise   # (DeviceScene.render_upscaled has a parameter of that name)
 
 
 def make_camera(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist, t0=0.0, t1=0.0) -> RtCamera:
@@ -1330,6 +1402,48 @@ class DeviceScene:
         r = {"color": color, "noisy": noisy, "albedo": aov["albedo"], "normal": aov["normal"], "depth": aov["depth"]}
         if variance:
             r["variance"] = var
+        return r
+
+    def render_upscaled(self, frame: RtFrameDesc, factor: int = 2, denoise: bool = True, **args) -> dict:
+        """The nx x ny frame of `frame` from paths traced at nx/factor x ny/factor: render() of the coarse frame at gamma 1,
+        render_aov() of it (albedo, normal, depth at min(frame.ns, 16) samples), with denoise=True denoise() of the coarse
+        frame with its own guides, render_aov() of the full frame at min(frame.ns, 16) samples, and upscale() of the lot.
+        Keyword arguments named denoise_* go to denoise() with the prefix stripped, the others to upscale().
+
+        frame.ns is the COARSE frame's sample count: a coarse frame has 1 / factor^2 of the pixels, so equal path cost with a
+        full-resolution render at n samples is ns = n * factor^2.  The frame must be the whole nx x ny image with nx and ny
+        multiples of factor, otherwise ValueError.
+
+        Returns {"color": the upscaled linear frame (ny, nx, 3), "low": the coarse frame that was upscaled (denoised when
+        denoise), "albedo", "normal", "depth": the full-resolution guides, "weight": upscale()'s weight_out} as numpy
+        arrays, and with denoise=True "noisy_low", the coarse render before the filter."""
+        if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or not 2 <= int(factor) <= 8:
+            raise ValueError("factor must be an integer in 2..8")
+        factor = int(factor)
+        if frame.nx <= 0 or frame.ny <= 0 or frame.ns <= 0:
+            raise ValueError("bad frame size or sample count")
+        if frame.tile_first != 0 or frame.tile_stride != 1 or frame.tile_rows < frame.ny:
+            raise ValueError("render_upscaled needs the whole frame (tile_rows >= ny, tile_first = 0, tile_stride = 1)")
+        if frame.nx % factor or frame.ny % factor:
+            raise ValueError(f"render_upscaled needs nx and ny to be multiples of factor = {factor}")
+        denoise_args = {k[len("denoise_"):]: v for k, v in args.items() if k.startswith("denoise_")}
+        upscale_args = {k: v for k, v in args.items() if not k.startswith("denoise_")}
+        lo = RtFrameDesc.from_buffer_copy(frame)
+        lo.nx, lo.ny, lo.gamma = frame.nx // factor, frame.ny // factor, 1.0
+        lo.tile_rows = lo.ny
+        noisy, _ = self.render(lo)
+        lo.ns = min(frame.ns, 16)
+        g_lo = self.render_aov(lo, alpha=False)
+        low = _denoise(noisy, g_lo["albedo"], g_lo["normal"], g_lo["depth"], **denoise_args) if denoise else noisy
+        full = RtFrameDesc.from_buffer_copy(frame)
+        full.ns, full.gamma = min(frame.ns, 16), 1.0
+        g = self.render_aov(full, alpha=False)
+        weight = np.empty((frame.ny, frame.nx), np.float32)
+        color = upscale(low, factor, g_lo["albedo"], g_lo["normal"], g_lo["depth"], g["albedo"], g["normal"], g["depth"], weight_out=weight,
+                        **upscale_args)
+        r = {"color": color, "low": low, "albedo": g["albedo"], "normal": g["normal"], "depth": g["depth"], "weight": weight}
+        if denoise:
+            r["noisy_low"] = noisy
         return r
 
     def render_variance(self, frame: RtFrameDesc, batches: int, out=None, variance_out=None, stream=0):

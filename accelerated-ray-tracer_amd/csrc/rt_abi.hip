@@ -96,6 +96,8 @@ struct rt_options {
     int aov_through_lds = -1;    // rt_render_aov_through: as trace_lds
     int denoise_lds = -1;        // rt_denoise: -1 = iterations with taps up to 4 pixels apart stage tile + halo in LDS, 0 = never,
                                  // 1 = wherever the tile fits (taps up to 8 apart)
+    int upscale_lds = -1;        // rt_upscale: -1 (auto) and 1 = the coarse pixels a tile reaches are prepared once in LDS, 0 = every
+                                 // tap is read through L1/L2
     int adaptive_tier = -1;      // rt_render_adaptive: -1 = a pass goes to the tier kernel when its active pixels fit the tier waves at once
                                  // (DESIGN.md 4.8), 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit
 };
@@ -767,6 +769,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "aov_lds") { if (value < -1 || value > 2) return invalid("aov_lds: -1 (auto) .. 2"); g_opt.aov_lds = value; }
     else if (k == "aov_through_lds") { if (value < -1 || value > 2) return invalid("aov_through_lds: -1 (auto) .. 2"); g_opt.aov_through_lds = value; }
     else if (k == "denoise_lds") { if (value < -1 || value > 1) return invalid("denoise_lds: -1 (auto), 0 (direct) or 1 (staged)"); g_opt.denoise_lds = value; }
+    else if (k == "upscale_lds") { if (value < -1 || value > 1) return invalid("upscale_lds: -1 (auto), 0 (direct) or 1 (staged)"); g_opt.upscale_lds = value; }
     else if (k == "trace_tree") { if (value < 0 || value > 1) return invalid("trace_tree: 0 (reference tree) or 1 (walk array)"); g_opt.trace_tree = value; }
     else if (k == "adaptive_tier") { if (value < -1 || value > 1) return invalid("adaptive_tier: -1 (auto), 0 (main kernel) or 1 (tier kernel)"); g_opt.adaptive_tier = value; }
     else if (k == "wg_per_cu") { if (value < 0 || value > 8) return invalid("wg_per_cu: 0 (per kernel family) .. 8"); g_opt.wg_per_cu = value; }
@@ -1999,6 +2002,84 @@ rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stre
 rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_variance_desc* vd, int buffers_on_device, void* stream_v, int blocking) {
     if (!vd) return invalid("rt_denoise_variance: null variance description");
     return denoise_impl(d, vd, "rt_denoise_variance", buffers_on_device, stream_v, blocking);
+}
+
+// ---- rt_upscale (include/rt_abi.h)
+rt_status rt_upscale(const rt_upscale_desc* d, int buffers_on_device, void* stream_v, int blocking) {
+    // argument checks: no HIP call before they pass
+    const char* who = "rt_upscale";
+    auto bad = [&](const char* why) { return invalid((std::string(who) + ": " + why).c_str()); };
+    if (!d) return bad("null description");
+    if (!d->color_lo) return bad("null color_lo");
+    if (!d->out) return bad("null out");
+    if (d->factor < 2 || d->factor > 8) return bad("factor must be in 2..8");
+    if (d->nx < 1 || d->ny < 1 || d->nx % d->factor || d->ny % d->factor) return bad("nx and ny must be positive multiples of factor");
+    if ((long long)d->nx * d->ny >= (1ll << 31)) return bad("frame too large");
+    if (d->normal_sharpness < 0 || d->normal_sharpness > 10) return bad("normal_sharpness must be in 0..10");
+    if (!(d->sigma_depth == 0.f || (std::isfinite(d->sigma_depth) && d->sigma_depth >= 1e-6f && d->sigma_depth <= 1e6f)))
+        return bad("sigma_depth must be 0 or in [1e-6, 1e6]");
+    if (!(std::isfinite(d->min_weight) && d->min_weight >= 0.f && d->min_weight <= 1.f)) return bad("min_weight must be in [0, 1]");
+    if (!d->normal != !d->normal_lo) return bad("normal and normal_lo must both be given or both be null");
+    if (!d->depth != !d->depth_lo) return bad("depth and depth_lo must both be given or both be null");
+    if (d->demodulate && !(d->albedo_lo && d->albedo)) return bad("demodulate needs albedo_lo and albedo");
+    const int lx = d->nx / d->factor, ly = d->ny / d->factor;
+    const size_t pixels = (size_t)d->nx * d->ny, coarse = (size_t)lx * ly;
+    struct buffer : traced_ptr { bool input; };
+    enum { COLOR_LO = 0, ALBEDO_LO, NORMAL_LO, DEPTH_LO, ALBEDO, NORMAL, DEPTH, OUT, WEIGHT_OUT, N_BUFS };
+    const buffer bufs[N_BUFS] = {{{d->color_lo, 3 * coarse * sizeof(float), "color_lo", 4}, true}, {{d->albedo_lo, 3 * coarse * sizeof(float), "albedo_lo", 4}, true},
+                                 {{d->normal_lo, 3 * coarse * sizeof(float), "normal_lo", 4}, true}, {{d->depth_lo, coarse * sizeof(float), "depth_lo", 4}, true},
+                                 {{d->albedo, 3 * pixels * sizeof(float), "albedo", 4}, true}, {{d->normal, 3 * pixels * sizeof(float), "normal", 4}, true},
+                                 {{d->depth, pixels * sizeof(float), "depth", 4}, true}, {{d->out, 3 * pixels * sizeof(float), "out", 4}, false},
+                                 {{d->weight_out, pixels * sizeof(float), "weight_out", 4}, false}};
+    {   // nothing may share a byte with out or with weight_out
+        auto overlap = [](const buffer& a, const buffer& b) {
+            const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
+            return a.p && b.p && pa < pb + b.bytes && pb < pa + a.bytes;
+        };
+        for (int k = 0; k < N_BUFS; ++k) {
+            if (k != OUT && overlap(bufs[k], bufs[OUT])) return bad("out overlaps another buffer");
+            if (k != WEIGHT_OUT && overlap(bufs[k], bufs[WEIGHT_OUT])) return bad("weight_out overlaps another buffer");
+        }
+    }
+    RT_TRY(use_device(g_device));
+    if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, g_device, who));
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+
+    const bool normal_on = d->normal && d->normal_sharpness > 0, depth_on = d->depth && d->sigma_depth > 0.f;
+    // host buffers are staged in one allocation of this call's own
+    const void* dev[N_BUFS];
+    for (int k = 0; k < N_BUFS; ++k) dev[k] = bufs[k].p;
+    call_memory mem;
+    mem.guard(stream);
+    if (!buffers_on_device) {
+        size_t total = 0;
+        for (const buffer& b : bufs) if (b.p) total += call_memory::rounded(b.bytes);
+        char* at = nullptr;
+        HIPCHK(mem.get((void**)&at, total));
+        for (int k = 0; k < N_BUFS; ++k) if (bufs[k].p) dev[k] = call_memory::take(at, bufs[k].bytes);
+        for (int k = 0; k < N_BUFS; ++k)
+            if (bufs[k].input && bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, stream));
+    }
+    auto in = [&](int k, bool used) { return used ? static_cast<const float*>(dev[k]) : nullptr; };
+    rt_upscale_params up;
+    memset(&up, 0, sizeof(up));
+    up.color_lo = in(COLOR_LO, true);
+    up.albedo_lo = in(ALBEDO_LO, d->demodulate != 0); up.albedo = in(ALBEDO, d->demodulate != 0);
+    up.normal_lo = in(NORMAL_LO, normal_on); up.normal = in(NORMAL, normal_on);
+    up.depth_lo = in(DEPTH_LO, depth_on); up.depth = in(DEPTH, depth_on);
+    up.out = static_cast<float*>(const_cast<void*>(dev[OUT]));
+    up.weight_out = static_cast<float*>(const_cast<void*>(dev[WEIGHT_OUT]));
+    up.nx = d->nx; up.ny = d->ny; up.lx = lx; up.ly = ly; up.factor = d->factor;
+    up.tiles_x = (d->nx + RT_DENOISE_TILE - 1) / RT_DENOISE_TILE;
+    up.normal_sharpness = d->normal_sharpness; up.demodulate = d->demodulate ? 1 : 0;
+    up.sigma_depth = d->sigma_depth; up.min_weight = d->min_weight;
+    // staged or direct: auto is staged
+    HIPCHK(rt_launch_upscale(normal_on, depth_on, g_opt.upscale_lds != 0, up, stream));
+    if (!buffers_on_device)
+        for (int k : {(int)OUT, (int)WEIGHT_OUT}) if (bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
+    if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
+    mem.settled();
+    return RT_OK;
 }
 
 // ---- rt_reproject (include/rt_abi.h)

@@ -380,6 +380,33 @@ hipError_t rt_launch_denoise_pack(const rt_denoise_params& dp, bool guide, hipSt
 // staged: the tile and its 2 s halo through LDS (step <= RT_DENOISE_MAX_STAGED_STEP), else every tap through L1/L2
 hipError_t rt_launch_denoise(bool normal_on, bool depth_on, bool color_on, bool staged, const rt_denoise_params& dp, hipStream_t st);
 
+// rt_upscale (rt_kernel_upscale.hip): one launch, the pointers already checked on the host.  The denoiser's workgroup: 256
+// threads on a 16x16 tile of the output, one output pixel per lane.
+struct rt_upscale_params {
+    const float* color_lo;    // ly * lx * 3
+    const float* albedo_lo;   // null unless `demodulate`
+    const float* normal_lo;   // null unless the normal factor is on
+    const float* depth_lo;    // null unless the depth factor is on
+    const float* albedo;      // ny * nx * 3, null unless `demodulate`
+    const float* normal;      // ny * nx * 3, as normal_lo
+    const float* depth;       // ny * nx, as depth_lo
+    float* out;               // ny * nx * 3
+    float* weight_out;        // ny * nx or null
+    int32_t nx, ny;           // the output
+    int32_t lx, ly;           // the coarse frame: nx / factor, ny / factor
+    int32_t factor;
+    int32_t tiles_x;          // 16x16-pixel workgroup tiles per row band of the output
+    int32_t normal_sharpness; // m
+    int32_t demodulate;
+    float sigma_depth;
+    float min_weight;
+};
+// The coarse records a tile's taps reach: columns x0 / f - 1 .. (x0 + 15) / f + 1, at most 16 / 2 + 3 = 11 (f >= 2), and as many
+// rows.  The staged variant keeps them in static LDS, 11 x 11 records of 16 bytes in each of two arrays (3872 bytes).
+#define RT_UPSCALE_WINDOW 11
+// staged: the window through LDS, prepared once per workgroup; else every tap is read and prepared through L1/L2
+hipError_t rt_launch_upscale(bool normal_on, bool depth_on, bool staged, const rt_upscale_params& up, hipStream_t st);
+
 // rt_render_adaptive (rt_kernel_adaptive.hip): after each pass, one lane per pixel of that pass decides whether the pixel has
 // converged at checkpoint n (include/rt_abi.h), writes the converged ones to fb / spp and appends the others -- wave-aggregated
 // -- to list_out (local pixel ids, the main kernel's pixel list) and queue_out ((n << 32) | pixel, the tier kernel's tail queue).

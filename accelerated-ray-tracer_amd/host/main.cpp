@@ -8,6 +8,7 @@
 //
 //   rayTracer [--scene NAME] [--nx W --ny H] [--ns SPP] [--seed S]
 //             [--texture file.ppm] [--device N] [--gpus N] [--p6] [--progressive K] [--adaptive T [--min-spp M]] [--aov PREFIX] [--denoise [K] [--denoise-variance [B]]] [--list]
+//             [--upscale F]
 //             [--aov-through PREFIX] [--through-bounces N] [--through-fuzz F] [--denoise-through]
 //             [--orbit FRAMES DEGREES --out PREFIX [--temporal] [--bounce HEIGHT] [--spin DEGREES [--follow-instances]]
 //                                                  [--grow AMOUNT [--follow-quads]]]
@@ -48,6 +49,12 @@
 // gamma is applied on the host afterwards -- as powf(c, 1 / gamma) per channel, so the image is not rt_render's bit for bit
 // even where the filter changes nothing.  With --aov PREFIX the unfiltered frame is written to PREFIX_noisy.ppm as well.  Works
 // with --adaptive; not with --progressive or --gpus > 1.
+// --upscale F (F in 2..8; --nx and --ny, which stay the size of the image, must be multiples of it) traces the paths at
+// nx/F x ny/F and rebuilds the image with rt_upscale (the binding's defaults): the coarse frame is rendered at gamma 1 with --ns
+// samples -- a coarse frame has 1 / F^2 of the pixels, so equal path cost with a full render at n samples is --ns n F^2 --, the
+// feature pass runs on both grids at min(ns, 16) samples, --denoise [K], when given, filters the coarse frame with its own
+// guides before the upscale, and the frame's gamma is applied on the host afterwards, as --denoise does.  Not with --gpus > 1,
+// --progressive, --adaptive, --orbit, --aov, --aov-through, --denoise-variance or --denoise-through.
 // --denoise-variance [B] (needs --denoise) makes the filter variance-guided (rt_denoise_variance, the binding's defaults): the
 // frame comes from rt_render_variance with B batches -- when B is left out, the largest divisor of --ns in 2..16 (an --ns without one is refused) -- and
 // its per-pixel variance takes the colour factor's place.  --ns must be a multiple of B (2..64).  Not with --adaptive.
@@ -93,6 +100,7 @@ int main(int argc, char** argv) {
     int nx = 0, ny = 0, ns = 0, device = 0, gpus = 1, progressive = 0;
     bool p6 = false, adaptive = false;
     float threshold = 0.f;
+    int upscale = 0;
     int min_spp = 0, denoise = 0, batches = -1;   // batches: -1 = no --denoise-variance, 0 = B left out
     int orbit_frames = 0;
     double orbit_degrees = 0.0;
@@ -126,6 +134,10 @@ int main(int argc, char** argv) {
             if (!(std::isfinite(chain.fuzz_limit) && chain.fuzz_limit >= 0.f)) { fprintf(stderr, "--through-fuzz F: F must be finite and >= 0\n"); return 2; }
         }
         else if (k == "--denoise-through") denoise_through = true;
+        else if (k == "--upscale") {
+            upscale = atoi(val());
+            if (upscale < 2 || upscale > 8) { fprintf(stderr, "--upscale F: F must be in 2..8\n"); return 2; }
+        }
         else if (k == "--denoise") {   // K is optional: the next argument when it is a number
             denoise = 5;
             if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') denoise = atoi(argv[++a]);
@@ -189,6 +201,11 @@ int main(int argc, char** argv) {
         return 2;
     }
 
+    if (upscale && (gpus > 1 || progressive > 0 || adaptive || orbit_frames > 0 || !aov_prefix.empty() || !through_prefix.empty() || batches >= 0 || denoise_through)) {
+        fprintf(stderr, "--upscale cannot be combined with --gpus > 1, --progressive, --adaptive, --orbit, --aov, --aov-through, --denoise-variance or --denoise-through\n");
+        return 2;
+    }
+
     std::vector<unsigned char> tex;
     int tw = 0, th = 0;
     if (!texture_path.empty() && !rtw::load_ppm(texture_path, tex, tw, th)) {
@@ -199,6 +216,10 @@ int main(int argc, char** argv) {
     auto scene = rtw::build_scene(scene_name, nx, ny, tex.empty() ? nullptr : tex.data(), tw, th, err);
     if (!scene) { fprintf(stderr, "%s\n", err.c_str()); return 2; }
     if (ns > 0) scene->ns = ns;
+    if (upscale && (scene->nx % upscale || scene->ny % upscale)) {
+        fprintf(stderr, "--upscale %d: the image size %dx%d is not a multiple of it\n", upscale, scene->nx, scene->ny);
+        return 2;
+    }
     if (batches == 0) {   // the largest divisor of ns that is at most 16
         batches = scene->ns < 16 ? scene->ns : 16;
         while (batches > 1 && scene->ns % batches) --batches;
@@ -390,6 +411,52 @@ int main(int argc, char** argv) {
             fprintf(stderr, "frame %d: %.3f ms -> %s\n", k, stats.ms_render, path.c_str());
         }
         fprintf(stderr, "took %g seconds.\n", ms * 1e-3);
+        check(rt_scene_destroy(dev_scene), "rt_scene_destroy");
+        check(rt_shutdown(), "rt_shutdown");
+        return 0;
+    }
+    if (upscale) {
+        // paths on the coarse grid, guides on both, rt_upscale (DeviceScene.render_upscaled of the binding, call for call)
+        const int lx = scene->nx / upscale, ly = scene->ny / upscale;
+        const size_t px = (size_t)scene->nx * scene->ny, px_lo = (size_t)lx * ly;
+        check(rt_init(device), "rt_init");
+        check(rt_scene_create(&desc, &dev_scene), "rt_scene_create");
+        rt_frame_desc lo = f;
+        lo.nx = lx; lo.ny = ly; lo.gamma = 1.0f; lo.tile_rows = ly;
+        std::vector<float> low(px_lo * 3), albedo_lo(px_lo * 3), normal_lo(px_lo * 3), depth_lo(px_lo), albedo(px * 3), normal(px * 3), depth(px);
+        check(rt_render(dev_scene, &lo, low.data(), /*fb_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1, &stats), "rt_render");
+        fprintf(stderr, "took %g seconds.\n", stats.ms_render * 1e-3);
+        if (lo.ns > 16) lo.ns = 16;
+        rt_aov_desc aov;
+        memset(&aov, 0, sizeof(aov));
+        aov.albedo = albedo_lo.data(); aov.normal = normal_lo.data(); aov.depth = depth_lo.data();
+        check(rt_render_aov(dev_scene, &lo, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
+        if (denoise) {
+            rt_denoise_desc dn;
+            memset(&dn, 0, sizeof(dn));
+            dn.nx = lx; dn.ny = ly;
+            dn.color = low.data(); dn.albedo = albedo_lo.data(); dn.normal = normal_lo.data(); dn.depth = depth_lo.data();
+            dn.out = low.data();
+            dn.iterations = denoise; dn.normal_sharpness = 4; dn.demodulate = 1;
+            dn.sigma_color = 2.0f; dn.color_floor = 0.01f; dn.sigma_depth = 0.2f;
+            check(rt_denoise(&dn, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_denoise");
+        }
+        rt_frame_desc full = f;
+        full.gamma = 1.0f;
+        if (full.ns > 16) full.ns = 16;
+        aov.albedo = albedo.data(); aov.normal = normal.data(); aov.depth = depth.data();
+        check(rt_render_aov(dev_scene, &full, &aov, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_render_aov");
+        rt_upscale_desc u;
+        memset(&u, 0, sizeof(u));
+        u.nx = scene->nx; u.ny = scene->ny; u.factor = upscale;
+        u.normal_sharpness = 4; u.demodulate = 1; u.sigma_depth = 0.2f; u.min_weight = 0.015625f;
+        u.color_lo = low.data(); u.albedo_lo = albedo_lo.data(); u.normal_lo = normal_lo.data(); u.depth_lo = depth_lo.data();
+        u.albedo = albedo.data(); u.normal = normal.data(); u.depth = depth.data();
+        u.out = fb.data();
+        check(rt_upscale(&u, /*buffers_on_device=*/0, /*stream=*/nullptr, /*blocking=*/1), "rt_upscale");
+        if (scene->gamma != 1.0f) for (float& c : fb) c = powf(c, 1.0f / scene->gamma);
+        if (p6) rtw::write_ppm_p6(stdout, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
+        else rtw::write_ppm_p3(stdout, fb.data(), scene->nx, scene->ny, scene->ppm_double_scale);
         check(rt_scene_destroy(dev_scene), "rt_scene_destroy");
         check(rt_shutdown(), "rt_shutdown");
         return 0;

@@ -588,6 +588,73 @@ typedef struct rt_denoise_variance_desc {
 } rt_denoise_variance_desc; /* 24 B */
 rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_variance_desc* vd, int buffers_on_device, void* stream, int blocking);
 
+/* ---- upscaler: joint bilateral upsampling of a coarse frame, guided by full-resolution feature buffers ----
+ * u = (i + xi) / nx (main.cu:120-121), so a frame of nx/f x ny/f pixels on the same rt_camera is the same view, and coarse pixel
+ * (I, J) covers the output pixels f I .. f I + f - 1 x f J .. f J + f - 1.  The paths cost 2-7 rays per sample at hundreds of
+ * samples, the feature pass one primary ray per sample at 16 samples at most: rt_upscale rebuilds the nx x ny frame from paths
+ * traced on the coarse grid and the guides of both grids.  It takes no scene and runs on the device the last rt_init selected.
+ *
+ * The numerical contract.  All arithmetic is binary32, every written operation is rounded once, nothing is contracted into
+ * an FMA, sums run left to right as written; only + - * /, max, abs and comparisons occur.  Images are whole frames, row-major,
+ * row 0 at the bottom.  lx = nx / factor, ly = ny / factor.  color_lo (x3, required), albedo_lo (x3), normal_lo (x3) and
+ * depth_lo (x1) are what rt_render (gamma 1) and rt_render_aov write for the lx x ly frame; albedo, normal and depth are what
+ * rt_render_aov writes for the nx x ny frame of the same camera.
+ *   Prepare.  demodulate != 0: x(Q) = color_lo(Q) / max(albedo_lo(Q), 2^-10) per channel (albedo_lo or albedo null is then
+ *     RT_ERR_INVALID); otherwise x = color_lo.
+ *   Position.  Output pixel p = (i, j), f = factor:  I = i / f (integers), r = i - I f;  J and s from j likewise.
+ *     c = (float)(2 r + 1) / (float)(2 f) - 0.5f;  a = 0.5f - c;  b = 0.5f + c;
+ *     B_x[-1] = 0.5f (a a);  B_x[0] = 0.75f - c c;  B_x[+1] = 0.5f (b b)  -- the quadratic B-spline: the three sum to one and
+ *     reproduce a linear ramp.  B_y comes from s the same way.
+ *   Taps.  W0 = W = 0, S0 = S = (0, 0, 0).  For dy = -1..1 (outer), dx = -1..1 (inner), Q = (I + dx, J + dy); a Q outside the
+ *     coarse image is skipped.  g = B_y[dy] B_x[dx];  w = g, then w = w * factor for each factor that is on, in this order:
+ *       normal  (normal and normal_lo non-null and normal_sharpness = m in 1..10; 0 = off):
+ *               d = (Np.x Nq.x + Np.y Nq.y) + Np.z Nq.z;  d = max(d, 0);  then d = d d, m times;  the factor is d.
+ *       depth   (depth and depth_lo non-null and sigma_depth > 0):
+ *               den = sigma_depth max(Zp, Zq) + 1e-20f;  r = |Zp - Zq| / den;  t = max(1 - r, 0);  the factor is t t.
+ *     Np, Zp are the output pixel's guides, Nq, Zq the coarse tap's.  Every tap takes the factors, the middle one included
+ *     (there is no free centre tap as in rt_denoise: the middle tap is another pixel of another grid).  Then W0 = W0 + g,
+ *     S0.ch = S0.ch + g x(Q).ch, W = W + w, S.ch = S.ch + w x(Q).ch.
+ *   Choose.  guided = (W >= min_weight * W0) and (W > 0).  result.ch = S.ch / W when guided, else S0.ch / W0: the plain spline,
+ *     for pixels no coarse tap resembles -- and for misses, whose normal is 0 and whose normal factor therefore is.  W0 > 0
+ *     always: tap (I, J) is inside the coarse image and B[0] >= 0.5.
+ *   Finish.  out = result * max(albedo(p), 2^-10) per channel when demodulating, else result.  No gamma is applied.
+ *     weight_out = W / W0, whichever branch was taken.
+ * tests/upscale_expect.py restates this in NumPy float32; the device result equals it bit for bit.  Inputs are expected to
+ * be finite; what a NaN or an infinity does to the output pixels within reach of it is unspecified, but no value of any
+ * input makes the call fault: no address depends on pixel data.
+ *
+ * Parameters (anything else is RT_ERR_INVALID): factor 2..8; nx and ny positive multiples of it and nx ny < 2^31;
+ * normal_sharpness 0..10; sigma_depth 0 or finite in [1e-6, 1e6]; min_weight finite and in [0, 1]; color_lo and out non-null;
+ * normal and normal_lo both null or both given, depth and depth_lo likewise; out and weight_out share no byte with any other
+ * buffer, where the host can see it (undefined otherwise).
+ *
+ * Buffers: rt_denoise's rules.  buffers_on_device != 0: every non-null buffer is device or managed memory of that device,
+ * 4-byte aligned, checked with hipPointerGetAttributes before anything is launched; the work is enqueued on `stream` and
+ * with `blocking` != 0 the call returns when out is written.  buffers_on_device == 0: host memory; the library stages the
+ * buffers in device memory of the call's own, copies out and weight_out back and returns when it is complete, whatever
+ * `blocking` says.  There is no workspace.  The argument checks run before any HIP call and rt_last_error_detail() names the
+ * one that failed.  The call uses no scene and no shared state, so it may run beside a pending non-blocking rt_render on
+ * another stream.  Option "upscale_lds": -1 (auto) and 1 = a workgroup prepares the coarse pixels its 16x16 output tile
+ * reaches once, in LDS; 0 = every tap is read through L1/L2.  It changes no result. */
+typedef struct rt_upscale_desc {
+    int32_t nx, ny;            /* size of the output; lx = nx / factor, ly = ny / factor */
+    int32_t factor;            /* 2..8; nx and ny must be multiples of it */
+    int32_t normal_sharpness;  /* 0..10, 0 = normal factor off (rt_denoise's meaning) */
+    int32_t demodulate, reserved;
+    float sigma_depth;         /* 0 = off, else finite in [1e-6, 1e6] */
+    float min_weight;          /* finite, in [0, 1] */
+    const float* color_lo;     /* ly*lx*3, linear; required */
+    const float* albedo_lo;    /* ly*lx*3 or null */
+    const float* normal_lo;    /* ly*lx*3 or null */
+    const float* depth_lo;     /* ly*lx   or null */
+    const float* albedo;       /* ny*nx*3 or null */
+    const float* normal;       /* ny*nx*3 or null */
+    const float* depth;        /* ny*nx   or null */
+    float* out;                /* ny*nx*3; required */
+    float* weight_out;         /* ny*nx or null */
+} rt_upscale_desc; /* 104 B */
+rt_status rt_upscale(const rt_upscale_desc* d, int buffers_on_device, void* stream, int blocking);
+
 /* ---- a camera per frame: another view of a scene that stays on the device ----
  * rt_scene_create copies the description's camera into the scene; rt_scene_set_camera replaces it, so that a turntable or a
  * viewport renders frame after frame without a second rt_scene_create (upload, tier data, calibration passes, regrouping and
