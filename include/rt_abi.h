@@ -429,9 +429,10 @@ rt_status rt_render_aov_through(rt_scene* scene, const rt_frame_desc* f, const r
  * It takes no scene and runs on the device the last rt_init selected.
  *
  * The numerical contract.  All arithmetic is binary32, every written operation is rounded once, nothing is contracted
- * into an FMA, sums run left to right as written; only + - * /, max, abs and comparisons occur.  Images are whole frames of
- * ny x nx pixels, row-major, row 0 at the bottom, as rt_render writes an unpartitioned frame: color (x3) is required;
- * albedo (x3), normal (x3) and depth (x1) are optional and are what rt_render_aov writes.
+ * into an FMA, sums run left to right as written; only + - * /, max, abs and comparisons occur (max returns the other operand
+ * when one is a NaN); subnormal results are kept, never flushed to zero.  Images are whole frames of ny x nx pixels,
+ * row-major, row 0 at the bottom, as rt_render writes an unpartitioned frame: color (x3) is required; albedo (x3), normal (x3)
+ * and depth (x1) are optional and are what rt_render_aov writes.
  *   Prepare.  demodulate != 0: per channel a = max(albedo, 2^-10), x_0 = color / a (a null albedo is then RT_ERR_INVALID);
  *     otherwise x_0 = color.
  *   Iteration k = 0 .. iterations-1, s = 2^k, pixel p = (i, j).  W = 0, S = (0, 0, 0).  For dy = -2..2 (outer), dx = -2..2
@@ -449,8 +450,11 @@ rt_status rt_render_aov_through(rt_scene* scene, const rt_frame_desc* f, const r
  *     Then W = W + w and, per channel, S.ch = S.ch + w xq.ch.  After the 25 taps x_{k+1}(p).ch = S.ch / W.
  *   Finish.  out = x_K a per channel when demodulating, else x_K.  No gamma is applied.
  * tests/denoise_expect.py restates this in NumPy float32; the device result equals it bit for bit.
- * Inputs are expected to be finite.  What a NaN or an infinity does to the pixels within reach of it (2 (2^K - 1) pixels
- * each way) is unspecified, but no value of any input makes the call fault: no address depends on pixel data.
+ * Inputs are expected to be finite.  A NaN, an infinity or a negative depth or albedo changes nothing beyond the pixels within
+ * reach of it (2 (2^K - 1) pixels each way); within reach the result is what the rules above give in IEEE 754 arithmetic with
+ * that max -- a NaN where the restatement has one (its sign and payload are not specified), the restatement's bits elsewhere.
+ * So a NaN depth or normal takes its taps' weight away (max(1 - NaN, 0) = 0) and a non-finite colour spreads as NaN (0 x NaN).
+ * No value of any input makes the call fault: no address depends on pixel data.  (tests/test_filter_domain.py)
  *
  * Parameters (anything else is RT_ERR_INVALID): iterations 1..8; nx, ny >= 1 and nx ny < 2^31; normal_sharpness 0..10;
  * sigma_depth and sigma_color each 0 or finite in [1e-6, 1e6]; color_floor finite and > 0 when sigma_color > 0; color and
@@ -576,11 +580,14 @@ rt_status rt_render_variance(rt_scene* scene, const rt_frame_desc* f, const rt_v
  *     t = max(1 - r, 0);  the factor is t t.  Beside W and S every tap, the centre included, adds with its final w
  *     Sv = Sv + (w w) vq, Sv from 0;  after the 25 taps v_{k+1}(p) = Sv / (W W).
  *   Finish.  variance_out = (v_K / t) / t when demodulating (t of the pixel, as above), else v_K.
- * Only + - * /, max, abs and comparisons occur; there is no square root.  The variance is expected to be finite and >= 0
- * (zeros are fine: the floor keeps den positive); what a negative or non-finite one does to the pixels within reach of it is
- * unspecified, but nothing faults: no address depends on data.  tests/variance_expect.py restates this in NumPy float32; the
- * device result equals it bit for bit.  A null d or vd and every violation above is RT_ERR_INVALID before any HIP call, and
- * rt_last_error_detail() names the failed check. */
+ * Only + - * /, max, abs and comparisons occur (max returns the other operand when one is a NaN); there is no square root.
+ * The variance is expected to be finite and >= 0 (zeros are fine: the floor keeps den positive, a subnormal one included:
+ * nothing is flushed to zero).  A negative or non-finite variance changes nothing beyond the pixels within reach of it --
+ * 2 (2^K - 1) + 1 pixels each way, the pre-blur's one more; the same for an albedo when demodulating, 2 (2^K - 1) for the other
+ * inputs -- and within reach the result is rt_denoise's rule: the restatement's, NaN for NaN.  Nothing faults: no address
+ * depends on data.  tests/variance_expect.py restates this in NumPy float32; the device result equals it bit for bit.
+ * A null d or vd and every violation above is RT_ERR_INVALID before any HIP call, and rt_last_error_detail() names the
+ * failed check. */
 typedef struct rt_denoise_variance_desc {
     const float* variance;     /* ny*nx, what rt_render_variance writes; required */
     float* variance_out;       /* ny*nx or null: the filtered variance */
@@ -595,7 +602,8 @@ rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_varianc
  * traced on the coarse grid and the guides of both grids.  It takes no scene and runs on the device the last rt_init selected.
  *
  * The numerical contract.  All arithmetic is binary32, every written operation is rounded once, nothing is contracted into
- * an FMA, sums run left to right as written; only + - * /, max, abs and comparisons occur.  Images are whole frames, row-major,
+ * an FMA, sums run left to right as written; only + - * /, max, abs and comparisons occur (max returns the other operand when
+ * one is a NaN); subnormal results are kept, never flushed to zero.  Images are whole frames, row-major,
  * row 0 at the bottom.  lx = nx / factor, ly = ny / factor.  color_lo (x3, required), albedo_lo (x3), normal_lo (x3) and
  * depth_lo (x1) are what rt_render (gamma 1) and rt_render_aov write for the lx x ly frame; albedo, normal and depth are what
  * rt_render_aov writes for the nx x ny frame of the same camera.
@@ -620,8 +628,11 @@ rt_status rt_denoise_variance(const rt_denoise_desc* d, const rt_denoise_varianc
  *   Finish.  out = result * max(albedo(p), 2^-10) per channel when demodulating, else result.  No gamma is applied.
  *     weight_out = W / W0, whichever branch was taken.
  * tests/upscale_expect.py restates this in NumPy float32; the device result equals it bit for bit.  Inputs are expected to
- * be finite; what a NaN or an infinity does to the output pixels within reach of it is unspecified, but no value of any
- * input makes the call fault: no address depends on pixel data.
+ * be finite.  A NaN, an infinity or a negative depth or albedo in coarse pixel Q changes nothing beyond the output pixels with
+ * I in Qx - 1 .. Qx + 1 and J in Qy - 1 .. Qy + 1, one in a full-resolution guide nothing beyond its own pixel; within that
+ * reach out and weight_out are what the rules above give in IEEE 754 arithmetic with that max -- a NaN where the restatement
+ * has one (sign and payload not specified), its bits elsewhere.  No value of any input makes the call fault: no address
+ * depends on pixel data.  (tests/test_filter_domain.py)
  *
  * Parameters (anything else is RT_ERR_INVALID): factor 2..8; nx and ny positive multiples of it and nx ny < 2^31;
  * normal_sharpness 0..10; sigma_depth 0 or finite in [1e-6, 1e6]; min_weight finite and in [0, 1]; color_lo and out non-null;

@@ -35,15 +35,16 @@ def _shift(a, s, dx, dy):
 
 
 def denoise(color, albedo=None, normal=None, depth=None, *, iterations, sigma_color, color_floor, normal_sharpness, sigma_depth,
-            demodulate=None):
-    """color (ny, nx, 3), albedo / normal (ny, nx, 3) or None, depth (ny, nx) or None -> (ny, nx, 3) float32."""
+            demodulate=None, steps=None):
+    """color (ny, nx, 3), albedo / normal (ny, nx, 3) or None, depth (ny, nx) or None -> (ny, nx, 3) float32.
+    steps: None (the contract: s = 2^k), or the tap spacing of each iteration -- for tests that ask what a wrong one would do."""
     color = np.asarray(color, F)
     if demodulate is None:
         demodulate = albedo is not None
     sigma_color, color_floor, sigma_depth = F(sigma_color), F(color_floor), F(sigma_depth)
     with np.errstate(all="ignore"):
         if demodulate:
-            a = np.maximum(np.asarray(albedo, F), ALBEDO_FLOOR)
+            a = np.fmax(np.asarray(albedo, F), ALBEDO_FLOOR)
             x = color / a
         else:
             x = color.copy()
@@ -53,7 +54,7 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations, sigma_co
         N = np.asarray(normal, F) if normal_on else None
         Z = np.asarray(depth, F) if depth_on else None
         for k in range(iterations):
-            s = 1 << k
+            s = 1 << k if steps is None else steps[k]
             sck = sigma_color * F(2.0 ** -k)
             W = np.zeros(x.shape[:2], F)
             S = np.zeros(x.shape, F)
@@ -66,22 +67,22 @@ def denoise(color, albedo=None, normal=None, depth=None, *, iterations, sigma_co
                         if normal_on:
                             Nq, _ = _shift(N, s, dx, dy)
                             d = (N[..., 0] * Nq[..., 0] + N[..., 1] * Nq[..., 1]) + N[..., 2] * Nq[..., 2]
-                            d = np.maximum(d, F(0))
+                            d = np.fmax(d, F(0))
                             for _ in range(normal_sharpness):
                                 d = d * d
                             w = w * d
                         if depth_on:
                             Zq, _ = _shift(Z, s, dx, dy)
-                            den = sigma_depth * np.maximum(Z, Zq) + TINY
+                            den = sigma_depth * np.fmax(Z, Zq) + TINY
                             r = np.abs(Z - Zq) / den
-                            t = np.maximum(F(1) - r, F(0))
+                            t = np.fmax(F(1) - r, F(0))
                             w = w * (t * t)
                         if color_on:
                             sq = (xq[..., 0] + xq[..., 1]) + xq[..., 2]
                             d1 = (np.abs(x[..., 0] - xq[..., 0]) + np.abs(x[..., 1] - xq[..., 1])) + np.abs(x[..., 2] - xq[..., 2])
                             den = sck * ((sp + sq) + color_floor)
                             r = d1 / den
-                            t = np.maximum(F(1) - r, F(0))
+                            t = np.fmax(F(1) - r, F(0))
                             w = w * (t * t)
                     assert w.dtype == F
                     W = np.where(ok, W + w, W)
@@ -111,6 +112,53 @@ def synthetic(nx, ny, seed):
     depth[blocky] = (depth[(by * 4).clip(0, ny - 1), (bx * 5).clip(0, nx - 1)] * rng.uniform(0.98, 1.02, (ny, nx)))[blocky]
     depth[rng.random((ny, nx)) < 0.1] = 0
     return {"color": color, "albedo": albedo, "normal": n.astype(F), "depth": depth.astype(F)}
+
+
+def reach(iterations):
+    """How far, each way, one input pixel can be felt in the output: the sum of 2 s over the iterations."""
+    return 2 * ((1 << iterations) - 1)
+
+
+FLAT_COLOR, FLAT_ALBEDO = (0.5, 0.25, 0.125), (0.5, 0.5, 0.25)
+
+
+def flat_regions(nx, ny):
+    """(black, flat) of synthetic_flat: (j0, j1, i0, i1) of the 3 x 5 block of black pixels and of the flat region."""
+    return (ny // 3, ny // 3 + 3, nx // 4, nx // 4 + 5), (ny // 2, min(ny, ny // 2 + 12), nx // 2, min(nx, nx // 2 + 16))
+
+
+def synthetic_flat(nx, ny, seed):
+    """synthetic()'s frame with what its random fields never hold.  The normal and the depth are exactly constant on blocks
+    of 7 x 6 pixels, without jitter (a tenth of the blocks at depth 0), so that the depth factor is exactly 1 inside a block
+    however small sigma_depth is.  A 3 x 5 block and six isolated pixels are exactly black, as in a few-sample frame of a
+    dark scene: between two of them the colour factor's denominator is sigma times the floor alone.  And a region of 12 x 16
+    pixels has one colour and one albedo, so that a tap pair there differs by exactly 0."""
+    s = synthetic(nx, ny, seed)
+    rng = np.random.default_rng(seed + 5)
+    by, bx = np.arange(ny)[:, None] // 6, np.arange(nx)[None, :] // 7
+    bn = rng.normal(size=(by.max() + 1, bx.max() + 1, 3))
+    bn /= np.linalg.norm(bn, axis=2, keepdims=True)
+    bz = rng.uniform(0.5, 30.0, bn.shape[:2])
+    bz[rng.random(bz.shape) < 0.1] = 0
+    s["normal"], s["depth"] = np.ascontiguousarray(bn[by, bx], F), np.ascontiguousarray(bz[by, bx], F)
+    (j0, j1, i0, i1), (fj0, fj1, fi0, fi1) = flat_regions(nx, ny)
+    s["color"][fj0:fj1, fi0:fi1], s["albedo"][fj0:fj1, fi0:fi1] = F(FLAT_COLOR), F(FLAT_ALBEDO)
+    s["color"][j0:j1, i0:i1] = 0
+    s["color"][rng.integers(0, ny, 6), rng.integers(0, nx, 6)] = 0
+    return s
+
+
+def synthetic_smooth(nx, ny, seed):
+    """A frame in which taps hundreds of pixels apart still carry weight, as on one evenly lit wall: the light is one colour
+    with 20 % noise per pixel, the normal one direction with a jitter of N(0, 0.02), the depth 10 within 3 %; the albedo is
+    synthetic()'s.  (On synthetic()'s random blocks a far tap's weight is 0 or rounds away.)"""
+    rng = np.random.default_rng(seed + 9)
+    albedo = synthetic(nx, ny, seed)["albedo"]
+    light = np.array([1.0, 0.7, 0.4]) * rng.uniform(0.8, 1.2, (ny, nx, 3))
+    n = np.array([0.36, 0.48, 0.8]) + rng.normal(0.0, 0.02, (ny, nx, 3))
+    n /= np.linalg.norm(n, axis=2, keepdims=True)
+    depth = 10.0 * rng.uniform(0.97, 1.03, (ny, nx))
+    return {"color": (albedo * light).astype(F), "albedo": albedo, "normal": n.astype(F), "depth": depth.astype(F)}
 
 
 def oracle_frame(art, orc, key, ns=4, nx=None, ny=None):

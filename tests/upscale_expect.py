@@ -46,7 +46,7 @@ def upscale(color_lo, factor, albedo_lo=None, normal_lo=None, depth_lo=None, alb
     normal_on = normal is not None and normal_lo is not None and normal_sharpness > 0
     depth_on = depth is not None and depth_lo is not None and sigma_depth > 0
     with np.errstate(all="ignore"):
-        x = color_lo / np.maximum(np.asarray(albedo_lo, F), ALBEDO_FLOOR) if demodulate else color_lo
+        x = color_lo / np.fmax(np.asarray(albedo_lo, F), ALBEDO_FLOOR) if demodulate else color_lo
         Bx, I = spline_weights(nx, f)
         By, J = spline_weights(ny, f)
         Np = np.asarray(normal, F) if normal_on else None
@@ -66,15 +66,15 @@ def upscale(color_lo, factor, albedo_lo=None, normal_lo=None, depth_lo=None, alb
                 if normal_on:
                     Nq = np.asarray(normal_lo, F)[at]
                     d = (Np[..., 0] * Nq[..., 0] + Np[..., 1] * Nq[..., 1]) + Np[..., 2] * Nq[..., 2]
-                    d = np.maximum(d, F(0))
+                    d = np.fmax(d, F(0))
                     for _ in range(normal_sharpness):
                         d = d * d
                     w = w * d
                 if depth_on:
                     Zq = np.asarray(depth_lo, F)[at]
-                    den = sigma_depth * np.maximum(Zp, Zq) + TINY
+                    den = sigma_depth * np.fmax(Zp, Zq) + TINY
                     r = np.abs(Zp - Zq) / den
-                    t = np.maximum(F(1) - r, F(0))
+                    t = np.fmax(F(1) - r, F(0))
                     w = w * (t * t)
                 assert g.dtype == F and w.dtype == F and xq.dtype == F
                 W0 = np.where(ok, W0 + g, W0)
@@ -84,7 +84,7 @@ def upscale(color_lo, factor, albedo_lo=None, normal_lo=None, depth_lo=None, alb
         guided = (W >= min_weight * W0) & (W > F(0))
         out = np.where(guided[..., None], S / W[..., None], S0 / W0[..., None])
         if demodulate:
-            out = out * np.maximum(np.asarray(albedo, F), ALBEDO_FLOOR)
+            out = out * np.fmax(np.asarray(albedo, F), ALBEDO_FLOOR)
         wout = W / W0
         assert out.dtype == F and wout.dtype == F
     if weight == "mask":
@@ -135,9 +135,42 @@ def synthetic(nx, ny, f, seed):
             "albedo": c(albedo, F), "normal": c(n, F), "depth": c(z, F)}
 
 
+def synthetic_blocks(nx, ny, f, seed):
+    """synthetic() with fine guides that are exactly constant on blocks of (5f+1) x (4f+1) pixels: no jitter and no misses.  The
+    normal of half the blocks is one of the six axis directions, of the others a random unit vector rounded to binary32; the
+    depths are binary32 values.  A coarse pixel inside one block then holds exactly its guides (the mean of f f equal binary32
+    values, taken in double, is that value), so an output pixel whose taps lie in its own block has a depth factor of exactly
+    1 at any sigma_depth, and under an axis normal W = W0 exactly; a coarse pixel across a block border holds a mixture no
+    output pixel matches.  The coarse guides are made first; then 8 % of the fine pixels are replaced by a random normal and a
+    depth beyond every block's, for the plain branch."""
+    s = synthetic(nx, ny, f, seed)
+    rng = np.random.default_rng(seed + 5)
+    bw, bh = 5 * f + 1, 4 * f + 1
+    nbx, nby = (nx + bw - 1) // bw, (ny + bh - 1) // bh
+    bn = rng.normal(size=(nby, nbx, 3))
+    bn /= np.linalg.norm(bn, axis=2, keepdims=True)
+    axes = np.concatenate([np.eye(3), -np.eye(3)])
+    axis = rng.random((nby, nbx)) < 0.5
+    axis[0, 0] = True
+    bn[axis] = axes[rng.integers(0, 6, (nby, nbx))][axis]
+    bz = rng.uniform(0.5, 30.0, (nby, nbx))
+    jj, ii = np.arange(ny)[:, None] // bh, np.arange(nx)[None, :] // bw
+    n, z = bn[jj, ii].astype(F).astype(np.float64), bz[jj, ii].astype(F).astype(np.float64)
+    c = np.ascontiguousarray
+    s.update(normal_lo=c(_box_mean(n, f), F), depth_lo=c(_box_mean(z, f), F))
+    # 8 % of the fine pixels, after the coarse guides are made, get a normal and a depth of their own: no tap resembles them
+    odd = rng.random((ny, nx)) < 0.08
+    rn = rng.normal(size=(ny, nx, 3))
+    rn /= np.linalg.norm(rn, axis=2, keepdims=True)
+    n[odd] = rn[odd]
+    z[odd] = rng.uniform(40.0, 80.0, (ny, nx))[odd]
+    s.update(normal=c(n, F), depth=c(z, F))
+    return s
+
+
 # the GPU test's shapes (output nx, ny, factor) and the seed of each: tests/test_upscale.py, tests/test_upscale_host.py
 SHAPES = [(2, 2, 2), (2, 140, 2), (140, 2, 2), (6, 4, 2), (34, 18, 2), (130, 66, 2), (3, 3, 3), (51, 33, 3), (195, 99, 3),
-          (68, 36, 4), (85, 45, 5), (136, 72, 8)]
+          (68, 36, 4), (85, 45, 5), (136, 72, 8), (36, 18, 6), (42, 21, 7), (6, 6, 6), (7, 7, 7)]
 
 
 def seed_of(nx, ny, f):

@@ -49,7 +49,7 @@ def render_variance(ex, n: int, batches: int, gamma: float = 1.0):
 
 # ----------------------------------------------------------------------------------------------- part 2: rt_denoise_variance
 def _variance_scale(albedo):
-    a = np.maximum(np.asarray(albedo, F), ALBEDO_FLOOR)
+    a = np.fmax(np.asarray(albedo, F), ALBEDO_FLOOR)
     return F(3) / ((a[..., 0] + a[..., 1]) + a[..., 2])
 
 
@@ -66,9 +66,10 @@ def preblur(u):
 
 
 def denoise_variance(color, variance, albedo=None, normal=None, depth=None, *, iterations, sigma_variance, variance_floor, normal_sharpness,
-                     sigma_depth, demodulate=None, sigma_color=0.0, color_floor=None):
+                     sigma_depth, demodulate=None, sigma_color=0.0, color_floor=None, steps=None):
     """color (ny, nx, 3), variance (ny, nx), guides as denoise_expect.denoise -> (out (ny, nx, 3), variance_out (ny, nx)), float32.
-    sigma_color / color_floor are accepted so that a DEFAULTS dict can be passed; sigma_color must be 0."""
+    sigma_color / color_floor are accepted so that a DEFAULTS dict can be passed; sigma_color must be 0.  steps: as in
+    denoise_expect.denoise."""
     assert sigma_color == 0
     color, variance = np.asarray(color, F), np.asarray(variance, F)
     if demodulate is None:
@@ -77,7 +78,7 @@ def denoise_variance(color, variance, albedo=None, normal=None, depth=None, *, i
     sigma2 = sigma_variance * sigma_variance
     with np.errstate(all="ignore"):
         if demodulate:
-            a = np.maximum(np.asarray(albedo, F), ALBEDO_FLOOR)
+            a = np.fmax(np.asarray(albedo, F), ALBEDO_FLOOR)
             x = color / a
             t = _variance_scale(albedo)
             u = (variance * t) * t
@@ -90,7 +91,7 @@ def denoise_variance(color, variance, albedo=None, normal=None, depth=None, *, i
         N = np.asarray(normal, F) if normal_on else None
         Z = np.asarray(depth, F) if depth_on else None
         for k in range(iterations):
-            s = 1 << k
+            s = 1 << k if steps is None else steps[k]
             W = np.zeros(x.shape[:2], F)
             S = np.zeros(x.shape, F)
             Sv = np.zeros(x.shape[:2], F)
@@ -103,20 +104,20 @@ def denoise_variance(color, variance, albedo=None, normal=None, depth=None, *, i
                         if normal_on:
                             Nq, _ = _shift(N, s, dx, dy)
                             d = (N[..., 0] * Nq[..., 0] + N[..., 1] * Nq[..., 1]) + N[..., 2] * Nq[..., 2]
-                            d = np.maximum(d, F(0))
+                            d = np.fmax(d, F(0))
                             for _ in range(normal_sharpness):
                                 d = d * d
                             w = w * d
                         if depth_on:
                             Zq, _ = _shift(Z, s, dx, dy)
-                            den = sigma_depth * np.maximum(Z, Zq) + TINY
+                            den = sigma_depth * np.fmax(Z, Zq) + TINY
                             r = np.abs(Z - Zq) / den
-                            tt = np.maximum(F(1) - r, F(0))
+                            tt = np.fmax(F(1) - r, F(0))
                             w = w * (tt * tt)
                         d1 = (np.abs(x[..., 0] - xq[..., 0]) + np.abs(x[..., 1] - xq[..., 1])) + np.abs(x[..., 2] - xq[..., 2])
                         den = sigma2 * (v + vq) + variance_floor
                         r = (d1 * d1) / den
-                        tt = np.maximum(F(1) - r, F(0))
+                        tt = np.fmax(F(1) - r, F(0))
                         w = w * (tt * tt)
                     assert w.dtype == F
                     W = np.where(ok, W + w, W)
@@ -138,6 +139,17 @@ def synthetic_variance(nx, ny, seed):
     v[rng.random((ny, nx)) < 0.15] = 0
     v[rng.random((ny, nx)) < 0.03] *= 50
     return v.astype(F)
+
+
+def synthetic_flat_variance(nx, ny, seed):
+    """synthetic_variance() for dx.synthetic_flat(nx, ny, ...): exactly 0 on the flat region and on the black block with two
+    pixels around it, so that the pre-blurred variance is 0 inside them and the variance factor's denominator between two of
+    their pixels is the floor alone -- where the colours are equal too: 0 / floor, a factor of exactly 1."""
+    v = synthetic_variance(nx, ny, seed)
+    (j0, j1, i0, i1), (fj0, fj1, fi0, fi1) = dx.flat_regions(nx, ny)
+    v[fj0:fj1, fi0:fi1] = 0
+    v[max(0, j0 - 2):j1 + 2, max(0, i0 - 2):i1 + 2] = 0
+    return v
 
 
 def oracle_frame(art, orc, key, ns=4, batches=4, nx=None, ny=None):
