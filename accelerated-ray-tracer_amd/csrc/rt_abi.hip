@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/rt_abi.h"
+#include "rt_call_buffers.h"
 #include "rt_device.h"
 #include "rt_refit_host.h"
 
@@ -159,9 +160,10 @@ template <class T> rt_status grow(T*& p, size_t& capacity, size_t need) {
 }
 
 // Device memory of one call, freed when the call returns: allocations of their own (get), which a caller may cut into
-// 256-byte-rounded pieces (rounded, take).  A call that enqueues work on the memory guards it with its stream: every way out
-// but the one through settled() -- the call has waited for its work -- synchronises that stream before the memory is freed.
-struct call_memory {
+// 256-byte-rounded pieces (rounded, take: rt_call_buffers.h).  A call that enqueues work on the memory guards it with its stream:
+// every way out but the one through settled() -- the call has waited for its work, or leaves it to the caller's stream (finish)
+// -- synchronises that stream before the memory is freed.
+struct call_memory : call_pieces {
     std::vector<void*> all;
     hipStream_t stream = nullptr;
     bool guarded = false;
@@ -172,8 +174,7 @@ struct call_memory {
     void guard(hipStream_t st) { stream = st; guarded = true; }
     void settled() { guarded = false; }
     hipError_t get(void** p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) all.push_back(*p); return e; }
-    static size_t rounded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    static char* take(char*& at, size_t bytes) { char* piece = at; at += rounded(bytes); return piece; }
+    rt_status finish(bool wait) { if (wait) HIPCHK(hipStreamSynchronize(stream)); settled(); return RT_OK; }
 };
 
 }  // namespace
@@ -1374,10 +1375,39 @@ rt_status check_trace_ptr(const void* p, size_t bytes, int device, const char* w
     }
     return RT_OK;
 }
-// a table of such pointers, checked in its order
-struct traced_ptr { const void* p; size_t bytes; const char* what; unsigned align; };
+// a table of such pointers (traced_ptr, rt_call_buffers.h), checked in its order
 extern "C++" template <class Table> rt_status check_trace_ptrs(const Table& table, int device, const char* who) {
     for (const traced_ptr& q : table) RT_TRY(check_trace_ptr(q.p, q.bytes, device, q.what, who, q.align));
+    return RT_OK;
+}
+
+// The image-space entries (rt_render_aov*, rt_denoise*, rt_upscale, rt_reproject*) keep their buffers in a table of call_buffer
+// (rt_call_buffers.h) beside dev[], the pointers their kernels get.  For host buffers those are images in one allocation of the
+// call's own, behind `lead` bytes the entry keeps for itself (`base`, if it asks for them): of the buffers for which used(k), in
+// table order.  (A HIP error in these helpers is reported with the helper's line and expression, not the entry's.)
+extern "C++" template <class Table, class Used>
+rt_status stage_buffers(call_memory& mem, const Table& table, Used used, const void** dev, size_t lead = 0, char** base = nullptr) {
+    char* memory = nullptr;
+    HIPCHK(mem.get((void**)&memory, staged_bytes(table, used, lead)));
+    place_staged(table, used, memory, lead, dev);
+    if (base) *base = memory;
+    return RT_OK;
+}
+// ... the used inputs go up and the given outputs come down on the call's stream
+extern "C++" template <class Table, class Used> rt_status upload_inputs(const Table& table, Used used, const void* const* dev, hipStream_t stream) {
+    int k = 0;
+    for (const call_buffer& b : table) {
+        if (used(k) && b.role == BUF_INPUT) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), b.p, b.bytes, hipMemcpyHostToDevice, stream));
+        ++k;
+    }
+    return RT_OK;
+}
+extern "C++" template <class Table> rt_status download_outputs(const Table& table, const void* const* dev, hipStream_t stream) {
+    int k = 0;
+    for (const call_buffer& b : table) {
+        if (b.p && b.role == BUF_OUTPUT) HIPCHK(hipMemcpyAsync(const_cast<void*>(b.p), dev[k], b.bytes, hipMemcpyDeviceToHost, stream));
+        ++k;
+    }
     return RT_OK;
 }
 
@@ -1818,27 +1848,22 @@ static rt_status aov_impl(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc
     rt_aov_through_params tp;
     memset(&tp, 0, sizeof(tp));
     const size_t pixels = g.n_pixels;
-    struct out_buffer : traced_ptr { void** dev; };
-    const out_buffer outs[] = {
-        {{a->albedo, 3 * pixels * sizeof(float), "albedo", 4}, (void**)&ap.albedo}, {{a->normal, 3 * pixels * sizeof(float), "normal", 4}, (void**)&ap.normal},
-        {{a->depth, pixels * sizeof(float), "depth", 4}, (void**)&ap.depth}, {{a->alpha, pixels * sizeof(float), "alpha", 4}, (void**)&ap.alpha},
-        {{a->prim, pixels * sizeof(int32_t), "prim", 4}, (void**)&ap.prim}, {{a->inst, pixels * sizeof(int32_t), "inst", 4}, (void**)&ap.inst},
-        {{a->mat, pixels * sizeof(int32_t), "mat", 4}, (void**)&ap.mat},
-        {{t ? t->through : nullptr, pixels * sizeof(float), "through", 4}, (void**)&tp.through},
-        {{t ? t->bounces : nullptr, pixels * sizeof(int32_t), "bounces", 4}, (void**)&tp.bounces}};
+    const size_t f1 = pixels * sizeof(float), i1 = pixels * sizeof(int32_t);
+    struct out_buffer : call_buffer { void** slot; };   // ... and where its device pointer goes
+    auto out = [](const void* p, size_t bytes, const char* what, const void* slot) { return out_buffer{{{p, bytes, what, 4}, BUF_OUTPUT}, (void**)slot}; };
+    const out_buffer bufs[] = {out(a->albedo, 3 * f1, "albedo", &ap.albedo), out(a->normal, 3 * f1, "normal", &ap.normal), out(a->depth, f1, "depth", &ap.depth),
+                               out(a->alpha, f1, "alpha", &ap.alpha), out(a->prim, i1, "prim", &ap.prim), out(a->inst, i1, "inst", &ap.inst),
+                               out(a->mat, i1, "mat", &ap.mat), out(t ? t->through : nullptr, f1, "through", &tp.through),
+                               out(t ? t->bounces : nullptr, i1, "bounces", &tp.bounces)};
+    enum { N_BUFS = sizeof(bufs) / sizeof(bufs[0]) };
+    if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, s->device, who_c));
     // host buffers are staged in one allocation of this call's own (no per-frame resource of rt_render is used)
+    const void* dev[N_BUFS];
+    for (int k = 0; k < N_BUFS; ++k) dev[k] = bufs[k].p;
     call_memory mem;
     mem.guard(stream);
-    if (buffers_on_device) {
-        RT_TRY(check_trace_ptrs(outs, s->device, who_c));
-        for (const auto& o : outs) *o.dev = const_cast<void*>(o.p);
-    } else {
-        size_t total = 0;
-        for (const auto& o : outs) if (o.p) total += call_memory::rounded(o.bytes);
-        char* staging = nullptr;
-        HIPCHK(mem.get((void**)&staging, total));
-        for (const auto& o : outs) if (o.p) *o.dev = call_memory::take(staging, o.bytes);
-    }
+    if (!buffers_on_device) RT_TRY(stage_buffers(mem, bufs, [&](int k) { return bufs[k].p != nullptr; }, dev));
+    for (int k = 0; k < N_BUFS; ++k) *bufs[k].slot = const_cast<void*>(dev[k]);
     ap.seed_base = f->seed_base;
     ap.nx = f->nx; ap.ny = f->ny; ap.ns = f->ns;
     ap.use_gradient_bg = f->use_gradient_bg;
@@ -1859,11 +1884,8 @@ static rt_status aov_impl(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc
                          }, plan));
     if (t) HIPCHK(rt_launch_aov_through(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, tp, plan.grid, plan.lds, stream));
     else HIPCHK(rt_launch_aov(s->spheres_only, s->tex_level, plan.lds_mode, sd, ap, plan.grid, plan.lds, stream));
-    if (!buffers_on_device)
-        for (const auto& o : outs) if (o.p) HIPCHK(hipMemcpyAsync(const_cast<void*>(o.p), *o.dev, o.bytes, hipMemcpyDeviceToHost, stream));
-    if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
-    mem.settled();
-    return RT_OK;
+    if (!buffers_on_device) RT_TRY(download_outputs(bufs, dev, stream));
+    return mem.finish(blocking || !buffers_on_device);
 }
 
 rt_status rt_render_aov(rt_scene* s, const rt_frame_desc* f, const rt_aov_desc* a, int buffers_on_device, void* stream_v, int blocking) {
@@ -1912,23 +1934,17 @@ static rt_status denoise_impl(const rt_denoise_desc* d, const rt_denoise_varianc
     const size_t ws_bytes = rt_denoise_workspace_bytes(d->nx, d->ny);
     const bool own_workspace = !buffers_on_device || !d->workspace;
     if (d->workspace && d->workspace_bytes < ws_bytes) return bad("workspace smaller than rt_denoise_workspace_bytes");
-    struct buffer : traced_ptr { bool input; };
     enum { COLOR = 0, ALBEDO, NORMAL, DEPTH, OUT, WORKSPACE, VARIANCE, VARIANCE_OUT, N_BUFS };
-    const buffer bufs[N_BUFS] = {{{d->color, 3 * pixels * sizeof(float), "color", 4}, true}, {{d->albedo, 3 * pixels * sizeof(float), "albedo", 4}, true},
-                                 {{d->normal, 3 * pixels * sizeof(float), "normal", 4}, true}, {{d->depth, pixels * sizeof(float), "depth", 4}, true},
-                                 {{d->out, 3 * pixels * sizeof(float), "out", 4}, false}, {{own_workspace ? nullptr : d->workspace, ws_bytes, "workspace", 16}, false},
-                                 {{vd ? vd->variance : nullptr, pixels * sizeof(float), "variance", 4}, true},
-                                 {{vd ? vd->variance_out : nullptr, pixels * sizeof(float), "variance_out", 4}, false}};
-    {   // out may be exactly color; nothing else may share a byte with out, with variance_out or with the workspace
-        auto overlap = [](const buffer& a, const buffer& b) {
-            const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
-            return a.p && b.p && pa < pb + b.bytes && pb < pa + a.bytes;
-        };
-        for (int k = 0; k < N_BUFS; ++k) {
-            if (k != OUT && overlap(bufs[k], bufs[OUT]) && !(k == COLOR && d->out == d->color)) return bad("out overlaps another buffer (it may only be exactly color)");
-            if (k != WORKSPACE && overlap(bufs[k], bufs[WORKSPACE])) return bad("the workspace overlaps another buffer");
-            if (k != VARIANCE_OUT && overlap(bufs[k], bufs[VARIANCE_OUT])) return bad("variance_out overlaps another buffer");
-        }
+    const size_t f1 = pixels * sizeof(float), f3 = 3 * f1;
+    const call_buffer bufs[N_BUFS] = {{{d->color, f3, "color", 4}, BUF_INPUT}, {{d->albedo, f3, "albedo", 4}, BUF_INPUT}, {{d->normal, f3, "normal", 4}, BUF_INPUT},
+                                      {{d->depth, f1, "depth", 4}, BUF_INPUT}, {{d->out, f3, "out", 4}, BUF_OUTPUT},
+                                      {{own_workspace ? nullptr : d->workspace, ws_bytes, "workspace", 16}, BUF_WORKSPACE},
+                                      {{vd ? vd->variance : nullptr, f1, "variance", 4}, BUF_INPUT}, {{vd ? vd->variance_out : nullptr, f1, "variance_out", 4}, BUF_OUTPUT}};
+    // out may be exactly color; nothing else may share a byte with out, with variance_out or with the workspace
+    for (int k = 0; k < N_BUFS; ++k) {
+        if (k != OUT && share_a_byte(bufs[k], bufs[OUT]) && !(k == COLOR && d->out == d->color)) return bad("out overlaps another buffer (it may only be exactly color)");
+        if (k != WORKSPACE && share_a_byte(bufs[k], bufs[WORKSPACE])) return bad("the workspace overlaps another buffer");
+        if (k != VARIANCE_OUT && share_a_byte(bufs[k], bufs[VARIANCE_OUT])) return bad("variance_out overlaps another buffer");
     }
     RT_TRY(use_device(g_device));
     if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, g_device, who_c));
@@ -1942,19 +1958,12 @@ static rt_status denoise_impl(const rt_denoise_desc* d, const rt_denoise_varianc
     call_memory mem;
     mem.guard(stream);
     char* ws = static_cast<char*>(d->workspace);
-    auto staged_image = [&](int k) { return k != WORKSPACE && bufs[k].p && !(k == OUT && d->out == d->color); };
-    if (own_workspace) {
-        size_t total = ws_bytes;
-        if (!buffers_on_device) for (int k = 0; k < N_BUFS; ++k) if (staged_image(k)) total += call_memory::rounded(bufs[k].bytes);
-        HIPCHK(mem.get((void**)&ws, total));
-        if (!buffers_on_device) {
-            char* at = ws + ws_bytes;
-            for (int k = 0; k < N_BUFS; ++k) if (staged_image(k)) dev[k] = call_memory::take(at, bufs[k].bytes);
-            if (d->out == d->color) dev[OUT] = dev[COLOR];
-        }
+    auto staged_image = [&](int k) { return !buffers_on_device && bufs[k].p && !(k == OUT && d->out == d->color); };
+    if (own_workspace) RT_TRY(stage_buffers(mem, bufs, staged_image, dev, ws_bytes, &ws));   // the workspace comes first
+    if (!buffers_on_device) {
+        if (d->out == d->color) dev[OUT] = dev[COLOR];
+        RT_TRY(upload_inputs(bufs, staged_image, dev, stream));
     }
-    if (!buffers_on_device)
-        for (int k = 0; k < N_BUFS; ++k) if (bufs[k].input && bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, stream));
     const size_t image = ws_bytes / 3;
     float4* x[2] = {reinterpret_cast<float4*>(ws), reinterpret_cast<float4*>(ws + image)};
     rt_denoise_params dp;
@@ -1988,11 +1997,8 @@ static rt_status denoise_impl(const rt_denoise_desc* d, const rt_denoise_varianc
         if (vd) HIPCHK(rt_launch_denoise_variance(normal_on, depth_on, dp.step <= max_staged, dp, dv, stream));
         else HIPCHK(rt_launch_denoise(normal_on, depth_on, color_on, dp.step <= max_staged, dp, stream));
     }
-    if (!buffers_on_device)
-        for (int k : {(int)OUT, (int)VARIANCE_OUT}) if (bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
-    if (blocking || own_workspace) HIPCHK(hipStreamSynchronize(stream));
-    mem.settled();
-    return RT_OK;
+    if (!buffers_on_device) RT_TRY(download_outputs(bufs, dev, stream));
+    return mem.finish(blocking || own_workspace);
 }
 
 rt_status rt_denoise(const rt_denoise_desc* d, int buffers_on_device, void* stream_v, int blocking) {
@@ -2024,22 +2030,15 @@ rt_status rt_upscale(const rt_upscale_desc* d, int buffers_on_device, void* stre
     if (d->demodulate && !(d->albedo_lo && d->albedo)) return bad("demodulate needs albedo_lo and albedo");
     const int lx = d->nx / d->factor, ly = d->ny / d->factor;
     const size_t pixels = (size_t)d->nx * d->ny, coarse = (size_t)lx * ly;
-    struct buffer : traced_ptr { bool input; };
     enum { COLOR_LO = 0, ALBEDO_LO, NORMAL_LO, DEPTH_LO, ALBEDO, NORMAL, DEPTH, OUT, WEIGHT_OUT, N_BUFS };
-    const buffer bufs[N_BUFS] = {{{d->color_lo, 3 * coarse * sizeof(float), "color_lo", 4}, true}, {{d->albedo_lo, 3 * coarse * sizeof(float), "albedo_lo", 4}, true},
-                                 {{d->normal_lo, 3 * coarse * sizeof(float), "normal_lo", 4}, true}, {{d->depth_lo, coarse * sizeof(float), "depth_lo", 4}, true},
-                                 {{d->albedo, 3 * pixels * sizeof(float), "albedo", 4}, true}, {{d->normal, 3 * pixels * sizeof(float), "normal", 4}, true},
-                                 {{d->depth, pixels * sizeof(float), "depth", 4}, true}, {{d->out, 3 * pixels * sizeof(float), "out", 4}, false},
-                                 {{d->weight_out, pixels * sizeof(float), "weight_out", 4}, false}};
-    {   // nothing may share a byte with out or with weight_out
-        auto overlap = [](const buffer& a, const buffer& b) {
-            const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
-            return a.p && b.p && pa < pb + b.bytes && pb < pa + a.bytes;
-        };
-        for (int k = 0; k < N_BUFS; ++k) {
-            if (k != OUT && overlap(bufs[k], bufs[OUT])) return bad("out overlaps another buffer");
-            if (k != WEIGHT_OUT && overlap(bufs[k], bufs[WEIGHT_OUT])) return bad("weight_out overlaps another buffer");
-        }
+    const size_t c1 = coarse * sizeof(float), c3 = 3 * c1, f1 = pixels * sizeof(float), f3 = 3 * f1;
+    const call_buffer bufs[N_BUFS] = {{{d->color_lo, c3, "color_lo", 4}, BUF_INPUT}, {{d->albedo_lo, c3, "albedo_lo", 4}, BUF_INPUT},
+                                      {{d->normal_lo, c3, "normal_lo", 4}, BUF_INPUT}, {{d->depth_lo, c1, "depth_lo", 4}, BUF_INPUT},
+                                      {{d->albedo, f3, "albedo", 4}, BUF_INPUT}, {{d->normal, f3, "normal", 4}, BUF_INPUT}, {{d->depth, f1, "depth", 4}, BUF_INPUT},
+                                      {{d->out, f3, "out", 4}, BUF_OUTPUT}, {{d->weight_out, f1, "weight_out", 4}, BUF_OUTPUT}};
+    for (int k = 0; k < N_BUFS; ++k) {   // nothing may share a byte with out or with weight_out
+        if (k != OUT && share_a_byte(bufs[k], bufs[OUT])) return bad("out overlaps another buffer");
+        if (k != WEIGHT_OUT && share_a_byte(bufs[k], bufs[WEIGHT_OUT])) return bad("weight_out overlaps another buffer");
     }
     RT_TRY(use_device(g_device));
     if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, g_device, who));
@@ -2052,13 +2051,9 @@ rt_status rt_upscale(const rt_upscale_desc* d, int buffers_on_device, void* stre
     call_memory mem;
     mem.guard(stream);
     if (!buffers_on_device) {
-        size_t total = 0;
-        for (const buffer& b : bufs) if (b.p) total += call_memory::rounded(b.bytes);
-        char* at = nullptr;
-        HIPCHK(mem.get((void**)&at, total));
-        for (int k = 0; k < N_BUFS; ++k) if (bufs[k].p) dev[k] = call_memory::take(at, bufs[k].bytes);
-        for (int k = 0; k < N_BUFS; ++k)
-            if (bufs[k].input && bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, stream));
+        auto given = [&](int k) { return bufs[k].p != nullptr; };
+        RT_TRY(stage_buffers(mem, bufs, given, dev));
+        RT_TRY(upload_inputs(bufs, given, dev, stream));
     }
     auto in = [&](int k, bool used) { return used ? static_cast<const float*>(dev[k]) : nullptr; };
     rt_upscale_params up;
@@ -2075,11 +2070,8 @@ rt_status rt_upscale(const rt_upscale_desc* d, int buffers_on_device, void* stre
     up.sigma_depth = d->sigma_depth; up.min_weight = d->min_weight;
     // staged or direct: auto is staged
     HIPCHK(rt_launch_upscale(normal_on, depth_on, g_opt.upscale_lds != 0, up, stream));
-    if (!buffers_on_device)
-        for (int k : {(int)OUT, (int)WEIGHT_OUT}) if (bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
-    if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
-    mem.settled();
-    return RT_OK;
+    if (!buffers_on_device) RT_TRY(download_outputs(bufs, dev, stream));
+    return mem.finish(blocking || !buffers_on_device);
 }
 
 // ---- rt_reproject (include/rt_abi.h)
@@ -2163,7 +2155,6 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
     memset(&rp, 0, sizeof(rp));
     if (rt_reproject_matrix(&d->prev, rp.m) != RT_OK) return bad("prev: the camera's basis is singular or its inverse is not finite");
     const size_t pixels = (size_t)d->nx * d->ny;
-    struct buffer : traced_ptr { bool input; };
     enum { COLOR = 0, DEPTH, ALPHA, NORMAL, PRIM, HISTORY, HISTORY_LEN, PREV_DEPTH, PREV_ALPHA, PREV_NORMAL, PREV_PRIM, OUT, OUT_LEN, MOTION,
            SPHERES, PREV_SPHERES, MEDIA,            // the three tables: rt_reproject_moving and up, inputs behind the outputs
            INSTANCES, PREV_INSTANCES, INST, PREV_INST,   // rt_reproject_instances and up
@@ -2171,26 +2162,23 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
     const size_t f1 = pixels * sizeof(float), f3 = 3 * f1;
     const size_t sphere_bytes = m ? (size_t)m->n_spheres * sizeof(rt_sphere) : 0, medium_bytes = m ? (size_t)m->n_media * sizeof(rt_medium) : 0;
     const size_t instance_bytes = im ? (size_t)im->n_instances * sizeof(rt_instance) : 0, quad_bytes = qm ? (size_t)qm->n_quads * sizeof(rt_quad) : 0;
-    const buffer bufs[N_BUFS] = {{{d->color, f3, "color", 4}, true}, {{d->depth, f1, "depth", 4}, true}, {{d->alpha, f1, "alpha", 4}, true},
-                                 {{d->normal, f3, "normal", 4}, true}, {{d->prim, f1, "prim", 4}, true}, {{d->history, f3, "history", 4}, true},
-                                 {{d->history_len, f1, "history_len", 4}, true}, {{d->prev_depth, f1, "prev_depth", 4}, true},
-                                 {{d->prev_alpha, f1, "prev_alpha", 4}, true}, {{d->prev_normal, f3, "prev_normal", 4}, true},
-                                 {{d->prev_prim, f1, "prev_prim", 4}, true}, {{d->out, f3, "out", 4}, false}, {{d->out_len, f1, "out_len", 4}, false},
-                                 {{d->motion, 2 * f1, "motion", 4}, false},
-                                 {{sphere_bytes ? m->spheres : nullptr, sphere_bytes, "spheres", 4}, true},
-                                 {{sphere_bytes ? m->prev_spheres : nullptr, sphere_bytes, "prev_spheres", 4}, true},
-                                 {{medium_bytes ? m->media : nullptr, medium_bytes, "media", 4}, true},
-                                 {{instance_bytes ? im->instances : nullptr, instance_bytes, "instances", 4}, true},
-                                 {{instance_bytes ? im->prev_instances : nullptr, instance_bytes, "prev_instances", 4}, true},
-                                 {{im ? im->inst : nullptr, f1, "inst", 4}, true}, {{im ? im->prev_inst : nullptr, f1, "prev_inst", 4}, true},
-                                 {{quad_bytes ? qm->quads : nullptr, quad_bytes, "quads", 4}, true},
-                                 {{quad_bytes ? qm->prev_quads : nullptr, quad_bytes, "prev_quads", 4}, true}};
+    const call_buffer bufs[N_BUFS] = {{{d->color, f3, "color", 4}, BUF_INPUT}, {{d->depth, f1, "depth", 4}, BUF_INPUT}, {{d->alpha, f1, "alpha", 4}, BUF_INPUT},
+                                      {{d->normal, f3, "normal", 4}, BUF_INPUT}, {{d->prim, f1, "prim", 4}, BUF_INPUT}, {{d->history, f3, "history", 4}, BUF_INPUT},
+                                      {{d->history_len, f1, "history_len", 4}, BUF_INPUT}, {{d->prev_depth, f1, "prev_depth", 4}, BUF_INPUT},
+                                      {{d->prev_alpha, f1, "prev_alpha", 4}, BUF_INPUT}, {{d->prev_normal, f3, "prev_normal", 4}, BUF_INPUT},
+                                      {{d->prev_prim, f1, "prev_prim", 4}, BUF_INPUT}, {{d->out, f3, "out", 4}, BUF_OUTPUT}, {{d->out_len, f1, "out_len", 4}, BUF_OUTPUT},
+                                      {{d->motion, 2 * f1, "motion", 4}, BUF_OUTPUT},
+                                      {{sphere_bytes ? m->spheres : nullptr, sphere_bytes, "spheres", 4}, BUF_INPUT},
+                                      {{sphere_bytes ? m->prev_spheres : nullptr, sphere_bytes, "prev_spheres", 4}, BUF_INPUT},
+                                      {{medium_bytes ? m->media : nullptr, medium_bytes, "media", 4}, BUF_INPUT},
+                                      {{instance_bytes ? im->instances : nullptr, instance_bytes, "instances", 4}, BUF_INPUT},
+                                      {{instance_bytes ? im->prev_instances : nullptr, instance_bytes, "prev_instances", 4}, BUF_INPUT},
+                                      {{im ? im->inst : nullptr, f1, "inst", 4}, BUF_INPUT}, {{im ? im->prev_inst : nullptr, f1, "prev_inst", 4}, BUF_INPUT},
+                                      {{quad_bytes ? qm->quads : nullptr, quad_bytes, "quads", 4}, BUF_INPUT},
+                                      {{quad_bytes ? qm->prev_quads : nullptr, quad_bytes, "prev_quads", 4}, BUF_INPUT}};
     for (int o = OUT; o <= MOTION; ++o)     // an output shares no byte with any other buffer
-        for (int k = 0; k < N_BUFS; ++k) {
-            const uintptr_t pa = (uintptr_t)bufs[o].p, pb = (uintptr_t)bufs[k].p;
-            if (k != o && bufs[o].p && bufs[k].p && pa < pb + bufs[k].bytes && pb < pa + bufs[o].bytes)
-                return bad((std::string(bufs[o].what) + " overlaps " + bufs[k].what).c_str());
-        }
+        for (int k = 0; k < N_BUFS; ++k)
+            if (k != o && share_a_byte(bufs[o], bufs[k])) return bad((std::string(bufs[o].what) + " overlaps " + bufs[k].what).c_str());
     RT_TRY(use_device(g_device));
     if (buffers_on_device) RT_TRY(check_trace_ptrs(bufs, g_device, who));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
@@ -2209,13 +2197,8 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
     call_memory mem;
     mem.guard(stream);
     if (!buffers_on_device) {   // host buffers: their device images in one allocation of this call's own
-        size_t total = 0;
-        for (int k = 0; k < N_BUFS; ++k) if (used(k)) total += call_memory::rounded(bufs[k].bytes);
-        char* at = nullptr;
-        HIPCHK(mem.get((void**)&at, total));
-        for (int k = 0; k < N_BUFS; ++k) if (used(k)) dev[k] = call_memory::take(at, bufs[k].bytes);
-        for (int k = 0; k < N_BUFS; ++k)
-            if (used(k) && bufs[k].input) HIPCHK(hipMemcpyAsync(const_cast<void*>(dev[k]), bufs[k].p, bufs[k].bytes, hipMemcpyHostToDevice, stream));
+        RT_TRY(stage_buffers(mem, bufs, used, dev));
+        RT_TRY(upload_inputs(bufs, used, dev, stream));
     }
     auto fptr = [&](int k) { return static_cast<const float*>(dev[k]); };
     auto iptr = [&](int k) { return static_cast<const int32_t*>(dev[k]); };
@@ -2256,11 +2239,8 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
     } else {
         HIPCHK(rt_launch_reproject(normals_on, ids_on, motion_on, rp, stream));
     }
-    if (!buffers_on_device)
-        for (int k = OUT; k <= MOTION; ++k) if (bufs[k].p) HIPCHK(hipMemcpyAsync(const_cast<void*>(bufs[k].p), dev[k], bufs[k].bytes, hipMemcpyDeviceToHost, stream));
-    if (blocking || !buffers_on_device) HIPCHK(hipStreamSynchronize(stream));
-    mem.settled();
-    return RT_OK;
+    if (!buffers_on_device) RT_TRY(download_outputs(bufs, dev, stream));
+    return mem.finish(blocking || !buffers_on_device);
 }
 }  // namespace
 

@@ -433,8 +433,8 @@ hipError_t rt_launch_adaptive(const rt_adaptive_params& p, hipStream_t st);
 
 // rt_denoise_variance (rt_kernel_denoise.hip): the variance-guided mode of the filter.  The fourth float of the colour record
 // carries the pixel's variance v_k instead of the colour sum (only the colour factor, which is off in this mode, reads that
-// sum), so a tap still costs two 16-byte reads and the workspace is rt_denoise's.  A second kernel argument beside
-// rt_denoise_params, which the existing instantiations keep as it is.
+// sum), so a tap still costs two 16-byte reads and the workspace is rt_denoise's.  Its kernels are entry points of rt_denoise's one
+// iteration body; these arguments are a second block that only they take, so rt_denoise's own kernels reserve nothing for it.
 struct rt_denoise_variance_params {
     const float* variance;    // pack: ny * nx, what rt_render_variance writes
     float* variance_out;      // last iteration: ny * nx, the filtered variance; null = not written

@@ -3,6 +3,7 @@
 // One kernel, the denoiser's workgroup: 256 threads = four waves on 8x8 output pixels each = a 16x16 tile of the output, one
 // output pixel per lane in registers.  A pixel reads its own guides (planar, once) and nine coarse taps; a coarse pixel is two
 // 16-byte records, colour (x.rgb, the demodulating divisions done) and guide (N.xyz, Z; zeros where a factor is off).
+// The tile, the records' contents, the two factors and the remodulation are the denoiser's definitions (rt_filter.h).
 // Specialised on which of the two factors are on and on how the taps are fetched:
 //   staged  the window of coarse pixels the tile's taps reach -- at most 11 x 11 (rt_device.h) -- is prepared once per
 //           workgroup into LDS, and the nine taps of every pixel are LDS reads;
@@ -16,27 +17,22 @@
 // (its column is within one of a column I = i / f of the tile, and the window starts at x0 / f - 1), so no slot is read that
 // was not written.  No address depends on pixel data.
 #include "rt_device.h"
+#include "rt_filter.h"
 #include "rt_launch.h"
 
 namespace {
 
-constexpr int TILE = RT_DENOISE_TILE;
+using namespace rt_filter;
 constexpr int WIN = RT_UPSCALE_WINDOW;
-constexpr float ALBEDO_FLOOR = 0.0009765625f;   // 2^-10
 
 // "Prepare" of the contract for coarse pixel q: x(q) and, where a factor is on, its guides
+// (the block by value and the guides fetched first: with the direct taps this order and form run 4 % faster than the colour
+// first through a reference; no operation depends on the order; profiles/filter_shared_mi355x.jsonl)
 template <bool NRM, bool DEP>
-__device__ __forceinline__ void coarse_record(const rt_upscale_params& up, size_t q, float4& x, float4& g) {
-    float r = up.color_lo[3 * q], gr = up.color_lo[3 * q + 1], b = up.color_lo[3 * q + 2];
-    if (up.demodulate) {
-        r = r / fmaxf(up.albedo_lo[3 * q], ALBEDO_FLOOR);
-        gr = gr / fmaxf(up.albedo_lo[3 * q + 1], ALBEDO_FLOOR);
-        b = b / fmaxf(up.albedo_lo[3 * q + 2], ALBEDO_FLOOR);
-    }
-    x = make_float4(r, gr, b, 0.f);
-    g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (NRM) { g.x = up.normal_lo[3 * q]; g.y = up.normal_lo[3 * q + 1]; g.z = up.normal_lo[3 * q + 2]; }
-    if (DEP) g.w = up.depth_lo[q];
+__device__ __forceinline__ void coarse_record(const rt_upscale_params up, size_t q, float4& x, float4& g) {
+    g = guide_record(NRM, DEP, up.normal_lo, up.depth_lo, q);
+    const float3 c = demodulated(up.color_lo, up.albedo_lo, up.demodulate, q);
+    x = make_float4(c.x, c.y, c.z, 0.f);
 }
 
 // "Position" of the contract: B[-1], B[0], B[+1] for the offset r = i - I f of an output coordinate in its coarse pixel
@@ -52,15 +48,12 @@ template <bool NRM, bool DEP, bool STAGED>
 __global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_upscale_kernel(rt_upscale_params up) {
     __shared__ float4 lds[STAGED ? 2 * WIN * WIN : 1];
     constexpr bool GUIDE = NRM || DEP;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int nx = up.nx, ny = up.ny, lx = up.lx, ly = up.ly, f = up.factor;
-    const int by = (int)(blockIdx.x / (unsigned)up.tiles_x), bx = (int)(blockIdx.x - (unsigned)by * (unsigned)up.tiles_x);
-    const int x0 = bx * TILE, y0 = by * TILE;
-    // a wave on one 8x8 tile, as in the other kernels
-    // (coordinates are unsigned: one below 0 wraps and compares as out of the image)
-    const unsigned i = (unsigned)x0 + (wave & 1) * 8 + (lane & 7), j = (unsigned)y0 + (wave >> 1) * 8 + (lane >> 3);
+    const tile_pixel tile = tile_mapping(up.tiles_x);
+    const unsigned i = tile.i, j = tile.j;
 
-    const unsigned ox = (unsigned)x0 / (unsigned)f - 1u, oy = (unsigned)y0 / (unsigned)f - 1u;   // coarse coordinates of LDS slot (0, 0)
+    const unsigned ox = (unsigned)tile.x0 / (unsigned)f - 1u, oy = (unsigned)tile.y0 / (unsigned)f - 1u;   // coarse coordinates of LDS slot (0, 0)
     const float4* lc = lds;
     const float4* lg = lds + WIN * WIN;
     if (STAGED) {
@@ -79,9 +72,7 @@ __global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_upscale_kernel(rt_upsca
     if (i >= (unsigned)nx || j >= (unsigned)ny) return;
 
     const size_t p = (size_t)j * nx + i;
-    float4 gp = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (NRM) { gp.x = up.normal[3 * p]; gp.y = up.normal[3 * p + 1]; gp.z = up.normal[3 * p + 2]; }
-    if (DEP) gp.w = up.depth[p];
+    const float4 gp = guide_record(NRM, DEP, up.normal, up.depth, p);
 
     const unsigned I = i / (unsigned)f, J = j / (unsigned)f;
     float Bx[3], By[3];
@@ -107,18 +98,8 @@ __global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_upscale_kernel(rt_upsca
             }
             const float g = By[dy + 1] * Bx[dx + 1];
             float w = g;
-            if (NRM) {
-                float d = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
-                d = fmaxf(d, 0.f);
-                for (int m = 0; m < up.normal_sharpness; ++m) d = d * d;
-                w = w * d;
-            }
-            if (DEP) {
-                const float den = up.sigma_depth * fmaxf(gp.w, gq.w) + 1e-20f;
-                const float r = fabsf(gp.w - gq.w) / den;
-                const float t = fmaxf(1.f - r, 0.f);
-                w = w * (t * t);
-            }
+            if (NRM) w = w * normal_factor(gp, gq, up.normal_sharpness);
+            if (DEP) w = w * depth_factor(gp, gq, up.sigma_depth);
             W0 = W0 + g;
             S0r = S0r + g * xq.x;
             S0g = S0g + g * xq.y;
@@ -133,11 +114,7 @@ __global__ __launch_bounds__(RT_DENOISE_THREADS) void rt_upscale_kernel(rt_upsca
     const bool guided = W >= up.min_weight * W0 && W > 0.f;
     const float den = guided ? W : W0;
     float r = (guided ? Sr : S0r) / den, g = (guided ? Sg : S0g) / den, b = (guided ? Sb : S0b) / den;
-    if (up.demodulate) {
-        r = r * fmaxf(up.albedo[3 * p], ALBEDO_FLOOR);
-        g = g * fmaxf(up.albedo[3 * p + 1], ALBEDO_FLOOR);
-        b = b * fmaxf(up.albedo[3 * p + 2], ALBEDO_FLOOR);
-    }
+    remodulate(up.albedo, up.demodulate, p, r, g, b);
     up.out[3 * p] = r;
     up.out[3 * p + 1] = g;
     up.out[3 * p + 2] = b;

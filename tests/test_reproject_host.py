@@ -160,7 +160,7 @@ def test_reproject_checks_name_what_failed(art):
         "singular prev": _desc(art, prev=singular),
         "out is color": _desc(art, out=FAKE), "out inside history": _desc(art, out=FAKE * 6 + 64), "out_len is depth": _desc(art, out_len=FAKE * 2),
         "motion overlaps out": _desc(art, motion=FAKE * 4 + 128), "motion is alpha": _desc(art, motion=FAKE * 3),
-        "out_len inside out": _desc(art, out_len=FAKE * 4 + 4),
+        "out_len inside out": _desc(art, out_len=FAKE * 4 + 4), "out ends in history": _desc(art, out=FAKE * 6 - 64),
     }
     texts = {}
     for name, d in cases.items():
@@ -181,6 +181,7 @@ def test_reproject_checks_name_what_failed(art):
     assert len({texts[k] for k in distinct}) == len(distinct), texts
     for name in ("out is color", "out inside history", "out_len is depth", "motion overlaps out", "motion is alpha", "out_len inside out"):
         assert "overlaps" in texts[name], (name, texts[name])
+    assert texts["out ends in history"] == texts["out inside history"]   # (an output that starts in front of the buffer it runs into)
     # what passes: with and without a history, every guide, motion, the ends of every range, a non-finite current camera
     wild = sg.make_camera(*CAMERAS[1], 0.0, 0.0)
     wild.origin[0] = nan
