@@ -857,13 +857,20 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             raise ValueError("spheres needs prev_spheres")
         if prim is None or prev_prim is None:
             raise ValueError("spheres / instances: prim and prev_prim are required to follow what moved")
-        # (each structure keeps what its pointers point to: a numpy table is referenced until the C call has returned)
+        def table_pair(name, current, previous, dtype, dtype_name):
+            """The record tables of both frames: one dtype, equal lengths.  -> (count, address, what keeps it alive, the previous
+            table's address, what keeps that alive); each structure keeps what its pointers point to, so that a numpy table is
+            referenced until the C call has returned."""
+            n, address, keep = bufs.table(current, name, dtype, dtype_name)
+            n_prev, prev_address, prev_keep = bufs.table(previous, "prev_" + name, dtype, dtype_name)
+            if n_prev != n:
+                raise ValueError(f"prev_{name}: {n_prev} records, {name} has {n}")
+            return n, address, keep, prev_address, prev_keep
+
         md = RtReprojectMotionDesc()
         if spheres is not None:
-            md.n_spheres, md.spheres, md.keep_spheres = bufs.table(spheres, "spheres", SPHERE_DTYPE, "SPHERE_DTYPE")
-            n_prev, md.prev_spheres, md.keep_prev_spheres = bufs.table(prev_spheres, "prev_spheres", SPHERE_DTYPE, "SPHERE_DTYPE")
-            if n_prev != md.n_spheres:
-                raise ValueError(f"prev_spheres: {n_prev} records, spheres has {md.n_spheres}")
+            md.n_spheres, md.spheres, md.keep_spheres, md.prev_spheres, md.keep_prev_spheres = table_pair(
+                "spheres", spheres, prev_spheres, SPHERE_DTYPE, "SPHERE_DTYPE")
         if media is not None:
             md.n_media, md.media, md.keep_media = bufs.table(media, "media", MEDIUM_DTYPE, "MEDIUM_DTYPE")
         if md.n_spheres >= 1 << 28 or md.n_media >= 1 << 28:
@@ -880,10 +887,8 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             if (prev_inst is None) != (history is None):
                 raise ValueError("instances: prev_inst is required exactly when history is given")
             imd = RtReprojectInstanceDesc()
-            imd.n_instances, imd.instances, imd.keep_instances = bufs.table(instances, "instances", INSTANCE_DTYPE, "INSTANCE_DTYPE")
-            n_prev, imd.prev_instances, imd.keep_prev_instances = bufs.table(prev_instances, "prev_instances", INSTANCE_DTYPE, "INSTANCE_DTYPE")
-            if n_prev != imd.n_instances:
-                raise ValueError(f"prev_instances: {n_prev} records, instances has {imd.n_instances}")
+            imd.n_instances, imd.instances, imd.keep_instances, imd.prev_instances, imd.keep_prev_instances = table_pair(
+                "instances", instances, prev_instances, INSTANCE_DTYPE, "INSTANCE_DTYPE")
             if imd.n_instances >= 1 << 28:
                 raise ValueError("instances: 2^28 records or more")
         if quads is not None:
@@ -896,10 +901,8 @@ def reproject(color, depth, alpha, cur: RtCamera, prev: RtCamera, normal=None, p
             if imd is None:
                 imd = RtReprojectInstanceDesc()
             qmd = RtReprojectQuadDesc()
-            qmd.n_quads, qmd.quads, qmd.keep_quads = bufs.table(quads, "quads", QUAD_DTYPE, "QUAD_DTYPE")
-            n_prev, qmd.prev_quads, qmd.keep_prev_quads = bufs.table(prev_quads, "prev_quads", QUAD_DTYPE, "QUAD_DTYPE")
-            if n_prev != qmd.n_quads:
-                raise ValueError(f"prev_quads: {n_prev} records, quads has {qmd.n_quads}")
+            qmd.n_quads, qmd.quads, qmd.keep_quads, qmd.prev_quads, qmd.keep_prev_quads = table_pair(
+                "quads", quads, prev_quads, QUAD_DTYPE, "QUAD_DTYPE")
             if qmd.n_quads >= 1 << 28:
                 raise ValueError("quads: 2^28 records or more")
 

@@ -2131,26 +2131,26 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
     } else if (d->history_len || d->prev_depth || d->prev_alpha) {
         return bad("history_len, prev_depth and prev_alpha need history");
     }
+    // one record table of both frames: the count's range, then both tables where it is positive.  `counts` is the subject of the
+    // range messages and `other` a second count they cover (the sphere tables' are shared with n_media)
+    auto check_table = [&](const std::string& counts, const std::string& name, int n, int other, const void* cur, const void* prev) -> rt_status {
+        if (n < 0 || other < 0) return bad((counts + " must not be negative").c_str());
+        if (n >= (1 << 28) || other >= (1 << 28)) return bad((counts + " must be below 2^28").c_str());
+        if (n > 0 && (!cur || !prev)) return bad(("n_" + name + " > 0 needs " + name + " and prev_" + name).c_str());
+        return RT_OK;
+    };
     if (m) {
         if (!d->prim || !d->prev_prim) return bad("prim and prev_prim are required: they say which sphere a pixel shows");
-        if (m->n_spheres < 0 || m->n_media < 0) return bad("n_spheres and n_media must not be negative");
-        if (m->n_spheres >= (1 << 28) || m->n_media >= (1 << 28)) return bad("n_spheres and n_media must be below 2^28");
-        if (m->n_spheres > 0 && (!m->spheres || !m->prev_spheres)) return bad("n_spheres > 0 needs spheres and prev_spheres");
+        RT_TRY(check_table("n_spheres and n_media", "spheres", m->n_spheres, m->n_media, m->spheres, m->prev_spheres));
         if (m->n_media > 0 && !m->media) return bad("n_media > 0 needs media");
         if (!std::isfinite(m->time) || !std::isfinite(m->prev_time)) return bad("time and prev_time must be finite");
     }
     if (im) {
         if (!im->inst) return bad("null inst: it says which instance a pixel shows");
         if (d->history ? !im->prev_inst : im->prev_inst != nullptr) return bad("prev_inst must be non-null exactly when history is");
-        if (im->n_instances < 0) return bad("n_instances must not be negative");
-        if (im->n_instances >= (1 << 28)) return bad("n_instances must be below 2^28");
-        if (im->n_instances > 0 && (!im->instances || !im->prev_instances)) return bad("n_instances > 0 needs instances and prev_instances");
+        RT_TRY(check_table("n_instances", "instances", im->n_instances, 0, im->instances, im->prev_instances));
     }
-    if (qm) {
-        if (qm->n_quads < 0) return bad("n_quads must not be negative");
-        if (qm->n_quads >= (1 << 28)) return bad("n_quads must be below 2^28");
-        if (qm->n_quads > 0 && (!qm->quads || !qm->prev_quads)) return bad("n_quads > 0 needs quads and prev_quads");
-    }
+    if (qm) RT_TRY(check_table("n_quads", "quads", qm->n_quads, 0, qm->quads, qm->prev_quads));
     rt_reproject_params rp;
     memset(&rp, 0, sizeof(rp));
     if (rt_reproject_matrix(&d->prev, rp.m) != RT_OK) return bad("prev: the camera's basis is singular or its inverse is not finite");
@@ -2214,31 +2214,19 @@ rt_status reproject_impl(const rt_reproject_desc* d, const rt_reproject_motion_d
         rp.prev_origin[c] = d->prev.origin[c];
     }
     rp.alpha_min = d->alpha_min; rp.depth_tol = d->depth_tol; rp.normal_min = d->normal_min; rp.max_history = d->max_history;
-    if (m) {
-        rt_reproject_follow_quad_params qp;
-        memset(&qp, 0, sizeof(qp));
-        rt_reproject_follow_instance_params& ip = qp;
-        rt_reproject_follow_params& fp = ip;
-        fp.spheres = static_cast<const rt_sphere*>(dev[SPHERES]); fp.prev_spheres = static_cast<const rt_sphere*>(dev[PREV_SPHERES]);
-        fp.media = static_cast<const rt_medium*>(dev[MEDIA]);
-        fp.n_spheres = m->n_spheres; fp.n_media = m->n_media; fp.time = m->time; fp.prev_time = m->prev_time;
-        if (im) {
-            ip.instances = static_cast<const rt_instance*>(dev[INSTANCES]); ip.prev_instances = static_cast<const rt_instance*>(dev[PREV_INSTANCES]);
-            ip.inst = iptr(INST); ip.prev_inst = iptr(PREV_INST);
-            ip.n_instances = im->n_instances;
-            if (qm) {
-                qp.quads = static_cast<const rt_quad*>(dev[QUADS]); qp.prev_quads = static_cast<const rt_quad*>(dev[PREV_QUADS]);
-                qp.n_quads = qm->n_quads;
-                HIPCHK(rt_launch_reproject_quads(normals_on, motion_on, rp, qp, stream));
-            } else {
-                HIPCHK(rt_launch_reproject_instances(normals_on, motion_on, rp, ip, stream));
-            }
-        } else {
-            HIPCHK(rt_launch_reproject_moving(normals_on, motion_on, rp, fp, stream));
-        }
-    } else {
-        HIPCHK(rt_launch_reproject(normals_on, ids_on, motion_on, rp, stream));
-    }
+    // the follow step's tables, filled as far as the entry's descriptions reach (dev[] and the byte counts are null and 0 beyond)
+    rt_reproject_follow_quad_params qp;
+    memset(&qp, 0, sizeof(qp));
+    qp.spheres = static_cast<const rt_sphere*>(dev[SPHERES]); qp.prev_spheres = static_cast<const rt_sphere*>(dev[PREV_SPHERES]);
+    qp.media = static_cast<const rt_medium*>(dev[MEDIA]);
+    if (m) { qp.n_spheres = m->n_spheres; qp.n_media = m->n_media; qp.time = m->time; qp.prev_time = m->prev_time; }
+    qp.instances = static_cast<const rt_instance*>(dev[INSTANCES]); qp.prev_instances = static_cast<const rt_instance*>(dev[PREV_INSTANCES]);
+    qp.inst = iptr(INST); qp.prev_inst = iptr(PREV_INST);
+    if (im) qp.n_instances = im->n_instances;
+    qp.quads = static_cast<const rt_quad*>(dev[QUADS]); qp.prev_quads = static_cast<const rt_quad*>(dev[PREV_QUADS]);
+    if (qm) qp.n_quads = qm->n_quads;
+    const rt_reproject_form form = qm ? RT_REPROJECT_QUADS : im ? RT_REPROJECT_INSTANCES : m ? RT_REPROJECT_SPHERES : RT_REPROJECT_STATIC;
+    HIPCHK(rt_launch_reproject(form, normals_on, ids_on, motion_on, rp, qp, stream));
     if (!buffers_on_device) RT_TRY(download_outputs(bufs, dev, stream));
     return mem.finish(blocking || !buffers_on_device);
 }

@@ -508,10 +508,10 @@ struct rt_reproject_params {
     float m[9];                // rt_reproject_matrix of the previous camera
     float alpha_min, depth_tol, normal_min, max_history;
 };
-hipError_t rt_launch_reproject(bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp, hipStream_t st);
-// rt_reproject_moving: a second kernel argument beside rt_reproject_params, which rt_reproject's kernels keep as it is -- the
-// sphere records of both frames and the media, whose boundaries say which sphere a fog ball follows.  The id test is always
-// on (prim and prev_prim are required).  A table is null exactly when its count is 0.
+// The follow step's tables, the kernel's optional second argument: each form's block extends the one before it, and the kernel of a
+// form takes exactly its own block (rt_reproject's kernels take none).  A table is null exactly when its count is 0.
+// Spheres (rt_reproject_moving): the sphere records of both frames and the media, whose boundaries say which sphere or instance a
+// fog ball follows.
 struct rt_reproject_follow_params {
     const rt_sphere* spheres;        // n_spheres records of the current frame
     const rt_sphere* prev_spheres;   // ... and of the previous frame, same order
@@ -519,9 +519,8 @@ struct rt_reproject_follow_params {
     int32_t n_spheres, n_media;
     float time, prev_time;           // c = c0 + time * vel
 };
-hipError_t rt_launch_reproject_moving(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_params& fp, hipStream_t st);
-// rt_reproject_instances: the third form of that argument -- the sphere tables (n_spheres may be 0) and, beside them, the instance
-// records of both frames and the two inst planes of rt_render_aov.  prev_inst is null exactly when rp.history is.
+// Instances (rt_reproject_instances): beside the sphere tables (n_spheres may be 0) the instance records of both frames and the two
+// inst planes of rt_render_aov.  prev_inst is null exactly when rp.history is.
 struct rt_reproject_follow_instance_params : rt_reproject_follow_params {
     const rt_instance* instances;        // n_instances records of the current frame
     const rt_instance* prev_instances;   // ... and of the previous frame, same order
@@ -529,14 +528,17 @@ struct rt_reproject_follow_instance_params : rt_reproject_follow_params {
     const int32_t* prev_inst;            // ny * nx, previous
     int32_t n_instances, pad;
 };
-hipError_t rt_launch_reproject_instances(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_instance_params& ip, hipStream_t st);
-// rt_reproject_quads: the fourth form -- the instance form (n_instances may be 0) and, beside it, the quad records of both frames
+// Quads (rt_reproject_quads): beside the instance form (n_instances may be 0) the quad records of both frames.
 struct rt_reproject_follow_quad_params : rt_reproject_follow_instance_params {
     const rt_quad* quads;        // n_quads records of the current frame
     const rt_quad* prev_quads;   // ... and of the previous frame, same order
     int32_t n_quads, pad_q;
 };
-hipError_t rt_launch_reproject_quads(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_quad_params& qp, hipStream_t st);
+// One launcher for the four entries.  `qp` is the full block, filled as far as `form` reaches.  ids_on is the static form's; the
+// follow forms always test ids (their entries require prim and prev_prim).
+enum rt_reproject_form { RT_REPROJECT_STATIC, RT_REPROJECT_SPHERES, RT_REPROJECT_INSTANCES, RT_REPROJECT_QUADS };
+hipError_t rt_launch_reproject(rt_reproject_form form, bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp,
+                               const rt_reproject_follow_quad_params& qp, hipStream_t st);
 
 // rt_scene_update_spheres, _instances and _quads (rt_kernel_refit.hip; include/rt_abi.h): the replaced
 // records, their leaves' boxes in every array that holds them, the per-64-leaf unions, the scene's coordinate bound and every

@@ -1,50 +1,50 @@
-// rt_kernel_reproject.hip -- rt_reproject: the current frame blended into the reprojected history of the previous frame, as
-// include/rt_abi.h ("temporal reprojection") spells it out, gfx950.
+// rt_kernel_reproject.hip -- the current frame blended into the reprojected history of the previous frame, as include/rt_abi.h
+// ("temporal reprojection" and its three extensions) spells it out, gfx950.  The arithmetic is the contract's, statement by
+// statement (-ffp-contract=off: no FMA is formed).
 //
-// One kernel, one lane per pixel, workgroups of 256 threads on 16x16 pixel tiles.  Inside a tile the lanes run row-major
+// One kernel template, one lane per pixel, workgroups of 256 threads on 16x16 pixel tiles.  Inside a tile the lanes run row-major
 // (lane & 15 across, four rows per wave): every planar access of a wave -- the pixel's own colour, depth, alpha, normal and
-// id, and the three outputs -- is then four runs of 16 consecutive pixels (64 B of a scalar plane, 192 B of an rgb plane),
+// ids, and the three outputs -- is then four runs of 16 consecutive pixels (64 B of a scalar plane, 192 B of an rgb plane),
 // and since a reprojection is locally close to a translation the four taps of those lanes fall on neighbouring runs of at
 // most six rows of the previous frame, which the next wave of the tile (four rows further up) mostly shares through L1/L2.
 // There is no LDS staging: where a tile's taps land is data (the depth), so a window cannot be fetched before it is known, and
-// the footprint of a tile is already about one tile of each plane.  Per pixel it reads up to 36 B of the current frame and
-// four taps of up to 40 B, and writes up to 24 B; what it waits for is the latency of two dependent memory phases (the pixel's
-// own data, then the taps), which is why the taps' loads are all issued before the first of them is looked at.
-// Specialised on (normal test, id test, motion output) so that a guide that is off costs neither loads nor registers.
+// the footprint of a tile is already about one tile of each plane.
 //
-// rt_reproject_moving ("temporal reprojection that follows moved spheres") launches the same kernel with its
-// tables as a second argument: a surface pixel on a sphere whose record changed is carried back to where that surface point was
-// before it is projected.  That is a third dependent memory phase between the two -- the pixel's prim, then at most one medium
-// record and, issued together, the two 32-byte sphere records -- whose lines the lanes of one sphere share; the instantiations
-// without the argument are, instruction for instruction, what they were before it existed.
+// Forms.  The kernel is specialised on (normal test, id test, motion output), so that a guide that is off costs neither loads
+// nor registers, and on its optional second argument, the tables of the follow step (rt_device.h):
+//   static     no second argument: rt_reproject, eight instantiations.  Steps 1 to 4 and nothing else.
+//   spheres    rt_reproject_follow_params: a surface pixel on a sphere, or in a medium a sphere bounds, whose record changed is
+//              carried back to where that surface point was.
+//   instances  ..._follow_instance_params: in front of that, a pixel on an instance (inst[p], or the boundary of its medium) whose
+//              record changed has its point and its normal taken through the current record's world -> object map and the
+//              previous record's object -> world map; a tap must also show the pixel's inst (4.19).
+//   quads      ..._follow_quad_params: in front of both, a pixel on a quad of the tables (a face of a box is one) whose Q, u or v
+//              changed goes into object space by its instance record, if it has one, onto the previous record's plane by its
+//              planar coordinates in the current one, and out by the previous instance record; its normal becomes the previous
+//              record's n on the side the pixel saw (4.21).
+// The follow forms always test ids: four instantiations each, twenty in all.  The follow step is written in the kernel's body, not
+// as helper functions: its prim decode, its sphere carry and its instance and quad block stand there once each, and `if constexpr`
+// on the argument's type leaves a form only its own paths.  The block's y-rotations (point and normal, in and out) are spelled out:
+// as functions or lambdas, in every spelling tried, they cost the instance kernels without normals two to four VGPRs and changed
+// which multiplies are packed (profiles/reproject_shared_isa.txt); as text all twenty kernels are what they were.
 //
-// rt_reproject_instances ("temporal reprojection that follows moved instances") passes a third form of that
-// argument, the sphere tables extended by the instance records of both frames and the two inst planes.  inst[p] is loaded with
-// the pixel's own data; the follow phase is still one round trip -- at most one medium record, then either the two 32-byte
-// instance records or the two sphere records, issued together -- and prev_inst is one more plane among the taps.  A pixel on a
-// moved instance has its point and, with normals on, its normal taken through the current record's world -> object map and the
-// previous record's object -> world map.  The twelve other instantiations are again what they were.
-//
-// rt_reproject_quads ("temporal reprojection that follows moved quads and boxes") passes a fourth form, the
-// instance form extended by the quad records of both frames.  A surface pixel whose prim is a quad of the tables (a face of a box
-// is one) and whose inst is none or in range loads the two 80-byte quad records and, under an instance, the two instance records,
-// all issued together: still one round trip, and such a pixel needs no medium record.  When Q, u or v differ the point goes into
-// object space by the current instance record (moved or not), onto the previous record's plane through its planar coordinates
-// in the current one, and out by the previous instance record; its normal becomes the previous record's n, on the side the pixel
-// saw.  Every line of that sits under if constexpr (QUA); the sixteen other instantiations are again what they were.
-//
-// The arithmetic is the contract's, statement by statement (-ffp-contract=off: no FMA is formed).
+// Memory phases.  What a lane waits for is the latency of dependent round trips, not bandwidth: per pixel it reads up to 40 B of
+// the current frame and four taps of up to 44 B, and writes up to 24 B.  Phase one is the pixel's own data.  The follow forms add
+// one phase: at most one medium record, then the records of both frames -- two 32-byte sphere records, or two 32-byte instance
+// records, or two 80-byte quad records, or those four -- issued together ahead of every test on them; the lanes of one object
+// share their lines.  The last phase is the taps: the loads of all four are issued before the first is looked at.
 //
 // Bounds.  The pixel's own index is tested against the frame before any address is formed.  A tap address is formed only from
 // x0, y0 after the float comparisons -1 <= x0 <= nx - 1, -1 <= y0 <= ny - 1 (false for a NaN) have passed and after the tap's
 // integer coordinates have compared as inside the image (unsigned: -1 wraps and compares as outside).  Every plane of the
-// previous frame holds ny * nx pixels, so every load of a tap that is inside the image is inside its buffer, whatever the
-// other buffers hold; a tap outside the image reads at the pixel's own index instead and is not counted.  The loads of all
-// four taps are issued together, ahead of the tests that decide whether a tap counts.  The follow step forms two more kinds of
-// address from data: media[index] after index < n_media and spheres[k] / prev_spheres[k] after k < n_spheres, both compared
-// unsigned; what the records hold is only ever arithmetic.  The instance form adds instances[i] / prev_instances[i] after
-// i < n_instances, compared unsigned, and inst / prev_inst at the pixel and tap indices bounded above; flag bits are only tested.
-// The quad form adds quads[g] / prev_quads[g] after g < n_quads, compared unsigned.
+// previous frame holds ny * nx pixels, prev_inst among them, so every load of a tap that is inside the image is inside its buffer,
+// whatever the other buffers hold; a tap outside the image reads at the pixel's own index instead and is not counted.  The
+// follow step forms four more kinds of address from data, each after an unsigned comparison with the table's count:
+// media[index] after index < n_media, spheres[k] / prev_spheres[k] after k < n_spheres, instances[i] / prev_instances[i] after
+// i < n_instances, quads[g] / prev_quads[g] after g < n_quads.  What the records hold is only ever arithmetic; a medium's
+// boundary is decoded into an index that passes the same comparisons; flag bits are only tested.
+#include <type_traits>
+
 #include "rt_device.h"
 #include "rt_launch.h"
 
@@ -52,26 +52,21 @@ namespace {
 
 constexpr int TILE = RT_REPROJECT_TILE;
 
+constexpr unsigned NONE = 0xFFFFFFFFu, INDEX = 0x0FFFFFFFu;   // no record; the index bits of an RT_PRIM_REF
+
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
-// the kernel's optional second argument (the FOL branch is not instantiated without one)
-__device__ __forceinline__ const rt_reproject_follow_params& follow_tables(const rt_reproject_follow_params& fp) { return fp; }
-__device__ __forceinline__ const rt_reproject_follow_instance_params& instance_tables(const rt_reproject_follow_instance_params& ip) { return ip; }
-template <class... Follow> struct follows_instances { static constexpr bool value = false; };
-template <> struct follows_instances<rt_reproject_follow_instance_params> { static constexpr bool value = true; };
-template <> struct follows_instances<rt_reproject_follow_quad_params> { static constexpr bool value = true; };
-__device__ __forceinline__ const rt_reproject_follow_quad_params& quad_tables(const rt_reproject_follow_quad_params& qp) { return qp; }
-template <class... Follow> struct follows_quads { static constexpr bool value = false; };
-template <> struct follows_quads<rt_reproject_follow_quad_params> { static constexpr bool value = true; };
+// the kernel's optional second argument, and what its type says the follow step looks for
+template <class F> __device__ __forceinline__ const F& tables(const F& f) { return f; }
+template <class... Follow> constexpr bool follows_instances = (std::is_base_of_v<rt_reproject_follow_instance_params, Follow> || ...);
+template <class... Follow> constexpr bool follows_quads = (std::is_base_of_v<rt_reproject_follow_quad_params, Follow> || ...);
 
-// rt_reproject launches <NRM, IDS, MOT> with no second argument.  rt_reproject_moving passes its tables as one: FOL, step 1 gains
-// its tail (a surface pixel on a sphere whose record changed is carried back to where that surface point was) and prim[p] is read
-// whatever IDS says.  rt_reproject_instances passes rt_reproject_follow_instance_params: INS, the tail looks for an instance first
-// and a tap must also show the pixel's inst.  rt_reproject_quads passes rt_reproject_follow_quad_params: INS and QUA, a pixel on
-// a quad of the tables takes the quad path, which shares the instance path's two maps.
+// One lane per pixel; the body is the contract's steps in order.  <NRM, IDS, MOT>: the normal test, the id test, the motion output.
+// Follow: nothing (rt_reproject), or the tables of the follow step as a second argument; a follow form reads prim[p] whatever IDS
+// says, an instance form also inst[p] and, among the taps, prev_inst.
 template <bool NRM, bool IDS, bool MOT, class... Follow>
 __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_reproject_params rp, Follow... follow) {
-    constexpr bool FOL = sizeof...(Follow) > 0, INS = follows_instances<Follow...>::value, QUA = follows_quads<Follow...>::value;
+    constexpr bool FOL = sizeof...(Follow) > 0, INS = follows_instances<Follow...>, QUA = follows_quads<Follow...>;
     const int tid = threadIdx.x;
     const int nx = rp.nx, ny = rp.ny;
     const unsigned by = blockIdx.x / (unsigned)rp.tiles_x, bx = blockIdx.x - by * (unsigned)rp.tiles_x;
@@ -86,7 +81,7 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
     int32_t idp = 0;
     if (IDS || FOL) idp = rp.prim[p];
     int32_t insp = 0;
-    if constexpr (INS) insp = instance_tables(follow...).inst[p];
+    if constexpr (INS) insp = tables(follow...).inst[p];
 
     // 1. the pixel's centre ray and its world point (or, for sky, its direction: a point at infinity)
     const float fi = (float)(int)i, fj = (float)(int)j, fnx = (float)nx, fny = (float)ny;
@@ -103,27 +98,28 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
             P[c] = rp.origin[c] + z * q[c];
             q[c] = P[c] - rp.prev_origin[c];
         }
+        // 1-follow. a surface point on something that moved goes back to where it was, its normal with it
         if constexpr (FOL) {
-            const rt_reproject_follow_params& fp = follow_tables(follow...);
-            // 1a. which sphere: the pixel's own, or the one that bounds its medium.  Both table indices are compared unsigned
-            // against the tables' lengths before an address is formed; nothing loaded from a record reaches an address.
-            unsigned k = 0xFFFFFFFFu;
-            if constexpr (INS) {
-                // 1a'. which instance: the pixel's own, or the one that bounds its medium -- the one medium record this step
-                // loads serves the sphere rule as well.  An instance in range takes the pixel: the sphere steps are skipped.
-                const rt_reproject_follow_instance_params& ip = instance_tables(follow...);
-                unsigned ii = 0xFFFFFFFFu;
-                if (insp >= 0) ii = (unsigned)insp;
-                if (idp >= 0) {
-                    const unsigned kind = (unsigned)idp >> 28, index = (unsigned)idp & 0x0FFFFFFFu;
-                    if (kind == (unsigned)RT_PRIM_SPHERE) {
-                        k = index;
-                    } else if (kind == (unsigned)RT_PRIM_MEDIUM && index < (unsigned)fp.n_media) {
-                        const int32_t b = fp.media[index].boundary;
-                        if (b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_SPHERE) k = (unsigned)b & 0x0FFFFFFFu;
-                        if (insp < 0 && b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_INSTANCE) ii = (unsigned)b & 0x0FFFFFFFu;
-                    }
+            const rt_reproject_follow_params& fp = tables(follow...);
+            // 1a. what the pixel's prim says it follows.  k: the sphere it shows, or the one that bounds the medium it shows.  ii
+            // (the instance forms): inst[p], or without one the instance that bounds its medium.  At most one medium record is
+            // loaded, after index < n_media compared unsigned; of what it holds only the kind is tested and the index bits kept,
+            // and those pass the tables' own comparisons before an address is formed.
+            unsigned k = NONE, ii = NONE;
+            if (INS && insp >= 0) ii = (unsigned)insp;
+            if (idp >= 0) {
+                const unsigned kind = (unsigned)idp >> 28, index = (unsigned)idp & INDEX;
+                if (kind == (unsigned)RT_PRIM_SPHERE) {
+                    k = index;
+                } else if (kind == (unsigned)RT_PRIM_MEDIUM && index < (unsigned)fp.n_media) {
+                    const int32_t b = fp.media[index].boundary;
+                    if (b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_SPHERE) k = (unsigned)b & INDEX;
+                    if (INS && insp < 0 && b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_INSTANCE) ii = (unsigned)b & INDEX;
                 }
+            }
+            if constexpr (INS) {
+                // 1a'. an instance in range takes the pixel: the sphere steps are skipped.
+                const rt_reproject_follow_instance_params& ip = tables(follow...);
                 bool ipath = ii < (unsigned)ip.n_instances;
                 // 1a''. which quad: the pixel's own prim, when the tables hold it and its inst is none or in range (a quad's prim
                 // is no medium, so ii is inst[p] or none here).  Such a pixel takes this block with or without an instance.
@@ -131,12 +127,12 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                 unsigned g = 0;
                 if constexpr (QUA) {
                     if (idp >= 0 && ((unsigned)idp >> 28) == (unsigned)RT_PRIM_QUAD) {
-                        g = (unsigned)idp & 0x0FFFFFFFu;
-                        qpath = g < (unsigned)quad_tables(follow...).n_quads && (insp < 0 || ipath);
+                        g = (unsigned)idp & INDEX;
+                        qpath = g < (unsigned)tables(follow...).n_quads && (insp < 0 || ipath);
                     }
                 }
                 if (ipath || qpath) {
-                    k = 0xFFFFFFFFu;
+                    k = NONE;
                     // 1b'. both records' loads are issued together; only their floats and flag bits are used
                     rt_instance I, J;
                     if constexpr (QUA) {   // 1b''. ... and with them the two quad records of a quad pixel
@@ -150,8 +146,8 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                     bool qmoved = false;
                     if constexpr (QUA) {
                         if (qpath) {
-                            const rt_quad* G = quad_tables(follow...).quads + g;
-                            const rt_quad* H = quad_tables(follow...).prev_quads + g;
+                            const rt_quad* G = tables(follow...).quads + g;
+                            const rt_quad* H = tables(follow...).prev_quads + g;
 #pragma unroll
                             for (int c = 0; c < 3; ++c) {
                                 GQ[c] = G->Q[c]; Gu[c] = G->u[c]; Gv[c] = G->v[c]; Gw[c] = G->w[c]; HQ[c] = H->Q[c]; Hu[c] = H->u[c]; Hv[c] = H->v[c];
@@ -217,14 +213,6 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                         }
                     }
                 }
-            } else if (idp >= 0) {
-                const unsigned kind = (unsigned)idp >> 28, index = (unsigned)idp & 0x0FFFFFFFu;
-                if (kind == (unsigned)RT_PRIM_SPHERE) {
-                    k = index;
-                } else if (kind == (unsigned)RT_PRIM_MEDIUM && index < (unsigned)fp.n_media) {
-                    const int32_t b = fp.media[index].boundary;
-                    if (b >= 0 && ((unsigned)b >> 28) == (unsigned)RT_PRIM_SPHERE) k = (unsigned)b & 0x0FFFFFFFu;
-                }
             }
             if (k < (unsigned)fp.n_spheres) {
                 // 1b. both records' loads are issued together (one round trip), ahead of the taps' phase
@@ -284,7 +272,7 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
                 hr[k] = rp.history[3 * o[k]]; hg[k] = rp.history[3 * o[k] + 1]; hb[k] = rp.history[3 * o[k] + 2];
                 if (NRM) { nqx[k] = rp.prev_normal[3 * o[k]]; nqy[k] = rp.prev_normal[3 * o[k] + 1]; nqz[k] = rp.prev_normal[3 * o[k] + 2]; }
                 if (IDS) idq[k] = rp.prev_prim[o[k]];
-                if constexpr (INS) insq[k] = instance_tables(follow...).prev_inst[o[k]];
+                if constexpr (INS) insq[k] = tables(follow...).prev_inst[o[k]];
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -331,52 +319,28 @@ __global__ __launch_bounds__(RT_REPROJECT_THREADS) void rt_reproject_kernel(rt_r
     }
 }
 
-template <bool NRM, bool IDS, bool MOT>
-hipError_t launch(const rt_reproject_params& rp, hipStream_t st) {
+template <bool NRM, bool IDS, bool MOT, class... Follow>
+hipError_t launch(const rt_reproject_params& rp, hipStream_t st, const Follow&... follow) {
     const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
-    return rt_launch_kernel(rt_reproject_kernel<NRM, IDS, MOT>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp);
+    return rt_launch_kernel(rt_reproject_kernel<NRM, IDS, MOT, Follow...>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, follow...);
 }
-// rt_reproject_moving: ids are always on (the entry requires prim and prev_prim; without a history no tap is read)
-template <bool NRM, bool MOT>
-hipError_t launch_moving(const rt_reproject_params& rp, const rt_reproject_follow_params& fp, hipStream_t st) {
-    const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
-    return rt_launch_kernel(rt_reproject_kernel<NRM, true, MOT, rt_reproject_follow_params>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, fp);
-}
-// rt_reproject_instances: likewise, with the instance form of the second argument
-template <bool NRM, bool MOT>
-hipError_t launch_instances(const rt_reproject_params& rp, const rt_reproject_follow_instance_params& ip, hipStream_t st) {
-    const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
-    return rt_launch_kernel(rt_reproject_kernel<NRM, true, MOT, rt_reproject_follow_instance_params>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, ip);
-}
-// rt_reproject_quads: likewise, with the quad form
-template <bool NRM, bool MOT>
-hipError_t launch_quads(const rt_reproject_params& rp, const rt_reproject_follow_quad_params& qp, hipStream_t st) {
-    const unsigned tiles_y = ((unsigned)rp.ny + TILE - 1) / TILE;
-    return rt_launch_kernel(rt_reproject_kernel<NRM, true, MOT, rt_reproject_follow_quad_params>, dim3(RT_REPROJECT_THREADS), dim3((unsigned)rp.tiles_x * tiles_y), 0, st, rp, qp);
-}
-template <bool NRM, bool IDS>
-hipError_t launch_motion(bool motion_on, const rt_reproject_params& rp, hipStream_t st) {
-    return motion_on ? launch<NRM, IDS, true>(rp, st) : launch<NRM, IDS, false>(rp, st);
+template <bool IDS, class... Follow>
+hipError_t launch_flags(bool normals_on, bool motion_on, const rt_reproject_params& rp, hipStream_t st, const Follow&... follow) {
+    if (normals_on) return motion_on ? launch<true, IDS, true>(rp, st, follow...) : launch<true, IDS, false>(rp, st, follow...);
+    return motion_on ? launch<false, IDS, true>(rp, st, follow...) : launch<false, IDS, false>(rp, st, follow...);
 }
 
 }  // namespace
 
-hipError_t rt_launch_reproject(bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp, hipStream_t st) {
-    if (normals_on) return ids_on ? launch_motion<true, true>(motion_on, rp, st) : launch_motion<true, false>(motion_on, rp, st);
-    return ids_on ? launch_motion<false, true>(motion_on, rp, st) : launch_motion<false, false>(motion_on, rp, st);
-}
-
-hipError_t rt_launch_reproject_moving(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_params& fp, hipStream_t st) {
-    if (normals_on) return motion_on ? launch_moving<true, true>(rp, fp, st) : launch_moving<true, false>(rp, fp, st);
-    return motion_on ? launch_moving<false, true>(rp, fp, st) : launch_moving<false, false>(rp, fp, st);
-}
-
-hipError_t rt_launch_reproject_instances(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_instance_params& ip, hipStream_t st) {
-    if (normals_on) return motion_on ? launch_instances<true, true>(rp, ip, st) : launch_instances<true, false>(rp, ip, st);
-    return motion_on ? launch_instances<false, true>(rp, ip, st) : launch_instances<false, false>(rp, ip, st);
-}
-
-hipError_t rt_launch_reproject_quads(bool normals_on, bool motion_on, const rt_reproject_params& rp, const rt_reproject_follow_quad_params& qp, hipStream_t st) {
-    if (normals_on) return motion_on ? launch_quads<true, true>(rp, qp, st) : launch_quads<true, false>(rp, qp, st);
-    return motion_on ? launch_quads<false, true>(rp, qp, st) : launch_quads<false, false>(rp, qp, st);
+// The kernel of a form takes the slice of `qp` that is the form's own argument: none, its sphere part, its instance part, all of it.
+// The follow forms always test ids (their entries require prim and prev_prim; without a history no tap is read).
+hipError_t rt_launch_reproject(rt_reproject_form form, bool normals_on, bool ids_on, bool motion_on, const rt_reproject_params& rp,
+                               const rt_reproject_follow_quad_params& qp, hipStream_t st) {
+    switch (form) {
+    case RT_REPROJECT_STATIC: return ids_on ? launch_flags<true>(normals_on, motion_on, rp, st) : launch_flags<false>(normals_on, motion_on, rp, st);
+    case RT_REPROJECT_SPHERES: return launch_flags<true, rt_reproject_follow_params>(normals_on, motion_on, rp, st, qp);
+    case RT_REPROJECT_INSTANCES: return launch_flags<true, rt_reproject_follow_instance_params>(normals_on, motion_on, rp, st, qp);
+    case RT_REPROJECT_QUADS: return launch_flags<true, rt_reproject_follow_quad_params>(normals_on, motion_on, rp, st, qp);
+    }
+    return hipErrorInvalidValue;
 }
