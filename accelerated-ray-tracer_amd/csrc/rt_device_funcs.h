@@ -150,6 +150,29 @@ DEV T uniform_load(const T* p) {
     return u.value;
 }
 
+// A field or record of a kernel's own argument blocks, read from the kernel-argument segment where it is used.  An argument
+// the compiler sees as a kernel parameter is loaded at entry and kept for the whole kernel; what does not fit into SGPRs is
+// parked in lanes of VGPRs, and every use on the way costs a v_readlane_b32, a VALU instruction.  For constants of a stage
+// that runs about once per 64 rays, a few s_load_dword* at the use are cheaper than carrying them through the walk.  The
+// pointer passes through an empty asm so that the (invariant) loads are not hoisted back to the kernel's entry; the address is
+// wave-uniform, so they stay on the scalar side.  `offset`: byte offset in the segment -- the kernel's by-value arguments lie
+// there one after the other, each at its natural alignment (kernarg_offset_2nd for the second of two).
+template <typename T>
+DEV T kernarg_load(unsigned int offset) {
+    static_assert(sizeof(T) % 4 == 0, "records are whole dwords");
+    typedef const __attribute__((address_space(4))) unsigned char* const_bytes;
+    typedef const __attribute__((address_space(4))) uint32_t* const_words;
+    const_words w = (const_words)((const_bytes)__builtin_amdgcn_kernarg_segment_ptr() + offset);
+    asm volatile("" : "+s"(w));
+    union { T value; uint32_t words[sizeof(T) / 4]; } u;
+#pragma unroll
+    for (unsigned int k = 0; k < sizeof(T) / 4; ++k) u.words[k] = w[k];
+    return u.value;
+}
+// where the second of a kernel's two by-value arguments (A first, B second) starts in the segment
+template <typename A, typename B>
+constexpr unsigned int kernarg_offset_2nd() { return (unsigned int)((sizeof(A) + alignof(B) - 1) / alignof(B) * alignof(B)); }
+
 // quad::hit (quad.cuh:60-90); inclusive bounds
 DEV bool quad_test(const rt_quad& q, const Ray& r, float tmin, float tmax, float& t_out) {
     const f3 n = ld3(q.n);

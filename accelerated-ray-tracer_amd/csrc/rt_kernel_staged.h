@@ -3,8 +3,29 @@
 #ifndef RT_STEP_UNROLL
 #define RT_STEP_UNROLL 2
 #endif
+// Two forms that change when a value is computed or read, never the value; 0 gives the other form back (experiment builds).
+//   RT_CARRY_LOOSE 1     the walk loop's addends (LooseRay) are computed in stage F with the ray's 1/d and kept in six VGPRs
+//                        for the ray's life, instead of once per trip in stage A's prologue.  Chosen by a family's translation
+//                        unit, the way rt_staged_spheres.hip chooses RT_DRAW_ONE_FMA: where the resource table shows the registers
+//   RT_KERNARG_AT_USE 1  stage E reads the camera record and the miss term's background from the kernel-argument segment
+//                        where it uses them (kernarg_load, rt_device_funcs.h) instead of holding them through the walk: fewer
+//                        VGPRs in every family
+#ifndef RT_CARRY_LOOSE
+#define RT_CARRY_LOOSE 0
+#endif
+#ifndef RT_KERNARG_AT_USE
+#define RT_KERNARG_AT_USE 1
+#endif
 #include "rt_device_funcs.h"
 #include "rt_launch.h"
+
+// the main kernel's arguments are (rt_scene_dev sd, rt_frame_params fp): where stage E finds its records in the segment
+static_assert(alignof(rt_scene_dev) == 8 && alignof(rt_frame_params) == 8 && sizeof(rt_scene_dev) % 8 == 0 && sizeof(rt_frame_params) % 8 == 0,
+              "kernel-argument offsets below assume both blocks are 8-byte aligned and whole");
+static_assert(offsetof(rt_scene_dev, camera) % 8 == 0 && sizeof(rt_camera) == 96, "the camera record is read as 24 dwords at its own offset");
+struct rt_sky_args { float background[3]; int32_t use_gradient_bg; };   // miss_color's fields, as they lie in rt_frame_params
+static_assert(offsetof(rt_frame_params, use_gradient_bg) == offsetof(rt_frame_params, background) + 12, "rt_sky_args mirrors rt_frame_params");
+constexpr unsigned int RT_KERNARG_FP = kernarg_offset_2nd<rt_scene_dev, rt_frame_params>();
 
 // =============================================================================
 // Kernel D ("staged"): kernel C with the shading block cut into stages.
@@ -103,6 +124,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
     int32_t parked = -1;         // index form only: leaf node the lane stopped at (node < 0)
     int32_t pend = -1;           // leaf node whose box passed during the walk and whose object test is still due
     float cur_a = 1.f;           // dot(d, d) of the current ray (sphere.cuh:58), hoisted out of the sphere tests
+    LooseRay lr_ray; lr_ray.clo = mk3(0, 0, 0); lr_ray.chi = mk3(0, 0, 0);   // RT_CARRY_LOOSE: the current ray's addends, written with `inv` in stage F
     bool have_pixel = false, first = true, finite_inv = true;
     bool tier3_open = true;      // this lane has not yet seen the end of the tier-3 queue
     bool leave = false;          // tail hand-off (rt_device.h): the frame's last pixels leave for the tail launch at their next sample boundary.  Wave-uniform
@@ -185,7 +207,8 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
             const int trip_pairs = ((sparse ? 2 * fp.steps_per_trip : fp.steps_per_trip) + RT_STEP_UNROLL - 1) / RT_STEP_UNROLL;
             // the loop's box test is the widened one-fma-per-bound form (rt_device_funcs.h, slab_test_loose): a superset of
             // aabb::hit's passes, which is all the walk needs -- stage B tests every noted leaf's own box again, exactly
-            const LooseRay lr = loose_setup(inv, cur.o, sd.bound);
+            // (its inputs change in stage F only: a family with six VGPRs to spare keeps it from there)
+            const LooseRay lr = RT_CARRY_LOOSE ? lr_ray : loose_setup(inv, cur.o, sd.bound);
             for (int pair = 0; pair < trip_pairs; ++pair) {
                 if (__ballot((unsigned)node < (unsigned)limit) == 0ull) break;
 #pragma unroll
@@ -445,8 +468,9 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                 if (node == ST_NEWPATH) {
                     // the background term of a path that ended in a miss (marked after stage B), before the sample is added and
                     // the pixel stored, parked or handed off.  The mark goes for every lane here, one that runs dry included: it
-                    // may be back with `first` set when its wave turns ordinary.
-                    if (bounce < 0) radiance = fma3(throughput, miss_color(fp, cur), radiance);
+                    // may be back with `first` set when its wave turns ordinary.  (RT_KERNARG_AT_USE: the background's four words, read here)
+                    if (bounce < 0) radiance = fma3(throughput, RT_KERNARG_AT_USE ? miss_color(kernarg_load<rt_sky_args>(RT_KERNARG_FP + offsetof(rt_frame_params, background)), cur)
+                                                                                    : miss_color(fp, cur), radiance);
                     bounce = 0;
                     if (!first) { col = col + radiance; ++sample; }
                     first = false;
@@ -532,7 +556,10 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                     if (alive) {
                         const float u = ((float)px_i + rt_xorwow_uniform(g)) / (float)fp.nx;
                         const float v = ((float)px_j + rt_xorwow_uniform(g)) / (float)fp.ny;
-                        cur = camera_get_ray(sd.camera, u, v, g);
+                        // (RT_KERNARG_AT_USE: the launch's own camera record, 24 words read here; held in SGPRs through the walk it was
+                        // the register pressure behind most of the v_readlane of stages A-D)
+                        cur = RT_KERNARG_AT_USE ? camera_get_ray(kernarg_load<rt_camera>(offsetof(rt_scene_dev, camera)), u, v, g)
+                                                : camera_get_ray(sd.camera, u, v, g);
                         throughput = mk3(1, 1, 1); radiance = mk3(0, 0, 0);
                         node = ST_SETUP;
                     } else {
@@ -560,6 +587,7 @@ __global__ void __launch_bounds__((SPHERES_ONLY && TEX < 2) ? RT_LEAN_MAX_THREAD
                 inv = mk3(1.0f / cur.d.x, 1.0f / cur.d.y, 1.0f / cur.d.z);
                 finite_inv = inv_is_finite(inv) && loose_ok(inv, cur.o, sd.bound);   // (else: the reference's own slab form, leaf by leaf)
                 cur_a = dot(cur.d, cur.d);
+                if (RT_CARRY_LOOSE) lr_ray = loose_setup(inv, cur.o, sd.bound);   // (never read while !finite_inv: the reference-form trip)
                 best.t = FLT_MAX; best.prim = -1; best.inst = -1;
                 node = n_nodes > 0 ? root : ST_DONE;
                 ++rays;
