@@ -610,6 +610,48 @@ def reset_options() -> None:
     _check(rt_lib().rt_reset_options(), "rt_reset_options")
 
 
+# ---- the order of the tail hand-off queue (csrc/rt_handoff_order.h), restated in NumPy
+HANDOFF_SUB_BITS = 2
+HANDOFF_BUCKETS = 1 + 64 * (1 << HANDOFF_SUB_BITS)
+HANDOFF_ORDER_MIN_PER_WAVE, HANDOFF_ORDER_MAX_PER_WAVE = 2, 32
+
+
+def handoff_order_key(entries, costs, sample_begin: int, sample_end: int):
+    """Remaining-work key of hand-off queue entries (next sample << 32 | pixel) whose pixels' parked costs are `costs`, entry for
+    entry: (sample_end - next) * (rays so far + 1) // (samples done + 1), exact, as an object array of Python integers."""
+    e = np.asarray(entries, np.uint64)
+    nxt = (e >> np.uint64(32)).astype(np.int64)
+    rays = (np.asarray(costs, np.uint32) & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    to_go, done = np.maximum(int(sample_end) - nxt, 0), np.maximum(nxt - int(sample_begin), 0)
+    return np.array([int(t) * (int(r) + 1) // (int(d) + 1) for t, r, d in zip(to_go, rays, done)], dtype=object)
+
+
+def handoff_order_bucket(keys):
+    """Bucket of each key on the fixed logarithmic scale: 0 for key 0, else 1 + 4 e + m with e the key's leading bit and m the two
+    bits below it (zeros shifted in under e < 2).  The ordered queue holds its entries in non-increasing bucket order."""
+    out = np.zeros(len(keys), np.int64)
+    for i, k in enumerate(keys):
+        k = int(k)
+        if k > 0:
+            e = k.bit_length() - 1
+            m = (k >> (e - HANDOFF_SUB_BITS) if e >= HANDOFF_SUB_BITS else k << (HANDOFF_SUB_BITS - e)) & ((1 << HANDOFF_SUB_BITS) - 1)
+            out[i] = 1 + (e << HANDOFF_SUB_BITS) + m
+    return out
+
+
+def debug_order_handoff(entries, costs, sample_begin: int, sample_end: int, tail_waves: int):
+    """rt_debug_order_handoff (tests): the ordering launch of one tail on n entries (every pixel below n; costs[pixel] its parked
+    cost) for a tail launch of `tail_waves` waves.  Returns (the ordered queue, spare slots behind it that were written)."""
+    e, c = np.ascontiguousarray(entries, np.uint64), np.ascontiguousarray(costs, np.uint32)
+    assert e.ndim == 1 and c.shape == e.shape
+    out, overrun = np.zeros(len(e), np.uint64), C.c_uint32(0xFFFFFFFF)
+    L = rt_lib()
+    L.rt_debug_order_handoff.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_uint32)]
+    _check(L.rt_debug_order_handoff(e.ctypes.data if len(e) else None, c.ctypes.data if len(e) else None, len(e), int(sample_begin), int(sample_end),
+                                    int(tail_waves), out.ctypes.data if len(e) else None, C.byref(overrun)), "rt_debug_order_handoff")
+    return out, int(overrun.value)
+
+
 def denoise_workspace_bytes(nx: int, ny: int) -> int:
     """Bytes of device memory rt_denoise wants as its workspace for an nx x ny frame (0 for a bad size)."""
     return int(rt_lib().rt_denoise_workspace_bytes(int(nx), int(ny)))
@@ -1162,6 +1204,20 @@ class DeviceScene:
         out = np.zeros((int(info[2]), int(info[1])), np.uint32)
         _check(L.rt_debug_cost_map(self._p, out.ctypes.data, out.size, info), "rt_debug_cost_map")
         return self.COST_MAP_STATES[info[0]], out, int(info[3])
+
+    def handoff_queue(self):
+        """The tail hand-off queue of the last frame's last part in push order (rt_debug_handoff_queue): (entries, costs, served, info) --
+        uint64 (next sample << 32 | pixel); entry for entry the pixel's parked cost; the queue as the tail launch was given it; and
+        dict(ordered: the ordering kernels ran, min, max: the entry counts between which they order and outside which they copy)."""
+        L = rt_lib()
+        L.rt_debug_handoff_queue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        info = (C.c_int64 * 4)()
+        _check(L.rt_debug_handoff_queue(self._p, None, None, None, 0, info), "rt_debug_handoff_queue")
+        n = int(info[0])
+        entries, costs, served = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        if n:
+            _check(L.rt_debug_handoff_queue(self._p, entries.ctypes.data, costs.ctypes.data, served.ctypes.data, n, info), "rt_debug_handoff_queue")
+        return entries, costs, served, dict(ordered=bool(info[1]), min=int(info[2]), max=int(info[3]))
 
     def set_cost_map(self, costs) -> None:
         """Install `costs` (one uint32 per local pixel of the last ranked frame) as that frame geometry's exact cost map

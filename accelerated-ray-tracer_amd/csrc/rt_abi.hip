@@ -21,6 +21,7 @@
 #include "../../include/rt_abi.h"
 #include "rt_call_buffers.h"
 #include "rt_device.h"
+#include "rt_handoff_order.h"
 #include "rt_refit_host.h"
 
 namespace {
@@ -80,6 +81,7 @@ struct rt_options {
     int handoff_scan = 1;        // ... also in scenes scanned in lockstep (lds_mode 4), which have no tier 1
     int handoff_poll_us = 1000;  // ... looked for this often by each wave that has run out of queued work
     int handoff_pixels = -1;     // ... when at most this many are in flight and the tile queue is dry; -1 = auto (render_impl)
+    int handoff_order = 1;       // ... served most remaining work first: the queue is ordered on the device before the tail launch (rt_handoff_order.h); 0 = push order
     int sparse_eager = 0;
     int sparse_work_percent = 5;  // tiers 0-2 hold at most this share of the frame's work (rays so far); dearer-than-average pixels beyond it go to tier 3
     int sparse_wg_percent = 35;   // at most this share of the workgroups starts in sparse mode
@@ -202,6 +204,12 @@ struct rt_scene {
     size_t tile_capacity = 0, pixel_capacity = 0;
     unsigned long long* d_handoff = nullptr;      // tail hand-off queue: (sample << 32 | pixel), one entry per resident lane at most
     size_t handoff_capacity = 0;
+    unsigned long long* d_handoff_ordered = nullptr;   // ... ordered for the tail launch (rt_handoff_order.h), grown like d_handoff
+    size_t handoff_ordered_capacity = 0;
+    unsigned int* d_handoff_scratch = nullptr;          // ... the ordering kernels' bucket counts
+    size_t handoff_scratch_capacity = 0;
+    bool tail_ordered = false;                           // the last frame's tail launches were served from d_handoff_ordered (rt_debug_handoff_queue)
+    uint32_t tail_order_min = 0, tail_order_max = 0;
     rt_rank_info* d_rank = nullptr;               // tier sizes of the next ranked launch (written and read on the device only)
     unsigned int* d_cal_cost = nullptr;           // cost prior: rays per pixel of the calibration frame (cal_nx x cal_ny at 4 spp)
     int cal_nx = 0, cal_ny = 0;
@@ -740,6 +748,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "handoff_scan") { if (value < 0 || value > 1) return invalid("handoff_scan: 0 or 1"); g_opt.handoff_scan = value; }
     else if (k == "handoff_poll_us") { if (value < 1 || value > 1000000) return invalid("handoff_poll_us: 1..1000000"); g_opt.handoff_poll_us = value; }
     else if (k == "handoff_pixels") { if (value < -1 || value > (1 << 24)) return invalid("handoff_pixels: -1 (auto) or 0..16777216"); g_opt.handoff_pixels = value; }
+    else if (k == "handoff_order") { if (value < 0 || value > 1) return invalid("handoff_order: 0 or 1"); g_opt.handoff_order = value; }
     else if (k == "prior") { if (value < 0 || value > 1) return invalid("prior: 0 or 1"); g_opt.prior = value; }
     else if (k == "presplit_samples") { if (value < 0 || value > 4096) return invalid("presplit_samples: 0..4096"); g_opt.presplit_samples = value; }
     else if (k == "resplit_samples") { if (value < 0 || value > 65536) return invalid("resplit_samples: 0..65536"); g_opt.resplit_samples = value; }
@@ -792,6 +801,8 @@ rt_status rt_scene_destroy(rt_scene* s) {
     if (s->d_heavy_pixels) (void)hipFree(s->d_heavy_pixels);
     if (s->d_rank) (void)hipFree(s->d_rank);
     if (s->d_handoff) (void)hipFree(s->d_handoff);
+    if (s->d_handoff_ordered) (void)hipFree(s->d_handoff_ordered);
+    if (s->d_handoff_scratch) (void)hipFree(s->d_handoff_scratch);
     if (s->d_cal_cost) (void)hipFree(s->d_cal_cost);
     if (s->cost_map.d) (void)hipFree(s->cost_map.d);
     for (void* p : {s->refit.block, (void*)s->refit.d_indices, (void*)s->refit.d_records}) if (p) (void)hipFree(p);
@@ -2265,6 +2276,86 @@ rt_status rt_debug_handoff(rt_scene* s, unsigned long long* out2) {
     return RT_OK;
 }
 
+// The hand-off queue of the last frame's last part, in push order (diagnostics, every build; tools/tail_order_stats.py): up to `cap`
+// entries (next sample << 32 | pixel), entry for entry the parked cost handoff_state[pixel].cost, and the queue as the tail launch
+// was given it (`served`: ordered, copied through, or -- handoff_order = 0 -- the queue itself).  info4: [0] entries the queue
+// holds, [1] 1 = the ordering kernels ran, [2] and [3] the counts between which they order (rt_handoff_order.h).  A pending
+// frame must have been closed.
+rt_status rt_debug_handoff_queue(rt_scene* s, unsigned long long* entries, uint32_t* costs, unsigned long long* served, int64_t cap, int64_t* info4) {
+    if (!s || !info4 || cap < 0 || (cap > 0 && (!entries || !costs || !served))) return invalid("rt_debug_handoff_queue: bad argument");
+    if (s->frame_pending) return invalid("rt_debug_handoff_queue: a frame is pending (rt_frame_finish first)");
+    info4[0] = 0; info4[1] = s->tail_ordered ? 1 : 0; info4[2] = s->tail_order_min; info4[3] = s->tail_order_max;
+    int64_t* const count_out = info4;
+    if (!s->d_handoff || !s->d_state || !s->ranked_frame) return RT_OK;
+    RT_TRY(use_device(s->device));
+    unsigned int pushed = 0;
+    HIPCHK(hipMemcpy(&pushed, s->d_work_counter + RT_WC_PUSHED, sizeof(pushed), hipMemcpyDeviceToHost));
+    const size_t count = pushed < s->handoff_capacity ? pushed : s->handoff_capacity;
+    *count_out = (int64_t)count;
+    const size_t n = count < (size_t)cap ? count : (size_t)cap;
+    if (n == 0) return RT_OK;
+    HIPCHK(hipMemcpy(entries, s->d_handoff, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(served, s->tail_ordered ? s->d_handoff_ordered : s->d_handoff, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::vector<rt_pixel_state> h_state(s->pixel_capacity);
+    HIPCHK(hipMemcpy(h_state.data(), s->d_state, h_state.size() * sizeof(rt_pixel_state), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t pix = (uint32_t)entries[i];
+        costs[i] = pix < h_state.size() ? h_state[pix].cost : 0u;
+    }
+    return RT_OK;
+}
+
+// Test seam of the queue ordering (rt_handoff_order.h; tests/test_handoff_order.py): the launch rt_render makes between the main
+// kernel and the tail launch, once, on n caller-supplied entries (next sample << 32 | pixel, every pixel below n) whose parked
+// costs are costs[pixel], for a tail launch of tail_waves waves and a part rendering [sample_begin, sample_end).  Null stream, synchronous.
+// The queue holds exactly n entries and the push counter stands ORDER_SEAM_SLACK beyond, as after a main kernel whose lanes found
+// the queue full; both device buffers have that many spare slots behind them, and *overrun_out = how many of the ordered
+// buffer's were written (0 unless the count was read unclipped).
+enum { ORDER_SEAM_SLACK = 3 };
+rt_status rt_debug_order_handoff(const unsigned long long* entries, const uint32_t* costs, int64_t n, int32_t sample_begin, int32_t sample_end,
+                                 int32_t tail_waves, unsigned long long* out, uint32_t* overrun_out) {
+    if (!overrun_out) return invalid("rt_debug_order_handoff: null argument");
+    if (n < 0 || n > (1ll << 24) || (n > 0 && (!entries || !costs || !out))) return invalid("rt_debug_order_handoff: n must be 0 .. 2^24 and the arrays non-null");
+    if (sample_begin < 0 || sample_end < sample_begin) return invalid("rt_debug_order_handoff: bad sample range");
+    if (tail_waves < 1 || tail_waves > (1 << 20)) return invalid("rt_debug_order_handoff: tail_waves must be 1 .. 2^20");
+    for (int64_t i = 0; i < n; ++i)
+        if ((int64_t)(uint32_t)entries[i] >= n) return invalid("rt_debug_order_handoff: an entry's pixel is not below n");
+    RT_TRY(use_device(g_device));
+    call_memory mem;
+    rt_handoff_order_params hp;
+    memset(&hp, 0, sizeof(hp));
+    const size_t most = (size_t)RT_HANDOFF_ORDER_MAX_PER_WAVE * (size_t)tail_waves;
+    hp.cap = (uint32_t)n; hp.min_items = (uint32_t)(RT_HANDOFF_ORDER_MIN_PER_WAVE * tail_waves); hp.max_items = (uint32_t)(most < (size_t)n ? most : (size_t)n);
+    hp.cost_begin = sample_begin; hp.sample_end = sample_end;
+    unsigned long long *d_queue = nullptr, *d_ordered = nullptr;
+    rt_pixel_state* d_state = nullptr;
+    unsigned int* d_pushed = nullptr;
+    const size_t scratch_bytes = rt_handoff_order_scratch_words(hp.max_items) * sizeof(unsigned int);
+    HIPCHK(mem.get((void**)&d_queue, (size_t)(n + ORDER_SEAM_SLACK) * sizeof(unsigned long long)));
+    HIPCHK(mem.get((void**)&d_ordered, (size_t)(n + ORDER_SEAM_SLACK) * sizeof(unsigned long long)));
+    HIPCHK(mem.get((void**)&d_state, (size_t)(n + 1) * sizeof(rt_pixel_state)));
+    HIPCHK(mem.get((void**)&d_pushed, sizeof(unsigned int)));
+    HIPCHK(mem.get((void**)&hp.scratch, scratch_bytes));
+    std::vector<rt_pixel_state> h_state((size_t)n + 1);                // (value-initialised)
+    for (int64_t i = 0; i < n; ++i) h_state[(size_t)i].cost = costs[i];
+    const unsigned int h_pushed = (unsigned int)n + ORDER_SEAM_SLACK;
+    HIPCHK(hipMemset(d_queue, 0, (size_t)(n + ORDER_SEAM_SLACK) * sizeof(unsigned long long)));     // spare slots: sample 0 of pixel 0
+    if (n > 0) HIPCHK(hipMemcpy(d_queue, entries, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_state, h_state.data(), h_state.size() * sizeof(rt_pixel_state), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_ordered, 0xFF, (size_t)(n + ORDER_SEAM_SLACK) * sizeof(unsigned long long)));
+    HIPCHK(hipMemcpy(d_pushed, &h_pushed, sizeof(h_pushed), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(hp.scratch, 0, scratch_bytes));
+    hp.queue = d_queue; hp.ordered = d_ordered; hp.state = d_state; hp.pushed = d_pushed;
+    HIPCHK(rt_launch_handoff_order(hp, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (n > 0) HIPCHK(hipMemcpy(out, d_ordered, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    unsigned long long spare[ORDER_SEAM_SLACK];
+    HIPCHK(hipMemcpy(spare, d_ordered + n, sizeof(spare), hipMemcpyDeviceToHost));
+    *overrun_out = 0u;
+    for (const unsigned long long w : spare) *overrun_out += w != ~0ull ? 1u : 0u;
+    return RT_OK;
+}
+
 // Diagnostic builds (-DRT_DIAG) leave per-stage execution counts behind the ray counter; 16 values.
 rt_status rt_debug_counters(rt_scene* s, unsigned long long* out16) {
     if (!s || !out16) return invalid("null argument");
@@ -2912,12 +3003,16 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     const size_t n_tiles = (size_t)g.tiles_x * (size_t)g.tiles_y;
     const size_t n_pixels = g.n_pixels;
     s->ranked_frame = false;
+    s->tail_ordered = false; s->tail_order_min = s->tail_order_max = 0;
     HIPCHK(hipMemsetAsync(s->d_ray_counter, 0, 256, stream));
     int part_index = 0;
+    bool order_tail = false;                 // option handoff_order: set with its buffers where the hand-off is set up
+    uint32_t order_min = 0, order_max = 0;
     // one part of the frame: the tier kernel (ranked parts of scenes that have tier data) on its own stream, forked from
     // and joined to the caller's stream by events, and the main kernel
     auto launch_part = [&](const rt_frame_params& q, dim3 grid_q, bool ranked) -> rt_status {
         HIPCHK(hipMemsetAsync(s->d_work_counter, 0, RT_WORK_COUNTER_BYTES, stream));
+        if (order_tail && q.handoff_queue) HIPCHK(hipMemsetAsync(s->d_handoff_scratch, 0, RT_HANDOFF_BUCKETS * sizeof(unsigned int), stream));
         const bool tiers = ranked && tier_possible;
         const int pi = part_index++ & 3;
         if (tiers) {
@@ -2932,6 +3027,19 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
             // running on its own stream: other pixels, other queue head -- leaves free of the machine
             rt_frame_params t = q;
             t.tail_mode = 1;
+            if (order_tail) {
+                // ... served most remaining work first: the tail's waves pull from a copy of the queue ordered on the device
+                // (rt_handoff_order.h), like every other queue of the frame.  The parked costs count from sample 0 except in a part
+                // that starts its pixels afresh.
+                rt_handoff_order_params hp;
+                memset(&hp, 0, sizeof(hp));
+                hp.queue = q.handoff_queue; hp.ordered = s->d_handoff_ordered; hp.state = q.handoff_state;
+                hp.pushed = q.work_counter + RT_WC_PUSHED; hp.scratch = s->d_handoff_scratch;
+                hp.cap = q.handoff_cap; hp.min_items = order_min; hp.max_items = order_max;
+                hp.cost_begin = (q.state_in && !q.fresh) ? 0 : q.sample_begin; hp.sample_end = q.sample_end;
+                HIPCHK(rt_launch_handoff_order(hp, stream));
+                t.handoff_queue = s->d_handoff_ordered;
+            }
             HIPCHK(launch_tier(s, t, dim3(tail_grid), tier_lds, stream));
         }
         if (tiers) HIPCHK(hipStreamWaitEvent(stream, s->ev_join[pi], 0));
@@ -2965,10 +3073,26 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
             fp.handoff_poll_ticks = g_opt.handoff_poll_us * 100;
             // auto: six pixels per wave of the tail launch (the headline frame: 18432 of 960000; 8192 .. 32768 measure the same,
             // profiles/r03_handoff.log), and never more than 1/8 of the pixels (small frames and shares: the Cornell box's
-            // 1/8 share, 45000 pixels, 178 ms without, 163 ms at 4096 - 8192, 180 ms at 16384)
+            // 1/8 share, 45000 pixels, 178 ms without, 163 ms at 4096 - 8192, 180 ms at 16384).
+            // Twelve per wave in the lean family when the tail is served most remaining work first (handoff_order): the tail ends with
+            // its longest chain, not with its queue, so a larger hand-off moves that chain to a tier wave earlier -- headline 67.3 ms at
+            // 6 in push order, 66.4 at 6 ordered, 65.0 - 65.1 at 10 - 12 ordered, 65.3 at 14, 66.1 at 16, and 67.7 at 12 in push order.
+            // The other families stay at 6: their tier waves spill and gain less on a main lane (Cornell smoke 46.6 ms at 6, 48.2 at
+            // 12; Cornell and Book-2 final measure the same at both; profiles/tail_order_mi355x.jsonl).
             const size_t tail_waves = (size_t)tail_grid * (RT_TIER_THREADS / 64);
             const size_t cap_px = n_pixels / 8;
-            fp.handoff_pixels = g_opt.handoff_pixels >= 0 ? g_opt.handoff_pixels : (int32_t)(6 * tail_waves < cap_px ? 6 * tail_waves : cap_px);
+            const size_t per_wave = (g_opt.handoff_order && lean_family) ? 12 : 6;
+            fp.handoff_pixels = g_opt.handoff_pixels >= 0 ? g_opt.handoff_pixels : (int32_t)(per_wave * tail_waves < cap_px ? per_wave * tail_waves : cap_px);
+            if (g_opt.handoff_order) {
+                // ordered between two and 32 entries per tail wave, copied through outside (rt_handoff_order.h)
+                const size_t most = (size_t)RT_HANDOFF_ORDER_MAX_PER_WAVE * tail_waves;
+                order_min = (uint32_t)(RT_HANDOFF_ORDER_MIN_PER_WAVE * tail_waves);
+                order_max = (uint32_t)(most < s->handoff_capacity ? most : s->handoff_capacity);
+                RT_TRY(grow(s->d_handoff_ordered, s->handoff_ordered_capacity, s->handoff_capacity));
+                RT_TRY(grow(s->d_handoff_scratch, s->handoff_scratch_capacity, rt_handoff_order_scratch_words(order_max)));
+                order_tail = true;
+                s->tail_ordered = true; s->tail_order_min = order_min; s->tail_order_max = order_max;
+            }
         }
         // ---- schedule
         // One ranking: three small kernels order the tiles, list the heavy pixels and size the tiers for the launch

@@ -12,10 +12,15 @@
 // The two orderings are bucket sorts by one workgroup: 2048 linear cost buckets, counted and scattered through LDS
 // atomics.  Within a bucket the order is whatever the atomics give -- this is scheduling only: which wave renders a
 // pixel never changes the pixel (its samples are one XORWOW stream, picked up where the previous part left it).
+//
+// The tail hand-off queue of every part is ordered here too, most remaining work first (rt_handoff_order.h): many workgroups,
+// fixed logarithmic buckets -- the one-workgroup sort above takes 0.25 ms for 32 k items, and these kernels run on the
+// frame's critical path between the main kernel and the tail launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "rt_device.h"
+#include "rt_handoff_order.h"
 
 namespace {
 
@@ -269,7 +274,78 @@ __global__ void rt_prior_map_kernel(rt_prior_params pp) {
     if ((threadIdx.x & 63) == 0 && sum) atomicAdd(pp.total, sum);
 }
 
+// ---- ordering the tail hand-off queue (rt_handoff_order.h): two kernels between the main kernel and the tail launch.
+// Both read the entry count from the device and fix their grids on max_items; workgroup w of both takes entries
+// [256 w, 256 w + 256), so what the first leaves per workgroup holds for the second.
+__device__ __forceinline__ unsigned int handoff_count(const rt_handoff_order_params& hp) {
+    const unsigned int pushed = *hp.pushed;
+    return pushed < hp.cap ? pushed : hp.cap;   // (slots taken beyond the queue's end were not filled)
+}
+__device__ __forceinline__ unsigned int handoff_bucket(const rt_handoff_order_params& hp, unsigned long long entry) {
+    const int next = (int)(entry >> 32);
+    const unsigned long long rays = hp.state[(uint32_t)entry].cost & 0x7FFFFFFFu;
+    const unsigned long long to_go = next < hp.sample_end ? (unsigned long long)(hp.sample_end - next) : 0ull;
+    const unsigned long long done = next > hp.cost_begin ? (unsigned long long)(next - hp.cost_begin) : 0ull;
+    const unsigned long long key = to_go * (rays + 1ull) / (done + 1ull);   // < 2^31 * 2^31
+    if (key == 0ull) return 0u;
+    const int e = 63 - __clzll((long long)key);
+    const unsigned int m = (unsigned int)(e >= RT_HANDOFF_SUB_BITS ? key >> (e - RT_HANDOFF_SUB_BITS) : key << (RT_HANDOFF_SUB_BITS - e)) & ((1u << RT_HANDOFF_SUB_BITS) - 1u);
+    return 1u + ((unsigned int)e << RT_HANDOFF_SUB_BITS) + m;
+}
+
+// 1. entries per bucket, and where each workgroup's entries start within each bucket
+__global__ void __launch_bounds__(RT_HANDOFF_ORDER_THREADS) rt_handoff_hist_kernel(rt_handoff_order_params hp) {
+    __shared__ unsigned int h[RT_HANDOFF_BUCKETS];
+    const unsigned int count = handoff_count(hp);
+    if (count < hp.min_items || count > hp.max_items || blockIdx.x * RT_HANDOFF_ORDER_THREADS >= count) return;
+    for (unsigned int b = threadIdx.x; b < RT_HANDOFF_BUCKETS; b += RT_HANDOFF_ORDER_THREADS) h[b] = 0u;
+    __syncthreads();
+    const unsigned int i = blockIdx.x * RT_HANDOFF_ORDER_THREADS + threadIdx.x;
+    if (i < count) atomicAdd(&h[handoff_bucket(hp, hp.queue[i])], 1u);
+    __syncthreads();
+    unsigned int* wg_start = hp.scratch + (size_t)RT_HANDOFF_BUCKETS * (blockIdx.x + 1u);
+    for (unsigned int b = threadIdx.x; b < RT_HANDOFF_BUCKETS; b += RT_HANDOFF_ORDER_THREADS) {
+        const unsigned int c = h[b];
+        wg_start[b] = c ? atomicAdd(&hp.scratch[b], c) : 0u;
+    }
+}
+
+// 2. the buckets scanned in descending order (by every workgroup for itself: 257 words), the entries scattered; or the plain copy
+__global__ void __launch_bounds__(RT_HANDOFF_ORDER_THREADS) rt_handoff_scatter_kernel(rt_handoff_order_params hp) {
+    __shared__ unsigned int total[RT_HANDOFF_BUCKETS], start[RT_HANDOFF_BUCKETS];
+    const unsigned int count = handoff_count(hp);
+    if (count < hp.min_items || count > hp.max_items) {
+        for (unsigned int i = blockIdx.x * RT_HANDOFF_ORDER_THREADS + threadIdx.x; i < count; i += gridDim.x * RT_HANDOFF_ORDER_THREADS) hp.ordered[i] = hp.queue[i];
+        return;
+    }
+    if (blockIdx.x * RT_HANDOFF_ORDER_THREADS >= count) return;
+    for (unsigned int b = threadIdx.x; b < RT_HANDOFF_BUCKETS; b += RT_HANDOFF_ORDER_THREADS) total[b] = hp.scratch[b];
+    __syncthreads();
+    const unsigned int* wg_start = hp.scratch + (size_t)RT_HANDOFF_BUCKETS * (blockIdx.x + 1u);
+    for (unsigned int b = threadIdx.x; b < RT_HANDOFF_BUCKETS; b += RT_HANDOFF_ORDER_THREADS) {
+        unsigned int above = 0u;   // entries in the buckets of more remaining work
+        for (unsigned int k = b + 1u; k < RT_HANDOFF_BUCKETS; ++k) above += total[k];
+        start[b] = above + wg_start[b];
+    }
+    __syncthreads();
+    const unsigned int i = blockIdx.x * RT_HANDOFF_ORDER_THREADS + threadIdx.x;
+    if (i < count) {
+        const unsigned long long entry = hp.queue[i];
+        hp.ordered[atomicAdd(&start[handoff_bucket(hp, entry)], 1u)] = entry;
+    }
+}
+
 }  // namespace
+
+hipError_t rt_launch_handoff_order(const rt_handoff_order_params& hp, hipStream_t st) {
+    const unsigned int wgs = (hp.max_items + RT_HANDOFF_ORDER_THREADS - 1u) / RT_HANDOFF_ORDER_THREADS;
+    const dim3 grid(wgs > 0u ? wgs : 1u);
+    hipLaunchKernelGGL(rt_handoff_hist_kernel, grid, dim3(RT_HANDOFF_ORDER_THREADS), 0, st, hp);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rt_handoff_scatter_kernel, grid, dim3(RT_HANDOFF_ORDER_THREADS), 0, st, hp);
+    return hipGetLastError();
+}
 
 hipError_t rt_launch_prior(const rt_prior_params& pp, hipStream_t st) {
     const unsigned int n = (unsigned int)pp.local_rows * (unsigned int)pp.nx;

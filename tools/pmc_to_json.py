@@ -23,7 +23,7 @@ RENDER_KERNELS = ("rt_render_staged_kernel", "rt_tier_kernel")
 
 
 def short(name):
-    for key in ("rt_tier_kernel", "rt_render_staged_kernel", "rt_rank_tiles", "rt_collect_heavy", "rt_rank_heavy", "rt_prior_kernel", "rt_prior_map_kernel", "fillBuffer", "copyBuffer"):
+    for key in ("rt_tier_kernel", "rt_render_staged_kernel", "rt_rank_tiles", "rt_collect_heavy", "rt_rank_heavy", "rt_prior_kernel", "rt_prior_map_kernel", "rt_handoff_hist_kernel", "rt_handoff_scatter_kernel", "fillBuffer", "copyBuffer"):
         if key in name:
             return key
     return name.split("(")[0][:48]

@@ -10,7 +10,7 @@ for p in paths:
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], int(r.get("Workgroup_Size", r.get("Workgroup_Size_X", 0)) or 0), int(r.get("Grid_Size", r.get("Grid_Size_X", 0)) or 0), r.get("VGPR_Count", "?"), r.get("Scratch_Size", r.get("Private_Segment_Size", "?")), r.get("LDS_Block_Size", "?")))
 rows.sort()
 def short(n):
-    for key, s in (("rt_tier_kernel", "tier"), ("rt_render_staged_kernel", "main"), ("rt_render_pixel_kernel", "pixel"), ("rt_rank_tiles", "rank_tiles"), ("rt_collect_heavy", "collect"), ("rt_rank_heavy", "rank_heavy"), ("rt_prior", "prior"), ("rt_uninterleave", "uninterleave")):
+    for key, s in (("rt_tier_kernel", "tier"), ("rt_render_staged_kernel", "main"), ("rt_render_pixel_kernel", "pixel"), ("rt_rank_tiles", "rank_tiles"), ("rt_collect_heavy", "collect"), ("rt_rank_heavy", "rank_heavy"), ("rt_prior", "prior"), ("rt_handoff_hist", "order_hist"), ("rt_handoff_scatter", "order_scat"),("rt_uninterleave", "uninterleave")):
         if key in n: return s
     return n[:40]
 # frames are separated by gaps; a frame starts at a "prior" kernel (or the first main kernel after a long gap)
