@@ -21,6 +21,7 @@
 #include "../../include/rt_abi.h"
 #include "rt_call_buffers.h"
 #include "rt_device.h"
+#include "rt_frame_plan.h"
 #include "rt_handoff_order.h"
 #include "rt_refit_host.h"
 
@@ -40,71 +41,7 @@ int g_device = -1;              // device new scenes are created on (the last rt
 int g_last_hip_error = 0;
 std::string g_detail;
 
-// Tuning knobs (rt_set_option); rt_reset_options() restores exactly these defaults, which are what ships.
-struct rt_options {
-    int kernel = RT_KERNEL_STAGED;
-    int lds_mode = -1;          // -1 = choose from the scene size
-    int steps_per_trip = 12;
-    int shade_threshold = 0;     // lanes with a finished walk that trigger stage C; 0 = 32, or 16 where the launch has less than 2.75 pixels per
-                                 // resident lane (a share of a frame: waiting for a stage's quorum costs chain time there; 1/8: 50.0 -> 47.6 ms, 1/4: 62.1 -> 60.2)
-    int wg_per_cu = 0;          // workgroups per CU of the staged kernel; 0 = per kernel family (2 x 512 lean, 3 x 256 otherwise)
-    int threads = 0;            // workgroup size of the staged kernel; 0 = what the kernel family's register budget calls for
-    int leaf_threshold = 8;     // lanes with an object test due that trigger the leaf pass (they keep walking meanwhile)
-    int diel_threshold = 2;
-    int box_threshold = 8;
-    int medium_threshold = 16;
-    int newpath_threshold = 0;   // lanes waiting for a new path before stage E runs; 0 = by kernel family: 24 spheres-only, 8 general (measured: Book-2 final 382 -> 364 ms with 8, Book-1 32.2 -> 35.1)
-    int sparse_stride = 8;      // lanes per pixel in sparse waves (64 / live lanes); 0 disables sparse waves
-    int split_samples = 16;      // samples per pixel rendered before pixels are ranked by measured cost (round 3: 16 and no presplit -- two parts; was 32 after a first look at 8)
-    int tier_auto = 1;           // size the tiers from the share of the frame this call renders (effective_tier_sizes); 0 = the knobs as set
-    int tier_kernel = 1;         // tier 1 of the list goes to the tier kernel (rt_kernel_tier.h) on a side stream; 0 = no tier 1
-    int prior = 1;               // the first part of a split frame is already ranked: on the cost prior of the calibration frame
-    int resplit_samples = 0;     // a second ranking: samples [split, resplit) run with tiers ranked on `split` samples, the rest ranked on `resplit` (0 = off)
-    int presplit_samples = 0;    // a first, shorter look: samples [presplit, split) already run with tiers ranked on it (0 = off).  Off since the
-                                 // cost prior ranks the first part: [0,16) + [16,ns) is as fast or faster than [0,8) + [8,32) + [32,ns) on every
-                                 // BASELINE frame and 10 % faster at 100 spp (profiles/r03_two_parts.log)
-    int tier1_factor_x10 = 45;   // tier 1 = heavy pixels costing >= this/10 x the mean
-    int tier1_pixels = 1536;     // heavy pixels served one per wave at a time (tier 1)
-    int cost_smooth_percent = 0;  // ranking: a pixel's cost estimate is at least this share of its dearest 4-neighbour's (0 = own cost only)
-    int tier1_depth = 3;         // ... each wave taking about this many of them, one after the other
-    int heavy_factor_x10 = 20;   // a pixel is listed ("heavy") when its cost so far is >= this/10 x the mean ...
-    int sparse_factor_x10 = 40;  // ... and goes to a sparse wave (tier 2) from this/10 x the mean; below, ordinary lanes take it first (tier 3)
-    int heavy_max_tiles = 0;     // 0 = as many as the sparse workgroups hold at once
-    int semi_stride = -1;        // lanes per pixel in the workgroups serving tier 3 (0 = ordinary lanes take tier 3 first); -1 = by kernel family:
-                                 // lean 1 -- whole waves of tier-3 pixels, which with semi_priority 1 measured 100.2 -> 94.3 ms on the headline
-                                 // (profiles/r03_priorities_whole.log) --, the others 0 (Book-2 final 352 -> 388 ms with 1, profiles/r03_general_defaults.log)
-    int sparse_priority = 3;
-    int tier_priority = 1;       // s_setprio level of the tier kernel's waves (1 instead of 3: 80.6 -> 76.3 ms on a half, 70.2 -> 62.7 on a quarter of
-                                 // the headline frame, nothing on the whole frame or an eighth: profiles/r03_share_sweep_pass2.log)
-    int semi_priority = 1;       // s_setprio level of the semi workgroups' waves (tier 3 on workgroups of its own)
-    int handoff = 1;             // tail hand-off (rt_device.h): the main kernel's last pixels are finished by a launch of the tier kernel after it
-    int handoff_scan = 1;        // ... also in scenes scanned in lockstep (lds_mode 4), which have no tier 1
-    int handoff_poll_us = 1000;  // ... looked for this often by each wave that has run out of queued work
-    int handoff_pixels = -1;     // ... when at most this many are in flight and the tile queue is dry; -1 = auto (render_impl)
-    int handoff_order = 1;       // ... served most remaining work first: the queue is ordered on the device before the tail launch (rt_handoff_order.h); 0 = push order
-    int sparse_eager = 0;
-    int sparse_work_percent = 5;  // tiers 0-2 hold at most this share of the frame's work (rays so far); dearer-than-average pixels beyond it go to tier 3
-    int sparse_wg_percent = 35;   // at most this share of the workgroups starts in sparse mode
-    int bvh_collapse = 3;        // walk array (rt_scene_create): 0 = the reference's tree as is, 1 = interior nodes that do not pay
-                                 // removed, decided from box surface areas, 2 = decided from pass counts measured on a small frame,
-                                 // 3 = as 2, and the leaves regrouped by surface-area cost if that predicts fewer box tests
-    int scan_nodes = 24;         // scenes whose walk array has at most this many nodes are scanned in lockstep (lds_mode 4); 0 = never
-    int multi_force_rccl = 0;    // rt_multi_render: go through the RCCL gather even with one device (tests the path on a one-GPU box)
-    int lpt = 1;                 // cost prepass + longest-first tile order (staged kernel, ns >= 2 * split_samples)
-    int cost_map = 1;            // ranked frames leave and use the scene's cost map (struct rt_scene); 0 = neither
-    int trace_lds = -1;          // rt_trace_rays: -1 = auto, 0 = scene through L1/L2, 1 = nodes in LDS, 2 = nodes and spheres in LDS
-    int trace_tree = 1;          // rt_trace_rays: 1 = the walk array, 0 = the reference's full tree
-    int radiance_lds = -1;       // rt_radiance_rays: as trace_lds
-    int aov_lds = -1;            // rt_render_aov: as trace_lds
-    int aov_through_lds = -1;    // rt_render_aov_through: as trace_lds
-    int denoise_lds = -1;        // rt_denoise: -1 = iterations with taps up to 4 pixels apart stage tile + halo in LDS, 0 = never,
-                                 // 1 = wherever the tile fits (taps up to 8 apart)
-    int upscale_lds = -1;        // rt_upscale: -1 (auto) and 1 = the coarse pixels a tile reaches are prepared once in LDS, 0 = every
-                                 // tap is read through L1/L2
-    int adaptive_tier = -1;      // rt_render_adaptive: -1 = a pass goes to the tier kernel when its active pixels fit the tier waves at once
-                                 // (DESIGN.md 4.8), 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit
-};
-rt_options g_opt;
+rt_options g_opt;   // the tuning knobs (rt_set_option; struct rt_options: rt_frame_plan.h)
 // bumped by every rt_set_option / rt_reset_options call: a cost map recorded under another value counts as stale (struct rt_scene)
 unsigned long long g_opt_epoch = 0;
 
@@ -208,8 +145,6 @@ struct rt_scene {
     size_t handoff_ordered_capacity = 0;
     unsigned int* d_handoff_scratch = nullptr;          // ... the ordering kernels' bucket counts
     size_t handoff_scratch_capacity = 0;
-    bool tail_ordered = false;                           // the last frame's tail launches were served from d_handoff_ordered (rt_debug_handoff_queue)
-    uint32_t tail_order_min = 0, tail_order_max = 0;
     rt_rank_info* d_rank = nullptr;               // tier sizes of the next ranked launch (written and read on the device only)
     unsigned int* d_cal_cost = nullptr;           // cost prior: rays per pixel of the calibration frame (cal_nx x cal_ny at 4 spp)
     int cal_nx = 0, cal_ny = 0;
@@ -219,13 +154,6 @@ struct rt_scene {
     // Rendering the same view again (key and both epochs equal: the map is EXACT) therefore needs no first look: the frame is
     // ranked on the map and runs as one part.  After rt_scene_set_camera / rt_scene_update_spheres without recalibration, or any
     // option call, the map is STALE: it replaces the calibration frame as the prior of part 1.  Scheduling only.
-    struct cost_map_key {
-        int32_t nx = 0, ny = 0, tile_rows = 0, tile_first = 0, tile_stride = 0, local_rows = 0, kernel_variant = 0;
-        bool operator==(const cost_map_key& o) const {
-            return nx == o.nx && ny == o.ny && tile_rows == o.tile_rows && tile_first == o.tile_first && tile_stride == o.tile_stride &&
-                   local_rows == o.local_rows && kernel_variant == o.kernel_variant;
-        }
-    };
     struct cost_map_state {
         unsigned int* d = nullptr;                // one word per local pixel, grown like the ranked buffers
         size_t capacity = 0;
@@ -233,12 +161,11 @@ struct rt_scene {
         cost_map_key key, last_key;               // of the map; of the last ranked frame (rt_debug_set_cost_map)
         bool have_last_key = false;
         unsigned long long scene_epoch = 0, opt_epoch = 0, total = 0;   // of the map; total = the sum of its words (0: not used)
-        int last_parts = 0;                       // parts of the last ranked frame
     } cost_map;
     unsigned long long scene_epoch = 0;           // bumped when the camera or a sphere changes
     hipStream_t tier_stream = nullptr;            // the tier kernel's stream (forked from / joined to the caller's stream by events)
     hipEvent_t ev_fork[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool ranked_frame = false;                    // the pending frame used the cost-aware schedule
+    frame_plan plan;                              // of the last frame render_impl enqueued (rt_frame_finish and the debug entries read it)
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool frame_pending = false;
     hipStream_t pending_stream = nullptr;
@@ -1233,13 +1160,6 @@ rt_status rt_scene_walk_info(const rt_scene* s, int32_t* nodes_reference, int32_
 }
 
 namespace {
-// What a call renders of the frame `f` describes: its rows of the partition, its grid of 8x8 tiles, and the pixels and work items
-// (64 per tile) in them.
-struct frame_geometry {
-    int local_rows, tiles_x, tiles_y;
-    size_t n_pixels;
-    uint32_t work_items;
-};
 // The words of the four failed checks.  They differ between the entry points, and tests and the Python layer match on them.
 struct frame_texts { const char *size, *large, *partition, *tiles; };
 const frame_texts RENDER_FRAME_TEXTS = {"nx, ny and ns must be positive", "frame too large", "bad row partition", "frame too large"};
@@ -1299,7 +1219,7 @@ rt_status rt_frame_finish(rt_scene* s, rt_stats* stats) {
     HIPCHK(hipMemcpy(&rays, s->d_ray_counter, sizeof(rays), hipMemcpyDeviceToHost));
     s->pending_stats.ms_render = (double)ms;
     s->pending_stats.rays = rays;
-    if (s->ranked_frame && s->d_rank) {   // how many pixels the last ranking listed as heavy (diagnostics)
+    if (s->plan.ranked && s->d_rank) {   // how many pixels the last ranking listed as heavy (diagnostics)
         rt_rank_info inf;
         HIPCHK(hipMemcpy(&inf, s->d_rank, sizeof(inf), hipMemcpyDeviceToHost));
         s->pending_stats.reserved = (int32_t)inf.heavy_items;
@@ -2284,9 +2204,9 @@ rt_status rt_debug_handoff(rt_scene* s, unsigned long long* out2) {
 rt_status rt_debug_handoff_queue(rt_scene* s, unsigned long long* entries, uint32_t* costs, unsigned long long* served, int64_t cap, int64_t* info4) {
     if (!s || !info4 || cap < 0 || (cap > 0 && (!entries || !costs || !served))) return invalid("rt_debug_handoff_queue: bad argument");
     if (s->frame_pending) return invalid("rt_debug_handoff_queue: a frame is pending (rt_frame_finish first)");
-    info4[0] = 0; info4[1] = s->tail_ordered ? 1 : 0; info4[2] = s->tail_order_min; info4[3] = s->tail_order_max;
+    info4[0] = 0; info4[1] = s->plan.tail_ordered ? 1 : 0; info4[2] = s->plan.order_min; info4[3] = s->plan.order_max;
     int64_t* const count_out = info4;
-    if (!s->d_handoff || !s->d_state || !s->ranked_frame) return RT_OK;
+    if (!s->d_handoff || !s->d_state || !s->plan.ranked) return RT_OK;
     RT_TRY(use_device(s->device));
     unsigned int pushed = 0;
     HIPCHK(hipMemcpy(&pushed, s->d_work_counter + RT_WC_PUSHED, sizeof(pushed), hipMemcpyDeviceToHost));
@@ -2295,7 +2215,7 @@ rt_status rt_debug_handoff_queue(rt_scene* s, unsigned long long* entries, uint3
     const size_t n = count < (size_t)cap ? count : (size_t)cap;
     if (n == 0) return RT_OK;
     HIPCHK(hipMemcpy(entries, s->d_handoff, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(served, s->tail_ordered ? s->d_handoff_ordered : s->d_handoff, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(served, s->plan.tail_ordered ? s->d_handoff_ordered : s->d_handoff, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     std::vector<rt_pixel_state> h_state(s->pixel_capacity);
     HIPCHK(hipMemcpy(h_state.data(), s->d_state, h_state.size() * sizeof(rt_pixel_state), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) {
@@ -2624,7 +2544,7 @@ rt_status rt_debug_cost_map(rt_scene* s, uint32_t* out, int64_t cap, int32_t* in
     const rt_scene::cost_map_state& cm = s->cost_map;
     const bool have = g_opt.cost_map && cm.valid;
     info4[0] = !have ? 0 : (cm.scene_epoch == s->scene_epoch && cm.opt_epoch == g_opt_epoch ? 1 : 2);
-    info4[1] = have ? cm.key.nx : 0; info4[2] = have ? cm.key.local_rows : 0; info4[3] = cm.last_parts;
+    info4[1] = have ? cm.key.nx : 0; info4[2] = have ? cm.key.local_rows : 0; info4[3] = s->plan.ranked_parts;
     if (!have || !out) return RT_OK;
     const long long n = (long long)cm.key.nx * cm.key.local_rows;
     if ((long long)cap < n) return invalid("rt_debug_cost_map: cap is smaller than the map (info is set)");
@@ -2654,7 +2574,7 @@ rt_status rt_debug_set_cost_map(rt_scene* s, const uint32_t* in, int64_t n) {
 rt_status rt_debug_rank_info(rt_scene* s, uint32_t* out13) {
     if (!s) return invalid("rt_debug_rank_info: null scene");
     if (!out13) return invalid("rt_debug_rank_info: null argument");
-    if (!s->ranked_frame || !s->d_rank) return invalid("rt_debug_rank_info: the scene's last frame was not ranked");
+    if (!s->plan.ranked || !s->d_rank) return invalid("rt_debug_rank_info: the scene's last frame was not ranked");
     RT_TRY(use_device(s->device));
     if (s->frame_pending) HIPCHK(hipStreamSynchronize(s->pending_stream));
     HIPCHK(hipMemcpy(out13, s->d_rank, sizeof(rt_rank_info), hipMemcpyDeviceToHost));
@@ -2662,90 +2582,36 @@ rt_status rt_debug_rank_info(rt_scene* s, uint32_t* out13) {
 }
 
 namespace {
-// The main kernel's launch shape for a launch over `n_pixels` pixels (`fp.work_items` work items): LDS residency mode, workgroup
-// shape, grid and stage quorums (written to fp).  Shared by rt_render / rt_render_window and rt_render_adaptive's passes.
-struct main_launch {
-    int kernel, lds_mode;
-    size_t lds_bytes;
-    dim3 grid, block;
-    int per_cu_resident;   // workgroups of this launch that can be resident on one CU (persistent kernels)
-    bool lean_family;
-};
-rt_status plan_main_launch(const rt_scene* s, int kernel, size_t n_pixels, rt_frame_params& fp, main_launch& ml) {
-    const int g_num_cu = g_devices[s->device].num_cu;
-    const size_t g_lds_per_cu = g_devices[s->device].lds_per_cu;
-    // LDS residency: nodes + spheres in every workgroup of a CU if they fit that many times (2 workgroups for the lean
-    // spheres-only kernels, 3 otherwise: see the workgroup shapes below), else once (one big workgroup per CU), else nodes only
-    int lds_mode = g_opt.lds_mode;
-    const bool lean_family = s->spheres_only && s->tex_level < 2;
-    const size_t budget1 = g_lds_per_cu - 2048;   // one workgroup per CU
-    // the staged kernel's image of the nodes carries a word per record behind them (the leaves' object references: rt_device.h)
-    const size_t image_bytes = s->node_bytes + (kernel == RT_KERNEL_STAGED ? (size_t)RT_WALK_PRIM_TABLE_BYTES(s->dev.n_nodes) : 0);
-    if (lds_mode < 0) {
-        // nodes + spheres where they fit a CU at all (several workgroups each with its own image, or one big workgroup
-        // sharing one: see the workgroup shapes below), else nodes only, else everything through L1 / L2
-        // (lds_mode 3 -- materials and textures in LDS too -- is selectable but measured no faster: profiles/r01_sweep34)
-        if (image_bytes + s->sphere_bytes <= budget1) lds_mode = 2;
-        else if (image_bytes <= budget1) lds_mode = 1;
-        else lds_mode = 0;
-    }
-    if (g_opt.lds_mode < 0 && kernel == RT_KERNEL_STAGED && g_opt.scan_nodes > 0 && s->dev.n_nodes <= g_opt.scan_nodes) lds_mode = 4;   // lockstep scan of a tiny scene
-    if (lds_mode >= 3 && kernel != RT_KERNEL_STAGED) lds_mode = 2;
-    if (kernel == RT_KERNEL_PIXEL) lds_mode = 0;   // the cross-check kernel reads the scene through L1/L2
-    size_t lds_bytes = 0;
-    if (lds_mode >= 1 && lds_mode <= 3) lds_bytes += image_bytes;
-    if (lds_mode >= 2 && lds_mode <= 3) lds_bytes += s->sphere_bytes;
-    if (lds_mode == 3) lds_bytes += s->shade_bytes;
-    if (lds_bytes > budget1) return invalid("requested lds_mode does not fit the CU's LDS");
-    dim3 grid, block;
-    int per_cu_resident = 1;   // workgroups of this launch that can be resident on one CU (persistent kernels)
-    if (kernel == RT_KERNEL_PIXEL) {
-        block = dim3(256);
-        grid = dim3((fp.work_items + 255u) / 256u);
-    } else {
-        // workgroup shape per kernel family (register budgets: launch bounds, rt_device.h): the lean spheres-only
-        // kernels 2 x 512 threads per CU (4 waves per SIMD), the others 3 x 256 (3 waves per SIMD; workgroups of four
-        // waves, one per SIMD -- 2 x 384 threads is the same occupancy and measured 1.4x slower on the Cornell box)
-        const bool lean = lean_family;
-        const int fam_max_threads = lean ? RT_LEAN_MAX_THREADS : RT_HEAVY_MAX_THREADS;
-        const int lds_fit = lds_bytes ? (int)(g_lds_per_cu / (lds_bytes + 512)) : 8;
-        int per_cu = g_opt.wg_per_cu > 0 ? g_opt.wg_per_cu : (lean ? 2 : 3);
-        int threads = g_opt.threads > 0 ? g_opt.threads : (lean ? 512 : 256);
-        if (g_opt.wg_per_cu <= 0 && g_opt.threads <= 0 && lds_fit < per_cu) {
-            // the scene's LDS image does not fit that many times: one workgroup with all the CU's waves shares one image
-            per_cu = 1; threads = fam_max_threads;
-        }
-        if (lds_fit < per_cu) per_cu = lds_fit < 1 ? 1 : lds_fit;
-        if (threads > fam_max_threads) threads = fam_max_threads;
-        if (threads < 64) threads = 64;
-        block = dim3((unsigned)threads);
-        unsigned want = (unsigned)(g_num_cu * per_cu);
-        const unsigned need = (fp.work_items + (unsigned)threads - 1) / (unsigned)threads;
-        grid = dim3(want < need ? want : need);
-        per_cu_resident = per_cu;
-    }
-    {   // stage quorums.  In a launch that leaves the machine mostly empty (a small share of a frame) a lane waiting for 32 others
-        // to finish their walks is waiting on the frame's critical path: the quorums are halved there.
-        const double pixels_per_lane = (double)n_pixels / ((double)g_num_cu * (double)per_cu_resident * (double)block.x);
-        // (lean family: every share of the BASELINE frames -- a whole frame is 3.3 - 3.7; the Cornell box's 1/8 share is slower with them: 172 -> 179 ms)
-        const bool latency_regime = kernel == RT_KERNEL_STAGED && lean_family && pixels_per_lane < 2.75;
-        fp.shade_threshold = g_opt.shade_threshold > 0 ? g_opt.shade_threshold : (latency_regime ? 16 : 32);
-        fp.newpath_threshold = g_opt.newpath_threshold > 0 ? g_opt.newpath_threshold : (s->spheres_only ? (latency_regime ? 12 : 24) : 8);
-    }
-    ml.kernel = kernel; ml.lds_mode = lds_mode; ml.lds_bytes = lds_bytes; ml.grid = grid; ml.block = block; ml.per_cu_resident = per_cu_resident;
-    ml.lean_family = lean_family;
+// What the plans of rt_frame_plan.h read of the scene and its device.
+plan_facts plan_facts_of(const rt_scene* s) {
+    const device_info& d = g_devices[s->device];
+    plan_facts c;
+    c.num_cu = d.num_cu; c.lds_per_cu = d.lds_per_cu;
+    c.spheres_only = s->spheres_only; c.tex_level = s->tex_level;
+    c.node_bytes = s->node_bytes; c.sphere_bytes = s->sphere_bytes; c.shade_bytes = s->shade_bytes; c.n_nodes = s->dev.n_nodes;
+    c.tier_data = s->dev.leaf_lo != nullptr;
+    c.n_slots = s->dev.n_slots; c.n_spheres = s->dev.n_spheres; c.n_materials = s->dev.n_materials; c.n_textures = s->dev.n_textures;
+    c.calibrated = s->d_cal_cost && s->cal_nx > 0 && s->cal_ny > 0;
+    c.handoff_capacity = s->handoff_capacity;
+    return c;
+}
+// The main kernel's launch shape (plan_main_launch) under the current options, its stage quorums written to fp; a refusal is the
+// caller's result.
+rt_status main_launch_of(const plan_facts& c, int kernel, size_t n_pixels, rt_frame_params& fp, main_launch& ml) {
+    const char* why = nullptr;
+    if (plan_main_launch(c, g_opt, kernel, n_pixels, fp.work_items, ml, why) != RT_OK) return invalid(why);
+    fp.shade_threshold = ml.shade_threshold; fp.newpath_threshold = ml.newpath_threshold;
     return RT_OK;
 }
-
 // kernel_variant and the launch shape as rt_stats reports them
-void stats_of_launch(const rt_scene* s, const main_launch& ml, rt_stats& out) {
-    out.kernel_variant = ml.kernel * 1000 + ml.lds_mode * 100 + s->tex_level * 10 + (s->spheres_only ? 1 : 0);
+void stats_of_launch(const plan_facts& c, const main_launch& ml, rt_stats& out) {
+    out.kernel_variant = kernel_variant_of(c, ml);
     out.workgroups = (int)ml.grid.x; out.threads_per_group = (int)ml.block.x; out.lds_bytes = (int)ml.lds_bytes;
 }
 
 // The frame parameters every entry of the main kernel sets alike, for a frame of `ns` samples per pixel: the scene's counters, the
 // frame description, the call's geometry and the scheduling knobs.  The caller adds fb, state_in / state_out, the sample window
-// and store_parked; plan_main_launch adds the stage quorums.
+// and store_parked, and the stage quorums of its main_launch.
 void fill_frame_params(const rt_scene* s, const rt_frame_desc* f, const frame_geometry& g, int ns, rt_frame_params& fp) {
     memset(&fp, 0, sizeof(fp));
     fp.ray_counter = s->d_ray_counter;
@@ -2765,70 +2631,10 @@ void fill_frame_params(const rt_scene* s, const rt_frame_desc* f, const frame_ge
     fp.box_threshold = g_opt.box_threshold; fp.medium_threshold = g_opt.medium_threshold;
 }
 
-// Room for the tier kernel (rt_kernel_tier.h) in `budget` bytes of LDS per workgroup: whether its image fits -- the scene has
-// tier data, and the leaf arrays, which the image always holds, fit --, whether spheres, materials and textures fit too
-// (rt_frame_params::tier_lds_scene), the image's size, and the grid of a tail launch.
-// The tail launch has the machine to itself: as many tier workgroups per CU as registers (launch bounds: 4 resp. 3 waves per SIMD,
-// a workgroup is one wave per SIMD) and LDS hold
-struct tier_room {
-    bool fits;
-    int lds_scene;
-    size_t lds;
-    unsigned tail_grid;
-};
-tier_room plan_tier_room(const rt_scene* s, size_t budget) {
-    tier_room r = {false, 0, 0, 0};
-    const int ns_ = s->dev.n_slots, nsph = s->dev.n_spheres, nm = s->dev.n_materials, nt = s->dev.n_textures;
-    if (s->dev.leaf_lo == nullptr || rt_tier_lds_bytes(ns_, nsph, nm, nt, false) > budget) return r;
-    r.fits = true;
-    r.lds_scene = rt_tier_lds_bytes(ns_, nsph, nm, nt, true) <= budget ? 1 : 0;
-    r.lds = rt_tier_lds_bytes(ns_, nsph, nm, nt, r.lds_scene != 0);
-    const bool lean_family = s->spheres_only && s->tex_level < 2;
-    const unsigned by_lds = (unsigned)(g_devices[s->device].lds_per_cu / (r.lds + 512));
-    const unsigned by_regs = lean_family ? 4u : 3u;
-    r.tail_grid = (unsigned)g_devices[s->device].num_cu * (by_lds < by_regs ? by_lds : by_regs);
-    if (r.tail_grid < 1u) r.tail_grid = 1u;
-    return r;
-}
 // the tier kernel of the scene's family
 hipError_t launch_tier(const rt_scene* s, const rt_frame_params& fp, dim3 grid, size_t lds, hipStream_t stream) {
     return s->spheres_only ? rt_launch_tier_spheres(s->tex_level, s->dev, fp, grid, lds, stream)
                            : rt_launch_tier_general(s->tex_level, s->need_uv, s->dev, fp, grid, lds, stream);
-}
-
-struct tier_sizes { int tier1_pixels, tier1_factor, tier1_depth, heavy_factor, sparse_factor, sparse_percent, work_percent; };
-tier_sizes effective_tier_sizes(double per_lane, bool lean_family, const rt_options& o) {
-    // Effective tier sizes by the share of the frame this call renders (1/N in an N-GPU run): the fewer pixels a
-    // rank has per lane, the more of them can afford a wave of their own.  Measured on rank-local renders of the
-    // headline frame (tools/partition_time.py).
-    int e_tier1_pixels = o.tier1_pixels, e_tier1_factor = o.tier1_factor_x10, e_tier1_depth = o.tier1_depth,
-        e_heavy_factor = o.heavy_factor_x10, e_sparse_factor = o.sparse_factor_x10, e_sparse_percent = o.sparse_wg_percent,
-        e_work_percent = o.sparse_work_percent;
-    if (o.tier_auto) {
-        // keyed by pixels per resident lane (the 1200x800 frame: 3.7 whole, 1.8 / 0.9 / 0.5 for a half, a quarter,
-        // an eighth; a quarter of 1920x1080 is 2.0): what matters is how empty the machine is, not the fraction
-        if (per_lane > 2.75) {
-            // whole frames.  Lean family: the defaults.  The others: a tier wave is a main workgroup's slot taken away and
-            // their dear pixels are many and alike (Book-2 final: the fog ball), so only the very dearest get one
-            // (Book-2 final 800x800 @ 200: 352 ms with the lean sizes, 342 ms with these, profiles/r03_general_defaults.log)
-            if (!lean_family) { e_tier1_factor = 70; e_tier1_pixels = 256; e_tier1_depth = 1; }
-        }
-        // shares, lean family: re-fitted in round 3 with the tier kernel beside the main kernel (tools/share_sweep.py on rank 0
-        // of the 1200x800 and 1920x1080 frames, profiles/r03_share_sweep_pass*.log; slowest-rank tables in DESIGN.md section 6)
-        // -- and again with the tail hand-off, which takes over what the largest tiers were there for (rank 0 of 8: 48.1 ms with
-        // round 3's first fit 16384 / 1.5x, 40.6 ms with the quarter's sizes; rank 0 of 2: 66.2 -> 62.6 ms, profiles/r03_handoff_shares.log)
-        else if (lean_family) {
-            if (per_lane > 1.375) { e_tier1_pixels = 1536; e_tier1_factor = 40; e_tier1_depth = 3; e_heavy_factor = 20; e_sparse_factor = 40; e_sparse_percent = 80; e_work_percent = 5; }
-            else { e_tier1_pixels = 8192; e_tier1_factor = 20; e_tier1_depth = 4; e_heavy_factor = 15; e_sparse_factor = 20; e_sparse_percent = 80; e_work_percent = 40; }
-        }
-        // shares, other families: round 2's sizes (Book-2 final's 1/8 share: 216 ms with these, 236 with the lean family's,
-        // 252 without a tier kernel, profiles/r03_share_sweep_final_eighth.log)
-        else if (per_lane > 1.375) { e_tier1_pixels = 4096; e_tier1_factor = 30; e_tier1_depth = 4; e_heavy_factor = 20; e_sparse_factor = 30; e_sparse_percent = 80; }
-        else if (per_lane > 0.6875) { e_tier1_pixels = 4096; e_tier1_factor = 30; e_tier1_depth = 4; e_heavy_factor = 20; e_sparse_factor = 30; e_sparse_percent = 80; e_work_percent = 20; }
-        else { e_tier1_pixels = 8192; e_tier1_factor = 20; e_tier1_depth = 4; e_heavy_factor = 15; e_sparse_factor = 15; e_sparse_percent = 80; e_work_percent = 40; }
-    }
-    if (e_sparse_factor < e_heavy_factor) e_sparse_factor = e_heavy_factor;
-    return {e_tier1_pixels, e_tier1_factor, e_tier1_depth, e_heavy_factor, e_sparse_factor, e_sparse_percent, e_work_percent};
 }
 
 // The buffers of a ranked frame (rt_scene), cached and grown together: tile costs and order, the parked pixels, the heavy list
@@ -2907,12 +2713,128 @@ rt_status rt_render_window(rt_scene* s, const rt_frame_desc* f, float* fb, int f
     return st;
 }
 
+// ---- cost-aware schedule (staged kernel): the frame is split at sample boundaries.
+// A pixel's samples are one sequential chain (one XORWOW stream) and the dearest pixels of a frame trace ~10x the
+// mean number of rays, so the frame time is bounded by a few pixels' chains, not by throughput
+// (tools/critical_chain.py: the worst 8 rows alone take as long as the whole frame).  Every part but the last parks
+// each pixel at its end (XORWOW state, colour sum, rays traced: at a sample boundary no path is in flight, so that is
+// the whole state), and every part is RANKED on what is known about the pixels' costs when it starts -- the
+// calibration frame's prior for the first part, measured rays for the later ones:
+//   * 8x8 tiles are served in descending cost (longest first);
+//   * pixels far above the mean go to a short list, dearest first: tier 1 to the tier kernel (rt_kernel_tier.h, one
+//     pixel per wave, on a stream of its own beside the main kernel), tier 2 to "sparse" main workgroups with a few live
+//     lanes per wave at raised priority -- a lane's rays advance about twice as fast in a wave with few live lanes --,
+//     tier 3 to ordinary lanes before any tile; ordinary waves skip listed pixels.
+//   * the end of every part is handed over (rt_device.h, "tail hand-off"): when the tile queue is dry and only a few thousand
+//     pixels are still in flight, the main kernel's lanes park them at their next sample boundary and a second launch of
+//     the tier kernel, right behind the main kernel on the same stream, finishes them one per wave -- the last pixels of a
+//     part are its cheapest ones started last, each still a chain of hundreds of rays at an ordinary lane's pace.
+// The ranking runs on the device (rt_rank.hip) and leaves the tier sizes in device memory, so the whole frame is
+// enqueued without a host round trip.  Scheduling only: every sample of every pixel is rendered exactly once, in
+// its pixel's stream order; frames are bit-identical with and without it (tests sweep the knobs).
+// What is decided -- the parts, what each is ranked on, the grids, the hand-off -- is plan_frame's (rt_frame_plan.h); the two
+// functions below enqueue one part of a plan.
+
+// One ranking: the cost prior of a fresh part into d_state and d_tile_cost, its sum into d_ray_counter[3] -- from the cost map,
+// pixel for pixel, or from the calibration frame --, then three small kernels that order the tiles, list the heavy pixels and
+// size the tiers for the launch described by `q` (which resumes every pixel from d_state).
+static rt_status rank_part(rt_scene* s, const frame_plan& plan, const frame_part& part, rt_frame_params& q, hipStream_t stream) {
+    if (part.ranked_on != RANK_MEASURED) {
+        const bool from_map = part.ranked_on == RANK_MAP;
+        rt_prior_params pp;
+        memset(&pp, 0, sizeof(pp));
+        pp.state = s->d_state; pp.tile_cost = s->d_tile_cost; pp.total = s->d_ray_counter + 3;
+        pp.cal_cost = from_map ? s->cost_map.d : s->d_cal_cost; pp.cal_nx = s->cal_nx; pp.cal_ny = s->cal_ny;
+        pp.nx = q.nx; pp.ny = q.ny; pp.local_rows = q.local_rows; pp.tiles_x = q.tiles_x;
+        pp.tile_rows = q.tile_rows; pp.tile_first = q.tile_first; pp.tile_stride = q.tile_stride;
+        HIPCHK(from_map ? rt_launch_prior_map(pp, stream) : rt_launch_prior(pp, stream));
+    }
+    const tier_sizes& e = plan.sizes;
+    const unsigned block = plan.ml.block.x;
+    rt_rank_params rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.state = s->d_state; rp.tile_cost = s->d_tile_cost; rp.tile_order = s->d_tile_order;
+    rp.ray_counter = part.ranked_on == RANK_MEASURED ? s->d_ray_counter : s->d_ray_counter + 3;   // the sum of the costs ranked on
+    rp.heavy_list = s->d_heavy_list; rp.heavy_pixels = s->d_heavy_pixels; rp.info = s->d_rank;
+    rp.n_pixels = (uint32_t)plan.ranked_pixels; rp.n_tiles = (uint32_t)plan.ranked_tiles; rp.heavy_cap = RT_HEAVY_CAP;
+    rp.max_grid = plan.max_grid; rp.waves_per_wg = block / 64u;
+    rp.normal_need = plan.normal_need;
+    rp.sparse_stride = plan.sparse_stride;
+    rp.semi_stride = plan.semi_stride;
+    rp.sparse_percent = e.sparse_percent;
+    rp.sparse_work_percent = e.work_percent;
+    rp.tier_possible = plan.tier_possible ? 1 : 0;
+    rp.tier1_pixels = e.tier1_pixels; rp.tier1_depth = e.tier1_depth;
+    rp.tier_wgs_cap = (int32_t)plan.tier_grid; rp.tier_waves_per_main_wg = plan.tier_waves_per_main_wg;
+    rp.nx = q.nx; rp.smooth_percent = plan.smooth_percent;
+    rp.heavy_factor = (float)e.heavy_factor / 10.0f; rp.sparse_factor = (float)e.sparse_factor / 10.0f; rp.tier1_factor = (float)e.tier1_factor / 10.0f;
+    HIPCHK(rt_launch_rank(rp, stream));
+    q.tile_order = s->d_tile_order; q.heavy_pixels = s->d_heavy_pixels; q.rank = s->d_rank;
+    return RT_OK;
+}
+
+// Part `k` of the frame: its ranking, the tier kernel (ranked parts of scenes that have tier data) on its own stream, forked from
+// and joined to the caller's stream by events, the main kernel, and the tail.  `fp`: what the frame's parts share; `state`: where
+// its pixels park (the scene's d_state, a progressive window's own).
+static rt_status launch_part(rt_scene* s, const frame_plan& plan, int k, const rt_frame_params& fp, rt_pixel_state* state, hipStream_t stream) {
+    const frame_part& part = plan.parts[k];
+    const bool last = k + 1 == plan.n_parts;
+    const size_t tier_lds = plan.room.lds;
+    rt_frame_params q = fp;
+    q.sample_begin = part.sample_begin; q.sample_end = part.sample_end; q.fresh = part.fresh ? 1 : 0;
+    q.state_in = part.reads_state ? state : nullptr; q.state_out = part.parks_state ? state : nullptr;
+    q.tile_cost = part.writes_tile_cost ? s->d_tile_cost : nullptr;
+    if (last && plan.cost_out) q.cost_out = s->cost_map.d;
+    if (part.tail) {
+        q.handoff_queue = s->d_handoff; q.handoff_cap = (uint32_t)plan.handoff_capacity; q.handoff_state = s->d_state;
+        q.handoff_poll_ticks = plan.handoff_poll_ticks; q.handoff_pixels = plan.handoff_pixels;
+    }
+    if (part.clear_before) HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, plan.ranked_tiles * sizeof(unsigned int), stream));
+    if (part.ranked_on != RANK_NONE) RT_TRY(rank_part(s, plan, part, q, stream));
+    if (part.clear_after) HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, plan.ranked_tiles * sizeof(unsigned int), stream));   // from here on: measured rays
+#ifdef RT_DIAG
+    if (last) {   // wave-end histograms of the frame's last launch only (rt_debug_wave_ends)
+        HIPCHK(hipMemsetAsync(s->d_ray_counter + RT_DIAG_T0_SLOT, 0xFF, 8, stream));
+        HIPCHK(hipMemsetAsync(s->d_ray_counter + RT_DIAG_HIST_SLOT, 0, (size_t)(2 * RT_DIAG_BINS + 7 + 2 * RT_DIAG_MAX_WAVES) * 8, stream));
+    }
+#endif
+    HIPCHK(hipMemsetAsync(s->d_work_counter, 0, RT_WORK_COUNTER_BYTES, stream));
+    if (plan.tail_ordered && part.tail) HIPCHK(hipMemsetAsync(s->d_handoff_scratch, 0, RT_HANDOFF_BUCKETS * sizeof(unsigned int), stream));
+    const int pi = k & 3;
+    if (part.tiers) {
+        HIPCHK(hipEventRecord(s->ev_fork[pi], stream));
+        HIPCHK(hipStreamWaitEvent(s->tier_stream, s->ev_fork[pi], 0));
+        HIPCHK(launch_tier(s, q, dim3(plan.tier_grid), tier_lds, s->tier_stream));
+        HIPCHK(hipEventRecord(s->ev_join[pi], s->tier_stream));
+    }
+    HIPCHK(launch_render(plan.kernel, plan.ml.lds_mode, s, q, dim3(part.grid), plan.ml.block, plan.ml.lds_bytes, stream));
+    if (part.tail) {
+        // the tail: the pixels the main kernel handed off, one per wave, on whatever the tier kernel -- which may still be
+        // running on its own stream: other pixels, other queue head -- leaves free of the machine
+        rt_frame_params t = q;
+        t.tail_mode = 1;
+        if (plan.tail_ordered) {
+            // ... served most remaining work first: the tail's waves pull from a copy of the queue ordered on the device
+            // (rt_handoff_order.h), like every other queue of the frame.
+            rt_handoff_order_params hp;
+            memset(&hp, 0, sizeof(hp));
+            hp.queue = q.handoff_queue; hp.ordered = s->d_handoff_ordered; hp.state = q.handoff_state;
+            hp.pushed = q.work_counter + RT_WC_PUSHED; hp.scratch = s->d_handoff_scratch;
+            hp.cap = q.handoff_cap; hp.min_items = plan.order_min; hp.max_items = plan.order_max;
+            hp.cost_begin = part.cost_begin; hp.sample_end = q.sample_end;
+            HIPCHK(rt_launch_handoff_order(hp, stream));
+            t.handoff_queue = s->d_handoff_ordered;
+        }
+        HIPCHK(launch_tier(s, t, dim3(plan.tail_grid), tier_lds, stream));
+    }
+    if (part.tiers) HIPCHK(hipStreamWaitEvent(stream, s->ev_join[pi], 0));
+    return RT_OK;
+}
+
 static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int fb_on_device, void* stream_v, int blocking, rt_stats* stats,
                              rt_progressive* win, int32_t win_begin, int32_t win_end) {
     if (!s || !f || !fb) return invalid("null argument");
     RT_TRY(use_device(s->device));
-    const int g_num_cu = g_devices[s->device].num_cu;
-    const size_t g_lds_per_cu = g_devices[s->device].lds_per_cu;
     // ---- check.  A progressive window averages over the samples rendered so far: win_end, which rt_render_window has checked,
     // stands for f->ns
     frame_geometry g;
@@ -2932,287 +2854,46 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     fill_frame_params(s, f, g, frame_ns, fp);
     const size_t floats = g.n_pixels * 3;
     RT_TRY(device_fb(s, fb, fb_on_device, floats, &fp.fb));
-    fp.sample_begin = 0; fp.sample_end = frame_ns;
+    fp.store_parked = win ? 1 : 0;
 
-    // ---- plan
-    const int kernel = win ? RT_KERNEL_STAGED : g_opt.kernel;   // (kernel 0 renders whole pixels only)
-    main_launch ml;
-    RT_TRY(plan_main_launch(s, kernel, g.n_pixels, fp, ml));
-    stats_of_launch(s, ml, out);
-    const int lds_mode = ml.lds_mode;
-    const bool lean_family = ml.lean_family;
-    dim3 grid = ml.grid;
-    const dim3 block = ml.block;
-    const int per_cu_resident = ml.per_cu_resident;
-
-    // ---- tier room.  The tier kernel of ranked launches (rt_kernel_tier.h): its LDS image and where its workgroups find room.
-    // Lean family: the main kernel's 4 x 104 registers per SIMD leave 96 free, so ONE tier workgroup (four waves, one per
-    // SIMD, 76 VGPRs) is resident on a CU beside a full main grid if the LDS left over holds its image.  Other families:
-    // no register room beside a full main grid; the ranking makes main workgroups leave (main_skip_wgs) and a tier workgroup
-    // has what one of them had.  The image always holds the leaf arrays; spheres, materials and textures too where all of them fit.
-    bool tier_possible = false;
-    unsigned tier_grid = 0;
-    int tier_waves_per_main_wg = 0;
-    tier_room room = {false, 0, 0, 0};   // fits: enough for the tail launches (tail hand-off) even where tier 1 is not used
-    if (kernel == RT_KERNEL_STAGED && (g_opt.tier_kernel || g_opt.handoff) && s->dev.leaf_lo != nullptr) {
-        size_t budget;
-        if (lean_family) {
-            const size_t used = (size_t)per_cu_resident * (ml.lds_bytes + 512);
-            budget = g_lds_per_cu > used + 1024 ? g_lds_per_cu - used - 1024 : 0;
-        } else {
-            // the slot of one main workgroup, shared by the tier workgroups it holds: as many as it has groups of four waves
-            const unsigned tier_wgs_per_slot = block.x / RT_TIER_THREADS > 0 ? block.x / RT_TIER_THREADS : 1u;
-            budget = (g_lds_per_cu / (size_t)per_cu_resident - 1024) / tier_wgs_per_slot;
-            tier_waves_per_main_wg = (int)(tier_wgs_per_slot * (RT_TIER_THREADS / 64));
-        }
-        room = plan_tier_room(s, budget);
-        if (room.fits) {
-            // (not for scenes scanned in lockstep, lds_mode 4: a handful of leaves, every pixel about as dear as the next -- the Cornell
-            // box's 1/8 share measured 182 ms without it and 199 ms with it, profiles/r03_general_defaults.log)
-            tier_possible = g_opt.tier_kernel && lds_mode != 4 && g_opt.tier1_pixels > 0;
-            // the tier kernel's grid is fixed before the ranking has sized the tier: what can be resident beside the main
-            // grid (one workgroup per CU) and as much again queued behind it; workgroups beyond the tier's size leave at once
-            tier_grid = lean_family ? (unsigned)(2 * g_num_cu) : (unsigned)(g_num_cu * per_cu_resident) * (unsigned)(tier_waves_per_main_wg / (RT_TIER_THREADS / 64)) / 2u;
-            if (tier_grid < 1u) tier_grid = 1u;
-        }
-    }
-    fp.tier_lds_scene = room.lds_scene;
-    const size_t tier_lds = room.lds;
-    const unsigned tail_grid = room.fits && g_opt.handoff && (lds_mode != 4 || g_opt.handoff_scan) ? room.tail_grid : 0u;
+    // ---- plan (rt_frame_plan.h): every decision of the frame, made before anything is enqueued
+    rt_scene::cost_map_state& cm = s->cost_map;
+    const cost_map_view view = {cm.valid, cm.total > 0, cm.key, cm.scene_epoch, cm.opt_epoch, s->scene_epoch, g_opt_epoch};
+    frame_plan plan;
+    const char* why = nullptr;
+    const plan_facts facts = plan_facts_of(s);
+    if (plan_frame(facts, g_opt, *f, g, {win != nullptr, win_begin, win_end}, view, plan, why) != RT_OK) return invalid(why);
+    if (!plan.ranked) plan.ranked_parts = s->plan.ranked_parts;
+    s->plan = plan;
+    fp.shade_threshold = plan.ml.shade_threshold; fp.newpath_threshold = plan.ml.newpath_threshold;
+    fp.tier_lds_scene = plan.room.lds_scene;
+    stats_of_launch(facts, plan.ml, out);
+    out.workgroups = (int)plan.parts[plan.n_parts - 1].grid;
 
     HIPCHK(hipEventRecord(s->ev_start, stream));
-    // ---- cost-aware schedule (staged kernel): the frame is split at sample boundaries.
-    // A pixel's samples are one sequential chain (one XORWOW stream) and the dearest pixels of a frame trace ~10x the
-    // mean number of rays, so the frame time is bounded by a few pixels' chains, not by throughput
-    // (tools/critical_chain.py: the worst 8 rows alone take as long as the whole frame).  Every part but the last parks
-    // each pixel at its end (XORWOW state, colour sum, rays traced: at a sample boundary no path is in flight, so that is
-    // the whole state), and every part is RANKED on what is known about the pixels' costs when it starts -- the
-    // calibration frame's prior for the first part, measured rays for the later ones:
-    //   * 8x8 tiles are served in descending cost (longest first);
-    //   * pixels far above the mean go to a short list, dearest first: tier 1 to the tier kernel (rt_kernel_tier.h, one
-    //     pixel per wave, on a stream of its own beside the main kernel), tier 2 to "sparse" main workgroups with a few live
-    //     lanes per wave at raised priority -- a lane's rays advance about twice as fast in a wave with few live lanes --,
-    //     tier 3 to ordinary lanes before any tile; ordinary waves skip listed pixels.
-    //   * the end of every part is handed over (rt_device.h, "tail hand-off"): when the tile queue is dry and only a few thousand
-    //     pixels are still in flight, the main kernel's lanes park them at their next sample boundary and a second launch of
-    //     the tier kernel, right behind the main kernel on the same stream, finishes them one per wave -- the last pixels of a
-    //     part are its cheapest ones started last, each still a chain of hundreds of rays at an ordinary lane's pace.
-    // The ranking runs on the device (rt_rank.hip) and leaves the tier sizes in device memory, so the whole frame is
-    // enqueued without a host round trip.  Scheduling only: every sample of every pixel is rendered exactly once, in
-    // its pixel's stream order; frames are bit-identical with and without it (tests sweep the knobs).
-    const size_t n_tiles = (size_t)g.tiles_x * (size_t)g.tiles_y;
-    const size_t n_pixels = g.n_pixels;
-    s->ranked_frame = false;
-    s->tail_ordered = false; s->tail_order_min = s->tail_order_max = 0;
     HIPCHK(hipMemsetAsync(s->d_ray_counter, 0, 256, stream));
-    int part_index = 0;
-    bool order_tail = false;                 // option handoff_order: set with its buffers where the hand-off is set up
-    uint32_t order_min = 0, order_max = 0;
-    // one part of the frame: the tier kernel (ranked parts of scenes that have tier data) on its own stream, forked from
-    // and joined to the caller's stream by events, and the main kernel
-    auto launch_part = [&](const rt_frame_params& q, dim3 grid_q, bool ranked) -> rt_status {
-        HIPCHK(hipMemsetAsync(s->d_work_counter, 0, RT_WORK_COUNTER_BYTES, stream));
-        if (order_tail && q.handoff_queue) HIPCHK(hipMemsetAsync(s->d_handoff_scratch, 0, RT_HANDOFF_BUCKETS * sizeof(unsigned int), stream));
-        const bool tiers = ranked && tier_possible;
-        const int pi = part_index++ & 3;
-        if (tiers) {
-            HIPCHK(hipEventRecord(s->ev_fork[pi], stream));
-            HIPCHK(hipStreamWaitEvent(s->tier_stream, s->ev_fork[pi], 0));
-            HIPCHK(launch_tier(s, q, dim3(tier_grid), tier_lds, s->tier_stream));
-            HIPCHK(hipEventRecord(s->ev_join[pi], s->tier_stream));
+    // ---- grow the buffers the plan names
+    if (plan.ranked) {
+        RT_TRY(grow_ranked_buffers(s, plan.ranked_tiles, plan.ranked_pixels));
+        if (cm.capacity < plan.cost_map_pixels) { cm.valid = false; RT_TRY(grow(cm.d, cm.capacity, plan.cost_map_pixels)); }
+        if (plan.handoff_capacity) RT_TRY(grow(s->d_handoff, s->handoff_capacity, plan.handoff_capacity));
+        if (plan.tail_ordered) {
+            RT_TRY(grow(s->d_handoff_ordered, s->handoff_ordered_capacity, plan.handoff_ordered_capacity));
+            RT_TRY(grow(s->d_handoff_scratch, s->handoff_scratch_capacity, plan.handoff_scratch_words));
         }
-        HIPCHK(launch_render(kernel, lds_mode, s, q, grid_q, block, ml.lds_bytes, stream));
-        if (q.handoff_queue) {
-            // the tail: the pixels the main kernel handed off, one per wave, on whatever the tier kernel -- which may still be
-            // running on its own stream: other pixels, other queue head -- leaves free of the machine
-            rt_frame_params t = q;
-            t.tail_mode = 1;
-            if (order_tail) {
-                // ... served most remaining work first: the tail's waves pull from a copy of the queue ordered on the device
-                // (rt_handoff_order.h), like every other queue of the frame.  The parked costs count from sample 0 except in a part
-                // that starts its pixels afresh.
-                rt_handoff_order_params hp;
-                memset(&hp, 0, sizeof(hp));
-                hp.queue = q.handoff_queue; hp.ordered = s->d_handoff_ordered; hp.state = q.handoff_state;
-                hp.pushed = q.work_counter + RT_WC_PUSHED; hp.scratch = s->d_handoff_scratch;
-                hp.cap = q.handoff_cap; hp.min_items = order_min; hp.max_items = order_max;
-                hp.cost_begin = (q.state_in && !q.fresh) ? 0 : q.sample_begin; hp.sample_end = q.sample_end;
-                HIPCHK(rt_launch_handoff_order(hp, stream));
-                t.handoff_queue = s->d_handoff_ordered;
-            }
-            HIPCHK(launch_tier(s, t, dim3(tail_grid), tier_lds, stream));
-        }
-        if (tiers) HIPCHK(hipStreamWaitEvent(stream, s->ev_join[pi], 0));
-        return RT_OK;
-    };
-    if (win) {
-        // a progressive window: one launch, every pixel resumed from (first window: started in) and parked into the caller's state,
-        // and written to fb as the average so far
-        fp.state_in = win_begin > 0 ? win->d_state : nullptr; fp.state_out = win->d_state;
-        fp.sample_begin = win_begin; fp.sample_end = win_end; fp.store_parked = 1;
-    } else if (g_opt.lpt && kernel == RT_KERNEL_STAGED && f->ns >= 2 * g_opt.split_samples && n_tiles >= 64 && n_pixels < (1ull << 31)) {
-        // ---- buffers
-        RT_TRY(grow_ranked_buffers(s, n_tiles, n_pixels));
-        // ---- the scene's cost map (struct rt_scene): exact -- this very view was rendered last, under these options --, stale, or of no use
-        rt_scene::cost_map_state& cm = s->cost_map;
-        rt_scene::cost_map_key key;
-        key.nx = f->nx; key.ny = f->ny; key.tile_rows = f->tile_rows; key.tile_first = f->tile_first; key.tile_stride = f->tile_stride;
-        key.local_rows = g.local_rows; key.kernel_variant = out.kernel_variant;
-        if (g_opt.cost_map && cm.capacity < n_pixels) { cm.valid = false; RT_TRY(grow(cm.d, cm.capacity, n_pixels)); }
-        // The map is read by the lean family and by scenes without tier 1 (scanned in lockstep, or no tier data).  Where tier workgroups
-        // take main workgroups' slots (the other families with tier 1) it is written and not read: Book-2 final 800x800 @ 200 measured
-        // 246-249 ms in two parts and 251-262 ms in one (profiles/cost_map_mi355x.jsonl): its tier-1 chain
-        // bounds the frame either way.
-        const bool map_read = lean_family || !tier_possible;
-        const bool map_usable = g_opt.cost_map && g_opt.prior && map_read && cm.valid && cm.total > 0 && cm.key == key;
-        const bool map_exact = map_usable && cm.scene_epoch == s->scene_epoch && cm.opt_epoch == g_opt_epoch;
-        if (tail_grid > 0) {
-            // tail hand-off (rt_device.h): a lane hands off at most one pixel per launch, so the queue holds one entry per resident lane
-            RT_TRY(grow(s->d_handoff, s->handoff_capacity, (size_t)g_num_cu * (size_t)per_cu_resident * (size_t)block.x));
-            fp.handoff_queue = s->d_handoff; fp.handoff_cap = (uint32_t)s->handoff_capacity; fp.handoff_state = s->d_state;
-            fp.handoff_poll_ticks = g_opt.handoff_poll_us * 100;
-            // auto: six pixels per wave of the tail launch (the headline frame: 18432 of 960000; 8192 .. 32768 measure the same,
-            // profiles/r03_handoff.log), and never more than 1/8 of the pixels (small frames and shares: the Cornell box's
-            // 1/8 share, 45000 pixels, 178 ms without, 163 ms at 4096 - 8192, 180 ms at 16384).
-            // Twelve per wave in the lean family when the tail is served most remaining work first (handoff_order): the tail ends with
-            // its longest chain, not with its queue, so a larger hand-off moves that chain to a tier wave earlier -- headline 67.3 ms at
-            // 6 in push order, 66.4 at 6 ordered, 65.0 - 65.1 at 10 - 12 ordered, 65.3 at 14, 66.1 at 16, and 67.7 at 12 in push order.
-            // The other families stay at 6: their tier waves spill and gain less on a main lane (Cornell smoke 46.6 ms at 6, 48.2 at
-            // 12; Cornell and Book-2 final measure the same at both; profiles/tail_order_mi355x.jsonl).
-            const size_t tail_waves = (size_t)tail_grid * (RT_TIER_THREADS / 64);
-            const size_t cap_px = n_pixels / 8;
-            const size_t per_wave = (g_opt.handoff_order && lean_family) ? 12 : 6;
-            fp.handoff_pixels = g_opt.handoff_pixels >= 0 ? g_opt.handoff_pixels : (int32_t)(per_wave * tail_waves < cap_px ? per_wave * tail_waves : cap_px);
-            if (g_opt.handoff_order) {
-                // ordered between two and 32 entries per tail wave, copied through outside (rt_handoff_order.h)
-                const size_t most = (size_t)RT_HANDOFF_ORDER_MAX_PER_WAVE * tail_waves;
-                order_min = (uint32_t)(RT_HANDOFF_ORDER_MIN_PER_WAVE * tail_waves);
-                order_max = (uint32_t)(most < s->handoff_capacity ? most : s->handoff_capacity);
-                RT_TRY(grow(s->d_handoff_ordered, s->handoff_ordered_capacity, s->handoff_capacity));
-                RT_TRY(grow(s->d_handoff_scratch, s->handoff_scratch_capacity, rt_handoff_order_scratch_words(order_max)));
-                order_tail = true;
-                s->tail_ordered = true; s->tail_order_min = order_min; s->tail_order_max = order_max;
-            }
-        }
-        // ---- schedule
-        // One ranking: three small kernels order the tiles, list the heavy pixels and size the tiers for the launch
-        // described by `q` (which resumes every pixel from d_state).  The grids are fixed here, before the sizes are known:
-        // the workgroups the ordinary queue needs plus the most the sparse tier may take; a workgroup that finds both its
-        // queues empty leaves at once.  `total` = the device counter holding the sum of the costs ranked on.
-        const unsigned max_grid = (unsigned)(g_num_cu * per_cu_resident);
-        const tier_sizes e = effective_tier_sizes((double)n_pixels / ((double)max_grid * (double)block.x), lean_family, g_opt);
-        auto rank_pixels = [&](rt_frame_params& q, dim3& grid_q, const unsigned long long* total) -> rt_status {
-            rt_rank_params rp;
-            memset(&rp, 0, sizeof(rp));
-            rp.state = s->d_state; rp.tile_cost = s->d_tile_cost; rp.tile_order = s->d_tile_order; rp.ray_counter = total;
-            rp.heavy_list = s->d_heavy_list; rp.heavy_pixels = s->d_heavy_pixels; rp.info = s->d_rank;
-            rp.n_pixels = (uint32_t)n_pixels; rp.n_tiles = (uint32_t)n_tiles; rp.heavy_cap = RT_HEAVY_CAP;
-            rp.max_grid = max_grid; rp.waves_per_wg = block.x / 64u;
-            rp.normal_need = (uint32_t)((q.work_items + block.x - 1) / block.x);
-            rp.sparse_stride = (g_opt.sparse_stride > 0 && block.x >= 64) ? g_opt.sparse_stride : 0;
-            rp.semi_stride = g_opt.semi_stride >= 0 ? g_opt.semi_stride : (lean_family ? 1 : 0);
-            rp.sparse_percent = e.sparse_percent;
-            rp.sparse_work_percent = e.work_percent;
-            rp.tier_possible = tier_possible ? 1 : 0;
-            rp.tier1_pixels = e.tier1_pixels; rp.tier1_depth = e.tier1_depth;
-            rp.tier_wgs_cap = (int32_t)tier_grid; rp.tier_waves_per_main_wg = tier_waves_per_main_wg;
-            rp.nx = f->nx; rp.smooth_percent = g_opt.cost_smooth_percent;
-            rp.heavy_factor = (float)e.heavy_factor / 10.0f; rp.sparse_factor = (float)e.sparse_factor / 10.0f; rp.tier1_factor = (float)e.tier1_factor / 10.0f;
-            HIPCHK(rt_launch_rank(rp, stream));
-            q.tile_order = s->d_tile_order; q.heavy_pixels = s->d_heavy_pixels; q.rank = s->d_rank;
-            unsigned total_wgs = rp.normal_need + (rp.sparse_stride > 0 ? max_grid * (unsigned)e.sparse_percent / 100u : 0u);
-            if (tier_waves_per_main_wg > 0 && tier_possible) total_wgs = max_grid;      // (workgroups that make room for the tier kernel are part of the grid)
-            if (total_wgs > max_grid) total_wgs = max_grid;
-            if (total_wgs < 1u) total_wgs = 1u;
-            grid_q = dim3(total_wgs);
-            return RT_OK;
-        };
-        // a ranked part between two others: samples [begin, end) of every pixel, resumed from and parked into d_state, with
-        // tiers ranked on the rays measured so far
-        auto ranked_part = [&](int begin, int end) -> rt_status {
-            rt_frame_params q = fp;
-            dim3 grid_q = grid;
-            q.sample_begin = begin; q.sample_end = end;
-            q.state_in = s->d_state; q.state_out = s->d_state; q.tile_cost = s->d_tile_cost;
-            RT_TRY(rank_pixels(q, grid_q, s->d_ray_counter));
-            return launch_part(q, grid_q, true);
-        };
-        // the cost prior of a fresh part into d_state and d_tile_cost, its sum into d_ray_counter[3]: from the cost map, pixel for
-        // pixel, or from the calibration frame
-        auto launch_prior = [&](bool from_map) -> rt_status {
-            rt_prior_params pp;
-            memset(&pp, 0, sizeof(pp));
-            pp.state = s->d_state; pp.tile_cost = s->d_tile_cost; pp.total = s->d_ray_counter + 3;
-            pp.cal_cost = from_map ? cm.d : s->d_cal_cost; pp.cal_nx = s->cal_nx; pp.cal_ny = s->cal_ny;
-            pp.nx = f->nx; pp.ny = f->ny; pp.local_rows = g.local_rows; pp.tiles_x = g.tiles_x;
-            pp.tile_rows = f->tile_rows; pp.tile_first = f->tile_first; pp.tile_stride = f->tile_stride;
-            HIPCHK(from_map ? rt_launch_prior_map(pp, stream) : rt_launch_prior(pp, stream));
-            return RT_OK;
-        };
-        if (map_exact) {
-            // ---- one part: the map holds what every pixel of this view cost over a whole frame, measured -- better than any first look of
-            // this frame could -- so samples [0, ns) run as a single fresh part ranked on it: no parking, no second ranking, one tail
-            HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));
-            RT_TRY(launch_prior(true));
-            fp.state_in = s->d_state; fp.fresh = 1;
-            RT_TRY(rank_pixels(fp, grid, s->d_ray_counter + 3));
-        } else {
-            // ---- part 1: samples [0, S_a); S_a = presplit_samples, or S0.  Nothing has been measured yet; with the cost prior
-            // (rt_prior_kernel: the calibration frame's rays per pixel, scaled to this frame) the part is ranked all the same,
-            // so that the dearest chains start on tier waves at sample 0 instead of running at an ordinary lane's pace.
-            const int first_end = (g_opt.presplit_samples > 0 && g_opt.presplit_samples < g_opt.split_samples) ? g_opt.presplit_samples : g_opt.split_samples;
-            HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));
-            rt_frame_params p1 = fp;
-            dim3 grid1 = grid;
-            p1.sample_end = first_end; p1.state_out = s->d_state; p1.tile_cost = s->d_tile_cost;
-            bool ranked1 = false;
-            // A stale map (the camera or a sphere has moved since, or an option was set) is still the better prior: measured, at this
-            // frame's own resolution.
-            if (map_usable || (g_opt.prior && s->d_cal_cost && s->cal_nx > 0 && s->cal_ny > 0)) {
-                RT_TRY(launch_prior(map_usable));
-                p1.state_in = s->d_state; p1.fresh = 1;
-                RT_TRY(rank_pixels(p1, grid1, s->d_ray_counter + 3));
-                HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, n_tiles * sizeof(unsigned int), stream));   // from here on: measured rays
-                ranked1 = true;
-            }
-            RT_TRY(launch_part(p1, grid1, ranked1));
-            // ---- part 1b: samples [S_a, S0), with tiers ranked on the first S_a samples.
-            if (first_end < g_opt.split_samples) RT_TRY(ranked_part(first_end, g_opt.split_samples));
-            // ---- part 1c (optional): samples [S0, S1), ranked on the first S0 samples; the last part is then ranked again on
-            // S1 samples.  A pixel's cost over 32 samples is a noisy estimate of its cost over 500 (paths through glass are
-            // heavy-tailed): pixels that look cheap and are not start late and end the frame (tools/diag_wave_ends.py).
-            int last_begin = g_opt.split_samples;
-            if (g_opt.resplit_samples > g_opt.split_samples && f->ns >= 2 * g_opt.resplit_samples) {
-                RT_TRY(ranked_part(g_opt.split_samples, g_opt.resplit_samples));
-                last_begin = g_opt.resplit_samples;
-            }
-            // ---- last part: samples [S1 or S0, ns), ranked on everything rendered so far
-            fp.state_in = s->d_state; fp.sample_begin = last_begin;
-            RT_TRY(rank_pixels(fp, grid, s->d_ray_counter));
-        }
-        out.workgroups = (int)grid.x;
-        s->ranked_frame = true;
-        cm.last_key = key; cm.have_last_key = true;
-        if (g_opt.cost_map) {   // the last part's launches leave the next map; it counts from rt_frame_finish on
-            fp.cost_out = cm.d;
-            cm.valid = false; cm.key = key; cm.scene_epoch = s->scene_epoch; cm.opt_epoch = g_opt_epoch;
-        }
+        cm.last_key = plan.key; cm.have_last_key = true;
+        if (plan.cost_out) { cm.valid = false; cm.key = plan.key; cm.scene_epoch = s->scene_epoch; cm.opt_epoch = g_opt_epoch; }
     }
-#ifdef RT_DIAG
-    // wave-end histograms of the frame's last launch only (rt_debug_wave_ends)
-    HIPCHK(hipMemsetAsync(s->d_ray_counter + RT_DIAG_T0_SLOT, 0xFF, 8, stream));
-    HIPCHK(hipMemsetAsync(s->d_ray_counter + RT_DIAG_HIST_SLOT, 0, (size_t)(2 * RT_DIAG_BINS + 7 + 2 * RT_DIAG_MAX_WAVES) * 8, stream));
-#endif
-    RT_TRY(launch_part(fp, grid, s->ranked_frame));
-    if (s->ranked_frame) s->cost_map.last_parts = part_index;
+    // ---- enqueue the parts
+    for (int k = 0; k < plan.n_parts; ++k) RT_TRY(launch_part(s, plan, k, fp, win ? win->d_state : s->d_state, stream));
     // ---- the finishing pass (rt_kernel_finish.hip): the main and tier kernels have left every local pixel's colour sum in the
     // frame, each written once by the last part's main, tier or tail launch, all of which the stream has joined; kernel 0 has
     // stored finished pixels.  Inside ev_start .. ev_stop: it is part of the frame's time.
-    if (kernel != RT_KERNEL_PIXEL) HIPCHK(rt_launch_finish(fp.fb, floats, frame_ns, f->gamma, stream));
+    if (plan.kernel != RT_KERNEL_PIXEL) HIPCHK(rt_launch_finish(fp.fb, floats, frame_ns, f->gamma, stream));
     // ---- finish
     HIPCHK(hipEventRecord(s->ev_stop, stream));
     s->frame_pending = true;
-    s->cost_map.pending = fp.cost_out != nullptr;   // only a frame that was enqueued whole makes its map count (rt_frame_finish)
+    s->cost_map.pending = plan.cost_out;   // only a frame that was enqueued whole makes its map count (rt_frame_finish)
     s->pending_stream = stream;
     s->pending_stats = out;
     if (!fb_on_device) {
@@ -3265,8 +2946,7 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
     RT_TRY(use_device(s->device));
     if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    const int num_cu = g_devices[s->device].num_cu;
-    const size_t lds_per_cu = g_devices[s->device].lds_per_cu;
+    const plan_facts facts = plan_facts_of(s);
     const int min_spp = a->min_spp, max_spp = a->max_spp;
     const size_t n_pixels = g.n_pixels;
     s->adapt_log.clear(); s->adapt_ms.clear();
@@ -3298,20 +2978,8 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
     const uint32_t all_items = g.work_items;
 
     // ---- the tier route: the tier kernel's tail mode alone on the machine, one pixel per wave, where the scene has tier data
-    // (at most 4096 leaves and 2 media) and its image fits a CU
-    const bool lean_family = s->spheres_only && s->tex_level < 2;
-    const tier_room room = plan_tier_room(s, lds_per_cu - 2048);
-    const size_t tier_waves = (size_t)room.tail_grid * (RT_TIER_THREADS / 64);
-    // auto crossover: a pass goes to the tier kernel when it has at most this many active pixels per resident tier wave.  Measured
-    // on row shares with every pixel active (tools/adaptive_sweep.py --config crossover, profiles/adaptive_mi355x.jsonl, DESIGN.md
-    // 4.8): the Cornell box's routes tie at 22 800 pixels (7.4 per wave of 3 072); on the headline scene the tier route is 1.6x
-    // faster at 60 000 pixels and still 10 % faster at 107 500 (26 per wave of 4 096), and 1.5x slower at 240 000
-    const size_t tier_per_wave = lean_family ? 32 : 6;
-    auto use_tier = [&](uint32_t active) -> bool {
-        if (!room.fits || g_opt.adaptive_tier == 0) return false;
-        if (g_opt.adaptive_tier == 1) return true;
-        return (size_t)active <= tier_per_wave * tier_waves;
-    };
+    // (at most 4096 leaves and 2 media) and its image fits a CU; which passes take it: adaptive_use_tier (rt_frame_plan.h)
+    const tier_room room = plan_tier_room(facts, facts.lds_per_cu - 2048);
 
     int pass_index = 0;
     // one render pass: samples [b, e) of `active` pixels -- every local pixel (list null), or the list / queue the last decision wrote
@@ -3319,7 +2987,7 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
         rt_frame_params q = fp;
         q.sample_begin = b; q.sample_end = e;
         q.state_in = b > 0 ? s->d_adapt_state : nullptr;
-        const bool tier = list && use_tier(active);
+        const bool tier = list && adaptive_use_tier(facts, room, g_opt, active);
         hipEvent_t* ev = s->adapt_events.data() + 2 * pass_index;
         HIPCHK(hipEventRecord(ev[0], stream));
         if (tier) {
@@ -3335,8 +3003,8 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
         } else {
             main_launch ml;
             q.work_items = list ? active : all_items;
-            RT_TRY(plan_main_launch(s, RT_KERNEL_STAGED, list ? (size_t)active : n_pixels, q, ml));
-            if (pass_index == 0) stats_of_launch(s, ml, out);
+            RT_TRY(main_launch_of(facts, RT_KERNEL_STAGED, list ? (size_t)active : n_pixels, q, ml));
+            if (pass_index == 0) stats_of_launch(facts, ml, out);
             dim3 grid = ml.grid;
             if (list) {
                 // the pixel list is tier 3 of a heavy list (rt_kernel_staged.h stage E): ordinary lanes take its entries first, and
@@ -3347,7 +3015,7 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
                 s->adapt_rank_host.sparse_stride = 1; s->adapt_rank_host.semi_stride = 1;
                 HIPCHK(hipMemcpyAsync(s->d_adapt_rank, &s->adapt_rank_host, sizeof(rt_rank_info), hipMemcpyHostToDevice, stream));
                 q.heavy_pixels = list; q.rank = s->d_adapt_rank; q.work_items = 0;
-                grid = dim3((unsigned)(num_cu * ml.per_cu_resident));
+                grid = dim3((unsigned)(facts.num_cu * ml.per_cu_resident));
             }
             HIPCHK(hipMemsetAsync(s->d_work_counter, 0, RT_WORK_COUNTER_BYTES, stream));
             HIPCHK(launch_render(RT_KERNEL_STAGED, ml.lds_mode, s, q, grid, ml.block, ml.lds_bytes, stream));
@@ -3449,8 +3117,9 @@ rt_status rt_render_variance(rt_scene* s, const rt_frame_desc* f, const rt_varia
     fp.fb = d_fb;
     fp.state_out = s->d_adapt_state;
     main_launch ml;
-    RT_TRY(plan_main_launch(s, RT_KERNEL_STAGED, n_pixels, fp, ml));
-    stats_of_launch(s, ml, out);
+    const plan_facts facts = plan_facts_of(s);
+    RT_TRY(main_launch_of(facts, RT_KERNEL_STAGED, n_pixels, fp, ml));
+    stats_of_launch(facts, ml, out);
 
     rt_variance_params vp;
     memset(&vp, 0, sizeof(vp));

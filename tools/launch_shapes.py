@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Launch shapes of every render entry point, one JSON line per case: what a change of the host code that plans the launches
 (csrc/rt_abi.hip) must leave as it is.  A wrong grid or LDS size still renders the right frame, so the test suite does not see
-it.  Per case: the launch fields of rt_stats, the 13 words of rt_debug_rank_info where the frame was ranked, whether the tail
-hand-off took pixels, the passes of an adaptive frame, and the SHA-256 of the outputs.
+it.  Per case: the launch fields of rt_stats, the 13 words of rt_debug_rank_info where the frame was ranked -- then also the number
+of parts it ran as (rt_debug_cost_map) and the counts between which its tails were ordered (rt_debug_handoff_queue) --, whether
+the tail hand-off took pixels, the passes of an adaptive frame, and the SHA-256 of the outputs.  The cases: 64x64-class frames
+through every render entry, then whole frames and row shares of the three scene families, repeat frames (exact and stale cost
+map) and one frame per option of the schedule, so that every regime of csrc/rt_frame_plan.h is reached.
 
   RT_LIB_OVERRIDE=<library of the parent commit> python tools/launch_shapes.py > parent.jsonl
   python tools/launch_shapes.py > new.jsonl && diff parent.jsonl new.jsonl
@@ -10,7 +13,8 @@ hand-off took pixels, the passes of an adaptive frame, and the SHA-256 of the ou
 RT_OPTS=key=value,... sets knobs for the whole run: with cost_map=0 (the cost map off, DESIGN.md 4.3c: the second render of a
 scene is ranked like its first) the output is that of a library from before the map.
 
-profiles/abi_refactor_launch_shapes.jsonl is this tool's output on an MI355X."""
+profiles/frame_plan_launch_shapes.jsonl is this tool's output on an MI355X (profiles/abi_refactor_launch_shapes.jsonl: its first
+half, from before the later cases were added)."""
 import ctypes as C
 import hashlib
 import json
@@ -52,7 +56,11 @@ def rank_and_handoff(ds):
     ranked = L.rt_debug_rank_info(ds._p, w.ctypes.data) == 0
     h = np.zeros(2, np.uint64)
     assert L.rt_debug_handoff(ds._p, h.ctypes.data) == 0
-    return dict(rank_info=[int(x) for x in w] if ranked else None, handoff=[bool(h[0]), bool(h[1])])
+    out = dict(rank_info=[int(x) for x in w] if ranked else None, handoff=[bool(h[0]), bool(h[1])])
+    if ranked:   # the schedule's own words: how many parts the frame ran as, and between which counts its tails were ordered
+        out["parts"] = ds.cost_map()[2]
+        out["tail_order"] = ds.handoff_queue()[3]
+    return out
 
 
 def sha(*arrays):
@@ -132,3 +140,43 @@ for scene in ("random_scene", "cornell"):
                       depth=np.ascontiguousarray(aov["depth"].reshape(64, 64)))
     emit(f"{scene} rt_denoise host", sha256=sha(den))
     ds.close()
+
+
+# ---- the regimes the 64x64-class frames above never reach (csrc/rt_frame_plan.h): whole frames, halves, quarters and eighths on
+# both sides of 2.75 / 1.375 / 0.6875 pixels per resident lane, repeat frames ranked on the cost map, and the schedule's options.
+# One frame each, into device memory.
+def one_frame(ds, hs, case, **kw):
+    f = hs.frame(**kw)
+    t = dev_buf(L.rt_frame_local_rows(C.byref(f)) * f.nx * 3)
+    _, st = ds.render(f, out=t.data_ptr())
+    emit(case, fb_sha256=sha(t.cpu().numpy()), **stats_dict(st), **rank_and_handoff(ds))
+
+
+def shifted(cam):
+    out = type(cam).from_buffer_copy(cam)
+    for k, d in enumerate((0.05, 0.03, -0.04)):
+        out.origin[k] += d
+        out.lower_left_corner[k] += d
+    return out
+
+
+for scene, nx, ny in (("random_scene", 1200, 800), ("cornell", 600, 600), ("final", 800, 800)):
+    hs = art.HostScene(scene, nx, ny, *art.default_texture(scene))
+    ds = art.DeviceScene(hs)
+    one_frame(ds, hs, f"{scene} {nx}x{ny}@32 whole", nx=nx, ny=ny, ns=32)
+    if scene == "random_scene":
+        one_frame(ds, hs, f"{scene} {nx}x{ny}@32 whole again (exact map)", nx=nx, ny=ny, ns=32)
+        ds.set_camera(shifted(hs.desc.camera))
+        one_frame(ds, hs, f"{scene} {nx}x{ny}@32 whole, camera moved (stale map)", nx=nx, ny=ny, ns=32)
+    for stride in (2, 4, 8) if scene == "random_scene" else (8,):
+        one_frame(ds, hs, f"{scene} {nx}x{ny}@32 rank 0 of {stride}", nx=nx, ny=ny, ns=32, tile_rows=4, tile_first=0, tile_stride=stride)
+    ds.close()
+
+hs = art.HostScene("random_scene", 256, 256)
+for key, value, ns in (("prior", 0, 32), ("presplit_samples", 8, 32), ("resplit_samples", 32, 64), ("handoff_order", 0, 32), ("handoff", 0, 32),
+                       ("tier_kernel", 0, 32), ("cost_map", 0, 32), ("lds_mode", 1, 32), ("wg_per_cu", 1, 32)):
+    art.set_option(key, value)
+    ds = art.DeviceScene(hs)
+    one_frame(ds, hs, f"random_scene 256x256@{ns} {key}={value}", nx=256, ny=256, ns=ns)
+    ds.close()
+    shipped_options()
