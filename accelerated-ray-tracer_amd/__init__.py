@@ -207,7 +207,7 @@ RT_ABI_SYMBOLS = ["rt_init", "rt_shutdown", "rt_strerror", "rt_last_hip_error", 
                   "rt_scene_update_instances", "rt_scene_get_instances", "rt_refit_instances", "rt_multi_update_instances",
                   "rt_debug_box_tests", "rt_reproject_instances",
                   "rt_scene_update_quads", "rt_scene_get_quads", "rt_refit_quads", "rt_multi_update_quads", "rt_debug_scene_quads",
-                  "rt_reproject_quads", "rt_debug_arith_tests", "rt_debug_math_tests", "rt_upscale"]
+                  "rt_reproject_quads", "rt_debug_arith_tests", "rt_debug_math_tests", "rt_upscale", "rt_debug_tier_room"]
 
 _rt = None
 _host = None
@@ -342,6 +342,8 @@ def rt_lib():
         if hasattr(L, "rt_debug_math_tests"):   # (likewise)
             L.rt_debug_math_tests.argtypes = [C.c_int32, C.c_int32, C.c_uint32, C.c_int64, C.c_float] + [C.c_void_p] * 5
         L.rt_scene_walk_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        if hasattr(L, "rt_debug_tier_room"):   # (absent from an older library measured through RT_LIB_OVERRIDE)
+            L.rt_debug_tier_room.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         _rt = L
     return _rt
 
@@ -1603,6 +1605,12 @@ class DeviceScene:
         a, b, x, y = C.c_int32(0), C.c_int32(0), C.c_double(0), C.c_double(0)
         _check(rt_lib().rt_scene_walk_info(self._p, C.byref(a), C.byref(b), C.byref(x), C.byref(y)), "rt_scene_walk_info")
         return {"nodes_reference": a.value, "nodes_walked": b.value, "tests_before": x.value, "tests_after": y.value}
+
+    def tier_room(self) -> dict:
+        """The tier kernel's room as rt_render plans it under the current options (rt_debug_tier_room; nothing is launched)."""
+        out = (C.c_int32 * 4)()
+        _status(rt_lib().rt_debug_tier_room(self._p, out), "rt_debug_tier_room")
+        return {"fits": bool(out[0]), "lds_scene": bool(out[1]), "lds": int(out[2]), "tail_grid": int(out[3])}
 
     def finish(self) -> RtStats:
         stats = RtStats()

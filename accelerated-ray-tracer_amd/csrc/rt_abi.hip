@@ -693,7 +693,7 @@ rt_status rt_set_option(const char* key, int value) {
     else if (k == "sparse_wg_percent") { if (value < 1 || value > 100) return invalid("sparse_wg_percent: 1..100"); g_opt.sparse_wg_percent = value; }
     else if (k == "heavy_max_tiles") { if (value < 0 || value > 4096) return invalid("heavy_max_tiles: 0..4096"); g_opt.heavy_max_tiles = value; }
     else if (k == "bvh_collapse") { if (value < 0 || value > 3) return invalid("bvh_collapse: 0..3 (read by rt_scene_create)"); g_opt.bvh_collapse = value; }
-    else if (k == "scan_nodes") { if (value < 0 || value > 64) return invalid("scan_nodes: 0..64"); g_opt.scan_nodes = value; }
+    else if (k == "scan_nodes") { if (value < 0 || value > 64) return invalid("scan_nodes: 0..64 (read by rt_scene_create and again by every render's plan)"); g_opt.scan_nodes = value; }
     else if (k == "multi_force_rccl") { if (value < 0 || value > 1) return invalid("multi_force_rccl: 0 or 1"); g_opt.multi_force_rccl = value; }
     else if (k == "cost_map") { if (value < 0 || value > 1) return invalid("cost_map: 0 or 1"); g_opt.cost_map = value; }
     else if (k == "lpt") { if (value < 0 || value > 1) return invalid("lpt: 0 or 1"); g_opt.lpt = value; }
@@ -2903,6 +2903,26 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     }
     if (blocking) return rt_frame_finish(s, stats);
     if (stats) *stats = out;
+    return RT_OK;
+}
+
+// The tier kernel's room as rt_render plans it for this scene under the current options (diagnostics, every build;
+// tests/test_kernel_matrix.py): plan_frame's tier_room -- out4 = fits, lds_scene (which instantiation of the tier kernel a tier or
+// tail launch takes), the LDS image's bytes and the tail launch's grid.  The room depends on the scene, the device and the
+// options, not on the frame, so the plan is made for the smallest ranked frame (64 tiles of 8 x 8 pixels).  Host only: no HIP
+// call, nothing launched, the scene untouched; a plan the options make impossible is refused as rt_render refuses it.
+rt_status rt_debug_tier_room(rt_scene* s, int32_t* out4) {
+    if (!s) return invalid("rt_debug_tier_room: null scene");
+    if (!out4) return invalid("rt_debug_tier_room: null argument");
+    rt_frame_desc f;
+    memset(&f, 0, sizeof(f));
+    f.nx = f.ny = 64; f.ns = 1; f.gamma = 1.0f; f.tile_rows = 64; f.tile_stride = 1;
+    const frame_geometry g = {64, 8, 8, 64u * 64u, 64u * 64u};
+    const cost_map_view view = {false, false, cost_map_key(), 0ull, 0ull, 0ull, 0ull};
+    frame_plan plan;
+    const char* why = nullptr;
+    if (plan_frame(plan_facts_of(s), g_opt, f, g, {false, 0, 0}, view, plan, why) != RT_OK) return invalid(why);
+    out4[0] = plan.room.fits ? 1 : 0; out4[1] = plan.room.lds_scene; out4[2] = (int32_t)plan.room.lds; out4[3] = (int32_t)plan.room.tail_grid;
     return RT_OK;
 }
 

@@ -1181,6 +1181,13 @@ rt_status rt_debug_prior(const uint32_t* cal_cost, int32_t cal_nx, int32_t cal_n
                          int32_t tile_stride, uint32_t* cost_out, uint32_t* tile_cost_out, uint64_t* total_out);
 rt_status rt_debug_cal_cost(rt_scene* scene, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny);
 rt_status rt_debug_rank_info(rt_scene* scene, uint32_t* out13);
+/* diagnostics of the tier kernel's room (tests/test_kernel_matrix.py): what rt_render plans for this scene under the current
+ * options -- out4 = [0] 1 when the tier kernel's LDS image fits beside the main kernel (tier 1 and the tail hand-off can run),
+ * [1] 1 when that image also holds spheres, materials and textures (which instantiation of the tier kernel runs), [2] the
+ * image's bytes, [3] the grid of a tail launch.  All 0 for a scene without tier data or with the tier kernel and the hand-off
+ * switched off.  Host only: nothing is launched and the scene is left as it was.  A null scene or a null out4 is
+ * RT_ERR_INVALID, and so is a plan rt_render would refuse (a forced lds_mode that does not fit). */
+rt_status rt_debug_tier_room(rt_scene* scene, int32_t* out4);
 /* diagnostics of the box tests (tests/test_box_tests.py): the walk's three forms of aabb::hit (rt_device_funcs.h: slab_test, the
  * reference's own; slab_test_finite, its equal for rays whose 1/d is finite; slab_test_loose, the walk loop's widened one) run
  * once, one thread per case, on caller-supplied HOST buffers: boxes bmin[n][3] / bmax[n][3], rays origins[n][3] /
@@ -1261,7 +1268,13 @@ rt_status rt_debug_set_cost_map(rt_scene* scene, const uint32_t* in, int64_t n);
 
 /* Tuning knobs (for A/B measurements; defaults are what ships).  Unknown keys
  * return RT_ERR_INVALID.  The knobs are process-wide; rt_reset_options()
- * restores every one of them to the shipped default.  None changes a pixel. */
+ * restores every one of them to the shipped default.  None changes a pixel.
+ * Two knobs are read by rt_scene_create and shape the scene it returns: "bvh_collapse" (how the walk array is planned) and
+ * "scan_nodes" (a walk array of at most that many nodes is reduced to its leaves, to be scanned in lockstep).  "scan_nodes" is
+ * read again by every render's plan, which scans an array of at most that many nodes ("lds_mode" -1) -- whatever the value
+ * was at creation, and "lds_mode" 4 scans an array of any size.  A scene created under one value and rendered under another is
+ * scanned with its interior nodes still in the array, or walked without them: such a mismatch costs box tests and never pixels
+ * (tests/test_kernel_matrix.py). */
 rt_status rt_set_option(const char* key, int value);
 rt_status rt_reset_options(void);
 
