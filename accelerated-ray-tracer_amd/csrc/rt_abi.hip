@@ -1,6 +1,8 @@
 // rt_abi.hip -- implementation of include/rt_abi.h: device bookkeeping, scene
-// validation + upload, the walk-array planner, tier data and cost prior, frame
-// launch, statistics.  The kernels are in rt_kernel_pixel.hip, rt_staged_*.hip
+// creation (what it uploads is decided in rt_scene_plan.h: the checks, the walk-array
+// planner, the regrouped hierarchies, the tier data; here: the uploads, the
+// calibration pass and the cost prior), frame launch (rt_frame_plan.h decides,
+// this file enqueues), statistics.  The kernels are in rt_kernel_pixel.hip, rt_staged_*.hip
 // (rt_kernel_staged.h), rt_tier_*.hip (rt_kernel_tier.h), rt_rank.hip and, for
 // rt_scene_update_spheres, rt_kernel_refit.hip (host half: rt_refit_host.h).
 // There is no CPU render path here or anywhere else in the
@@ -24,6 +26,7 @@
 #include "rt_frame_plan.h"
 #include "rt_handoff_order.h"
 #include "rt_refit_host.h"
+#include "rt_scene_plan.h"
 
 namespace {
 
@@ -67,19 +70,23 @@ rt_status invalid(const char* why) { g_detail = why; return RT_ERR_INVALID; }
 // 8x8 pixel tiles across `pixels` pixels or rows (the tile grid of a call is tiles_across(nx) x tiles_across(local_rows))
 inline int tiles_across(int pixels) { return (pixels + 7) / 8; }
 
-template <class T>
-rt_status upload(const T* src, size_t count, const T** dst) {
+// A device copy of `bytes` bytes in an allocation of its own, zero-filled up to the next multiple of 64 bytes.
+rt_status upload(const void* src, size_t bytes, const void** dst) {
     *dst = nullptr;
-    // always allocate at least one element so kernels never see a null array base
-    size_t bytes = (count ? count : 1) * sizeof(T);
-    bytes = (bytes + 63) & ~(size_t)63;
+    // always allocate something so kernels never see a null array base
+    const size_t room = ((bytes ? bytes : 1) + 63) & ~(size_t)63;
     void* p = nullptr;
-    HIPCHK(hipMalloc(&p, bytes));
-    HIPCHK(hipMemset(p, 0, bytes));
-    if (count) HIPCHK(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *dst = static_cast<const T*>(p);
+    HIPCHK(hipMalloc(&p, room));
+    hipError_t e = hipMemset(p, 0, room);
+    if (e == hipSuccess && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(p); HIPCHK(e); }
+    *dst = p;
     return RT_OK;
 }
+// One row of an upload table: `count` elements at `src` go to the device, where *dst points at them afterwards.
+struct array_upload { const void* src; size_t bytes; const void** dst; };
+template <class T> array_upload array_of(const T* src, size_t count, const T** dst) { return {src, count * sizeof(T), (const void**)dst}; }
+template <class T> array_upload array_of(const std::vector<T>& v, const T** dst) { return array_of(v.data(), v.size(), dst); }
 
 // Frees what the pointers hold and allocates them anew: the step every cached buffer, or group of buffers under one capacity,
 // takes when a frame needs more than it has.
@@ -113,6 +120,8 @@ struct call_memory : call_pieces {
     void guard(hipStream_t st) { stream = st; guarded = true; }
     void settled() { guarded = false; }
     hipError_t get(void** p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) all.push_back(*p); return e; }
+    void own(const void* p) { all.push_back(const_cast<void*>(p)); }                              // an allocation made elsewhere: freed with the rest
+    void disown(const void* p) { all.erase(std::remove(all.begin(), all.end(), p), all.end()); }   // one that outlives the call after all
     rt_status finish(bool wait) { if (wait) HIPCHK(hipStreamSynchronize(stream)); settled(); return RT_OK; }
 };
 
@@ -228,365 +237,6 @@ hipError_t launch_render(int kernel, int lds_mode, const rt_scene* s, const rt_f
     }
     if (s->tex_level <= 1 && !s->need_uv) return rt_launch_staged_general(lds_mode, s->dev, fp, grid, block, lds_bytes, stream);
     return rt_launch_staged_general_tex(lds_mode, s->dev, fp, grid, block, lds_bytes, stream);
-}
-
-bool simple_ref_ok(const rt_scene_desc* d, int32_t ref) {
-    if (ref < 0) return false;
-    const int k = RT_PRIM_KIND(ref), i = RT_PRIM_INDEX(ref);
-    if (k == RT_PRIM_SPHERE) return i < d->n_spheres;
-    if (k == RT_PRIM_QUAD) return i < d->n_quads;
-    if (k == RT_PRIM_BOX) return i < d->n_boxes;
-    return false;
-}
-bool solid_ref_ok(const rt_scene_desc* d, int32_t ref) {
-    if (ref < 0) return false;
-    if (RT_PRIM_KIND(ref) == RT_PRIM_INSTANCE) return RT_PRIM_INDEX(ref) < d->n_instances;
-    return simple_ref_ok(d, ref);
-}
-
-// Every index a kernel will follow is checked here, on the host, so that a
-// malformed description is an error code and never a GPU fault.
-rt_status validate(const rt_scene_desc* d, bool& spheres_only, int& tex_level, bool& need_uv) {
-    if (!d) return invalid("null scene description");
-    if (d->n_nodes < 0 || d->n_spheres < 0 || d->n_quads < 0 || d->n_boxes < 0 || d->n_instances < 0 || d->n_media < 0 ||
-        d->n_materials < 0 || d->n_textures < 0)
-        return invalid("negative count");
-    if ((d->n_nodes && !d->nodes) || (d->n_spheres && !d->spheres) || (d->n_quads && !d->quads) || (d->n_boxes && !d->boxes) ||
-        (d->n_instances && !d->instances) || (d->n_media && !d->media) || (d->n_materials && !d->materials) ||
-        (d->n_textures && !d->textures) || (d->image_bytes && !d->images))
-        return invalid("null array with non-zero count");
-    if (d->n_nodes >= (1 << 28) || d->n_spheres >= (1 << 28) || d->n_quads >= (1 << 28)) return invalid("scene too large");
-    spheres_only = true;
-    for (int i = 0; i < d->n_nodes; ++i) {
-        const rt_node& n = d->nodes[i];
-        if (n.skip <= i || n.skip > d->n_nodes) return invalid("node skip link does not move forward");
-        if (n.prim >= 0) {
-            const int k = RT_PRIM_KIND(n.prim), idx = RT_PRIM_INDEX(n.prim);
-            if (k != RT_PRIM_SPHERE) spheres_only = false;
-            if (k == RT_PRIM_MEDIUM) { if (idx >= d->n_media) return invalid("medium index out of range"); }
-            else if (!solid_ref_ok(d, n.prim)) return invalid("leaf primitive reference out of range");
-        }
-    }
-    for (int i = 0; i < d->n_spheres; ++i)
-        if (d->spheres[i].mat < 0 || d->spheres[i].mat >= d->n_materials) return invalid("sphere material out of range");
-    for (int i = 0; i < d->n_quads; ++i)
-        if (d->quads[i].mat < 0 || d->quads[i].mat >= d->n_materials) return invalid("quad material out of range");
-    for (int i = 0; i < d->n_boxes; ++i)
-        if (d->boxes[i].first_quad < 0 || d->boxes[i].first_quad + 6 > d->n_quads) return invalid("box faces out of range");
-    for (int i = 0; i < d->n_instances; ++i)
-        if (!simple_ref_ok(d, d->instances[i].child)) return invalid("instance child must be a sphere, quad or box");
-    for (int i = 0; i < d->n_media; ++i) {
-        if (!solid_ref_ok(d, d->media[i].boundary)) return invalid("medium boundary must be a sphere, quad, box or instance");
-        if (d->media[i].mat < 0 || d->media[i].mat >= d->n_materials) return invalid("medium material out of range");
-    }
-    tex_level = 0; need_uv = false;
-    for (int i = 0; i < d->n_materials; ++i) {
-        const rt_material& m = d->materials[i];
-        if (m.kind < RT_MAT_LAMBERTIAN || m.kind > RT_MAT_ISOTROPIC) return invalid("unknown material kind");
-        if (m.tex >= d->n_textures) return invalid("material texture out of range");
-        if (m.tex >= 0 && tex_level < 1) tex_level = 1;
-    }
-    for (int i = 0; i < d->n_textures; ++i) {
-        const rt_texture& t = d->textures[i];
-        if (t.kind == RT_TEX_CHECKER) {
-            // even/odd must point at later-or-earlier non-self entries that terminate: forbid checker children
-            if (t.a < 0 || t.a >= d->n_textures || t.b < 0 || t.b >= d->n_textures) return invalid("checker child out of range");
-            if (d->textures[t.a].kind == RT_TEX_CHECKER || d->textures[t.b].kind == RT_TEX_CHECKER ||
-                d->textures[t.a].kind == RT_TEX_UV_OFFSET || d->textures[t.b].kind == RT_TEX_UV_OFFSET)
-                return invalid("checker children must be plain textures");
-        } else if (t.kind == RT_TEX_IMAGE) {
-            need_uv = true; tex_level = 2;
-            if (t.a >= 0) {
-                if (t.b <= 0 || t.c <= 0) return invalid("image texture with non-positive size");
-                if ((size_t)t.a + (size_t)t.b * t.c * 3 > d->image_bytes) return invalid("image texture outside the image pool");
-            }
-        } else if (t.kind == RT_TEX_NOISE || t.kind == RT_TEX_NOODLE || t.kind == RT_TEX_FELT) {
-            tex_level = 2;
-            if (t.kind == RT_TEX_NOODLE && (t.a < 0 || t.a > 16)) return invalid("noodle texture octaves out of range");
-        } else if (t.kind == RT_TEX_UV_OFFSET) {
-            tex_level = 2; need_uv = true;
-            if (t.a < 0 || t.a >= d->n_textures) return invalid("uv_offset child out of range");
-            if (d->textures[t.a].kind == RT_TEX_UV_OFFSET || d->textures[t.a].kind == RT_TEX_CHECKER)
-                return invalid("uv_offset may wrap image, solid, noise, noodle or felt textures only");
-        } else if (t.kind != RT_TEX_SOLID) {
-            return invalid("unknown texture kind");
-        }
-    }
-    if (d->n_quads || d->n_boxes || d->n_instances || d->n_media) spheres_only = spheres_only && false;
-    return RT_OK;
-}
-
-}  // namespace
-
-namespace {
-
-// ---------------------------------------------------------------------------------------------------------------
-// "Collapse": which interior nodes of the reference's tree are worth testing.
-//
-// bvh_node::hit (bvh.cuh:95-106) reaches an object iff every ancestor box and the object's own box (its single-object
-// node, bvh.cuh:38-43) pass against the closest hit so far.  The slab test (aabb.cuh:45-61) is monotone in the box (a
-// box containing another is entered no later and left no earlier, rounding included: the same subtract-multiply on
-// ordered operands; a NaN from 0 * inf leaves a limit unconstrained for parent and child alike) and in the limit, and
-// limits only shrink during a walk.  So "the own box passes at the moment of the object test" already implies every
-// ancestor passed earlier: the interior boxes never change a result, they only save work -- and only if they fail
-// often enough.  Dropping interior node X (its children take its place in the depth-first array) removes one test per
-// visit of X and adds one failing test per direct child whenever X would have failed; with v = visits and p = passes
-// that is a saving iff p / v > 1 - 1 / k.  A median-split tree has many such nodes (the random scene: 40.1 -> 29.4 box
-// tests per ray, Cornell 14.6 -> 8.6, Book-2 final 55.1 -> 35.6).  The choice is an exact tree DP over (node, nearest
-// kept ancestor) on pass counts -- measured by kernel 0 on a small frame of the scene's own camera (bvh_collapse = 2),
-// or taken proportional to box surface area (1).  Order of the leaves, every leaf node and every box value are the
-// reference's; frames are bit-identical with the option on or off (tests/test_gpu_parity.py).
-// ---------------------------------------------------------------------------------------------------------------
-struct collapse_plan {
-    std::vector<char> keep;     // per reference node
-    double tests_before = 0, tests_after = 0;   // expected box tests per calibration ray
-};
-
-// children of interior node i in the depth-first array: i + 1, then each next sibling at the previous one's skip link
-template <class F> void for_children(const rt_node* nodes, int i, F f) {
-    for (int c = i + 1; c < nodes[i].skip; c = nodes[c].skip) f(c);
-}
-
-bool plan_collapse(const rt_node* nodes, int n, const std::vector<double>& pass, double root_visits, collapse_plan& plan) {
-    plan.keep.assign((size_t)n, 1);
-    if (n < 3 || root_visits <= 0) return false;
-    // depth of every node (= length of its ancestor chain); parents precede children in the array
-    std::vector<int> depth((size_t)n, 0), parent((size_t)n, -1);
-    int max_depth = 0;
-    for (int i = 0; i < n; ++i)
-        if (nodes[i].prim < 0) for_children(nodes, i, [&](int c) { depth[c] = depth[i] + 1; parent[c] = i; if (depth[c] > max_depth) max_depth = depth[c]; });
-    if (max_depth > 60) return false;   // a degenerate (list-like) tree: leave it alone
-    // the argument above needs a real tree (children tile their parent's range of the array) whose boxes contain their
-    // children's; a description that is anything else is walked as given
-    for (int i = 0; i < n; ++i) {
-        if (i > 0 && parent[i] < 0) return false;
-        if (nodes[i].prim >= 0) { if (nodes[i].skip != i + 1) return false; continue; }
-        int c = i + 1, kids = 0;
-        for (; c < nodes[i].skip; c = nodes[c].skip) {
-            ++kids;
-            for (int a = 0; a < 3; ++a)
-                if (!(nodes[c].bmin[a] >= nodes[i].bmin[a] && nodes[c].bmax[a] <= nodes[i].bmax[a])) return false;
-        }
-        if (c != nodes[i].skip || kids == 0) return false;
-    }
-    // cost[i][d]: fewest tests in the subtree of i per calibration run when the nearest kept ancestor is the d-th entry of
-    // i's ancestor chain (0 = "above the root": root_visits, 1.. = ancestors from the root down); visits of a node = passes
-    // of its nearest kept ancestor (a fixed-order walk has no other way to skip it)
-    std::vector<std::vector<double>> cost((size_t)n);
-    std::vector<int> chain;   // scratch
-    auto visits = [&](int i, int d) -> double {   // d-th entry of i's chain
-        if (d == 0) return root_visits;
-        int a = i;
-        for (int up = depth[i] - d + 1; up > 0; --up) a = parent[a];
-        return pass[a];
-    };
-    for (int i = n - 1; i >= 0; --i) {   // children have larger indices: reverse order is post-order enough
-        const int D = depth[i] + 1;
-        cost[i].assign((size_t)D, 0.0);
-        if (nodes[i].prim >= 0) { for (int d = 0; d < D; ++d) cost[i][d] = visits(i, d); continue; }
-        for (int d = 0; d < D; ++d) {
-            double keep = visits(i, d), drop = 0.0;
-            for_children(nodes, i, [&](int c) { keep += cost[c][(size_t)D]; drop += cost[c][(size_t)d]; });
-            cost[i][d] = keep <= drop ? keep : drop;
-        }
-    }
-    // decide top-down
-    std::vector<int> nearest((size_t)n, 0);
-    double before = 0.0;
-    for (int i = 0; i < n; ++i) before += (i == 0) ? root_visits : pass[parent[i]];
-    for (int i = 0; i < n; ++i) {
-        const int d = nearest[i];
-        bool keep = true;
-        if (nodes[i].prim < 0) {
-            double k = visits(i, d), drop = 0.0;
-            const int D = depth[i] + 1;
-            for_children(nodes, i, [&](int c) { k += cost[c][(size_t)D]; drop += cost[c][(size_t)d]; });
-            keep = k <= drop;
-            for_children(nodes, i, [&](int c) { nearest[c] = keep ? D : d; });
-        }
-        plan.keep[i] = keep ? 1 : 0;
-    }
-    plan.tests_before = before / root_visits;
-    plan.tests_after = cost[0][0] / root_visits;
-    return true;
-}
-
-// the walk array: kept nodes in the reference's depth-first order, skip links re-pointed at the next kept node
-std::vector<rt_node> build_walk_array(const rt_node* nodes, int n, const std::vector<char>& keep) {
-    std::vector<int> kept_before((size_t)n + 1, 0);
-    for (int i = 0; i < n; ++i) kept_before[i + 1] = kept_before[i] + (keep[i] ? 1 : 0);
-    std::vector<rt_node> walk;
-    walk.reserve((size_t)kept_before[n]);
-    for (int i = 0; i < n; ++i) {
-        if (!keep[i]) continue;
-        rt_node w = nodes[i];
-        w.skip = kept_before[nodes[i].skip];
-        walk.push_back(w);
-    }
-    return walk;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// "Regroup": another hierarchy over the same leaves.
-//
-// By the argument above the walk returns what the reference's returns as long as (1) the leaves -- the reference's
-// single-object nodes, with their boxes -- come in the reference's depth-first order and (2) every interior box contains
-// the boxes below it: then "a leaf's own box passes" still implies that everything above it passed, and a subtree is
-// only ever skipped when none of its leaves could have passed.  Which contiguous runs of leaves are grouped is free.  The
-// reference groups by halving (bvh.cuh:25-36), which puts a huge object (the ground sphere: a 2000-unit box) into half of
-// the top of the tree: every box above it is as large as it is and always passes.  regroup_leaves() builds a binary tree
-// over the same leaf sequence, interior boxes = the exact union (float min / max) of their leaves' boxes, in one of two
-// ways: top-down -- split [a, b) at the k that minimises area(a..k) * (k - a) + area(k..b) * (b - k) -- or bottom-up --
-// keep merging the two neighbouring groups with the smallest union, "smallest" by surface area (method 1) or by how many
-// of ~4000 rays sampled from the calibration pass meet it (method 2: the scene as this camera's paths see it).  Each goes
-// through the same calibration pass and collapse DP as the reference's tree, and whichever walk array predicts the fewest
-// box tests per ray is used (bvh_collapse = 3).
-// ---------------------------------------------------------------------------------------------------------------
-std::vector<rt_node> regroup_leaves(const rt_node* nodes, int n, int method, const std::vector<float>* sample = nullptr) {
-    std::vector<rt_node> leaves;
-    for (int i = 0; i < n; ++i) if (nodes[i].prim >= 0) leaves.push_back(nodes[i]);
-    const int m = (int)leaves.size();
-    std::vector<rt_node> out;
-    if (m == 0) return out;
-    out.reserve((size_t)(2 * m));
-    struct box { float lo[3], hi[3]; };
-    auto grow = [](box& b, const rt_node& l) { for (int a = 0; a < 3; ++a) { b.lo[a] = fminf(b.lo[a], l.bmin[a]); b.hi[a] = fmaxf(b.hi[a], l.bmax[a]); } };
-    auto area = [](const box& b) -> double {
-        const double x = fmax(0.0, (double)b.hi[0] - b.lo[0]), y = fmax(0.0, (double)b.hi[1] - b.lo[1]), z = fmax(0.0, (double)b.hi[2] - b.lo[2]);
-        return 2.0 * (x * y + y * z + x * z);
-    };
-    const box empty = {{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
-    if (method >= 1) {
-        // bottom-up: merge, again and again, the two neighbouring groups whose union has the smallest surface area (a heap
-        // of neighbour pairs with lazy deletion); the huge leaf is merged last and ends up directly under the root.
-        // method 2: "smallest" by the share of the calibration pass's sampled rays that pass the union box (each with the
-        // limit it ended with) -- the scene as this camera's paths see it -- with the surface area as the tie-break
-        const size_t n_rays = (method == 2 && sample) ? sample->size() / 7 : 0;
-        // the sample as seven arrays (origin, 1 / direction, limit) so that the loop below vectorises
-        std::vector<float> q[7];
-        for (int a = 0; a < 7; ++a) q[a].resize(n_rays);
-        for (size_t r = 0; r < n_rays; ++r) {
-            for (int a = 0; a < 3; ++a) { q[a][r] = (*sample)[r * 7 + a]; q[3 + a][r] = 1.0f / (*sample)[r * 7 + 3 + a]; }
-            q[6][r] = (*sample)[r * 7 + 6];
-        }
-        auto seen_by = [&](const box& b) -> double {
-            unsigned int hits = 0;
-            for (size_t r = 0; r < n_rays; ++r) {
-                float t0 = 0.001f, t1 = q[6][r];
-                for (int a = 0; a < 3; ++a) {
-                    const float x = (b.lo[a] - q[a][r]) * q[3 + a][r], y = (b.hi[a] - q[a][r]) * q[3 + a][r];
-                    const float lo_t = x < y ? x : y, hi_t = x < y ? y : x;
-                    t0 = lo_t > t0 ? lo_t : t0;
-                    t1 = hi_t < t1 ? hi_t : t1;
-                }
-                hits += (t1 <= t0) ? 0u : 1u;
-            }
-            return (double)hits;
-        };
-        struct group { box b; int left, right, leaf, prev, next, count; bool alive; };
-        std::vector<group> g((size_t)m);
-        for (int i = 0; i < m; ++i) {
-            g[(size_t)i].b = empty; grow(g[(size_t)i].b, leaves[(size_t)i]);
-            g[(size_t)i].left = g[(size_t)i].right = -1; g[(size_t)i].leaf = i; g[(size_t)i].prev = i - 1; g[(size_t)i].next = i + 1 < m ? i + 1 : -1;
-            g[(size_t)i].count = 1; g[(size_t)i].alive = true;
-        }
-        auto unite = [](const box& x, const box& y) { box u = x; for (int a = 0; a < 3; ++a) { u.lo[a] = fminf(u.lo[a], y.lo[a]); u.hi[a] = fmaxf(u.hi[a], y.hi[a]); } return u; };
-        struct pair_key { double area; int i, j; };
-        auto worse = [](const pair_key& x, const pair_key& y) { return x.area > y.area || (x.area == y.area && x.i > y.i); };
-        std::vector<pair_key> heap;
-        auto push = [&](int i, int j) {
-            const box ub = unite(g[(size_t)i].b, g[(size_t)j].b);
-            double ar = area(ub);
-            if (!std::isfinite(ar)) ar = DBL_MAX;
-            else if (n_rays) ar = seen_by(ub) + ar / (ar + 1.0);      // rays first, area (squashed below one ray) second
-            heap.push_back({ar, i, j});
-            std::push_heap(heap.begin(), heap.end(), worse);
-        };
-        for (int i = 0; i + 1 < m; ++i) push(i, i + 1);
-        int root = m - 1;
-        while (!heap.empty()) {
-            std::pop_heap(heap.begin(), heap.end(), worse);
-            const pair_key k = heap.back();
-            heap.pop_back();
-            if (!g[(size_t)k.i].alive || !g[(size_t)k.j].alive) continue;
-            group u;
-            u.b = unite(g[(size_t)k.i].b, g[(size_t)k.j].b); u.left = k.i; u.right = k.j; u.leaf = -1;
-            u.prev = g[(size_t)k.i].prev; u.next = g[(size_t)k.j].next; u.count = g[(size_t)k.i].count + g[(size_t)k.j].count; u.alive = true;
-            g[(size_t)k.i].alive = g[(size_t)k.j].alive = false;
-            const int id = (int)g.size();
-            g.push_back(u);
-            root = id;
-            if (u.prev >= 0) { g[(size_t)u.prev].next = id; push(u.prev, id); }
-            if (u.next >= 0) { g[(size_t)u.next].prev = id; push(id, u.next); }
-        }
-        // emit depth-first
-        std::vector<int> todo2;
-        todo2.push_back(root);
-        std::vector<std::pair<int, int>> open2;
-        while (!todo2.empty()) {
-            const int id = todo2.back();
-            todo2.pop_back();
-            if (g[(size_t)id].leaf >= 0) {
-                rt_node l = leaves[(size_t)g[(size_t)id].leaf];
-                l.skip = (int32_t)out.size() + 1;
-                out.push_back(l);
-                for (auto& o : open2) --o.second;
-                while (!open2.empty() && open2.back().second == 0) { out[(size_t)open2.back().first].skip = (int32_t)out.size(); open2.pop_back(); }
-                continue;
-            }
-            rt_node nd;
-            for (int a = 0; a < 3; ++a) { nd.bmin[a] = g[(size_t)id].b.lo[a]; nd.bmax[a] = g[(size_t)id].b.hi[a]; }
-            nd.prim = -1; nd.skip = 0;
-            open2.push_back({(int)out.size(), g[(size_t)id].count});
-            out.push_back(nd);
-            todo2.push_back(g[(size_t)id].right);
-            todo2.push_back(g[(size_t)id].left);
-        }
-        return out;
-    }
-    std::vector<double> right_area((size_t)m + 1);
-    // explicit stack: (a, b) ranges in depth-first order; the interior node's skip link is patched when its range ends
-    struct item { int a, b; };
-    std::vector<item> todo;
-    todo.push_back({0, m});
-    std::vector<std::pair<int, int>> open;   // (index of an interior node, number of leaves still to be emitted under it)
-    auto leaf_done = [&]() {
-        // every enclosing interior node has one leaf fewer to wait for; those that are complete end here
-        for (auto& o : open) --o.second;
-        while (!open.empty() && open.back().second == 0) { out[(size_t)open.back().first].skip = (int32_t)out.size(); open.pop_back(); }
-    };
-    while (!todo.empty()) {
-        const item it = todo.back();
-        todo.pop_back();
-        if (it.b - it.a == 1) {
-            rt_node l = leaves[(size_t)it.a];
-            l.skip = (int32_t)out.size() + 1;
-            out.push_back(l);
-            leaf_done();
-            continue;
-        }
-        box all = empty;
-        for (int k = it.a; k < it.b; ++k) grow(all, leaves[(size_t)k]);
-        // areas of the right parts [k, b), then sweep the left part
-        box r = empty;
-        for (int k = it.b - 1; k > it.a; --k) { grow(r, leaves[(size_t)k]); right_area[(size_t)k] = area(r); }
-        box l = empty;
-        int best_k = (it.a + it.b) / 2;
-        double best = -1.0;
-        for (int k = it.a + 1; k < it.b; ++k) {
-            grow(l, leaves[(size_t)k - 1]);
-            const double c = area(l) * (double)(k - it.a) + right_area[(size_t)k] * (double)(it.b - k);
-            if (std::isfinite(c) && (best < 0.0 || c < best)) { best = c; best_k = k; }
-        }
-        rt_node nd;
-        for (int a = 0; a < 3; ++a) { nd.bmin[a] = all.lo[a]; nd.bmax[a] = all.hi[a]; }
-        nd.prim = -1; nd.skip = 0;
-        open.push_back({(int)out.size(), it.b - it.a});
-        out.push_back(nd);
-        todo.push_back({best_k, it.b});      // right part second
-        todo.push_back({it.a, best_k});      // left part first
-    }
-    return out;
 }
 
 }  // namespace
@@ -746,9 +396,30 @@ rt_status rt_scene_destroy(rt_scene* s) {
 }
 
 namespace {
-// Pass counts of the reference's nodes on a small frame through the scene's own camera (kernel 0 with its counters on).
-// keep_cost: the pass's per-pixel ray counts stay in the scene as the cost prior of ranked first parts (rt_prior_kernel)
-rt_status measure_pass_counts(rt_scene* s, const rt_node* d_tree, int n_tree, std::vector<double>& pass, double& rays, std::vector<float>* sample = nullptr, uint32_t sample_stride = 0, bool keep_cost = false) {
+// the rows of an upload table in their order, each a scene's allocation from then on (rt_scene_destroy frees it)
+rt_status upload_arrays(rt_scene* s, std::initializer_list<array_upload> table) {
+    for (const array_upload& u : table) {
+        RT_TRY(upload(u.src, u.bytes, u.dst));
+        s->allocs.push_back(const_cast<void*>(*u.dst));
+    }
+    return RT_OK;
+}
+
+// The calibration pass: a small frame through the scene's own camera by kernel 0 with its counters on, which walks `d_tree`
+// (n_tree nodes in the device's encoding) in the place of the reference's tree.
+struct calibration_request {
+    const rt_node* d_tree;
+    int n_tree;
+    uint32_t sample_stride;   // > 0: every sample_stride-th ray of the pass is kept (the caller knows how many there will be and keeps that
+                              // below the capacity, so the SET of sampled rays does not depend on the order the lanes get there)
+    bool keep_cost;           // the pass's per-pixel ray counts stay in the scene as the cost prior of ranked first parts (rt_prior_kernel)
+};
+struct calibration_result {
+    std::vector<double> pass;    // per node: the box tests it passed
+    double rays = 0.0;
+    std::vector<float> sample;   // seven floats per kept ray: origin, direction, the limit it ended with
+};
+rt_status measure_pass_counts(rt_scene* s, const calibration_request& rq, calibration_result& out) {
     const rt_camera& c = s->dev.camera;
     const double hw = sqrt((double)c.horizontal[0] * c.horizontal[0] + (double)c.horizontal[1] * c.horizontal[1] + (double)c.horizontal[2] * c.horizontal[2]);
     const double vh = sqrt((double)c.vertical[0] * c.vertical[0] + (double)c.vertical[1] * c.vertical[1] + (double)c.vertical[2] * c.vertical[2]);
@@ -757,200 +428,117 @@ rt_status measure_pass_counts(rt_scene* s, const rt_node* d_tree, int n_tree, st
     int nx = aspect >= 1.0 ? 256 : (int)(256 * aspect + 0.5), ny = aspect >= 1.0 ? (int)(256 / aspect + 0.5) : 256;
     if (nx < 8) nx = 8;
     if (ny < 8) ny = 8;
-    const int n = n_tree;
+    const size_t n = (size_t)rq.n_tree;
     rt_scene_dev dev = s->dev;
-    dev.nodes_ref = d_tree; dev.n_nodes_ref = n_tree;          // the tree kernel 0 walks in this pass
-    unsigned int* d_pass = nullptr;
-    unsigned int* d_cost = nullptr;
-    float* d_fb = nullptr;
-    HIPCHK(hipMalloc((void**)&d_pass, (size_t)n * sizeof(unsigned int)));
-    hipError_t e = hipMalloc((void**)&d_fb, (size_t)nx * ny * 3 * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(d_pass); HIPCHK(e); }
-    if (keep_cost && hipMalloc((void**)&d_cost, (size_t)nx * ny * sizeof(unsigned int)) != hipSuccess) d_cost = nullptr;   // no prior then
+    dev.nodes_ref = rq.d_tree; dev.n_nodes_ref = rq.n_tree;
+    enum { SAMPLE_CAP = 8192 };
+    call_memory mem;          // the pass runs on the null stream and is waited for below
+    mem.guard(nullptr);
+    unsigned int *d_pass = nullptr, *d_cost = nullptr;
+    float *d_fb = nullptr, *d_sample = nullptr;
+    HIPCHK(mem.get((void**)&d_pass, n * sizeof(unsigned int)));
+    HIPCHK(mem.get((void**)&d_fb, (size_t)nx * ny * 3 * sizeof(float)));
+    if (rq.keep_cost && mem.get((void**)&d_cost, (size_t)nx * ny * sizeof(unsigned int)) != hipSuccess) d_cost = nullptr;   // no prior then
+    if (rq.sample_stride > 0 && mem.get((void**)&d_sample, (size_t)SAMPLE_CAP * 7 * sizeof(float)) != hipSuccess) d_sample = nullptr;   // no sample then
     rt_frame_params fp;
     memset(&fp, 0, sizeof(fp));
     fp.fb = d_fb; fp.ray_counter = s->d_ray_counter; fp.work_counter = s->d_work_counter; fp.node_pass = d_pass; fp.pixel_cost = d_cost;
-    fp.node_pass_lds = (size_t)n * sizeof(unsigned int) <= 48u * 1024u ? 1 : 0;
+    fp.node_pass_lds = n * sizeof(unsigned int) <= 48u * 1024u ? 1 : 0;
     fp.seed_base = 1984; fp.nx = nx; fp.ny = ny; fp.ns = 4; fp.gamma = 1.0f;
     fp.tile_rows = ny; fp.tile_first = 0; fp.tile_stride = 1; fp.local_rows = ny;
     fp.tiles_x = tiles_across(nx);
     fp.work_items = (uint32_t)fp.tiles_x * (uint32_t)tiles_across(ny) * 64u;
     fp.sample_begin = 0; fp.sample_end = fp.ns;
-    rt_status st = RT_OK;
-    std::vector<unsigned int> h((size_t)n);
+    if (d_sample) { fp.ray_sample = d_sample; fp.ray_sample_cap = SAMPLE_CAP; fp.ray_sample_stride = rq.sample_stride; }
+    std::vector<unsigned int> h(n);
     unsigned long long r = 0;
-    enum { SAMPLE_CAP = 8192 };
-    float* d_sample = nullptr;
-    if (sample && sample_stride > 0) {
-        // every sample_stride-th ray of the pass (the caller knows how many there will be and keeps that below the
-        // capacity, so the SET of sampled rays does not depend on the order the lanes get there)
-        if (hipMalloc((void**)&d_sample, (size_t)SAMPLE_CAP * 7 * sizeof(float)) == hipSuccess) {
-            fp.ray_sample = d_sample; fp.ray_sample_cap = SAMPLE_CAP; fp.ray_sample_stride = sample_stride;
-        }
-    }
-    do {
-        if ((e = hipMemset(d_pass, 0, (size_t)n * sizeof(unsigned int))) != hipSuccess) break;
-        if ((e = hipMemset(s->d_ray_counter, 0, RT_COUNTER_BYTES)) != hipSuccess) break;
-        if ((e = rt_launch_pixel(s->spheres_only, s->tex_level, s->need_uv, dev, fp, dim3((fp.work_items + 255u) / 256u), dim3(256), nullptr)) != hipSuccess) break;
-        if ((e = hipDeviceSynchronize()) != hipSuccess) break;
-        if ((e = hipMemcpy(h.data(), d_pass, (size_t)n * sizeof(unsigned int), hipMemcpyDeviceToHost)) != hipSuccess) break;
-        if ((e = hipMemcpy(&r, s->d_ray_counter, sizeof(r), hipMemcpyDeviceToHost)) != hipSuccess) break;
+    const hipError_t e = [&]() -> hipError_t {
+        hipError_t e;
+        if ((e = hipMemset(d_pass, 0, n * sizeof(unsigned int))) != hipSuccess) return e;
+        if ((e = hipMemset(s->d_ray_counter, 0, RT_COUNTER_BYTES)) != hipSuccess) return e;
+        if ((e = rt_launch_pixel(s->spheres_only, s->tex_level, s->need_uv, dev, fp, dim3((fp.work_items + 255u) / 256u), dim3(256), nullptr)) != hipSuccess) return e;
+        if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+        if ((e = hipMemcpy(h.data(), d_pass, n * sizeof(unsigned int), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+        if ((e = hipMemcpy(&r, s->d_ray_counter, sizeof(r), hipMemcpyDeviceToHost)) != hipSuccess) return e;
         if (d_sample) {
             unsigned long long taken = 0;
-            if ((e = hipMemcpy(&taken, s->d_ray_counter + 2, sizeof(taken), hipMemcpyDeviceToHost)) != hipSuccess) break;
+            if ((e = hipMemcpy(&taken, s->d_ray_counter + 2, sizeof(taken), hipMemcpyDeviceToHost)) != hipSuccess) return e;
             if (taken > SAMPLE_CAP) taken = SAMPLE_CAP;
-            sample->resize((size_t)taken * 7);
-            if (taken && (e = hipMemcpy(sample->data(), d_sample, (size_t)taken * 7 * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) break;
+            out.sample.resize((size_t)taken * 7);
+            if (taken && (e = hipMemcpy(out.sample.data(), d_sample, (size_t)taken * 7 * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return e;
         }
-    } while (0);
-    (void)hipFree(d_pass); (void)hipFree(d_fb);
-    if (d_sample) (void)hipFree(d_sample);
-    if (d_cost) {
-        if (e == hipSuccess) { if (s->d_cal_cost) (void)hipFree(s->d_cal_cost); s->d_cal_cost = d_cost; s->cal_nx = nx; s->cal_ny = ny; }
-        else (void)hipFree(d_cost);
+        return hipSuccess;
+    }();
+    if (e != hipSuccess) { g_last_hip_error = (int)e; g_detail = std::string("calibration pass: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+    mem.settled();
+    if (d_cost) {   // the scene's prior from now on; the one it had goes with this call's memory
+        if (s->d_cal_cost) mem.own(s->d_cal_cost);
+        mem.disown(d_cost);
+        s->d_cal_cost = d_cost; s->cal_nx = nx; s->cal_ny = ny;
     }
-    if (e != hipSuccess) { g_last_hip_error = (int)e; g_detail = std::string("calibration pass: ") + hipGetErrorString(e); st = RT_ERR_HIP; }
-    pass.assign((size_t)n, 0.0);
-    for (int i = 0; i < n; ++i) pass[i] = (double)h[i];
-    rays = (double)r;
-    return st;
+    out.pass.assign(h.begin(), h.end());
+    out.rays = (double)r;
+    return RT_OK;
+}
+// the cost half of the calibration alone, for a scene that kept a prior at creation (one that kept none gets none: a fresh scene
+// would have none either): the pass on the reference's tree with keep_cost, its pass counts dropped
+rt_status recalibrate_cost(rt_scene* s) {
+    if (!s->d_cal_cost) return RT_OK;
+    calibration_result dropped;
+    return measure_pass_counts(s, {s->dev.nodes_ref, s->dev.n_nodes_ref, 0, true}, dropped);
 }
 
-// a node array in the device's link encoding (rt_device.h, RT_NODE_SKIP)
-void device_nodes(const rt_node* nodes, size_t n, std::vector<rt_node>& out) {
-    out.assign(nodes, nodes + n);
-    for (size_t i = 0; i < n; ++i) {
-        out[i].skip = ~out[i].skip;
-        if (out[i].prim < 0) out[i].prim = ~(int32_t)(i + 1);
-    }
-}
-
-// Tier data (rt_kernel_tier.h): the scene's leaves -- the reference's single-object nodes, in its depth-first order, which
-// every walk array keeps -- as two float4 arrays padded to whole 64-leaf slots, and per slot the union of its boxes.  A scene
-// with more than 64 slots (one lane tests one slot's union) or more than two constant_medium leaves gets none: it renders
-// without a tier kernel.
+// uploads the tier data (rt_scene_plan.h) and points dev at them; a scene that gets none keeps the null arrays
 rt_status build_tier_data(rt_scene* s, const rt_scene_desc* d) {
-    s->dev.leaf_lo = s->dev.leaf_hi = nullptr; s->dev.slot_ranges = nullptr;
-    s->dev.n_leaves = s->dev.n_slots = s->dev.n_media_leaves = 0;
-    s->dev.media_ord[0] = s->dev.media_ord[1] = 0x7FFFFFFF;
-    std::vector<const rt_node*> leaves;
-    for (int i = 0; i < d->n_nodes; ++i) if (d->nodes[i].prim >= 0) leaves.push_back(&d->nodes[i]);
-    const int m = (int)leaves.size();
-    if (m == 0 || m > 64 * 64) return RT_OK;
-    int media = 0, media_ord[2] = {0x7FFFFFFF, 0x7FFFFFFF};
-    for (int q = 0; q < m; ++q)
-        if (RT_PRIM_KIND(leaves[q]->prim) == RT_PRIM_MEDIUM) { if (media < 2) media_ord[media] = q; ++media; }
-    if (media > 2) return RT_OK;
-    const int slots = (m + 63) / 64;
-    std::vector<float> lo((size_t)slots * 64 * 4), hi((size_t)slots * 64 * 4), ranges((size_t)slots * 8, 0.0f);
-    for (int k = 0; k < slots; ++k) {
-        float rl[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, rh[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-        for (int l = 0; l < 64; ++l) {
-            const int q = k * 64 + l;
-            float* a = &lo[(size_t)q * 4];
-            float* b = &hi[(size_t)q * 4];
-            // lo.w = what a lane tests: the leaf's sphere or quad, for a box (compound6, quad.cuh:124-139) its FIRST face, for an
-            // instance the same of its child; a medium stays itself.  hi.w = instance index + 1 (0 = none) | bit 30: "six faces
-            // from lo.w on" (rt_kernel_tier.h shares those out over six lanes)
-            int32_t prim = -1, xw = 0;
-            if (q < m) {
-                for (int c = 0; c < 3; ++c) { a[c] = leaves[q]->bmin[c]; b[c] = leaves[q]->bmax[c]; rl[c] = fminf(rl[c], a[c]); rh[c] = fmaxf(rh[c], b[c]); }
-                prim = leaves[q]->prim;
-                if (RT_PRIM_KIND(prim) == RT_PRIM_INSTANCE) {
-                    const int idx = RT_PRIM_INDEX(prim);
-                    if (idx >= d->n_instances || idx >= (1 << 29)) return RT_OK;   // (rt_scene_create has validated the refs; no tier data otherwise)
-                    xw = idx + 1;
-                    prim = d->instances[idx].child;
-                }
-                if (RT_PRIM_KIND(prim) == RT_PRIM_BOX) {
-                    const int idx = RT_PRIM_INDEX(prim);
-                    if (idx >= d->n_boxes) return RT_OK;
-                    prim = RT_PRIM_REF(RT_PRIM_QUAD, d->boxes[idx].first_quad & 0x3FFFFFFF);
-                    xw |= 1 << 30;
-                }
-            } else {
-                for (int c = 0; c < 3; ++c) { a[c] = 0.0f; b[c] = 0.0f; }
-            }
-            memcpy(&a[3], &prim, 4);
-            memcpy(&b[3], &xw, 4);
-        }
-        for (int c = 0; c < 3; ++c) { ranges[(size_t)k * 8 + c] = rl[c]; ranges[(size_t)k * 8 + 3 + c] = rh[c]; }
-    }
-    const float* d_lo = nullptr; const float* d_hi = nullptr; const float* d_ranges = nullptr;
-    RT_TRY(upload(lo.data(), lo.size(), &d_lo));
-    s->allocs.push_back(const_cast<float*>(d_lo));
-    RT_TRY(upload(hi.data(), hi.size(), &d_hi));
-    s->allocs.push_back(const_cast<float*>(d_hi));
-    RT_TRY(upload(ranges.data(), ranges.size(), &d_ranges));
-    s->allocs.push_back(const_cast<float*>(d_ranges));
+    const rt_scene_plan::tier_data t = rt_scene_plan::plan_tier_data(d);
+    const float *d_lo = nullptr, *d_hi = nullptr, *d_ranges = nullptr;
+    if (t.present) RT_TRY(upload_arrays(s, {array_of(t.lo, &d_lo), array_of(t.hi, &d_hi), array_of(t.ranges, &d_ranges)}));
     s->dev.leaf_lo = reinterpret_cast<const float4*>(d_lo); s->dev.leaf_hi = reinterpret_cast<const float4*>(d_hi); s->dev.slot_ranges = d_ranges;
-    s->dev.n_leaves = m; s->dev.n_slots = slots; s->dev.n_media_leaves = media;
-    s->dev.media_ord[0] = media_ord[0]; s->dev.media_ord[1] = media_ord[1];
+    s->dev.n_leaves = t.n_leaves; s->dev.n_slots = t.n_slots; s->dev.n_media_leaves = t.n_media_leaves;
+    s->dev.media_ord[0] = t.media_ord[0]; s->dev.media_ord[1] = t.media_ord[1];
     return RT_OK;
 }
 
-// A walk array this small is not walked but scanned in lockstep (lds_mode 4): every lane of a wave steps through every node
-// whatever its own boxes said, so an interior node can only cost.  The leaves alone, in their order, are the array then (the
-// Cornell box: 11 -> 10 nodes).  Returns whether `walk` was replaced.
-bool leaves_only_if_scanned(const rt_node* src, int m, std::vector<rt_node>& walk) {
-    if (g_opt.scan_nodes <= 0 || m > g_opt.scan_nodes) return false;
-    std::vector<rt_node> leaves;
-    for (int i = 0; i < m; ++i)
-        if (src[i].prim >= 0) { rt_node w = src[i]; w.skip = (int32_t)leaves.size() + 1; leaves.push_back(w); }
-    if (leaves.empty() || (int)leaves.size() >= m) return false;
-    walk.swap(leaves);
-    return true;
-}
-
-// builds the walk array (see "Collapse" above) and points dev.nodes at it
+// builds the walk array ("Collapse" and "Regroup", rt_scene_plan.h) and points dev.nodes at it
 rt_status build_walk(rt_scene* s, const rt_scene_desc* d) {
+    using namespace rt_scene_plan;
     const int n = d->n_nodes;
     s->walk_tests_before = s->walk_tests_after = 0.0;
     if (g_opt.bvh_collapse == 0 || n < 3) return RT_OK;
-    std::vector<double> pass;
-    std::vector<float> ray_sample;
-    double root_visits = 0.0;
-    if (g_opt.bvh_collapse >= 2) RT_TRY(measure_pass_counts(s, s->dev.nodes_ref, n, pass, root_visits, nullptr, 0, /*keep_cost=*/true));
-    const bool measured = root_visits > 0.0;
-    if (!measured) {   // by surface area: a ray that passes a box passes a box inside it about in proportion to the areas
-        pass.assign((size_t)n, 0.0);
-        for (int i = 0; i < n; ++i) {
-            const double ex = fmax(0.0, (double)d->nodes[i].bmax[0] - d->nodes[i].bmin[0]), ey = fmax(0.0, (double)d->nodes[i].bmax[1] - d->nodes[i].bmin[1]),
-                         ez = fmax(0.0, (double)d->nodes[i].bmax[2] - d->nodes[i].bmin[2]);
-            pass[i] = 2.0 * (ex * ey + ey * ez + ex * ez);
-        }
-        root_visits = pass[0];
-    }
+    calibration_result ref;   // of the reference's tree
+    if (g_opt.bvh_collapse >= 2) RT_TRY(measure_pass_counts(s, {s->dev.nodes_ref, n, 0, true}, ref));
+    const bool measured = ref.rays > 0.0;
+    if (!measured) { ref.pass = area_passes(d->nodes, n); ref.rays = ref.pass[0]; }
+    const double root_visits = ref.rays;
     collapse_plan plan;
-    const bool planned = plan_collapse(d->nodes, n, pass, root_visits, plan);
+    const bool planned = plan_collapse(d->nodes, n, ref.pass, root_visits, plan);
     std::vector<rt_node> walk;
     if (planned) walk = build_walk_array(d->nodes, n, plan.keep);
     bool changed = planned && (int)walk.size() != n;
-    // the regrouped hierarchy over the same leaves ("Regroup" above), through the same calibration pass and DP; it needs
-    // the reference's own tree to have passed the checks (a real tree, boxes containing their children's)
+    // the regrouped hierarchies over the same leaves, through the same calibration pass and DP; they need the reference's own
+    // tree to have passed the checks (a real tree, boxes containing their children's)
     if (g_opt.bvh_collapse >= 3 && measured && planned) {
         // bounds on the planning time of very large scenes (the reference's have at most 1410 leaves): the top-down split is
         // quadratic in the worst case, the sampled-ray key costs leaves x rays
         int n_leaves = 0;
         for (int i = 0; i < n; ++i) n_leaves += d->nodes[i].prim >= 0 ? 1 : 0;
+        std::vector<float> ray_sample;
         for (int method = 0; method < 3; ++method) {
             if (method == 0 && n_leaves > 65536) continue;
             if (method == 2 && (ray_sample.size() < 7 * 256 || n_leaves > 8192)) continue;
             const std::vector<rt_node> tree = regroup_leaves(d->nodes, n, method, &ray_sample);
             const int m = (int)tree.size();
             if (m < 3) continue;
-            std::vector<rt_node> enc;
-            device_nodes(tree.data(), tree.size(), enc);
-            const rt_node* d_tree = nullptr;
-            RT_TRY(upload(enc.data(), enc.size(), &d_tree));
-            std::vector<double> pass2;
-            double rays2 = 0.0;
+            call_memory mem;   // the candidate on the device
+            const void* d_tree = nullptr;
+            RT_TRY(upload(device_nodes(tree.data(), tree.size()).data(), tree.size() * sizeof(rt_node), &d_tree));
+            mem.own(d_tree);
             // the first of these passes also keeps ~4000 of its rays for method 2 (same frame, same rays in every pass)
-            const rt_status st = measure_pass_counts(s, d_tree, m, pass2, rays2, method == 0 ? &ray_sample : nullptr, (uint32_t)(root_visits / 4096.0) + 1u);
-            (void)hipFree(const_cast<rt_node*>(d_tree));
-            if (st != RT_OK) return st;
+            calibration_result c;
+            RT_TRY(measure_pass_counts(s, {static_cast<const rt_node*>(d_tree), m, method == 0 ? (uint32_t)(root_visits / 4096.0) + 1u : 0u, false}, c));
+            if (method == 0) ray_sample.swap(c.sample);
             collapse_plan plan2;
-            const bool ok2 = rays2 == root_visits && plan_collapse(tree.data(), m, pass2, rays2, plan2);
+            const bool ok2 = c.rays == root_visits && plan_collapse(tree.data(), m, c.pass, c.rays, plan2);
             if (ok2 && plan2.tests_after < plan.tests_after) {
                 walk = build_walk_array(tree.data(), m, plan2.keep);
                 plan.tests_after = plan2.tests_after;            // "before" stays the reference tree's figure
@@ -960,16 +548,32 @@ rt_status build_walk(rt_scene* s, const rt_scene_desc* d) {
     }
     {   // (the estimates stay the plan's: per-lane box tests of the array a walk would use)
         std::vector<rt_node> cur = changed ? walk : std::vector<rt_node>(d->nodes, d->nodes + n);
-        if (leaves_only_if_scanned(cur.data(), (int)cur.size(), walk)) changed = true;
+        if (leaves_only_if_scanned(cur.data(), (int)cur.size(), g_opt.scan_nodes, walk)) changed = true;
     }
     if (!changed) return RT_OK;
-    const rt_node* d_walk = nullptr;
-    std::vector<rt_node> enc;
-    device_nodes(walk.data(), walk.size(), enc);
-    RT_TRY(upload(enc.data(), enc.size(), &d_walk));
-    s->allocs.push_back(const_cast<void*>(static_cast<const void*>(d_walk)));
-    s->dev.nodes = d_walk; s->dev.n_nodes = (int32_t)walk.size();
+    RT_TRY(upload_arrays(s, {array_of(device_nodes(walk.data(), walk.size()), &s->dev.nodes)}));
+    s->dev.n_nodes = (int32_t)walk.size();
     s->walk_tests_before = plan.tests_before; s->walk_tests_after = plan.tests_after;
+    return RT_OK;
+}
+
+// the per-frame resources of a new scene: the counters, the frame's events, and the tier kernel's stream with the events that
+// fork it from / join it to the caller's stream, one pair per ranked part
+rt_status create_frame_resources(rt_scene* s) {
+    hipError_t e;
+    if ((e = hipMalloc((void**)&s->d_ray_counter, RT_COUNTER_BYTES)) != hipSuccess || (e = hipMalloc((void**)&s->d_work_counter, RT_WORK_COUNTER_BYTES)) != hipSuccess ||
+        (e = hipEventCreate(&s->ev_start)) != hipSuccess || (e = hipEventCreate(&s->ev_stop)) != hipSuccess) {
+        g_last_hip_error = (int)e; g_detail = "allocating per-frame resources failed";
+        return RT_ERR_HIP;
+    }
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    e = hipStreamCreateWithPriority(&s->tier_stream, hipStreamNonBlocking, prio_hi);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
+        e = hipEventCreateWithFlags(&s->ev_fork[k], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join[k], hipEventDisableTiming);
+    }
+    if (e != hipSuccess) { g_last_hip_error = (int)e; g_detail = "creating the tier stream failed"; return RT_ERR_HIP; }
     return RT_OK;
 }
 }  // namespace
@@ -992,123 +596,45 @@ rt_status rt_internal_init_device(int device_ordinal) {
 void rt_internal_set_error(rt_status st, int hip_error, const std::string& detail) { (void)st; g_last_hip_error = hip_error; g_detail = detail; }
 int rt_internal_option(const char* key) { return std::string(key) == "multi_force_rccl" ? g_opt.multi_force_rccl : 0; }
 
+// Validate; derive the host arrays (rt_scene_plan.h); upload; create the per-frame resources; build the tier data; build the walk.
 rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_scene** out) {
     if (!out) return invalid("null output pointer");
     *out = nullptr;
     RT_TRY(use_device(device));
-    bool so = false, uv = false;
-    int tx = 0;
-    RT_TRY(validate(d, so, tx, uv));
-    rt_status st = RT_OK;
+    rt_scene_plan::scene_class cls;
+    if (const char* why = rt_scene_plan::validate(d, cls)) return invalid(why);
+    // what the device gets in place of the description's arrays: the nodes in its link encoding, quads, boxes and materials marked
+    const std::vector<rt_node> nodes = rt_scene_plan::device_nodes(d->nodes, (size_t)d->n_nodes);
+    const std::vector<rt_quad> quads = rt_scene_plan::marked_quads(d);
+    const std::vector<rt_box> boxes = rt_scene_plan::marked_boxes(d);
+    const std::vector<rt_material> materials = rt_scene_plan::marked_materials(d);
 
-#define UPSRC_spheres spheres
-#define UPSRC_quads quads
-#define UPSRC_boxes boxes
-#define UPSRC_instances instances
-#define UPSRC_media media
-#define UPSRC_materials materials
-#define UPSRC_textures textures
-#define UPSRC_images images
     rt_scene* s = new rt_scene;
     s->device = device;
     memset(&s->dev, 0, sizeof(s->dev));
     memset(&s->pending_stats, 0, sizeof(s->pending_stats));
-    s->spheres_only = so; s->tex_level = tx; s->need_uv = uv;
-#define UP(field, count)                                                             \
-    do {                                                                             \
-        st = upload(d->UPSRC_##field, (size_t)(count), &s->dev.field);               \
-        if (st != RT_OK) { rt_scene_destroy(s); return st; }                         \
-        s->allocs.push_back(const_cast<void*>(static_cast<const void*>(s->dev.field))); \
-    } while (0)
-    {
-        std::vector<rt_node> enc;
-        device_nodes(d->nodes, (size_t)d->n_nodes, enc);
-        st = upload(enc.data(), enc.size(), &s->dev.nodes_ref);
-        if (st != RT_OK) { rt_scene_destroy(s); return st; }
-        s->allocs.push_back(const_cast<void*>(static_cast<const void*>(s->dev.nodes_ref)));
-    }
-    UP(spheres, d->n_spheres);
-    {   // quads and boxes: mark the axis-aligned ones (quad_test_axis, rt_device_funcs.h).  A quad qualifies when its unit
-        // normal is exactly +-e_C and u, v, w each have exactly one non-zero component on the fitting axes; a box when its
-        // six faces do, with normals along z, x, z, x, y, y (make_box's order, quad.cuh:145-162).  Both rules live in
-        // rt_refit_host.h, where rt_scene_update_quads takes them from too.
-        std::vector<rt_quad> quads(d->quads, d->quads + d->n_quads);
-        for (rt_quad& q : quads) { const int32_t code = rt_refit::axis_code(q); memcpy(&q.pad0, &code, 4); }
-        std::vector<rt_box> boxes(d->boxes, d->boxes + d->n_boxes);
-        for (rt_box& b : boxes) {
-            int32_t codes[6];
-            for (int f = 0; f < 6; ++f) codes[f] = rt_refit::axis_code(quads[(size_t)b.first_quad + f]);
-            if (rt_refit::canonical_codes(codes)) b.first_quad |= RT_BOX_CANONICAL;
-        }
-        st = upload(quads.data(), quads.size(), &s->dev.quads);
-        if (st != RT_OK) { rt_scene_destroy(s); return st; }
-        s->allocs.push_back(const_cast<void*>(static_cast<const void*>(s->dev.quads)));
-        st = upload(boxes.data(), boxes.size(), &s->dev.boxes);
-        if (st != RT_OK) { rt_scene_destroy(s); return st; }
-        s->allocs.push_back(const_cast<void*>(static_cast<const void*>(s->dev.boxes)));
-    }
-    UP(instances, d->n_instances);
-    UP(media, d->n_media);
-    {   // materials: `pad` tells resolve_hit() whether the material's texture reads the hit's (u, v)
-        std::vector<rt_material> mats(d->materials, d->materials + d->n_materials);
-        auto reads_uv = [&](int tex) -> bool {
-            if (tex < 0) return false;
-            const rt_texture& t = d->textures[tex];
-            if (t.kind == RT_TEX_IMAGE || t.kind == RT_TEX_UV_OFFSET) return true;
-            if (t.kind == RT_TEX_CHECKER) {
-                const int ka = d->textures[t.a].kind, kb = d->textures[t.b].kind;   // validate(): checker children are plain textures
-                return ka == RT_TEX_IMAGE || kb == RT_TEX_IMAGE;
-            }
-            return false;
-        };
-        for (rt_material& m : mats) m.pad = reads_uv(m.tex) ? 1.0f : 0.0f;
-        st = upload(mats.data(), mats.size(), &s->dev.materials);
-        if (st != RT_OK) { rt_scene_destroy(s); return st; }
-        s->allocs.push_back(const_cast<void*>(static_cast<const void*>(s->dev.materials)));
-    }
-    UP(textures, d->n_textures);
-    UP(images, d->image_bytes);
-#undef UP
-    s->dev.n_nodes_ref = d->n_nodes;
-    for (int c = 0; c < 3; ++c) {   // the scene's coordinate bound per axis (regrouped interior boxes are unions of these: the same bound)
-        float b = 0.0f;
-        for (int i = 0; i < d->n_nodes; ++i) b = fmaxf(b, fmaxf(fabsf(d->nodes[i].bmin[c]), fabsf(d->nodes[i].bmax[c])));
-        s->dev.bound[c] = b;
-    }
-    s->dev.bound_pad = 0.0f;
-    s->dev.nodes = s->dev.nodes_ref; s->dev.n_nodes = d->n_nodes;     // until the walk array is built below
-    s->dev.n_spheres = d->n_spheres;
+    s->spheres_only = cls.spheres_only; s->tex_level = cls.tex_level; s->need_uv = cls.need_uv;
+    rt_scene_dev& dev = s->dev;
+    rt_status st = upload_arrays(s, {
+        array_of(nodes, &dev.nodes_ref), array_of(d->spheres, (size_t)d->n_spheres, &dev.spheres), array_of(quads, &dev.quads), array_of(boxes, &dev.boxes),
+        array_of(d->instances, (size_t)d->n_instances, &dev.instances), array_of(d->media, (size_t)d->n_media, &dev.media), array_of(materials, &dev.materials),
+        array_of(d->textures, (size_t)d->n_textures, &dev.textures), array_of(d->images, d->image_bytes, &dev.images)});
+    dev.nodes = dev.nodes_ref; dev.n_nodes = dev.n_nodes_ref = d->n_nodes;     // until the walk array is built below
+    dev.n_spheres = d->n_spheres; dev.n_materials = d->n_materials; dev.n_textures = d->n_textures;
+    rt_scene_plan::axis_bound(d->nodes, d->n_nodes, dev.bound);
+    dev.bound_pad = 0.0f;
+    dev.camera = d->camera;
     s->n_instances = d->n_instances; s->n_media = d->n_media;
     s->n_quads = d->n_quads; s->n_boxes = d->n_boxes;
     s->refit.instanced = rt_refit::instanced_spheres(d->instances, d->n_instances, d->n_spheres);   // (host only: an update's checks need no HIP call)
     for (int i = 0; i < d->n_instances; ++i) s->refit.inst_child.push_back(d->instances[i].child);
-    s->dev.n_materials = d->n_materials; s->dev.n_textures = d->n_textures;
     s->shade_bytes = (size_t)d->n_materials * sizeof(rt_material) + (size_t)d->n_textures * sizeof(rt_texture);
-    s->dev.camera = d->camera;
-    s->node_bytes = (size_t)d->n_nodes * sizeof(rt_node);
     s->sphere_bytes = (size_t)d->n_spheres * sizeof(rt_sphere);
-    hipError_t e;
-    if ((e = hipMalloc((void**)&s->d_ray_counter, RT_COUNTER_BYTES)) != hipSuccess || (e = hipMalloc((void**)&s->d_work_counter, RT_WORK_COUNTER_BYTES)) != hipSuccess ||
-        (e = hipEventCreate(&s->ev_start)) != hipSuccess || (e = hipEventCreate(&s->ev_stop)) != hipSuccess) {
-        g_last_hip_error = (int)e; g_detail = "allocating per-frame resources failed";
-        rt_scene_destroy(s);
-        return RT_ERR_HIP;
-    }
-    {   // the tier kernel's stream and the events that fork it from / join it to the caller's stream, one pair per ranked part
-        int prio_lo = 0, prio_hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        e = hipStreamCreateWithPriority(&s->tier_stream, hipStreamNonBlocking, prio_hi);
-        for (int k = 0; k < 4 && e == hipSuccess; ++k) {
-            e = hipEventCreateWithFlags(&s->ev_fork[k], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_join[k], hipEventDisableTiming);
-        }
-        if (e != hipSuccess) { g_last_hip_error = (int)e; g_detail = "creating the tier stream failed"; rt_scene_destroy(s); return RT_ERR_HIP; }
-    }
-    st = build_tier_data(s, d);
+    if (st == RT_OK) st = create_frame_resources(s);
+    if (st == RT_OK) st = build_tier_data(s, d);
+    if (st == RT_OK) st = build_walk(s, d);
     if (st != RT_OK) { rt_scene_destroy(s); return st; }
-    st = build_walk(s, d);
-    if (st != RT_OK) { rt_scene_destroy(s); return st; }
-    s->node_bytes = (size_t)s->dev.n_nodes * sizeof(rt_node);
+    s->node_bytes = (size_t)dev.n_nodes * sizeof(rt_node);
     *out = s;
     return RT_OK;
 }
@@ -1122,19 +648,11 @@ rt_status rt_plan_walk_array(const rt_node* nodes, int32_t n, const double* pass
                              int32_t* n_out, double* tests_before, double* tests_after) {
     if (!nodes || n <= 0 || !n_out) return invalid("rt_plan_walk_array: bad argument");
     for (int i = 0; i < n; ++i) if (nodes[i].skip <= i || nodes[i].skip > n) return invalid("node skip link does not move forward");
-    std::vector<double> p((size_t)n, 0.0);
-    if (pass) p.assign(pass, pass + n);
-    else {
-        for (int i = 0; i < n; ++i) {
-            const double ex = fmax(0.0, (double)nodes[i].bmax[0] - nodes[i].bmin[0]), ey = fmax(0.0, (double)nodes[i].bmax[1] - nodes[i].bmin[1]),
-                         ez = fmax(0.0, (double)nodes[i].bmax[2] - nodes[i].bmin[2]);
-            p[i] = 2.0 * (ex * ey + ey * ez + ex * ez);
-        }
-        root_visits = p[0];
-    }
-    collapse_plan plan;
+    const std::vector<double> p = pass ? std::vector<double>(pass, pass + n) : rt_scene_plan::area_passes(nodes, n);
+    if (!pass) root_visits = p[0];
+    rt_scene_plan::collapse_plan plan;
     std::vector<rt_node> walk(nodes, nodes + n);
-    if (plan_collapse(nodes, n, p, root_visits, plan)) walk = build_walk_array(nodes, n, plan.keep);
+    if (rt_scene_plan::plan_collapse(nodes, n, p, root_visits, plan)) walk = rt_scene_plan::build_walk_array(nodes, n, plan.keep);
     *n_out = (int32_t)walk.size();
     if (tests_before) *tests_before = plan.tests_before;
     if (tests_after) *tests_after = plan.tests_after;
@@ -1144,7 +662,7 @@ rt_status rt_plan_walk_array(const rt_node* nodes, int32_t n, const double* pass
 
 rt_status rt_regroup_leaves(const rt_node* nodes, int32_t n, int32_t method, rt_node* out, int32_t cap, int32_t* n_out) {
     if (!nodes || n <= 0 || !n_out || method < 0 || method > 1) return invalid("rt_regroup_leaves: bad argument");
-    const std::vector<rt_node> tree = regroup_leaves(nodes, n, method);
+    const std::vector<rt_node> tree = rt_scene_plan::regroup_leaves(nodes, n, method);
     *n_out = (int32_t)tree.size();
     if (out) for (int i = 0; i < (int)tree.size() && i < cap; ++i) out[i] = tree[i];
     return RT_OK;
@@ -1257,11 +775,7 @@ rt_status rt_scene_set_camera(rt_scene* s, const rt_camera* camera, int recalibr
     s->dev.camera = *camera;
     ++s->scene_epoch;                                // the cost map is stale ...
     if (recalibrate) s->cost_map.valid = false;      // ... or, with a fresh calibration prior asked for, dropped
-    if (recalibrate && s->d_cal_cost) {   // (a scene that kept no prior at creation gets none: a fresh scene would have none either)
-        std::vector<double> pass;
-        double rays = 0.0;
-        RT_TRY(measure_pass_counts(s, s->dev.nodes_ref, s->dev.n_nodes_ref, pass, rays, nullptr, 0, /*keep_cost=*/true));
-    }
+    if (recalibrate) RT_TRY(recalibrate_cost(s));
     return RT_OK;
 }
 
@@ -1486,11 +1000,7 @@ rt_status run_refit(rt_scene* s, const rt_refit_params& p, int kind, hipStream_t
     uint32_t flag = 0;
     memcpy(&flag, &result[3], 4);
     refused = flag != 0;
-    if (recalibrate && s->d_cal_cost) {
-        std::vector<double> pass;
-        double rays = 0.0;
-        RT_TRY(measure_pass_counts(s, s->dev.nodes_ref, s->dev.n_nodes_ref, pass, rays, nullptr, 0, /*keep_cost=*/true));
-    }
+    if (recalibrate) RT_TRY(recalibrate_cost(s));
     return RT_OK;
 }
 
@@ -1577,9 +1087,9 @@ void restate(const rt_scene_desc* d, int kind, const Update* u, std::vector<Reco
     if (records_out && !changed.empty()) memcpy(records_out, changed.data(), changed.size() * sizeof(Record));
 }
 rt_status validate_desc(const rt_scene_desc* d) {
-    bool so = false, uv = false;
-    int tx = 0;
-    return validate(d, so, tx, uv);
+    rt_scene_plan::scene_class cls;
+    const char* why = rt_scene_plan::validate(d, cls);
+    return why ? invalid(why) : RT_OK;
 }
 }  // namespace
 
