@@ -4,229 +4,37 @@
 // calibration pass and the cost prior), frame launch (rt_frame_plan.h decides,
 // this file enqueues), statistics.  The kernels are in rt_kernel_pixel.hip, rt_staged_*.hip
 // (rt_kernel_staged.h), rt_tier_*.hip (rt_kernel_tier.h), rt_rank.hip and, for
-// rt_scene_update_spheres, rt_kernel_refit.hip (host half: rt_refit_host.h).
+// rt_scene_update_spheres, rt_kernel_refit.hip (host half: rt_refit_host.h).  The rt_debug_* entries are in rt_abi_debug.hip;
+// what this file shares with it and with rt_multi.hip -- the globals defined below, struct rt_scene -- is declared in rt_host.h.
 // There is no CPU render path here or anywhere else in the
 // library: without a HIP device every entry point fails with
 // RT_ERR_NO_DEVICE / RT_ERR_HIP.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cfloat>
 #include <utility>
 #include <cmath>
 #include <functional>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/rt_abi.h"
-#include "rt_call_buffers.h"
-#include "rt_device.h"
-#include "rt_frame_plan.h"
+#include "rt_host.h"
 #include "rt_handoff_order.h"
-#include "rt_refit_host.h"
 #include "rt_scene_plan.h"
+
+namespace rt_host {
+device_info g_devices[RT_MAX_DEVICES];
+int g_device = -1;
+int g_last_hip_error = 0;
+std::string g_detail;
+rt_options g_opt;
+unsigned long long g_opt_epoch = 0;
+}  // namespace rt_host
+using namespace rt_host;
 
 namespace {
 
-// Devices this process has initialised (rt_init / rt_init_devices).  A scene remembers the device it was created on and
-// every entry point that touches it makes that device current first, so a caller may drive several devices from one
-// thread (rt_multi_*) or change the current device between calls.
-struct device_info {
-    bool ready = false;
-    int num_cu = 256;
-    size_t lds_per_cu = 160 * 1024;
-};
-enum { RT_MAX_DEVICES = 16 };
-device_info g_devices[RT_MAX_DEVICES];
-int g_device = -1;              // device new scenes are created on (the last rt_init)
-int g_last_hip_error = 0;
-std::string g_detail;
-
-rt_options g_opt;   // the tuning knobs (rt_set_option; struct rt_options: rt_frame_plan.h)
-// bumped by every rt_set_option / rt_reset_options call: a cost map recorded under another value counts as stale (struct rt_scene)
-unsigned long long g_opt_epoch = 0;
-
-// the reference's checkCudaErrors (main.cu:23-35) records "<code> at file:line 'expr'"; it then
-// exits with 99, which a library must not do, so the status is returned instead.
-#define HIPCHK(expr)                                                                  \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess) {                                                       \
-            g_last_hip_error = (int)e_;                                               \
-            char buf_[512];                                                           \
-            snprintf(buf_, sizeof(buf_), "HIP error = %u at %s:%d '%s' (%s)", (unsigned)e_, __FILE__, __LINE__, #expr, \
-                     hipGetErrorString(e_));                                          \
-            g_detail = buf_;                                                          \
-            return RT_ERR_HIP;                                                        \
-        }                                                                             \
-    } while (0)
-// a step that returns an rt_status: a failure is the caller's result
-#define RT_TRY(expr) do { const rt_status st_ = (expr); if (st_ != RT_OK) return st_; } while (0)
-
-rt_status invalid(const char* why) { g_detail = why; return RT_ERR_INVALID; }
-
-// 8x8 pixel tiles across `pixels` pixels or rows (the tile grid of a call is tiles_across(nx) x tiles_across(local_rows))
-inline int tiles_across(int pixels) { return (pixels + 7) / 8; }
-
-// A device copy of `bytes` bytes in an allocation of its own, zero-filled up to the next multiple of 64 bytes.
-rt_status upload(const void* src, size_t bytes, const void** dst) {
-    *dst = nullptr;
-    // always allocate something so kernels never see a null array base
-    const size_t room = ((bytes ? bytes : 1) + 63) & ~(size_t)63;
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, room));
-    hipError_t e = hipMemset(p, 0, room);
-    if (e == hipSuccess && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(p); HIPCHK(e); }
-    *dst = p;
-    return RT_OK;
-}
 // One row of an upload table: `count` elements at `src` go to the device, where *dst points at them afterwards.
 struct array_upload { const void* src; size_t bytes; const void** dst; };
 template <class T> array_upload array_of(const T* src, size_t count, const T** dst) { return {src, count * sizeof(T), (const void**)dst}; }
 template <class T> array_upload array_of(const std::vector<T>& v, const T** dst) { return array_of(v.data(), v.size(), dst); }
-
-// Frees what the pointers hold and allocates them anew: the step every cached buffer, or group of buffers under one capacity,
-// takes when a frame needs more than it has.
-struct sized_buffer { void** p; size_t bytes; };
-rt_status reallocate(std::initializer_list<sized_buffer> buffers) {
-    for (const sized_buffer& b : buffers) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
-    for (const sized_buffer& b : buffers) HIPCHK(hipMalloc(b.p, b.bytes));
-    return RT_OK;
-}
-// a cached device buffer of `capacity` elements, grown to hold `need`
-template <class T> rt_status grow(T*& p, size_t& capacity, size_t need) {
-    if (capacity >= need) return RT_OK;
-    capacity = 0;
-    RT_TRY(reallocate({{(void**)&p, need * sizeof(T)}}));
-    capacity = need;
-    return RT_OK;
-}
-
-// Device memory of one call, freed when the call returns: allocations of their own (get), which a caller may cut into
-// 256-byte-rounded pieces (rounded, take: rt_call_buffers.h).  A call that enqueues work on the memory guards it with its stream:
-// every way out but the one through settled() -- the call has waited for its work, or leaves it to the caller's stream (finish)
-// -- synchronises that stream before the memory is freed.
-struct call_memory : call_pieces {
-    std::vector<void*> all;
-    hipStream_t stream = nullptr;
-    bool guarded = false;
-    ~call_memory() {
-        if (guarded && !all.empty()) (void)hipStreamSynchronize(stream);   // nothing of a failed call may still use the memory
-        for (void* p : all) (void)hipFree(p);
-    }
-    void guard(hipStream_t st) { stream = st; guarded = true; }
-    void settled() { guarded = false; }
-    hipError_t get(void** p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes ? bytes : 1); if (e == hipSuccess) all.push_back(*p); return e; }
-    void own(const void* p) { all.push_back(const_cast<void*>(p)); }                              // an allocation made elsewhere: freed with the rest
-    void disown(const void* p) { all.erase(std::remove(all.begin(), all.end(), p), all.end()); }   // one that outlives the call after all
-    rt_status finish(bool wait) { if (wait) HIPCHK(hipStreamSynchronize(stream)); settled(); return RT_OK; }
-};
-
-}  // namespace
-
-rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_scene** out);
-
-struct rt_scene {
-    int device = 0;             // the device every allocation below lives on
-    rt_scene_dev dev;
-    std::vector<void*> allocs;
-    bool spheres_only = false, need_uv = false;
-    int tex_level = 0;
-    size_t node_bytes = 0, sphere_bytes = 0, shade_bytes = 0;   // node_bytes: the walk array; shade_bytes: materials + textures
-    double walk_tests_before = 0, walk_tests_after = 0;          // expected box tests per calibration ray, reference tree / walk array
-    // per-frame resources
-    unsigned long long* d_ray_counter = nullptr;
-    unsigned int* d_work_counter = nullptr;
-    float* d_fb = nullptr;
-    size_t d_fb_floats = 0;
-    unsigned int* d_tile_cost = nullptr;   // cost prepass: rays per 8x8 tile
-    unsigned int* d_tile_order = nullptr;  // tiles in descending cost
-    rt_pixel_state* d_state = nullptr;     // split frames: pixels parked between the two parts
-    unsigned long long* d_heavy_list = nullptr;   // (cost << 32 | pixel), unsorted, from rt_collect_heavy_kernel
-    unsigned int* d_heavy_pixels = nullptr;       // heavy pixels, dearest first
-    size_t tile_capacity = 0, pixel_capacity = 0;
-    unsigned long long* d_handoff = nullptr;      // tail hand-off queue: (sample << 32 | pixel), one entry per resident lane at most
-    size_t handoff_capacity = 0;
-    unsigned long long* d_handoff_ordered = nullptr;   // ... ordered for the tail launch (rt_handoff_order.h), grown like d_handoff
-    size_t handoff_ordered_capacity = 0;
-    unsigned int* d_handoff_scratch = nullptr;          // ... the ordering kernels' bucket counts
-    size_t handoff_scratch_capacity = 0;
-    rt_rank_info* d_rank = nullptr;               // tier sizes of the next ranked launch (written and read on the device only)
-    unsigned int* d_cal_cost = nullptr;           // cost prior: rays per pixel of the calibration frame (cal_nx x cal_ny at 4 spp)
-    int cal_nx = 0, cal_ny = 0;
-    // The cost map: the rays every local pixel cost over all its samples, written by the last launches of the last ranked frame
-    // (rt_frame_params::cost_out) and valid once rt_frame_finish has closed that frame.  A pixel's cost depends on the scene, the
-    // camera, the frame geometry and the row partition -- `key` and `scene_epoch` -- and not on the seed or the sample count.
-    // Rendering the same view again (key and both epochs equal: the map is EXACT) therefore needs no first look: the frame is
-    // ranked on the map and runs as one part.  After rt_scene_set_camera / rt_scene_update_spheres without recalibration, or any
-    // option call, the map is STALE: it replaces the calibration frame as the prior of part 1.  Scheduling only.
-    struct cost_map_state {
-        unsigned int* d = nullptr;                // one word per local pixel, grown like the ranked buffers
-        size_t capacity = 0;
-        bool valid = false, pending = false;      // pending: the frame in flight writes it
-        cost_map_key key, last_key;               // of the map; of the last ranked frame (rt_debug_set_cost_map)
-        bool have_last_key = false;
-        unsigned long long scene_epoch = 0, opt_epoch = 0, total = 0;   // of the map; total = the sum of its words (0: not used)
-    } cost_map;
-    unsigned long long scene_epoch = 0;           // bumped when the camera or a sphere changes
-    hipStream_t tier_stream = nullptr;            // the tier kernel's stream (forked from / joined to the caller's stream by events)
-    hipEvent_t ev_fork[4] = {nullptr, nullptr, nullptr, nullptr}, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
-    frame_plan plan;                              // of the last frame render_impl enqueued (rt_frame_finish and the debug entries read it)
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    bool frame_pending = false;
-    hipStream_t pending_stream = nullptr;
-    rt_stats pending_stats;
-    // rt_render_adaptive (cached like d_state): parked pixels, the average at the previous checkpoint, two pixel lists, the tail
-    // queue, and a small block: [0] the decision kernel's append head, then an rt_rank_info and the host copy of a work-counter block
-    rt_pixel_state* d_adapt_state = nullptr;
-    float* d_adapt_half = nullptr;
-    uint32_t* d_adapt_list[2] = {nullptr, nullptr};
-    unsigned long long* d_adapt_queue = nullptr;
-    int32_t* d_adapt_spp = nullptr;              // host spp_out: the device map copied back
-    uint32_t* d_adapt_count = nullptr;
-    rt_rank_info* d_adapt_rank = nullptr;
-    size_t adapt_capacity = 0, adapt_lists_capacity = 0;   // d_adapt_state and d_adapt_spp; half, lists and queue
-    std::vector<hipEvent_t> adapt_events;        // two per pass (rt_debug_adaptive_passes)
-    std::vector<long long> adapt_log;            // per pass of the last adaptive frame: route, active pixels, sample_begin, sample_end
-    std::vector<float> adapt_ms;
-    rt_rank_info adapt_rank_host;                // host sides of the small copies between passes (alive until the next sync)
-    unsigned int adapt_wc_host[RT_WORK_COUNTER_BYTES / 4];
-    // rt_render_variance: per local pixel T_{b-1}, A, Q (the parked pixels live in d_adapt_state, a host variance_out's device
-    // image in d_adapt_spp: 4 bytes per pixel either way)
-    double* d_var_acc = nullptr;
-    size_t var_capacity = 0;                     // in doubles: three per pixel
-    // rt_scene_update_spheres, _instances and _quads: the lookup tables of the refit kernels, built on
-    // the scene's first update from a read-back of the node arrays, so that a scene that never moves pays nothing; refit.block
-    // holds all of them
-    int32_t n_instances = 0, n_media = 0;        // of the description (rt_scene_dev carries neither)
-    int32_t n_quads = 0, n_boxes = 0;
-    struct refit_tables {
-        bool ready = false;
-        void* block = nullptr;                   // one allocation, cut into the arrays of `p` and the stamps
-        rt_refit_params p;                       // the per-scene half of the kernels' argument, filled once
-        std::vector<char> instanced;             // per sphere: the child of an instance (kept from rt_scene_create, host only)
-        std::vector<int32_t> inst_child;         // per instance: its child, which no update changes (the same)
-        uint32_t* stamp[rt_refit::KINDS] = {};   // per kind (the kinds index different arrays): one word per record ...
-        uint32_t epoch[rt_refit::KINDS] = {};    // ... equal to this after the update that last replaced the record
-        int32_t* d_indices = nullptr;            // the update's index list and (host records) its records on the device
-        char* d_records = nullptr;
-        size_t indices_capacity = 0, records_capacity = 0;   // in indices, in bytes
-    } refit;
-};
-
-// Progressive accumulation (rt_render_window): the parked pixels of one frame description between windows.
-struct rt_progressive {
-    rt_scene* scene = nullptr;
-    rt_pixel_state* d_state = nullptr;
-    size_t pixels = 0;
-    rt_frame_desc frame;         // the description it was made for (its partition must not change between windows)
-    int32_t next_sample = 0;     // the sample_begin the next window must have
-};
-
-namespace {
 
 // picks the kernel family; LDS_MODE and texture level select the instantiation inside (rt_staged_*.hip)
 hipError_t launch_render(int kernel, int lds_mode, const rt_scene* s, const rt_frame_params& fp, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream) {
@@ -241,10 +49,7 @@ hipError_t launch_render(int kernel, int lds_mode, const rt_scene* s, const rt_f
 
 }  // namespace
 
-extern "C" {
-
-namespace {
-rt_status init_device(int device_ordinal) {
+rt_status rt_host::init_device(int device_ordinal) {
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0) {
@@ -266,20 +71,15 @@ rt_status init_device(int device_ordinal) {
     d.ready = true;
     return RT_OK;
 }
-// makes the scene's device current (a no-op when it already is)
-rt_status use_device(int device) {
-    if (device < 0 || device >= RT_MAX_DEVICES || !g_devices[device].ready) { g_detail = "rt_init has not succeeded for this device"; return RT_ERR_NO_DEVICE; }
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != device) HIPCHK(hipSetDevice(device));
-    return RT_OK;
-}
-}  // namespace
-
-rt_status rt_init(int device_ordinal) {
+rt_status rt_host::rt_internal_init_device(int device_ordinal) {
     const rt_status st = init_device(device_ordinal);
     if (st == RT_OK) g_device = device_ordinal;
     return st;
 }
+
+extern "C" {
+
+rt_status rt_init(int device_ordinal) { return rt_internal_init_device(device_ordinal); }
 
 rt_status rt_shutdown(void) {
     for (device_info& d : g_devices) d.ready = false;
@@ -367,31 +167,12 @@ rt_status rt_set_option(const char* key, int value) {
 rt_status rt_scene_destroy(rt_scene* s) {
     if (!s) return RT_OK;
     (void)use_device(s->device);
-    for (void* p : s->allocs) (void)hipFree(p);
-    if (s->d_ray_counter) (void)hipFree(s->d_ray_counter);
-    if (s->d_work_counter) (void)hipFree(s->d_work_counter);
-    if (s->d_fb) (void)hipFree(s->d_fb);
-    if (s->d_tile_cost) (void)hipFree(s->d_tile_cost);
-    if (s->d_tile_order) (void)hipFree(s->d_tile_order);
-    if (s->d_state) (void)hipFree(s->d_state);
-    if (s->d_heavy_list) (void)hipFree(s->d_heavy_list);
-    if (s->d_heavy_pixels) (void)hipFree(s->d_heavy_pixels);
-    if (s->d_rank) (void)hipFree(s->d_rank);
-    if (s->d_handoff) (void)hipFree(s->d_handoff);
-    if (s->d_handoff_ordered) (void)hipFree(s->d_handoff_ordered);
-    if (s->d_handoff_scratch) (void)hipFree(s->d_handoff_scratch);
-    if (s->d_cal_cost) (void)hipFree(s->d_cal_cost);
-    if (s->cost_map.d) (void)hipFree(s->cost_map.d);
-    for (void* p : {s->refit.block, (void*)s->refit.d_indices, (void*)s->refit.d_records}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)s->d_adapt_state, (void*)s->d_adapt_half, (void*)s->d_adapt_list[0], (void*)s->d_adapt_list[1], (void*)s->d_adapt_queue,
-                    (void*)s->d_adapt_spp, (void*)s->d_adapt_count, (void*)s->d_adapt_rank, (void*)s->d_var_acc})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : s->adapt_events) (void)hipEventDestroy(e);
     if (s->tier_stream) (void)hipStreamDestroy(s->tier_stream);
     for (int k = 0; k < 4; ++k) { if (s->ev_fork[k]) (void)hipEventDestroy(s->ev_fork[k]); if (s->ev_join[k]) (void)hipEventDestroy(s->ev_join[k]); }
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
     if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
-    delete s;
+    delete s;   // (its buffers free themselves: the device is current)
     return RT_OK;
 }
 
@@ -399,8 +180,11 @@ namespace {
 // the rows of an upload table in their order, each a scene's allocation from then on (rt_scene_destroy frees it)
 rt_status upload_arrays(rt_scene* s, std::initializer_list<array_upload> table) {
     for (const array_upload& u : table) {
-        RT_TRY(upload(u.src, u.bytes, u.dst));
-        s->allocs.push_back(const_cast<void*>(*u.dst));
+        *u.dst = nullptr;
+        owned<char> copy;
+        RT_TRY(upload(u.src, u.bytes, copy));
+        *u.dst = copy.get();
+        s->allocs.push_back(std::move(copy));
     }
     return RT_OK;
 }
@@ -432,17 +216,18 @@ rt_status measure_pass_counts(rt_scene* s, const calibration_request& rq, calibr
     rt_scene_dev dev = s->dev;
     dev.nodes_ref = rq.d_tree; dev.n_nodes_ref = rq.n_tree;
     enum { SAMPLE_CAP = 8192 };
+    owned<unsigned int> cost;  // (before mem: freed after mem's wait)
     call_memory mem;          // the pass runs on the null stream and is waited for below
     mem.guard(nullptr);
-    unsigned int *d_pass = nullptr, *d_cost = nullptr;
+    unsigned int* d_pass = nullptr;
     float *d_fb = nullptr, *d_sample = nullptr;
     HIPCHK(mem.get((void**)&d_pass, n * sizeof(unsigned int)));
     HIPCHK(mem.get((void**)&d_fb, (size_t)nx * ny * 3 * sizeof(float)));
-    if (rq.keep_cost && mem.get((void**)&d_cost, (size_t)nx * ny * sizeof(unsigned int)) != hipSuccess) d_cost = nullptr;   // no prior then
+    if (rq.keep_cost) (void)cost.grow((size_t)nx * ny);   // (a failure: no prior then)
     if (rq.sample_stride > 0 && mem.get((void**)&d_sample, (size_t)SAMPLE_CAP * 7 * sizeof(float)) != hipSuccess) d_sample = nullptr;   // no sample then
     rt_frame_params fp;
     memset(&fp, 0, sizeof(fp));
-    fp.fb = d_fb; fp.ray_counter = s->d_ray_counter; fp.work_counter = s->d_work_counter; fp.node_pass = d_pass; fp.pixel_cost = d_cost;
+    fp.fb = d_fb; fp.ray_counter = s->d_ray_counter; fp.work_counter = s->d_work_counter; fp.node_pass = d_pass; fp.pixel_cost = cost;
     fp.node_pass_lds = n * sizeof(unsigned int) <= 48u * 1024u ? 1 : 0;
     fp.seed_base = 1984; fp.nx = nx; fp.ny = ny; fp.ns = 4; fp.gamma = 1.0f;
     fp.tile_rows = ny; fp.tile_first = 0; fp.tile_stride = 1; fp.local_rows = ny;
@@ -471,10 +256,9 @@ rt_status measure_pass_counts(rt_scene* s, const calibration_request& rq, calibr
     }();
     if (e != hipSuccess) { g_last_hip_error = (int)e; g_detail = std::string("calibration pass: ") + hipGetErrorString(e); return RT_ERR_HIP; }
     mem.settled();
-    if (d_cost) {   // the scene's prior from now on; the one it had goes with this call's memory
-        if (s->d_cal_cost) mem.own(s->d_cal_cost);
-        mem.disown(d_cost);
-        s->d_cal_cost = d_cost; s->cal_nx = nx; s->cal_ny = ny;
+    if (cost) {   // the scene's prior from now on, in the place of the one it had
+        s->d_cal_cost.adopt(cost.release(), (size_t)nx * ny);
+        s->cal_nx = nx; s->cal_ny = ny;
     }
     out.pass.assign(h.begin(), h.end());
     out.rays = (double)r;
@@ -529,13 +313,11 @@ rt_status build_walk(rt_scene* s, const rt_scene_desc* d) {
             const std::vector<rt_node> tree = regroup_leaves(d->nodes, n, method, &ray_sample);
             const int m = (int)tree.size();
             if (m < 3) continue;
-            call_memory mem;   // the candidate on the device
-            const void* d_tree = nullptr;
-            RT_TRY(upload(device_nodes(tree.data(), tree.size()).data(), tree.size() * sizeof(rt_node), &d_tree));
-            mem.own(d_tree);
+            owned<char> d_tree;   // the candidate on the device
+            RT_TRY(upload(device_nodes(tree.data(), tree.size()).data(), tree.size() * sizeof(rt_node), d_tree));
             // the first of these passes also keeps ~4000 of its rays for method 2 (same frame, same rays in every pass)
             calibration_result c;
-            RT_TRY(measure_pass_counts(s, {static_cast<const rt_node*>(d_tree), m, method == 0 ? (uint32_t)(root_visits / 4096.0) + 1u : 0u, false}, c));
+            RT_TRY(measure_pass_counts(s, {reinterpret_cast<const rt_node*>(d_tree.get()), m, method == 0 ? (uint32_t)(root_visits / 4096.0) + 1u : 0u, false}, c));
             if (method == 0) ray_sample.swap(c.sample);
             collapse_plan plan2;
             const bool ok2 = c.rays == root_visits && plan_collapse(tree.data(), m, c.pass, c.rays, plan2);
@@ -561,7 +343,7 @@ rt_status build_walk(rt_scene* s, const rt_scene_desc* d) {
 // fork it from / join it to the caller's stream, one pair per ranked part
 rt_status create_frame_resources(rt_scene* s) {
     hipError_t e;
-    if ((e = hipMalloc((void**)&s->d_ray_counter, RT_COUNTER_BYTES)) != hipSuccess || (e = hipMalloc((void**)&s->d_work_counter, RT_WORK_COUNTER_BYTES)) != hipSuccess ||
+    if ((e = (hipError_t)s->d_ray_counter.grow(RT_COUNTER_BYTES / 8)) != hipSuccess || (e = (hipError_t)s->d_work_counter.grow(RT_WORK_COUNTER_BYTES / 4)) != hipSuccess ||
         (e = hipEventCreate(&s->ev_start)) != hipSuccess || (e = hipEventCreate(&s->ev_stop)) != hipSuccess) {
         g_last_hip_error = (int)e; g_detail = "allocating per-frame resources failed";
         return RT_ERR_HIP;
@@ -587,17 +369,8 @@ rt_status rt_scene_create(const rt_scene_desc* d, rt_scene** out) {
 
 }  // extern "C"
 
-// ---- internals shared with rt_multi.hip
-rt_status rt_internal_init_device(int device_ordinal) {
-    const rt_status st = init_device(device_ordinal);
-    if (st == RT_OK) g_device = device_ordinal;
-    return st;
-}
-void rt_internal_set_error(rt_status st, int hip_error, const std::string& detail) { (void)st; g_last_hip_error = hip_error; g_detail = detail; }
-int rt_internal_option(const char* key) { return std::string(key) == "multi_force_rccl" ? g_opt.multi_force_rccl : 0; }
-
-// Validate; derive the host arrays (rt_scene_plan.h); upload; create the per-frame resources; build the tier data; build the walk.
-rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_scene** out) {
+// (shared with rt_multi.hip: rt_host.h)
+rt_status rt_host::rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_scene** out) {
     if (!out) return invalid("null output pointer");
     *out = nullptr;
     RT_TRY(use_device(device));
@@ -678,30 +451,9 @@ rt_status rt_scene_walk_info(const rt_scene* s, int32_t* nodes_reference, int32_
 }
 
 namespace {
-// The words of the four failed checks.  They differ between the entry points, and tests and the Python layer match on them.
-struct frame_texts { const char *size, *large, *partition, *tiles; };
-const frame_texts RENDER_FRAME_TEXTS = {"nx, ny and ns must be positive", "frame too large", "bad row partition", "frame too large"};
-const frame_texts STATE_FRAME_TEXTS = {"bad frame size", "bad frame size", "bad row partition", "bad frame size"};
-
-// The frame checks of every entry point that takes a frame: a positive size (and sample count, where the entry point reads
-// f->ns), fewer than 2^31 pixels, a valid row partition, fewer than 2^31 work items.  `who` (may be null) prefixes the text of
-// a failed check.  No HIP call.
-rt_status check_frame(const char* who, const rt_frame_desc* f, bool check_ns, const frame_texts& text, frame_geometry& g) {
-    auto bad = [&](const char* why) { return who ? invalid((std::string(who) + ": " + why).c_str()) : invalid(why); };
-    if (f->nx <= 0 || f->ny <= 0 || (check_ns && f->ns <= 0)) return bad(text.size);
-    if ((long long)f->nx * f->ny >= (1ll << 31)) return bad(text.large);
-    g.local_rows = rt_frame_local_rows(f);
-    if (g.local_rows < 0) return bad(text.partition);
-    g.tiles_x = tiles_across(f->nx); g.tiles_y = tiles_across(g.local_rows);
-    if ((long long)g.tiles_x * g.tiles_y * 64 >= (1ll << 31)) return bad(text.tiles);
-    g.n_pixels = (size_t)g.local_rows * (size_t)f->nx;
-    g.work_items = (uint32_t)g.tiles_x * (uint32_t)g.tiles_y * 64u;
-    return RT_OK;
-}
-
 // where the kernels write the frame: the caller's device buffer, or the scene's image of a host buffer (`floats` floats)
 rt_status device_fb(rt_scene* s, float* fb, int fb_on_device, size_t floats, float** d_fb) {
-    if (!fb_on_device) RT_TRY(grow(s->d_fb, s->d_fb_floats, floats));
+    if (!fb_on_device) HIPCHK(s->d_fb.grow(floats));
     *d_fb = fb_on_device ? fb : s->d_fb;
     return RT_OK;
 }
@@ -959,16 +711,14 @@ rt_status build_refit_tables(rt_scene* s) {
     };
     size_t total = 0;
     for (const piece& pc : pieces) total += call_memory::rounded(pc.bytes ? pc.bytes : 1);
-    void* block = nullptr;
-    HIPCHK(hipMalloc(&block, total));
-    hipError_t e = hipMemset(block, 0, total);                         // stamps 0 (epochs start at 1), padding boxes 0
-    char* at = static_cast<char*>(block);
+    HIPCHK(t.block.grow(total));
+    hipError_t e = hipMemset(t.block, 0, total);                       // stamps 0 (epochs start at 1), padding boxes 0
+    char* at = t.block;
     for (const piece& pc : pieces) {
         *pc.dst = call_memory::take(at, pc.bytes ? pc.bytes : 1);
         if (e == hipSuccess && pc.src && pc.bytes) e = hipMemcpy(*pc.dst, pc.src, pc.bytes, hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) { (void)hipFree(block); HIPCHK(e); }
-    t.block = block;
+    if (e != hipSuccess) { t.block.adopt(nullptr, 0); HIPCHK(e); }
     rt_refit_params& p = t.p;
     memset(&p, 0, sizeof(p));
     p.n_materials = s->dev.n_materials;
@@ -1041,13 +791,13 @@ rt_status update_records(rt_scene* s, int kind, const Update* u, const std::stri
     if (++t.epoch[kind] == 0) { HIPCHK(hipMemsetAsync(p.stamp, 0, (size_t)n * 4, stream)); t.epoch[kind] = 1; }
     p.epoch = t.epoch[kind];
     if (u->indices) {
-        RT_TRY(grow(t.d_indices, t.indices_capacity, (size_t)u->count));
+        HIPCHK(t.d_indices.grow((size_t)u->count));
         HIPCHK(hipMemcpyAsync(t.d_indices, u->indices, (size_t)u->count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
         p.indices = t.d_indices;
     }
     if (on_device) p.records = rt_refit::records_of(*u);
     else {
-        RT_TRY(grow(t.d_records, t.records_capacity, bytes));
+        HIPCHK(t.d_records.grow(bytes));
         HIPCHK(hipMemcpyAsync(t.d_records, rt_refit::records_of(*u), bytes, hipMemcpyHostToDevice, stream));
         p.records = t.d_records;
     }
@@ -1128,15 +878,6 @@ rt_status rt_scene_get_quads(const rt_scene* s, rt_quad* out, int32_t cap) {
     return RT_OK;
 }
 
-rt_status rt_debug_scene_quads(const rt_scene* s, rt_quad* quads_out, int32_t quad_cap, rt_box* boxes_out, int32_t box_cap) {
-    if (!s) return invalid("rt_debug_scene_quads: null scene");
-    if ((quads_out && quad_cap < s->n_quads) || (boxes_out && box_cap < s->n_boxes)) return invalid("rt_debug_scene_quads: a cap is below the scene's count");
-    RT_TRY(use_device(s->device));
-    if (quads_out && s->n_quads) HIPCHK(hipMemcpy(quads_out, s->dev.quads, (size_t)s->n_quads * sizeof(rt_quad), hipMemcpyDeviceToHost));
-    if (boxes_out && s->n_boxes) HIPCHK(hipMemcpy(boxes_out, s->dev.boxes, (size_t)s->n_boxes * sizeof(rt_box), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
 rt_status rt_refit_nodes(const rt_scene_desc* d, const rt_sphere_update* u, rt_node* nodes_out, rt_sphere* spheres_out) {
     RT_TRY(validate_desc(d));
     const std::string why = rt_refit::check_update(u, true, d->n_spheres, d->n_materials, rt_refit::instanced_spheres(d->instances, d->n_instances, d->n_spheres));
@@ -1163,23 +904,6 @@ rt_status rt_refit_quads(const rt_scene_desc* d, const rt_quad_update* u, rt_nod
     if (!why.empty()) return invalid(("rt_refit_quads: " + why).c_str());
     std::vector<rt_quad> quads(d->quads, d->quads + d->n_quads);
     restate(d, rt_refit::QUADS, u, quads, d->spheres, d->instances, quads.data(), nodes_out, quads_out);
-    return RT_OK;
-}
-
-rt_status rt_debug_scene_boxes(const rt_scene* s, int32_t which, void* out, size_t cap, size_t* n) {
-    if (!s || !n || which < 0 || which > 5) return invalid("rt_debug_scene_boxes: bad argument");
-    const void* src = nullptr;
-    size_t bytes = 0;
-    if (which == 0) { src = s->dev.nodes_ref; bytes = (size_t)s->dev.n_nodes_ref * sizeof(rt_node); }
-    else if (which == 1) { src = s->dev.nodes; bytes = (size_t)s->dev.n_nodes * sizeof(rt_node); }
-    else if (which == 2 || which == 3) { src = which == 2 ? s->dev.leaf_lo : s->dev.leaf_hi; bytes = src ? (size_t)s->dev.n_slots * 64 * sizeof(float4) : 0; }
-    else if (which == 4) { src = s->dev.slot_ranges; bytes = src ? (size_t)s->dev.n_slots * 32 : 0; }
-    *n = which == 5 ? 12 : bytes;
-    const size_t take = std::min(*n, cap);
-    if (!out || take == 0) return RT_OK;
-    if (which == 5) { memcpy(out, s->dev.bound, take); return RT_OK; }
-    RT_TRY(use_device(s->device));
-    HIPCHK(hipMemcpy(out, src, take, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1697,414 +1421,7 @@ rt_status rt_reproject_quads(const rt_reproject_desc* d, const rt_reproject_moti
     return reproject_impl(d, m, im, qm, "rt_reproject_quads", buffers_on_device, stream_v, blocking);
 }
 
-// Tail hand-off of the last frame (diagnostics, every build): [0] pixels the main kernel handed to the tail launches, summed over
-// the frame's parts, [1] the samples those pixels still had to go.
-rt_status rt_debug_handoff(rt_scene* s, unsigned long long* out2) {
-    if (!s || !out2) return invalid("null argument");
-    RT_TRY(use_device(s->device));
-    HIPCHK(hipMemcpy(out2, s->d_ray_counter + 28, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// The hand-off queue of the last frame's last part, in push order (diagnostics, every build; tools/tail_order_stats.py): up to `cap`
-// entries (next sample << 32 | pixel), entry for entry the parked cost handoff_state[pixel].cost, and the queue as the tail launch
-// was given it (`served`: ordered, copied through, or -- handoff_order = 0 -- the queue itself).  info4: [0] entries the queue
-// holds, [1] 1 = the ordering kernels ran, [2] and [3] the counts between which they order (rt_handoff_order.h).  A pending
-// frame must have been closed.
-rt_status rt_debug_handoff_queue(rt_scene* s, unsigned long long* entries, uint32_t* costs, unsigned long long* served, int64_t cap, int64_t* info4) {
-    if (!s || !info4 || cap < 0 || (cap > 0 && (!entries || !costs || !served))) return invalid("rt_debug_handoff_queue: bad argument");
-    if (s->frame_pending) return invalid("rt_debug_handoff_queue: a frame is pending (rt_frame_finish first)");
-    info4[0] = 0; info4[1] = s->plan.tail_ordered ? 1 : 0; info4[2] = s->plan.order_min; info4[3] = s->plan.order_max;
-    int64_t* const count_out = info4;
-    if (!s->d_handoff || !s->d_state || !s->plan.ranked) return RT_OK;
-    RT_TRY(use_device(s->device));
-    unsigned int pushed = 0;
-    HIPCHK(hipMemcpy(&pushed, s->d_work_counter + RT_WC_PUSHED, sizeof(pushed), hipMemcpyDeviceToHost));
-    const size_t count = pushed < s->handoff_capacity ? pushed : s->handoff_capacity;
-    *count_out = (int64_t)count;
-    const size_t n = count < (size_t)cap ? count : (size_t)cap;
-    if (n == 0) return RT_OK;
-    HIPCHK(hipMemcpy(entries, s->d_handoff, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(served, s->plan.tail_ordered ? s->d_handoff_ordered : s->d_handoff, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    std::vector<rt_pixel_state> h_state(s->pixel_capacity);
-    HIPCHK(hipMemcpy(h_state.data(), s->d_state, h_state.size() * sizeof(rt_pixel_state), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t pix = (uint32_t)entries[i];
-        costs[i] = pix < h_state.size() ? h_state[pix].cost : 0u;
-    }
-    return RT_OK;
-}
-
-// Test seam of the queue ordering (rt_handoff_order.h; tests/test_handoff_order.py): the launch rt_render makes between the main
-// kernel and the tail launch, once, on n caller-supplied entries (next sample << 32 | pixel, every pixel below n) whose parked
-// costs are costs[pixel], for a tail launch of tail_waves waves and a part rendering [sample_begin, sample_end).  Null stream, synchronous.
-// The queue holds exactly n entries and the push counter stands ORDER_SEAM_SLACK beyond, as after a main kernel whose lanes found
-// the queue full; both device buffers have that many spare slots behind them, and *overrun_out = how many of the ordered
-// buffer's were written (0 unless the count was read unclipped).
-enum { ORDER_SEAM_SLACK = 3 };
-rt_status rt_debug_order_handoff(const unsigned long long* entries, const uint32_t* costs, int64_t n, int32_t sample_begin, int32_t sample_end,
-                                 int32_t tail_waves, unsigned long long* out, uint32_t* overrun_out) {
-    if (!overrun_out) return invalid("rt_debug_order_handoff: null argument");
-    if (n < 0 || n > (1ll << 24) || (n > 0 && (!entries || !costs || !out))) return invalid("rt_debug_order_handoff: n must be 0 .. 2^24 and the arrays non-null");
-    if (sample_begin < 0 || sample_end < sample_begin) return invalid("rt_debug_order_handoff: bad sample range");
-    if (tail_waves < 1 || tail_waves > (1 << 20)) return invalid("rt_debug_order_handoff: tail_waves must be 1 .. 2^20");
-    for (int64_t i = 0; i < n; ++i)
-        if ((int64_t)(uint32_t)entries[i] >= n) return invalid("rt_debug_order_handoff: an entry's pixel is not below n");
-    RT_TRY(use_device(g_device));
-    call_memory mem;
-    rt_handoff_order_params hp;
-    memset(&hp, 0, sizeof(hp));
-    const size_t most = (size_t)RT_HANDOFF_ORDER_MAX_PER_WAVE * (size_t)tail_waves;
-    hp.cap = (uint32_t)n; hp.min_items = (uint32_t)(RT_HANDOFF_ORDER_MIN_PER_WAVE * tail_waves); hp.max_items = (uint32_t)(most < (size_t)n ? most : (size_t)n);
-    hp.cost_begin = sample_begin; hp.sample_end = sample_end;
-    unsigned long long *d_queue = nullptr, *d_ordered = nullptr;
-    rt_pixel_state* d_state = nullptr;
-    unsigned int* d_pushed = nullptr;
-    const size_t scratch_bytes = rt_handoff_order_scratch_words(hp.max_items) * sizeof(unsigned int);
-    HIPCHK(mem.get((void**)&d_queue, (size_t)(n + ORDER_SEAM_SLACK) * sizeof(unsigned long long)));
-    HIPCHK(mem.get((void**)&d_ordered, (size_t)(n + ORDER_SEAM_SLACK) * sizeof(unsigned long long)));
-    HIPCHK(mem.get((void**)&d_state, (size_t)(n + 1) * sizeof(rt_pixel_state)));
-    HIPCHK(mem.get((void**)&d_pushed, sizeof(unsigned int)));
-    HIPCHK(mem.get((void**)&hp.scratch, scratch_bytes));
-    std::vector<rt_pixel_state> h_state((size_t)n + 1);                // (value-initialised)
-    for (int64_t i = 0; i < n; ++i) h_state[(size_t)i].cost = costs[i];
-    const unsigned int h_pushed = (unsigned int)n + ORDER_SEAM_SLACK;
-    HIPCHK(hipMemset(d_queue, 0, (size_t)(n + ORDER_SEAM_SLACK) * sizeof(unsigned long long)));     // spare slots: sample 0 of pixel 0
-    if (n > 0) HIPCHK(hipMemcpy(d_queue, entries, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_state, h_state.data(), h_state.size() * sizeof(rt_pixel_state), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_ordered, 0xFF, (size_t)(n + ORDER_SEAM_SLACK) * sizeof(unsigned long long)));
-    HIPCHK(hipMemcpy(d_pushed, &h_pushed, sizeof(h_pushed), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(hp.scratch, 0, scratch_bytes));
-    hp.queue = d_queue; hp.ordered = d_ordered; hp.state = d_state; hp.pushed = d_pushed;
-    HIPCHK(rt_launch_handoff_order(hp, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    if (n > 0) HIPCHK(hipMemcpy(out, d_ordered, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    unsigned long long spare[ORDER_SEAM_SLACK];
-    HIPCHK(hipMemcpy(spare, d_ordered + n, sizeof(spare), hipMemcpyDeviceToHost));
-    *overrun_out = 0u;
-    for (const unsigned long long w : spare) *overrun_out += w != ~0ull ? 1u : 0u;
-    return RT_OK;
-}
-
-// Diagnostic builds (-DRT_DIAG) leave per-stage execution counts behind the ray counter; 16 values.
-rt_status rt_debug_counters(rt_scene* s, unsigned long long* out16) {
-    if (!s || !out16) return invalid("null argument");
-    RT_TRY(use_device(s->device));
-    HIPCHK(hipMemcpy(out16, s->d_ray_counter + 1, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-// Diagnostic builds: cycles the waves of the frame spent per part of the staged kernel's loop, summed over waves
-// ([0] box steps, [1] object tests, [2] stage C, [3] D, [4] E, [6] stage gating, [7] stage F + loop; then, first wave of each
-// tier workgroup: [8] resolve + shade in the tier loops, [9] the whole tier loop; shader-clock cycles).
-rt_status rt_debug_stage_cycles(rt_scene* s, unsigned long long* out10) {
-    if (!s || !out10) return invalid("null argument");
-    RT_TRY(use_device(s->device));
-    HIPCHK(hipMemcpy(out10, s->d_ray_counter + 17, 10 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-// Diagnostic builds: when the waves of the LAST launch ended, as two histograms of RT_DIAG_BINS bins of 1 ms after the first
-// wave's start (ordinary waves, then waves that started in sparse / tier mode).
-rt_status rt_debug_wave_ends(rt_scene* s, unsigned long long* out, int n) {
-    if (!s || !out || n < 0 || n > 2 * RT_DIAG_BINS) return invalid("bad argument");
-    RT_TRY(use_device(s->device));
-    HIPCHK(hipMemcpy(out, s->d_ray_counter + RT_DIAG_HIST_SLOT, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-// ... and per wave of the last launch, two words about the lane that ran out of work last: (done_us << 32 | fetch_us of its last
-// pixel), (source queue << 60 | started sparse << 59 | local pixel id)
-rt_status rt_debug_wave_last(rt_scene* s, unsigned long long* out, int n_waves) {
-    if (!s || !out || n_waves < 0 || n_waves > RT_DIAG_MAX_WAVES) return invalid("bad argument");
-    RT_TRY(use_device(s->device));
-    HIPCHK(hipMemcpy(out, s->d_ray_counter + RT_DIAG_WAVE_SLOT, (size_t)2 * n_waves * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// ---- test seams of the ranking and the cost prior (rt_rank.hip; tests/test_rank.py): the launches rt_render makes, once, on
-// caller-supplied host data.  Null stream, synchronous; every check runs before any HIP call.
 namespace {
-enum { RANK_PARAM_WORDS = 20, RANK_INFO_WORDS = 13 };
-static_assert(sizeof(rt_rank_info) == RANK_INFO_WORDS * 4, "rt_debug_rank / rt_debug_rank_info copy rt_rank_info as 13 words");
-}  // namespace
-
-rt_status rt_debug_rank(const uint32_t* cost, const uint32_t* tile_cost, uint64_t rays, const uint32_t* params, uint32_t* tile_order,
-                        uint32_t* cost_out, uint32_t* heavy_pixels, uint32_t* info13) {
-    if (!cost || !tile_cost || !params || !tile_order || !cost_out || !heavy_pixels || !info13) return invalid("rt_debug_rank: null argument");
-    rt_rank_params rp;
-    memset(&rp, 0, sizeof(rp));
-    const int32_t* ip = reinterpret_cast<const int32_t*>(params);
-    rp.n_pixels = params[0]; rp.n_tiles = params[1]; rp.heavy_cap = params[2];
-    rp.max_grid = params[3]; rp.waves_per_wg = params[4]; rp.normal_need = params[5];
-    rp.sparse_stride = ip[6]; rp.semi_stride = ip[7]; rp.sparse_percent = ip[8]; rp.sparse_work_percent = ip[9];
-    rp.tier_possible = ip[10]; rp.tier1_pixels = ip[11]; rp.tier1_depth = ip[12]; rp.tier_wgs_cap = ip[13];
-    rp.tier_waves_per_main_wg = ip[14]; rp.nx = ip[15]; rp.smooth_percent = ip[16];
-    memcpy(&rp.heavy_factor, params + 17, 4); memcpy(&rp.sparse_factor, params + 18, 4); memcpy(&rp.tier1_factor, params + 19, 4);
-    if (rp.n_pixels < 1u || rp.n_pixels >= (1u << 31)) return invalid("rt_debug_rank: n_pixels must be 1 .. 2^31 - 1");
-    if (rp.n_tiles < 1u || rp.n_tiles > rp.n_pixels) return invalid("rt_debug_rank: n_tiles must be 1 .. n_pixels");
-    if (rp.heavy_cap < 1u || rp.heavy_cap > (1u << 24)) return invalid("rt_debug_rank: heavy_cap must be 1 .. 2^24");
-    if (rp.max_grid > (1u << 20) || rp.normal_need > (1u << 20)) return invalid("rt_debug_rank: max_grid and normal_need must be at most 2^20");
-    if (rp.waves_per_wg < 1u || rp.waves_per_wg > 16u) return invalid("rt_debug_rank: waves_per_wg must be 1 .. 16");
-    if (rp.sparse_stride < 0 || rp.sparse_stride > 64 || rp.semi_stride < 0 || rp.semi_stride > 64) return invalid("rt_debug_rank: sparse_stride and semi_stride must be 0 .. 64");
-    if (rp.sparse_percent < 0 || rp.sparse_percent > 100 || rp.sparse_work_percent < 0 || rp.sparse_work_percent > 100 || rp.smooth_percent < 0 || rp.smooth_percent > 100)
-        return invalid("rt_debug_rank: sparse_percent, sparse_work_percent and smooth_percent must be 0 .. 100");
-    if (rp.tier1_pixels < 0 || rp.tier1_depth < 0 || rp.tier1_depth > 65536 || rp.tier_wgs_cap < 0 || rp.tier_waves_per_main_wg < 0)
-        return invalid("rt_debug_rank: tier1_pixels, tier1_depth (at most 65536), tier_wgs_cap and tier_waves_per_main_wg must not be negative");
-    if (rp.nx < 1 || (uint32_t)rp.nx > rp.n_pixels) return invalid("rt_debug_rank: nx must be 1 .. n_pixels");
-    float top = 0.f;
-    for (const float fac : {rp.heavy_factor, rp.sparse_factor, rp.tier1_factor}) {
-        if (!(fac >= 0.f) || !(fac <= 1000.f)) return invalid("rt_debug_rank: the three factors must be 0 .. 1000");
-        top = fac > top ? fac : top;
-    }
-    if (!((double)rays / (double)rp.n_pixels * (double)top + 1.0 < 4294967296.0)) return invalid("rt_debug_rank: rays / n_pixels x the largest factor must stay below 2^32");
-    RT_TRY(use_device(g_device));
-    call_memory mem;
-    unsigned int *d_tile_cost = nullptr, *d_tile_order = nullptr;
-    unsigned long long* d_rays = nullptr;
-    HIPCHK(mem.get((void**)&rp.state, (size_t)rp.n_pixels * sizeof(rt_pixel_state)));
-    HIPCHK(mem.get((void**)&d_tile_cost, (size_t)rp.n_tiles * sizeof(unsigned int)));
-    HIPCHK(mem.get((void**)&d_tile_order, (size_t)rp.n_tiles * sizeof(unsigned int)));
-    HIPCHK(mem.get((void**)&d_rays, sizeof(unsigned long long)));
-    HIPCHK(mem.get((void**)&rp.heavy_list, (size_t)rp.heavy_cap * sizeof(unsigned long long)));
-    HIPCHK(mem.get((void**)&rp.heavy_pixels, (size_t)rp.heavy_cap * sizeof(unsigned int)));
-    HIPCHK(mem.get((void**)&rp.info, sizeof(rt_rank_info)));
-    rp.tile_cost = d_tile_cost; rp.tile_order = d_tile_order; rp.ray_counter = d_rays;
-    std::vector<rt_pixel_state> h_state(rp.n_pixels);                  // (value-initialised: every field but the cost is zero)
-    for (uint32_t i = 0; i < rp.n_pixels; ++i) h_state[i].cost = cost[i];
-    const unsigned long long h_rays = rays;
-    HIPCHK(hipMemcpy(rp.state, h_state.data(), (size_t)rp.n_pixels * sizeof(rt_pixel_state), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_tile_cost, tile_cost, (size_t)rp.n_tiles * sizeof(unsigned int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_rays, &h_rays, sizeof(h_rays), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_tile_order, 0xFF, (size_t)rp.n_tiles * sizeof(unsigned int)));
-    HIPCHK(hipMemset(rp.heavy_list, 0xFF, (size_t)rp.heavy_cap * sizeof(unsigned long long)));
-    HIPCHK(hipMemset(rp.heavy_pixels, 0xFF, (size_t)rp.heavy_cap * sizeof(unsigned int)));   // entries the ranking does not write stay 0xFFFFFFFF
-    HIPCHK(hipMemset(rp.info, 0xFF, sizeof(rt_rank_info)));
-    HIPCHK(rt_launch_rank(rp, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(h_state.data(), rp.state, (size_t)rp.n_pixels * sizeof(rt_pixel_state), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < rp.n_pixels; ++i) cost_out[i] = h_state[i].cost;
-    HIPCHK(hipMemcpy(tile_order, d_tile_order, (size_t)rp.n_tiles * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(heavy_pixels, rp.heavy_pixels, (size_t)rp.heavy_cap * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(info13, rp.info, sizeof(rt_rank_info), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-rt_status rt_debug_prior(const uint32_t* cal_cost, int32_t cal_nx, int32_t cal_ny, int32_t nx, int32_t ny, int32_t tile_rows, int32_t tile_first,
-                         int32_t tile_stride, uint32_t* cost_out, uint32_t* tile_cost_out, uint64_t* total_out) {
-    if (!cal_cost || !cost_out || !tile_cost_out || !total_out) return invalid("rt_debug_prior: null argument");
-    if (cal_nx < 1 || cal_ny < 1 || (long long)cal_nx * cal_ny >= (1ll << 31)) return invalid("rt_debug_prior: bad calibration grid size");
-    rt_frame_desc f;
-    memset(&f, 0, sizeof(f));
-    f.nx = nx; f.ny = ny; f.tile_rows = tile_rows; f.tile_first = tile_first; f.tile_stride = tile_stride;
-    frame_geometry g;
-    RT_TRY(check_frame("rt_debug_prior", &f, false, STATE_FRAME_TEXTS, g));
-    if (g.local_rows == 0) return invalid("rt_debug_prior: the partition has no rows");
-    RT_TRY(use_device(g_device));
-    rt_prior_params pp;
-    memset(&pp, 0, sizeof(pp));
-    pp.cal_nx = cal_nx; pp.cal_ny = cal_ny; pp.nx = nx; pp.ny = ny; pp.local_rows = g.local_rows; pp.tiles_x = g.tiles_x;
-    pp.tile_rows = tile_rows; pp.tile_first = tile_first; pp.tile_stride = tile_stride;
-    const size_t n_pixels = g.n_pixels, n_tiles = (size_t)g.tiles_x * (size_t)g.tiles_y, n_cal = (size_t)cal_nx * (size_t)cal_ny;
-    call_memory mem;
-    unsigned int* d_cal = nullptr;
-    HIPCHK(mem.get((void**)&pp.state, n_pixels * sizeof(rt_pixel_state)));
-    HIPCHK(mem.get((void**)&pp.tile_cost, n_tiles * sizeof(unsigned int)));
-    HIPCHK(mem.get((void**)&pp.total, sizeof(unsigned long long)));
-    HIPCHK(mem.get((void**)&d_cal, n_cal * sizeof(unsigned int)));
-    pp.cal_cost = d_cal;
-    HIPCHK(hipMemcpy(d_cal, cal_cost, n_cal * sizeof(unsigned int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(pp.state, 0xFF, n_pixels * sizeof(rt_pixel_state)));          // a pixel the kernel skips shows as 0xFFFFFFFF
-    HIPCHK(hipMemset(pp.tile_cost, 0, n_tiles * sizeof(unsigned int)));            // (the kernel adds to both, as in rt_render)
-    HIPCHK(hipMemset(pp.total, 0, sizeof(unsigned long long)));
-    HIPCHK(rt_launch_prior(pp, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<rt_pixel_state> h_state(n_pixels);
-    HIPCHK(hipMemcpy(h_state.data(), pp.state, n_pixels * sizeof(rt_pixel_state), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n_pixels; ++i) cost_out[i] = h_state[i].cost;
-    HIPCHK(hipMemcpy(tile_cost_out, pp.tile_cost, n_tiles * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    unsigned long long total = 0;
-    HIPCHK(hipMemcpy(&total, pp.total, sizeof(total), hipMemcpyDeviceToHost));
-    *total_out = total;
-    return RT_OK;
-}
-
-rt_status rt_debug_box_tests(int32_t n, const float* bmin, const float* bmax, const float* origins, const float* directions,
-                             const float* tmin, const float* tmax, const float* bound3, uint8_t* flags) {
-    if (!bmin || !bmax || !origins || !directions || !tmin || !tmax || !bound3 || !flags) return invalid("rt_debug_box_tests: null argument");
-    if (n < 1 || n > (1 << 24)) return invalid("rt_debug_box_tests: n must be 1 .. 2^24");
-    for (int k = 0; k < 3; ++k)
-        if (!(bound3[k] >= 0.f) || !std::isfinite(bound3[k])) return invalid("rt_debug_box_tests: bound3 must be finite and not negative");
-    RT_TRY(use_device(g_device));
-    rt_box_test_params bp;
-    memset(&bp, 0, sizeof(bp));
-    bp.n = n;
-    for (int k = 0; k < 3; ++k) bp.bound[k] = bound3[k];
-    const size_t n3 = (size_t)n * 3 * sizeof(float), n1 = (size_t)n * sizeof(float);
-    call_memory mem;
-    const struct { const float** dev; const float* host; size_t bytes; } in[] = {
-        {&bp.bmin, bmin, n3}, {&bp.bmax, bmax, n3}, {&bp.origins, origins, n3}, {&bp.directions, directions, n3}, {&bp.tmin, tmin, n1}, {&bp.tmax, tmax, n1}};
-    for (const auto& b : in) {
-        HIPCHK(mem.get((void**)b.dev, b.bytes));
-        HIPCHK(hipMemcpy((void*)*b.dev, b.host, b.bytes, hipMemcpyHostToDevice));
-    }
-    HIPCHK(mem.get((void**)&bp.flags, (size_t)n * 4));
-    HIPCHK(hipMemset(bp.flags, 0xFF, (size_t)n * 4));   // a case the kernel skipped would show as 255
-    HIPCHK(rt_launch_box_tests(bp, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(flags, bp.flags, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-rt_status rt_debug_arith_tests(int32_t mode, int64_t n, const float* a, const float* b, const float* bound3, uint8_t* path, uint64_t* out3) {
-    if (mode < RT_ARITH_UNIFORM || mode > RT_ARITH_LOOSE) return invalid("rt_debug_arith_tests: unknown mode");
-    const bool draws = mode == RT_ARITH_UNIFORM || mode == RT_ARITH_SIGNED;
-    if (!out3 || (!draws && (!a || !b || !bound3))) return invalid("rt_debug_arith_tests: null argument");
-    if (draws && path) return invalid("rt_debug_arith_tests: the draw modes report no path");
-    if (draws ? (n < 1 || n > (1ll << 32)) : (n < 1 || n > (1 << 24))) return invalid(draws ? "rt_debug_arith_tests: n must be 1 .. 2^32" : "rt_debug_arith_tests: n must be 1 .. 2^24");
-    if (!draws)
-        for (int k = 0; k < 3; ++k)
-            if (!(bound3[k] >= 0.f) || !std::isfinite(bound3[k])) return invalid("rt_debug_arith_tests: bound3 must be finite and not negative");
-    RT_TRY(use_device(g_device));
-    rt_arith_test_params ap;
-    memset(&ap, 0, sizeof(ap));
-    ap.mode = mode; ap.n = n;
-    call_memory mem;
-    if (!draws) {
-        for (int k = 0; k < 3; ++k) ap.bound[k] = bound3[k];
-        const size_t n3 = (size_t)n * 3 * sizeof(float);
-        HIPCHK(mem.get((void**)&ap.a, n3));
-        HIPCHK(hipMemcpy((void*)ap.a, a, n3, hipMemcpyHostToDevice));
-        HIPCHK(mem.get((void**)&ap.b, n3));
-        HIPCHK(hipMemcpy((void*)ap.b, b, n3, hipMemcpyHostToDevice));
-        if (path) {
-            HIPCHK(mem.get((void**)&ap.path, (size_t)n));
-            HIPCHK(hipMemset(ap.path, 0xFF, (size_t)n));   // a case the kernel skipped would show as 255
-        }
-    }
-    const unsigned long long init[3] = {0ull, ~0ull, 0ull};
-    HIPCHK(mem.get((void**)&ap.out, sizeof(init)));
-    HIPCHK(hipMemcpy(ap.out, init, sizeof(init), hipMemcpyHostToDevice));
-    HIPCHK(rt_launch_arith_tests(ap, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    unsigned long long got[3];
-    HIPCHK(hipMemcpy(got, ap.out, sizeof(got), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; ++k) out3[k] = got[k];
-    if (path) HIPCHK(hipMemcpy(path, ap.path, (size_t)n, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-rt_status rt_debug_math_tests(int32_t form, int32_t fn, uint32_t first, int64_t count, float operand, const float* a, const float* b,
-                              const float* c, float* out, uint64_t* digests) {
-    if (form != RT_MATH_SWEEP && form != RT_MATH_LIST) return invalid("rt_debug_math_tests: unknown form");
-    if (fn < RT_MATH_LOG || fn > RT_MATH_MULADD) return invalid("rt_debug_math_tests: unknown function");
-    const bool sweep = form == RT_MATH_SWEEP;
-    const bool reads_b = fn == RT_MATH_ATAN2 || fn == RT_MATH_POW || fn == RT_MATH_DIV || fn == RT_MATH_MULADD, reads_c = fn == RT_MATH_MULADD;
-    if (sweep) {
-        if (reads_b && fn != RT_MATH_POW) return invalid("rt_debug_math_tests: a sweep takes a function of one input, or RT_MATH_POW");
-        if (!digests) return invalid("rt_debug_math_tests: null argument");
-        if (a || b || c || out) return invalid("rt_debug_math_tests: a sweep reads no array and writes digests only");
-        if (count < 1 || count > (1ll << 32) || (int64_t)first + count > (1ll << 32)) return invalid("rt_debug_math_tests: count must be 1 .. 2^32 and first + count at most 2^32");
-        if (fn == RT_MATH_POW && (!(operand > 0.f) || !std::isfinite(operand))) return invalid("rt_debug_math_tests: gamma must be finite and positive");
-    } else {
-        if (!a || !out || (reads_b && !b) || (reads_c && !c)) return invalid("rt_debug_math_tests: null argument");
-        if (digests) return invalid("rt_debug_math_tests: a list writes out only");
-        if (count < 1 || count > (1 << 24) || first != 0u) return invalid("rt_debug_math_tests: count must be 1 .. 2^24 and first 0");
-    }
-    RT_TRY(use_device(g_device));
-    rt_math_test_params mp;
-    memset(&mp, 0, sizeof(mp));
-    mp.form = form; mp.fn = fn; mp.first = first; mp.count = count; mp.operand = operand;
-    call_memory mem;
-    const size_t n_digests = (size_t)((count + (1ll << 20) - 1) >> 20), list_bytes = (size_t)count * sizeof(float);
-    if (sweep) {
-        HIPCHK(mem.get((void**)&mp.digests, n_digests * sizeof(unsigned long long)));
-        HIPCHK(hipMemset(mp.digests, 0, n_digests * sizeof(unsigned long long)));
-    } else {
-        const struct { const float** dev; const float* host; } in[] = {{&mp.a, a}, {&mp.b, reads_b ? b : nullptr}, {&mp.c, reads_c ? c : nullptr}};
-        for (const auto& v : in) {
-            if (!v.host) continue;
-            HIPCHK(mem.get((void**)v.dev, list_bytes));
-            HIPCHK(hipMemcpy((void*)*v.dev, v.host, list_bytes, hipMemcpyHostToDevice));
-        }
-        HIPCHK(mem.get((void**)&mp.out, list_bytes));
-        HIPCHK(hipMemset(mp.out, 0xFF, list_bytes));   // an element the kernel skipped would show as a NaN with payload
-    }
-    HIPCHK(rt_launch_math_tests(mp, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    if (sweep) HIPCHK(hipMemcpy(digests, mp.digests, n_digests * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    else HIPCHK(hipMemcpy(out, mp.out, list_bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-rt_status rt_debug_cal_cost(rt_scene* s, uint32_t* out, int32_t cap, int32_t* nx, int32_t* ny) {
-    if (!s) return invalid("rt_debug_cal_cost: null scene");
-    if (!out || !nx || !ny) return invalid("rt_debug_cal_cost: null argument");
-    if (cap < 64) return invalid("rt_debug_cal_cost: cap must be at least 64 (the smallest calibration grid is 8 x 8)");
-    if (!s->d_cal_cost || s->cal_nx <= 0 || s->cal_ny <= 0) return invalid("rt_debug_cal_cost: the scene kept no calibration costs");
-    *nx = s->cal_nx; *ny = s->cal_ny;
-    if ((long long)cap < (long long)s->cal_nx * s->cal_ny) return invalid("rt_debug_cal_cost: cap is smaller than the calibration grid (nx and ny are set)");
-    RT_TRY(use_device(s->device));
-    HIPCHK(hipMemcpy(out, s->d_cal_cost, (size_t)s->cal_nx * s->cal_ny * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-rt_status rt_debug_cost_map(rt_scene* s, uint32_t* out, int64_t cap, int32_t* info4) {
-    if (!s) return invalid("rt_debug_cost_map: null scene");
-    if (!info4 || (!out && cap != 0)) return invalid("rt_debug_cost_map: null argument");
-    RT_TRY(use_device(s->device));
-    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
-    const rt_scene::cost_map_state& cm = s->cost_map;
-    const bool have = g_opt.cost_map && cm.valid;
-    info4[0] = !have ? 0 : (cm.scene_epoch == s->scene_epoch && cm.opt_epoch == g_opt_epoch ? 1 : 2);
-    info4[1] = have ? cm.key.nx : 0; info4[2] = have ? cm.key.local_rows : 0; info4[3] = s->plan.ranked_parts;
-    if (!have || !out) return RT_OK;
-    const long long n = (long long)cm.key.nx * cm.key.local_rows;
-    if ((long long)cap < n) return invalid("rt_debug_cost_map: cap is smaller than the map (info is set)");
-    HIPCHK(hipMemcpy(out, cm.d, (size_t)n * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-rt_status rt_debug_set_cost_map(rt_scene* s, const uint32_t* in, int64_t n) {
-    if (!s) return invalid("rt_debug_set_cost_map: null scene");
-    if (!in) return invalid("rt_debug_set_cost_map: null argument");
-    if (!g_opt.cost_map) return invalid("rt_debug_set_cost_map: option cost_map is 0");
-    rt_scene::cost_map_state& cm = s->cost_map;
-    if (!cm.have_last_key) return invalid("rt_debug_set_cost_map: the scene has rendered no ranked frame");
-    if ((long long)n != (long long)cm.last_key.nx * cm.last_key.local_rows) return invalid("rt_debug_set_cost_map: n is not the last ranked frame's local pixel count");
-    RT_TRY(use_device(s->device));
-    if (s->frame_pending) RT_TRY(rt_frame_finish(s, nullptr));
-    std::vector<unsigned int> words((size_t)n);
-    unsigned long long total = 0;
-    for (size_t k = 0; k < (size_t)n; ++k) { words[k] = in[k] & 0x7FFFFFFFu; total += words[k]; }
-    cm.valid = false;
-    RT_TRY(grow(cm.d, cm.capacity, (size_t)n));
-    HIPCHK(hipMemcpy(cm.d, words.data(), (size_t)n * sizeof(unsigned int), hipMemcpyHostToDevice));
-    cm.key = cm.last_key; cm.scene_epoch = s->scene_epoch; cm.opt_epoch = g_opt_epoch; cm.total = total; cm.valid = true;
-    return RT_OK;
-}
-
-rt_status rt_debug_rank_info(rt_scene* s, uint32_t* out13) {
-    if (!s) return invalid("rt_debug_rank_info: null scene");
-    if (!out13) return invalid("rt_debug_rank_info: null argument");
-    if (!s->plan.ranked || !s->d_rank) return invalid("rt_debug_rank_info: the scene's last frame was not ranked");
-    RT_TRY(use_device(s->device));
-    if (s->frame_pending) HIPCHK(hipStreamSynchronize(s->pending_stream));
-    HIPCHK(hipMemcpy(out13, s->d_rank, sizeof(rt_rank_info), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-namespace {
-// What the plans of rt_frame_plan.h read of the scene and its device.
-plan_facts plan_facts_of(const rt_scene* s) {
-    const device_info& d = g_devices[s->device];
-    plan_facts c;
-    c.num_cu = d.num_cu; c.lds_per_cu = d.lds_per_cu;
-    c.spheres_only = s->spheres_only; c.tex_level = s->tex_level;
-    c.node_bytes = s->node_bytes; c.sphere_bytes = s->sphere_bytes; c.shade_bytes = s->shade_bytes; c.n_nodes = s->dev.n_nodes;
-    c.tier_data = s->dev.leaf_lo != nullptr;
-    c.n_slots = s->dev.n_slots; c.n_spheres = s->dev.n_spheres; c.n_materials = s->dev.n_materials; c.n_textures = s->dev.n_textures;
-    c.calibrated = s->d_cal_cost && s->cal_nx > 0 && s->cal_ny > 0;
-    c.handoff_capacity = s->handoff_capacity;
-    return c;
-}
 // The main kernel's launch shape (plan_main_launch) under the current options, its stage quorums written to fp; a refusal is the
 // caller's result.
 rt_status main_launch_of(const plan_facts& c, int kernel, size_t n_pixels, rt_frame_params& fp, main_launch& ml) {
@@ -2147,18 +1464,7 @@ hipError_t launch_tier(const rt_scene* s, const rt_frame_params& fp, dim3 grid, 
                            : rt_launch_tier_general(s->tex_level, s->need_uv, s->dev, fp, grid, lds, stream);
 }
 
-// The buffers of a ranked frame (rt_scene), cached and grown together: tile costs and order, the parked pixels, the heavy list
-// unsorted and sorted, the tier sizes.
-enum { RT_HEAVY_CAP = 262144 };
-rt_status grow_ranked_buffers(rt_scene* s, size_t n_tiles, size_t n_pixels) {
-    if (s->tile_capacity >= n_tiles && s->pixel_capacity >= n_pixels && s->d_rank) return RT_OK;
-    s->tile_capacity = s->pixel_capacity = 0;
-    RT_TRY(reallocate({{(void**)&s->d_tile_cost, n_tiles * sizeof(unsigned int)}, {(void**)&s->d_tile_order, n_tiles * sizeof(unsigned int)},
-                       {(void**)&s->d_state, n_pixels * sizeof(rt_pixel_state)}, {(void**)&s->d_heavy_list, (size_t)RT_HEAVY_CAP * sizeof(unsigned long long)},
-                       {(void**)&s->d_heavy_pixels, (size_t)RT_HEAVY_CAP * sizeof(unsigned int)}, {(void**)&s->d_rank, sizeof(rt_rank_info)}}));
-    s->tile_capacity = n_tiles; s->pixel_capacity = n_pixels;
-    return RT_OK;
-}
+enum { RT_HEAVY_CAP = 262144 };   // entries of the heavy list, unsorted and sorted
 
 // The end of a synchronous frame (rt_render_adaptive, rt_render_variance), after its last enqueue: the wait, the time between
 // ev_start and ev_stop, the ray counter, and the statistics, which stay in the scene as rt_render's do.  `passes` is what
@@ -2194,7 +1500,7 @@ rt_status rt_progressive_state_create(rt_scene* s, const rt_frame_desc* f, void*
     RT_TRY(check_frame(nullptr, f, false, STATE_FRAME_TEXTS, g));
     rt_progressive* p = new rt_progressive;
     p->scene = s; p->frame = *f; p->pixels = g.n_pixels; p->next_sample = 0;
-    const hipError_t e = hipMalloc((void**)&p->d_state, (p->pixels ? p->pixels : 1) * sizeof(rt_pixel_state));
+    const hipError_t e = (hipError_t)p->d_state.grow(p->pixels ? p->pixels : 1);
     if (e != hipSuccess) { delete p; g_last_hip_error = (int)e; g_detail = "allocating the progressive state failed"; return RT_ERR_HIP; }
     *state = p;
     return RT_OK;
@@ -2204,7 +1510,6 @@ rt_status rt_progressive_state_destroy(rt_scene* s, void* state) {
     if (!state) return RT_OK;
     rt_progressive* p = static_cast<rt_progressive*>(state);
     if (s) (void)use_device(s->device);
-    if (p->d_state) (void)hipFree(p->d_state);
     delete p;
     return RT_OK;
 }
@@ -2384,12 +1689,17 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     HIPCHK(hipMemsetAsync(s->d_ray_counter, 0, 256, stream));
     // ---- grow the buffers the plan names
     if (plan.ranked) {
-        RT_TRY(grow_ranked_buffers(s, plan.ranked_tiles, plan.ranked_pixels));
-        if (cm.capacity < plan.cost_map_pixels) { cm.valid = false; RT_TRY(grow(cm.d, cm.capacity, plan.cost_map_pixels)); }
-        if (plan.handoff_capacity) RT_TRY(grow(s->d_handoff, s->handoff_capacity, plan.handoff_capacity));
+        HIPCHK(s->d_tile_cost.grow(plan.ranked_tiles));
+        HIPCHK(s->d_tile_order.grow(plan.ranked_tiles));
+        HIPCHK(s->d_state.grow(plan.ranked_pixels));
+        HIPCHK(s->d_heavy_list.grow(RT_HEAVY_CAP));
+        HIPCHK(s->d_heavy_pixels.grow(RT_HEAVY_CAP));
+        HIPCHK(s->d_rank.grow(1));
+        RT_TRY(cm.grow(plan.cost_map_pixels));
+        HIPCHK(s->d_handoff.grow(plan.handoff_capacity));
         if (plan.tail_ordered) {
-            RT_TRY(grow(s->d_handoff_ordered, s->handoff_ordered_capacity, plan.handoff_ordered_capacity));
-            RT_TRY(grow(s->d_handoff_scratch, s->handoff_scratch_capacity, plan.handoff_scratch_words));
+            HIPCHK(s->d_handoff_ordered.grow(plan.handoff_ordered_capacity));
+            HIPCHK(s->d_handoff_scratch.grow(plan.handoff_scratch_words));
         }
         cm.last_key = plan.key; cm.have_last_key = true;
         if (plan.cost_out) { cm.valid = false; cm.key = plan.key; cm.scene_epoch = s->scene_epoch; cm.opt_epoch = g_opt_epoch; }
@@ -2413,43 +1723,6 @@ static rt_status render_impl(rt_scene* s, const rt_frame_desc* f, float* fb, int
     }
     if (blocking) return rt_frame_finish(s, stats);
     if (stats) *stats = out;
-    return RT_OK;
-}
-
-// The tier kernel's room as rt_render plans it for this scene under the current options (diagnostics, every build;
-// tests/test_kernel_matrix.py): plan_frame's tier_room -- out4 = fits, lds_scene (which instantiation of the tier kernel a tier or
-// tail launch takes), the LDS image's bytes and the tail launch's grid.  The room depends on the scene, the device and the
-// options, not on the frame, so the plan is made for the smallest ranked frame (64 tiles of 8 x 8 pixels).  Host only: no HIP
-// call, nothing launched, the scene untouched; a plan the options make impossible is refused as rt_render refuses it.
-rt_status rt_debug_tier_room(rt_scene* s, int32_t* out4) {
-    if (!s) return invalid("rt_debug_tier_room: null scene");
-    if (!out4) return invalid("rt_debug_tier_room: null argument");
-    rt_frame_desc f;
-    memset(&f, 0, sizeof(f));
-    f.nx = f.ny = 64; f.ns = 1; f.gamma = 1.0f; f.tile_rows = 64; f.tile_stride = 1;
-    const frame_geometry g = {64, 8, 8, 64u * 64u, 64u * 64u};
-    const cost_map_view view = {false, false, cost_map_key(), 0ull, 0ull, 0ull, 0ull};
-    frame_plan plan;
-    const char* why = nullptr;
-    if (plan_frame(plan_facts_of(s), g_opt, f, g, {false, 0, 0}, view, plan, why) != RT_OK) return invalid(why);
-    out4[0] = plan.room.fits ? 1 : 0; out4[1] = plan.room.lds_scene; out4[2] = (int32_t)plan.room.lds; out4[3] = (int32_t)plan.room.tail_grid;
-    return RT_OK;
-}
-
-// the per-pixel buffers of rt_render_adaptive, cached in the scene and grown when a frame needs more, in two groups: the parked
-// pixels and the 4-byte-per-pixel map, which rt_render_variance shares, and (`lists`) what only the adaptive decisions need
-static rt_status ensure_adaptive_buffers(rt_scene* s, size_t n_pixels, bool lists) {
-    if (s->adapt_capacity < n_pixels) {
-        s->adapt_capacity = 0;
-        RT_TRY(reallocate({{(void**)&s->d_adapt_state, n_pixels * sizeof(rt_pixel_state)}, {(void**)&s->d_adapt_spp, n_pixels * sizeof(int32_t)}}));
-        s->adapt_capacity = n_pixels;
-    }
-    if (lists && s->adapt_lists_capacity < n_pixels) {
-        s->adapt_lists_capacity = 0;
-        RT_TRY(reallocate({{(void**)&s->d_adapt_half, n_pixels * 3 * sizeof(float)}, {(void**)&s->d_adapt_list[0], n_pixels * sizeof(uint32_t)},
-                           {(void**)&s->d_adapt_list[1], n_pixels * sizeof(uint32_t)}, {(void**)&s->d_adapt_queue, n_pixels * sizeof(unsigned long long)}}));
-        s->adapt_lists_capacity = n_pixels;
-    }
     return RT_OK;
 }
 
@@ -2488,9 +1761,14 @@ rt_status rt_render_adaptive(rt_scene* s, const rt_frame_desc* f, const rt_adapt
 
     // ---- buffers: cached in the scene, grown when a frame needs more
     const size_t floats = n_pixels * 3;
-    RT_TRY(ensure_adaptive_buffers(s, n_pixels, true));
-    if (!s->d_adapt_count) HIPCHK(hipMalloc((void**)&s->d_adapt_count, 64));
-    if (!s->d_adapt_rank) HIPCHK(hipMalloc((void**)&s->d_adapt_rank, sizeof(rt_rank_info)));
+    HIPCHK(s->d_adapt_state.grow(n_pixels));      // (rt_render_variance shares the parked pixels and the 4-byte-per-pixel map)
+    HIPCHK(s->d_adapt_spp.grow(n_pixels));
+    HIPCHK(s->d_adapt_half.grow(n_pixels * 3));
+    HIPCHK(s->d_adapt_list[0].grow(n_pixels));
+    HIPCHK(s->d_adapt_list[1].grow(n_pixels));
+    HIPCHK(s->d_adapt_queue.grow(n_pixels));
+    HIPCHK(s->d_adapt_count.grow(16));
+    HIPCHK(s->d_adapt_rank.grow(1));
     while (s->adapt_events.size() < 2u * 18u) {
         hipEvent_t e = nullptr;
         HIPCHK(hipEventCreate(&e));
@@ -2635,11 +1913,12 @@ rt_status rt_render_variance(rt_scene* s, const rt_frame_desc* f, const rt_varia
     // ---- buffers: the adaptive frame's parked pixels and 4-byte-per-pixel map, the accumulators (T_{b-1}, A, Q: three doubles
     // per pixel), a host fb's device image
     const size_t floats = n_pixels * 3;
-    RT_TRY(ensure_adaptive_buffers(s, n_pixels, false));
-    RT_TRY(grow(s->d_var_acc, s->var_capacity, n_pixels * 3));
+    HIPCHK(s->d_adapt_state.grow(n_pixels));
+    HIPCHK(s->d_adapt_spp.grow(n_pixels));
+    HIPCHK(s->d_var_acc.grow(n_pixels * 3));
     float* d_fb = nullptr;
     RT_TRY(device_fb(s, fb, fb_on_device, floats, &d_fb));
-    float* d_var = fb_on_device ? variance_out : reinterpret_cast<float*>(s->d_adapt_spp);
+    float* d_var = fb_on_device ? variance_out : reinterpret_cast<float*>(s->d_adapt_spp.get());
 
     // ---- the main kernel's frame parameters (rt_render_adaptive's: a pass only parks)
     rt_frame_params fp;
@@ -2673,18 +1952,6 @@ rt_status rt_render_variance(rt_scene* s, const rt_frame_desc* f, const rt_varia
         HIPCHK(hipMemcpyAsync(variance_out, d_var, n_pixels * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
     return finish_sync_frame(s, stream, B, out, stats);
-}
-
-// The passes of the last adaptive frame (diagnostics, tools/adaptive_sweep.py): per pass 5 values -- route (0 main kernel,
-// 1 tier kernel), active pixels, sample_begin, sample_end, device ms (x1000) of the render launch.  Returns the number of passes.
-int32_t rt_debug_adaptive_passes(const rt_scene* s, long long* out, int32_t cap) {
-    if (!s) return -1;
-    const int32_t np = (int32_t)s->adapt_ms.size();
-    for (int32_t k = 0; k < np && k < cap; ++k) {
-        for (int c = 0; c < 4; ++c) out[5 * k + c] = s->adapt_log[4 * k + c];
-        out[5 * k + 4] = (long long)llround((double)s->adapt_ms[k] * 1000.0);
-    }
-    return np;
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // rt_call_buffers.h -- the buffer table of an image-space entry point (rt_abi.hip: rt_render_aov*, rt_denoise*, rt_upscale,
 // rt_reproject*): the record of one caller buffer, whether two of them share a byte, and how the device images of host buffers
-// are cut out of the call's one allocation.  Plain host code without a HIP call, so that it also builds into a stand-alone
+// are cut out of the call's one allocation (call_memory, rt_host.h).  Plain host code without a HIP call, so that it also builds into a stand-alone
 // program (tests/test_call_buffers_host.py runs it under the address and undefined-behaviour sanitizers).
 #pragma once
 #include <cstddef>

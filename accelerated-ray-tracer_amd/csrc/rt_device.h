@@ -1,5 +1,5 @@
 // rt_device.h -- kernel argument blocks shared by the kernel translation units (rt_kernel_pixel.hip, rt_staged_*.hip,
-// rt_tier_*.hip, rt_rank.hip) and rt_abi.hip (the C-ABI implementation).  Internal to librt_mi355x.so.
+// rt_tier_*.hip, rt_rank.hip) and the host units (rt_abi.hip, rt_abi_debug.hip: the C-ABI implementation).  Internal to librt_mi355x.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -76,7 +76,7 @@ struct rt_options {
                                  // (DESIGN.md 4.8), 0 = always the main kernel, 1 = the tier kernel wherever the scene's tier data fit
 };
 
-// The facts a plan reads about the device and the scene (rt_abi.hip fills them in one place, plan_facts_of).
+// The facts a plan reads about the device and the scene (rt_host.h fills them in one place, plan_facts_of).
 struct plan_facts {
     int num_cu;
     size_t lds_per_cu;

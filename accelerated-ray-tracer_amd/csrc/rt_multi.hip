@@ -7,25 +7,18 @@
 // RCCL is loaded with dlopen, and only when a gather is needed (n_gpus > 1, or the "multi_force_rccl" option on a
 // one-GPU box): a process that also runs PyTorch (bench.py) already carries torch's own copy of the library, and
 // resolving ncclGather through the global symbol table would mix the two.
-#include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
 #include <chrono>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/rt_abi.h"
-#include "rt_device.h"
+#include "rt_host.h"
 
-// internals of rt_abi.hip this file builds on
-rt_status rt_internal_init_device(int device_ordinal);
-rt_status rt_internal_scene_create_on(int device, const rt_scene_desc* d, rt_scene** out);
-void rt_internal_set_error(rt_status st, int hip_error, const std::string& detail);
-int rt_internal_option(const char* key);
+using namespace rt_host;
 
 namespace {
+
+// a failed call's status, with the error state this file's entries leave: the HIP or RCCL code (0: none) and the text
+rt_status fail(rt_status st, int code, const std::string& detail) { g_last_hip_error = code; g_detail = detail; return st; }
 
 // the handful of RCCL entry points used, with the types of <rccl/rccl.h> (ncclComm_t is an opaque pointer,
 // ncclFloat = 7, ncclSuccess = 0; rccl.h:36,466,52)
@@ -109,21 +102,10 @@ struct rt_multi {
     bool comms_ready = false;
 };
 
-#define MHIP(expr)                                                                                         \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) {                                                                            \
-            char b_[512];                                                                                  \
-            snprintf(b_, sizeof(b_), "HIP error = %u at %s:%d '%s' (%s)", (unsigned)e_, __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-            rt_internal_set_error(RT_ERR_HIP, (int)e_, b_);                                                \
-            return RT_ERR_HIP;                                                                             \
-        }                                                                                                  \
-    } while (0)
-
 extern "C" {
 
 rt_status rt_init_devices(int n_gpus) {
-    if (n_gpus < 1) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_init_devices: n_gpus must be >= 1"); return RT_ERR_INVALID; }
+    if (n_gpus < 1) return fail(RT_ERR_INVALID, 0, "rt_init_devices: n_gpus must be >= 1");
     for (int d = n_gpus - 1; d >= 0; --d) {   // device 0 last: it stays the device new single-GPU scenes are created on
         const rt_status st = rt_internal_init_device(d);
         if (st != RT_OK) return st;
@@ -150,9 +132,9 @@ rt_status rt_multi_destroy(rt_multi* m) {
 }
 
 rt_status rt_multi_create(const rt_scene_desc* desc, int n_gpus, rt_multi** out) {
-    if (!out) { rt_internal_set_error(RT_ERR_INVALID, 0, "null output pointer"); return RT_ERR_INVALID; }
+    if (!out) return fail(RT_ERR_INVALID, 0, "null output pointer");
     *out = nullptr;
-    if (n_gpus < 1 || n_gpus > 16) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_create: n_gpus must be 1..16"); return RT_ERR_INVALID; }
+    if (n_gpus < 1 || n_gpus > 16) return fail(RT_ERR_INVALID, 0, "rt_multi_create: n_gpus must be 1..16");
     rt_multi* m = new rt_multi;
     m->n = n_gpus;
     m->scenes.assign((size_t)n_gpus, nullptr);
@@ -162,7 +144,7 @@ rt_status rt_multi_create(const rt_scene_desc* desc, int n_gpus, rt_multi** out)
         const rt_status st = rt_internal_scene_create_on(d, desc, &m->scenes[d]);   // also makes device d current
         if (st != RT_OK) { rt_multi_destroy(m); return st; }
         hipError_t e = hipStreamCreateWithFlags(&m->streams[d], hipStreamNonBlocking);
-        if (e != hipSuccess) { rt_internal_set_error(RT_ERR_HIP, (int)e, "rt_multi_create: hipStreamCreate failed"); rt_multi_destroy(m); return RT_ERR_HIP; }
+        if (e != hipSuccess) { rt_multi_destroy(m); return fail(RT_ERR_HIP, (int)e, "rt_multi_create: hipStreamCreate failed"); }
     }
     *out = m;
     return RT_OK;
@@ -174,7 +156,7 @@ int32_t rt_multi_device_count(const rt_multi* m) { return m ? m->n : 0; }
 // calls, before any HIP call, and a refusal there leaves every replica untouched.
 extern "C++" template <class Call>
 static rt_status on_every_replica(rt_multi* m, const char* null_handle, Call&& call) {
-    if (!m) { rt_internal_set_error(RT_ERR_INVALID, 0, null_handle); return RT_ERR_INVALID; }
+    if (!m) return fail(RT_ERR_INVALID, 0, null_handle);
     for (int d = m->n - 1; d >= 0; --d) {
         const rt_status st = call(m->scenes[d]);
         if (st != RT_OK) return st;
@@ -198,7 +180,7 @@ rt_status rt_multi_update_quads(rt_multi* m, const rt_quad_update* update, int r
 }
 
 rt_status rt_multi_row_owner(int32_t global_row, int32_t tile_rows, int32_t n_gpus, int32_t* device, int32_t* local_row) {
-    if (global_row < 0 || tile_rows <= 0 || n_gpus <= 0 || !device || !local_row) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_row_owner: bad argument"); return RT_ERR_INVALID; }
+    if (global_row < 0 || tile_rows <= 0 || n_gpus <= 0 || !device || !local_row) return fail(RT_ERR_INVALID, 0, "rt_multi_row_owner: bad argument");
     int r, l;
     row_owner(global_row, tile_rows, n_gpus, r, l);
     *device = r; *local_row = l;
@@ -221,22 +203,22 @@ static rt_status multi_setup(rt_multi* m, size_t local_floats, size_t frame_floa
     const int n = m->n;
     if (m->local_floats < local_floats) {
         for (int d = 0; d < n; ++d) {
-            MHIP(hipSetDevice(d));
+            HIPCHK(hipSetDevice(d));
             if (m->d_local[d]) (void)hipFree(m->d_local[d]);
             m->d_local[d] = nullptr;
         }
         m->local_floats = 0;
         for (int d = 0; d < n; ++d) {
-            MHIP(hipSetDevice(d));
-            MHIP(hipMalloc((void**)&m->d_local[d], (local_floats ? local_floats : 1) * sizeof(float)));
+            HIPCHK(hipSetDevice(d));
+            HIPCHK(hipMalloc((void**)&m->d_local[d], (local_floats ? local_floats : 1) * sizeof(float)));
         }
         m->local_floats = local_floats;
     }
-    MHIP(hipSetDevice(0));
+    HIPCHK(hipSetDevice(0));
     if (m->frame_floats < frame_floats) {
         if (m->d_frame) (void)hipFree(m->d_frame);
         m->d_frame = nullptr; m->frame_floats = 0;
-        MHIP(hipMalloc((void**)&m->d_frame, frame_floats * sizeof(float)));
+        HIPCHK(hipMalloc((void**)&m->d_frame, frame_floats * sizeof(float)));
         m->frame_floats = frame_floats;
     }
     // the gather writes n * local_floats floats of THIS frame: its capacity is tracked on its own (a frame rendered
@@ -245,27 +227,27 @@ static rt_status multi_setup(rt_multi* m, size_t local_floats, size_t frame_floa
     if (m->staging_floats < staging_need) {
         if (m->d_staging) (void)hipFree(m->d_staging);
         m->d_staging = nullptr; m->staging_floats = 0;
-        MHIP(hipMalloc((void**)&m->d_staging, staging_need * sizeof(float)));
+        HIPCHK(hipMalloc((void**)&m->d_staging, staging_need * sizeof(float)));
         m->staging_floats = staging_need;
     }
     if (gather && !m->comms_ready) {
         std::string why;
-        if (!load_rccl(m->rccl, why)) { rt_internal_set_error(RT_ERR_HIP, 0, why); return RT_ERR_HIP; }
+        if (!load_rccl(m->rccl, why)) return fail(RT_ERR_HIP, 0, why);
         m->comms.assign((size_t)n, nullptr);
         std::vector<int> devs((size_t)n);
         for (int d = 0; d < n; ++d) devs[d] = d;
         const int rc = m->rccl.CommInitAll(m->comms.data(), n, devs.data());    // rccl.h:236
-        if (rc != 0) { rt_internal_set_error(RT_ERR_HIP, rc, std::string("ncclCommInitAll: ") + (m->rccl.GetErrorString ? m->rccl.GetErrorString(rc) : "failed")); return RT_ERR_HIP; }
+        if (rc != 0) return fail(RT_ERR_HIP, rc, std::string("ncclCommInitAll: ") + (m->rccl.GetErrorString ? m->rccl.GetErrorString(rc) : "failed"));
         m->comms_ready = true;
     }
     return RT_OK;
 }
 
 rt_status rt_multi_render(rt_multi* m, const rt_frame_desc* whole, float* fb, int fb_on_device, int tile_rows, rt_stats* stats) {
-    if (!m || !whole || !fb) { rt_internal_set_error(RT_ERR_INVALID, 0, "null argument"); return RT_ERR_INVALID; }
-    if (whole->nx <= 0 || whole->ny <= 0 || whole->ns <= 0) { rt_internal_set_error(RT_ERR_INVALID, 0, "nx, ny and ns must be positive"); return RT_ERR_INVALID; }
+    if (!m || !whole || !fb) return fail(RT_ERR_INVALID, 0, "null argument");
+    if (whole->nx <= 0 || whole->ny <= 0 || whole->ns <= 0) return fail(RT_ERR_INVALID, 0, "nx, ny and ns must be positive");
     const int n = m->n, nx = whole->nx, ny = whole->ny;
-    const bool force_rccl = rt_internal_option("multi_force_rccl") != 0;
+    const bool force_rccl = g_opt.multi_force_rccl != 0;
     const bool gather = n > 1 || force_rccl;
     if (tile_rows <= 0) tile_rows = 4;
     if (!gather) tile_rows = ny;
@@ -276,7 +258,7 @@ rt_status rt_multi_render(rt_multi* m, const rt_frame_desc* whole, float* fb, in
     for (int d = 0; d < n; ++d) {
         f[d].tile_rows = tile_rows; f[d].tile_first = d; f[d].tile_stride = n;
         const int rows = rt_frame_local_rows(&f[d]);
-        if (rows < 0) { rt_internal_set_error(RT_ERR_INVALID, 0, "bad row partition"); return RT_ERR_INVALID; }
+        if (rows < 0) return fail(RT_ERR_INVALID, 0, "bad row partition");
         if (rows > max_rows) max_rows = rows;
     }
     const size_t local_floats = (size_t)max_rows * nx * 3, frame_floats = (size_t)ny * nx * 3;
@@ -287,16 +269,8 @@ rt_status rt_multi_render(rt_multi* m, const rt_frame_desc* whole, float* fb, in
     const auto t0 = std::chrono::steady_clock::now();
     // from here on frames are in flight: an error drains every device before it is returned
     rt_status failed = RT_OK;
-#define MTRY(expr)                                                                                         \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess && failed == RT_OK) {                                                         \
-            char b_[512];                                                                                  \
-            snprintf(b_, sizeof(b_), "HIP error = %u at %s:%d '%s' (%s)", (unsigned)e_, __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-            rt_internal_set_error(RT_ERR_HIP, (int)e_, b_);                                                \
-            failed = RT_ERR_HIP;                                                                           \
-        }                                                                                                  \
-    } while (0)
+    // (HIPCHK's record of the first error, without its return)
+#define MTRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess && failed == RT_OK) failed = hip_failed(e_, __FILE__, __LINE__, #expr); } while (0)
 
     // ---- every device renders its rows (enqueue only: the devices run concurrently)
     for (int d = 0; d < n && failed == RT_OK; ++d) {
@@ -313,8 +287,7 @@ rt_status rt_multi_render(rt_multi* m, const rt_frame_desc* whole, float* fb, in
         const int rc2 = m->rccl.GroupEnd();   // always closes the group that GroupStart opened
         if (rc == 0) rc = rc2;
         if (rc != 0 && failed == RT_OK) {
-            rt_internal_set_error(RT_ERR_HIP, rc, std::string("ncclGather: ") + (m->rccl.GetErrorString ? m->rccl.GetErrorString(rc) : "failed"));
-            failed = RT_ERR_HIP;
+            failed = fail(RT_ERR_HIP, rc, std::string("ncclGather: ") + (m->rccl.GetErrorString ? m->rccl.GetErrorString(rc) : "failed"));
         }
         if (failed == RT_OK) {
             MTRY(hipSetDevice(0));
@@ -361,18 +334,18 @@ rt_status rt_multi_render(rt_multi* m, const rt_frame_desc* whole, float* fb, in
 rt_status rt_multi_probe_rccl(const char* library_name) {
     rccl_api r;
     std::string why;
-    if (!load_rccl(r, why, library_name)) { rt_internal_set_error(RT_ERR_HIP, 0, why); return RT_ERR_HIP; }
+    if (!load_rccl(r, why, library_name)) return fail(RT_ERR_HIP, 0, why);
     dlclose(r.handle);
     return RT_OK;
 }
 // The reassembly step of rt_multi_render on caller-supplied DEVICE buffers: staging[world][max_rows][nx*3] -> frame[ny][nx*3]
 // on the current device's default stream (synchronous).  Lets a one-GPU box check the index arithmetic for any world size.
 rt_status rt_multi_debug_uninterleave(const float* staging, float* frame, int32_t nx, int32_t ny, int32_t tile_rows, int32_t world, int32_t max_rows) {
-    if (!staging || !frame || nx <= 0 || ny <= 0 || tile_rows <= 0 || world <= 0 || max_rows <= 0) { rt_internal_set_error(RT_ERR_INVALID, 0, "rt_multi_debug_uninterleave: bad argument"); return RT_ERR_INVALID; }
+    if (!staging || !frame || nx <= 0 || ny <= 0 || tile_rows <= 0 || world <= 0 || max_rows <= 0) return fail(RT_ERR_INVALID, 0, "rt_multi_debug_uninterleave: bad argument");
     const long long total = (long long)ny * nx * 3;
     hipLaunchKernelGGL(rt_uninterleave_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, staging, frame, nx * 3, ny, tile_rows, world, max_rows);
-    MHIP(hipGetLastError());
-    MHIP(hipDeviceSynchronize());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
     return RT_OK;
 }
 

@@ -27,7 +27,7 @@ static plan_facts scene(bool lean, size_t sphere_bytes = 16000) {
     c.calibrated = true;
     return c;
 }
-// the geometry of `rows` local rows of an nx-wide frame (what check_frame in rt_abi.hip computes)
+// the geometry of `rows` local rows of an nx-wide frame (what check_frame in rt_host.h computes)
 static frame_geometry geometry(int nx, int rows) {
     frame_geometry g;
     g.local_rows = rows; g.tiles_x = (nx + 7) / 8; g.tiles_y = (rows + 7) / 8;

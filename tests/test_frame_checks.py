@@ -1,6 +1,6 @@
 """The frame checks of every entry point that takes a frame description, pinned word for word.
 
-The entries share one check (check_frame, csrc/rt_abi.hip) but keep their own texts, which the Python layer and other tests
+The entries share one check (check_frame, csrc/rt_host.h) but keep their own texts, which the Python layer and other tests
 match on.  EXPECT_HOST and EXPECT_DEVICE hold the (status, detail) each entry returned for each bad frame BEFORE the checks
 were shared, recorded from that build, with three additions.  All three concern the frame that has fewer than 2^31 pixels but
 2^31 work items in its 8x8 tiles (1 x 2^28):
