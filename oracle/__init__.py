@@ -30,6 +30,31 @@ def build() -> None:
         raise RuntimeError("oracle build failed:\n" + r.stdout + r.stderr)
 
 
+def load(path: str):
+    """A ctypes handle of its own on an oracle library, with the argument types declared.  lib() loads the committed text's
+    library through this; tests/oracle_mutants.py loads planted errors built elsewhere, each beside the others."""
+    L = C.CDLL(path)
+    if not hasattr(L, "orc_math_sweep"):
+        raise RuntimeError(f"{path} is out of date and could not be rebuilt (make -C oracle)")
+    L.orc_scene_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.orc_scene_from_desc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
+    L.orc_scene_defaults.restype = C.c_float
+    L.orc_scene_defaults.argtypes = [C.c_int, C.c_void_p]
+    L.orc_render.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int,
+                             C.c_ulonglong, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.orc_xorwow.argtypes = [C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orc_dump_nodes.argtypes = [C.c_int, C.c_void_p, C.c_int]
+    L.orc_scene_census.argtypes = [C.c_int, C.c_void_p]
+    L.orc_camera.argtypes = [C.c_int, C.c_void_p]
+    L.orc_perlin_noise.restype = C.c_float
+    L.orc_perlin_noise.argtypes = [C.c_float] * 3
+    L.orc_perlin_turb.restype = C.c_float
+    L.orc_perlin_turb.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int]
+    L.orc_math_sweep.argtypes = [C.c_int, C.c_uint, C.c_longlong, C.c_float, C.c_void_p, C.c_int]
+    L.orc_math_list.argtypes = [C.c_int, C.c_longlong] + [C.c_void_p] * 4 + [C.c_int]
+    return L
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -38,26 +63,7 @@ def lib():
         except (RuntimeError, OSError):
             if not os.path.exists(LIB_PATH):
                 raise        # (a read-only tree with a library already built is still usable)
-        L = C.CDLL(LIB_PATH)
-        if not hasattr(L, "orc_math_sweep"):
-            raise RuntimeError(f"{LIB_PATH} is out of date and could not be rebuilt (make -C oracle)")
-        L.orc_scene_create.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
-        L.orc_scene_from_desc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float]
-        L.orc_scene_defaults.restype = C.c_float
-        L.orc_scene_defaults.argtypes = [C.c_int, C.c_void_p]
-        L.orc_render.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int,
-                                 C.c_ulonglong, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        L.orc_xorwow.argtypes = [C.c_ulonglong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.orc_dump_nodes.argtypes = [C.c_int, C.c_void_p, C.c_int]
-        L.orc_scene_census.argtypes = [C.c_int, C.c_void_p]
-        L.orc_camera.argtypes = [C.c_int, C.c_void_p]
-        L.orc_perlin_noise.restype = C.c_float
-        L.orc_perlin_noise.argtypes = [C.c_float] * 3
-        L.orc_perlin_turb.restype = C.c_float
-        L.orc_perlin_turb.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int]
-        L.orc_math_sweep.argtypes = [C.c_int, C.c_uint, C.c_longlong, C.c_float, C.c_void_p, C.c_int]
-        L.orc_math_list.argtypes = [C.c_int, C.c_longlong] + [C.c_void_p] * 4 + [C.c_int]
-        _lib = L
+        _lib = load(LIB_PATH)
     return _lib
 
 
